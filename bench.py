@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the hot path on MI355X.  Default: ESM-2 650M bulk embedding extraction, synthetic L=1022 batches.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload NAME] [--dump-outputs DIR]
 
 ``--gpus N`` from a plain shell re-executes this script as N ranks (one per GPU) under torch.distributed.run
 (esm_amd/launch.py); started by a launcher already (RANK / WORLD_SIZE set) it joins it.  Ranks create the process
@@ -93,19 +93,22 @@ def logits_l2_report(logits, ref_logits):
 
 
 PER_RANK_MS = []  # each rank's own ms per step of the last timed region (before it waits for the others)
+LAST_OUTPUT = []  # what the last step of the last timed region returned (for --dump-outputs)
 
 
 def timed_steps(step, steps, warmup, sync_all, dist, dev):
     """The contract's timed region: `warmup` untimed steps, then exactly `steps` steps bracketed by
     synchronise + barrier on both sides; returns the MAX elapsed seconds over ranks.  Every rank's own time (its K
     steps done, before the closing barrier) is gathered into PER_RANK_MS: a straggler shows up there, not only in
-    the maximum."""
+    the maximum.  The last step's return value is kept in LAST_OUTPUT."""
     for _ in range(warmup):
         step()
     sync_all()
+    LAST_OUTPUT[:] = [None]
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        LAST_OUTPUT[0] = None  # released before the next step allocates, as a discarded result would be
+        LAST_OUTPUT[0] = step()
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)  # sync_all() starts with the same call: no extra wait inside the timed region
     own = time.perf_counter() - t0
@@ -128,6 +131,59 @@ def finish(dist):
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs writes at most this much array data
+DUMP_SEED = 0
+
+
+def output_arrays(out, prefix=""):
+    """The tensors of a forward's result (a tensor, or a dict of tensors / dicts) as {name: tensor}: dict keys joined by
+    '_', e.g. {"logits": .., "representations": {33: ..}} -> logits, representations_33."""
+    if torch.is_tensor(out):
+        return {prefix or "output": out}
+    arrays = {}
+    if isinstance(out, dict):
+        for k, v in out.items():
+            arrays.update(output_arrays(v, f"{prefix}_{k}" if prefix else str(k)))
+    return arrays
+
+
+def dump_outputs(out, directory):
+    """Write the arrays of `out` as <directory>/<name>.npy (float32, float64 kept), at most DUMP_BUDGET_BYTES in all.  An
+    array is viewed as rows over its last dimension; arrays that do not fit their share of the budget (smallest first,
+    each taking at most an equal share of what is left) keep a sample of rows: a sorted random subset drawn with the
+    fixed seed DUMP_SEED, written as [rows, last dim].  Returns {name: {shape, rows, rows_total}} for the result line."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    arrays = {n: t.detach() for n, t in output_arrays(out).items()}
+    left, report = DUMP_BUDGET_BYTES - 1024 * len(arrays), {}  # room for the .npy headers
+    for i, (name, t) in enumerate(sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))):
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        t = t.to(dt)
+        rows = t.reshape(-1, t.shape[-1]) if t.dim() > 1 else t.reshape(-1, 1)
+        row_bytes = rows.shape[1] * rows.element_size()
+        share = left // (len(arrays) - i)
+        if rows.numel() * rows.element_size() <= share:
+            keep = t
+        else:
+            n = share // row_bytes
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randperm(rows.shape[0], generator=g)[:n].sort().values
+            keep = rows[idx.to(rows.device)]
+        a = keep.cpu().numpy()
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+        left -= a.nbytes
+        report[name] = {"shape": list(a.shape), "rows": int(a.size // max(rows.shape[1], 1)), "rows_total": int(rows.shape[0])}
+    return report
+
+
+def dump_last_step(args, rank):
+    """--dump-outputs: rank 0 writes what the last timed step returned (its own shard of the batch)."""
+    if not args.dump_outputs or rank != 0:
+        return None
+    return {"dir": args.dump_outputs, "arrays": dump_outputs(LAST_OUTPUT[0], args.dump_outputs)}
 
 
 def protocol_test(args):
@@ -303,6 +359,7 @@ def run_esm2_650m(args, dist, rank, world, dev):
     step = lambda: model(toks, repr_layers=[L])
     with torch.no_grad():
         elapsed = timed_steps(step, args.steps, args.warmup, sync_all, dist, dev)
+        dumped = dump_last_step(args, rank)
         prof, prof_steps = profile_steps(model, step)  # separate steps: the timed region is unperturbed
 
         # figure (ii): every step's representations[33] also goes to pinned host memory on a side stream while the
@@ -362,6 +419,8 @@ def run_esm2_650m(args, dist, rank, world, dev):
                                     f"{batch * (args.seq_len + 2) * E * 4 / 1e6:.0f} MB per step) into pinned memory on a "
                                     "side stream, overlapped with the next forward"}
     result["library"] = build
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     if world == 1 and args.also_qk_gain > 0:
         # data sensitivity, second point: the same run once more on weights with this q / k gain (timing only — random
         # weights with maps this sharp make a chaotic network: the operand floor itself is O(1) there, parity is undefined)
@@ -591,6 +650,7 @@ def run_esm2_3b_contacts(args, dist, rank, world, dev):
     step = lambda: model.predict_contacts(toks)
     with torch.no_grad():
         elapsed = timed_steps(step, args.steps, args.warmup, sync_all, dist, dev)
+        dumped = dump_last_step(args, rank)
         prof, prof_steps = profile_steps(model, step)
     value = world * batch * args.seq_len * args.steps / elapsed
     if rank != 0:
@@ -604,6 +664,8 @@ def run_esm2_3b_contacts(args, dist, rank, world, dev):
     result["roofline_hbm"] = hbm_roofline(prof)
     result["kernel_classes"] = class_table(prof, prof_steps)
     result["library"] = library_build()
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     result["roofline"]["traffic"], result["roofline"]["traffic_source"] = pmc_traffic(
         PMC_CLASS.get(dom["name"], dom["name"]), result["library"]["src_hash"], "esm2_3b_contacts", batch, model.ln_fold_active())
     if world == 1 and not args.no_cpu_baseline:
@@ -678,6 +740,7 @@ def run_msa1b(args, dist, rank, world, dev):
     step = lambda: model(toks, repr_layers=[L])
     with torch.no_grad():
         elapsed = timed_steps(step, args.steps, args.warmup, sync_all, dist, dev)
+        dumped = dump_last_step(args, rank)
         prof, prof_steps = profile_steps(model, step)
     residues = batch * R * (C - 1)
     value = world * residues * args.steps / elapsed
@@ -693,6 +756,8 @@ def run_msa1b(args, dist, rank, world, dev):
     result["roofline_hbm"] = hbm_roofline(prof)
     result["kernel_classes"] = class_table(prof, prof_steps)
     result["library"] = library_build()
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     result["roofline"]["traffic"], result["roofline"]["traffic_source"] = pmc_traffic(
         PMC_CLASS.get(dom["name"], dom["name"]), result["library"]["src_hash"], "msa1b", batch, None)
     if world == 1 and not args.no_cpu_baseline:
@@ -894,7 +959,15 @@ def main():
     ap.add_argument("--protocol-test", action="store_true",
                     help="CPU/gloo dry run of the launch + timing protocol with a stub step (tests/test_bench_protocol.py); "
                          "never a measurement")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="esm2_650m / esm2_3b_contacts / msa1b: after the timed steps, write what the last timed step returned "
+                         "(rank 0's shard) as DIR/<name>.npy in float32, at most 64 MB in all (larger outputs: a fixed, seeded "
+                         "sample of rows); the inputs are the same from run to run, so two builds can be compared array by array")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload == "extract_650m":
+        ap.error("--dump-outputs: extract_650m returns no arrays (its timed path writes result files)")
 
     from esm_amd.launch import init_ranks, relaunch, under_launcher
 

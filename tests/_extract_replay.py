@@ -1,8 +1,8 @@
 """Test helper (never part of the product): the call sequence of the reference's bulk-extraction script, step by step,
-against whatever ``esm`` package is importable — on the GPU box /root/reference does not exist, so the unmodified script
-cannot be the thing that runs there; this replay issues the same calls in the same order with the same arguments
-(reference scripts/extract.py:63-131; each step cites its line).  tests/test_extract_script_gpu.py runs the real script
-instead whenever it is present.
+against whatever ``esm`` package is importable — the unmodified script is not part of this repository, so this replay
+issues the same calls in the same order with the same arguments (reference scripts/extract.py:63-131; each step cites
+its line).  tests/test_extract_script_gpu.py runs it on the engine; tests/test_reference_differential.py runs it with
+--nogpu under tests/_run_reference_script.py and compares with the recorded result files of the real script.
 
     python tests/_extract_replay.py <checkpoint> <fasta> <out_dir> --repr_layers .. --include .. [--toks_per_batch N]
                                     [--truncation_seq_length N]
@@ -20,8 +20,10 @@ def replay(a):
     model, alphabet = pretrained.load_model_and_alphabet(a.model_location)  # extract.py:64
     model.eval()  # :65
     assert not isinstance(model, MSATransformer)  # :66-69
-    assert torch.cuda.is_available()
-    model = model.cuda()  # :70-72
+    on_gpu = torch.cuda.is_available() and not a.nogpu
+    assert on_gpu or a.nogpu  # without --nogpu the replay is a run on the engine
+    if on_gpu:
+        model = model.cuda()  # :70-72
     dataset = FastaBatchedDataset.from_file(a.fasta_file)  # :74
     batches = dataset.get_batch_indices(a.toks_per_batch, extra_toks_per_seq=1)  # :75
     loader = torch.utils.data.DataLoader(  # :76-78
@@ -33,7 +35,8 @@ def replay(a):
     layers = [(i + nl + 1) % (nl + 1) for i in a.repr_layers]  # :85
     with torch.no_grad():  # :87
         for labels, strs, toks in loader:  # :88
-            toks = toks.to(device="cuda", non_blocking=True)  # :92-93
+            if on_gpu:
+                toks = toks.to(device="cuda", non_blocking=True)  # :92-93
             out = model(toks, repr_layers=layers, return_contacts=want_contacts)  # :95
             out["logits"].to(device="cpu")  # :97
             reps = {l: t.to(device="cpu") for l, t in out["representations"].items()}  # :98-100

@@ -1,21 +1,133 @@
-"""Runs INSIDE the reference implementation (sys.path -> /root/reference; never imported by the test process, whose
-``esm`` is this repo's shim) and pickles what the reference computes for seeded random inputs.  Used by
-tests/test_reference_differential.py; the synthetic weights come from esm_amd.synth (loaded by file path so that
-``import esm`` keeps meaning the reference here).
+"""Runs INSIDE the reference implementation (sys.path -> the reference checkout; its ``esm`` is the reference, not this
+repo's shim) and records what the reference computes for seeded random inputs into the fixture
+tests/golden/reference_probe.pt that tests/test_reference_differential.py compares against.  The synthetic weights come
+from esm_amd.synth (loaded by file path so that ``import esm`` keeps meaning the reference here).  The fixture holds
+data only: inputs (including the text of the reference's example FASTA / a3m files the cases read), outputs, and the
+result files of the reference's scripts/extract.py.
 
-    python tests/_reference_probe.py out.pkl
+    python tests/_reference_probe.py tests/golden/reference_probe.pt <checkout of the reference implementation>
+
+The test process imports this module for the shared case definitions below (EXTRACT_CASES, write_checkpoints); the
+reference is imported inside main() only.
 """
 import argparse
+import hashlib
 import importlib.util
 import os
-import pickle
 import random
+import shutil
+import subprocess
 import sys
+import tempfile
 
 import torch
 
-REFERENCE = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_probe.pt")
+
+# the two runs of the reference's scripts/extract.py whose result files are recorded: (checkpoint name, layers, embed dim,
+# heads, weight seed) and the script's arguments after <checkpoint> <fasta> <output dir>
+EXTRACT_CASES = {
+    "few_proteins_8M": dict(ckpt=("esm2_t6_8M_UR50D", 6, 320, 20, 7),
+                            args=["--repr_layers", "0", "5", "6", "--include", "mean", "per_tok", "bos", "contacts",
+                                  "--nogpu", "--toks_per_batch", "2048"]),
+    "tiny_truncated": dict(ckpt=("esm2_t3_tiny_UR50D", 3, 128, 2, 17),
+                           args=["--nogpu", "--repr_layers", "-1", "1", "--include", "mean", "per_tok", "bos", "contacts",
+                                 "--truncation_seq_length", "40", "--toks_per_batch", "150"]),
+}
+# the batches of the reference's tests/test_alphabet.py helpers (truncation_seq_length, batch)
+ALPHABET_TEST_BATCHES = [
+    (None, [("protein1", "MKTVRQG"), ("protein2 with mask", "KALTA<mask>ISQP"), ("protein3", "K A <mask> I S Q")]),
+    (10, [("protein1", "MKTVRQGMKTVRQG"), ("protein2 with mask", "KALTA<mask>ISQPISQP"), ("protein3", "K A <mask> I S Q")]),
+]
+
+
+def tiny_truncated_fasta():
+    """FASTA text of the "tiny_truncated" extract case: five seeded sequences of 8..70 residues."""
+    g = torch.Generator().manual_seed(8)
+    aas = "LAGVSERTIDPKQNFYMHWC"
+    seqs = {f"sp|P{i:05d}|NAME_{i} desc": "".join(aas[j] for j in torch.randint(0, 20, (n,), generator=g).tolist())
+            for i, n in enumerate([12, 55, 31, 70, 8])}
+    return "".join(f">{k}\n{v}\n" for k, v in seqs.items())
+
+
+def write_checkpoints(ck_dir, synth):
+    """Checkpoint files in the released formats (ESM-2 cfg format; ESM-1b / MSA Transformer fairseq-args formats with
+    encoder_* argument names, encoder.sentence_encoder.* key prefixes, the row/column key swap of the MSA files, sibling
+    -contact-regression.pt), from seeded synthetic weights: the same bytes on every call.  Returns their paths."""
+    os.makedirs(ck_dir, exist_ok=True)
+
+    def split_regression(sd):
+        reg = {k: v for k, v in sd.items() if k.startswith("contact_head.")}
+        body = {k: v for k, v in sd.items() if not k.startswith("contact_head.")}
+        return body, reg
+
+    paths = []
+    # ESM-2 (cfg format, esm/pretrained.py:164-188)
+    paths.append(synth.write_esm2_checkpoint(ck_dir, "esm2_t3_synth_UR50D", 3, 128, 2, seed=201))
+    # ESM-1b (fairseq args format with encoder_* argument names and encoder.sentence_encoder.* keys, :87-99)
+    body, reg = split_regression(synth.synth_esm1b_state_dict(2, 128, 2, seed=202, ln_before=True))
+    args = argparse.Namespace(arch="roberta_large", encoder_layers=2, encoder_embed_dim=128, encoder_ffn_embed_dim=512,
+                              encoder_attention_heads=2, max_positions=1024, token_dropout=True)
+    path = os.path.join(ck_dir, "esm1b_t2_synth_UR50S.pt")
+    torch.save({"args": args, "model": {"encoder.sentence_encoder." + k: v for k, v in body.items()}}, path)
+    torch.save({"model": reg}, path[:-3] + "-contact-regression.pt")
+    paths.append(path)
+    # MSA Transformer (args format; released files have row / column swapped in the key names, :109-121)
+    body, reg = split_regression(synth.synth_msa_state_dict(2, 128, 2, 256, seed=203))
+    swap = lambda s: s.replace("row", "column") if "row" in s else s.replace("column", "row")
+    args = argparse.Namespace(arch="msa_transformer", encoder_layers=2, encoder_embed_dim=128, encoder_ffn_embed_dim=256,
+                              encoder_attention_heads=2, dropout=0.1, attention_dropout=0.1, activation_dropout=0.1,
+                              max_positions=1024, embed_positions_msa=True, max_tokens=2 ** 14, max_tokens_per_msa=2 ** 14)
+    path = os.path.join(ck_dir, "esm_msa1b_t2_synth_UR50S.pt")
+    torch.save({"args": args, "model": {"encoder.sentence_encoder." + swap(k): v for k, v in body.items()}}, path)
+    torch.save({"model": reg}, path[:-3] + "-contact-regression.pt")
+    paths.append(path)
+    return paths
+
+
+def tensor_digest(t):
+    """(dtype, shape, SHA-256 of the bytes): equal digests <=> bit-identical tensors."""
+    raw = t.detach().cpu().contiguous().reshape(-1).view(torch.uint8).numpy().tobytes()
+    return str(t.dtype), tuple(t.shape), hashlib.sha256(raw).hexdigest()
+
+
+PER_TOK_STRIDE = 32
+
+
+def per_tok_rows(n):
+    """The residue rows of an [n, E] per-token representation or [n, n] contact map the fixture keeps: every
+    PER_TOK_STRIDE-th and the last."""
+    return sorted(set(range(0, n, PER_TOK_STRIDE)) | ({n - 1} if n else set()))
+
+
+def slim_result_file(d):
+    """An extract.py result file as the fixture stores it: label, mean and <bos> representations whole; of the per-token
+    representations and the contact map the shape, the dtype and the rows per_tok_rows()."""
+    out = {k: v for k, v in d.items() if k not in ("representations", "contacts")}
+    out["keys"] = sorted(d)
+    if "contacts" in d:
+        c = d["contacts"]
+        out["contacts_shape"], out["contacts_dtype"] = tuple(c.shape), c.dtype
+        out["contacts_rows"] = c[per_tok_rows(c.shape[0])].clone()
+    if "representations" in d:
+        reps = d["representations"]
+        out["per_tok_shape"] = {l: tuple(t.shape) for l, t in reps.items()}
+        out["per_tok_dtype"] = {l: t.dtype for l, t in reps.items()}
+        out["per_tok_rows"] = {l: t[per_tok_rows(t.shape[0])].clone() for l, t in reps.items()}
+    return out
+
+
+def first_records(text, n):
+    """The text of the first n records of a FASTA / a3m file."""
+    lines, seen = [], 0
+    for line in text.splitlines(keepends=True):
+        if line.startswith(">"):
+            seen += 1
+            if seen > n:
+                break
+        lines.append(line)
+    return "".join(lines)
 
 
 def load_synth():
@@ -30,7 +142,8 @@ def rand_seq(rng, n, alphabet="LAGVSERTIDPKQNFYMHWCXBUZO"):
 
 
 def main():
-    out_path = sys.argv[1]
+    out_path = os.path.abspath(sys.argv[1])
+    REFERENCE = os.path.abspath(sys.argv[2])
     sys.path.insert(0, REFERENCE)
     import esm  # the reference
 
@@ -86,7 +199,7 @@ def main():
         n = rng.randint(1, 25)
         lines = []
         for i in range(n):
-            s = rand_seq(rng, rng.randint(1, 400), "LAGVSERTIDPKQNFYMHWC")
+            s = rand_seq(rng, rng.randint(1, 200), "LAGVSERTIDPKQNFYMHWC")
             lines.append(f">seq{i} some description {i}")
             for j in range(0, len(s), 60):  # wrapped lines
                 lines.append(s[j:j + 60])
@@ -103,9 +216,14 @@ def main():
                                                       ds.get_batch_indices(tpb, extra_toks_per_seq=extra))))
         os.unlink(name)
     res["read_fasta"] = []
-    a3m = os.path.join(REFERENCE, "examples", "data", "1a3a_1_A.a3m")
+    with open(os.path.join(REFERENCE, "examples", "data", "1a3a_1_A.a3m")) as f:
+        a3m_text = first_records(f.read(), 20)  # what the first 20 records read back from
+    with tempfile.NamedTemporaryFile("w", suffix=".a3m", delete=False) as f:
+        f.write(a3m_text)
+        a3m = f.name
     for kw in (dict(), dict(keep_gaps=False), dict(keep_insertions=False, to_upper=True)):
-        res["read_fasta"].append((a3m, kw, list(esm.data.read_fasta(a3m, **kw))[:20]))
+        res["read_fasta"].append((a3m_text, kw, list(esm.data.read_fasta(a3m, **kw))[:20]))
+    os.unlink(a3m)
 
     # ---- model forwards on synthetic weights at dims / seeds outside the committed fixtures ----------
     def toks2d(B, T, seed, ragged=True):
@@ -122,8 +240,9 @@ def main():
         return t
 
     res["esm2"] = []
-    for L, E, H, seed, B, T in ((2, 480, 20, 101, 2, 37), (3, 640, 20, 102, 2, 23), (2, 256, 2, 103, 3, 41),
-                                (4, 128, 2, 104, 1, 140), (1, 320, 20, 105, 2, 9)):
+    # head dims 24, 32, 128, 64, 16 at few heads and short rows: every output is stored whole, so the cases stay small
+    for L, E, H, seed, B, T in ((2, 48, 2, 101, 2, 14), (3, 64, 2, 102, 2, 11), (1, 128, 1, 103, 2, 10),
+                                (4, 64, 1, 104, 1, 16), (1, 32, 2, 105, 2, 9)):
         sd = synth.synth_esm2_state_dict(L, E, H, seed=seed)
         m = esm.ESM2(num_layers=L, embed_dim=E, attention_heads=H, alphabet="ESM-1b", token_dropout=True).eval()
         m.load_state_dict(sd, strict=True)
@@ -136,7 +255,7 @@ def main():
 
     res["esm1b"] = []
     ab = esm.Alphabet.from_architecture("roberta_large")
-    for L, E, H, seed, B, T, lnb in ((2, 256, 4, 111, 2, 33, True), (3, 128, 2, 112, 3, 18, False)):
+    for L, E, H, seed, B, T, lnb in ((2, 64, 1, 111, 2, 12, True), (3, 64, 2, 112, 2, 8, False)):
         sd = synth.synth_esm1b_state_dict(L, E, H, seed=seed, ln_before=lnb)
         args = argparse.Namespace(arch="roberta_large", layers=L, embed_dim=E, ffn_embed_dim=4 * E, attention_heads=H,
                                   max_positions=1024, token_dropout=True, emb_layer_norm_before=lnb)
@@ -150,7 +269,7 @@ def main():
 
     res["msa"] = []
     am = esm.Alphabet.from_architecture("msa_transformer")
-    for L, E, H, F, seed, B, R, C in ((2, 128, 2, 256, 121, 1, 7, 26), (1, 192, 3, 384, 122, 2, 4, 15)):
+    for L, E, H, F, seed, B, R, C in ((2, 64, 1, 128, 121, 1, 3, 10), (1, 64, 2, 128, 122, 2, 3, 8)):
         sd = synth.synth_msa_state_dict(L, E, H, F, seed=seed)
         args = argparse.Namespace(layers=L, embed_dim=E, ffn_embed_dim=F, attention_heads=H, dropout=0.1,
                                   attention_dropout=0.1, activation_dropout=0.1, max_positions=1024,
@@ -172,41 +291,13 @@ def main():
                                row_attentions=o["row_attentions"].float(), contacts=o["contacts"].float()))
 
     # ---- checkpoint files in the released formats, loaded by the reference's esm.pretrained -----------------
-    ck_dir = os.path.join(os.path.dirname(os.path.abspath(out_path)), "ckpt")
-    os.makedirs(ck_dir, exist_ok=True)
+    work = tempfile.mkdtemp(prefix="reference_probe_")
     res["checkpoints"] = []
-
-    def split_regression(sd):
-        reg = {k: v for k, v in sd.items() if k.startswith("contact_head.")}
-        body = {k: v for k, v in sd.items() if not k.startswith("contact_head.")}
-        return body, reg
-
-    def record(path):
+    for path in write_checkpoints(os.path.join(work, "ckpt"), synth):
         model, alphabet = esm.pretrained.load_model_and_alphabet(path)
-        res["checkpoints"].append(dict(path=path, cls=type(model).__name__, all_toks=list(alphabet.all_toks),
-                                       state={k: v.clone() for k, v in model.state_dict().items()},
+        res["checkpoints"].append(dict(name=os.path.basename(path), cls=type(model).__name__, all_toks=list(alphabet.all_toks),
+                                       state={k: tensor_digest(v) for k, v in model.state_dict().items()},
                                        num_layers=model.num_layers))
-
-    # ESM-2 (cfg format, esm/pretrained.py:164-188)
-    record(synth.write_esm2_checkpoint(ck_dir, "esm2_t3_synth_UR50D", 3, 128, 2, seed=201))
-    # ESM-1b (fairseq args format with encoder_* argument names and encoder.sentence_encoder.* keys, :87-99)
-    body, reg = split_regression(synth.synth_esm1b_state_dict(2, 128, 2, seed=202, ln_before=True))
-    args = argparse.Namespace(arch="roberta_large", encoder_layers=2, encoder_embed_dim=128, encoder_ffn_embed_dim=512,
-                              encoder_attention_heads=2, max_positions=1024, token_dropout=True)
-    path = os.path.join(ck_dir, "esm1b_t2_synth_UR50S.pt")
-    torch.save({"args": args, "model": {"encoder.sentence_encoder." + k: v for k, v in body.items()}}, path)
-    torch.save({"model": reg}, path[:-3] + "-contact-regression.pt")
-    record(path)
-    # MSA Transformer (args format; released files have row / column swapped in the key names, :109-121)
-    body, reg = split_regression(synth.synth_msa_state_dict(2, 128, 2, 256, seed=203))
-    swap = lambda s: s.replace("row", "column") if "row" in s else s.replace("column", "row")
-    args = argparse.Namespace(arch="msa_transformer", encoder_layers=2, encoder_embed_dim=128, encoder_ffn_embed_dim=256,
-                              encoder_attention_heads=2, dropout=0.1, attention_dropout=0.1, activation_dropout=0.1,
-                              max_positions=1024, embed_positions_msa=True, max_tokens=2 ** 14, max_tokens_per_msa=2 ** 14)
-    path = os.path.join(ck_dir, "esm_msa1b_t2_synth_UR50S.pt")
-    torch.save({"args": args, "model": {"encoder.sentence_encoder." + swap(k): v for k, v in body.items()}}, path)
-    torch.save({"model": reg}, path[:-3] + "-contact-regression.pt")
-    record(path)
 
     # ---- Alphabet object surface + dataset edge cases (esm/data.py:91-297, 24-88) -------------------------------
     res["alphabet_surface"] = {}
@@ -270,26 +361,47 @@ def main():
         "esm2_default": {"attrs": {a: getattr(esm.ESM2(num_layers=1), a) for a in ("embed_dim", "attention_heads")}},
     }
 
-    # ---- the reference-side binding stub on the REAL reference class (examples/reference_binding/_esmk.py) ------
-    import ctypes
+    # ---- what examples/reference_binding/_esmk.py reads off the REAL reference class (esm2.py:24-38) -------------
+    m = esm.ESM2(6, 320, 20)
+    res["binding_attrs"] = dict(attrs={a: getattr(m, a) for a in (
+        "num_layers", "embed_dim", "attention_heads", "alphabet_size", "padding_idx", "mask_idx", "cls_idx", "eos_idx",
+        "token_dropout", "prepend_bos", "append_eos")}, state_keys=list(m.state_dict()))
 
-    spec = importlib.util.spec_from_file_location("ref_esmk_stub", os.path.join(ROOT, "examples", "reference_binding", "_esmk.py"))
-    stub = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(stub)
-    libpath = os.path.join(ROOT, "esm_amd", "lib", "libesmk.so")
-    if os.path.exists(libpath):
-        L_ = stub.lib(libpath)
-        m = esm.ESM2(6, 320, 20)
-        cfg = stub.config_for(m)  # reads the attributes the reference's ESM2.__init__ sets
-        h, n = ctypes.c_void_p(), ctypes.c_size_t()
-        rc = L_.esmk_create(ctypes.byref(cfg), ctypes.byref(h))
-        L_.esmk_packed_bytes(h, ctypes.byref(n))
-        L_.esmk_destroy(h)
-        res["stub"] = dict(rc=rc, packed_bytes=n.value, cfg=[getattr(cfg, f[0]) for f in stub.Config._fields_],
-                           state_keys=[k for k in m.state_dict()])
+    # ---- the batches of the reference's own tests/test_alphabet.py, through the reference's alphabets -----------------
+    res["alphabet_tests"] = {}
+    for arch in ("ESM-1b", "roberta_large"):
+        a = esm.Alphabet.from_architecture(arch)
+        res["alphabet_tests"][arch] = [(trunc, batch, a.get_batch_converter(trunc)(batch))
+                                       for trunc, batch in ALPHABET_TEST_BATCHES]
 
-    with open(out_path, "wb") as f:
-        pickle.dump(res, f)
+    # ---- result files of the reference's scripts/extract.py (unmodified, --nogpu) ------------------------------------
+    res["extract"] = {}
+    for name, case in EXTRACT_CASES.items():
+        d = os.path.join(work, name)
+        ck_name, L, E, H, seed = case["ckpt"]
+        ckpt = synth.write_esm2_checkpoint(d, ck_name, L, E, H, seed=seed)
+        if name == "few_proteins_8M":
+            with open(os.path.join(REFERENCE, "examples", "data", "few_proteins.fasta")) as f:
+                text = f.read()
+        else:
+            text = tiny_truncated_fasta()
+        fasta = os.path.join(d, "in.fasta")
+        with open(fasta, "w") as f:
+            f.write(text)
+        out_dir = os.path.join(d, "out")
+        r = subprocess.run([sys.executable, os.path.join(REFERENCE, "scripts", "extract.py"), ckpt, fasta, out_dir] + case["args"],
+                           capture_output=True, text=True, cwd=d, timeout=900,
+                           env=dict(os.environ, PYTHONPATH=REFERENCE, TORCH_FORCE_NO_WEIGHTS_ONLY_LOAD="1"))
+        assert r.returncode == 0, r.stderr[-3000:]
+        files = {}
+        for dirpath, _, names in os.walk(out_dir):
+            for n in names:
+                p = os.path.join(dirpath, n)
+                files[os.path.relpath(p, out_dir)] = slim_result_file(torch.load(p, weights_only=False))
+        res["extract"][name] = dict(fasta=text, files=files)
+
+    shutil.rmtree(work, ignore_errors=True)
+    torch.save(res, out_path)
 
 
 if __name__ == "__main__":

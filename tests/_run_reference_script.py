@@ -1,5 +1,6 @@
-"""Test launcher (never part of the product): runs an UNMODIFIED script of the reference (e.g.
-/root/reference/scripts/extract.py) against this repo's ``esm`` package on a machine without a GPU.
+"""Test launcher (never part of the product): runs a script written against the reference's ``esm`` package (the
+reference's scripts/extract.py, or its step-by-step replay tests/_extract_replay.py) against this repo's ``esm``
+package on a machine without a GPU.
 
 The engine has no CPU path by design, so ONLY inside this launcher ``ESM2.forward`` is replaced by the oracle
 (test infrastructure, oracle/esm2_oracle.py).  What the test then exercises is everything else the script touches:
@@ -7,7 +8,7 @@ The engine has no CPU path by design, so ONLY inside this launcher ``ESM2.forwar
 a torch DataLoader, ``isinstance(model, MSATransformer)``, ``model.eval()`` / ``num_layers``, the keys and shapes of
 the output dict, the per-sequence result files.
 
-    python tests/_run_reference_script.py /root/reference/scripts/extract.py <script arguments...>
+    python tests/_run_reference_script.py <script.py> <script arguments...>
 """
 import os
 import runpy

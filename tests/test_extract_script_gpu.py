@@ -2,9 +2,8 @@
 ``pretrained.load_model_and_alphabet`` -> ``.eval().cuda()`` -> ``FastaBatchedDataset`` + DataLoader with
 ``alphabet.get_batch_converter(truncation_seq_length)`` -> ``toks.to("cuda", non_blocking=True)`` ->
 ``model(toks, repr_layers=.., return_contacts=..)`` -> per-label crops -> ``torch.save``
-(reference scripts/extract.py:63-131).  Where /root/reference exists the UNMODIFIED script file runs (with this repo's
-``esm`` package on the path); on the GPU box, which has no /root/reference, tests/_extract_replay.py issues the same
-calls line by line.  The written files are checked against the CPU oracle."""
+(reference scripts/extract.py:63-131), issued line by line by tests/_extract_replay.py with this repo's ``esm`` package
+on the path.  The written files are checked against the CPU oracle."""
 import os
 import subprocess
 import sys
@@ -20,7 +19,6 @@ import _contract as C
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SCRIPT = "/root/reference/scripts/extract.py"
 
 
 @pytest.mark.parametrize("trunc,tpb", [(1022, 4096), (60, 300)], ids=["defaults", "truncated_small_batches"])
@@ -35,7 +33,7 @@ def test_reference_extract_call_sequence_on_the_engine(tmp_path, trunc, tpb):
     fasta = tmp_path / "in.fasta"
     fasta.write_text("".join(f">{k}\n{v[:40]}\n{v[40:]}\n" for k, v in seqs.items()))  # wrapped sequence lines
     out_dir = tmp_path / "out"
-    script = REF_SCRIPT if os.path.exists(REF_SCRIPT) else os.path.join(ROOT, "tests", "_extract_replay.py")
+    script = os.path.join(ROOT, "tests", "_extract_replay.py")
     env = dict(os.environ, PYTHONPATH=ROOT, TORCH_FORCE_NO_WEIGHTS_ONLY_LOAD="1")
     r = subprocess.run([sys.executable, script, ckpt, str(fasta), str(out_dir), "--repr_layers", "-1", "0", "3", "--include", "mean",
                         "per_tok", "bos", "contacts", "--toks_per_batch", str(tpb), "--truncation_seq_length", str(trunc)],

@@ -1,39 +1,32 @@
-"""Live differential tests against the reference implementation itself — only where /root/reference is mounted
-(the build container; skipped on the GPU box, where the committed fixtures of tests/golden/ take over).
-
-The reference package is also called ``esm``, so it runs in a SUBPROCESS (tests/_reference_probe.py) that dumps
-what the reference computes for seeded random inputs; this process then compares
+"""Differential tests against the reference implementation itself, through the committed fixture
+tests/golden/reference_probe.pt: tests/_reference_probe.py runs inside the reference (its package is also called
+``esm``) and records what it computes for seeded random inputs — tokenisation, batching, FASTA parsing, model
+forwards, checkpoint loading, module surfaces, and the result files of its unmodified scripts/extract.py.  Regenerate
+the fixture with that script where a checkout of the reference exists; these tests need only the repository.
+This process then compares
   * the host side (esm_amd.Alphabet / BatchConverter / MSABatchConverter / FastaBatchedDataset.get_batch_indices /
     read_fasta) — integer work, bit-exact — with reference esm/data.py:19-378;
   * the oracles (oracle/esm2_oracle.py, esm1b_oracle.py, msa_oracle.py) with reference ESM2 / ProteinBertModel /
     MSATransformer forwards on synthetic weights at dims and seeds that are NOT among the committed fixtures
-    (head dims 24 / 32 / 128, other depths), to <= 2e-5: the pin of the oracle is re-checked wherever the reference
-    is available, not only on the frozen vectors.
+    (head dims 24 / 32 / 128, other depths), to <= 2e-5: a second pin of the oracle, independent of the fixtures
+    the model tests use.
 """
 import os
-import pickle
 import subprocess
 import sys
 
 import pytest
 import torch
 
-REFERENCE = "/root/reference"
+import _reference_probe as P
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "esm")),
-                                reason="/root/reference is not mounted here")
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("refprobe") / "probe.pkl"
-    env = dict(os.environ, TORCH_FORCE_NO_WEIGHTS_ONLY_LOAD="1")
-    env.pop("PYTHONPATH", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_reference_probe.py"), str(out)],
-                       capture_output=True, text=True, env=env, cwd=str(out.parent), timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    with open(out, "rb") as f:
-        return pickle.load(f)
+def probe():
+    assert os.path.exists(P.FIXTURE), f"{P.FIXTURE} missing: regenerate with tests/_reference_probe.py"
+    return torch.load(P.FIXTURE, weights_only=False)
 
 
 def test_tokenizer_and_batch_converter_bit_exact(probe):
@@ -78,8 +71,10 @@ def test_fasta_dataset_and_batching_bit_exact(probe, tmp_path):
         ds = esm.FastaBatchedDataset.from_file(f)
         assert list(ds.sequence_labels) == labels and list(ds.sequence_strs) == seqs
         assert ds.get_batch_indices(toks_per_batch, extra_toks_per_seq=extra) == batches
-    for path, kw, rows in probe["read_fasta"]:
-        assert list(esm.data.read_fasta(path, **kw))[:len(rows)] == rows, kw
+    for text, kw, rows in probe["read_fasta"]:
+        f = tmp_path / "x.a3m"
+        f.write_text(text)
+        assert list(esm.data.read_fasta(str(f), **kw))[:len(rows)] == rows, kw
 
 
 def _close(a, b, tol, mask=None):
@@ -133,74 +128,87 @@ def test_msa_oracle_matches_live_reference(probe):
         assert _close(out["contacts"], c["contacts"], 5e-5)
 
 
-def test_reference_extract_script_runs_unmodified_against_the_shim(tmp_path):
-    """BASELINE configs[0]: the reference's scripts/extract.py (8M dims, examples FASTA, --nogpu), once inside the
-    reference package and once — the SAME unmodified file — against this repo's ``esm`` package.  The shim run has the
-    engine replaced by the oracle inside the test launcher only (tests/_run_reference_script.py): the product has no
-    CPU path.  Same files, same labels, same shapes, values to oracle precision."""
+def _check_result_file(got, ref, layers, tol, tag):
+    """A result file written here against the reference's, as the fixture stores it (tests/_reference_probe.py
+    slim_result_file): label and keys; mean and <bos> representations whole; per-token representations and the contact map
+    by shape and dtype, their values on the rows per_tok_rows() keeps."""
+    assert got["label"] == ref["label"] and sorted(got) == ref["keys"], tag
+    for key in ("mean_representations", "bos_representations"):
+        assert sorted(got[key]) == sorted(ref[key]) == layers, (tag, key)
+        for l in ref[key]:
+            assert got[key][l].shape == ref[key][l].shape and got[key][l].dtype == ref[key][l].dtype, (tag, key, l)
+            assert (got[key][l] - ref[key][l]).abs().max().item() < tol, (tag, key, l)
+    assert sorted(got["representations"]) == sorted(ref["per_tok_shape"]) == layers, tag
+    for l, t in got["representations"].items():
+        assert tuple(t.shape) == ref["per_tok_shape"][l] and t.dtype == ref["per_tok_dtype"][l], (tag, l)
+        assert (t[P.per_tok_rows(t.shape[0])] - ref["per_tok_rows"][l]).abs().max().item() < tol, (tag, l)
+    c = got["contacts"]
+    assert tuple(c.shape) == ref["contacts_shape"] and c.dtype == ref["contacts_dtype"], tag
+    assert (c[P.per_tok_rows(c.shape[0])] - ref["contacts_rows"]).abs().max().item() < tol, tag
+
+
+def test_reference_extract_script_runs_unmodified_against_the_shim(probe, tmp_path):
+    """BASELINE configs[0]: the result files of the reference's unmodified scripts/extract.py (8M dims, the reference's
+    examples FASTA, --nogpu), recorded in the fixture (per-token and contact-map rows at a stride), against the same call
+    sequence on this repo's ``esm`` package (tests/_extract_replay.py, each step citing the script's line).  The shim run
+    has the engine replaced by the oracle inside the test launcher only (tests/_run_reference_script.py): the product has
+    no CPU path.  Same files, same labels, same keys, shapes and dtypes, values to oracle precision."""
     from esm_amd.synth import write_esm2_checkpoint
 
-    ckpt = write_esm2_checkpoint(str(tmp_path), "esm2_t6_8M_UR50D", 6, 320, 20, seed=7)
-    fasta = os.path.join(REFERENCE, "examples", "data", "few_proteins.fasta")
-    script = os.path.join(REFERENCE, "scripts", "extract.py")
-    args = [ckpt, fasta, "OUT", "--repr_layers", "0", "5", "6", "--include", "mean", "per_tok", "bos", "contacts",
-            "--nogpu", "--toks_per_batch", "2048"]
-    env = dict(os.environ, TORCH_FORCE_NO_WEIGHTS_ONLY_LOAD="1")
-    outs = {}
-    for tag, cmd, pp in (("ref", [sys.executable, script], REFERENCE),
-                         ("shim", [sys.executable, os.path.join(ROOT, "tests", "_run_reference_script.py"), script], ROOT)):
-        out_dir = tmp_path / tag
-        a = [x if x != "OUT" else str(out_dir) for x in args]
-        r = subprocess.run(cmd + a, capture_output=True, text=True, env=dict(env, PYTHONPATH=pp), cwd=str(tmp_path),
-                           timeout=900)
-        assert r.returncode == 0, (tag, r.stderr[-3000:])
-        outs[tag] = {p.name: torch.load(p, weights_only=False) for p in sorted(out_dir.glob("*.pt"))}
+    case, rec = P.EXTRACT_CASES["few_proteins_8M"], probe["extract"]["few_proteins_8M"]
+    name, L, E, H, seed = case["ckpt"]
+    ckpt = write_esm2_checkpoint(str(tmp_path), name, L, E, H, seed=seed)
+    fasta = tmp_path / "few_proteins.fasta"
+    fasta.write_text(rec["fasta"])
+    out_dir = tmp_path / "shim"
+    cmd = [sys.executable, os.path.join(ROOT, "tests", "_run_reference_script.py"), os.path.join(ROOT, "tests", "_extract_replay.py"),
+           ckpt, str(fasta), str(out_dir)] + case["args"]
+    r = subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp_path), timeout=900,
+                       env=dict(os.environ, PYTHONPATH=ROOT, TORCH_FORCE_NO_WEIGHTS_ONLY_LOAD="1"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    outs = {"ref": rec["files"],
+            "shim": {str(p.relative_to(out_dir)): torch.load(p, weights_only=False) for p in sorted(out_dir.rglob("*.pt"))}}
     assert outs["ref"] and sorted(outs["ref"]) == sorted(outs["shim"])
     for name, ref in outs["ref"].items():
-        got = outs["shim"][name]
-        assert got["label"] == ref["label"] and sorted(got) == sorted(ref)
-        for key in ("representations", "mean_representations", "bos_representations"):
-            assert sorted(got[key]) == sorted(ref[key]) == [0, 5, 6]
-            for l in ref[key]:
-                assert got[key][l].shape == ref[key][l].shape and got[key][l].dtype == ref[key][l].dtype
-                assert (got[key][l] - ref[key][l]).abs().max().item() < 5e-5, (name, key, l)
-        assert got["contacts"].shape == ref["contacts"].shape
-        assert (got["contacts"] - ref["contacts"]).abs().max().item() < 5e-5
+        _check_result_file(outs["shim"][name], ref, [0, 5, 6], 5e-5, name)
 
 
-def test_reference_own_alphabet_tests_pass_on_our_alphabets():
-    """The reference's OWN test helpers (tests/test_alphabet.py:6-45, loaded by file path — they import nothing at
-    module level) executed on this repo's Alphabet objects; their public wrappers download checkpoints just to get an
-    alphabet, which ``Alphabet.from_architecture`` provides offline (esm/pretrained.py:87-127 picks the same names)."""
-    import importlib.util
-
+def test_reference_own_alphabet_tests_pass_on_our_alphabets(probe):
+    """The batches of the reference's OWN alphabet tests (tests/test_alphabet.py:6-45, plain and truncated at 10) through
+    this repo's Alphabet objects give what the reference's alphabets gave (recorded in the fixture); their public
+    wrappers download checkpoints just to get an alphabet, which ``Alphabet.from_architecture`` provides offline
+    (esm/pretrained.py:87-127 picks the same names)."""
     import esm
 
-    spec = importlib.util.spec_from_file_location("ref_test_alphabet", os.path.join(REFERENCE, "tests", "test_alphabet.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
     for arch in ("ESM-1b", "roberta_large"):  # esm1b_t33_650M_UR50S / esm1v_t33_650M_UR90S_* use this alphabet
         a = esm.Alphabet.from_architecture(arch)
-        mod._test_esm1b(a)
-        mod._test_esm1b_truncation(a)
+        cases = probe["alphabet_tests"][arch]
+        assert [(t, b) for t, b, _ in cases] == P.ALPHABET_TEST_BATCHES
+        for trunc, batch, (labels, strs, toks) in cases:
+            got = a.get_batch_converter(trunc)(batch)
+            assert got[0] == labels and got[1] == strs, (arch, trunc)
+            assert got[2].dtype == toks.dtype and torch.equal(got[2], toks), (arch, trunc)
 
 
-def test_checkpoint_loading_matches_reference(probe):
+def test_checkpoint_loading_matches_reference(probe, tmp_path):
     """esm.pretrained.load_model_and_alphabet on checkpoint FILES in the released formats (ESM-2 cfg format;
     ESM-1b / MSA Transformer fairseq-args formats with encoder_* argument names, encoder.sentence_encoder.* key
     prefixes, the row/column key swap of the MSA files, sibling -contact-regression.pt): same model class name, same
-    alphabet, same state-dict keys, identical tensors as the reference's loader (esm/pretrained.py:52-221)."""
+    alphabet, same state-dict keys, bit-identical tensors (dtype, shape, SHA-256 of the bytes) as the reference's loader
+    (esm/pretrained.py:52-221) produced from the same files."""
     import esm
+    from esm_amd import synth
 
-    assert len(probe["checkpoints"]) == 3
-    for c in probe["checkpoints"]:
-        model, alphabet = esm.pretrained.load_model_and_alphabet(c["path"])
-        assert type(model).__name__ == c["cls"], c["path"]
+    paths = P.write_checkpoints(str(tmp_path / "ckpt"), synth)
+    assert [os.path.basename(p) for p in paths] == [c["name"] for c in probe["checkpoints"]] and len(paths) == 3
+    for path, c in zip(paths, probe["checkpoints"]):
+        model, alphabet = esm.pretrained.load_model_and_alphabet(path)
+        assert type(model).__name__ == c["cls"], c["name"]
         assert list(alphabet.all_toks) == c["all_toks"] and model.num_layers == c["num_layers"]
         got = model.state_dict()
         assert sorted(got) == sorted(c["state"]), set(got) ^ set(c["state"])
         for k, v in c["state"].items():
-            assert got[k].dtype == v.dtype and torch.equal(got[k], v), (c["path"], k)
+            assert P.tensor_digest(got[k]) == v, (c["name"], k)
 
 
 def test_module_surface_matches_reference(probe):
@@ -287,56 +295,59 @@ def test_alphabet_object_and_dataset_edge_cases(probe, tmp_path):
 
 
 def test_binding_stub_reads_the_real_reference_class(probe):
-    """examples/reference_binding/_esmk.py configured from an instance of the REFERENCE's ESM2 (attribute names of
-    esm2.py:24-38): esmk_create accepts it and plans the same packed image as for this repo's class."""
+    """examples/reference_binding/_esmk.py configured from the attributes an instance of the REFERENCE's ESM2 carries
+    (esm2.py:24-38, recorded in the fixture): esmk_create accepts it and plans the same packed image as for this repo's
+    class."""
     import ctypes
+    import importlib.util
+    import types
 
     import esm
     from esm_amd import _native
 
-    if "stub" not in probe:
-        pytest.skip("libesmk.so not built")
-    assert probe["stub"]["rc"] == 0
+    spec = importlib.util.spec_from_file_location("ref_esmk_stub", os.path.join(ROOT, "examples", "reference_binding", "_esmk.py"))
+    stub = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(stub)
+    L_ = stub.lib(_native.LIB_PATH)
+    ref = probe["binding_attrs"]
+    scfg = stub.config_for(types.SimpleNamespace(**ref["attrs"]))  # reads the attributes the reference's ESM2.__init__ sets
+    h, n_ref = ctypes.c_void_p(), ctypes.c_size_t()
+    assert L_.esmk_create(ctypes.byref(scfg), ctypes.byref(h)) == 0
+    L_.esmk_packed_bytes(h, ctypes.byref(n_ref))
+    L_.esmk_destroy(h)
     m = esm.ESM2(6, 320, 20)
     cfg = _native.EsmkConfig(6, 320, 20, 1280, m.alphabet_size, m.padding_idx, m.mask_idx, m.cls_idx, m.eos_idx, 1, 1, 1,
                              _native.dtype_code(torch.float16), 0, 0, 0)
-    assert probe["stub"]["cfg"] == [getattr(cfg, f[0]) for f in _native.EsmkConfig._fields_]
+    assert [getattr(scfg, f[0]) for f in stub.Config._fields_] == [getattr(cfg, f[0]) for f in _native.EsmkConfig._fields_]
     h, n = ctypes.c_void_p(), ctypes.c_size_t()
     _native.check(_native.lib.esmk_create(ctypes.byref(cfg), ctypes.byref(h)))
     _native.check(_native.lib.esmk_packed_bytes(h, ctypes.byref(n)))
     _native.lib.esmk_destroy(h)
-    assert n.value == probe["stub"]["packed_bytes"]
-    assert probe["stub"]["state_keys"] == list(m.state_dict())  # every key esmk_pack_weight will be handed
+    assert n.value == n_ref.value
+    assert ref["state_keys"] == list(m.state_dict())  # every key esmk_pack_weight will be handed
 
 
-def test_extraction_driver_writes_the_files_the_reference_script_writes(tmp_path):
+def test_extraction_driver_writes_the_files_the_reference_script_writes(probe, tmp_path):
     """esm_amd.extract.extract (the sharded driver; here one rank on CPU with the oracle as its embed_fn — test
-    infrastructure, the product's embed_fn is the engine) against the reference's scripts/extract.py run on the same
-    checkpoint and FASTA: the same set of <label>.pt files, the same keys, dtypes and shapes, truncation at
-    --truncation_seq_length, values to oracle precision."""
+    infrastructure, the product's embed_fn is the engine) against the result files of the reference's scripts/extract.py
+    run on a checkpoint with the same weights and the same FASTA (recorded in the fixture, rows at a stride as above): the
+    same set of <label>.pt files, the same keys, dtypes and shapes, truncation at --truncation_seq_length, values to
+    oracle precision."""
     import pathlib
 
     import esm
     from esm_amd.extract import extract
-    from esm_amd.synth import synth_esm2_state_dict, write_esm2_checkpoint
+    from esm_amd.synth import synth_esm2_state_dict
     from oracle.esm2_oracle import esm2_forward
 
-    L, E, H = 3, 128, 2
-    ckpt = write_esm2_checkpoint(str(tmp_path), "esm2_t3_tiny_UR50D", L, E, H, seed=17)
-    g = torch.Generator().manual_seed(8)
-    aas = "LAGVSERTIDPKQNFYMHWC"
-    seqs = {f"sp|P{i:05d}|NAME_{i} desc": "".join(aas[j] for j in torch.randint(0, 20, (n,), generator=g).tolist())
-            for i, n in enumerate([12, 55, 31, 70, 8])}
+    case, rec = P.EXTRACT_CASES["tiny_truncated"], probe["extract"]["tiny_truncated"]
+    _, L, E, H, seed = case["ckpt"]
+    assert (L, E, H, seed) == (3, 128, 2, 17) and "--truncation_seq_length" in case["args"]
+    assert rec["fasta"] == P.tiny_truncated_fasta()
     fasta = tmp_path / "in.fasta"
-    fasta.write_text("".join(f">{k}\n{v}\n" for k, v in seqs.items()))
-    common = ["--repr_layers", "-1", "1", "--include", "mean", "per_tok", "bos", "contacts", "--truncation_seq_length", "40",
-              "--toks_per_batch", "150"]
-    r = subprocess.run([sys.executable, os.path.join(REFERENCE, "scripts", "extract.py"), ckpt, str(fasta),
-                        str(tmp_path / "ref"), "--nogpu"] + common, capture_output=True, text=True, cwd=str(tmp_path),
-                       env=dict(os.environ, PYTHONPATH=REFERENCE, TORCH_FORCE_NO_WEIGHTS_ONLY_LOAD="1"), timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
+    fasta.write_text(rec["fasta"])
 
-    sd = synth_esm2_state_dict(L, E, H, seed=17)
+    sd = synth_esm2_state_dict(L, E, H, seed=seed)
     alphabet = esm.Alphabet.from_architecture("ESM-1b")
     ds = esm.FastaBatchedDataset.from_file(fasta)
 
@@ -346,16 +357,8 @@ def test_extraction_driver_writes_the_files_the_reference_script_writes(tmp_path
     extract(ds, alphabet, embed_fn, L, E, [-1, 1], ["mean", "per_tok", "bos", "contacts"],
             output_dir=pathlib.Path(tmp_path / "ours"), toks_per_batch=150, truncation_seq_length=40, device=None,
             gather_mean=False, log=lambda s: None)
-    ref_files = sorted(p.relative_to(tmp_path / "ref") for p in (tmp_path / "ref").rglob("*.pt"))
-    our_files = sorted(p.relative_to(tmp_path / "ours") for p in (tmp_path / "ours").rglob("*.pt"))
+    ref_files = sorted(rec["files"])
+    our_files = sorted(str(p.relative_to(tmp_path / "ours")) for p in (tmp_path / "ours").rglob("*.pt"))
     assert ref_files == our_files and len(ref_files) == 5
     for rel in ref_files:
-        a = torch.load(tmp_path / "ref" / rel, weights_only=False)
-        b = torch.load(tmp_path / "ours" / rel, weights_only=False)
-        assert a["label"] == b["label"] and sorted(a) == sorted(b)
-        for key in ("representations", "mean_representations", "bos_representations"):
-            assert sorted(a[key]) == sorted(b[key]) == [1, L]
-            for l in a[key]:
-                assert a[key][l].shape == b[key][l].shape and a[key][l].dtype == b[key][l].dtype, (rel, key, l)
-                assert (a[key][l] - b[key][l]).abs().max().item() < 5e-5
-        assert a["contacts"].shape == b["contacts"].shape and (a["contacts"] - b["contacts"]).abs().max().item() < 5e-5
+        _check_result_file(torch.load(tmp_path / "ours" / rel, weights_only=False), rec["files"][rel], [1, L], 5e-5, rel)
