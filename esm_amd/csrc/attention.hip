@@ -654,7 +654,9 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const T* __restrict__ q
                 const int qr = q0 + mfma32_row(r, h);
                 if (qr < Tlen) {
                     const float sc = (fill && kb != 0.f) ? -10000.f * LOG2E : s[r] + kb;  // masked_fill vs additive -inf
-                    const float p = __builtin_amdgcn_exp2f(sc - row_lse[r]) * row_keep[r];  // log2 domain
+                    // log2 domain.  Padded query rows: a select, not a multiply by 0 — their lse is the last real row's
+                    // (or 0 in a padding-only wave, attn_fwd_kernel), so exp2 of their own scores can overflow to inf
+                    const float p = row_keep[r] != 0.f ? __builtin_amdgcn_exp2f(sc - row_lse[r]) : 0.f;
                     out[(size_t)qr * Tlen + key] = (O)p;
                 }
             }

@@ -213,8 +213,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd128_kernel(
     }
 
     // ---- normalise and store ctx[b*T + q][head*128 + dv] through a wave-private 8 KiB LDS slice ----------
+    // A sequence of padding only (seq_info: kv_end = 0) has no key tile: O^T and lsum are zero.  As in attention.hip,
+    // inv = 0 writes ctx = 0 and the lse is 0 (1 / 0 gave 0 * inf = NaN and lse -inf, and the maps NaN from that).
+    const bool any_key = kv_end > 0;  // wave uniform
     const float ltot = lsum + __shfl_xor(lsum, 32, 64);
-    const float inv = 1.0f / ltot;
+    const float inv = any_key ? 1.0f / ltot : 0.f;
     using V4 = typename Op<T>::v4;
     char* wl = smem + wave * 8192;  // rows of 256 B (128 dv), 16 chunks, swizzle (row & 15)
 #pragma unroll
@@ -235,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd128_kernel(
         if (q0 + r < Tseg) *reinterpret_cast<V8*>(dst + (size_t)(q0 + r) * ((size_t)H * HD) + c * 8) = v;
     }
     const int qrow = q0 + lm;
-    if (lse != nullptr && h == 0 && qrow < Tseg) lse[rbase + qrow] = m2 + log2f(ltot);  // log2 domain
+    if (lse != nullptr && h == 0 && qrow < Tseg) lse[rbase + qrow] = any_key ? m2 + log2f(ltot) : 0.f;  // log2 domain
 }
 
 template <typename TT>
@@ -324,7 +327,9 @@ __global__ __launch_bounds__(256) void attn_probs128_kernel(const T* __restrict_
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int qr = q0 + mfma32_row(r, h);
-                if (qr < Tlen) out[(size_t)qr * Tlen + key] = (O)(__builtin_amdgcn_exp2f(s[r] + kbv - row_lse[r]) * row_keep[r]);
+                // padded query rows: a select, not a multiply by 0 (exp2 of a padded row's scores may overflow)
+                if (qr < Tlen)
+                    out[(size_t)qr * Tlen + key] = (O)(row_keep[r] != 0.f ? __builtin_amdgcn_exp2f(s[r] + kbv - row_lse[r]) : 0.f);
             }
         }
     }

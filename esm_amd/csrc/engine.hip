@@ -1352,6 +1352,68 @@ int esmk_op_attention_probs(const void* q_dev, const void* k_dev, const float* l
     return 0;
 }
 
+// Every form of the attention core that esmk_forward / esmk_msa_forward launch, reachable one kernel at a time
+// (tests/test_attention_variants_gpu.py).  Validation only, then the engine's own launchers.
+int esmk_op_attention_ex(const void* q_dev, const void* k_dev, const void* vt_dev, const float* key_bias_dev,
+                         const int32_t* seq_info_dev, const int32_t* any_pad_dev, void* ctx_out, float* lse_out, int B,
+                         int H, int T, int Tp, int head_dim, int mode, int operand_dtype, void* stream) {
+    if (!q_dev || !k_dev || !vt_dev || !ctx_out) return fail("esmk_op_attention_ex: null argument");
+    if (B <= 0 || H <= 0 || T <= 0) return fail("esmk_op_attention_ex: B, H and T must be positive");
+    if (Tp < T || Tp % 64 != 0) return fail("esmk_op_attention_ex: Tp must be a multiple of 64 and >= T");
+    if (head_dim != 64 && head_dim != 128) return fail("esmk_op_attention_ex: head_dim must be 64 or 128");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_attention_ex: operand_dtype must be fp16 or bf16");
+    if (mode < 0 || mode > 2) return fail("esmk_op_attention_ex: mode must be 0, 1 or 2");
+    if (mode != 0 && head_dim != 64) return fail("esmk_op_attention_ex: modes 1 and 2 need head_dim 64");
+    if (mode == 2 && operand_dtype != ESMK_DT_F16) return fail("esmk_op_attention_ex: mode 2 (f16x3) needs fp16");
+    if (seq_info_dev && (mode == 1 || !key_bias_dev))
+        return fail("esmk_op_attention_ex: seq_info needs key_bias and mode 0 or 2");
+    if (any_pad_dev && mode != 1) return fail("esmk_op_attention_ex: any_pad belongs to mode 1");
+    hipStream_t st = (hipStream_t)stream;
+    if (head_dim == 128)
+        ESMK_TRY(launch_attention128(q_dev, k_dev, vt_dev, key_bias_dev, seq_info_dev, ctx_out, lse_out, B, H, T, Tp,
+                                     operand_dtype, st));
+    else if (mode == 1)
+        ESMK_TRY(launch_attention_fill(q_dev, k_dev, vt_dev, key_bias_dev, any_pad_dev, ctx_out, lse_out, B, H, T, Tp,
+                                       operand_dtype, st));
+    else if (mode == 2)
+        ESMK_TRY(launch_attention_x3(q_dev, k_dev, vt_dev, key_bias_dev, seq_info_dev, ctx_out, lse_out, B, H, T, Tp,
+                                     operand_dtype, st));
+    else
+        ESMK_TRY(launch_attention(q_dev, k_dev, vt_dev, key_bias_dev, seq_info_dev, ctx_out, lse_out, B, H, T, Tp,
+                                  operand_dtype, st));
+    return 0;
+}
+
+int esmk_op_attention_probs_ex(const void* q_dev, const void* k_dev, const float* lse_dev, const float* key_bias_dev,
+                               const int32_t* any_pad_dev, void* probs_out, int B, int H, int T, int head_dim, int layer,
+                               int num_layers_total, int msa_C, int out_dtype, int operand_dtype, void* stream) {
+    if (!q_dev || !k_dev || !lse_dev || !probs_out) return fail("esmk_op_attention_probs_ex: null argument");
+    if (B <= 0 || H <= 0 || T <= 0) return fail("esmk_op_attention_probs_ex: B, H and T must be positive");
+    if (head_dim != 64 && head_dim != 128) return fail("esmk_op_attention_probs_ex: head_dim must be 64 or 128");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_attention_probs_ex: operand_dtype must be fp16 or bf16");
+    if (out_dtype != ESMK_DT_F32 && out_dtype != operand_dtype)
+        return fail("esmk_op_attention_probs_ex: out_dtype must be fp32 or the operand dtype");
+    if (layer < 0 || layer >= num_layers_total) return fail("esmk_op_attention_probs_ex: layer out of range");
+    if (msa_C < 0) return fail("esmk_op_attention_probs_ex: msa_C must be >= 0");
+    if (msa_C > 0 && (head_dim != 64 || out_dtype != ESMK_DT_F32 || B % msa_C != 0))
+        return fail("esmk_op_attention_probs_ex: the MSA layout needs head_dim 64, fp32 maps and B a multiple of msa_C");
+    if (any_pad_dev && msa_C == 0) return fail("esmk_op_attention_probs_ex: any_pad belongs to the MSA layout");
+    hipStream_t st = (hipStream_t)stream;
+    const bool lowp = out_dtype != ESMK_DT_F32;
+    if (msa_C > 0)
+        ESMK_TRY(launch_attention_probs_msa(q_dev, k_dev, lse_dev, key_bias_dev, any_pad_dev, (float*)probs_out, B / msa_C,
+                                            msa_C, H, T, layer, num_layers_total, operand_dtype, st));
+    else if (head_dim == 128)
+        ESMK_TRY(launch_attention_probs128(q_dev, k_dev, lse_dev, key_bias_dev, (float*)probs_out, B, H, T, layer,
+                                           num_layers_total, operand_dtype, st, lowp));
+    else
+        ESMK_TRY(launch_attention_probs(q_dev, k_dev, lse_dev, key_bias_dev, (float*)probs_out, B, H, T, layer,
+                                        num_layers_total, operand_dtype, st, lowp));
+    return 0;
+}
+
 int esmk_op_contacts(const float* attn_dev, const int64_t* tokens_dev, const float* w_dev,
                      const float* b_dev, float* scratch_dev, float* out_dev, int B, int C, int T,
                      int eos_idx, int prepend_bos, int append_eos, void* stream) {

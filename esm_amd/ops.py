@@ -103,29 +103,56 @@ def to_log2_domain(q, dtype=None):
     return qk, qk.float() / LOG2E
 
 
-def attention(q, k, vt, key_bias=None, want_lse=False):
-    """softmax(q k^T + key_bias) v for head_dim 64.  q [B,H,T,64] in the LOG2 domain (``to_log2_domain``), k
-    [B,H,T,64]; vt [B,H,64,Tp] (layout of the fused QKV epilogue, see csrc/attention.hip).  Returns ctx
-    [B*T, H*64] (+ the row log-sum-exp converted to the natural log, [B,H,T])."""
-    _req_cuda(q, k, vt, key_bias)
+def attention(q, k, vt, key_bias=None, want_lse=False, seq_info=None, fill_any_pad=None, x3=False):
+    """softmax(q k^T + key_bias) v.  q [B,H,T,D] in the LOG2 domain (``to_log2_domain``), k [B,H,T,D], D = 64 or 128
+    (taken from q); vt [B,H,D,Tp] (layout of the fused QKV epilogue, see csrc/attention.hip).  Returns ctx
+    [B*T, H*D] (+ the row log-sum-exp converted to the natural log, [B,H,T]).
+
+    seq_info: int32 [B,2] = (#pads, 1 + index of the last non-pad token), the padded-batch form esmk_forward launches
+    (needs key_bias).  fill_any_pad: int32 device tensor of one element — the MSA column form: key_bias holds 0/1
+    fill flags, used when the flag is non-zero (D = 64).  x3: the f16x3 form, ctx [B*T, 3*H*64] with hi | hi | lo per
+    head (D = 64, fp16).  Without any of the three this is esmk_op_attention (D = 64) or the plain d128 kernel."""
+    _req_cuda(q, k, vt, key_bias, seq_info, fill_any_pad)
     B, H, T, D = q.shape
-    assert D == 64 and vt.shape[-1] == (T + 63) // 64 * 64
-    ctx = torch.empty((B * T, H * 64), dtype=q.dtype, device=q.device)
+    assert vt.shape[-2] == D and vt.shape[-1] % 64 == 0 and vt.shape[-1] >= T
     lse = torch.empty((B, H, T), dtype=torch.float32, device=q.device) if want_lse else None
-    N.check(N.lib.esmk_op_attention(N.ptr(q), N.ptr(k), N.ptr(vt), N.ptr(key_bias), N.ptr(ctx), N.ptr(lse),
-                                    B, H, T, N.dtype_code(q.dtype), N.cur_stream()))
+    mode = 2 if x3 else 1 if fill_any_pad is not None else 0
+    if seq_info is None and mode == 0 and D == 64 and vt.shape[-1] == (T + 63) // 64 * 64:
+        ctx = torch.empty((B * T, H * 64), dtype=q.dtype, device=q.device)
+        N.check(N.lib.esmk_op_attention(N.ptr(q), N.ptr(k), N.ptr(vt), N.ptr(key_bias), N.ptr(ctx), N.ptr(lse),
+                                        B, H, T, N.dtype_code(q.dtype), N.cur_stream()))
+    else:
+        if seq_info is not None:
+            assert seq_info.dtype == torch.int32 and tuple(seq_info.shape) == (B, 2)
+        if fill_any_pad is not None:
+            assert fill_any_pad.dtype == torch.int32 and fill_any_pad.numel() == 1
+        ctx = torch.empty((B * T, H * D * (3 if x3 else 1)), dtype=q.dtype, device=q.device)
+        N.check(N.lib.esmk_op_attention_ex(N.ptr(q), N.ptr(k), N.ptr(vt), N.ptr(key_bias), N.ptr(seq_info),
+                                           N.ptr(fill_any_pad), N.ptr(ctx), N.ptr(lse), B, H, T, vt.shape[-1], D, mode,
+                                           N.dtype_code(q.dtype), N.cur_stream()))
     return (ctx, lse / LOG2E) if want_lse else ctx  # the kernel's lse is log2-domain
 
 
-def attention_probs(q, k, lse, key_bias=None, out=None, layer=0, num_layers=1):
-    """q in the log2 domain; lse: natural-log row log-sum-exp as returned by ``attention(..., want_lse=True)``."""
-    _req_cuda(q, k, lse, key_bias, out)
+def attention_probs(q, k, lse, key_bias=None, out=None, layer=0, num_layers=1, fill_any_pad=None, msa_C=0,
+                    out_dtype=torch.float32):
+    """q in the log2 domain; lse: natural-log row log-sum-exp as returned by ``attention(..., want_lse=True)``.
+    Maps [B, num_layers, H, T, T] (slice `layer`) in out_dtype (fp32 or q's dtype), D = 64 or 128 from q.  msa_C > 0:
+    the MSA column layout [B / msa_C, num_layers, H, msa_C, T, T] with key_bias = fill flags and fill_any_pad as in
+    ``attention`` (D = 64, fp32)."""
+    _req_cuda(q, k, lse, key_bias, out, fill_any_pad)
     lse = (lse * LOG2E).contiguous()
     B, H, T, D = q.shape
     if out is None:
-        out = torch.empty((B, num_layers, H, T, T), dtype=torch.float32, device=q.device)
-    N.check(N.lib.esmk_op_attention_probs(N.ptr(q), N.ptr(k), N.ptr(lse), N.ptr(key_bias), N.ptr(out), B, H, T,
-                                          layer, num_layers, N.dtype_code(q.dtype), N.cur_stream()))
+        shape = (B // msa_C, num_layers, H, msa_C, T, T) if msa_C else (B, num_layers, H, T, T)
+        out = torch.empty(shape, dtype=out_dtype, device=q.device)
+    assert out.dtype == out_dtype
+    if D == 64 and msa_C == 0 and fill_any_pad is None and out_dtype == torch.float32:
+        N.check(N.lib.esmk_op_attention_probs(N.ptr(q), N.ptr(k), N.ptr(lse), N.ptr(key_bias), N.ptr(out), B, H, T,
+                                              layer, num_layers, N.dtype_code(q.dtype), N.cur_stream()))
+    else:
+        N.check(N.lib.esmk_op_attention_probs_ex(N.ptr(q), N.ptr(k), N.ptr(lse), N.ptr(key_bias), N.ptr(fill_any_pad),
+                                                 N.ptr(out), B, H, T, D, layer, num_layers, msa_C,
+                                                 N.dtype_code(out_dtype), N.dtype_code(q.dtype), N.cur_stream()))
     return out
 
 
@@ -153,7 +180,8 @@ def permute_keys16(t):
 
 
 def make_vt(v):
-    """Reference layout helper: v [B,H,T,64] -> vt [B,H,64,Tp] as the QKV epilogue writes it."""
+    """Reference layout helper: v [B,H,T,D] -> vt [B,H,D,Tp] as the QKV epilogue writes it (D = 64 or 128: the key
+    permutation is the same for both head dims, csrc/attention128.hip)."""
     B, H, T, D = v.shape
     Tp = (T + 63) // 64 * 64
     vt = torch.zeros((B, H, D, Tp), dtype=v.dtype, device=v.device)

@@ -335,6 +335,29 @@ int esmk_op_attention_probs(const void* q_dev, const void* k_dev, const float* l
                             const float* key_bias_dev, float* probs_out, int B, int H, int T,
                             int layer, int num_layers_total, int operand_dtype, void* stream);
 
+/* Every form of the attention core the engine launches, one kernel at a time (tests / micro-benchmarks; no reference
+ * counterpart beyond the two entries above).  Same score domain as esmk_op_attention; vt [B,H,head_dim,Tp], Tp a
+ * multiple of 64 and >= T.
+ *   mode 0: key_bias fp32 [B,T] (0 / -inf, or NULL); seq_info int32 [B,2] = (#pads, 1 + index of the last non-pad
+ *           token) as esmk_forward computes it, or NULL (needs key_bias); head_dim 64 or 128.  With seq_info, all-pad
+ *           key tiles behind the last real token are skipped and padded query rows give finite values (ctx and lse
+ *           0 for a sequence of padding only).  ctx_out [B*T, H*head_dim].
+ *   mode 1: MSA column attention (axial_attention.py:207-218): key_bias holds 0/1 fill flags, used only when the
+ *           device int *any_pad_dev != 0 (NULL = 0); a flagged key's score is REPLACED by -10000; head_dim 64.
+ *   mode 2: precision mode f16x3: ctx_out [B*T, 3*H*64], per head hi | hi | lo with lo = fp16(v - hi); head_dim 64,
+ *           fp16 only.
+ * lse_out fp32 [B,H,T] (log2 domain) or NULL.  Invalid combinations fail before the HIP runtime is touched. */
+int esmk_op_attention_ex(const void* q_dev, const void* k_dev, const void* vt_dev, const float* key_bias_dev,
+                         const int32_t* seq_info_dev, const int32_t* any_pad_dev, void* ctx_out, float* lse_out, int B,
+                         int H, int T, int Tp, int head_dim, int mode, int operand_dtype, void* stream);
+/* Probabilities of every form: msa_C = 0 is the ESM-2 layout probs_out [B, Ltot, H, T, T] (rows / cols of padded
+ * tokens zeroed, head_dim 64 or 128, out_dtype fp32 or the operand dtype); msa_C > 0 is the MSA column layout
+ * [B / msa_C, Ltot, H, msa_C, T, T] (B = batch x columns, key_bias = fill flags with any_pad_dev as in mode 1, query rows
+ * not zeroed, head_dim 64, fp32). */
+int esmk_op_attention_probs_ex(const void* q_dev, const void* k_dev, const float* lse_dev, const float* key_bias_dev,
+                               const int32_t* any_pad_dev, void* probs_out, int B, int H, int T, int head_dim, int layer,
+                               int num_layers_total, int msa_C, int out_dtype, int operand_dtype, void* stream);
+
 /* ContactPredictionHead.forward (modules.py:338-357) incl. symmetrize/apc (modules.py:27-41).
  * attn fp32 [B,C=L*H,T,T]; w fp32 [C]; b fp32 [1]; scratch fp32 >= B*C*(T+1) floats;
  * out fp32 [B,T-2,T-2] (crop follows prepend_bos/append_eos). */

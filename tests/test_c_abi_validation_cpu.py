@@ -189,3 +189,40 @@ def test_ln_fold_validation_without_gpu():
     cfg = N.EsmkConfig(1, 128, 2, 512, 33, 1, 32, 0, 2, 1, 1, 1, f16, 0, 0, 0, 0, -1)
     assert N.lib.esmk_create(ctypes.byref(cfg), ctypes.byref(h)) == 0
     N.lib.esmk_destroy(h)
+
+
+def test_attention_ex_argument_checks():
+    """esmk_op_attention_ex / esmk_op_attention_probs_ex: every invalid combination of head_dim, mode, dtype and tile
+    padding is refused before a launch (the buffers are fake)."""
+    f16, bf16 = N.dtype_code(torch.float16), N.dtype_code(torch.bfloat16)
+
+    def fwd(head_dim=64, mode=0, dt=f16, B=2, H=2, T=100, Tp=128, bias=FAKE, seq=None, anyp=None, q=FAKE):
+        return N.lib.esmk_op_attention_ex(q, FAKE, FAKE, bias, seq, anyp, FAKE, None, B, H, T, Tp, head_dim, mode, dt,
+                                          None)
+
+    assert fwd(q=None) != 0 and "null" in err()
+    assert fwd(T=0) != 0 and "positive" in err()
+    for Tp in (100, 96, 64):  # not a multiple of 64 / shorter than T
+        assert fwd(Tp=Tp) != 0 and "Tp" in err(), Tp
+    for hd in (32, 96, 256):
+        assert fwd(head_dim=hd) != 0 and "head_dim" in err(), hd
+    assert fwd(dt=N.F32) != 0 and "operand_dtype" in err()
+    assert fwd(mode=3) != 0 and "mode" in err()
+    assert fwd(head_dim=128, mode=1) != 0 and "head_dim 64" in err()
+    assert fwd(head_dim=128, mode=2) != 0 and "head_dim 64" in err()
+    assert fwd(mode=2, dt=bf16) != 0 and "fp16" in err()
+    assert fwd(seq=FAKE, bias=None) != 0 and "seq_info" in err()
+    assert fwd(mode=1, seq=FAKE) != 0 and "seq_info" in err()
+    assert fwd(mode=0, anyp=FAKE) != 0 and "any_pad" in err()
+
+    def probs(head_dim=64, msa_C=0, out=f16, dt=f16, B=4, layer=0, L=1, anyp=None):
+        return N.lib.esmk_op_attention_probs_ex(FAKE, FAKE, FAKE, None, anyp, FAKE, B, 2, 100, head_dim, layer, L,
+                                                msa_C, out, dt, None)
+
+    assert probs(head_dim=96) != 0 and "head_dim" in err()
+    assert probs(out=bf16) != 0 and "out_dtype" in err()
+    assert probs(layer=1) != 0 and "layer" in err()
+    assert probs(msa_C=3, out=N.F32) != 0 and "msa_C" in err()          # B = 4 columns of a batch of 4 / 3
+    assert probs(msa_C=2, out=f16) != 0 and "fp32" in err()
+    assert probs(msa_C=2, head_dim=128, out=N.F32) != 0 and "head_dim 64" in err()
+    assert probs(anyp=FAKE, out=N.F32) != 0 and "any_pad" in err()

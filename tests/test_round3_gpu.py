@@ -17,12 +17,13 @@ def _small(L=3, E=128, H=2, seed=2):
     return m.cuda()
 
 
-def test_pad_positions_are_finite_and_an_all_pad_sequence_gives_zeros_not_nan():
+@pytest.mark.parametrize("E,H", [(128, 2), (256, 2)])   # head_dim 64 and 128 (attention.hip / attention128.hip)
+def test_pad_positions_are_finite_and_an_all_pad_sequence_gives_zeros_not_nan(E, H):
     """Outputs at <pad> positions are UNSPECIFIED (README / INTEGRATION.md): the reference computes garbage there and
     NaN for a sequence made of padding only; the engine copies the last real query row inside a wave, writes zeros for
     padding-only waves — and never inf / NaN, because ESM_AMD_CHECK_FINITE and downstream reductions look at the whole
     tensor.  Real rows are unaffected by their neighbours' padding: bit-equal to the sequence alone."""
-    model = _small()
+    model = _small(E=E, H=H)
     T = 70
     toks = synth_tokens(3, T - 2, seed=9)
     toks[1, 21] = 2      # <eos> after 20 residues, padding behind it
