@@ -519,11 +519,12 @@ hipError_t launch_attention_fill(const void* q, const void* k, const void* vt, c
 }
 
 // token-packed batch: one row space of `rows` rows, `n_items` query blocks described by segs.work
+// lse: nullptr, or [H, rows] (log2 domain; the packed contact kernels read it)
 hipError_t launch_attention_packed(const void* q, const void* k, const void* vt, const float* key_bias, void* ctx,
-                                   int H, int rows, int Tp, AttnSegs segs, int n_items, int operand_dtype,
+                                   float* lse, int H, int rows, int Tp, AttnSegs segs, int n_items, int operand_dtype,
                                    hipStream_t st) {
     if (segs.work == nullptr || segs.npad == nullptr || n_items <= 0) return hipErrorInvalidValue;
-    return launch_attention_impl(q, k, vt, key_bias, nullptr, ctx, nullptr, 1, H, rows, Tp, operand_dtype, 0, nullptr,
+    return launch_attention_impl(q, k, vt, key_bias, nullptr, ctx, lse, 1, H, rows, Tp, operand_dtype, 0, nullptr,
                                  st, segs, n_items);
 }
 

@@ -261,13 +261,13 @@ static hipError_t launch128(const void* q, const void* k, const void* vt, const 
 
 // token-packed batch (see launch_attention_packed)
 hipError_t launch_attention128_packed(const void* q, const void* k, const void* vt, const float* key_bias, void* ctx,
-                                      int H, int rows, int Tp, AttnSegs segs, int n_items, int operand_dtype,
-                                      hipStream_t st) {
+                                      float* lse, int H, int rows, int Tp, AttnSegs segs, int n_items,
+                                      int operand_dtype, hipStream_t st) {
     if (segs.work == nullptr || segs.npad == nullptr || n_items <= 0 || H <= 0 || rows <= 0 || Tp < rows || (Tp & 63))
         return hipErrorInvalidValue;
     if (operand_dtype == ESMK_DT_BF16)
-        return launch128<__bf16>(q, k, vt, key_bias, nullptr, ctx, nullptr, 1, H, rows, Tp, st, segs, n_items);
-    return launch128<_Float16>(q, k, vt, key_bias, nullptr, ctx, nullptr, 1, H, rows, Tp, st, segs, n_items);
+        return launch128<__bf16>(q, k, vt, key_bias, nullptr, ctx, lse, 1, H, rows, Tp, st, segs, n_items);
+    return launch128<_Float16>(q, k, vt, key_bias, nullptr, ctx, lse, 1, H, rows, Tp, st, segs, n_items);
 }
 
 hipError_t launch_attention128(const void* q, const void* k, const void* vt, const float* key_bias,

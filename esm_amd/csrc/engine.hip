@@ -103,11 +103,18 @@ struct PackedCtx {
     int n_seg = 0, max_len = 0, n_items = 0;
     double sum_len2 = 0;                // sum of len^2: the attention work
     const int32_t* seg_host = nullptr;  // [n_seg][2] = (first row, length)
+    const CtPackedPlan* ct = nullptr;   // contacts (esmk_forward_packed_ex): scratch sizes and work lists
 };
 // query blocks of 128 rows: sum over segments of ceil(len / 128) <= rows / 128 + n_seg
 inline size_t packed_items_bound(int n_seg, int rows) { return (size_t)rows / 128 + (size_t)n_seg; }
+// int32 slots of the packed batch's table in front of the contact tables (kept 8-byte aligned for their offsets)
+inline size_t packed_ct_table_base(int n_seg, int rows) {
+    return ((size_t)3 * n_seg + 4 * packed_items_bound(n_seg, rows) + 1) & ~(size_t)1;
+}
 
-Workspace plan_workspace(const esmk_model* m, int B, int T, uint32_t flags, int packed_segs = 0) {
+// ct: token-packed batch with ESMK_OUT_CONTACTS (flags must then hold it): per-segment contact scratch
+Workspace plan_workspace(const esmk_model* m, int B, int T, uint32_t flags, int packed_segs = 0,
+                         const CtPackedPlan* ct = nullptr) {
     Workspace w{};
     const size_t os = op_size(m->cfg.operand_dtype);
     const size_t N = (size_t)B * T, E = m->E, F = m->F, EA = m->EA, Kp = m->Kp;
@@ -152,16 +159,27 @@ Workspace plan_workspace(const esmk_model* m, int B, int T, uint32_t flags, int 
     w.ct_scratch = c.take(((flags & ESMK_OUT_CONTACTS) && !fused_ct)
                               ? (size_t)B * m->L * m->H * (size_t)(S > 0 ? S + 1 : 1) * 4 : 0);
     const size_t C = (size_t)m->L * m->H;
-    w.ct_acc = c.take(fused_ct ? (size_t)contacts_head_groups(B, T, m->H, m->D == 128 ? 128 : 64) * B * T * T * 4 : 0);
-    w.ct_row = c.take(fused_ct ? (size_t)B * C * T * 4 : 0);
-    w.ct_col = c.take(fused_ct ? (size_t)B * C * T * 4 : 0);
-    w.ct_rowp = c.take(fused_ct ? (size_t)B * ((T + 127) / 128) * m->H * T * 4 : 0);
-    w.ct_colp = c.take(fused_ct ? (size_t)B * ((T + 31) / 32) * m->H * T * 4 : 0);
-    w.ct_wt = c.take(fused_ct ? (size_t)B * C * 4 : 0);
+    const long long nQ = (T + 127) / 128;
+    if (ct != nullptr) {  // per segment: G x len^2 accumulators, [C, len] sums, row / column partials (contacts.hip)
+        w.ct_acc = c.take((size_t)ct->G * ct->sum_len2 * 4);
+        w.ct_row = c.take((size_t)C * T * 4);
+        w.ct_col = c.take((size_t)C * T * 4);
+        w.ct_rowp = c.take((size_t)ct->rowp * 4);
+        w.ct_colp = c.take((size_t)ct->colp * 4);
+        w.ct_wt = c.take((size_t)packed_segs * C * 4);
+    } else {
+        w.ct_acc = c.take(fused_ct ? (size_t)contacts_head_groups((long long)B * nQ * nQ, m->H, m->D == 128 ? 128 : 64) * B * T * T * 4 : 0);
+        w.ct_row = c.take(fused_ct ? (size_t)B * C * T * 4 : 0);
+        w.ct_col = c.take(fused_ct ? (size_t)B * C * T * 4 : 0);
+        w.ct_rowp = c.take(fused_ct ? (size_t)B * ((T + 127) / 128) * m->H * T * 4 : 0);
+        w.ct_colp = c.take(fused_ct ? (size_t)B * ((T + 31) / 32) * m->H * T * 4 : 0);
+        w.ct_wt = c.take(fused_ct ? (size_t)B * C * 4 : 0);
+    }
     if (packed_segs > 0) {
         w.row_pos = c.take(N * 4);
-        // [seg 2 n_seg][npad n_seg][work 4 n_items]
-        w.tables = c.take(((size_t)3 * packed_segs + 4 * packed_items_bound(packed_segs, T)) * 4);
+        // [seg 2 n_seg][npad n_seg][work 4 n_items] and, with contacts, the contact tables (kernels.h, CtPackedPlan)
+        w.tables = c.take(ct != nullptr ? (packed_ct_table_base(packed_segs, T) + ct->table_ints()) * 4
+                                        : ((size_t)3 * packed_segs + 4 * packed_items_bound(packed_segs, T)) * 4);
     }
     w.total = c.off;
     return w;
@@ -560,6 +578,47 @@ int esmk_packed_workspace_bytes(const esmk_model* m, int n_seg, int rows, uint32
     return 0;
 }
 
+// esmk_packed_workspace_bytes_ex / esmk_forward_packed_ex: flags, handle and segment table checks shared by both;
+// with ESMK_OUT_CONTACTS the contact plan of the batch is made in *ct
+static int check_packed_ex(const char* who, const esmk_model* m, const int32_t* seg, int n_seg, int rows,
+                           uint32_t out_flags, PackedCtx* pc, CtPackedPlan* ct) {
+    const std::string w(who);
+    if (check_segments(who, m, seg, n_seg, rows, pc)) return 1;
+    if (out_flags & (ESMK_OUT_ATTN | ESMK_OUT_ATTN_LOWP))
+        return fail(w + ": attention maps take padded batches (esmk_forward)");
+    if (out_flags & ~(uint32_t)(ESMK_OUT_LOGITS | ESMK_OUT_REPR_LOWP | ESMK_OUT_CONTACTS))
+        return fail(w + ": only ESMK_OUT_LOGITS / ESMK_OUT_REPR_LOWP / ESMK_OUT_CONTACTS are available");
+    if (split_x3(m))
+        return fail(w + ": the f16x3 precision mode runs padded batches of head_dim-64 models (no token-packed form)");
+    if (out_flags & ESMK_OUT_CONTACTS) {
+        *ct = contacts_packed_plan(seg, n_seg, m->H, m->D == 128 ? 128 : 64, m->cfg.prepend_bos ? 1 : 0,
+                                   m->cfg.append_eos ? 1 : 0);
+        if (pc) pc->ct = ct;
+    }
+    return 0;
+}
+
+int esmk_packed_workspace_bytes_ex(const esmk_model* m, const int32_t* segments_host, int n_seg, int rows,
+                                   uint32_t out_flags, size_t* bytes) {
+    if (!m || !bytes) return fail("esmk_packed_workspace_bytes_ex: null argument");
+    PackedCtx pc;
+    CtPackedPlan ct;
+    if (check_packed_ex("esmk_packed_workspace_bytes_ex", m, segments_host, n_seg, rows, out_flags, &pc, &ct)) return 1;
+    *bytes = plan_workspace(m, 1, rows, out_flags, n_seg, pc.ct).total;
+    return 0;
+}
+
+int esmk_forward_packed_ex(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev,
+                           const int32_t* segments_host, int n_seg, int rows, const int32_t* repr_layers,
+                           int n_repr, void* const* repr_out_dev, uint32_t out_flags, void* logits_out_dev,
+                           void* contacts_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    PackedCtx pc;
+    CtPackedPlan ct;
+    if (check_packed_ex("esmk_forward_packed_ex", m, segments_host, n_seg, rows, out_flags, &pc, &ct)) return 1;
+    return forward_impl(m, packed_dev, tokens_dev, 1, rows, repr_layers, n_repr, repr_out_dev, out_flags,
+                        logits_out_dev, nullptr, contacts_out_dev, workspace_dev, workspace_bytes, stream, &pc);
+}
+
 int esmk_forward_packed(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev,
                         const int32_t* segments_host, int n_seg, int rows, const int32_t* repr_layers,
                         int n_repr, void* const* repr_out_dev, uint32_t out_flags, void* logits_out_dev,
@@ -597,7 +656,7 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
     for (int i = 0; i < n_repr; ++i)
         if (repr_layers[i] < 0 || repr_layers[i] > m->L || !repr_out_dev[i])
             return fail("esmk_forward: bad repr layer request");
-    const Workspace w = plan_workspace(m, B, T, out_flags, pc ? pc->n_seg : 0);
+    const Workspace w = plan_workspace(m, B, T, out_flags, pc ? pc->n_seg : 0, pc ? pc->ct : nullptr);
     if (workspace_bytes < w.total) return fail("esmk_forward: workspace too small");
 
     hipStream_t st = (hipStream_t)stream;
@@ -627,9 +686,11 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
     // token-packed batch: segment table, <pad> counts and the attention work list live behind the workspace
     int* row_pos = nullptr;
     AttnSegs segs;
+    CtPackedDev ctd;
     if (pc) {
         int* tab = (int*)(ws + w.tables);
-        const size_t n_int = (size_t)3 * pc->n_seg + (size_t)4 * pc->n_items;
+        const size_t ct_base = packed_ct_table_base(pc->n_seg, T);  // contact tables, if any, from this slot on
+        const size_t n_int = pc->ct ? ct_base + pc->ct->table_ints() : (size_t)3 * pc->n_seg + (size_t)4 * pc->n_items;
         if (m->pk_event) ESMK_TRY(hipEventSynchronize(m->pk_event));  // the previous upload has read the staging
         else ESMK_TRY(hipEventCreateWithFlags(&m->pk_event, hipEventDisableTiming));
         if (m->pk_host_cap < n_int) {
@@ -657,6 +718,17 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
                 wk[3] = s;
                 wk += 4;
             }
+        }
+        if (pc->ct) {  // contact offsets and work lists: the same upload
+            contacts_packed_tables(*pc->ct, pc->seg_host, m->cfg.prepend_bos ? 1 : 0, m->cfg.append_eos ? 1 : 0, m->H,
+                                   hostv + ct_base);
+            ctd.seg = tab;
+            ctd.off = reinterpret_cast<const long long*>(tab + ct_base);
+            ctd.acc_work = tab + ct_base + 8 * (size_t)pc->n_seg;
+            ctd.red_work = ctd.acc_work + 4 * pc->ct->n_acc;
+            ctd.rt_work = ctd.red_work + 2 * pc->ct->n_red;
+            ctd.fin_work = ctd.rt_work + pc->ct->n_rt;
+            ctd.rows = T;
         }
         ESMK_TRY(hipMemcpyAsync(tab, hostv, n_int * 4, hipMemcpyHostToDevice, st));
         ESMK_TRY(hipEventRecord(m->pk_event, st));
@@ -888,13 +960,22 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
             if (pc)  // gap rows of the context (the rows of h were last read by the two GEMMs above)
                 ESMK_TRY(launch_zero_gap_rows(hB, (const int*)(ws + w.tables), pc->n_seg, T, (size_t)EA * os, st));
             if (pc && m->D == 128)
-                ESMK_TRY(launch_attention128_packed(q, k, vt, key_bias, hB, H, T, w.Tp, segs, pc->n_items, op, st));
-            else if (pc) ESMK_TRY(launch_attention_packed(q, k, vt, key_bias, hB, H, T, w.Tp, segs, pc->n_items, op, st));
+                ESMK_TRY(launch_attention128_packed(q, k, vt, key_bias, hB, lse, H, T, w.Tp, segs, pc->n_items, op, st));
+            else if (pc) ESMK_TRY(launch_attention_packed(q, k, vt, key_bias, hB, lse, H, T, w.Tp, segs, pc->n_items, op, st));
             else if (m->D == 128) ESMK_TRY(launch_attention128(q, k, vt, key_bias, seq_info, hB, lse, B, H, T, w.Tp, op, st));
             else if (x3) ESMK_TRY(launch_attention_x3(q, k, vt, key_bias, seq_info, a3, lse, B, H, T, w.Tp, op, st));
             else ESMK_TRY(launch_attention(q, k, vt, key_bias, seq_info, hB, lse, B, H, T, w.Tp, op, st));
         }
-        if (fused_ct && S_ct > 0) {
+        if (fused_ct && pc) {  // the same per segment (its [len,len] accumulators; segments with S <= 0 have no work)
+            const CtPackedPlan& cp = *pc->ct;
+            ProfScope ps(m, st, PC_ATTN_PROBS, 2.0 * cp.sum_len2 * E, 2 * NE * os + 8.0 * cp.sum_len2);
+            ESMK_TRY(launch_contacts_packed_layer(q, k, lse, key_bias, tokens_dev, (const float*)(pk + m->ct_w),
+                                                  (float*)(ws + w.ct_acc), (float*)(ws + w.ct_row),
+                                                  (float*)(ws + w.ct_col), (float*)(ws + w.ct_rowp),
+                                                  (float*)(ws + w.ct_colp), cp, ctd, H, L * H, l,
+                                                  m->D == 128 ? 128 : 64, m->cfg.pad_idx, m->cfg.eos_idx,
+                                                  m->cfg.prepend_bos, m->cfg.append_eos, op, st));
+        } else if (fused_ct && S_ct > 0) {
             // q, k and lse of this layer are still in the workspace: add the layer's channels to the
             // [B,T,T] accumulator and the per-channel masked row / column sums
             ProfScope ps(m, st, PC_ATTN_PROBS, 2.0 * N * (double)T * E, 2 * NE * os + 8.0 * N * T);
@@ -1040,7 +1121,15 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
         g.K = Kp;
         if (gemm(PC_LM_LOGITS, g, EPI_STORE_F32, 4)) return 1;
     }
-    if (fused_ct && S_ct > 0) {
+    if (fused_ct && pc) {
+        const CtPackedPlan& cp = *pc->ct;
+        ProfScope ps(m, st, PC_CONTACTS, 0, 4.0 * ((double)cp.sum_len2 * 2 + 3.0 * L * H * T));
+        ESMK_TRY(launch_contacts_packed_final((const float*)(ws + w.ct_acc), (float*)(ws + w.ct_row),
+                                              (const float*)(ws + w.ct_col), (float*)(ws + w.ct_wt), tokens_dev,
+                                              (const float*)(pk + m->ct_w), (const float*)(pk + m->ct_b),
+                                              (float*)contacts_out_dev, cp, ctd, L * H, m->cfg.pad_idx,
+                                              m->cfg.eos_idx, m->cfg.prepend_bos, m->cfg.append_eos, st));
+    } else if (fused_ct && S_ct > 0) {
         ProfScope ps(m, st, PC_CONTACTS, 0, 4.0 * B * ((double)T * T * 2 + 3.0 * L * H * T));
         ESMK_TRY(launch_contacts_fused_final((const float*)(ws + w.ct_acc), (float*)(ws + w.ct_row),
                                              (const float*)(ws + w.ct_col), (float*)(ws + w.ct_wt), tokens_dev,

@@ -181,9 +181,10 @@ hipError_t launch_contacts(const float* attn, const int64_t* tokens, const float
 
 // contacts.hip — contact maps without the [B,L,H,T,T] attention tensor (predict_contacts, esm2.py:146-147).
 // Per layer, after the attention kernel (q, k, lse still in the workspace): A[G][B,T,T] += sum_h w[layer,h] P_h
-// (G = contacts_head_groups(B,T,H) accumulators, one per head group), rowsum / colsum [B,C,T] (C = L*H) masked sums
+// (G = contacts_head_groups(B ceil(T/128)^2, H) accumulators, one per head group), rowsum / colsum [B,C,T] (C = L*H) masked sums
 // of every channel; rowp [B, ceil(T/128), H, T] and colp [B, ceil(T/32), H, T] are per-layer scratch.
-int contacts_head_groups(int B, int T, int H, int head_dim);
+// pairs: (128-query block, 128-key chunk) pairs of the batch, B ceil(T/128)^2 padded (see contacts.hip)
+int contacts_head_groups(long long pairs, int H, int head_dim);
 hipError_t launch_contacts_fused_layer(const void* q, const void* k, const float* lse, const float* key_bias,
                                        const int64_t* tokens, const float* wreg, float* acc, float* rowsum,
                                        float* colsum, float* rowp, float* colp, int B, int H, int T, int C, int layer,
@@ -194,6 +195,46 @@ hipError_t launch_contacts_fused_final(const float* acc, float* rowsum, const fl
                                        const int64_t* tokens, const float* wreg, const float* bias, float* out,
                                        int B, int H, int C, int T, int head_dim, int pad_idx, int eos_idx,
                                        int prepend_bos, int append_eos, hipStream_t st);
+
+// Token-packed batch with contacts (esmk_forward_packed_ex).  Only segments with S = len - bos - eos > 0 get work
+// and scratch.  Per segment s, element offsets off[4s..4s+3] (int64) into: one head group's accumulator (the G
+// accumulators are [G][sum len^2]), rowp ([ceil(len/128), H, len] per segment), colp ([ceil(len/32), H, len]), and
+// the ragged output (segment s's [S_s,S_s] map at sum_{s'<s} S_s'^2).  rowsum / colsum are [C, len] at C * (first
+// row of s), wt [n_seg, C].  The work lists of the four kernels follow the offsets in one int32 table:
+//   off [n_seg][8 int32] | accumulate [n_acc][4] (segment, key chunk, query block, 0), longest segments first |
+//   reduce [n_red][2] (segment, 256-row block) | rt [n_rt] (segment) | final [n_fin][4] (segment, tile i, tile j, 0)
+struct CtSegs {  // kernel argument of the packed contact kernels
+    const int* seg = nullptr;        // [n_seg][2] (first row, length)
+    const long long* off = nullptr;  // [n_seg][4]
+    const int* work = nullptr;       // this launch's work list
+    long long acc_stride = 0;        // elements of one head-group accumulator: sum of len^2
+    int rows = 0, n_items = 0;       // row space of q / k / lse ([H, rows]); items of `work`
+};
+struct CtPackedPlan {
+    int n_seg = 0, G = 1;
+    long long sum_len2 = 0, rowp = 0, colp = 0, out = 0;  // elements
+    long long n_acc = 0, n_red = 0, n_rt = 0, n_fin = 0;  // work items
+    size_t table_ints() const { return 8 * (size_t)n_seg + 4 * n_acc + 2 * n_red + n_rt + 4 * n_fin; }
+};
+struct CtPackedDev {  // the table above on the device
+    const int* seg = nullptr;
+    const long long* off = nullptr;
+    const int *acc_work = nullptr, *red_work = nullptr, *rt_work = nullptr, *fin_work = nullptr;
+    int rows = 0;
+};
+CtPackedPlan contacts_packed_plan(const int32_t* seg, int n_seg, int H, int head_dim, int bos, int eos);
+// dst: plan.table_ints() int32, 8-byte aligned
+void contacts_packed_tables(const CtPackedPlan& p, const int32_t* seg, int bos, int eos, int H, int32_t* dst);
+hipError_t launch_contacts_packed_layer(const void* q, const void* k, const float* lse, const float* key_bias,
+                                        const int64_t* tokens, const float* wreg, float* acc, float* rowsum,
+                                        float* colsum, float* rowp, float* colp, const CtPackedPlan& p,
+                                        const CtPackedDev& d, int H, int C, int layer, int head_dim, int pad_idx,
+                                        int eos_idx, int prepend_bos, int append_eos, int operand_dtype,
+                                        hipStream_t st);
+hipError_t launch_contacts_packed_final(const float* acc, float* rowsum, const float* colsum, float* wt,
+                                        const int64_t* tokens, const float* wreg, const float* bias, float* out,
+                                        const CtPackedPlan& p, const CtPackedDev& d, int C, int pad_idx, int eos_idx,
+                                        int prepend_bos, int append_eos, hipStream_t st);
 
 // token-packed batch (esmk_forward_packed): per-row bookkeeping of the packed row space.  Segment s occupies
 // rows [seg[2s], seg[2s] + seg[2s+1]); rows outside every segment are gaps.
@@ -217,12 +258,13 @@ struct AttnSegs {
     const int* work = nullptr;
     const int* npad = nullptr;
 };
+// lse: nullptr, or [H, rows] row log-sum-exp (log2 domain) for the packed contact kernels
 hipError_t launch_attention_packed(const void* q, const void* k, const void* vt, const float* key_bias, void* ctx,
-                                   int H, int rows, int Tp, AttnSegs segs, int n_items, int operand_dtype,
+                                   float* lse, int H, int rows, int Tp, AttnSegs segs, int n_items, int operand_dtype,
                                    hipStream_t st);
 hipError_t launch_attention128_packed(const void* q, const void* k, const void* vt, const float* key_bias, void* ctx,
-                                      int H, int rows, int Tp, AttnSegs segs, int n_items, int operand_dtype,
-                                      hipStream_t st);
+                                      float* lse, int H, int rows, int Tp, AttnSegs segs, int n_items,
+                                      int operand_dtype, hipStream_t st);
 hipError_t launch_attention(const void* q, const void* k, const void* vt, const float* key_bias,
                             const int* seq_info, void* ctx, float* lse, int B, int H, int T, int Tp,
                             int operand_dtype, hipStream_t st);

@@ -311,6 +311,12 @@ class _Engine:
         self.fingerprint = fp
         return repacked
 
+    def workspace_for_bytes(self, n):
+        if self.workspace is None or self.workspace.numel() < n:
+            self.workspace = None
+            self.workspace = torch.empty(n, dtype=torch.uint8, device=self.device)
+        return self.workspace
+
     def workspace_for(self, B, T, flags):
         N = self.N
         need = ctypes.c_size_t()
@@ -503,8 +509,10 @@ class ESM2(nn.Module):
     # token-packed batches: no compute on padding (include/esmk.h, esmk_forward_packed)
     supports_varlen = True  # ESM-2 (all sizes) and ESM-1b / ESM-1v; the MSA Transformer has no such path
     supports_contacts_only = True  # forward(contacts_only=True): contact maps without the attention tensor
+    supports_varlen_contacts = True  # forward_varlen(contacts_only=True / return_contacts=True): packed contact maps
 
-    def forward_varlen(self, tokens, repr_layers=[], lengths=None, min_saving=0.08, unpack=True):
+    def forward_varlen(self, tokens, repr_layers=[], lengths=None, min_saving=0.08, unpack=True, return_contacts=False,
+                       contacts_only=False):
         """Same results as ``forward(tokens, repr_layers)`` on the non-pad positions of a RIGHT-padded batch
         (what ``BatchConverter`` yields, reference esm/data.py:262-297), but the sequences are laid back to back
         in one row space and the engine does no work on padding.  Pad positions of the returned tensors are zero
@@ -515,8 +523,12 @@ class ESM2(nn.Module):
         min_saving  fall back to ``forward`` when packing saves less than this fraction of the rows
                     (None: always pack)
         unpack   False: return the packed tensors ([rows, .]) plus ``segments`` ([B,2] first row, length)
+        return_contacts  also return "contacts" (predict_contacts' maps, accumulated per segment without the attention
+                    tensor); ``contacts_only`` as in ``forward``: contacts and representations, no logits.  unpack=True:
+                    [B, T-2, T-2] like ``forward(contacts_only=True)``, sequence b's map in the top-left [S_b, S_b] block
+                    (S_b = its length - 2), zeros elsewhere; unpack=False: a list of per-sequence [S_b, S_b] views.
 
-        Attention maps and contacts are per-sequence [T,T] objects: use ``forward`` for those."""
+        Attention maps are per-sequence [T,T] objects: use ``forward`` for those."""
         assert tokens.ndim == 2
         from . import _native as N
         from .packing import pack_plan
@@ -528,9 +540,17 @@ class ESM2(nn.Module):
         dev = w.device
         B, T = tokens.shape
         L, E, V = self.num_layers, self.embed_dim, self.alphabet_size
+        if contacts_only:
+            return_contacts = True
         plan = pack_plan(tokens, self.padding_idx, lengths)
         if unpack and ((min_saving is not None and plan.rows > (1.0 - min_saving) * B * T) or _weight_split() == 4):
-            return self.forward(tokens.to(dev), repr_layers=repr_layers)  # (f16x3 has no token-packed form)
+            # (f16x3 has no token-packed form)
+            if return_contacts:
+                out = self.forward(tokens.to(dev), repr_layers=repr_layers, contacts_only=True)
+                if not contacts_only:
+                    out = dict(self.forward(tokens.to(dev), repr_layers=repr_layers), contacts=out["contacts"])
+                return out
+            return self.forward(tokens.to(dev), repr_layers=repr_layers)
         repr_set = sorted({int(i) for i in repr_layers if 0 <= int(i) <= L})
         with torch.cuda.device(dev):
             eng = self._engine_ready(dev)
@@ -538,25 +558,54 @@ class ESM2(nn.Module):
             flat = plan.pack(tokens, self.padding_idx, idx)
             f32 = dict(dtype=torch.float32, device=dev)
             lowp = _native_lowp(w.dtype, eng.operand_dtype) and bool(repr_set)
-            pflags = N.OUT_LOGITS | (N.OUT_REPR_LOWP if lowp else 0)
-            logits = torch.empty((plan.rows, V), **f32)
+            pflags = (0 if contacts_only else N.OUT_LOGITS) | (N.OUT_REPR_LOWP if lowp else 0)
+            logits = None if contacts_only else torch.empty((plan.rows, V), **f32)
             reps = [torch.empty((plan.rows, E), dtype=w.dtype if lowp else torch.float32, device=dev) for _ in repr_set]
-            ws = eng.workspace_for_packed(B, plan.rows, pflags)
             seg = plan.segments  # int32 [B,2], CPU, contiguous
+            seg_ptr = ctypes.cast(seg.data_ptr(), ctypes.POINTER(ctypes.c_int32))
             layers_arr = (ctypes.c_int32 * max(1, len(repr_set)))(*repr_set)
             outs_arr = (ctypes.c_void_p * max(1, len(repr_set)))(*[r.data_ptr() for r in reps])
-            N.check(N.lib.esmk_forward_packed(
-                eng.handle, N.ptr(eng.packed), N.ptr(flat),
-                ctypes.cast(seg.data_ptr(), ctypes.POINTER(ctypes.c_int32)), B, plan.rows,
-                layers_arr, len(repr_set), outs_arr, pflags, N.ptr(logits), N.ptr(ws), ws.numel(),
-                N.cur_stream()))
+            if return_contacts:
+                pflags |= N.OUT_CONTACTS
+                # ragged fp32 maps: sequence b's [S_b, S_b] block at sum_{b'<b} S_b'^2 (include/esmk.h)
+                S = (plan.lengths.cpu().to(torch.int64) - int(self.prepend_bos) - int(self.append_eos)).clamp(min=0)
+                sq = S * S
+                flat_ct = torch.empty((max(1, int(sq.sum())),), **f32)
+                need = ctypes.c_size_t()
+                N.check(N.lib.esmk_packed_workspace_bytes_ex(eng.handle, seg_ptr, B, plan.rows, pflags,
+                                                             ctypes.byref(need)))
+                ws = eng.workspace_for_bytes(need.value)
+                N.check(N.lib.esmk_forward_packed_ex(
+                    eng.handle, N.ptr(eng.packed), N.ptr(flat), seg_ptr, B, plan.rows, layers_arr, len(repr_set),
+                    outs_arr, pflags, N.ptr(logits), N.ptr(flat_ct), N.ptr(ws), ws.numel(), N.cur_stream()))
+            else:
+                ws = eng.workspace_for_packed(B, plan.rows, pflags)
+                N.check(N.lib.esmk_forward_packed(
+                    eng.handle, N.ptr(eng.packed), N.ptr(flat), seg_ptr, B, plan.rows,
+                    layers_arr, len(repr_set), outs_arr, pflags, N.ptr(logits), N.ptr(ws), ws.numel(),
+                    N.cur_stream()))
         out_dt = w.dtype
         cast = lambda t: t if t.dtype == out_dt else t.to(out_dt)
         if not unpack:
-            return {"logits": cast(logits), "representations": {l: cast(r) for l, r in zip(repr_set, reps)},
-                    "segments": seg}
-        un = lambda t: plan.unpack(t, idx, keep)
-        return {"logits": cast(un(logits)), "representations": {l: cast(un(r)) for l, r in zip(repr_set, reps)}}
+            out = {"representations": {l: cast(r) for l, r in zip(repr_set, reps)}, "segments": seg}
+        else:
+            un = lambda t: plan.unpack(t, idx, keep)
+            out = {"representations": {l: cast(un(r)) for l, r in zip(repr_set, reps)}}
+        if logits is not None:
+            out["logits"] = cast(logits) if not unpack else cast(un(logits))
+        if return_contacts:
+            flat_ct = cast(flat_ct)
+            offs = [0] + torch.cumsum(sq, 0).tolist()
+            views = [flat_ct[offs[b]:offs[b + 1]].view(int(S[b]), int(S[b])) for b in range(B)]
+            if unpack:
+                St = max(T - int(self.prepend_bos) - int(self.append_eos), 0)
+                contacts = torch.zeros((B, St, St), dtype=flat_ct.dtype, device=dev)
+                for b, v in enumerate(views):
+                    contacts[b, :v.shape[0], :v.shape[1]] = v
+                out["contacts"] = contacts
+            else:
+                out["contacts"] = views
+        return out
 
     def profile_begin(self):
         """Arm per-kernel-class HIP-event timing of the following forward calls (bench.py)."""

@@ -353,12 +353,16 @@ def extract(dataset, alphabet, embed_fn: Callable[[torch.Tensor, List[int], bool
 
 def make_embed_fn(model, varlen: bool = True):
     """The ``embed_fn`` of :func:`extract` for an engine model: token-packed batches (no compute on padding)
-    where the model has them and no contact maps are asked for (those are per-sequence [T,T]: padded path)."""
+    where the model has them — with contact maps too where it has packed contacts (``supports_varlen_contacts``);
+    otherwise contacts take the padded path."""
+    varlen_ct = varlen and getattr(model, "supports_varlen_contacts", False)
     varlen = varlen and getattr(model, "supports_varlen", False)
 
     def embed_fn(toks, layers, return_contacts, lengths=None):
         if varlen and not return_contacts:
             return model.forward_varlen(toks, repr_layers=layers, lengths=lengths)
+        if return_contacts and varlen_ct:
+            return model.forward_varlen(toks, repr_layers=layers, lengths=lengths, contacts_only=True)
         if return_contacts and getattr(model, "supports_contacts_only", False):
             # only the map is kept (scripts/extract.py:104-131 never looks at "attentions" / "logits")
             return model(toks, repr_layers=layers, contacts_only=True)

@@ -147,12 +147,28 @@ int esmk_forward(esmk_model* m, const void* packed_dev, const int64_t* tokens_de
  *   segments_host   int32 [n_seg][2] on the HOST (first row, length incl. <cls>/<eos>)
  *   repr_out_dev[i] fp32 [rows,E]; logits_out_dev fp32 [rows,V] (iff ESMK_OUT_LOGITS); gap rows are undefined
  * ESM-1b / ESM-1v handles work the same way (learned positions restart at each segment, esm/modules.py:240-257).
- * Attention maps / contacts are [T,T] per sequence and stay with esmk_forward: those flags fail with an error. */
+ * esmk_packed_workspace_bytes / esmk_forward_packed refuse ESMK_OUT_ATTN and ESMK_OUT_CONTACTS: attention maps stay
+ * with esmk_forward, contacts of a packed batch take the _ex entries below. */
 int esmk_packed_workspace_bytes(const esmk_model* m, int n_seg, int rows, uint32_t out_flags, size_t* bytes);
 int esmk_forward_packed(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev,
                         const int32_t* segments_host, int n_seg, int rows, const int32_t* repr_layers,
                         int n_repr, void* const* repr_out_dev, uint32_t out_flags, void* logits_out_dev,
                         void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The same with contact maps (ESMK_OUT_CONTACTS, predict_contacts' formula, no attention tensor): every segment's map
+ * is the one esmk_forward(ESMK_OUT_CONTACTS) gives that sequence alone.  The workspace grows with sum(len^2) instead
+ * of B*Tmax^2, so its size takes the segment table.  Accepted flags: ESMK_OUT_LOGITS (optional), ESMK_OUT_REPR_LOWP,
+ * ESMK_OUT_CONTACTS; ESMK_OUT_ATTN / ESMK_OUT_ATTN_LOWP fail (attention maps stay padded-only), as does an MSA handle
+ * or the f16x3 precision mode.  Without ESMK_OUT_CONTACTS both behave as the entries above.
+ *   contacts_out_dev fp32, ragged: with S_s = len_s - prepend_bos - append_eos, segment s's [S_s,S_s] map is row-major
+ *                    at element offset sum_{s'<s} max(S_s',0)^2 (segments with S_s <= 0 have an empty map); required
+ *                    iff ESMK_OUT_CONTACTS, even when every map is empty */
+int esmk_packed_workspace_bytes_ex(const esmk_model* m, const int32_t* segments_host, int n_seg, int rows,
+                                   uint32_t out_flags, size_t* bytes);
+int esmk_forward_packed_ex(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev,
+                           const int32_t* segments_host, int n_seg, int rows, const int32_t* repr_layers,
+                           int n_repr, void* const* repr_out_dev, uint32_t out_flags, void* logits_out_dev,
+                           void* contacts_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- MSA Transformer (reference esm/model/msa_transformer.py:20-238, esm/axial_attention.py) -------- */
 

@@ -7,6 +7,9 @@ fill up to toks_per_batch) or in file order (--unsorted; what a streaming servic
 per second (pad positions do not count) for model.forward and model.forward_varlen on the same batches.
 
   python tools/bench_varlen.py --model 650M --n 2048 --toks-per-batch 65536
+  python tools/bench_varlen.py --model 650M --contacts [--unsorted]   # contact maps: forward(contacts_only=True)
+                                                                       # vs forward_varlen(contacts_only=True)
+With --contacts the engine workspace each path grew to (its peak over the batches) is reported as well.
 """
 import argparse
 import os
@@ -44,6 +47,7 @@ def main():
     ap.add_argument("--toks-per-batch", type=int, default=65536)
     ap.add_argument("--unsorted", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--contacts", action="store_true", help="time the contact-map paths instead of the logits ones")
     args = ap.parse_args()
     name = next(k for k in ESM2_DIMS if k == args.model or k.split("_")[2] == args.model)
     L, E, H = ESM2_DIMS[name]
@@ -79,6 +83,21 @@ def main():
             torch.cuda.synchronize()
         return time.perf_counter() - t0
 
+    if args.contacts:
+        def peak(fn):
+            if model._engine is not None:
+                model._engine.workspace = None  # each path grows its own workspace from empty
+            torch.cuda.empty_cache()
+            t = run(fn)
+            return t, model._engine.workspace.numel()
+
+        t_pad, w_pad = peak(lambda t: model(t.cuda(), repr_layers=[L], contacts_only=True))
+        t_var, w_var = peak(lambda t: model.forward_varlen(t, repr_layers=[L], contacts_only=True, min_saving=None))
+        print("contacts padded  forward(contacts_only)        : %8.1f ms  %9.0f real residues/s  workspace %6.0f MiB" % (
+            t_pad * 1e3, real / t_pad, w_pad / 2**20))
+        print("contacts packed  forward_varlen(contacts_only) : %8.1f ms  %9.0f real residues/s  workspace %6.0f MiB  (%.2fx)" % (
+            t_var * 1e3, real / t_var, w_var / 2**20, t_pad / t_var))
+        return
     t_pad = run(lambda t: model(t.cuda(), repr_layers=[L]))
     t_var = run(lambda t: model.forward_varlen(t, repr_layers=[L]))
     t_raw = run(lambda t: model.forward_varlen(t, repr_layers=[L], unpack=False))
