@@ -153,6 +153,14 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
          c_int, c_int, c_void_p],
     ),
+    "esmk_op_contacts_fused_workspace_bytes_ex": (
+        c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int32), c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "esmk_op_contacts_fused_ex": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_int, c_void_p,
+         c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int),
+         c_int, c_void_p],
+    ),
     "esmk_op_contacts": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

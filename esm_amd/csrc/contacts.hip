@@ -1094,10 +1094,10 @@ hipError_t launch_contacts_fused_layer(const void* q, const void* k, const float
                                        const int64_t* tokens, const float* wreg, float* acc, float* rowsum,
                                        float* colsum, float* rowp, float* colp, int B, int H, int T, int C, int layer,
                                        int head_dim, int pad_idx, int eos_idx, int prepend_bos, int append_eos,
-                                       int operand_dtype, hipStream_t st) {
+                                       int operand_dtype, hipStream_t st, int G_force) {
     const int bos = prepend_bos ? 1 : 0, eos = append_eos ? 1 : 0;
     const long long nQ = (T + 127) / 128;
-    const int G = contacts_head_groups((long long)B * nQ * nQ, H, head_dim);
+    const int G = G_force > 0 ? G_force : contacts_head_groups((long long)B * nQ * nQ, H, head_dim);
     hipError_t e;
     if (operand_dtype == ESMK_DT_BF16) {
         e = head_dim == 128 ? launch_accum<__bf16, 128>(q, k, lse, key_bias, tokens, wreg, acc, rowp, colp, B, H, T, layer,
@@ -1121,7 +1121,7 @@ hipError_t launch_contacts_fused_layer(const void* q, const void* k, const float
 hipError_t launch_contacts_fused_final(const float* acc, float* rowsum, const float* colsum, float* wt,
                                        const int64_t* tokens, const float* wreg, const float* bias, float* out,
                                        int B, int H, int C, int T, int head_dim, int pad_idx, int eos_idx,
-                                       int prepend_bos, int append_eos, hipStream_t st) {
+                                       int prepend_bos, int append_eos, hipStream_t st, int G_force) {
     const int bos = prepend_bos ? 1 : 0, eos = append_eos ? 1 : 0;
     const int S = T - bos - eos;
     if (S <= 0) return hipErrorInvalidValue;
@@ -1132,7 +1132,8 @@ hipError_t launch_contacts_fused_final(const float* acc, float* rowsum, const fl
     const int nt = (S + 31) / 32;
     const long long nQ = (T + 127) / 128;
     hipLaunchKernelGGL(contact_final_kernel, dim3(nt, nt, B), dim3(256), 0, st, acc, rowsum, wt, tokens, bias, out, B,
-                       contacts_head_groups((long long)B * nQ * nQ, H, head_dim), C, T, pad_idx, eos_idx, bos, eos);
+                       G_force > 0 ? G_force : contacts_head_groups((long long)B * nQ * nQ, H, head_dim), C, T, pad_idx,
+                       eos_idx, bos, eos);
     return hipGetLastError();
 }
 

@@ -1503,6 +1503,158 @@ int esmk_op_attention_probs_ex(const void* q_dev, const void* k_dev, const float
     return 0;
 }
 
+// Contact pipeline of the fused path (contacts.hip) on caller-supplied q, k and lse, stacked over layers
+// (tests/test_contacts_kernels_gpu.py).  Validation and planning shared by the two entries below; the launches are
+// the engine's own.  Packed form (seg != NULL): B = 1, T = rows; segments may leave gaps, start anywhere, come in any
+// order and be empty, but must not overlap.  G: 0 = the engine's head-group count, else a forced one, raised to the
+// count whose groups all hold a head (ceil(H / ceil(H / G))).
+struct CtOpLayout {
+    int G = 0;
+    CtPackedPlan plan;
+    size_t acc = 0, row = 0, col = 0, rowp = 0, colp = 0, wt = 0, tables = 0, total = 0;
+    size_t ct_base = 0, n_int = 0;  // packed: int32 slot of the contact tables, int32 slots uploaded
+};
+
+static int contacts_op_plan(const char* who, int B, int H, int T, int L, int head_dim, const int32_t* seg, int n_seg,
+                            int prepend_bos, int append_eos, int G_req, CtOpLayout* lay) {
+    const std::string w(who);
+    if (B <= 0 || H <= 0 || T <= 0 || L <= 0) return fail(w + ": B, H, T and num_layers must be positive");
+    if (head_dim != 64 && head_dim != 128) return fail(w + ": head_dim must be 64 or 128");
+    if ((prepend_bos != 0 && prepend_bos != 1) || (append_eos != 0 && append_eos != 1))
+        return fail(w + ": prepend_bos and append_eos must be 0 or 1");
+    if ((long long)B * T > ESMK_MAX_ROWS) return fail(w + ": B*T exceeds 2^24 rows");
+    if ((long long)L * H > (1 << 20)) return fail(w + ": num_layers * H is too large");
+    if (G_req < 0 || G_req > H) return fail(w + ": head_groups must be 0 (engine's choice) or in [1, H]");
+    if (G_req > 0 && head_dim == 128 && (H + G_req - 1) / G_req > 20)
+        return fail(w + ": head_dim 128 takes at most 20 heads per group");
+    const size_t C = (size_t)L * H;
+    Carve c;
+    if (seg == nullptr) {
+        if (n_seg != 0) return fail(w + ": n_seg without a segment table");
+        if (T - prepend_bos - append_eos <= 0) return fail(w + ": no contact map: T - prepend_bos - append_eos <= 0");
+        const long long nQ = (T + 127) / 128;
+        lay->G = contacts_head_groups((long long)B * nQ * nQ, H, head_dim);
+        if (G_req > 0) {
+            const int hg = (H + G_req - 1) / G_req;
+            lay->G = (H + hg - 1) / hg;
+        }
+        lay->acc = c.take((size_t)lay->G * B * T * T * 4);
+        lay->row = c.take((size_t)B * C * T * 4);
+        lay->col = c.take((size_t)B * C * T * 4);
+        lay->rowp = c.take((size_t)B * nQ * H * T * 4);
+        lay->colp = c.take((size_t)B * ((T + 31) / 32) * H * T * 4);
+        lay->wt = c.take((size_t)B * C * 4);
+    } else {
+        if (B != 1) return fail(w + ": the packed form takes B = 1 (T = rows)");
+        if (n_seg <= 0) return fail(w + ": n_seg must be positive");
+        std::vector<std::pair<long long, long long>> span;
+        for (int s = 0; s < n_seg; ++s) {
+            const long long start = seg[2 * s], len = seg[2 * s + 1];
+            if (start < 0 || len < 0 || start + len > T)
+                return fail(w + ": segment table: every segment must lie inside [0, rows)");
+            if (len > 0) span.emplace_back(start, start + len);
+        }
+        std::sort(span.begin(), span.end());
+        for (size_t i = 1; i < span.size(); ++i)
+            if (span[i].first < span[i - 1].second) return fail(w + ": segment table: segments overlap");
+        lay->plan = contacts_packed_plan(seg, n_seg, H, head_dim, prepend_bos, append_eos);
+        if (G_req > 0) {
+            const int hg = (H + G_req - 1) / G_req;
+            lay->plan.G = (H + hg - 1) / hg;
+        }
+        lay->G = lay->plan.G;
+        const CtPackedPlan& p = lay->plan;
+        lay->acc = c.take((size_t)p.G * p.sum_len2 * 4);
+        lay->row = c.take(C * T * 4);
+        lay->col = c.take(C * T * 4);
+        lay->rowp = c.take((size_t)p.rowp * 4);
+        lay->colp = c.take((size_t)p.colp * 4);
+        lay->wt = c.take((size_t)n_seg * C * 4);
+        lay->ct_base = ((size_t)2 * n_seg + 1) & ~(size_t)1;  // [seg 2 n_seg] | contact tables (8-byte aligned)
+        lay->n_int = lay->ct_base + p.table_ints();
+        lay->tables = c.take(lay->n_int * 4);
+    }
+    lay->total = c.off;
+    return 0;
+}
+
+int esmk_op_contacts_fused_workspace_bytes_ex(int B, int H, int T, int num_layers, int head_dim,
+                                              const int32_t* segments_host, int n_seg, int prepend_bos, int append_eos,
+                                              int head_groups, size_t* bytes) {
+    if (!bytes) return fail("esmk_op_contacts_fused_workspace_bytes_ex: null argument");
+    CtOpLayout lay;
+    if (contacts_op_plan("esmk_op_contacts_fused_workspace_bytes_ex", B, H, T, num_layers, head_dim, segments_host,
+                         n_seg, prepend_bos, append_eos, head_groups, &lay))
+        return 1;
+    *bytes = lay.total;
+    return 0;
+}
+
+int esmk_op_contacts_fused_ex(const void* q_dev, const void* k_dev, const float* lse_dev, const float* key_bias_dev,
+                              const int64_t* tokens_dev, const float* w_dev, const float* b_dev,
+                              const int32_t* segments_host, int n_seg, float* out_dev, void* workspace_dev,
+                              size_t workspace_bytes, int B, int H, int T, int num_layers, int head_dim, int pad_idx,
+                              int eos_idx, int prepend_bos, int append_eos, int head_groups, int* head_groups_used,
+                              int operand_dtype, void* stream) {
+    const char* who = "esmk_op_contacts_fused_ex";
+    if (!q_dev || !k_dev || !lse_dev || !tokens_dev || !w_dev || !out_dev || !workspace_dev)
+        return fail("esmk_op_contacts_fused_ex: null argument");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_contacts_fused_ex: operand_dtype must be fp16 or bf16");
+    CtOpLayout lay;
+    if (contacts_op_plan(who, B, H, T, num_layers, head_dim, segments_host, n_seg, prepend_bos, append_eos,
+                         head_groups, &lay))
+        return 1;
+    if (workspace_bytes < lay.total) return fail("esmk_op_contacts_fused_ex: workspace too small");
+    if (head_groups_used) *head_groups_used = lay.G;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace_dev;
+    const int L = num_layers, C = L * H;
+    const size_t os = op_size(operand_dtype);
+    // one layer of q / k: [B, H, T, D] padded, [H, rows, D] packed (B = 1, T = rows): the same stride
+    const size_t qk_layer = (size_t)B * H * T * head_dim * os, lse_layer = (size_t)B * H * T;
+    float* acc = (float*)(ws + lay.acc);
+    float* row = (float*)(ws + lay.row);
+    float* col = (float*)(ws + lay.col);
+    float* rowp = (float*)(ws + lay.rowp);
+    float* colp = (float*)(ws + lay.colp);
+    float* wt = (float*)(ws + lay.wt);
+    if (segments_host == nullptr) {
+        for (int l = 0; l < L; ++l)
+            ESMK_TRY(launch_contacts_fused_layer((const char*)q_dev + l * qk_layer, (const char*)k_dev + l * qk_layer,
+                                                 lse_dev + l * lse_layer, key_bias_dev, tokens_dev, w_dev, acc, row,
+                                                 col, rowp, colp, B, H, T, C, l, head_dim, pad_idx, eos_idx,
+                                                 prepend_bos, append_eos, operand_dtype, st, lay.G));
+        ESMK_TRY(launch_contacts_fused_final(acc, row, col, wt, tokens_dev, w_dev, b_dev, out_dev, B, H, C, T, head_dim,
+                                             pad_idx, eos_idx, prepend_bos, append_eos, st, lay.G));
+        return 0;
+    }
+    // the segment table and the contact tables, uploaded as esmk_forward_packed_ex does (tables behind the workspace)
+    std::vector<int32_t> host(lay.n_int, 0);
+    memcpy(host.data(), segments_host, (size_t)2 * n_seg * 4);
+    contacts_packed_tables(lay.plan, segments_host, prepend_bos, append_eos, H, host.data() + lay.ct_base);
+    int* tab = (int*)(ws + lay.tables);
+    ESMK_TRY(hipMemcpyAsync(tab, host.data(), lay.n_int * 4, hipMemcpyHostToDevice, st));
+    ESMK_TRY(hipStreamSynchronize(st));  // `host` goes out of scope below
+    const CtPackedPlan& p = lay.plan;
+    CtPackedDev d;
+    d.seg = tab;
+    d.off = reinterpret_cast<const long long*>(tab + lay.ct_base);
+    d.acc_work = tab + lay.ct_base + 8 * (size_t)n_seg;
+    d.red_work = d.acc_work + 4 * p.n_acc;
+    d.rt_work = d.red_work + 2 * p.n_red;
+    d.fin_work = d.rt_work + p.n_rt;
+    d.rows = T;
+    for (int l = 0; l < L; ++l)
+        ESMK_TRY(launch_contacts_packed_layer((const char*)q_dev + l * qk_layer, (const char*)k_dev + l * qk_layer,
+                                              lse_dev + l * lse_layer, key_bias_dev, tokens_dev, w_dev, acc, row, col,
+                                              rowp, colp, p, d, H, C, l, head_dim, pad_idx, eos_idx, prepend_bos,
+                                              append_eos, operand_dtype, st));
+    ESMK_TRY(launch_contacts_packed_final(acc, row, col, wt, tokens_dev, w_dev, b_dev, out_dev, p, d, C, pad_idx,
+                                          eos_idx, prepend_bos, append_eos, st));
+    return 0;
+}
+
 int esmk_op_contacts(const float* attn_dev, const int64_t* tokens_dev, const float* w_dev,
                      const float* b_dev, float* scratch_dev, float* out_dev, int B, int C, int T,
                      int eos_idx, int prepend_bos, int append_eos, void* stream) {

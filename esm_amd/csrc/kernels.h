@@ -189,12 +189,14 @@ hipError_t launch_contacts_fused_layer(const void* q, const void* k, const float
                                        const int64_t* tokens, const float* wreg, float* acc, float* rowsum,
                                        float* colsum, float* rowp, float* colp, int B, int H, int T, int C, int layer,
                                        int head_dim, int pad_idx, int eos_idx, int prepend_bos, int append_eos,
-                                       int operand_dtype, hipStream_t st);
+                                       int operand_dtype, hipStream_t st, int G = 0);
 // after the last layer: rowsum becomes r_c (in place), wt [B,C] = w_c / t_c, out [B,S,S] = sigmoid(logits)
+// G: 0 = contacts_head_groups(); otherwise the head-group count the layers ran with (esmk_op_contacts_fused_ex), which
+// must hold a head in every group: G == ceil(H / ceil(H / G))
 hipError_t launch_contacts_fused_final(const float* acc, float* rowsum, const float* colsum, float* wt,
                                        const int64_t* tokens, const float* wreg, const float* bias, float* out,
                                        int B, int H, int C, int T, int head_dim, int pad_idx, int eos_idx,
-                                       int prepend_bos, int append_eos, hipStream_t st);
+                                       int prepend_bos, int append_eos, hipStream_t st, int G = 0);
 
 // Token-packed batch with contacts (esmk_forward_packed_ex).  Only segments with S = len - bos - eos > 0 get work
 // and scratch.  Per segment s, element offsets off[4s..4s+3] (int64) into: one head group's accumulator (the G

@@ -170,6 +170,56 @@ def contacts(attn, tokens, w, b, eos_idx=2, prepend_bos=True, append_eos=True):
     return out
 
 
+def contacts_fused(q, k, lse, tokens, w, b=None, key_bias=None, segments=None, pad_idx=1, eos_idx=2,
+                   prepend_bos=True, append_eos=True, head_groups=0, workspace=None, out=None):
+    """Contact maps of predict_contacts through the fused kernels (csrc/contacts.hip), the layers' q, k and lse given.
+
+    Padded: q, k [L,B,H,T,D], lse [L,B,H,T], key_bias fp32 [B,T] (0 / -inf) or None, tokens int64 [B,T] -> [B,S,S].
+    Packed: segments = int32 [n_seg,2] (first row, length) on the host; q, k [L,H,rows,D], lse [L,H,rows], key_bias
+    [rows], tokens [rows] -> the ragged fp32 buffer (each segment with S > 0, in table order, flattened).
+    q in the LOG2 domain (``to_log2_domain``); lse the NATURAL-log row log-sum-exp (as ``attention`` returns it),
+    converted here as fp32(lse * log2 e) in fp64.  w fp32 [L*H], b fp32 [1].  head_groups: 0 = the engine's choice.
+    workspace: optional uint8 buffer of at least the queried size (a caller may pre-fill it).
+    Returns (maps, head groups used)."""
+    _req_cuda(q, k, tokens, w, b, key_bias, workspace, out)
+    D = q.shape[-1]
+    assert q.dtype == k.dtype and q.shape == k.shape and tokens.dtype == torch.int64
+    lse2 = (lse.double() * LOG2E).float().contiguous()
+    L = q.shape[0]
+    bos, eos = int(prepend_bos), int(append_eos)
+    if segments is None:
+        _, B, H, T, _ = q.shape
+        seg_p, n_seg = None, 0
+        n_out = B * (T - bos - eos) ** 2
+    else:
+        _, H, T, _ = q.shape
+        B = 1
+        seg = torch.as_tensor(segments, dtype=torch.int32).reshape(-1, 2).contiguous().cpu()
+        n_seg = seg.shape[0]
+        seg_p = ctypes.cast(seg.data_ptr(), ctypes.POINTER(ctypes.c_int32))
+        n_out = sum(max(int(n) - bos - eos, 0) ** 2 for n in seg[:, 1].tolist())
+    assert lse2.numel() == q.numel() // D
+    n = ctypes.c_size_t()
+    N.check(N.lib.esmk_op_contacts_fused_workspace_bytes_ex(B, H, T, L, D, seg_p, n_seg, bos, eos, head_groups,
+                                                           ctypes.byref(n)))
+    if workspace is None:
+        workspace = torch.empty(max(n.value, 1), dtype=torch.uint8, device=q.device)
+    assert workspace.numel() >= n.value
+    if out is None:
+        out = torch.empty(n_out, dtype=torch.float32, device=q.device)
+    assert out.dtype == torch.float32 and out.numel() >= n_out
+    used = ctypes.c_int(0)
+    N.check(N.lib.esmk_op_contacts_fused_ex(N.ptr(q), N.ptr(k), N.ptr(lse2), N.ptr(key_bias), N.ptr(tokens),
+                                            N.ptr(w.reshape(-1)), N.ptr(b), seg_p, n_seg, N.ptr(out),
+                                            N.ptr(workspace), workspace.numel(), B, H, T, L, D, pad_idx, eos_idx, bos,
+                                            eos, head_groups, ctypes.byref(used), N.dtype_code(q.dtype),
+                                            N.cur_stream()))
+    if segments is None:
+        S = T - bos - eos
+        out = out[:n_out].view(B, S, S)
+    return out, used.value
+
+
 def permute_keys16(t):
     """Key position used by the V^T layout: inside each group of 16 keys the 4-groups 1 and 2
     are swapped (position p holds key perm[p])."""

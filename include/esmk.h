@@ -374,6 +374,29 @@ int esmk_op_attention_probs_ex(const void* q_dev, const void* k_dev, const float
                                const int32_t* any_pad_dev, void* probs_out, int B, int H, int T, int head_dim, int layer,
                                int num_layers_total, int msa_C, int out_dtype, int operand_dtype, void* stream);
 
+/* The fused contact pipeline of predict_contacts (contacts.hip: accumulate + reduce per layer, then rt + final) on
+ * caller-supplied operands, one entry for the padded and the token-packed form.  Inputs are stacked over layers in the
+ * layouts esmk_forward leaves in its workspace:
+ *   padded (segments_host NULL, n_seg 0): q, k [L, B, H, T, head_dim] (q in the log2 domain, as esmk_op_attention takes
+ *     it), lse fp32 [L, B, H, T] (log2 domain), key_bias fp32 [B, T] (0 / -inf) or NULL, tokens int64 [B, T];
+ *     out fp32 [B, S, S], S = T - prepend_bos - append_eos > 0.
+ *   packed (segments_host = int32 [n_seg][2] (first row, length), B = 1, T = rows): q, k [L, H, rows, head_dim], lse
+ *     [L, H, rows], key_bias [rows] or NULL, tokens [rows]; out is the ragged buffer of esmk_forward_packed_ex (each
+ *     segment with S_s > 0 in table order, [S_s, S_s] at sum of the previous S^2).  Segments may leave gaps, start at
+ *     any row, come in any order and be empty; they must not overlap.
+ * w fp32 [L*H] (contact_head.regression.weight), b fp32 [1] or NULL.  head_groups: 0 = the engine's head-group count,
+ * else 1 <= G <= H (head_dim 128: at most 20 heads per group), raised to ceil(H / ceil(H / G)) so that every group holds
+ * a head; *head_groups_used (optional) receives the count that ran.  Invalid arguments fail before any launch. */
+int esmk_op_contacts_fused_workspace_bytes_ex(int B, int H, int T, int num_layers, int head_dim,
+                                              const int32_t* segments_host, int n_seg, int prepend_bos, int append_eos,
+                                              int head_groups, size_t* bytes);
+int esmk_op_contacts_fused_ex(const void* q_dev, const void* k_dev, const float* lse_dev, const float* key_bias_dev,
+                              const int64_t* tokens_dev, const float* w_dev, const float* b_dev,
+                              const int32_t* segments_host, int n_seg, float* out_dev, void* workspace_dev,
+                              size_t workspace_bytes, int B, int H, int T, int num_layers, int head_dim, int pad_idx,
+                              int eos_idx, int prepend_bos, int append_eos, int head_groups, int* head_groups_used,
+                              int operand_dtype, void* stream);
+
 /* ContactPredictionHead.forward (modules.py:338-357) incl. symmetrize/apc (modules.py:27-41).
  * attn fp32 [B,C=L*H,T,T]; w fp32 [C]; b fp32 [1]; scratch fp32 >= B*C*(T+1) floats;
  * out fp32 [B,T-2,T-2] (crop follows prepend_bos/append_eos). */

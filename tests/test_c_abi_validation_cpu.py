@@ -226,3 +226,67 @@ def test_attention_ex_argument_checks():
     assert probs(msa_C=2, out=f16) != 0 and "fp32" in err()
     assert probs(msa_C=2, head_dim=128, out=N.F32) != 0 and "head_dim 64" in err()
     assert probs(anyp=FAKE, out=N.F32) != 0 and "any_pad" in err()
+
+
+def test_contacts_fused_ex_argument_checks():
+    """esmk_op_contacts_fused_ex / esmk_op_contacts_fused_workspace_bytes_ex: null pointers, head-group overrides out
+    of range, head_dim-128 groups over 20 heads, bad dtypes and inconsistent segment tables are refused before a launch
+    (the buffers are fake)."""
+    f16 = N.dtype_code(torch.float16)
+
+    def seg_arr(pairs):
+        flat = [v for p in pairs for v in p]
+        return (ctypes.c_int32 * max(len(flat), 1))(*flat), len(pairs)
+
+    def run(q=FAKE, lse=FAKE, tok=FAKE, w=FAKE, out=FAKE, ws=FAKE, nbytes=1 << 40, B=2, H=4, T=100, L=2, hd=64, G=0,
+            dt=f16, bos=1, eos=1, seg=None):
+        sp, n = seg_arr(seg) if seg is not None else (None, 0)
+        used = ctypes.c_int(-1)
+        rc = N.lib.esmk_op_contacts_fused_ex(q, FAKE, lse, None, tok, w, None, sp, n, out, ws, nbytes, B, H, T, L, hd,
+                                              1, 2, bos, eos, G, ctypes.byref(used), dt, None)
+        assert rc == 0 or used.value == -1  # a refusal reports nothing
+        return rc
+
+    def size(B=2, H=4, T=100, L=2, hd=64, G=0, bos=1, eos=1, seg=None):
+        sp, n = seg_arr(seg) if seg is not None else (None, 0)
+        nb = ctypes.c_size_t()
+        return N.lib.esmk_op_contacts_fused_workspace_bytes_ex(B, H, T, L, hd, sp, n, bos, eos, G, ctypes.byref(nb)), nb
+
+    for kw in (dict(q=None), dict(lse=None), dict(tok=None), dict(w=None), dict(out=None), dict(ws=None)):
+        assert run(**kw) != 0 and "null" in err(), kw
+    assert N.lib.esmk_op_contacts_fused_workspace_bytes_ex(2, 4, 100, 2, 64, None, 0, 1, 1, 0, None) != 0
+    assert "null" in err()
+    for kw in (dict(B=0), dict(H=0), dict(T=0), dict(L=0)):
+        assert run(**kw) != 0 and "positive" in err(), kw
+    for hd in (32, 96, 256):
+        assert run(hd=hd) != 0 and "head_dim" in err(), hd
+    for dt in (N.F32, 7):
+        assert run(dt=dt) != 0 and "operand_dtype" in err(), dt
+    assert run(bos=2) != 0 and "prepend_bos" in err()
+    assert run(T=2) != 0 and "no contact map" in err()  # S = T - 2 = 0
+    for G in (-1, 5):  # H = 4
+        assert run(G=G) != 0 and "head_groups" in err(), G
+    assert run(hd=128, H=41, G=2) != 0 and "20 heads" in err()  # 21 heads per group
+    assert run(hd=128, H=40, G=1) != 0 and "20 heads" in err()
+    assert run(H=40, G=1, nbytes=0) != 0 and "workspace" in err()  # head_dim 64 takes 40 heads: past the checks
+    rc, nb = size(hd=128, H=40, G=2)
+    assert rc == 0 and nb.value > 0
+    rc, nb = size(hd=128, H=40, G=1)
+    assert rc != 0 and "20 heads" in err()
+    # segment tables
+    for seg, msg in (([(0, 100), (90, 20)], "overlap"), ([(200, 100)], "inside"), ([(-1, 10)], "inside"),
+                     ([(0, -3)], "inside"), ([(10, 20), (0, 11)], "overlap")):
+        assert run(B=1, T=256, seg=seg) != 0 and msg in err(), seg
+        rc, _ = size(B=1, T=256, seg=seg)
+        assert rc != 0 and msg in err(), seg
+    assert run(B=2, T=256, seg=[(0, 10)]) != 0 and "B = 1" in err()
+    sp, _ = seg_arr([(0, 10)])
+    nb = ctypes.c_size_t()
+    assert N.lib.esmk_op_contacts_fused_workspace_bytes_ex(1, 4, 256, 2, 64, sp, 0, 1, 1, 0, ctypes.byref(nb)) != 0
+    assert "n_seg" in err()
+    assert N.lib.esmk_op_contacts_fused_workspace_bytes_ex(1, 4, 256, 2, 64, None, 3, 1, 1, 0, ctypes.byref(nb)) != 0
+    assert "n_seg" in err()
+    # gaps, unsorted, a late first segment and empty segments are a valid table (sized, not run)
+    rc, nb = size(B=1, T=512, seg=[(300, 130), (17, 2), (40, 0), (100, 129), (20, 1)])
+    assert rc == 0 and nb.value > 0
+    assert run(B=1, T=512, seg=[(300, 130), (17, 2)], nbytes=0) != 0 and "workspace" in err()
