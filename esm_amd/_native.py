@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libesmk.so")
 F32, F16, BF16 = 0, 1, 2
 OUT_LOGITS, OUT_ATTN, OUT_CONTACTS, OUT_COL_ATTN, OUT_REPR_LOWP, OUT_ATTN_LOWP = 1, 2, 4, 8, 16, 32
 EPI_STORE_T, EPI_STORE_F32, EPI_GELU_T, EPI_GELU_F32, EPI_RESID_F32 = 0, 1, 2, 3, 4
+EPI_QKV_ROPE, EPI_V_T, EPI_MSA_CTX = 5, 6, 7
 
 
 class EsmkConfig(ctypes.Structure):
@@ -48,6 +49,27 @@ class EsmkMsaConfig(ctypes.Structure):
 class EsmkProfileEntry(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", c_int32), ("ms", ctypes.c_double),
                 ("flops", ctypes.c_double), ("bytes", ctypes.c_double)]
+
+
+class EsmkGemmExArgs(ctypes.Structure):
+    """esmk_gemm_ex_args (include/esmk.h): one field per generalised GemmArgs field of the engine."""
+    _fields_ = [
+        ("size", c_size_t),
+        ("A", c_void_p), ("W", c_void_p), ("bias", c_void_p), ("out", c_void_p),
+        ("M", c_int32), ("N", c_int32), ("K", c_int32), ("a_kt_repeat", c_int32),
+        ("a_row_bytes", c_int64), ("w_row_bytes", c_int64), ("a_kt_bytes", c_int64), ("w_kt_bytes", c_int64),
+        ("batch", c_int32), ("batch_inner", c_int32),
+        ("a_bo", c_int64), ("a_bi", c_int64), ("w_bo", c_int64), ("w_bi", c_int64), ("o_bo", c_int64), ("o_bi", c_int64),
+        ("n_valid", c_int32), ("ldc", c_int32),
+        ("q", c_void_p), ("k", c_void_p), ("vt", c_void_p), ("cos", c_void_p), ("sin", c_void_p),
+        ("T", c_int32), ("H", c_int32), ("E", c_int32), ("Tp", c_int32),
+        ("scaling", c_float), ("vt_rows", c_int32),
+        ("row_keep", c_void_p),
+        ("rowmap_R", c_int32), ("rowmap_C", c_int32), ("ctx_R", c_int32), ("ctx_C", c_int32),
+        ("head_dim", c_int32), ("epilogue", c_int32),
+        ("row_pos", c_void_p),
+        ("operand_dtype", c_int32), ("reserved", c_int32),
+    ]
 
 
 # name -> (restype, argtypes); must list every symbol include/esmk.h declares
@@ -160,6 +182,12 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_int, c_void_p,
          c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int),
          c_int, c_void_p],
+    ),
+    "esmk_op_gemm_ex": (c_int, [POINTER(EsmkGemmExArgs), c_void_p]),
+    "esmk_op_msa_row_softmax": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+         c_void_p],
     ),
     "esmk_op_contacts": (
         c_int,

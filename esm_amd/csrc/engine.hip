@@ -1655,6 +1655,113 @@ int esmk_op_contacts_fused_ex(const void* q_dev, const void* k_dev, const float*
     return 0;
 }
 
+// The generalised-addressing GEMM forms esmk_forward / esmk_msa_forward launch, one launch at a time
+// (tests/test_gemm_forms_gpu.py).  Validation only, then launch_gemm unchanged.
+int esmk_op_gemm_ex(const esmk_gemm_ex_args* a, void* stream) {
+    if (!a) return fail("esmk_op_gemm_ex: null argument");
+    if (a->size != sizeof(esmk_gemm_ex_args)) return fail("esmk_op_gemm_ex: size must be sizeof(esmk_gemm_ex_args)");
+    const int epi = a->epilogue;
+    if (epi < EPI_STORE_T || epi > EPI_MSA_CTX) return fail("esmk_op_gemm_ex: epilogue must be 0 ... 7");
+    if (a->operand_dtype != ESMK_DT_F16 && a->operand_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_gemm_ex: operand_dtype must be fp16 or bf16");
+    const bool qk = epi == EPI_QKV_ROPE, vt = epi == EPI_V_T, ctx = epi == EPI_MSA_CTX;
+    if (!a->A || !a->W) return fail("esmk_op_gemm_ex: null operand");
+    if (qk && (!a->q || !a->k || !a->cos || !a->sin)) return fail("esmk_op_gemm_ex: epilogue 5 needs q, k, cos and sin");
+    if (vt && !a->vt) return fail("esmk_op_gemm_ex: epilogue 6 needs vt");
+    if (!qk && !vt && !a->out) return fail("esmk_op_gemm_ex: null output");
+    if (a->M <= 0 || a->N <= 0 || a->K <= 0) return fail("esmk_op_gemm_ex: M, N and K must be positive");
+    if (a->K % 64 != 0 || a->N % 8 != 0) return fail("esmk_op_gemm_ex: need K % 64 == 0 and N % 8 == 0");
+    if ((qk || vt || ctx) && a->N % 64 != 0) return fail("esmk_op_gemm_ex: epilogues 5, 6 and 7 need N % 64 == 0");
+    if (a->head_dim != 64 && a->head_dim != 128) return fail("esmk_op_gemm_ex: head_dim must be 64 or 128");
+    if (a->head_dim == 128 && !qk && !vt) return fail("esmk_op_gemm_ex: head_dim 128 belongs to epilogues 5 and 6");
+    if (a->batch < 1 || a->batch_inner < 1 || a->batch % a->batch_inner != 0)
+        return fail("esmk_op_gemm_ex: batch and batch_inner must be >= 1 and batch_inner must divide batch");
+    if (a->a_row_bytes < 0 || a->w_row_bytes < 0 || a->a_kt_bytes < 0 || a->w_kt_bytes < 0 || a->a_bo < 0 ||
+        a->a_bi < 0 || a->w_bo < 0 || a->w_bi < 0 || a->o_bo < 0 || a->o_bi < 0 || a->n_valid < 0 || a->ldc < 0 ||
+        a->vt_rows < 0 || a->rowmap_R < 0 || a->rowmap_C < 0 || a->ctx_R < 0 || a->ctx_C < 0)
+        return fail("esmk_op_gemm_ex: strides, offsets and counts must not be negative");
+    if (a->a_kt_repeat != 0 && (a->a_kt_repeat != 1 || a->K % 128 != 0))
+        return fail("esmk_op_gemm_ex: a_kt_repeat is 0 or 1, and 1 needs K % 128 == 0");
+    if (a->n_valid > a->N) return fail("esmk_op_gemm_ex: n_valid must be <= N");
+    if (a->ldc > 0 && !ctx && a->ldc < a->N) return fail("esmk_op_gemm_ex: ldc must be >= N");
+    if ((a->row_keep || a->row_pos) && !qk) return fail("esmk_op_gemm_ex: row_keep and row_pos belong to epilogue 5");
+    if (a->vt_rows > 0 && !vt) return fail("esmk_op_gemm_ex: vt_rows belongs to epilogue 6");
+    if (a->vt_rows > 0 && a->head_dim == 128) return fail("esmk_op_gemm_ex: vt_rows needs head_dim 64");
+    if (qk || vt) {
+        if (a->T <= 0 || a->H <= 0 || a->E != a->H * a->head_dim || a->N != (qk ? 2 : 1) * a->E || a->M % a->T != 0)
+            return fail("esmk_op_gemm_ex: epilogues 5 and 6 need T, H > 0, E = H head_dim, N = 2E (5) or E (6), M % T == 0");
+        if (vt && (a->Tp < a->T || a->Tp % 64 != 0)) return fail("esmk_op_gemm_ex: Tp must be a multiple of 64 and >= T");
+        if (a->vt_rows > 0 && (a->M / a->T) % a->vt_rows != 0)
+            return fail("esmk_op_gemm_ex: vt_rows must divide the number of sequences M / T");
+    }
+    if ((a->rowmap_R > 0 || a->rowmap_C > 0) &&
+        (epi != EPI_RESID_F32 || a->rowmap_R <= 0 || a->rowmap_C <= 0 || a->M % (a->rowmap_R * a->rowmap_C) != 0))
+        return fail("esmk_op_gemm_ex: the row map needs epilogue 4, rowmap_R, rowmap_C > 0 and M % (R C) == 0");
+    if ((a->ctx_R > 0 || a->ctx_C > 0) && !ctx) return fail("esmk_op_gemm_ex: ctx_R and ctx_C belong to epilogue 7");
+    if (ctx && (a->ctx_R <= 0 || a->ctx_C < a->M || a->N != 64 * a->ctx_R || a->ldc < 64 * a->batch_inner))
+        return fail("esmk_op_gemm_ex: epilogue 7 needs N = 64 ctx_R, ctx_C >= M and ldc >= 64 batch_inner");
+    GemmArgs g;
+    g.A = a->A;
+    g.W = a->W;
+    g.bias = a->bias;
+    g.out = a->out;
+    g.M = a->M;
+    g.N = a->N;
+    g.K = a->K;
+    g.q = a->q;
+    g.k = a->k;
+    g.vt = a->vt;
+    g.cos = a->cos;
+    g.sin = a->sin;
+    g.T = a->T;
+    g.H = a->H;
+    g.E = a->E;
+    g.Tp = a->Tp;
+    g.scaling = a->scaling;
+    g.a_row_bytes = a->a_row_bytes;
+    g.w_row_bytes = a->w_row_bytes;
+    g.a_kt_bytes = a->a_kt_bytes;
+    g.w_kt_bytes = a->w_kt_bytes;
+    g.a_kt_repeat = a->a_kt_repeat;
+    g.batch = a->batch;
+    g.batch_inner = a->batch_inner;
+    g.a_bo = a->a_bo;
+    g.a_bi = a->a_bi;
+    g.w_bo = a->w_bo;
+    g.w_bi = a->w_bi;
+    g.o_bo = a->o_bo;
+    g.o_bi = a->o_bi;
+    g.n_valid = a->n_valid;
+    g.ldc = a->ldc;
+    g.row_keep = a->row_keep;
+    g.vt_rows = a->vt_rows;
+    g.rowmap_R = a->rowmap_R;
+    g.rowmap_C = a->rowmap_C;
+    g.ctx_R = a->ctx_R;
+    g.ctx_C = a->ctx_C;
+    g.head_dim = a->head_dim;
+    g.row_pos = a->row_pos;
+    if (epi == EPI_GELU_F32 && gemm8_generalised(g, epi))
+        return fail("esmk_op_gemm_ex: epilogue 3 (fp32 gelu) has no generalised form");
+    ESMK_TRY(launch_gemm(g, epi, a->operand_dtype, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_msa_row_softmax(const float* scores_dev, const float* keep_dev, const int32_t* any_pad_dev, void* probs_out,
+                            float* attn_out, int B, int H, int R, int C, int ldp, int layer, int num_layers_total,
+                            int nslice, int operand_dtype, void* stream) {
+    if (!scores_dev || !keep_dev || !any_pad_dev || !probs_out) return fail("esmk_op_msa_row_softmax: null argument");
+    if (B <= 0 || H <= 0 || R <= 0 || C <= 0) return fail("esmk_op_msa_row_softmax: B, H, R and C must be positive");
+    if (C > 1024 || ldp > 1024 || ldp < C) return fail("esmk_op_msa_row_softmax: need C <= ldp <= 1024");
+    if (nslice < 1) return fail("esmk_op_msa_row_softmax: nslice must be >= 1");
+    if (attn_out && (layer < 0 || layer >= num_layers_total)) return fail("esmk_op_msa_row_softmax: layer out of range");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_msa_row_softmax: operand_dtype must be fp16 or bf16");
+    ESMK_TRY(launch_msa_row_softmax(scores_dev, keep_dev, any_pad_dev, probs_out, attn_out, B, H, R, C, ldp, layer,
+                                    num_layers_total, operand_dtype, (hipStream_t)stream, nslice));
+    return 0;
+}
+
 int esmk_op_contacts(const float* attn_dev, const int64_t* tokens_dev, const float* w_dev,
                      const float* b_dev, float* scratch_dev, float* out_dev, int B, int C, int T,
                      int eos_idx, int prepend_bos, int append_eos, void* stream) {

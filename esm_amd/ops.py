@@ -220,6 +220,40 @@ def contacts_fused(q, k, lse, tokens, w, b=None, key_bias=None, segments=None, p
     return out, used.value
 
 
+_GEMM_EX_PTRS = ("A", "W", "bias", "out", "q", "k", "vt", "cos", "sin", "row_keep", "row_pos")
+
+
+def gemm_ex(epilogue, **fields):
+    """One launch of the persistent GEMM with generalised addressing (esmk_op_gemm_ex, include/esmk.h): keyword
+    arguments are the fields of esmk_gemm_ex_args.  Pointer fields take GPU tensors (any view: the address of its first
+    element) or None; A decides the operand dtype.  Nothing is allocated: every output buffer is the caller's."""
+    a = N.EsmkGemmExArgs()
+    a.size = ctypes.sizeof(a)
+    a.batch, a.batch_inner, a.head_dim, a.scaling = 1, 1, 64, 1.0
+    a.epilogue = epilogue
+    a.operand_dtype = N.dtype_code(fields["A"].dtype)
+    for name, v in fields.items():
+        if name in _GEMM_EX_PTRS:
+            if v is not None and not v.is_cuda:
+                raise RuntimeError("esm_amd.ops: tensors must live on the GPU (no CPU fallback)")
+            setattr(a, name, v.data_ptr() if v is not None else None)
+        else:
+            setattr(a, name, v)
+    N.check(N.lib.esmk_op_gemm_ex(ctypes.byref(a), N.cur_stream()))
+
+
+def msa_row_softmax(scores, keep, any_pad, probs, B, H, R, C, ldp, nslice=1, attn_out=None, layer=0, num_layers=1):
+    """Tied row-attention softmax (esmk_op_msa_row_softmax): scores fp32 [B, nslice, H, C, ldp], keep fp32 [B, R, C],
+    any_pad int32 [1] on the GPU -> probs (operand dtype, [B, H, C, ldp]) and optionally attn_out fp32
+    [B, num_layers, H, C, C] slice `layer`."""
+    _req_cuda(scores, keep, any_pad, probs, attn_out)
+    assert scores.dtype == torch.float32 and keep.dtype == torch.float32 and any_pad.dtype == torch.int32
+    N.check(N.lib.esmk_op_msa_row_softmax(N.ptr(scores), N.ptr(keep), N.ptr(any_pad), N.ptr(probs), N.ptr(attn_out),
+                                          B, H, R, C, ldp, layer, num_layers, nslice, N.dtype_code(probs.dtype),
+                                          N.cur_stream()))
+    return probs
+
+
 def permute_keys16(t):
     """Key position used by the V^T layout: inside each group of 16 keys the 4-groups 1 and 2
     are swapped (position p holds key perm[p])."""

@@ -397,6 +397,54 @@ int esmk_op_contacts_fused_ex(const void* q_dev, const void* k_dev, const float*
                               int eos_idx, int prepend_bos, int append_eos, int head_groups, int* head_groups_used,
                               int operand_dtype, void* stream);
 
+/* The generalised-addressing GEMM forms the engine launches (MSA Transformer, head_dim 128, token-packed rotary
+ * positions), one launch at a time (tests).  One field per field of the engine's internal GemmArgs, with the same
+ * meaning (esm_amd/csrc/kernels.h); 0 / NULL = the dense default.  `size` = sizeof(esmk_gemm_ex_args).  Operand rows
+ * and byte offsets are the caller's: the entry checks the shape rules below, not the extent of the buffers.
+ *   out = A . W^T + bias through `epilogue` (0 store, 1 fp32 store, 2 gelu, 4 fp32 residual add, 5 q/k + rotary,
+ *   6 v transposed, 7 MSA row-attention context); batched: entry z = zo * batch_inner + zi reads A + zo a_bo + zi a_bi,
+ *   W + zo w_bo + zi w_bi and writes out + zo o_bo + zi o_bi (bytes).
+ * Refused before any HIP call: null operands or outputs, K % 64 != 0, N % 8 != 0, N % 64 != 0 for epilogues 5, 6
+ * and 7, head_dim not 64 / 128, batch_inner not dividing batch, vt_rows with head_dim 128, epilogue 3 (fp32 gelu)
+ * with any generalised field.  The LayerNorm-fold and f16x3 forms have entries of their own and no field here. */
+typedef struct esmk_gemm_ex_args {
+    size_t size;
+    const void* A;
+    const void* W;
+    const float* bias;
+    void* out;
+    int32_t M, N, K;
+    int32_t a_kt_repeat;
+    int64_t a_row_bytes, w_row_bytes, a_kt_bytes, w_kt_bytes;
+    int32_t batch, batch_inner;
+    int64_t a_bo, a_bi, w_bo, w_bi, o_bo, o_bi;
+    int32_t n_valid, ldc;
+    void* q;
+    void* k;
+    void* vt;
+    const float* cos;
+    const float* sin;
+    int32_t T, H, E, Tp;
+    float scaling;
+    int32_t vt_rows;
+    const float* row_keep;
+    int32_t rowmap_R, rowmap_C, ctx_R, ctx_C;
+    int32_t head_dim;
+    int32_t epilogue;
+    const int32_t* row_pos;
+    int32_t operand_dtype;
+    int32_t reserved;
+} esmk_gemm_ex_args;
+int esmk_op_gemm_ex(const esmk_gemm_ex_args* args, void* stream);
+
+/* Tied row-attention softmax of the MSA Transformer (axial_attention.py:96-100,127): scores fp32 [B, nslice, H, C, ldp]
+ * (nslice partial maps, summed in index order), keep fp32 [B, R, C] (1 - pad; columns padded in MSA row 0 get -10000
+ * when the device int *any_pad != 0), probs_out operand dtype [B, H, C, ldp] with columns [C, ldp) set to 0, attn_out
+ * fp32 [B, num_layers_total, H, C, C] slice `layer`, or NULL.  C <= ldp <= 1024, nslice >= 1. */
+int esmk_op_msa_row_softmax(const float* scores_dev, const float* keep_dev, const int32_t* any_pad_dev, void* probs_out,
+                            float* attn_out, int B, int H, int R, int C, int ldp, int layer, int num_layers_total,
+                            int nslice, int operand_dtype, void* stream);
+
 /* ContactPredictionHead.forward (modules.py:338-357) incl. symmetrize/apc (modules.py:27-41).
  * attn fp32 [B,C=L*H,T,T]; w fp32 [C]; b fp32 [1]; scratch fp32 >= B*C*(T+1) floats;
  * out fp32 [B,T-2,T-2] (crop follows prepend_bos/append_eos). */

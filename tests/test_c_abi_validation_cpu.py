@@ -290,3 +290,98 @@ def test_contacts_fused_ex_argument_checks():
     rc, nb = size(B=1, T=512, seg=[(300, 130), (17, 2), (40, 0), (100, 129), (20, 1)])
     assert rc == 0 and nb.value > 0
     assert run(B=1, T=512, seg=[(300, 130), (17, 2)], nbytes=0) != 0 and "workspace" in err()
+
+
+def gemm_args(**kw):
+    """A valid tied-score launch of esmk_op_gemm_ex (engine_msa.hip: B = 1, S = 1, H = 2, R = 2, C = 100) on fake
+    addresses, with the fields in `kw` replaced."""
+    a = N.EsmkGemmExArgs()
+    a.size = ctypes.sizeof(a)
+    f = dict(A=0x1000, W=0x2000, out=0x3000, M=100, N=128, K=128, n_valid=100, ldc=128, a_row_bytes=128,
+             w_row_bytes=128, a_kt_bytes=2 * 100 * 64 * 2, w_kt_bytes=2 * 100 * 64 * 2, batch=2, batch_inner=2,
+             a_bi=100 * 64 * 2, w_bi=100 * 64 * 2, o_bi=100 * 128 * 4, head_dim=64, scaling=1.0,
+             epilogue=N.EPI_STORE_F32, operand_dtype=N.F16)
+    f.update(kw)
+    for k, v in f.items():
+        setattr(a, k, v)
+    return a
+
+
+def test_gemm_ex_argument_checks():
+    assert ctypes.sizeof(N.EsmkGemmExArgs) == 264  # include/esmk.h: no padding between the fields
+    call = lambda **kw: N.lib.esmk_op_gemm_ex(ctypes.byref(gemm_args(**kw)), None)  # noqa: E731
+    assert N.lib.esmk_op_gemm_ex(None, None) != 0 and "null" in err()
+    assert call(size=8) != 0 and "sizeof" in err()
+    for kw in (dict(A=None), dict(W=None), dict(out=None)):
+        assert call(**kw) != 0 and "null" in err(), kw
+    for kw in (dict(epilogue=-1), dict(epilogue=8)):
+        assert call(**kw) != 0 and "epilogue must be" in err(), kw
+    for dt in (N.F32, 3):
+        assert call(operand_dtype=dt) != 0 and "operand_dtype" in err(), dt
+    for kw in (dict(M=0), dict(N=-8), dict(K=0)):
+        assert call(**kw) != 0 and "positive" in err(), kw
+    for kw in (dict(K=96), dict(N=100, n_valid=0, ldc=0)):
+        assert call(**kw) != 0 and "K % 64" in err(), kw
+    assert call(epilogue=N.EPI_MSA_CTX, N=136, ldc=0, n_valid=0) != 0 and "N % 64" in err()
+    for hd in (0, 32, 96, 256):
+        assert call(head_dim=hd) != 0 and "head_dim" in err(), hd
+    assert call(head_dim=128) != 0 and "head_dim 128 belongs" in err()
+    for kw in (dict(batch=0), dict(batch_inner=0), dict(batch=3, batch_inner=2)):
+        assert call(**kw) != 0 and "batch_inner" in err(), kw
+    for f in ("a_row_bytes", "w_kt_bytes", "a_bo", "o_bi", "n_valid", "ldc"):
+        assert call(**{f: -1}) != 0 and "negative" in err(), f
+    assert call(a_kt_repeat=2) != 0 and "a_kt_repeat" in err()
+    assert call(a_kt_repeat=1, K=192) != 0 and "a_kt_repeat" in err()
+    assert call(n_valid=129) != 0 and "n_valid" in err()
+    assert call(ldc=120) != 0 and "ldc" in err()
+    # fp32 gelu exists for dense calls only
+    assert call(epilogue=N.EPI_GELU_F32) != 0 and "epilogue 3" in err()
+    assert call(epilogue=N.EPI_GELU_F32, n_valid=0, ldc=0, a_row_bytes=0, w_row_bytes=0, a_kt_bytes=0, w_kt_bytes=0,
+                batch=1, batch_inner=1, a_kt_repeat=1, K=256) != 0 and "epilogue 3" in err()
+    # fields that belong to one epilogue
+    assert call(row_keep=0x4000) != 0 and "row_keep" in err()
+    assert call(row_pos=0x4000) != 0 and "row_pos" in err()
+    assert call(vt_rows=2) != 0 and "vt_rows" in err()
+    assert call(ctx_R=2, ctx_C=100) != 0 and "ctx_R" in err()
+    assert call(rowmap_R=2, rowmap_C=50) != 0 and "row map" in err()
+    dense = dict(n_valid=0, ldc=0, a_row_bytes=0, w_row_bytes=0, a_kt_bytes=0, w_kt_bytes=0, batch=1, batch_inner=1,
+                 a_bi=0, w_bi=0, o_bi=0, M=600, N=768, K=768)
+    for kw in (dict(rowmap_R=7, rowmap_C=0), dict(rowmap_R=7, rowmap_C=65)):  # 600 % 455 != 0
+        assert call(epilogue=N.EPI_RESID_F32, **dense, **kw) != 0 and "row map" in err(), kw
+    # q / k / v forms
+    qk = dict(dense, epilogue=N.EPI_QKV_ROPE, out=None, q=0x5000, k=0x6000, cos=0x7000, sin=0x8000, T=100, H=12,
+              E=768, N=1536)
+    vt = dict(dense, epilogue=N.EPI_V_T, out=None, vt=0x5000, T=100, H=12, E=768, Tp=128)
+    for f in ("q", "k", "cos", "sin"):
+        assert call(**dict(qk, **{f: None})) != 0 and "needs q, k, cos and sin" in err(), f
+    assert call(**dict(vt, vt=None)) != 0 and "needs vt" in err()
+    for kw in (dict(T=0), dict(H=0), dict(E=640), dict(N=768), dict(T=7)):  # 600 % 7 != 0
+        assert call(**dict(qk, **kw)) != 0 and "E = H head_dim" in err(), kw
+    for kw in (dict(Tp=64), dict(Tp=120)):
+        assert call(**dict(vt, **kw)) != 0 and "Tp" in err(), kw
+    assert call(**dict(vt, vt_rows=4)) != 0 and "vt_rows must divide" in err()  # 6 sequences
+    assert call(**dict(vt, vt_rows=2, head_dim=128, H=6)) != 0 and "vt_rows needs head_dim 64" in err()
+    # the context form
+    ctx = dict(dense, epilogue=N.EPI_MSA_CTX, M=100, N=7 * 64, K=128, ldc=768, batch=12, batch_inner=12, ctx_R=7,
+               ctx_C=100)
+    for kw in (dict(ctx_R=0), dict(ctx_C=99), dict(ctx_R=6), dict(ldc=704)):
+        assert call(**dict(ctx, **kw)) != 0 and "epilogue 7 needs" in err(), kw
+
+
+def test_msa_row_softmax_argument_checks():
+    def call(scores=FAKE, keep=FAKE, any_pad=FAKE, probs=FAKE, attn=None, B=1, H=2, R=3, C=100, ldp=128, layer=0,
+             Ltot=1, nslice=1, dt=N.F16):
+        return N.lib.esmk_op_msa_row_softmax(scores, keep, any_pad, probs, attn, B, H, R, C, ldp, layer, Ltot, nslice,
+                                             dt, None)
+
+    for kw in (dict(scores=None), dict(keep=None), dict(any_pad=None), dict(probs=None)):
+        assert call(**kw) != 0 and "null" in err(), kw
+    for kw in (dict(B=0), dict(H=0), dict(R=0), dict(C=0)):
+        assert call(**kw) != 0 and "positive" in err(), kw
+    for kw in (dict(C=1025, ldp=1088), dict(C=100, ldp=1088), dict(C=100, ldp=64)):
+        assert call(**kw) != 0 and "ldp" in err(), kw
+    assert call(nslice=0) != 0 and "nslice" in err()
+    for kw in (dict(layer=1, Ltot=1), dict(layer=-1, Ltot=2)):
+        assert call(attn=FAKE, **kw) != 0 and "layer" in err(), kw
+    for dt in (N.F32, 5):
+        assert call(dt=dt) != 0 and "operand_dtype" in err(), dt
