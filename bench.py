@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the hot path on MI355X.  Default: ESM-2 650M bulk embedding extraction, synthetic L=1022 batches.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload NAME] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload NAME] [--dump-outputs DIR] [--full]
 
 ``--gpus N`` from a plain shell re-executes this script as N ranks (one per GPU) under torch.distributed.run
 (esm_amd/launch.py); started by a launcher already (RANK / WORLD_SIZE set) it joins it.  Ranks create the process
@@ -17,21 +17,27 @@ BASELINE configs driver-measurable):
   extract_650m      the extraction driver end to end: FASTA strings -> tokens -> forward -> device->host ->
                     per-sequence .pt files written (--include mean per_tok), SURVEY §8 f-3
 
-Prints ONE JSON line (rank 0): metric residues/sec (whole job) plus
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: set up, `--warmup` untimed steps,
+`--steps` timed steps, `--dump-outputs` if asked, print.  The line carries metric residues/sec (whole job), `value`,
+`ms_per_step`, `per_rank_ms_per_step` (every rank's own time before the closing barrier), the configuration and `library`
+(version + source hash).  `--full` adds everything that takes runs of its own:
   roofline            dominant kernel class vs the fp16/bf16 MFMA roof (2.5 PFLOP/s dense), HIP events on the launch
                       stream in extra profiled steps after the timed region; `traffic` = HBM bytes per launch from the
                       committed rocprofv3 PMC pass — only when that pass was taken on THIS build of the library
                       (source hash in esmk_version()), else null;
   roofline_attention  the attention kernel against the same roof;  roofline_hbm: LayerNorm against 8 TB/s HBM;
+  kernel_classes      per-class times of the same profiled steps;
   e2e_with_d2h        SURVEY §8 d figure (ii): forward + device->host copy of representations[33], overlapped;
   cpu_baseline        the oracle (CPU restatement of the reference, oracle/esm2_oracle.py) timed on the host cores
                       at B=1 (1 warm-up + 3 timed, median) and B=4, and the parity of the GPU outputs against it
                       (parity.operand_floor_same_inputs: the same sample through the oracle with fp16 rounding at
-                      every operand point — the floor of any 16-bit-operand engine, DESIGN.md §2);
-  per_rank_ms_per_step  every rank's own time before the closing barrier;
-  secondary_workloads   default run (esm2_650m, N = 1, CPU baseline on) only: the msa1b, extract_650m and
-                      esm2_3b_contacts lines of this same script, run as child processes inside a 3-minute budget
-                      (--no-secondary skips them), so that one driver run records every BASELINE configuration.
+                      every operand point — the floor of any 16-bit-operand engine); --no-cpu-baseline
+                      skips it;
+  also_qk_gain, parity  (--also-qk-gain / --parity-ref) the data-sensitivity timing and the parity of this configuration
+                      against a saved oracle sample;
+  secondary_workloads   esm2_650m at N = 1 with the CPU baseline on only: the msa1b, extract_650m, esm2_3b_contacts and
+                      further esm2_650m lines of this same script, run with --full as child processes inside a time
+                      budget (--no-secondary skips them), so that one run records every BASELINE configuration.
 """
 import argparse
 import json
@@ -360,30 +366,31 @@ def run_esm2_650m(args, dist, rank, world, dev):
     with torch.no_grad():
         elapsed = timed_steps(step, args.steps, args.warmup, sync_all, dist, dev)
         dumped = dump_last_step(args, rank)
-        prof, prof_steps = profile_steps(model, step)  # separate steps: the timed region is unperturbed
+        if args.full:
+            prof, prof_steps = profile_steps(model, step)  # separate steps: the timed region is unperturbed
 
-        # figure (ii): every step's representations[33] also goes to pinned host memory on a side stream while the
-        # next forward runs (what the extraction driver does, scripts/extract.py:97-100)
-        d2h_steps = max(2, min(args.steps, 10))
-        copy_stream = torch.cuda.Stream(dev)
-        host = [torch.empty((batch, args.seq_len + 2, E), dtype=torch.float32, pin_memory=True) for _ in range(2)]
-        done = [torch.cuda.Event() for _ in range(2)]
-        sync_all()
-        t0 = time.perf_counter()
-        for i in range(d2h_steps):
-            out = model(toks, repr_layers=[L])["representations"][L]
-            ready = torch.cuda.Event()
-            ready.record(torch.cuda.current_stream(dev))
-            if i >= 2:
-                done[i % 2].synchronize()  # the host buffer is free again
-            with torch.cuda.stream(copy_stream):
-                copy_stream.wait_event(ready)
-                host[i % 2].copy_(out, non_blocking=True)
-                out.record_stream(copy_stream)
-                done[i % 2].record(copy_stream)
-        copy_stream.synchronize()
-        sync_all()
-        d2h_elapsed = time.perf_counter() - t0
+            # figure (ii): every step's representations[33] also goes to pinned host memory on a side stream while the
+            # next forward runs (what the extraction driver does, scripts/extract.py:97-100)
+            d2h_steps = max(2, min(args.steps, 10))
+            copy_stream = torch.cuda.Stream(dev)
+            host = [torch.empty((batch, args.seq_len + 2, E), dtype=torch.float32, pin_memory=True) for _ in range(2)]
+            done = [torch.cuda.Event() for _ in range(2)]
+            sync_all()
+            t0 = time.perf_counter()
+            for i in range(d2h_steps):
+                out = model(toks, repr_layers=[L])["representations"][L]
+                ready = torch.cuda.Event()
+                ready.record(torch.cuda.current_stream(dev))
+                if i >= 2:
+                    done[i % 2].synchronize()  # the host buffer is free again
+                with torch.cuda.stream(copy_stream):
+                    copy_stream.wait_event(ready)
+                    host[i % 2].copy_(out, non_blocking=True)
+                    out.record_stream(copy_stream)
+                    done[i % 2].record(copy_stream)
+            copy_stream.synchronize()
+            sync_all()
+            d2h_elapsed = time.perf_counter() - t0
 
     value = world * residues_per_step * args.steps / elapsed
     if rank != 0:
@@ -394,34 +401,37 @@ def run_esm2_650m(args, dist, rank, world, dev):
         "of the 650M architecture", {"batch_per_gpu": batch, "seq_len": args.seq_len,
                                      "synthetic_weights": {"qk_gain": args.qk_gain, "ln_gamma_std": args.ln_gamma_std}}, model)
     build = library_build()
-    fold_on = model.ln_fold_active()
-    traffic = lambda cls: pmc_traffic(cls, build["src_hash"], "esm2_650m", batch, fold_on)
-    dom, roof = mfma_roofline(prof)
-    roof["traffic"], roof["traffic_source"] = traffic(dom["name"])
     result["e2e_mfma_frac_per_gpu"] = round(value / world * FLOP_PER_RESIDUE / (MFMA_PEAK_TFLOPS * 1e12), 4)
-    result["roofline"] = roof
-    _, ra = mfma_roofline(prof, "attention")
-    ra["traffic"], _ = traffic("attention")
-    result["roofline_attention"] = ra
-    # the HBM-bound kernel of the step: the standalone LayerNorm passes (plain mode: 66 per step; with the fold only the
-    # row-statistics entry, the per-layer finalize launches and the final LayerNorm are left in this class)
-    rh = hbm_roofline(prof)
-    if rh is not None:
-        rh["traffic"], _ = traffic("layernorm")
-        rh["note"] = ("LayerNorm fold on: this class holds rowstats + ln_finalize + the final LayerNorm only" if fold_on
-                      else "standalone LayerNorm passes, 2 per layer")
-    result["roofline_hbm"] = rh
-    result["kernel_classes"] = class_table(prof, prof_steps)
-    result["profiled_ms_per_step"] = round(sum(e["ms"] for e in prof) / prof_steps, 3)
-    result["e2e_with_d2h"] = {
-        "value": round(residues_per_step * d2h_steps / d2h_elapsed, 1), "unit": "residues/s (this rank)",
-        "steps": d2h_steps, "what": "forward + device->host copy of representations[33] (fp32, "
-                                    f"{batch * (args.seq_len + 2) * E * 4 / 1e6:.0f} MB per step) into pinned memory on a "
-                                    "side stream, overlapped with the next forward"}
+    if args.full:
+        fold_on = model.ln_fold_active()
+        traffic = lambda cls: pmc_traffic(cls, build["src_hash"], "esm2_650m", batch, fold_on)
+        dom, roof = mfma_roofline(prof)
+        roof["traffic"], roof["traffic_source"] = traffic(dom["name"])
+        result["roofline"] = roof
+        _, ra = mfma_roofline(prof, "attention")
+        ra["traffic"], _ = traffic("attention")
+        result["roofline_attention"] = ra
+        # the HBM-bound kernel of the step: the standalone LayerNorm passes (plain mode: 66 per step; with the fold only the
+        # row-statistics entry, the per-layer finalize launches and the final LayerNorm are left in this class)
+        rh = hbm_roofline(prof)
+        if rh is not None:
+            rh["traffic"], _ = traffic("layernorm")
+            rh["note"] = ("LayerNorm fold on: this class holds rowstats + ln_finalize + the final LayerNorm only" if fold_on
+                          else "standalone LayerNorm passes, 2 per layer")
+        result["roofline_hbm"] = rh
+        result["kernel_classes"] = class_table(prof, prof_steps)
+        result["profiled_ms_per_step"] = round(sum(e["ms"] for e in prof) / prof_steps, 3)
+        result["e2e_with_d2h"] = {
+            "value": round(residues_per_step * d2h_steps / d2h_elapsed, 1), "unit": "residues/s (this rank)",
+            "steps": d2h_steps, "what": "forward + device->host copy of representations[33] (fp32, "
+                                        f"{batch * (args.seq_len + 2) * E * 4 / 1e6:.0f} MB per step) into pinned memory on a "
+                                        "side stream, overlapped with the next forward"}
     result["library"] = build
     if dumped is not None:
         result["dumped_outputs"] = dumped
-    if world == 1 and args.also_qk_gain > 0:
+    if not args.full or world != 1:  # everything below takes runs of its own
+        return result
+    if args.also_qk_gain > 0:
         # data sensitivity, second point: the same run once more on weights with this q / k gain (timing only — random
         # weights with maps this sharp make a chaotic network: the operand floor itself is O(1) there, parity is undefined)
         try:
@@ -437,7 +447,7 @@ def run_esm2_650m(args, dist, rank, world, dev):
             result["also_qk_gain"] = {"error": f"{type(e).__name__}: {e}"[:200]}
 
     if world == 1 and args.parity_ref and os.path.exists(args.parity_ref):
-        # a secondary line of the default run: parity of THIS engine configuration on the parent's 4 sample sequences,
+        # a secondary line of the --full run: parity of THIS engine configuration on the parent's 4 sample sequences,
         # against the oracle outputs the parent computed once (bench.py secondary_workloads)
         try:
             pr = torch.load(args.parity_ref)
@@ -550,9 +560,9 @@ def operand_floor_report(sd, toks_cpu, L, H, r_ref, logits_ref=None, fold=False)
         return {"error": str(e)}
 
 
-# The other BASELINE configurations, so that the driver's default run records them too ("driver-visible numbers
+# The other BASELINE configurations, so that one --full run records them too ("driver-visible numbers
 # for everything but config 2").  Each is the same `--workload` run a user would start, as a child process with a
-# time limit; nothing in here can cost the flagship line.
+# time limit and with --full (each child's own roofline, parity and CPU sample); nothing in here can cost the flagship line.
 SECONDARY = [  # --quick-baseline: the children's own CPU-oracle sample (parity + cpu_baseline), sized for a few seconds
     ("msa1b", ["--workload", "msa1b", "--quick-baseline"], 120),
     # 24 batches: the timed region ends when the writer threads have closed the LAST file, i.e. it contains one un-overlapped
@@ -583,7 +593,7 @@ SECONDARY = [  # --quick-baseline: the children's own CPU-oracle sample (parity 
                          "--ln-fold", "0", "--parity-ref", "{PARITY_REF}"], 90),
 ]
 T_PROCESS_START = time.perf_counter()
-SECONDARY_BUDGET_S = 270.0  # the default run, children included, ends within ~4.5 minutes of its start (eight children: ~165 s)
+SECONDARY_BUDGET_S = 270.0  # the --full run, children included, ends within ~4.5 minutes of its start (eight children: ~165 s)
 SECONDARY_MIN_S = 30.0      # a child is not started with less than this left
 
 
@@ -603,11 +613,11 @@ def secondary_workloads(extra=(), budget_end=None, parity_ref=""):
         t0 = time.perf_counter()
         limit = min(limit, budget_end - t0)
         if limit < SECONDARY_MIN_S:
-            out[name] = {"skipped": "time budget of the default run spent (run it with --workload " + name + ")"}
+            out[name] = {"skipped": "time budget of the --full run spent (run it with --workload " + name + ")"}
             continue
         try:
             argv = [a.replace("{PARITY_REF}", parity_ref) for a in argv]
-            p = subprocess.run([sys.executable, os.path.abspath(__file__)] + argv + list(extra), capture_output=True,
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--full"] + argv + list(extra), capture_output=True,
                                text=True, timeout=limit, env=env)
             lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
             if p.returncode != 0 or not lines:
@@ -651,7 +661,8 @@ def run_esm2_3b_contacts(args, dist, rank, world, dev):
     with torch.no_grad():
         elapsed = timed_steps(step, args.steps, args.warmup, sync_all, dist, dev)
         dumped = dump_last_step(args, rank)
-        prof, prof_steps = profile_steps(model, step)
+        if args.full:
+            prof, prof_steps = profile_steps(model, step)
     value = world * batch * args.seq_len * args.steps / elapsed
     if rank != 0:
         return None
@@ -660,12 +671,15 @@ def run_esm2_3b_contacts(args, dist, rank, world, dev):
         f"{MODEL} predict_contacts(tokens [B,{T}]): 36-layer forward + contact head without the [B,L,H,T,T] tensor, "
         "random-init weights of the 3B architecture", {"batch_per_gpu": batch, "seq_len": args.seq_len}, model)
     result["e2e_mfma_frac_per_gpu"] = round(value / world / args.seq_len * flop_per_seq / (MFMA_PEAK_TFLOPS * 1e12), 4)
-    dom, result["roofline"] = mfma_roofline(prof)
-    result["roofline_hbm"] = hbm_roofline(prof)
-    result["kernel_classes"] = class_table(prof, prof_steps)
+    if args.full:
+        dom, result["roofline"] = mfma_roofline(prof)
+        result["roofline_hbm"] = hbm_roofline(prof)
+        result["kernel_classes"] = class_table(prof, prof_steps)
     result["library"] = library_build()
     if dumped is not None:
         result["dumped_outputs"] = dumped
+    if not args.full:
+        return result
     result["roofline"]["traffic"], result["roofline"]["traffic_source"] = pmc_traffic(
         PMC_CLASS.get(dom["name"], dom["name"]), result["library"]["src_hash"], "esm2_3b_contacts", batch, model.ln_fold_active())
     if world == 1 and not args.no_cpu_baseline:
@@ -741,7 +755,8 @@ def run_msa1b(args, dist, rank, world, dev):
     with torch.no_grad():
         elapsed = timed_steps(step, args.steps, args.warmup, sync_all, dist, dev)
         dumped = dump_last_step(args, rank)
-        prof, prof_steps = profile_steps(model, step)
+        if args.full:
+            prof, prof_steps = profile_steps(model, step)
     residues = batch * R * (C - 1)
     value = world * residues * args.steps / elapsed
     if rank != 0:
@@ -752,12 +767,15 @@ def run_msa1b(args, dist, rank, world, dev):
         "attention + column attention + FFN, random-init weights", {"msas_per_gpu": batch, "rows": R, "cols": C}, model)
     result["e2e_mfma_frac_per_gpu"] = round(flop * args.steps / elapsed / (MFMA_PEAK_TFLOPS * 1e12), 4)
     result["tflops_algorithmic"] = round(flop * args.steps / elapsed / 1e12, 1)
-    dom, result["roofline"] = mfma_roofline(prof)
-    result["roofline_hbm"] = hbm_roofline(prof)
-    result["kernel_classes"] = class_table(prof, prof_steps)
+    if args.full:
+        dom, result["roofline"] = mfma_roofline(prof)
+        result["roofline_hbm"] = hbm_roofline(prof)
+        result["kernel_classes"] = class_table(prof, prof_steps)
     result["library"] = library_build()
     if dumped is not None:
         result["dumped_outputs"] = dumped
+    if not args.full:
+        return result
     result["roofline"]["traffic"], result["roofline"]["traffic_source"] = pmc_traffic(
         PMC_CLASS.get(dom["name"], dom["name"]), result["library"]["src_hash"], "msa1b", batch, None)
     if world == 1 and not args.no_cpu_baseline:
@@ -863,7 +881,7 @@ def run_extract_650m(args, dist, rank, world, dev):
         n_files = sum(1 for _ in out_dir.rglob("*.pt"))
         nbytes = sum(p.stat().st_size for p in out_dir.rglob("*.pt"))
         check = None
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             # parity of what was WRITTEN: one result file of the timed run read back and compared with the CPU oracle on
             # that sequence (a bounded sample: one L = 1022 forward, ~2 s on 32 threads); its timing is the CPU baseline
             try:
@@ -904,7 +922,8 @@ def run_extract_650m(args, dist, rank, world, dev):
     result["files_written_this_rank"] = n_files
     result["file_gb_per_s_this_rank"] = round(nbytes / elapsed / 1e9 * args.steps / (args.steps + max(args.warmup, 1)), 3)
     result["e2e_mfma_frac_per_gpu"] = round(value / world * 1.4769e9 / (MFMA_PEAK_TFLOPS * 1e12), 4)
-    result["roofline"] = None   # a host + PCIe + file-system pipeline: the forward's roofline is the esm2_650m line
+    if args.full:
+        result["roofline"] = None   # a host + PCIe + file-system pipeline: the forward's roofline is the esm2_650m line
     result["library"] = library_build()
     if check is not None:
         result["parity"], cb = check
@@ -926,15 +945,20 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="units per GPU per step (0 = the workload's default: 64 "
                                                          "sequences for esm2_650m, 32 for esm2_3b_contacts, 1 MSA)")
     ap.add_argument("--seq-len", type=int, default=1022)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the result line's own steps, also measure and check everything else: per-class profiled steps "
+                         "and rooflines, the overlapped device->host figure, the CPU-oracle baseline with parity and the "
+                         "operand floor, and (esm2_650m, N = 1) the other configurations as `secondary_workloads`; a plain "
+                         "run (the default) only sets up, warms up, times --steps, dumps if asked and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU-oracle baseline / parity sample")
     ap.add_argument("--quick-baseline", action="store_true",
                     help="esm2_3b_contacts / msa1b: a smaller CPU-oracle sample (128 residues / 8 MSA rows), used by the "
-                         "default run's child processes to stay inside its time budget")
+                         "--full run's child processes to stay inside its time budget")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="esm2_650m with --gpus N: weak = --batch sequences per GPU (default), strong = --batch sequences "
                          "in total per step (default 512), split over the GPUs")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="esm2_650m at N = 1: do not append the other workloads (msa1b, esm2_3b_contacts, extract_650m; "
+                    help="esm2_650m at N = 1 with --full: do not append the other workloads (msa1b, esm2_3b_contacts, extract_650m; "
                          "child runs, ~2 min) as `secondary_workloads`; --no-cpu-baseline implies it")
     ap.add_argument("--out-dir", default=None, help="extract_650m: directory (file system) the result files go to")
     ap.add_argument("--writer-threads", type=int, default=0, help="extract_650m: writer threads (0 = from host cores)")
@@ -946,11 +970,11 @@ def main():
                          "split weights W = W_hi + W_lo: 2x GEMM time, ~40 %% lower error — the precision mode with "
                          "margin under the 1e-3 contract).  Sets ESM_AMD_OPERAND for this run.")
     ap.add_argument("--qk-gain", type=float, default=2.0, help="esm2_650m: gain of the synthetic q / k projection weights (default 2)")
-    ap.add_argument("--also-qk-gain", type=float, default=0.0, help="esm2_650m: after the run, time the same batch on weights with "
-                    "this q / k gain as well (data-sensitivity line; timing only)")
+    ap.add_argument("--also-qk-gain", type=float, default=0.0, help="esm2_650m with --full: after the run, time the same batch on "
+                    "weights with this q / k gain as well (data-sensitivity line; timing only)")
     ap.add_argument("--ln-gamma-std", type=float, default=0.02, help="esm2_650m: spread of the synthetic LayerNorm gains (default 0.02)")
-    ap.add_argument("--parity-ref", default="", help="esm2_650m: file with {tokens, repr, logits} of the fp32 oracle on 4 sample "
-                                                       "sequences (written by the default run for its secondary lines): report "
+    ap.add_argument("--parity-ref", default="", help="esm2_650m with --full: file with {tokens, repr, logits} of the fp32 oracle on 4 sample "
+                                                       "sequences (written by the --full run for its secondary lines): report "
                                                        "`parity` of this configuration against it")
     ap.add_argument("--save-parity-ref", default="", help=argparse.SUPPRESS)
     ap.add_argument("--spawn", action="store_true",
@@ -986,7 +1010,8 @@ def main():
     dist, rank, world, local_rank = init_ranks(args.gpus, "nccl")
     dev = torch.device("cuda", local_rank)
     torch.cuda.set_device(dev)
-    with_secondary = world == 1 and args.workload == "esm2_650m" and not (args.no_cpu_baseline or args.no_secondary)
+    with_secondary = (args.full and world == 1 and args.workload == "esm2_650m"
+                      and not (args.no_cpu_baseline or args.no_secondary))
     ref_file = None
     if with_secondary and not args.save_parity_ref:
         import tempfile

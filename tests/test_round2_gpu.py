@@ -119,17 +119,39 @@ def test_extract_duplicate_layers_and_model_dtype_means(tmp_path):
 
 def test_bench_self_spawn_initialises_rccl(tmp_path):
     """`python bench.py --spawn` = the N = 1 run through the same self-launch + init_process_group("nccl") +
-    all-reduce path that `python bench.py --gpus N` takes: proves RCCL comes up on the box."""
+    all-reduce path that `python bench.py --gpus N` takes: proves RCCL comes up on the box.  --full: the roofline and
+    device->host figures of the line come from steps of their own."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["PYTHONPATH"] = ROOT
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--spawn", "--steps", "2", "--warmup", "1",
-                          "--batch", "4", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
+                          "--batch", "4", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
                          cwd=str(tmp_path), timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert r["n_gpus"] == 1 and r["collective_backend"] == "nccl" and r["value"] > 0
     assert r["roofline"]["bound"] == "mfma" and r["roofline_hbm"]["bound"] == "hbm"
     assert r["host_cores"] == os.cpu_count() and r["e2e_with_d2h"]["value"] > 0
+
+
+def test_bench_plain_run_is_lean(tmp_path):
+    """Without --full the line holds the headline and the dumped outputs only: no profiled steps, no device->host
+    figure, no CPU baseline and no child runs."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    env["PYTHONPATH"] = ROOT
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "4",
+                          "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, env=env,
+                         cwd=str(tmp_path), timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    r = json.loads(lines[0])
+    assert r["unit"] == "residues/s" and r["higher_is_better"] is True and r["dtype"] and r["steps"] == 2
+    assert abs(r["value"] - 4 * 1022 * 2 / (r["ms_per_step"] * 2e-3)) / r["value"] < 1e-3
+    for key in ("roofline", "roofline_attention", "roofline_hbm", "kernel_classes", "e2e_with_d2h", "cpu_baseline", "parity",
+                "also_qk_gain", "secondary_workloads"):
+        assert key not in r, key
+    assert set(r["dumped_outputs"]["arrays"]) == {"logits", "representations_33"}
+    assert all((tmp_path / "dump" / f"{n}.npy").exists() for n in r["dumped_outputs"]["arrays"])
 
 
 def test_extract_cli_refuses_nogpu_and_msa(tmp_path):

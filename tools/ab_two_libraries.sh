@@ -22,7 +22,7 @@ run() {  # $1 = tag
       b16)  a="--batch 16" ;;
       *)    a="$w" ;;
     esac
-    timeout 300 python bench.py $a --no-cpu-baseline > $OUT/$1_$w.log 2>&1
+    timeout 300 python bench.py --full $a --no-cpu-baseline > $OUT/$1_$w.log 2>&1
     grep '^{' $OUT/$1_$w.log | python -c "
 import sys, json
 r = json.loads(sys.stdin.read())

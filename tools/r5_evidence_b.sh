@@ -7,7 +7,7 @@ O=gpurun_out/r5bb
 mkdir -p $O
 T0=$(date +%s)
 timeout 200 python __graft_entry__.py smoke > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-T1=$(date +%s); timeout 500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_650m.log 2>&1; echo "default bench rc=$? wall $(( $(date +%s) - T1 )) s"
+T1=$(date +%s); timeout 500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_650m.log 2>&1; echo "default bench rc=$? wall $(( $(date +%s) - T1 )) s"
 grep '^{' $O/bench_650m.log > $O/bench_650m.json
 for spec in "b1:--batch 1 --steps 20 --warmup 5" "b4:--batch 4 --steps 20 --warmup 5" "b8:--batch 8 --steps 20 --warmup 5" "b16:--batch 16" "b32:--batch 32" "bf16:--operand bf16" "f16x2:--operand f16x2"; do
   tag=${spec%%:*}; a=${spec#*:}

@@ -5,7 +5,7 @@ set -u
 O=gpurun_out/r5c
 mkdir -p $O
 T0=$(date +%s)
-T1=$(date +%s); timeout 500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_650m.log 2>&1; echo "default bench rc=$? wall $(( $(date +%s) - T1 )) s"
+T1=$(date +%s); timeout 500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_650m.log 2>&1; echo "default bench rc=$? wall $(( $(date +%s) - T1 )) s"
 grep '^{' $O/bench_650m.log > $O/bench_650m.json
 timeout 200 bash tools/smi_under_bench.sh > $O/rocm_smi_under_load.log 2>&1; tail -3 $O/rocm_smi_under_load.log
 timeout 300 python tools/bench_vendor_gemm.py --smi > $O/vendor_gemm_calibration.log 2>&1; tail -12 $O/vendor_gemm_calibration.log

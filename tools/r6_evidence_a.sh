@@ -22,7 +22,7 @@ cp $O/prof_650m_b4_plain/pmc_summary.json profiles/r6_pmc_summary_esm2_650m_b4_p
 cp $O/prof_3b/pmc_summary.json profiles/r6_pmc_summary_esm2_3b_contacts.json
 cp $O/prof_msa/pmc_summary.json profiles/r6_pmc_summary_msa1b.json
 mkdir -p $O/pmc_summaries; cp profiles/r6_pmc_summary_*.json $O/pmc_summaries/
-T1=$(date +%s); timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_650m.log 2> $O/bench_650m.err; echo "default bench rc=$? wall $(( $(date +%s) - T1 )) s"
+T1=$(date +%s); timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_650m.log 2> $O/bench_650m.err; echo "default bench rc=$? wall $(( $(date +%s) - T1 )) s"
 grep '^{' $O/bench_650m.log > $O/bench_650m.json
 for spec in "b1:--batch 1 --steps 20 --warmup 5" "b8:--batch 8 --steps 20 --warmup 5" "b16:--batch 16" "b32:--batch 32" "bf16:--operand bf16"; do
   tag=${spec%%:*}; a=${spec#*:}

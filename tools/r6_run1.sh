@@ -8,7 +8,7 @@ timeout 900 python -m pytest tests -m gpu -q -s -p no:cacheprovider > $O/pytest_
 grep -E "contract |FAILED|Error" $O/pytest_gpu.log > $O/contract_lines.txt
 ESM_AMD_LN_FOLD=0 timeout 900 python -m pytest tests -m gpu -q -s -p no:cacheprovider > $O/pytest_gpu_plain.log 2>&1; echo "pytest plain rc=$? $(( $(date +%s) - T0 )) s"; tail -3 $O/pytest_gpu_plain.log
 grep -E "contract |FAILED|Error" $O/pytest_gpu_plain.log > $O/contract_lines_plain.txt
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_650m.json 2> $O/bench_650m.err; echo "bench rc=$? $(( $(date +%s) - T0 )) s"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_650m.json 2> $O/bench_650m.err; echo "bench rc=$? $(( $(date +%s) - T0 )) s"
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r6a/bench_650m.json").read().strip().splitlines()[-1])

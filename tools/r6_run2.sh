@@ -6,11 +6,11 @@ mkdir -p $O
 T0=$(date +%s)
 timeout 600 python -m pytest tests/test_f16x2_gpu.py tests/test_fullsize_gpu.py -m gpu -q -s -p no:cacheprovider -k "split or f16x2" > $O/pytest_f16x2.log 2>&1; echo "pytest rc=$? $(( $(date +%s) - T0 )) s"; tail -3 $O/pytest_f16x2.log; grep -E "contract |650M dims" $O/pytest_f16x2.log
 for op in f16 f16x2a f16x2; do
-  timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --operand $op --ln-fold $([ $op = f16 ] && echo 1 || echo 0) > $O/bench_$op.json 2> $O/bench_$op.err; echo "bench $op rc=$? $(( $(date +%s) - T0 )) s"
+  timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --operand $op --ln-fold $([ $op = f16 ] && echo 1 || echo 0) > $O/bench_$op.json 2> $O/bench_$op.err; echo "bench $op rc=$? $(( $(date +%s) - T0 )) s"
 done
-timeout 300 python bench.py --steps 10 --warmup 3 --no-secondary --quick-baseline --qk-gain 4 --ln-gamma-std 0.1 > $O/bench_sharp.json 2> $O/bench_sharp.err; echo "bench sharp rc=$? $(( $(date +%s) - T0 )) s"
-timeout 300 python bench.py --steps 10 --warmup 3 --no-secondary --quick-baseline > $O/bench_default_quick.json 2> $O/bench_default_quick.err
-timeout 300 python bench.py --workload msa1b --operand f16x2a --quick-baseline > $O/bench_msa_f16x2a.json 2> $O/bench_msa_f16x2a.err; echo "msa f16x2a rc=$?"
+timeout 300 python bench.py --full --steps 10 --warmup 3 --no-secondary --quick-baseline --qk-gain 4 --ln-gamma-std 0.1 > $O/bench_sharp.json 2> $O/bench_sharp.err; echo "bench sharp rc=$? $(( $(date +%s) - T0 )) s"
+timeout 300 python bench.py --full --steps 10 --warmup 3 --no-secondary --quick-baseline > $O/bench_default_quick.json 2> $O/bench_default_quick.err
+timeout 300 python bench.py --full --workload msa1b --operand f16x2a --quick-baseline > $O/bench_msa_f16x2a.json 2> $O/bench_msa_f16x2a.err; echo "msa f16x2a rc=$?"
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/r6b/bench_*.json")):

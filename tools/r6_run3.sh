@@ -5,11 +5,11 @@ O=gpurun_out/r6c
 mkdir -p $O
 T0=$(date +%s)
 timeout 600 python -m pytest tests/test_f16x2_gpu.py -m gpu -q -s -p no:cacheprovider -k "attention_split" > $O/pytest_f16x2v.log 2>&1; echo "pytest rc=$? $(( $(date +%s) - T0 )) s"; tail -3 $O/pytest_f16x2v.log; grep -E "contract " $O/pytest_f16x2v.log
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_650m.json 2> $O/bench_650m.err; echo "bench rc=$? $(( $(date +%s) - T0 )) s"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_650m.json 2> $O/bench_650m.err; echo "bench rc=$? $(( $(date +%s) - T0 )) s"
 for op in f16x2v f16x2a; do
-  timeout 300 python bench.py --steps 10 --warmup 3 --no-secondary --quick-baseline --operand $op > $O/bench_$op.json 2> $O/bench_$op.err; echo "bench $op rc=$? $(( $(date +%s) - T0 )) s"
+  timeout 300 python bench.py --full --steps 10 --warmup 3 --no-secondary --quick-baseline --operand $op > $O/bench_$op.json 2> $O/bench_$op.err; echo "bench $op rc=$? $(( $(date +%s) - T0 )) s"
 done
-timeout 300 python bench.py --workload esm2_3b_contacts --steps 4 --quick-baseline --operand f16x2a > $O/bench_3b_f16x2a.json 2> $O/bench_3b_f16x2a.err; echo "3b f16x2a rc=$?"
+timeout 300 python bench.py --full --workload esm2_3b_contacts --steps 4 --quick-baseline --operand f16x2a > $O/bench_3b_f16x2a.json 2> $O/bench_3b_f16x2a.err; echo "3b f16x2a rc=$?"
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/r6c/bench_*.json")):

@@ -12,7 +12,7 @@ timeout 1200 python tools/outlier_stress_study.py > $O/outlier_stress_study.log 
 timeout 600 python tools/outlier_stress_study.py --balanced --magnitudes 2000 > $O/outlier_stress_study_balanced.log 2>> $O/outlier_stress_study.err; echo "study balanced rc=$? $(( $(date +%s) - T0 )) s"
 grep -A8 "^==" $O/outlier_stress_study.log $O/outlier_stress_study_balanced.log | cut -c1-330
 tail -5 $O/outlier_stress_study.err
-timeout 300 python bench.py --steps 20 --warmup 5 --batch 4 --no-secondary --quick-baseline > $O/bench_b4.json 2> $O/bench_b4.err; echo "bench b4 rc=$?"
+timeout 300 python bench.py --full --steps 20 --warmup 5 --batch 4 --no-secondary --quick-baseline > $O/bench_b4.json 2> $O/bench_b4.err; echo "bench b4 rc=$?"
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r6s/bench_b4.json").read().strip().splitlines()[-1])
