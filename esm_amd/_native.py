@@ -135,6 +135,7 @@ SIGNATURES = {
     ),
     "esmk_debug_gemm_timing": (c_int, [c_void_p]),
     "esmk_debug_gemm_impl": (c_int, [c_int, c_int]),
+    "esmk_debug_gemm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int32)]),
     "esmk_debug_set": (c_int, [c_char_p, c_double]),
     "esmk_op_rowstats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "esmk_op_ln_finalize": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -494,11 +494,14 @@ static hipError_t launch_attention_impl(const void* q, const void* k, const void
                                         int operand_dtype, int fill_mode, const int* any_pad, hipStream_t st,
                                         AttnSegs segs = AttnSegs(), int n_items = 0, bool x3 = false);
 
-// start-up stagger of the co-resident workgroups in shader cycles per wave slot (attn_fwd_kernel); < 0 = read
-// ESMK_ATTN_STAGGER on the first launch; esmk_debug_set("attn_stagger", cycles)
-static std::atomic<int> g_attn_stagger{-1};
+// start-up stagger of the co-resident workgroups in shader cycles per wave slot (attn_fwd_kernel): zero-sum on the GPU,
+// the shipped library passes 0
 constexpr int kAttnStaggerDefault = 0;
+#ifdef ESMK_EXPERIMENTS
+// < 0 = read ESMK_ATTN_STAGGER on the first launch; esmk_debug_set("attn_stagger", cycles)
+static std::atomic<int> g_attn_stagger{-1};
 void attention_set_stagger(int cycles) { g_attn_stagger = cycles < 0 ? 0 : cycles; }
+#endif
 
 hipError_t launch_attention(const void* q, const void* k, const void* vt, const float* key_bias,
                             const int* seq_info, void* ctx, float* lse, int B, int H, int T, int Tp,
@@ -549,6 +552,7 @@ static hipError_t launch_attention_impl(const void* q, const void* k, const void
         const char* e = getenv("ESMK_ATTN");
         return e ? atoi(e) : ATTN_DEFAULT_VARIANT;
     }();
+#ifdef ESMK_EXPERIMENTS
     static std::once_flag stagger_once;  // launches may come from several host threads
     std::call_once(stagger_once, [] {
         if (g_attn_stagger.load() < 0) {
@@ -557,6 +561,9 @@ static hipError_t launch_attention_impl(const void* q, const void* k, const void
         }
     });
     const int stagger = g_attn_stagger.load();
+#else
+    const int stagger = kAttnStaggerDefault;
+#endif
 #define ESMK_ATTN_LAUNCH(TT, LZ, BF, ...)                                                                      \
     hipLaunchKernelGGL((attn_fwd_kernel<TT, LZ, BF, ##__VA_ARGS__>), grid, dim3(256), 0, st, (const TT*)q, (const TT*)k,   \
                        (const TT*)vt, key_bias, seq_info, (TT*)ctx, lse, H, B * H, nq, T, Tp, var & 1, fill_mode, any_pad, segs, stagger)

@@ -313,9 +313,6 @@ void esmk_destroy(esmk_model* m) {
     if (m->d_usin) (void)hipFree(m->d_usin);
     if (m->pk_host) (void)hipHostFree(m->pk_host);
     if (m->pk_event) (void)hipEventDestroy(m->pk_event);
-    if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
-    if (m->ev_join) (void)hipEventDestroy(m->ev_join);
-    if (m->side_stream) (void)hipStreamDestroy(m->side_stream);
     delete m;
 }
 
@@ -871,17 +868,6 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
     }
     if (repr_copy(0, x)) return 1;  // esm2.py:99-100
 
-    // ESMK_QKV_FORK=1: q/k and v projections side by side on two streams (see esmk_model::side_stream)
-    static const bool env_fork = [] {
-        const char* e = getenv("ESMK_QKV_FORK");
-        return e != nullptr && atoi(e) != 0;
-    }();
-    const bool fork_v = env_fork && !m->prof_on && !m->cfg.weight_split;
-    if (fork_v && !m->side_stream) {
-        ESMK_TRY(hipStreamCreateWithFlags(&m->side_stream, hipStreamNonBlocking));
-        ESMK_TRY(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
-        ESMK_TRY(hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming));
-    }
     GemmArgs g;
     for (int l = 0; l < L; ++l) {  // esm2.py:111-121 -> modules.py:120-142
         const LayerOff& o = m->layer[l];
@@ -933,16 +919,7 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
         gv.bias = (const float*)(pk + o.bqkv) + 2 * EA;
         if (fold) gv.bias2 = (const float*)(pk + o.bqkv2) + 2 * EA;
         gv.N = EA;
-        if (fork_v) {
-            // v on the side stream, after everything queued so far (the LayerNorm that wrote h, the V^T clear); the
-            // attention below waits for it.  Not under the per-class profiler: its events live on one stream.
-            ESMK_TRY(hipEventRecord(m->ev_fork, st));
-            ESMK_TRY(hipStreamWaitEvent(m->side_stream, m->ev_fork, 0));
-            ESMK_TRY(launch_gemm(gv, EPI_V_T, op, m->side_stream));
-            ESMK_TRY(hipEventRecord(m->ev_join, m->side_stream));
-            if (gemm(PC_GEMM_QKV, g, EPI_QKV_ROPE, os)) return 1;  // q, k: weight rows [0,2EA)
-            ESMK_TRY(hipStreamWaitEvent(st, m->ev_join, 0));
-        } else if (!any_split && gemm_qkv_one_launch(g)) {
+        if (!any_split && gemm_qkv_one_launch(g)) {
             // small batches: q, k and v in one launch — same tiles, same bits, fewer rounds over the CUs (kernels.h, EPI_QKV_ALL)
             GemmArgs ga = g;
             ga.N = 3 * EA;
@@ -1343,16 +1320,51 @@ int esmk_op_linear_ln(const void* a_dev, const void* w_dev, const float* bias_de
 int esmk_debug_set(const char* key, double value) {
     if (!key) return fail("esmk_debug_set: null key");
     if (gemm_set_knob(key, value)) return 0;
+#ifdef ESMK_EXPERIMENTS
     if (strcmp(key, "attn_stagger") == 0) {
         attention_set_stagger((int)value);
         return 0;
     }
+#endif
     return fail("esmk_debug_set: unknown key");
 }
 
 int esmk_debug_gemm_impl(int impl, int variant) {
     if (impl != 8 && impl != 9 && impl != 0) return fail("esmk_debug_gemm_impl: impl must be 8, 9 or 0 (automatic choice)");
-    gemm_set_impl(impl, variant);
+    if (!gemm_set_impl(impl, variant))
+        return fail("esmk_debug_gemm_impl: variant must be 0 (the gemm9 variants exist in ESMK_EXPERIMENTS builds only)");
+    return 0;
+}
+
+int esmk_debug_gemm_plan(int M, int N, int K, int epilogue, int flags, int32_t out[4]) {
+    if (!out) return fail("esmk_debug_gemm_plan: null argument");
+    if (epilogue < EPI_STORE_T || epilogue > EPI_QKV_ALL) return fail("esmk_debug_gemm_plan: bad epilogue");
+    if (flags & ~31) return fail("esmk_debug_gemm_plan: unknown flag");
+    static const float fake = 0.f;  // stands for the pointers that select a form; gemm_plan dereferences nothing
+    GemmArgs g;
+    g.bias = &fake;
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    if (epilogue == EPI_QKV_ALL) g.E = N % 3 == 0 ? N / 3 : 0;
+    if (flags & 1) g.force_generic = 1;
+    if (flags & 2) g.force_old = 1;
+    if (flags & 4) {  // LayerNorm fold: producer form of the residual epilogue, consumer form of q / k, v, fc1
+        if (epilogue == EPI_RESID_F32) g.ln_part = const_cast<float*>(&fake);
+        else g.ln_rstd = &fake;
+        if (!gemm9_ln_fold(g, epilogue)) return fail("esmk_debug_gemm_plan: this epilogue has no LayerNorm-fold form");
+    }
+    if (flags & 8) {  // as esmk_op_linear_split: the GEMM runs over the [N,2K] hi | lo image of the weight
+        g.K = 2 * K;
+        g.a_row_bytes = (long long)K * 2;
+        g.a_kt_repeat = 1;
+    }
+    if (flags & 16) g.batch = 2;
+    const GemmPlan pl = gemm_plan(g, epilogue);
+    out[0] = pl.kernel;
+    out[1] = pl.half_m;
+    out[2] = pl.variant;
+    out[3] = 0;
     return 0;
 }
 

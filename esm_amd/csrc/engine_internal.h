@@ -80,11 +80,6 @@ struct esmk_model {
     int32_t* pk_host = nullptr;
     size_t pk_host_cap = 0;
     hipEvent_t pk_event = nullptr;
-    // ESMK_QKV_FORK: the v projection of a layer runs on a stream of the library's own, next to the q/k projection on
-    // the caller's stream (both only read the normalised rows): when neither launch fills a whole number of rounds
-    // over the CUs (small batches, MSA row counts), the workgroups of one take the CUs the other leaves idle
-    hipStream_t side_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // LayerNorm fold: q/k/v and fc1 weights are packed gamma-folded and row-centred, the per-layer
     // LayerNorm passes become GEMM epilogue work.  fold_state[l]: bits of FoldBits — which inputs of the fold have been
     // packed, and which folded images are current (a LayerNorm parameter packed after its weights makes them stale).

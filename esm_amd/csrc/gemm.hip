@@ -1,16 +1,20 @@
-// gemm.hip — nn.Linear on the gfx950 matrix cores:  C[M,N] = A[M,K] . W[N,K]^T (+ bias, + epilogue)
+// gemm.hip — the two one-tile-per-workgroup nn.Linear kernels and their launchers:
+//     C[M,N] = A[M,K] . W[N,K]^T (+ bias, + epilogue)
 //
-// Replaces every torch.nn.Linear / F.linear call of the ESM-2 layer stack
-// (reference esm/multihead_attention.py:256-261,395; esm/modules.py:138-139,309,313) and fuses
-// what the reference runs as separate elementwise ops into the epilogue:
+// gemm256 is the reference the persistent kernels (gemm8.hip, gemm9.hip) are tested against bit for bit (force_old);
+// gemm64 serves the shapes no other kernel covers (K % 64 != 0, N % 8 != 0 such as the 33-wide vocabulary projection).
+// Which kernel a call gets is decided in gemm_dispatch.hip (gemm_plan); nothing here reads a switch.
+//
+// The linear layers replace every torch.nn.Linear / F.linear call of the ESM-2 layer stack
+// (reference esm/multihead_attention.py:256-261,395; esm/modules.py:138-139,309,313) and fuse
+// what the reference runs as separate elementwise ops into the epilogue (gemm_epi.h):
 //   * bias add,
 //   * q scaling (multihead_attention.py:261), rotary embedding (rotary_embedding.py:11-20,63-69)
 //     and the head split / transpose (multihead_attention.py:280-284)        -> EPI_QKV_ROPE (q,k), EPI_V_T (v)
 //   * exact-erf GELU (modules.py:17-24)                                      -> EPI_GELU_*
 //   * residual add into the fp32 stream (modules.py:134,140)                 -> EPI_RESID_F32
 //
-// One-tile-per-workgroup kernel (gemm256; the reference the persistent kernels are tested against bit for bit):
-// 256x256 output tile, K step 64, 8 waves (2 along M x 4 along N, each
+// gemm256: 256x256 output tile, K step 64, 8 waves (2 along M x 4 along N, each
 // wave 128x64 = 8x4 v_mfma_f32_16x16x32 blocks), operands staged HBM->LDS with
 // global_load_lds_dwordx4 into two 64 KiB LDS buffers (one barrier per K step), LDS rows are
 // 128 B with the 16-byte chunk index XOR-swizzled by ((row>>1)&7) so that every ds_read_b128
@@ -23,16 +27,10 @@
 // The MFMA is issued "swapped" (A operand = weight rows, B operand = activation rows) so a
 // lane owns 4 consecutive output columns of one output row: epilogue stores are 8 B (f16/bf16)
 // or 16 B (fp32) per lane, and the RoPE partner (column + 32 of the same head) lives in the
-// same lane and register index two 16-column blocks further (epilogues: gemm_epi.h).
+// same lane and register index two 16-column blocks further.
 //
-// Generic kernel (gemm64): 64x64 tile, K step 32, register staged with row clamping and
-// per-element predicated stores; used for shapes the fast kernel does not cover
-// (K % 64 != 0, N % 4 != 0 such as the 33-wide vocabulary projection).
+// gemm64: 64x64 tile, K step 32, register staged with row clamping and per-element predicated stores.
 #include "gemm_epi.h"
-#include <atomic>
-#include <mutex>
-#include <stdlib.h>
-#include <string.h>
 
 namespace esmk {
 
@@ -311,16 +309,18 @@ static hipError_t launch_generic(const GemmArgs& p, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <typename T>
-static hipError_t dispatch(const GemmArgs& p, int epi, hipStream_t st) {
+// Which of the two tile kernels takes a dense call: 256, 64, or 0 = neither (gemm_plan asks; the launchers re-check).
+int gemm_tile_kernel(const GemmArgs& p, int epi) {
     const bool fast = (p.K % G_BK == 0) && (p.N % 8 == 0) && !p.force_generic;
-    if (epi == EPI_QKV_ROPE || epi == EPI_V_T) {
-        if (!fast || p.N % 64 != 0) return hipErrorInvalidValue;
-        return epi == EPI_V_T ? launch_fast<T, EPI_V_T>(p, st) : launch_fast<T, EPI_QKV_ROPE>(p, st);
-    }
-    if (!fast && (p.K % 32 != 0)) return hipErrorInvalidValue;
+    if (epi == EPI_QKV_ROPE || epi == EPI_V_T) return (fast && p.N % 64 == 0) ? 256 : 0;
+    if (epi < EPI_STORE_T || epi > EPI_RESID_F32) return 0;
+    return fast ? 256 : (p.K % 32 == 0 ? 64 : 0);
+}
+
+template <typename T>
+static hipError_t dispatch256(const GemmArgs& p, int epi, hipStream_t st) {
 #ifdef ESMK_EXPERIMENTS
-    if (p.dbg && fast && epi == EPI_STORE_T) {  // timing experiments (results wrong)
+    if (p.dbg && epi == EPI_STORE_T) {  // timing experiments (results wrong)
         switch (p.dbg) {
             case 1: return launch_fast<T, EPI_STORE_T, 1>(p, st);
             case 2: return launch_fast<T, EPI_STORE_T, 2>(p, st);
@@ -338,183 +338,43 @@ static hipError_t dispatch(const GemmArgs& p, int epi, hipStream_t st) {
             case 160: return launch_fast<T, EPI_STORE_T, 160>(p, st);
         }
     }
-#else
-    if (p.dbg) return hipErrorInvalidValue;
 #endif
-#define ESMK_CASE(E)                                               \
-    case E:                                                        \
-        return fast ? launch_fast<T, E>(p, st) : launch_generic<T, E>(p, st);
     switch (epi) {
-        ESMK_CASE(EPI_STORE_T)
-        ESMK_CASE(EPI_STORE_F32)
-        ESMK_CASE(EPI_GELU_T)
-        ESMK_CASE(EPI_GELU_F32)
-        ESMK_CASE(EPI_RESID_F32)
+        case EPI_STORE_T: return launch_fast<T, EPI_STORE_T>(p, st);
+        case EPI_STORE_F32: return launch_fast<T, EPI_STORE_F32>(p, st);
+        case EPI_GELU_T: return launch_fast<T, EPI_GELU_T>(p, st);
+        case EPI_GELU_F32: return launch_fast<T, EPI_GELU_F32>(p, st);
+        case EPI_RESID_F32: return launch_fast<T, EPI_RESID_F32>(p, st);
+        case EPI_QKV_ROPE: return launch_fast<T, EPI_QKV_ROPE>(p, st);
+        case EPI_V_T: return launch_fast<T, EPI_V_T>(p, st);
     }
-#undef ESMK_CASE
     return hipErrorInvalidValue;
 }
 
-// Which persistent kernel serves a dense call.  g_impl: 8 = gemm8 always, 9 = gemm9 wherever it applies, 0 = auto.
-// Shipped policy (auto, ESMK_GEMM9_POLICY=1): EVERY dense call gemm9 supports goes to gemm9 (mask 127 = all epilogues,
-// no minimum K), full- or half-height tiles by rounds over the CUs x tile cost; gemm8 serves the generalised-addressing
-// calls.  Both give the same bits.  A/B switches: ESMK_GEMM_IMPL = 8 | 9 | 9:<variant> | auto;  ESMK_GEMM9_MASK = bit
-// mask over epilogue codes that may go to gemm9 in auto mode (default 127), ESMK_GEMM9_MIN_K = shortest K of the
-// residual GEMM that goes to gemm9 (default 0), ESMK_GEMM9_POLICY=0 = the round-3a rule.  The settings are read from
-// the environment ONCE (std::call_once: launches may come from several host threads); esmk_debug_gemm_impl overrides
-// the kernel choice only and never suppresses the other variables.
-static int g_impl = -1, g_impl_var = 0, g_mask9 = 127, g_mink9 = 0, g_auto_var = 0;
-void gemm_set_impl(int impl, int var) {
-    g_impl = impl;
-    g_impl_var = var;
-}
-
-// Start-up delay of one workgroup group in the residual GEMMs (gemm9.hip), as a fraction of a tile's main loop
-// (nk K tiles x ~2700 cycles); < 0 = not read yet (ESMK_RESID_DESYNC / ESMK_RESID_DESYNC_GROUP, esmk_debug_set).
-// Knobs: atomics, so that a launch thread never reads a half-initialised value; their environment defaults are read inside
-// gemm_env_init's call_once like every other ESMK_GEMM_* variable (launches may come from several host threads).
-static std::atomic<int> g_lnf_dbg{0};
-static std::atomic<int> g_qkv_one{-2};  // -2: not set (environment decides)
-static std::atomic<int> g_qkv_one_env{-1};
-static std::atomic<double> g_desync{-1.0};
-static std::atomic<int> g_desync_group{-1};
-constexpr double kDesyncDefault = 0.0;
-bool gemm_set_knob(const char* key, double value) {
-    if (strcmp(key, "resid_desync") == 0) g_desync = value < 0 ? 0.0 : value;
-    else if (strcmp(key, "resid_desync_group") == 0) g_desync_group = (int)value;
-    else if (strcmp(key, "lnf_dbg") == 0) {
-        if (!kExperiments && (int)value != 0) return false;  // removes parts of the producer epilogue: ESMK_EXPERIMENTS builds only
-        g_lnf_dbg = (int)value;
-    } else if (strcmp(key, "qkv_one_launch") == 0) g_qkv_one = (int)value < -1 ? -2 : (int)value;
-    else return false;
-    return true;
-}
-static void gemm_env_init();
-static void desync_for(GemmArgs& q, long long tiles) {
-    gemm_env_init();
-    // only launches of at least two rounds of tiles: the delay is paid once, a hidden burst is won per further round
-    const double ds = g_desync.load();
-    if (ds > 0 && tiles >= 512) {
-        q.desync = (int)(ds * (double)(q.K / 64) * 2700.0);
-        q.desync_group = g_desync_group.load();
+template <typename T>
+static hipError_t dispatch64(const GemmArgs& p, int epi, hipStream_t st) {
+    switch (epi) {
+        case EPI_STORE_T: return launch_generic<T, EPI_STORE_T>(p, st);
+        case EPI_STORE_F32: return launch_generic<T, EPI_STORE_F32>(p, st);
+        case EPI_GELU_T: return launch_generic<T, EPI_GELU_T>(p, st);
+        case EPI_GELU_F32: return launch_generic<T, EPI_GELU_F32>(p, st);
+        case EPI_RESID_F32: return launch_generic<T, EPI_RESID_F32>(p, st);
     }
+    return hipErrorInvalidValue;
 }
 
-// ESMK_GEMM_IMPL / ESMK_GEMM9_* are read from the environment ONCE (launches may come from several host threads)
-static void gemm_env_init() {
-    static std::once_flag env_once;
-    std::call_once(env_once, [] {
-        if (g_impl < 0) {  // not set through esmk_debug_gemm_impl
-            const char* e = getenv("ESMK_GEMM_IMPL");
-            g_impl = (e != nullptr && e[0] == '9') ? 9 : (e != nullptr && e[0] == '8') ? 8 : 0;
-            g_impl_var = (e != nullptr && e[0] == '9' && e[1] == ':') ? atoi(e + 2) : 0;
-        }
-        if (const char* m = getenv("ESMK_GEMM9_MASK")) g_mask9 = atoi(m);
-        if (const char* k = getenv("ESMK_GEMM9_MIN_K")) g_mink9 = atoi(k);
-        if (const char* v = getenv("ESMK_GEMM9_VAR")) g_auto_var = atoi(v);  // issue pattern of the auto choice (2 | 3: A/B)
-        if (g_desync.load() < 0) {  // not set through esmk_debug_set
-            const char* e = getenv("ESMK_RESID_DESYNC");
-            g_desync = e ? atof(e) : kDesyncDefault;
-        }
-        if (g_desync_group.load() < 0) {
-            const char* e = getenv("ESMK_RESID_DESYNC_GROUP");
-            g_desync_group = e ? atoi(e) : 0;
-        }
-        if (const char* e = getenv("ESMK_QKV_ONE_LAUNCH")) g_qkv_one_env = atoi(e);
-    });
+// the dbg codes (timing experiments, results wrong) exist in ESMK_EXPERIMENTS builds only (common.h)
+hipError_t launch_gemm256(const GemmArgs& p, int epi, int operand_dtype, hipStream_t st) {
+    if (gemm_tile_kernel(p, epi) != 256 || (p.dbg && !kExperiments)) return hipErrorInvalidValue;
+    if (operand_dtype == ESMK_DT_F16) return dispatch256<_Float16>(p, epi, st);
+    if (operand_dtype == ESMK_DT_BF16) return dispatch256<__bf16>(p, epi, st);
+    return hipErrorInvalidValue;
 }
 
-// Cost of a dense gemm9 launch in the unit the tile-height choice below uses: rounds of tiles over the 256 workgroups, a
-// half-height tile counted as 0.58 of a full one (profiles/r3_gemm9_half_height_b4.log).
-static double gemm9_round_cost(int M, int N) {
-    const long long tn = (N + 255) / 256;
-    const long long tiles = (long long)((M + 255) / 256) * tn, tiles_h = (long long)((M + 127) / 128) * tn;
-    const double cost_f = (double)((tiles + 255) / 256), cost_h = 0.58 * (double)((tiles_h + 255) / 256);
-    return cost_h < 0.92 * cost_f ? cost_h : cost_f;
-}
-
-// q / k (N = 2E) and v (N = E) as ONE launch (EPI_QKV_ALL)?  Only when it saves rounds: the two launches each round their
-// tile count up to whole rounds of 256 workgroups, the combined launch rounds once (B = 1 x 1022 at E = 1280: 80 + 40
-// half-height tiles = two part-filled rounds against one of 120; B = 64: 10 + 5 against 15 rounds — no gain, the two launches stay).  ESMK_QKV_ONE_LAUNCH
-// = 0 / 1 forces the choice (A/B runs); the results are bit-identical either way.
-bool gemm_qkv_one_launch(const GemmArgs& qk) {
-    static const bool env_old = [] { const char* e = getenv("ESMK_GEMM"); return e != nullptr && strcmp(e, "old") == 0; }();
-    gemm_env_init();
-    const int knob = g_qkv_one.load();
-    const int mode = knob >= -1 ? knob : g_qkv_one_env.load();  // esmk_debug_set("qkv_one_launch", -1 | 0 | 1) overrides the environment
-    GemmArgs all = qk;
-    all.N = 3 * qk.E;
-    if (mode == 0 || qk.N != 2 * qk.E || g_impl == 8 || env_old || qk.force_old || qk.force_generic || qk.dbg ||
-        !gemm9_supports(all, EPI_QKV_ALL))
-        return false;
-    if (mode == 1) return true;
-    // The combined kernel exists with HALF-height tiles only.  A full-height instantiation holding both K loops was built
-    // twice: round 4 (accumulator quads shuffled through VGPRs: 1.7 x the time per tile) and round 5 with the quads pinned
-    // to the AGPR file — clean K loops in the ISA report, but on the GPU 26.1 against 20.4 ms per step for q / k / v at
-    // B = 64 and 7.12 against 6.25 ms at B = 16 (profiles/r5_qkv_one_launch_full_height.log): removed again.
-    const long long tiles_h = (long long)((qk.M + 127) / 128) * ((3 * qk.E + 255) / 256);
-    return 0.58 * (double)((tiles_h + 255) / 256) < gemm9_round_cost(qk.M, 2 * qk.E) + gemm9_round_cost(qk.M, qk.E) - 0.25;
-}
-
-hipError_t launch_gemm(const GemmArgs& p, int epi, int operand_dtype, hipStream_t st) {
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0) return hipErrorInvalidValue;
-    gemm_env_init();
-    static const bool env_old = [] {
-        const char* e = getenv("ESMK_GEMM");
-        return e != nullptr && strcmp(e, "old") == 0;
-    }();
-    if (p.x3_out) {  // the hi | hi | lo output form of the f16x3 mode exists in gemm9 only (full-height tiles)
-        if (!gemm9_supports(p, epi)) return hipErrorInvalidValue;
-        GemmArgs q = p;
-        q.half_m = 0;
-        return launch_gemm9(q, epi, operand_dtype, 0, st);
-    }
-    // the LayerNorm-fold forms of the epilogues exist in gemm9 only: such a call never takes another kernel
-    const bool lnf = gemm9_ln_fold(p, epi);
-    if (lnf && !gemm9_supports(p, epi)) return hipErrorInvalidValue;
-    // the one-launch q / k / v form exists in gemm9 only as well (the caller asks gemm_qkv_one_launch first)
-    if (epi == EPI_QKV_ALL && (!gemm9_supports(p, epi) || p.force_old || p.force_generic || p.dbg)) return hipErrorInvalidValue;
-    const bool only9 = lnf || epi == EPI_QKV_ALL;
-    if (only9 || (!env_old && !p.force_old && !p.force_generic && !p.dbg && g_impl != 8 && gemm9_supports(p, epi))) {
-        static const bool hm9 = [] { const char* e = getenv("ESMK_GEMM9_HM"); return e == nullptr || atoi(e) != 0; }();
-        if (!only9 && g_impl == 9 && g_impl_var >= 0) {
-            GemmArgs q = p;
-            if (epi == EPI_RESID_F32 && g_impl_var == 0 && p.half_m <= 0)
-                desync_for(q, (long long)((p.M + 255) / 256) * ((p.N + 255) / 256));
-            return launch_gemm9(q, epi, operand_dtype, g_impl_var, st);
-        }
-        // auto: tile height by rounds over the CUs x cost of a tile (a half-height tile costs ~0.58 of a full one:
-        // 1470 against 2400 - 2600 cycles per K tile, profiles/r3_gemm9_half_height_b4.log).  ESMK_GEMM9_POLICY=0: the
-        // round-3a rule (gemm9 for >= 256 full tiles or where gemm8 would take half-height tiles, gemm8 otherwise).
-        static const int policy = [] { const char* e = getenv("ESMK_GEMM9_POLICY"); return e ? atoi(e) : 1; }();
-        const long long tn = (p.N + 255) / 256;
-        const long long tiles = (long long)((p.M + 255) / 256) * tn, tiles_h = (long long)((p.M + 127) / 128) * tn;
-        if (only9 || (((g_mask9 >> epi) & 1) && (epi != EPI_RESID_F32 || p.K >= g_mink9))) {
-            bool half, use9;
-            if (policy == 0 && !only9) {
-                half = p.half_m > 0 || (p.half_m == 0 && tiles < 256 && gemm8_half_height(p));
-                use9 = half ? hm9 : tiles >= 256;
-            } else {
-                const double wg = 256.0;
-                const double cost_f = (double)((tiles + 255) / 256), cost_h = 0.58 * (double)((tiles_h + 255) / 256);
-                (void)wg;
-                half = p.half_m > 0 || (p.half_m == 0 && cost_h < 0.92 * cost_f) || epi == EPI_QKV_ALL;
-                use9 = true;
-            }
-            if (use9) {
-                GemmArgs q = p;
-                q.half_m = half ? 1 : 0;
-                q.lnf_dbg = g_lnf_dbg.load();
-                if (epi == EPI_RESID_F32 && !half && g_auto_var == 0 && !lnf) desync_for(q, tiles);
-                return launch_gemm9(q, epi, operand_dtype, (half || only9) ? 0 : g_auto_var, st);
-            }
-        }
-    }
-    if (!env_old && !p.force_old && !p.force_generic && gemm8_supports(p, epi))
-        return launch_gemm8(p, epi, operand_dtype, st);
-    if (gemm8_generalised(p, epi)) return hipErrorInvalidValue;  // the tile kernels below only know dense calls
-    if (operand_dtype == ESMK_DT_F16) return dispatch<_Float16>(p, epi, st);
-    if (operand_dtype == ESMK_DT_BF16) return dispatch<__bf16>(p, epi, st);
+hipError_t launch_gemm64(const GemmArgs& p, int epi, int operand_dtype, hipStream_t st) {
+    if (gemm_tile_kernel(p, epi) != 64 || (p.dbg && !kExperiments)) return hipErrorInvalidValue;
+    if (operand_dtype == ESMK_DT_F16) return dispatch64<_Float16>(p, epi, st);
+    if (operand_dtype == ESMK_DT_BF16) return dispatch64<__bf16>(p, epi, st);
     return hipErrorInvalidValue;
 }
 

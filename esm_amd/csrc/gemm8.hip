@@ -38,8 +38,6 @@
 //   L2/L3 (after b_4); U2/U3 of cur^1 were last read one K tile earlier.  RAW: every unit is
 //   waited for by ALL waves before a barrier that precedes its first read.
 #include "gemm_epi.h"
-#include <stdlib.h>
-#include <string.h>
 #include <type_traits>
 
 namespace esmk {
@@ -489,16 +487,10 @@ static int num_workgroups();
 // Half-height tiles (gemm8_kernel<..., HM>) cost 0.7 - 0.95 of a full tile each (tools/bench_half_tiles.py,
 // profiles/r2_half_height_tiles.log: with half the MFMAs the K step lands on the loop's ~1700-cycle non-MFMA
 // skeleton — DMA landing, fragment reads, barriers — instead of 1041 cycles of MFMA issue), so they only pay when BOTH tile heights fit in the same number of rounds over the
-// CUs, i.e. when 256-row tiles leave CUs idle (B <= 4 sequences of 1024 tokens at N = 1280).  ESMK_GEMM8_HM = 0 / 1
-// forces.
+// CUs, i.e. when 256-row tiles leave CUs idle (B <= 4 sequences of 1024 tokens at N = 1280).
 constexpr double HM_TILE_COST = 0.8;
 bool gemm8_half_height(const GemmArgs& p) {
     if (p.half_m != 0) return p.half_m > 0;
-    static const int env = [] {
-        const char* e = getenv("ESMK_GEMM8_HM");
-        return e ? atoi(e) : -1;
-    }();
-    if (env >= 0) return env != 0;
     const long long wg = num_workgroups(), tn = (p.N + 255) / 256;
     const long long t256 = (long long)((p.M + 255) / 256) * tn, t128 = (long long)((p.M + 127) / 128) * tn;
     const double full = (double)((t256 + wg - 1) / wg), half = HM_TILE_COST * (double)((t128 + wg - 1) / wg);
@@ -533,11 +525,6 @@ static hipError_t launch8(GemmArgs p, hipStream_t st) {
         attr_set = true;
     }
     const int tiles_n = (p.N + 255) / 256;
-    static const int env_panel = [] {
-        const char* e = getenv("ESMK_PANEL_C");
-        return e ? atoi(e) : 0;
-    }();
-    if (p.panel_c <= 0 && env_panel > 0) p.panel_c = env_panel < tiles_n ? env_panel : tiles_n;
     if (p.panel_c <= 0) {
         // 32 concurrent tiles per XCD should form a block as square as possible: ~6 x 5 or 8 x 4
         if (tiles_n <= 6) p.panel_c = tiles_n;
@@ -550,16 +537,13 @@ static hipError_t launch8(GemmArgs p, hipStream_t st) {
         // when a workgroup has ONE tile (small batches: nothing else hides the epilogue's residual loads — fc2 at B = 4:
         // 4.26 -> 3.38 ms per forward) and costs when every workgroup walks several tiles and the chip is bandwidth /
         // power bound (B = 64, round 2, one call: fc2 26.2 -> 25.3 ms per step without it, out_proj 8.75 -> 9.7-10.0 with
-        // it), so it is used for single-round launches with a long K loop only.
-        // ESMK_XPF_D / ESMK_XPF_MIN_NK / ESMK_XPF_ROUNDS (experiments): distance from the end of the K loop, shortest K
-        // loop, most tile rounds it is used for.
-        static const int xd = [] { const char* e = getenv("ESMK_XPF_D"); return e ? atoi(e) : 1; }();
-        static const int xmin = [] { const char* e = getenv("ESMK_XPF_MIN_NK"); return e ? atoi(e) : 40; }();
-        static const int xrounds = [] { const char* e = getenv("ESMK_XPF_ROUNDS"); return e ? atoi(e) : 1; }();
+        // it), so it is used for single-round launches (xrounds) with a long K loop (xmin K tiles) only, xd K tiles
+        // before the end of the loop.
+        constexpr int xd = 1, xmin = 40, xrounds = 1;
         const int nk = p.K / 64, wg = num_workgroups();
         const long long tiles = (long long)((p.M + (HM ? 127 : 255)) / (HM ? 128 : 256)) * ((p.N + 255) / 256) * (p.batch > 0 ? p.batch : 1);
         const bool few = (tiles + wg - 1) / wg <= xrounds;
-        p.xpf_kt = (few && nk >= xmin && xd > 0) ? (nk - xd > 0 ? nk - xd : 0) : -1;
+        p.xpf_kt = (few && nk >= xmin) ? nk - xd : -1;
     }
     hipLaunchKernelGGL(kern, dim3(num_workgroups()), dim3(512), P_LDS, st, p, g_timing);
     return hipGetLastError();
@@ -592,27 +576,8 @@ static hipError_t dispatch8(const GemmArgs& p, int epi, hipStream_t st) {
 #endif
         return hipErrorInvalidValue;
     }
-    // ESMK_GEMM8_MODE (read once): engine-level A/B of kernel variants with bench.py
-    static const int mode = [] {
-        const char* e = getenv("ESMK_GEMM8_MODE");
-        if (e == nullptr) return 0;
-        if (!strcmp(e, "pf4")) return 2;
-        if (!strcmp(e, "young")) return 3;
-        if (!strcmp(e, "noxpf")) return 4;
-        return 0;
-    }();
     // generalised addressing requested?  (MSA Transformer calls, batched / strided / remapped GEMMs)
     const bool gen = gemm8_generalised(p, epi);
-#define ESMK_CASES(SC, DB, PFD)                                                          \
-    switch (epi) {                                                                       \
-        case EPI_STORE_T: return launch8<T, EPI_STORE_T, SC, DB, PFD>(p, st);            \
-        case EPI_STORE_F32: return launch8<T, EPI_STORE_F32, SC, DB, PFD>(p, st);        \
-        case EPI_GELU_T: return launch8<T, EPI_GELU_T, SC, DB, PFD>(p, st);              \
-        case EPI_GELU_F32: return launch8<T, EPI_GELU_F32, SC, DB, PFD>(p, st);          \
-        case EPI_RESID_F32: return launch8<T, EPI_RESID_F32, SC, DB, PFD>(p, st);        \
-        case EPI_QKV_ROPE: return launch8<T, EPI_QKV_ROPE, SC, DB, PFD>(p, st);          \
-        case EPI_V_T: return launch8<T, EPI_V_T, SC, DB, PFD>(p, st);                    \
-    }
     if (gen) {
         switch (epi) {
             case EPI_STORE_T: return launch8<T, EPI_STORE_T, 0, 0, 0, true>(p, st);
@@ -625,23 +590,7 @@ static hipError_t dispatch8(const GemmArgs& p, int epi, hipStream_t st) {
         }
         return hipErrorInvalidValue;
     }
-    if constexpr (std::is_same<T, _Float16>::value) {
-        if (mode == 3) { ESMK_CASES(0, 32, 0) }
-        if (mode == 4) { ESMK_CASES(0, 128, 0) }
-    }
     if (gemm8_half_height(p)) {
-        // ESMK_HM_PF=4 (experiment): half-height launches (small batches: latency bound, operands come from the MALL)
-        // with the L2 prefetch stream four K tiles ahead
-        static const int hm_pf = [] { const char* e = getenv("ESMK_HM_PF"); return e ? atoi(e) : 0; }();
-        if (hm_pf == 4) {
-            switch (epi) {
-                case EPI_STORE_T: return launch8<T, EPI_STORE_T, 0, 0, 4, false, true>(p, st);
-                case EPI_GELU_T: return launch8<T, EPI_GELU_T, 0, 0, 4, false, true>(p, st);
-                case EPI_RESID_F32: return launch8<T, EPI_RESID_F32, 0, 0, 4, false, true>(p, st);
-                case EPI_QKV_ROPE: return launch8<T, EPI_QKV_ROPE, 0, 0, 4, false, true>(p, st);
-                case EPI_V_T: return launch8<T, EPI_V_T, 0, 0, 4, false, true>(p, st);
-            }
-        }
         switch (epi) {
             case EPI_STORE_T: return launch8<T, EPI_STORE_T, 0, 0, 0, false, true>(p, st);
             case EPI_STORE_F32: return launch8<T, EPI_STORE_F32, 0, 0, 0, false, true>(p, st);
@@ -652,14 +601,22 @@ static hipError_t dispatch8(const GemmArgs& p, int epi, hipStream_t st) {
             case EPI_V_T: return launch8<T, EPI_V_T, 0, 0, 0, false, true>(p, st);
         }
     }
-    ESMK_CASES(0, 0, PF_DEFAULT)
-#undef ESMK_CASES
+    switch (epi) {
+        case EPI_STORE_T: return launch8<T, EPI_STORE_T>(p, st);
+        case EPI_STORE_F32: return launch8<T, EPI_STORE_F32>(p, st);
+        case EPI_GELU_T: return launch8<T, EPI_GELU_T>(p, st);
+        case EPI_GELU_F32: return launch8<T, EPI_GELU_F32>(p, st);
+        case EPI_RESID_F32: return launch8<T, EPI_RESID_F32>(p, st);
+        case EPI_QKV_ROPE: return launch8<T, EPI_QKV_ROPE>(p, st);
+        case EPI_V_T: return launch8<T, EPI_V_T>(p, st);
+    }
     return hipErrorInvalidValue;
 }
 
 bool gemm8_supports(const GemmArgs& p, int epi) {
     if (p.K % 64 != 0 || p.N % 8 != 0 || p.M <= 0) return false;
     if ((epi == EPI_QKV_ROPE || epi == EPI_V_T || epi == EPI_MSA_CTX) && p.N % 64 != 0) return false;
+    if (epi == EPI_GELU_F32 && gemm8_generalised(p, epi)) return false;  // not instantiated (dispatch8)
     return true;
 }
 

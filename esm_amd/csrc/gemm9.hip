@@ -49,8 +49,6 @@
 // The K tiles of all tiles of a workgroup form one stream, as in gemm8: the first operands of the next tile land
 // during the epilogue.  Half-height tiles (small batches): see the HM parameter of the kernel.
 #include "gemm_epi.h"
-#include <stdlib.h>
-#include <string.h>
 #include <type_traits>
 
 namespace esmk {
@@ -978,6 +976,7 @@ bool gemm9_supports(const GemmArgs& p, int epi) {
 
 template <typename T>
 static hipError_t dispatch9(const GemmArgs& p, int epi, int var, hipStream_t st) {
+#ifdef ESMK_EXPERIMENTS  // every VAR != 0: issue patterns (same results) and timing experiments (results wrong)
 #define ESMK_G9_ALL(V)                                                       \
     switch (epi) {                                                            \
         case EPI_STORE_T: return launch9<T, EPI_STORE_T, V>(p, st);           \
@@ -991,7 +990,6 @@ static hipError_t dispatch9(const GemmArgs& p, int epi, int var, hipStream_t st)
     if (var == 2) { ESMK_G9_ALL(2) }  // A/B of the issue patterns in the whole forward (ESMK_GEMM_IMPL=9:2 / 9:3)
     if (var == 3) { ESMK_G9_ALL(3) }
 #undef ESMK_G9_ALL
-#ifdef ESMK_EXPERIMENTS
     if constexpr (std::is_same<T, _Float16>::value) {
         if (p.half_m > 0 && epi == EPI_STORE_T) {  // timing experiments on the half-height kernel (results wrong)
             switch (var) {
@@ -1005,6 +1003,8 @@ static hipError_t dispatch9(const GemmArgs& p, int epi, int var, hipStream_t st)
             }
         }
     }
+#else
+    if (var != 0) return hipErrorInvalidValue;
 #endif
     if (p.x3_out) {  // f16x3: fc1 + GELU with hi | hi | lo output rows — full height, fp16
         if constexpr (std::is_same<T, _Float16>::value) {
@@ -1059,6 +1059,7 @@ static hipError_t dispatch9(const GemmArgs& p, int epi, int var, hipStream_t st)
             case EPI_QKV_ALL: return hipErrorInvalidValue;  // half-height tiles only (see gemm_qkv_one_launch)
         }
     }
+#ifdef ESMK_EXPERIMENTS
     if constexpr (std::is_same<T, _Float16>::value) {
         if (epi == EPI_STORE_T) {  // timing experiments (tools/bench_gemm9.py --dbg)
             switch (var) {  // schedule variants: same results
@@ -1067,7 +1068,7 @@ static hipError_t dispatch9(const GemmArgs& p, int epi, int var, hipStream_t st)
                 case 512: return launch9<T, EPI_STORE_T, 512>(p, st);    // K stagger by column block
                 case 2048: return launch9<T, EPI_STORE_T, 2048>(p, st);  // non-temporal operand loads
                 case 4096: return launch9<T, EPI_STORE_T, 4096>(p, st);  // plain (temporal) stores
-#ifdef ESMK_EXPERIMENTS  // parts of the kernel removed: results wrong
+                // parts of the kernel removed: results wrong
                 case 8: return launch9<T, EPI_STORE_T, 8>(p, st);
                 case 16: return launch9<T, EPI_STORE_T, 16>(p, st);
                 case 32: return launch9<T, EPI_STORE_T, 32>(p, st);
@@ -1076,10 +1077,10 @@ static hipError_t dispatch9(const GemmArgs& p, int epi, int var, hipStream_t st)
                 case 96: return launch9<T, EPI_STORE_T, 96>(p, st);
                 case 224: return launch9<T, EPI_STORE_T, 224>(p, st);
                 case 1040: return launch9<T, EPI_STORE_T, 1040>(p, st);  // no MFMAs, half the DMA bytes
-#endif
             }
         }
     }
+#endif
     return hipErrorInvalidValue;
 }
 

@@ -277,23 +277,27 @@ int esmk_debug_mma_selftest(const void* a_dev, const void* b_dev, const float* c
 
 /* Measurement / A-B hook (no reference counterpart): which persistent GEMM kernel serves the dense nn.Linear calls
  * from now on — 8 = gemm8.hip (two waves per SIMD), 9 = gemm9.hip (one wave per SIMD, 128 x 128 wave blocks;
- * bit-identical results) wherever it applies, 0 = the library's own choice per call (default).  `variant` selects a
- * gemm9 barrier placement / timing experiment (gemm9.hip).  The environment variable ESMK_GEMM_IMPL=8|9[:variant]|auto
- * sets the same thing for a whole process. */
+ * bit-identical results) wherever it applies, 0 = the library's own choice per call (default).  `variant` must be 0:
+ * the gemm9 issue patterns and timing experiments it selects exist only in libraries built with
+ * ESMK_HIPCC_EXTRA="-DESMK_EXPERIMENTS".  The environment variable ESMK_GEMM_IMPL=8|9|auto sets the same thing for a
+ * whole process. */
 int esmk_debug_gemm_impl(int impl, int variant);
 
-/* Measurement / A-B hook (no reference counterpart): named tuning knobs of the library, process wide.  Timing only —
- * no knob changes a result bit.  (Timing experiments that DO break results — kernels with their MFMAs, exponentials,
- * DMA or epilogue stores removed: the "lnf_dbg" knob, ESMK_ATTN_HACK, the gemm8 / gemm9 variant codes with parts switched
- * off — exist only in libraries built with ESMK_HIPCC_EXTRA="-DESMK_EXPERIMENTS"; the shipped library refuses them.)  "resid_desync" (>= 0): start-up delay of every other XCD's workgroups in the residual
- * GEMMs (out-projection, fc2), as a fraction of one tile's main loop, which takes the HBM-bound read-modify-write
- * epilogues of the two halves of the chip out of lockstep (gemm9.hip; environment: ESMK_RESID_DESYNC);
- * "resid_desync_group": 0 = odd XCDs late, 1 = every other workgroup of each XCD, 2 = four phases.
- * "attn_stagger" (>= 0): start-up delay, in shader cycles per wave slot, of the co-resident workgroups of the attention
- * kernel (attention.hip; environment: ESMK_ATTN_STAGGER).
- * "qkv_one_launch": 1 / 0 = always / never run the q, k and v projections of a layer as ONE GEMM launch, -1 = the library's
- * choice (one launch where it needs fewer rounds of tiles over the CUs, i.e. small batches; gemm.hip; environment:
- * ESMK_QKV_ONE_LAUNCH). */
+/* What the library would launch for a dense nn.Linear call (no reference counterpart, no GPU needed): out =
+ * {kernel, half_m, variant, 0}; kernel 9 = gemm9.hip, 8 = gemm8.hip, 256 / 64 = the one-tile-per-workgroup kernels of
+ * gemm.hip, 0 = no kernel takes the call; half_m 1 = 128-row tiles.  epilogue: the codes of esmk_op_linear, 5 / 6 = the
+ * q, k / v projections, 7 = the MSA row-attention context, 8 = q, k and v in one launch (N = 3E).  flags: 1 = the
+ * force_generic and 2 = the force_old test hook of esmk_op_linear, 4 = the LayerNorm-fold form of the epilogue (producer
+ * for 4, consumer for 2, 5, 6, 8; an error for the others), 8 = the split-weight form of esmk_op_linear_split (K as
+ * there), 16 = a batched call (generalised addressing, batch = 2).  Follows ESMK_GEMM_IMPL / esmk_debug_gemm_impl. */
+int esmk_debug_gemm_plan(int M, int N, int K, int epilogue, int flags, int32_t out[4]);
+
+/* Measurement / A-B hook (no reference counterpart): named switches of the library, process wide.  No switch changes a
+ * result bit.  "qkv_one_launch": 1 / 0 = always / never run the q, k and v projections of a layer as ONE GEMM launch,
+ * -1 = the library's choice (one launch where it needs fewer rounds of tiles over the CUs, i.e. small batches;
+ * gemm_dispatch.hip; environment: ESMK_QKV_ONE_LAUNCH).  Any other key is an error ("unknown key").  Libraries built with
+ * ESMK_HIPCC_EXTRA="-DESMK_EXPERIMENTS" add timing experiments, some of which DO break results (kernels with their
+ * MFMAs, exponentials, DMA or epilogue stores removed): see common.h. */
 int esmk_debug_set(const char* key, double value);
 
 /* Fused q/k/v projection + scaling + rotary + head split (multihead_attention.py:256-284,

@@ -350,9 +350,9 @@ def test_pmc_summary_tells_the_two_residual_gemms_apart(tmp_path):
         c.commit()
         c.close()
 
-    g9r = "_ZN4esmk12gemm9_kernelIDF16_Li4ELi0ELb0EEEvNS_8GemmArgsEPy"
+    g9r = "_ZN4esmk12gemm9_kernelIDF16_Li4ELi0ELb0ELb0ELb0EEEvNS_8GemmArgsEPy"
     g8r = "_ZN4esmk12gemm8_kernelIDF16_Li4ELi0ELi0ELi0ELb0ELb0EEEvNS_8GemmArgsEPy"
-    g9g = "_ZN4esmk12gemm9_kernelIDF16_Li2ELi0ELb0EEEvNS_8GemmArgsEPy"
+    g9g = "_ZN4esmk12gemm9_kernelIDF16_Li2ELi0ELb0ELb0ELb0EEEvNS_8GemmArgsEPy"
     for tag, layer, want in (("same", [(g9r, 100.0), (g9g, 7.0), (g9r, 300.0)], (100.0, 300.0)),
                              ("split", [(g8r, 100.0), (g9g, 7.0), (g9r, 300.0)], (100.0, 300.0))):
         db, out = tmp_path / f"{tag}.db", tmp_path / f"{tag}.json"

@@ -33,12 +33,3 @@ print('$1 $w', r['value'], r['unit'], r['ms_per_step'], 'ms/step', r.get('librar
 run new                                  # candidate, cold box
 cp esm_amd/lib/libesmk_prev.so $LIB; run old
 cp /tmp/libesmk_new.so $LIB; run new2    # candidate again: brackets the baseline in time
-# environment-switched variants of the candidate (off by default): q/k and v projections on two streams
-for w in b4 b16 msa; do
-  case $w in b4) a="--batch 4" ;; b16) a="--batch 16" ;; msa) a="--workload msa1b" ;; esac
-  ESMK_QKV_FORK=1 timeout 300 python bench.py $a --no-cpu-baseline > $OUT/fork_$w.log 2>&1
-  timeout 300 python bench.py $a --no-cpu-baseline > $OUT/nofork_$w.log 2>&1
-  for t in fork nofork; do grep '^{' $OUT/${t}_$w.log | python -c "
-import sys, json
-r = json.loads(sys.stdin.read()); print('$t $w', r['value'], r['ms_per_step'])" 2>/dev/null; done
-done
