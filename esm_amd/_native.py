@@ -15,6 +15,7 @@ F32, F16, BF16 = 0, 1, 2
 OUT_LOGITS, OUT_ATTN, OUT_CONTACTS, OUT_COL_ATTN, OUT_REPR_LOWP, OUT_ATTN_LOWP = 1, 2, 4, 8, 16, 32
 EPI_STORE_T, EPI_STORE_F32, EPI_GELU_T, EPI_GELU_F32, EPI_RESID_F32 = 0, 1, 2, 3, 4
 EPI_QKV_ROPE, EPI_V_T, EPI_MSA_CTX = 5, 6, 7
+ESM1, ESM1_FINAL_BIAS = 2, 4  # esmk_config.no_rope values of the original ESM-1 architecture (include/esmk.h)
 
 
 class EsmkConfig(ctypes.Structure):
@@ -170,6 +171,11 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
          c_int, c_int, c_int, c_void_p],
+    ),
+    "esmk_op_attention_biaskv": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+         c_int, c_int, c_void_p],
     ),
     "esmk_op_attention_probs_ex": (
         c_int,

@@ -7,9 +7,9 @@ Checkpoint formats understood
     token_dropout)}, "model": state}`` with the key prefixes ``encoder.sentence_encoder.`` /
     ``encoder.`` removed; dispatched by the file stem starting with ``esm2``;
   * optional sibling ``<stem>-contact-regression.pt`` holding ``contact_head.regression.*``.
-  * ``{"args": Namespace(arch=...), "model": state}``: ``msa_transformer`` (MSA Transformer) and
-    ``roberta_large`` (ESM-1b / ESM-1v), with the reference's key-prefix upgrades.
-Other model families of the reference (ESM-1 ``protein_bert_base``, ESM-IF1, ESMFold) are outside the MI355X
+  * ``{"args": Namespace(arch=...), "model": state}``: ``msa_transformer`` (MSA Transformer),
+    ``roberta_large`` (ESM-1b / ESM-1v) and ``protein_bert_base`` (ESM-1), with the reference's key-prefix upgrades.
+Other model families of the reference (ESM-IF1, ESMFold) are outside the MI355X
 engine's scope and raise ``NotImplementedError`` when a checkpoint asks for them.
 """
 import re
@@ -89,13 +89,19 @@ _PREFIX = re.compile(r"^(encoder\.sentence_encoder\.|encoder\.|sentence_encoder\
 _ARG_PREFIX = re.compile(r"^encoder_")
 
 
-def strip_key_prefix(key):
-    """'encoder.sentence_encoder.layers.0.fc1.weight' / 'encoder.lm_head.bias' -> module-relative key."""
+def strip_key_prefix(key, prefix=None):
+    """'encoder.sentence_encoder.layers.0.fc1.weight' / 'encoder.lm_head.bias' -> module-relative key.
+    ``prefix``: a literal prefix instead (ESM-1: 'decoder.')."""
+    if prefix is not None:
+        return key[len(prefix):] if key.startswith(prefix) else key
     return _PREFIX.sub("", key)
 
 
-def strip_arg_prefix(name):
-    """'encoder_embed_dim' -> 'embed_dim' (hyper-parameter names of the v1 checkpoints)."""
+def strip_arg_prefix(name, prefix=None):
+    """'encoder_embed_dim' -> 'embed_dim' (hyper-parameter names of the v1 checkpoints); ``prefix``: a literal prefix
+    instead (ESM-1: 'decoder_')."""
+    if prefix is not None:
+        return name[len(prefix):] if name.startswith(prefix) else name
     return _ARG_PREFIX.sub("", name)
 
 
@@ -119,13 +125,13 @@ def _build_v1(model_data):
         from .msa_transformer import build_from_checkpoint
 
         return build_from_checkpoint(model_data)
-    if arch == "roberta_large":  # ESM-1b / ESM-1v
+    if arch in ("roberta_large", "protein_bert_base"):  # ESM-1b / ESM-1v; ESM-1
         from .esm1 import build_from_checkpoint
 
         return build_from_checkpoint(model_data)
     raise NotImplementedError(
         f"architecture {arch!r} is outside the scope of the MI355X ESM-2 engine "
-        "(ESM-1 / ESM-1b / ESM-1v / ESM-IF1 are not implemented)"
+        "(ESM-IF1 and ESMFold are not implemented)"
     )
 
 
@@ -180,6 +186,11 @@ _RELEASED = {
     "esm1v_t33_650M_UR90S_3": "33 layer ESM-1v model with 650M params, trained on UniRef90 (ensemble member 3).",
     "esm1v_t33_650M_UR90S_4": "33 layer ESM-1v model with 650M params, trained on UniRef90 (ensemble member 4).",
     "esm1v_t33_650M_UR90S_5": "33 layer ESM-1v model with 650M params, trained on UniRef90 (ensemble member 5).",
+    "esm1_t34_670M_UR50S": "34 layer ESM-1 model with 670M params, trained on UniRef50 Sparse.",
+    "esm1_t34_670M_UR50D": "34 layer ESM-1 model with 670M params, trained on UniRef50 Dense.",
+    "esm1_t34_670M_UR100": "34 layer ESM-1 model with 670M params, trained on UniRef100.",
+    "esm1_t12_85M_UR50S": "12 layer ESM-1 model with 85M params, trained on UniRef50 Sparse.",
+    "esm1_t6_43M_UR50S": "6 layer ESM-1 model with 43M params, trained on UniRef50 Sparse.",
     "esm_msa1_t12_100M_UR50S": "MSA Transformer (ESM-MSA-1), 12 layers, 100M params.",
     "esm_msa1b_t12_100M_UR50S": "MSA Transformer (ESM-MSA-1b), 12 layers, 100M params.",
 }

@@ -94,12 +94,26 @@ constexpr float LAZY_LIMIT = 4096.f;
 // X3 (precision mode f16x3, esmk_config::weight_split 4): the context rows leave as the A operand of that mode's out-projection —
 // per head (= one 64-column K tile) hi | hi | lo, lo = T(v - T(v)), row stride 3 H 64 (the layout the LayerNorm kernel writes
 // with LnExtra::x3).  An instantiation of its own: the shipped kernel keeps its code.
-template <typename T, int LAZY, bool BUF = true, int HACK = 0, bool X3 = false>
-__global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
+// NK (ESM-1, esmk_config::no_rope = ESMK_ESM1: add_bias_kv of esm/multihead_attention.py:263-278): every (query, head) sees ONE more key / value
+// pair, the learned rows bias_k[head] / bias_v[head] (64 operand-dtype values each; bias_k unscaled — only q carries the scale), which
+// no padding mask covers.  It is not a row of K / V^T: its score s0 = q . bias_k[head] is a lane-local dot over the Q fragments (+ the
+// cross-half exchange), and after the key-tile loop the pair is folded into the finished online softmax — one
+// shift of the offset m_off up to s0 where s0 is above it (a dominant null key cannot overflow), lsum += p0, O^T += p0 bias_v.  The
+// saved lse therefore INCLUDES the null key, and attn_probs_kernel / the contact kernels (contacts.hip), which compute exp2(s - lse)
+// over the T real keys only, yield the reference's maps with the null column dropped (esm1.py:181-183: rows sum to 1 - p0) with no
+// change.  A kernel of its own around the shared body (attn_fwd_nullkv_kernel): the other instantiations keep their code.
+template <typename T>
+struct NullKv {
+    const T* k;  // [H, 64]
+    const T* v;  // [H, 64]
+};
+struct NoNullKv {};
+template <typename T, int LAZY, bool BUF, int HACK, bool X3, bool NK>
+ESMK_DEV void attn_fwd_body(
     const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ vt,
     const float* __restrict__ key_bias, const int* __restrict__ seq_info, T* __restrict__ ctx,
     float* __restrict__ lse, int H, int BH, int nq, int Tlen, int Tp, int xcdmap, int fill_mode,
-    const int* __restrict__ any_pad, AttnSegs segs, int stagger) {
+    const int* __restrict__ any_pad, AttnSegs segs, int stagger, std::conditional_t<NK, NullKv<T>, NoNullKv> nkv) {
     __shared__ __attribute__((aligned(16))) char smem[2 * A_STAGE];
     using V8 = typename Op<T>::v8;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -192,7 +206,6 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const V8*>(qp + 16 * ks);
     }
-
     // Staging: 2 rounds of 256 lanes each for K and for V^T; lane tid copies 16-byte chunk c of row r0 (round 0)
     // and of row r0 + 32 (round 1) — the swizzle (r >> 1) & 7 is the same for both rows.  The copies are
     // buffer_load ... lds with the per-lane byte offset FIXED and the tile advance in the scalar offset: the whole
@@ -411,6 +424,39 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
         __syncthreads();
     }
 
+    // ---- NK: fold the null key / value pair into the finished softmax state -------------------
+    if constexpr (NK) {
+        if (wave_active) {
+            // score of the null key (log2 domain, like every q . k): this lane's 32 of the 64 products, then the other half's
+            // (taken here, not before the loop: one more live register there costs the third wave per SIMD)
+            float s0 = 0.f;
+            const T* bk = nkv.k + head * 64 + 8 * h;
+    #pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const V8 kf = *reinterpret_cast<const V8*>(bk + 16 * ks);
+    #pragma unroll
+                for (int e = 0; e < 8; ++e) s0 += Op<T>::to(qf[ks][e]) * Op<T>::to(kf[e]);
+            }
+            s0 += __shfl_xor(s0, 32, 64);
+            // the offset moves up to s0 where s0 is above it; a row without any finite score yet (every real key masked) takes s0
+            // outright.  m_off and m_ok are equal in the two lanes of a row, so both take the same shift.
+            const float dlt = m_ok ? fmaxf(s0 - m_off, 0.f) : s0 - m_off;
+            const float alpha = m_ok ? __builtin_amdgcn_exp2f(-dlt) : 1.f;  // dlt = 0 -> exactly 1
+            const float p0 = __builtin_amdgcn_exp2f(s0 - m_off - dlt);
+            m_off += dlt;
+            lsum = lsum * alpha + (h == 0 ? p0 : 0.f);  // lsum is the lane's SHARE of the row sum: p0 joins one of the two
+            const T* bv = nkv.v + head * 64 + 4 * h;
+            using V4n = typename Op<T>::v4;
+#pragma unroll
+            for (int d = 0; d < 2; ++d)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const V4n vf = *reinterpret_cast<const V4n*>(bv + 32 * d + 8 * g);  // dv = 32 d + 8 g + 4 h + e
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[d][4 * g + e] = o[d][4 * g + e] * alpha + p0 * Op<T>::to(vf[e]);
+                }
+        }
+    }
     // ---- normalise and store ctx[b*T + q][head*64 + dv] ---------------------------------------
     const float ltot = lsum + __shfl_xor(lsum, 32, 64);
     const float inv = wave_active ? 1.0f / ltot : 0.f;  // padding-only waves: O^T is still zero
@@ -452,6 +498,26 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
     // log-sum-exp of the row in the log2 domain (the map kernels compute exp2(s - lse2))
     const int qrow = q0 + lm;
     if (lse != nullptr && h == 0 && qrow < Tseg) lse[rbase + qrow] = wave_active ? m_off + log2f(ltot) : 0.f;
+}
+
+template <typename T, int LAZY, bool BUF = true, int HACK = 0, bool X3 = false>
+__global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
+    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ vt,
+    const float* __restrict__ key_bias, const int* __restrict__ seq_info, T* __restrict__ ctx,
+    float* __restrict__ lse, int H, int BH, int nq, int Tlen, int Tp, int xcdmap, int fill_mode,
+    const int* __restrict__ any_pad, AttnSegs segs, int stagger) {
+    attn_fwd_body<T, LAZY, BUF, HACK, X3, false>(q, k, vt, key_bias, seq_info, ctx, lse, H, BH, nq, Tlen, Tp, xcdmap, fill_mode,
+                                                 any_pad, segs, stagger, NoNullKv());
+}
+
+// ESM-1: the shipped form (lazy offset, buffer-load staging) of a padded batch with the null key / value pair (NK above)
+template <typename T>
+__global__ __launch_bounds__(256, 3) void attn_fwd_nullkv_kernel(
+    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ vt,
+    const float* __restrict__ key_bias, const int* __restrict__ seq_info, T* __restrict__ ctx,
+    float* __restrict__ lse, int H, int BH, int nq, int Tlen, int Tp, NullKv<T> nkv) {
+    attn_fwd_body<T, 1, true, 0, false, true>(q, k, vt, key_bias, seq_info, ctx, lse, H, BH, nq, Tlen, Tp, 1, 0, nullptr,
+                                              AttnSegs(), 0, nkv);
 }
 
 // Self-test of Op<T>::mma_keep_c (common.h): the inline-asm MFMA with an early-clobber destination that keeps its C
@@ -513,6 +579,29 @@ hipError_t launch_attention(const void* q, const void* k, const void* vt, const 
 hipError_t launch_attention_x3(const void* q, const void* k, const void* vt, const float* key_bias, const int* seq_info, void* ctx3,
                                float* lse, int B, int H, int T, int Tp, int operand_dtype, hipStream_t st) {
     return launch_attention_impl(q, k, vt, key_bias, seq_info, ctx3, lse, B, H, T, Tp, operand_dtype, 0, nullptr, st, AttnSegs(), 0, true);
+}
+
+// ESM-1: padded batches with the learned null key / value rows bias_k, bias_v [H, 64] (attn_fwd_kernel NK)
+template <typename TT>
+static hipError_t launch_biaskv_t(const void* q, const void* k, const void* vt, const float* key_bias, const int* seq_info,
+                                  const void* bias_k, const void* bias_v, void* ctx, float* lse, int B, int H, int T, int Tp,
+                                  hipStream_t st) {
+    const int nq = (T + 127) / 128;
+    NullKv<TT> nkv{(const TT*)bias_k, (const TT*)bias_v};
+    hipLaunchKernelGGL((attn_fwd_nullkv_kernel<TT>), dim3(nq * B * H), dim3(256), 0, st, (const TT*)q, (const TT*)k,
+                       (const TT*)vt, key_bias, seq_info, (TT*)ctx, lse, H, B * H, nq, T, Tp, nkv);
+    return hipGetLastError();
+}
+
+hipError_t launch_attention_biaskv(const void* q, const void* k, const void* vt, const float* key_bias, const int* seq_info,
+                                   const void* bias_k, const void* bias_v, void* ctx, float* lse, int B, int H, int T, int Tp,
+                                   int operand_dtype, hipStream_t st) {
+    if (B <= 0 || H <= 0 || T <= 0 || Tp < T || (Tp & 63) || bias_k == nullptr || bias_v == nullptr) return hipErrorInvalidValue;
+    if (operand_dtype == ESMK_DT_BF16)
+        return launch_biaskv_t<__bf16>(q, k, vt, key_bias, seq_info, bias_k, bias_v, ctx, lse, B, H, T, Tp, st);
+    if (operand_dtype == ESMK_DT_F16)
+        return launch_biaskv_t<_Float16>(q, k, vt, key_bias, seq_info, bias_k, bias_v, ctx, lse, B, H, T, Tp, st);
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_attention_fill(const void* q, const void* k, const void* vt, const float* key_fill,

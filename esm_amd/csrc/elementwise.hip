@@ -266,6 +266,66 @@ hipError_t launch_embed(const int64_t* tokens, const float* table, const float* 
 }
 
 // ---------------------------------------------------------------------------------------------
+// ESM-1 embedding — reference esm/model/esm1.py:123 (embed_scale * gather), :125-131 (token dropout, ESM-1b's formula),
+// :133 (+ sinusoidal positions).  No pad zeroing afterwards (that is ESM-1b, :135-139): a pad row keeps its scaled
+// embedding and gets the table's zero row (modules.py:281,292-295).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void embed_esm1_kernel(const int64_t* __restrict__ tokens, const float* __restrict__ table,
+                                                          const float* __restrict__ scale, const float* __restrict__ sinus,
+                                                          float* __restrict__ x, int T, int E4, int vocab, int pad_idx,
+                                                          int mask_idx, int token_dropout, float embed_scale, size_t total4) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total4) return;
+    const size_t row = idx / E4;
+    const int c4 = (int)(idx - row * E4);
+    const int64_t tok = tokens[row];
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (tok >= 0 && tok < vocab) v = *reinterpret_cast<const f32x4*>(table + (size_t)tok * E4 * 4 + c4 * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] *= embed_scale;
+    if (token_dropout) {
+        if (tok == mask_idx) v = f32x4{0.f, 0.f, 0.f, 0.f};
+        const float den = scale[row / T];
+        const float keep = (float)(1.0 - 0.15 * 0.8);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (v[e] * keep) / den;
+    }
+    if (tok != pad_idx) {
+        const f32x4 pe = *reinterpret_cast<const f32x4*>(sinus + ((size_t)(row % T) * E4 + c4) * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] += pe[e];
+    }
+    *reinterpret_cast<f32x4*>(x + idx * 4) = v;
+}
+
+hipError_t launch_embed_esm1(const int64_t* tokens, const float* table, const float* scale, const float* sinus, float* x,
+                             int B, int T, int E, int vocab, int pad_idx, int mask_idx, int token_dropout,
+                             float embed_scale, hipStream_t st) {
+    if (E % 4 != 0) return hipErrorInvalidValue;
+    const size_t total4 = (size_t)B * T * (E / 4);
+    hipLaunchKernelGGL(embed_esm1_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, tokens, table, scale,
+                       sinus, x, T, E / 4, vocab, pad_idx, mask_idx, token_dropout, embed_scale, total4);
+    return hipGetLastError();
+}
+
+// Sinusoidal table — reference esm/modules.py:283-295 (get_embedding): angle = position x frequency as an fp32 product,
+// sin | cos halves.  Precise sinf / cosf: the angles reach ~1030 rad.
+__global__ __launch_bounds__(256) void sinus_table_kernel(const float* __restrict__ freq, float* __restrict__ table, int T,
+                                                           int half, int pos0) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= T * half) return;
+    const int t = idx / half, i = idx - t * half;
+    const float ang = (float)(pos0 + t) * freq[i];
+    table[(size_t)t * 2 * half + i] = sinf(ang);
+    table[(size_t)t * 2 * half + half + i] = cosf(ang);
+}
+
+hipError_t launch_sinus_table(const float* freq, float* table, int T, int half, int pos0, hipStream_t st) {
+    hipLaunchKernelGGL(sinus_table_kernel, dim3((unsigned)((T * half + 255) / 256)), dim3(256), 0, st, freq, table, T, half, pos0);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // LayerNorm — reference esm/modules.py:68-81 (ESM1bLayerNorm == torch.nn.LayerNorm, eps 1e-5,
 // biased variance, affine).  One wave per row, the row is held in registers (NCH float4 per
 // lane), two-pass mean / variance in fp32, 16-byte loads and 8/16-byte stores.
@@ -331,7 +391,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         s[r] = q;
     }
 #pragma unroll
-    for (int r = 0; r < RPW; ++r) rstd[r] = 1.0f / sqrtf(wave_sum(s[r]) / (float)E + 1e-5f);
+    for (int r = 0; r < RPW; ++r) rstd[r] = 1.0f / sqrtf(wave_sum(s[r]) / (float)E + ex.eps);
     const f32x4* g4 = reinterpret_cast<const f32x4*>(gamma);
     const f32x4* b4 = reinterpret_cast<const f32x4*>(beta);
 #pragma unroll

@@ -81,6 +81,11 @@ void plan_packed(esmk_model* m) {
             o.bqkv2 = c.take(3 * EA * 4);
             o.b12 = c.take(F * 4);
         }
+        if (m->esm1) o.bkv = c.take(2 * EA * os);
+    }
+    if (m->esm1) {
+        m->out_w = c.take(V * Kp * os);
+        m->out_b = c.take(V * 4);
     }
     m->packed_bytes = c.off;
 }
@@ -205,6 +210,34 @@ int ensure_rope(esmk_model* m, int T, hipStream_t st) {
     return 0;
 }
 
+// ESM-1: the sinusoidal position table for rows 0 .. T-1 (SinusoidalPositionalEmbedding.get_embedding, modules.py:283-295).
+// The half frequencies exp(j * -(ln 10000 / (half - 1))) are fp32 values of an fp32 argument, as the reference computes them
+// (correctly rounded here); angles, sin and cos on the device (sinus_table_kernel).
+int ensure_sinus(esmk_model* m, int T, hipStream_t st) {
+    if (T <= m->sinus_cap) return 0;
+    int cap = 1024;
+    while (cap < T) cap *= 2;
+    if (m->d_sinus) {
+        ESMK_TRY(hipStreamSynchronize(st));
+        ESMK_TRY(hipFree(m->d_sinus));
+        m->d_sinus = nullptr;
+        m->sinus_cap = 0;
+    }
+    const int half = m->E / 2;
+    std::vector<float> freq(half);
+    const float step = (float)(-(log(10000.0) / (double)(half - 1)));
+    for (int j = 0; j < half; ++j) freq[j] = (float)exp((double)((float)j * step));
+    float* d_freq = nullptr;
+    ESMK_TRY(hipMalloc(&m->d_sinus, (size_t)cap * m->E * 4));
+    ESMK_TRY(hipMalloc(&d_freq, (size_t)half * 4));
+    ESMK_TRY(hipMemcpy(d_freq, freq.data(), (size_t)half * 4, hipMemcpyHostToDevice));
+    ESMK_TRY(launch_sinus_table(d_freq, m->d_sinus, cap, half, m->cfg.pad_idx + 1, st));
+    ESMK_TRY(hipStreamSynchronize(st));
+    ESMK_TRY(hipFree(d_freq));
+    m->sinus_cap = cap;
+    return 0;
+}
+
 }  // namespace
 
 __global__ void fill_f32_kernel(float* p, float v, size_t n) {
@@ -278,8 +311,22 @@ int esmk_create(const esmk_config* cfg, esmk_model** out) {
         return fail("esmk_create: weight_split 4 (f16x3) needs head_dim 64 and embed_dim % 64 == 0");
     if (cfg->weight_split != 0 && cfg->operand_dtype != ESMK_F16)
         return fail("esmk_create: weight_split (precision modes f16x2 / f16x2a / f16x2v / f16x3) needs operand_dtype ESMK_F16");
+    if (cfg->no_rope < 0 || (cfg->no_rope > 1 && cfg->no_rope != ESMK_ESM1 && cfg->no_rope != (ESMK_ESM1 | ESMK_ESM1_FINAL_BIAS)))
+        return fail("esmk_create: no_rope must be 0, 1, ESMK_ESM1 (2) or ESMK_ESM1 | ESMK_ESM1_FINAL_BIAS (6): final_bias belongs to ESM-1");
+    const bool cfg_esm1 = (cfg->no_rope & ESMK_ESM1) != 0;
+    if (cfg_esm1) {  // ESM-1 (protein_bert_base): what this family does not have is refused here, before any HIP call
+        if (d != 64) return fail("esmk_create: ESM-1 (no_rope = ESMK_ESM1, bias_kv attention) needs head_dim 64, got " + std::to_string(d));
+        if (cfg->weight_split != 0)
+            return fail("esmk_create: ESM-1 (no_rope = ESMK_ESM1) runs with plain fp16 / bf16 operands only (weight_split must be 0)");
+        if (cfg->ln_fold > 0)
+            return fail("esmk_create: ESM-1 (no_rope = ESMK_ESM1) has no LayerNorm fold (LayerNorm eps 1e-12, no final LayerNorm): ln_fold "
+                        "must be 0 or -1");
+        if (cfg->num_positions != 0 || cfg->ln_before != 0)
+            return fail("esmk_create: ESM-1 (no_rope = ESMK_ESM1) has sinusoidal positions and no embedding LayerNorm: num_positions and "
+                        "ln_before must be 0");
+    }
     // LayerNorm fold: explicit request, or the library default / ESMK_LN_FOLD where the configuration supports it
-    const bool fold_ok = cfg->weight_split == 0 && d <= 64;
+    const bool fold_ok = cfg->weight_split == 0 && d <= 64 && !cfg_esm1;
     if (cfg->ln_fold > 0 && !fold_ok)
         return fail("esmk_create: ln_fold needs plain fp16 / bf16 operands (no weight_split) and head_dim <= 64");
     bool fold = cfg->ln_fold > 0;
@@ -291,6 +338,8 @@ int esmk_create(const esmk_config* cfg, esmk_model** out) {
     m->fold = fold;
     m->fold_state.assign(cfg->num_layers, 0u);
     m->cfg = *cfg;
+    m->esm1 = cfg_esm1 ? 1 : 0;
+    m->final_bias = (cfg->no_rope & ESMK_ESM1_FINAL_BIAS) ? 1 : 0;
     m->L = cfg->num_layers;
     m->E = cfg->embed_dim;
     m->H = cfg->num_heads;
@@ -311,6 +360,7 @@ void esmk_destroy(esmk_model* m) {
     if (m->d_inv_freq) (void)hipFree(m->d_inv_freq);
     if (m->d_ucos) (void)hipFree(m->d_ucos);
     if (m->d_usin) (void)hipFree(m->d_usin);
+    if (m->d_sinus) (void)hipFree(m->d_sinus);
     if (m->pk_host) (void)hipHostFree(m->pk_host);
     if (m->pk_event) (void)hipEventDestroy(m->pk_event);
     delete m;
@@ -420,6 +470,13 @@ int esmk_pack_weight(esmk_model* m, void* packed_dev, size_t packed_bytes, const
             return 0;
         }
     }
+    if (m->esm1) {  // ESM-1: untied output projection (esm1.py:111-114,174)
+        if (!strcmp(key, "embed_out")) return put2d(m->out_w, op, V, E, Kp, 0, 0);
+        if (!strcmp(key, "embed_out_bias")) {
+            if (!m->final_bias) return fail("esmk_pack_weight: embed_out_bias on an ESM-1 handle created without final_bias");
+            return put(m->out_b, ESMK_DT_F32, V);
+        }
+    }
     if (!strcmp(key, "lm_head.weight")) return 0;  // tied to embed_tokens.weight (esm2.py:71-75)
     if (!m->is_msa && m->cfg.num_positions > 0 && !strcmp(key, "embed_positions.weight"))
         return put(m->pos_emb, ESMK_DT_F32, (size_t)m->cfg.num_positions * E);
@@ -484,6 +541,9 @@ int esmk_pack_weight(esmk_model* m, void* packed_dev, size_t packed_bytes, const
             if (!strcmp(sub, "final_layer_norm.weight")) return ln_put(o.ln2g, FB_LN2G, FB_W1);
             if (!strcmp(sub, "final_layer_norm.bias")) return ln_put(o.ln2b, FB_LN2B, FB_W1);
         }
+        // ESM-1: the null key / value rows [1,1,E] = [H,64] per head, operand dtype; bias_k is NOT scaled (only q carries the scale)
+        if (m->esm1 && !strcmp(sub, "self_attn.bias_k")) return put(o.bkv, op, E);
+        if (m->esm1 && !strcmp(sub, "self_attn.bias_v")) return put(o.bkv + EA * os, op, E);
         // q/k/v: output rows are head dims -> spread over 64 slots; input columns padded to Kp
         if (!strcmp(sub, "self_attn.q_proj.weight")) return putw(o.wqkv, E, E, Kp, qkmap, 0, sp.qk);
         if (!strcmp(sub, "self_attn.k_proj.weight")) return putw(o.wqkv + EA * Kp * os * sp.qk, E, E, Kp, qkmap, 0, sp.qk);
@@ -538,6 +598,7 @@ static int check_segments(const char* who, const esmk_model* m, const int32_t* s
     const std::string w(who);
     if (!m || !seg) return fail(w + ": null argument");
     if (m->is_msa) return fail(w + ": not an ESM-2 handle");
+    if (m->esm1) return fail(w + ": ESM-1 (no_rope = ESMK_ESM1) runs padded batches only (esmk_forward); it has no token-packed form yet");
     if (n_seg <= 0 || rows <= 0) return fail(w + ": n_seg and rows must be positive");
     if (rows % 64 != 0) return fail(w + ": rows must be a multiple of 64");
     if (rows > ESMK_MAX_ROWS) return fail(w + ": rows exceed 2^24");
@@ -567,6 +628,8 @@ static int check_segments(const char* who, const esmk_model* m, const int32_t* s
 int esmk_packed_workspace_bytes(const esmk_model* m, int n_seg, int rows, uint32_t out_flags, size_t* bytes) {
     if (!m || !bytes) return fail("esmk_packed_workspace_bytes: null argument");
     if (m->is_msa) return fail("esmk_packed_workspace_bytes: not an ESM-2 handle");
+    if (m->esm1)
+        return fail("esmk_packed_workspace_bytes: ESM-1 (no_rope = ESMK_ESM1) runs padded batches only (esmk_forward); it has no token-packed form yet");
     if (n_seg <= 0 || rows <= 0 || rows % 64 != 0 || rows > ESMK_MAX_ROWS)
         return fail("esmk_packed_workspace_bytes: need n_seg > 0 and 0 < rows <= 2^24, rows % 64 == 0");
     if (out_flags & ~(uint32_t)(ESMK_OUT_LOGITS | ESMK_OUT_REPR_LOWP))
@@ -674,6 +737,9 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
     float* g32 = (float*)(ws + w.big);
     float* lse = (want_attn || fused_ct) ? (float*)(ws + w.lse) : nullptr;
 
+    const bool esm1 = m->esm1 != 0;
+    if (esm1 && pc) return fail("esmk_forward_packed: ESM-1 (no_rope = ESMK_ESM1) has no token-packed form yet");
+    if (esm1 && ensure_sinus(m, T, st)) return 1;
     const int T_rope = pc ? pc->max_len : T;  // longest run of positions
     if (m->cfg.no_rope) {
         if (ensure_unit_rope(m, T_rope, st)) return 1;
@@ -784,6 +850,7 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
         ProfScope ps(m, st, PC_LAYERNORM, 8 * NE, NE * (4 + (y ? os : 0) + (y32 ? 4 : 0)));
         LnExtra ex;
         ex.ldy = Kp;  // normalised rows are K operands: row stride = E rounded up to the 64-wide K tile
+        if (esm1) ex.eps = 1e-12f;  // ESM1LayerNorm (modules.py:44-65)
         ESMK_TRY(launch_layernorm_ex(in, (const float*)(pk + go), (const float*)(pk + bo), y, y32, N, E, op, ex, st));
         return 0;
     };
@@ -834,7 +901,12 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
         ProfScope ps(m, st, PC_EMBED, 0, (double)N * 8 + 4 * NE);
         const bool esm1b = m->cfg.num_positions > 0;
         float* keep = esm1b ? (float*)(ws + w.keep) : nullptr;
-        if (pc) {
+        if (esm1) {  // esm1.py:123-133: sqrt(E) x embedding, token dropout, + sinusoidal positions; no pad zeroing
+            ESMK_TRY(launch_seq_stats(tokens_dev, B, T, m->cfg.pad_idx, m->cfg.mask_idx, m->cfg.token_dropout, scale, key_bias,
+                                      seq_info, st, nullptr));
+            ESMK_TRY(launch_embed_esm1(tokens_dev, (const float*)(pk + m->embed_f32), scale, m->d_sinus, x, B, T, E, m->V,
+                                       m->cfg.pad_idx, m->cfg.mask_idx, m->cfg.token_dropout, (float)sqrt((double)E), st));
+        } else if (pc) {
             ESMK_TRY(launch_packed_stats(tokens_dev, (const int*)(ws + w.tables), pc->n_seg, T, m->cfg.pad_idx,
                                          m->cfg.mask_idx, scale, key_bias, row_pos, (int*)segs.npad, st, keep));
             // the token-dropout divisor is per row: "sequences" of one token
@@ -941,6 +1013,9 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
             else if (pc) ESMK_TRY(launch_attention_packed(q, k, vt, key_bias, hB, lse, H, T, w.Tp, segs, pc->n_items, op, st));
             else if (m->D == 128) ESMK_TRY(launch_attention128(q, k, vt, key_bias, seq_info, hB, lse, B, H, T, w.Tp, op, st));
             else if (x3) ESMK_TRY(launch_attention_x3(q, k, vt, key_bias, seq_info, a3, lse, B, H, T, w.Tp, op, st));
+            else if (esm1)  // T + 1 keys: the learned null key / value pair of the layer (attention.hip, NK)
+                ESMK_TRY(launch_attention_biaskv(q, k, vt, key_bias, seq_info, pk + o.bkv, pk + o.bkv + (size_t)EA * os, hB, lse, B,
+                                                 H, T, w.Tp, op, st));
             else ESMK_TRY(launch_attention(q, k, vt, key_bias, seq_info, hB, lse, B, H, T, w.Tp, op, st));
         }
         if (fused_ct && pc) {  // the same per segment (its [len,len] accumulators; segments with S <= 0 have no work)
@@ -1032,8 +1107,27 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
         } else
         if (layer_gemm(PC_GEMM_FC2, g, EPI_RESID_F32, feeds_next ? 8 + os : 8)) return 1;
         if (feeds_next && finalize()) return 1;
-        if (l + 1 < L && repr_copy(l + 1, x)) return 1;  // esm2.py:117-118
+        if ((l + 1 < L || esm1) && repr_copy(l + 1, x)) return 1;  // esm2.py:117-118; ESM-1: layer L too (no final LayerNorm)
     }
+
+    if (esm1) {
+        // esm1.py:173-175: no final LayerNorm; logits = x . embed_out^T (+ embed_out_bias): one GEMM on the rounded stream
+        if (want_logits) {
+            {
+                ProfScope ps(m, st, PC_COPY, 0, (4 + os) * NE);
+                ESMK_TRY(launch_convert(x, ESMK_DT_F32, h, op, (size_t)N * E, st));  // head_dim 64: Kp == E
+            }
+            g = GemmArgs();
+            g.A = h;
+            g.W = pk + m->out_w;
+            g.bias = m->final_bias ? (const float*)(pk + m->out_b) : nullptr;
+            g.out = logits_out_dev;
+            g.M = N;
+            g.N = m->V;
+            g.K = Kp;
+            if (gemm(PC_LM_LOGITS, g, EPI_STORE_F32, 4)) return 1;
+        }
+    } else {
 
     // esm2.py:123-128: final LayerNorm; representation L is the normalised stream
     float* rep_last = nullptr;
@@ -1098,6 +1192,7 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
         g.K = Kp;
         if (gemm(PC_LM_LOGITS, g, EPI_STORE_F32, 4)) return 1;
     }
+    }  // !esm1
     if (fused_ct && pc) {
         const CtPackedPlan& cp = *pc->ct;
         ProfScope ps(m, st, PC_CONTACTS, 0, 4.0 * ((double)cp.sum_len2 * 2 + 3.0 * L * H * T));
@@ -1483,6 +1578,20 @@ int esmk_op_attention_ex(const void* q_dev, const void* k_dev, const void* vt_de
     else
         ESMK_TRY(launch_attention(q_dev, k_dev, vt_dev, key_bias_dev, seq_info_dev, ctx_out, lse_out, B, H, T, Tp,
                                   operand_dtype, st));
+    return 0;
+}
+
+int esmk_op_attention_biaskv(const void* q_dev, const void* k_dev, const void* vt_dev, const float* key_bias_dev,
+                             const int32_t* seq_info_dev, const void* bias_k_dev, const void* bias_v_dev, void* ctx_out,
+                             float* lse_out, int B, int H, int T, int Tp, int operand_dtype, void* stream) {
+    if (!q_dev || !k_dev || !vt_dev || !bias_k_dev || !bias_v_dev || !ctx_out) return fail("esmk_op_attention_biaskv: null argument");
+    if (B <= 0 || H <= 0 || T <= 0) return fail("esmk_op_attention_biaskv: B, H and T must be positive");
+    if (Tp < T || Tp % 64 != 0) return fail("esmk_op_attention_biaskv: Tp must be a multiple of 64 and >= T");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_attention_biaskv: operand_dtype must be fp16 or bf16");
+    if (seq_info_dev && !key_bias_dev) return fail("esmk_op_attention_biaskv: seq_info needs key_bias");
+    ESMK_TRY(launch_attention_biaskv(q_dev, k_dev, vt_dev, key_bias_dev, seq_info_dev, bias_k_dev, bias_v_dev, ctx_out, lse_out, B,
+                                     H, T, Tp, operand_dtype, (hipStream_t)stream));
     return 0;
 }
 

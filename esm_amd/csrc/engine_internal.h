@@ -30,6 +30,7 @@ struct Carve {
 struct LayerOff {
     size_t wqkv, bqkv, wo, bo, w1, b1, w2, b2, ln1g, ln1b, ln2g, ln2b;
     size_t bqkv2 = 0, b12 = 0;  // LayerNorm fold: W . beta of the folded q/k/v and fc1 weights (GemmArgs::bias2)
+    size_t bkv = 0;             // ESM-1: self_attn.bias_k | bias_v, [H,64] each, operand dtype
 };
 // one AxialTransformerLayer (reference esm/modules.py:145-221)
 struct AttnOff {
@@ -93,6 +94,11 @@ struct esmk_model {
     int npos = 0, has_msa_pos = 0;
     size_t pos_emb = 0, msa_pos = 0, lnb_g = 0, lnb_b = 0;
     std::vector<esmk_host::MsaLayerOff> mlayer;
+    // ESM-1 (esmk_config::no_rope = ESMK_ESM1 [| ESMK_ESM1_FINAL_BIAS]): embed_out [V,Kp] operand dtype, embed_out_bias [V] fp32; the sinusoidal table [sinus_cap, E]
+    int esm1 = 0, final_bias = 0;
+    size_t out_w = 0, out_b = 0;
+    float* d_sinus = nullptr;
+    int sinus_cap = 0;
     float* d_ucos = nullptr;  // "unit" rotary tables (cos = 1, sin = 0): the MSA model has no RoPE
     float* d_usin = nullptr;
     int unit_cap = 0;

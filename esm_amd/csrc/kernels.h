@@ -143,6 +143,13 @@ hipError_t launch_scale_rows(float* x, const float* keep, int rows, int E, hipSt
 hipError_t launch_embed(const int64_t* tokens, const float* table, const float* scale, float* x,
                         int B, int T, int E, int vocab, int pad_idx, int mask_idx,
                         int token_dropout, hipStream_t st);
+// ESM-1 embedding (esm1.py:123-133): x = embed_scale * embed[tok], token dropout as above, + sinus[t] on non-pad tokens
+// (SinusoidalPositionalEmbedding, modules.py:260-295: position pad_idx + 1 + t, pads take the zero row); no pad zeroing
+hipError_t launch_embed_esm1(const int64_t* tokens, const float* table, const float* scale, const float* sinus, float* x,
+                             int B, int T, int E, int vocab, int pad_idx, int mask_idx, int token_dropout,
+                             float embed_scale, hipStream_t st);
+// sinus[t][0 .. half) = sin((pos0 + t) freq[i]), [half .. 2 half) = cos(...), fp32, precise sinf / cosf; row stride 2 half
+hipError_t launch_sinus_table(const float* freq, float* table, int T, int half, int pos0, hipStream_t st);
 // LayerNorm(E, eps=1e-5) (modules.py:68-81): fp32 rows -> operand-dtype and/or fp32 rows
 hipError_t launch_layernorm(const float* x, const float* gamma, const float* beta, void* y,
                             float* y32, int rows, int E, int operand_dtype, hipStream_t st);
@@ -160,6 +167,7 @@ struct LnExtra {
     int map_R = 0, map_C = 0;
     int ldy = 0;  // row stride of the operand-dtype output in elements (0 = E): K-padded activation rows
     int x3 = 0;   // precision mode f16x3: y rows in the hi | hi | lo layout per 64-column K tile (ldy >= 3 E), lo = T(o - T(o))
+    float eps = 1e-5f;  // 1e-12 for ESM-1 (ESM1LayerNorm, modules.py:44-65: the same formula)
 };
 hipError_t launch_layernorm_ex(const float* x, const float* gamma, const float* beta, void* y,
                                float* y32, int rows, int E, int operand_dtype, LnExtra ex,
@@ -290,6 +298,11 @@ hipError_t launch_attention(const void* q, const void* k, const void* vt, const 
                             int operand_dtype, hipStream_t st);
 hipError_t launch_attention_x3(const void* q, const void* k, const void* vt, const float* key_bias, const int* seq_info, void* ctx3,
                                float* lse, int B, int H, int T, int Tp, int operand_dtype, hipStream_t st);
+// ESM-1 (add_bias_kv): the same padded-batch kernel with one learned null key / value pair per head, bias_k / bias_v [H, 64] in
+// the operand dtype (bias_k unscaled); ctx and lse include it (attn_fwd_kernel NK)
+hipError_t launch_attention_biaskv(const void* q, const void* k, const void* vt, const float* key_bias, const int* seq_info,
+                                   const void* bias_k, const void* bias_v, void* ctx, float* lse, int B, int H, int T, int Tp,
+                                   int operand_dtype, hipStream_t st);
 // attention128.hip: head_dim 128 (esm2_t48_15B)
 hipError_t launch_attention128(const void* q, const void* k, const void* vt, const float* key_bias,
                                const int* seq_info, void* ctx, float* lse, int B, int H, int T, int Tp,

@@ -237,6 +237,14 @@ class _Engine:
         self.no_rope = int(getattr(model, "_engine_no_rope", 0))
         num_positions = int(getattr(model, "_engine_num_positions", 0))
         ln_before = int(getattr(model, "_engine_ln_before", 0))
+        # ESM-1 (esm_amd.esm1.ProteinBertModel, arch protein_bert_base): esmk_config.no_rope = ESMK_ESM1 (| ESMK_ESM1_FINAL_BIAS)
+        esm1 = int(getattr(model, "_engine_esm1", 0))
+        if esm1 and self.weight_split:
+            raise RuntimeError(
+                f"ESM_AMD_OPERAND={os.environ.get('ESM_AMD_OPERAND', '')}: the split-operand precision modes (f16x2*, f16x3) are not "
+                "available for ESM-1 models (bias_kv attention); use f16 or bf16")
+        if esm1:
+            self.no_rope = N.ESM1 | (N.ESM1_FINAL_BIAS if getattr(model, "_engine_final_bias", 0) else 0)
         cfg = N.EsmkConfig(
             model.num_layers, model.embed_dim, model.attention_heads, int(getattr(model, "ffn_embed_dim", 4 * model.embed_dim)),
             model.alphabet_size, model.padding_idx, model.mask_idx, model.cls_idx, model.eos_idx,
@@ -543,8 +551,9 @@ class ESM2(nn.Module):
         if contacts_only:
             return_contacts = True
         plan = pack_plan(tokens, self.padding_idx, lengths)
-        if unpack and ((min_saving is not None and plan.rows > (1.0 - min_saving) * B * T) or _weight_split() == 4):
-            # (f16x3 has no token-packed form)
+        if unpack and ((min_saving is not None and plan.rows > (1.0 - min_saving) * B * T) or _weight_split() == 4
+                       or getattr(self, "_engine_esm1", 0)):
+            # (f16x3 and the ESM-1 models have no token-packed form)
             if return_contacts:
                 out = self.forward(tokens.to(dev), repr_layers=repr_layers, contacts_only=True)
                 if not contacts_only:

@@ -133,6 +133,25 @@ def attention(q, k, vt, key_bias=None, want_lse=False, seq_info=None, fill_any_p
     return (ctx, lse / LOG2E) if want_lse else ctx  # the kernel's lse is log2-domain
 
 
+def attention_biaskv(q, k, vt, bias_k, bias_v, key_bias=None, seq_info=None):
+    """``attention`` (D = 64, padded-batch form) with the learned null key / value pair of the ESM-1 models: bias_k, bias_v
+    [H,64] in the operand dtype (bias_k unscaled); T + 1 keys per row, the extra one never masked.  Returns ctx [B*T, H*64]
+    and the natural-log row log-sum-exp [B,H,T], both INCLUDING the null key."""
+    _req_cuda(q, k, vt, bias_k, bias_v, key_bias, seq_info)
+    B, H, T, D = q.shape
+    assert D == 64 and vt.shape[-2] == 64 and vt.shape[-1] % 64 == 0 and vt.shape[-1] >= T
+    assert tuple(bias_k.shape) == (H, 64) and tuple(bias_v.shape) == (H, 64) and bias_k.dtype == bias_v.dtype == q.dtype
+    assert bias_k.is_contiguous() and bias_v.is_contiguous()
+    if seq_info is not None:
+        assert seq_info.dtype == torch.int32 and tuple(seq_info.shape) == (B, 2)
+    lse = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
+    ctx = torch.empty((B * T, H * 64), dtype=q.dtype, device=q.device)
+    N.check(N.lib.esmk_op_attention_biaskv(N.ptr(q), N.ptr(k), N.ptr(vt), N.ptr(key_bias), N.ptr(seq_info), N.ptr(bias_k),
+                                           N.ptr(bias_v), N.ptr(ctx), N.ptr(lse), B, H, T, vt.shape[-1],
+                                           N.dtype_code(q.dtype), N.cur_stream()))
+    return ctx, lse / LOG2E
+
+
 def attention_probs(q, k, lse, key_bias=None, out=None, layer=0, num_layers=1, fill_any_pad=None, msa_C=0,
                     out_dtype=torch.float32):
     """q in the log2 domain; lse: natural-log row log-sum-exp as returned by ``attention(..., want_lse=True)``.

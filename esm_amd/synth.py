@@ -295,3 +295,59 @@ def synth_esm1b_state_dict(num_layers, embed_dim, heads, ffn_dim=None, seed=0, q
     sd["embed_tokens.weight"][32] = 0.0  # pretrained.py:97 zeroes the <mask> row for token dropout
     sd["lm_head.weight"] = sd["embed_tokens.weight"]
     return sd
+
+
+# ---------------------------------------------------------------------------------------------------
+# ESM-1 (reference esm/model/esm1.py, arch "protein_bert_base")
+# ---------------------------------------------------------------------------------------------------
+def synth_esm1_state_dict(num_layers, embed_dim, heads, seed=0, final_bias=False, qk_gain=2.0, null_gain=8.0, vocab=35):
+    """fp32 ESM-1 state dict with the reference's key names: the layer stack of ESM-2 without rot_emb.inv_freq, plus
+    ``self_attn.bias_k`` / ``bias_v`` per layer, ``embed_positions._float_tensor``, the untied ``embed_out`` and (``final_bias``)
+    ``embed_out_bias``; no emb_layer_norm_after, no lm_head.
+
+    The null key must MATTER (random weights give a near-uniform softmax in which it would hold 1 / (T + 1) of a row, and a
+    kernel that dropped it would pass every bound): the q-projection biases are drawn at std 0.5, and each head's ``bias_k`` is
+    ``null_gain`` times the unit vector along that head's q bias plus unit-variance noise / 4, so q . bias_k has a positive
+    constant part of d^-1/2 null_gain |b_q,head|; ``bias_v`` has the scale of the value rows.  The token embedding is drawn at
+    std 0.5 / sqrt(E): the model multiplies it by sqrt(E)."""
+    E, d = embed_dim, embed_dim // heads
+    base = synth_esm2_state_dict(num_layers, E, heads, seed=seed, qk_gain=qk_gain, vocab=vocab)
+    sd = {k: v for k, v in base.items()
+          if not (k.endswith("inv_freq") or k.startswith("lm_head.") or k.startswith("emb_layer_norm_after."))}
+    sd["embed_tokens.weight"] = _draw("embed_tokens.weight", (vocab, E), seed, 0.5 / E ** 0.5)
+    sd["embed_positions._float_tensor"] = torch.zeros(1)
+    for i in range(num_layers):
+        p = f"layers.{i}.self_attn."
+        bq = _draw(p + "q_proj.bias", (E,), seed, 0.5)
+        sd[p + "q_proj.bias"] = bq
+        unit = bq.view(heads, d) / bq.view(heads, d).norm(dim=-1, keepdim=True)
+        bk = null_gain * unit + 0.25 * _draw(p + "bias_k", (heads, d), seed, 1.0)
+        sd[p + "bias_k"] = bk.reshape(1, 1, E).contiguous()
+        sd[p + "bias_v"] = _draw(p + "bias_v", (1, 1, E), seed, 0.7)
+    sd["embed_out"] = _draw("embed_out", (vocab, E), seed, 0.25)
+    if final_bias:
+        sd["embed_out_bias"] = _draw("embed_out_bias", (vocab,), seed, 0.5)
+    return sd
+
+
+def esm1_args(num_layers, embed_dim, heads, final_bias=False, token_dropout=False, prefix=""):
+    """The hyper-parameters an ESM-1 checkpoint carries (``prefix`` "decoder_": as stored in the released files)."""
+    a = dict(layers=num_layers, embed_dim=embed_dim, ffn_embed_dim=4 * embed_dim, attention_heads=heads, final_bias=final_bias)
+    ns = argparse.Namespace(arch="protein_bert_base", token_dropout=token_dropout)
+    for k, v in a.items():
+        setattr(ns, prefix + k, v)
+    return ns
+
+
+def write_esm1_checkpoint(directory, name, num_layers, embed_dim, heads, seed=0, final_bias=False, token_dropout=False):
+    """Write ``<name>.pt`` + ``<name>-contact-regression.pt`` in the format of the released ESM-1 checkpoints
+    (``{"args": Namespace(arch="protein_bert_base", decoder_<name>...), "model": {"decoder.<key>": tensor}}``, reference
+    esm/pretrained.py:103-110)."""
+    os.makedirs(directory, exist_ok=True)
+    sd = synth_esm1_state_dict(num_layers, embed_dim, heads, seed=seed, final_bias=final_bias)
+    regression = {k: v for k, v in sd.items() if k.startswith("contact_head.")}
+    body = {"decoder." + k: v for k, v in sd.items() if not k.startswith("contact_head.")}
+    path = os.path.join(directory, name + ".pt")
+    torch.save({"args": esm1_args(num_layers, embed_dim, heads, final_bias, token_dropout, prefix="decoder_"), "model": body}, path)
+    torch.save({"model": regression}, os.path.join(directory, name + "-contact-regression.pt"))
+    return path

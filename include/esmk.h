@@ -50,6 +50,21 @@ typedef struct esmk_model esmk_model;
 
 /* Model hyper-parameters: the constructor arguments of ESM2 (esm/model/esm2.py:15-38) plus the
  * alphabet ids it copies from the Alphabet (esm/data.py:116-120). */
+/* esmk_config::no_rope values above 1: the original ESM-1 models (arch "protein_bert_base", reference
+ * esm/model/esm1.py:107-114).  They ride in this field because the struct has no size field and its layout is pinned
+ * (18 int32_t = 72 bytes): a caller built against it keeps working, and 0 / 1 keep their meaning.
+ * ESMK_ESM1: token embedding x sqrt(embed_dim); sinusoidal positions (sin | cos halves, position pad_idx + 1 + t, pads take
+ * the zero row; the table is built by the engine) instead of a learned table; no embedding LayerNorm and no pad zeroing;
+ * LayerNorm eps 1e-12; every attention layer has one learned null key / value pair (packed keys
+ * layers.N.self_attn.bias_k / bias_v, [1,1,E]; never masked); no final LayerNorm — representation num_layers is the raw
+ * stream — and logits = x . embed_out^T (packed key embed_out [vocab,E]).  Attention maps drop the null key's column (rows sum
+ * to less than 1), as the reference returns them.
+ * ESMK_ESM1_FINAL_BIAS (only together with ESMK_ESM1): args.final_bias — embed_out_bias [vocab] is added to the logits.
+ * Needs head_dim 64, weight_split 0, num_positions 0, ln_before 0; the LayerNorm fold does not exist for these models
+ * (ln_fold 0 resolves to off, ln_fold 1 fails) and neither does the token-packed form (esmk_forward_packed* fail). */
+#define ESMK_ESM1 2
+#define ESMK_ESM1_FINAL_BIAS 4
+
 typedef struct esmk_config {
     int32_t num_layers;      /* L                                                        */
     int32_t embed_dim;       /* E                                                        */
@@ -63,7 +78,9 @@ typedef struct esmk_config {
                                 residual stream, LayerNorm, softmax are always fp32     */
     /* ESM-1b / ESM-1v (ProteinBertModel with arch "roberta_large", esm/model/esm1.py:88-104,117-143); all
      * zero for ESM-2 */
-    int32_t no_rope;         /* 1: no rotary embedding (TransformerLayer(use_rotary_embeddings=False)) */
+    int32_t no_rope;         /* 1: no rotary embedding (TransformerLayer(use_rotary_embeddings=False));
+                                ESMK_ESM1 (2), or ESMK_ESM1 | ESMK_ESM1_FINAL_BIAS (6): the original ESM-1 architecture, see
+                                above (no rotary embedding either)                                     */
     int32_t num_positions;   /* > 0: rows of the LearnedPositionalEmbedding table added to the token embedding
                                 (esm1.py:133, modules.py:240-257); key "embed_positions.weight"   */
     int32_t ln_before;       /* 1: emb_layer_norm_before (esm1.py:136-137)                          */
@@ -370,6 +387,13 @@ int esmk_op_attention_probs(const void* q_dev, const void* k_dev, const float* l
 int esmk_op_attention_ex(const void* q_dev, const void* k_dev, const void* vt_dev, const float* key_bias_dev,
                          const int32_t* seq_info_dev, const int32_t* any_pad_dev, void* ctx_out, float* lse_out, int B,
                          int H, int T, int Tp, int head_dim, int mode, int operand_dtype, void* stream);
+/* esmk_op_attention_ex mode 0 (head_dim 64, padded batch) with the learned null key / value pair of the ESM-1 models:
+ * bias_k_dev / bias_v_dev [H,64] in the operand dtype, bias_k in k's domain (unscaled: q carries d^-1/2 log2 e).  Every query
+ * row sees T + 1 keys, the extra one never masked; ctx_out and lse_out include it, so esmk_op_attention_probs* on the same
+ * q / k / lse give the maps with the null column dropped. */
+int esmk_op_attention_biaskv(const void* q_dev, const void* k_dev, const void* vt_dev, const float* key_bias_dev,
+                             const int32_t* seq_info_dev, const void* bias_k_dev, const void* bias_v_dev, void* ctx_out,
+                             float* lse_out, int B, int H, int T, int Tp, int operand_dtype, void* stream);
 /* Probabilities of every form: msa_C = 0 is the ESM-2 layout probs_out [B, Ltot, H, T, T] (rows / cols of padded
  * tokens zeroed, head_dim 64 or 128, out_dtype fp32 or the operand dtype); msa_C > 0 is the MSA column layout
  * [B / msa_C, Ltot, H, msa_C, T, T] (B = batch x columns, key_bias = fill flags with any_pad_dev as in mode 1, query rows
