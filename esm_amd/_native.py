@@ -113,6 +113,15 @@ SIGNATURES = {
             c_uint32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
         ],
     ),
+    "esmk_packed_workspace_bytes_maps": (c_int, [c_void_p, POINTER(c_int32), c_int, c_int, c_uint32, POINTER(c_size_t)]),
+    "esmk_forward_packed_maps": (
+        c_int,
+        [
+            c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_int, c_int,
+            POINTER(c_int32), c_int, POINTER(c_void_p),
+            c_uint32, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p,
+        ],
+    ),
     "esmk_msa_create": (c_int, [POINTER(EsmkMsaConfig), POINTER(c_void_p)]),
     "esmk_msa_workspace_bytes": (c_int, [c_void_p, c_int, c_int, c_int, c_uint32, POINTER(c_size_t)]),
     "esmk_msa_forward": (
@@ -181,6 +190,16 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
          c_int, c_int, c_void_p],
+    ),
+    "esmk_op_attention_packed": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "esmk_op_attention_probs_packed": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+         c_void_p, c_size_t, c_void_p],
     ),
     "esmk_op_contacts_fused_workspace_bytes_ex": (
         c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int32), c_int, c_int, c_int, c_int, POINTER(c_size_t)]),

@@ -34,6 +34,7 @@
 // attn_probs_kernel: re-computes S tile by tile from q, k and the saved log-sum-exp and writes
 // normalised fp32 probabilities for need_head_weights=True / the contact head
 // (multihead_attention.py:396-403, esm2.py:119-121,132-139) with padded rows/cols zeroed.
+// attn_probs_packed_kernel: the same per segment of a token-packed batch, into ragged [L,H,len,len] blocks (end of file).
 #include "common.h"
 #include "kernels.h"
 #include <math.h>
@@ -800,6 +801,145 @@ hipError_t launch_attention_probs_msa(const void* q, const void* k, const float*
                                       int layer, int num_layers_total, int operand_dtype, hipStream_t st) {
     return launch_probs_impl(q, k, lse, key_fill, probs, Bmsa * C, H, R, layer, num_layers_total, operand_dtype,
                              C, any_pad, st);
+}
+
+// ---------------------------------------------------------------------------------------------
+// attention probabilities of a token-packed batch (multihead_attention.py:396-403, esm2.py:132-139 per sequence)
+// ---------------------------------------------------------------------------------------------
+// attn_probs_kernel on the packed row space: workgroup (head, item) takes work item `item` of the attention launch's
+// list (a 128-query block of one segment; longest segments first), its waves 32 query rows each from row0 + qrel, the
+// key loop covers the segment's own rows only, and the map goes to the segment's ragged [Ltot, H, len, len] block.  The
+// arithmetic per element is attn_probs_kernel's — the same four MFMAs over the 64 dims, s + bias, exp2(s - lse) — and
+// lse is the packed attention kernel's, which is the padded one's bit for bit: so is every probability.  key_bias is
+// read only for segments that contain <pad> tokens (adding the 0.0 of a real key changes no probability bit).
+// Consecutive workgroups share (head, segment): the K rows of a segment stay in the L2 while its query blocks run.
+template <typename T, typename O = float>
+__global__ __launch_bounds__(256) void attn_probs_packed_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                 const float* __restrict__ lse,
+                                                                 const float* __restrict__ key_bias, O* __restrict__ probs,
+                                                                 int H, int rows, int layer, int Ltot, int n_items,
+                                                                 AttnSegs segs,
+                                                                 const unsigned long long* __restrict__ map_off) {
+    using V8 = typename Op<T>::v8;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int h = lane >> 5, lm = lane & 31;
+    const int head = blockIdx.x / n_items, item = blockIdx.x - head * n_items;
+    const int row0 = __builtin_amdgcn_readfirstlane(segs.work[4 * item]);
+    const int Tseg = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 1]);
+    const int qrel = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 2]);
+    const int seg = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 3]);
+    const int q0 = qrel + wave * 32;
+    if (q0 >= Tseg) return;
+    if (segs.npad[seg] <= 0) key_bias = nullptr;
+    const size_t rbase = (size_t)head * rows + row0;  // first row of the segment in the [H, rows] row spaces
+
+    V8 qf[4];
+    {
+        const int qr = min(q0 + lm, Tseg - 1);
+        const T* qp = q + (rbase + qr) * 64 + 8 * h;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const V8*>(qp + 16 * ks);
+    }
+    float row_lse[16];
+    float row_keep[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int qc = min(q0 + mfma32_row(r, h), Tseg - 1);
+        row_lse[r] = lse[rbase + qc];
+        row_keep[r] = (key_bias != nullptr && key_bias[(size_t)row0 + qc] != 0.f) ? 0.f : 1.f;
+    }
+    const size_t plane = (size_t)Tseg * Tseg;
+    O* out = probs + (size_t)Ltot * H * (size_t)map_off[seg] + ((size_t)layer * H + head) * plane;
+
+    for (int k0 = 0; k0 < Tseg; k0 += 32) {
+        const int key = k0 + lm;
+        const int kc = min(key, Tseg - 1);
+        const T* kp = k + (rbase + kc) * 64 + 8 * h;
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const V8 kf = *reinterpret_cast<const V8*>(kp + 16 * ks);
+            s = Op<T>::mma(qf[ks], kf, s);  // D[row = query][col = key]
+        }
+        const float kb = (key_bias != nullptr) ? key_bias[(size_t)row0 + kc] : 0.f;
+        if (key < Tseg) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int qr = q0 + mfma32_row(r, h);
+                if (qr < Tseg) {
+                    // <pad> query rows: a select, not a multiply by 0 (see attn_probs_kernel)
+                    const float p = row_keep[r] != 0.f ? __builtin_amdgcn_exp2f(s[r] + kb - row_lse[r]) : 0.f;
+                    out[(size_t)qr * Tseg + key] = (O)p;
+                }
+            }
+        }
+    }
+}
+
+hipError_t launch_attention_probs_packed(const void* q, const void* k, const float* lse, const float* key_bias, void* probs,
+                                         int H, int rows, int layer, int num_layers_total, AttnSegs segs,
+                                         const unsigned long long* map_off, int n_items, int operand_dtype, bool lowp,
+                                         hipStream_t st) {
+    if (segs.work == nullptr || segs.npad == nullptr || map_off == nullptr || n_items <= 0 || H <= 0 || rows <= 0 ||
+        (long long)n_items * H > 0x7fffffffLL)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)n_items * (unsigned)H);
+#define ESMK_PROBS_PACKED(TT, OO)                                                                                     \
+    hipLaunchKernelGGL((attn_probs_packed_kernel<TT, OO>), grid, dim3(256), 0, st, (const TT*)q, (const TT*)k, lse,   \
+                       key_bias, (OO*)probs, H, rows, layer, num_layers_total, n_items, segs, map_off)
+    if (operand_dtype == ESMK_DT_BF16) {
+        if (lowp) ESMK_PROBS_PACKED(__bf16, __bf16);
+        else ESMK_PROBS_PACKED(__bf16, float);
+    } else if (operand_dtype == ESMK_DT_F16) {
+        if (lowp) ESMK_PROBS_PACKED(_Float16, _Float16);
+        else ESMK_PROBS_PACKED(_Float16, float);
+    } else {
+        return hipErrorInvalidValue;
+    }
+#undef ESMK_PROBS_PACKED
+    return hipGetLastError();
+}
+
+// npad of a packed batch from its key_bias alone (the engine counts <pad> tokens in launch_packed_stats)
+__global__ __launch_bounds__(64) void seg_npad_kernel(const float* __restrict__ key_bias, const int* __restrict__ seg,
+                                                     int* __restrict__ npad) {
+    const int s = blockIdx.x, row0 = seg[2 * s], len = seg[2 * s + 1];
+    int n = 0;
+    if (key_bias != nullptr)
+        for (int i = threadIdx.x; i < len; i += 64) n += key_bias[(size_t)row0 + i] != 0.f ? 1 : 0;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) n += __shfl_xor(n, d, 64);
+    if (threadIdx.x == 0) npad[s] = n;
+}
+
+// Segments made of padding only (npad == length): ctx rows and lse := 0, what the padded kernels give such a sequence
+// through seq_info (kv_end = 0: no wave is active).  The packed kernels divide by a zero row sum there.
+__global__ __launch_bounds__(256) void zero_allpad_segments_kernel(char* __restrict__ ctx, float* __restrict__ lse,
+                                                                   const int* __restrict__ seg, const int* __restrict__ npad,
+                                                                   int H, int rows, int row_bytes) {
+    const int s = blockIdx.x, row0 = seg[2 * s], len = seg[2 * s + 1];
+    if (npad[s] < len) return;
+    const size_t n = (size_t)len * row_bytes;
+    char* dst = ctx + (size_t)row0 * row_bytes;
+    for (size_t i = threadIdx.x; i < n; i += 256) dst[i] = 0;
+    if (lse != nullptr)
+        for (int i = threadIdx.x; i < H * len; i += 256) lse[(size_t)(i / len) * rows + row0 + i % len] = 0.f;
+}
+
+hipError_t launch_zero_allpad_segments(void* ctx, float* lse, const int* seg, const int* npad, int n_seg, int H, int rows,
+                                       size_t row_bytes, hipStream_t st) {
+    if (ctx == nullptr || seg == nullptr || npad == nullptr || n_seg <= 0 || row_bytes > 0x7fffffffu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(zero_allpad_segments_kernel, dim3(n_seg), dim3(256), 0, st, (char*)ctx, lse, seg, npad, H, rows,
+                       (int)row_bytes);
+    return hipGetLastError();
+}
+
+hipError_t launch_seg_npad(const float* key_bias, const int* seg, int n_seg, int* npad, hipStream_t st) {
+    if (seg == nullptr || npad == nullptr || n_seg <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(seg_npad_kernel, dim3(n_seg), dim3(64), 0, st, key_bias, seg, npad);
+    return hipGetLastError();
 }
 
 }  // namespace esmk

@@ -357,4 +357,91 @@ hipError_t launch_attention_probs128(const void* q, const void* k, const float* 
     return hipGetLastError();
 }
 
+// The same for a token-packed batch: attn_probs_packed_kernel (attention.hip) with the eight MFMAs of a 128-wide head.
+// One workgroup = (head, work item of the attention launch); ragged [Ltot, H, len, len] block per segment at
+// Ltot * H * map_off[segment]; every element carries attn_probs128_kernel's bits for the same sequence in a padded batch.
+template <typename T, typename O = float>
+__global__ __launch_bounds__(256) void attn_probs128_packed_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                    const float* __restrict__ lse,
+                                                                    const float* __restrict__ key_bias,
+                                                                    O* __restrict__ probs, int H, int rows, int layer,
+                                                                    int Ltot, int n_items, AttnSegs segs,
+                                                                    const unsigned long long* __restrict__ map_off) {
+    using V8 = typename Op<T>::v8;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int h = lane >> 5, lm = lane & 31;
+    const int head = blockIdx.x / n_items, item = blockIdx.x - head * n_items;
+    const int row0 = __builtin_amdgcn_readfirstlane(segs.work[4 * item]);
+    const int Tseg = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 1]);
+    const int qrel = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 2]);
+    const int seg = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 3]);
+    const int q0 = qrel + wave * 32;
+    if (q0 >= Tseg) return;
+    if (segs.npad[seg] <= 0) key_bias = nullptr;
+    const size_t rbase = (size_t)head * rows + row0;
+    V8 qf[8];
+    {
+        const int qr = min(q0 + lm, Tseg - 1);
+        const T* qp = q + (rbase + qr) * HD + 8 * h;
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) qf[ks] = *reinterpret_cast<const V8*>(qp + 16 * ks);
+    }
+    float row_lse[16], row_keep[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int qc = min(q0 + mfma32_row(r, h), Tseg - 1);
+        row_lse[r] = lse[rbase + qc];
+        row_keep[r] = (key_bias != nullptr && key_bias[(size_t)row0 + qc] != 0.f) ? 0.f : 1.f;
+    }
+    const size_t plane = (size_t)Tseg * Tseg;
+    O* out = probs + (size_t)Ltot * H * (size_t)map_off[seg] + ((size_t)layer * H + head) * plane;
+    for (int k0 = 0; k0 < Tseg; k0 += 32) {
+        const int key = k0 + lm;
+        const int kc = min(key, Tseg - 1);
+        const T* kp = k + (rbase + kc) * HD + 8 * h;
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+            const V8 kf = *reinterpret_cast<const V8*>(kp + 16 * ks);
+            s = Op<T>::mma(qf[ks], kf, s);
+        }
+        const float kbv = (key_bias != nullptr) ? key_bias[(size_t)row0 + kc] : 0.f;
+        if (key < Tseg) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int qr = q0 + mfma32_row(r, h);
+                // <pad> query rows: a select, not a multiply by 0 (see attn_probs128_kernel)
+                if (qr < Tseg)
+                    out[(size_t)qr * Tseg + key] = (O)(row_keep[r] != 0.f ? __builtin_amdgcn_exp2f(s[r] + kbv - row_lse[r]) : 0.f);
+            }
+        }
+    }
+}
+
+hipError_t launch_attention_probs128_packed(const void* q, const void* k, const float* lse, const float* key_bias,
+                                            void* probs, int H, int rows, int layer, int num_layers_total, AttnSegs segs,
+                                            const unsigned long long* map_off, int n_items, int operand_dtype, bool lowp,
+                                            hipStream_t st) {
+    if (segs.work == nullptr || segs.npad == nullptr || map_off == nullptr || n_items <= 0 || H <= 0 || rows <= 0 ||
+        (long long)n_items * H > 0x7fffffffLL)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)n_items * (unsigned)H);
+#define ESMK_PROBS128_PACKED(TT, OO)                                                                                    \
+    hipLaunchKernelGGL((attn_probs128_packed_kernel<TT, OO>), grid, dim3(256), 0, st, (const TT*)q, (const TT*)k, lse, \
+                       key_bias, (OO*)probs, H, rows, layer, num_layers_total, n_items, segs, map_off)
+    if (operand_dtype == ESMK_DT_BF16) {
+        if (lowp) ESMK_PROBS128_PACKED(__bf16, __bf16);
+        else ESMK_PROBS128_PACKED(__bf16, float);
+    } else if (operand_dtype == ESMK_DT_F16) {
+        if (lowp) ESMK_PROBS128_PACKED(_Float16, _Float16);
+        else ESMK_PROBS128_PACKED(_Float16, float);
+    } else {
+        return hipErrorInvalidValue;
+    }
+#undef ESMK_PROBS128_PACKED
+    return hipGetLastError();
+}
+
 }  // namespace esmk

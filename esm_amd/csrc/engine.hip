@@ -109,6 +109,9 @@ struct PackedCtx {
     double sum_len2 = 0;                // sum of len^2: the attention work
     const int32_t* seg_host = nullptr;  // [n_seg][2] = (first row, length)
     const CtPackedPlan* ct = nullptr;   // contacts (esmk_forward_packed_ex): scratch sizes and work lists
+    // attention maps (esmk_forward_packed_maps): ragged [L, H, len, len] blocks in maps_out, fp32 or the operand dtype
+    bool maps = false, maps_lowp = false;
+    void* maps_out = nullptr;
 };
 // query blocks of 128 rows: sum over segments of ceil(len / 128) <= rows / 128 + n_seg
 inline size_t packed_items_bound(int n_seg, int rows) { return (size_t)rows / 128 + (size_t)n_seg; }
@@ -118,8 +121,9 @@ inline size_t packed_ct_table_base(int n_seg, int rows) {
 }
 
 // ct: token-packed batch with ESMK_OUT_CONTACTS (flags must then hold it): per-segment contact scratch
+// packed_maps: token-packed batch with attention maps: lse and the 64-bit map offsets; nothing that grows with Tmax^2
 Workspace plan_workspace(const esmk_model* m, int B, int T, uint32_t flags, int packed_segs = 0,
-                         const CtPackedPlan* ct = nullptr) {
+                         const CtPackedPlan* ct = nullptr, bool packed_maps = false) {
     Workspace w{};
     const size_t os = op_size(m->cfg.operand_dtype);
     const size_t N = (size_t)B * T, E = m->E, F = m->F, EA = m->EA, Kp = m->Kp;
@@ -156,7 +160,7 @@ Workspace plan_workspace(const esmk_model* m, int B, int T, uint32_t flags, int 
     w.q = w.big;
     w.k = w.big + qb;
     w.vt = w.big + 2 * qb;
-    const bool attn = flags & (ESMK_OUT_ATTN | ESMK_OUT_CONTACTS);
+    const bool attn = (flags & (ESMK_OUT_ATTN | ESMK_OUT_CONTACTS)) || packed_maps;
     w.lse = c.take(attn ? (size_t)B * m->H * T * 4 : 0);
     const int S = T - (m->cfg.prepend_bos ? 1 : 0) - (m->cfg.append_eos ? 1 : 0);
     // ESMK_OUT_CONTACTS without ESMK_OUT_ATTN: no [B,L,H,T,T] tensor anywhere (contacts.hip)
@@ -183,8 +187,10 @@ Workspace plan_workspace(const esmk_model* m, int B, int T, uint32_t flags, int 
     if (packed_segs > 0) {
         w.row_pos = c.take(N * 4);
         // [seg 2 n_seg][npad n_seg][work 4 n_items] and, with contacts, the contact tables (kernels.h, CtPackedPlan)
-        w.tables = c.take(ct != nullptr ? (packed_ct_table_base(packed_segs, T) + ct->table_ints()) * 4
-                                        : ((size_t)3 * packed_segs + 4 * packed_items_bound(packed_segs, T)) * 4);
+        // and, with attention maps, the segments' map offsets (uint64 [n_seg], 8-byte aligned) behind all of it
+        const size_t ints = ct != nullptr ? packed_ct_table_base(packed_segs, T) + ct->table_ints()
+                                          : (size_t)3 * packed_segs + 4 * packed_items_bound(packed_segs, T);
+        w.tables = c.take((packed_maps ? ((ints + 1) & ~(size_t)1) + 2 * (size_t)packed_segs : ints) * 4);
     }
     w.total = c.off;
     return w;
@@ -593,33 +599,74 @@ int esmk_forward(esmk_model* m, const void* packed_dev, const int64_t* tokens_de
 }
 
 // ---- token-packed batches (no compute on padding) --------------------------------------
+// The segment table of a packed row space, shared by the engine entries and the single-kernel entries: the layout rules,
+// and the tables every packed attention launch reads.  lead_gap: the first segment may start behind row 0 (op entries).
+struct SegTableInfo {
+    int max_len = 0;
+    size_t items = 0;                // 128-query blocks = entries of the attention work list
+    unsigned long long sum_len2 = 0;
+};
+static int check_seg_table(const std::string& w, const int32_t* seg, int n_seg, int rows, bool lead_gap, SegTableInfo* info) {
+    if (n_seg <= 0 || rows <= 0) return fail(w + ": n_seg and rows must be positive");
+    if (rows % 64 != 0) return fail(w + ": rows must be a multiple of 64");
+    if (rows > ESMK_MAX_ROWS) return fail(w + ": rows exceed 2^24");
+    long long end = 0;
+    for (int s = 0; s < n_seg; ++s) {
+        const int start = seg[2 * s], len = seg[2 * s + 1];
+        if (len <= 0) return fail(w + ": empty segment");
+        if (start % 16 != 0) return fail(w + ": segment starts must be multiples of 16");
+        if ((s == 0 && start != 0 && !lead_gap) || start < end)
+            return fail(w + (lead_gap ? ": segments must be ascending and disjoint" : ": segments must start at row 0, ascending, disjoint"));
+        end = (long long)start + len;
+        if (end > rows) return fail(w + ": segment past the last row");
+        info->max_len = std::max(info->max_len, len);
+        info->items += (size_t)(len + 127) / 128;
+        info->sum_len2 += (unsigned long long)len * (unsigned long long)len;
+    }
+    return 0;
+}
+// dst: [seg 2 n][npad n (zero: filled on the device)][work 4 items] — query blocks of 128 rows, longest segments first: the
+// tail of the grid is made of short work items
+static void fill_attn_tables(const int32_t* seg, int n_seg, int32_t* dst) {
+    memcpy(dst, seg, (size_t)2 * n_seg * 4);
+    memset(dst + (size_t)2 * n_seg, 0, (size_t)n_seg * 4);
+    std::vector<int> order(n_seg);
+    for (int s = 0; s < n_seg; ++s) order[s] = s;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return seg[2 * a + 1] > seg[2 * b + 1]; });
+    int32_t* wk = dst + (size_t)3 * n_seg;
+    for (int s : order) {
+        const int start = seg[2 * s], len = seg[2 * s + 1];
+        for (int q0 = 0; q0 < len; q0 += 128) {
+            wk[0] = start;
+            wk[1] = len;
+            wk[2] = q0;
+            wk[3] = s;
+            wk += 4;
+        }
+    }
+}
+// dst: uint64 [n_seg] (as int32 pairs, 8-byte aligned): map offset of segment s = sum of len^2 of the segments in front
+static void fill_map_offsets(const int32_t* seg, int n_seg, int32_t* dst) {
+    unsigned long long acc = 0;
+    for (int s = 0; s < n_seg; ++s) {
+        memcpy(dst + 2 * (size_t)s, &acc, 8);
+        acc += (unsigned long long)seg[2 * s + 1] * (unsigned long long)seg[2 * s + 1];
+    }
+}
+
 static int check_segments(const char* who, const esmk_model* m, const int32_t* seg, int n_seg, int rows,
                           PackedCtx* pc) {
     const std::string w(who);
     if (!m || !seg) return fail(w + ": null argument");
     if (m->is_msa) return fail(w + ": not an ESM-2 handle");
     if (m->esm1) return fail(w + ": ESM-1 (no_rope = ESMK_ESM1) runs padded batches only (esmk_forward); it has no token-packed form yet");
-    if (n_seg <= 0 || rows <= 0) return fail(w + ": n_seg and rows must be positive");
-    if (rows % 64 != 0) return fail(w + ": rows must be a multiple of 64");
-    if (rows > ESMK_MAX_ROWS) return fail(w + ": rows exceed 2^24");
-    long long end = 0;
-    int max_len = 0;
-    size_t items = 0;
-    for (int s = 0; s < n_seg; ++s) {
-        const int start = seg[2 * s], len = seg[2 * s + 1];
-        if (len <= 0) return fail(w + ": empty segment");
-        if (start % 16 != 0) return fail(w + ": segment starts must be multiples of 16");
-        if ((s == 0 && start != 0) || start < end) return fail(w + ": segments must start at row 0, ascending, disjoint");
-        end = (long long)start + len;
-        if (end > rows) return fail(w + ": segment past the last row");
-        max_len = std::max(max_len, len);
-        items += (size_t)(len + 127) / 128;
-        if (pc) pc->sum_len2 += (double)len * len;
-    }
+    SegTableInfo info;
+    if (check_seg_table(w, seg, n_seg, rows, false, &info)) return 1;
     if (pc) {
         pc->n_seg = n_seg;
-        pc->max_len = max_len;
-        pc->n_items = (int)items;
+        pc->max_len = info.max_len;
+        pc->n_items = (int)info.items;
+        pc->sum_len2 = (double)info.sum_len2;
         pc->seg_host = seg;
     }
     return 0;
@@ -679,6 +726,60 @@ int esmk_forward_packed_ex(esmk_model* m, const void* packed_dev, const int64_t*
                         logits_out_dev, nullptr, contacts_out_dev, workspace_dev, workspace_bytes, stream, &pc);
 }
 
+// esmk_packed_workspace_bytes_maps / esmk_forward_packed_maps: the _ex entries plus attention maps.  The map flags never
+// reach forward_impl (contacts stay the fused per-segment form): they travel in the PackedCtx.
+static int check_packed_maps(const char* who, const esmk_model* m, const int32_t* seg, int n_seg, int rows,
+                             uint32_t out_flags, PackedCtx* pc, CtPackedPlan* ct) {
+    const std::string w(who);
+    if (check_segments(who, m, seg, n_seg, rows, pc)) return 1;
+    if (out_flags & ~(uint32_t)(ESMK_OUT_LOGITS | ESMK_OUT_REPR_LOWP | ESMK_OUT_CONTACTS | ESMK_OUT_ATTN | ESMK_OUT_ATTN_LOWP))
+        return fail(w + ": only ESMK_OUT_LOGITS / ESMK_OUT_REPR_LOWP / ESMK_OUT_CONTACTS / ESMK_OUT_ATTN / ESMK_OUT_ATTN_LOWP are available");
+    if (split_x3(m))
+        return fail(w + ": the f16x3 precision mode runs padded batches of head_dim-64 models (no token-packed form)");
+    if (out_flags & ESMK_OUT_CONTACTS) {
+        *ct = contacts_packed_plan(seg, n_seg, m->H, m->D == 128 ? 128 : 64, m->cfg.prepend_bos ? 1 : 0,
+                                   m->cfg.append_eos ? 1 : 0);
+        pc->ct = ct;
+    }
+    pc->maps = (out_flags & (ESMK_OUT_ATTN | ESMK_OUT_ATTN_LOWP)) != 0;
+    pc->maps_lowp = (out_flags & ESMK_OUT_ATTN_LOWP) != 0;
+    return 0;
+}
+constexpr uint32_t kMapFlags = ESMK_OUT_ATTN | ESMK_OUT_ATTN_LOWP;
+
+int esmk_packed_workspace_bytes_maps(const esmk_model* m, const int32_t* segments_host, int n_seg, int rows,
+                                     uint32_t out_flags, size_t* bytes) {
+    if (!m || !bytes) return fail("esmk_packed_workspace_bytes_maps: null argument");
+    PackedCtx pc;
+    CtPackedPlan ct;
+    if (check_packed_maps("esmk_packed_workspace_bytes_maps", m, segments_host, n_seg, rows, out_flags, &pc, &ct)) return 1;
+    *bytes = plan_workspace(m, 1, rows, out_flags & ~kMapFlags, n_seg, pc.ct, pc.maps).total;
+    return 0;
+}
+
+int esmk_forward_packed_maps(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev,
+                             const int32_t* segments_host, int n_seg, int rows, const int32_t* repr_layers, int n_repr,
+                             void* const* repr_out_dev, uint32_t out_flags, void* logits_out_dev, void* attn_out_dev,
+                             size_t attn_out_elems, void* contacts_out_dev, void* workspace_dev, size_t workspace_bytes,
+                             void* stream) {
+    PackedCtx pc;
+    CtPackedPlan ct;
+    if (check_packed_maps("esmk_forward_packed_maps", m, segments_host, n_seg, rows, out_flags, &pc, &ct)) return 1;
+    if (pc.maps) {
+        if (!attn_out_dev) return fail("esmk_forward_packed_maps: attention buffer missing");
+        // sum(len^2) <= rows^2 <= 2^48 (check_segments): the product with L H stays inside 64 bits
+        unsigned long long need = 0;
+        for (int s = 0; s < n_seg; ++s) need += (unsigned long long)segments_host[2 * s + 1] * (unsigned long long)segments_host[2 * s + 1];
+        need *= (unsigned long long)m->L * (unsigned long long)m->H;
+        if ((unsigned long long)attn_out_elems < need)
+            return fail("esmk_forward_packed_maps: attention buffer too small (" + std::to_string(attn_out_elems) + " elements, need " +
+                        std::to_string(need) + " = L H sum(len^2))");
+        pc.maps_out = attn_out_dev;
+    }
+    return forward_impl(m, packed_dev, tokens_dev, 1, rows, repr_layers, n_repr, repr_out_dev, out_flags & ~kMapFlags,
+                        logits_out_dev, nullptr, contacts_out_dev, workspace_dev, workspace_bytes, stream, &pc);
+}
+
 int esmk_forward_packed(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev,
                         const int32_t* segments_host, int n_seg, int rows, const int32_t* repr_layers,
                         int n_repr, void* const* repr_out_dev, uint32_t out_flags, void* logits_out_dev,
@@ -716,7 +817,8 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
     for (int i = 0; i < n_repr; ++i)
         if (repr_layers[i] < 0 || repr_layers[i] > m->L || !repr_out_dev[i])
             return fail("esmk_forward: bad repr layer request");
-    const Workspace w = plan_workspace(m, B, T, out_flags, pc ? pc->n_seg : 0, pc ? pc->ct : nullptr);
+    const bool packed_maps = pc != nullptr && pc->maps;
+    const Workspace w = plan_workspace(m, B, T, out_flags, pc ? pc->n_seg : 0, pc ? pc->ct : nullptr, packed_maps);
     if (workspace_bytes < w.total) return fail("esmk_forward: workspace too small");
 
     hipStream_t st = (hipStream_t)stream;
@@ -735,7 +837,7 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
     void* vt = ws + w.vt;
     void* ffn = ws + w.big;
     float* g32 = (float*)(ws + w.big);
-    float* lse = (want_attn || fused_ct) ? (float*)(ws + w.lse) : nullptr;
+    float* lse = (want_attn || fused_ct || packed_maps) ? (float*)(ws + w.lse) : nullptr;
 
     const bool esm1 = m->esm1 != 0;
     if (esm1 && pc) return fail("esmk_forward_packed: ESM-1 (no_rope = ESMK_ESM1) has no token-packed form yet");
@@ -750,10 +852,13 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
     int* row_pos = nullptr;
     AttnSegs segs;
     CtPackedDev ctd;
+    const unsigned long long* map_off = nullptr;  // packed attention maps: sum of len^2 of the segments in front
     if (pc) {
         int* tab = (int*)(ws + w.tables);
         const size_t ct_base = packed_ct_table_base(pc->n_seg, T);  // contact tables, if any, from this slot on
-        const size_t n_int = pc->ct ? ct_base + pc->ct->table_ints() : (size_t)3 * pc->n_seg + (size_t)4 * pc->n_items;
+        size_t n_int = pc->ct ? ct_base + pc->ct->table_ints() : (size_t)3 * pc->n_seg + (size_t)4 * pc->n_items;
+        const size_t n_int_lists = n_int, map_base = (n_int + 1) & ~(size_t)1;  // uint64 [n_seg]
+        if (packed_maps) n_int = map_base + 2 * (size_t)pc->n_seg;
         if (m->pk_event) ESMK_TRY(hipEventSynchronize(m->pk_event));  // the previous upload has read the staging
         else ESMK_TRY(hipEventCreateWithFlags(&m->pk_event, hipEventDisableTiming));
         if (m->pk_host_cap < n_int) {
@@ -764,24 +869,7 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
             m->pk_host_cap = 2 * n_int;
         }
         int32_t* hostv = m->pk_host;
-        memcpy(hostv, pc->seg_host, (size_t)2 * pc->n_seg * 4);
-        memset(hostv + (size_t)2 * pc->n_seg, 0, (size_t)pc->n_seg * 4);
-        // query blocks, longest segments first: the tail of the grid is made of short work items
-        std::vector<int> order(pc->n_seg);
-        for (int s = 0; s < pc->n_seg; ++s) order[s] = s;
-        std::stable_sort(order.begin(), order.end(),
-                         [&](int a, int b) { return pc->seg_host[2 * a + 1] > pc->seg_host[2 * b + 1]; });
-        int32_t* wk = hostv + (size_t)3 * pc->n_seg;
-        for (int s : order) {
-            const int start = pc->seg_host[2 * s], len = pc->seg_host[2 * s + 1];
-            for (int q0 = 0; q0 < len; q0 += 128) {
-                wk[0] = start;
-                wk[1] = len;
-                wk[2] = q0;
-                wk[3] = s;
-                wk += 4;
-            }
-        }
+        fill_attn_tables(pc->seg_host, pc->n_seg, hostv);
         if (pc->ct) {  // contact offsets and work lists: the same upload
             contacts_packed_tables(*pc->ct, pc->seg_host, m->cfg.prepend_bos ? 1 : 0, m->cfg.append_eos ? 1 : 0, m->H,
                                    hostv + ct_base);
@@ -792,6 +880,11 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
             ctd.rt_work = ctd.red_work + 2 * pc->ct->n_red;
             ctd.fin_work = ctd.rt_work + pc->ct->n_rt;
             ctd.rows = T;
+        }
+        if (packed_maps) {
+            if (map_base != n_int_lists) hostv[n_int_lists] = 0;  // the alignment slot
+            fill_map_offsets(pc->seg_host, pc->n_seg, hostv + map_base);
+            map_off = reinterpret_cast<const unsigned long long*>(tab + map_base);
         }
         ESMK_TRY(hipMemcpyAsync(tab, hostv, n_int * 4, hipMemcpyHostToDevice, st));
         ESMK_TRY(hipEventRecord(m->pk_event, st));
@@ -1037,6 +1130,15 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
                                                  (float*)(ws + w.ct_colp), B, H, T, L * H, l,
                                                  m->D == 128 ? 128 : 64, m->cfg.pad_idx, m->cfg.eos_idx,
                                                  m->cfg.prepend_bos, m->cfg.append_eos, op, st));
+        }
+        if (packed_maps) {  // multihead_attention.py:396-403 per segment: [L, H, len, len] blocks, no padding anywhere
+            ProfScope ps(m, st, PC_ATTN_PROBS, 2.0 * pc->sum_len2 * E, 2 * NE * os + (pc->maps_lowp ? (double)os : 4.0) * pc->sum_len2 * H);
+            if (m->D == 128)
+                ESMK_TRY(launch_attention_probs128_packed(q, k, lse, key_bias, pc->maps_out, H, T, l, L, segs, map_off,
+                                                          pc->n_items, op, pc->maps_lowp, st));
+            else
+                ESMK_TRY(launch_attention_probs_packed(q, k, lse, key_bias, pc->maps_out, H, T, l, L, segs, map_off,
+                                                       pc->n_items, op, pc->maps_lowp, st));
         }
         if (want_attn) {
             ProfScope ps(m, st, PC_ATTN_PROBS, 2.0 * N * (double)T * E, 2 * NE * os + 4.0 * N * T * H);
@@ -1621,6 +1723,109 @@ int esmk_op_attention_probs_ex(const void* q_dev, const void* k_dev, const float
     else
         ESMK_TRY(launch_attention_probs(q_dev, k_dev, lse_dev, key_bias_dev, (float*)probs_out, B, H, T, layer,
                                         num_layers_total, operand_dtype, st, lowp));
+    return 0;
+}
+
+// The packed attention core and the packed map kernel one kernel at a time (tests/test_attention_packed_ops_gpu.py).
+// Validation first, before the HIP runtime is touched; then a work list of the entry's own — [seg 2 n][npad n][work 4 items]
+// [map offsets uint64 n], the layout esmk_forward_packed_maps uploads — is built, uploaded, used and freed: no state stays.
+namespace {
+struct PackedOpTables {
+    std::vector<int32_t> host;
+    int n_items = 0;
+    size_t map_base = 0;
+    unsigned long long sum_len2 = 0;
+};
+struct DevBuf {  // freed on every way out of the entry
+    void* p = nullptr;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+};
+int packed_op_tables(const std::string& w, const int32_t* seg, int n_seg, int rows, PackedOpTables* t) {
+    if (!seg) return fail(w + ": null segment table");
+    SegTableInfo info;
+    if (check_seg_table(w, seg, n_seg, rows, true, &info)) return 1;
+    t->n_items = (int)info.items;
+    t->sum_len2 = info.sum_len2;
+    const size_t lists = (size_t)3 * n_seg + (size_t)4 * t->n_items;
+    t->map_base = (lists + 1) & ~(size_t)1;
+    t->host.assign(t->map_base + 2 * (size_t)n_seg, 0);
+    fill_attn_tables(seg, n_seg, t->host.data());
+    fill_map_offsets(seg, n_seg, t->host.data() + t->map_base);
+    return 0;
+}
+}  // namespace
+
+int esmk_op_attention_packed(const void* q_dev, const void* k_dev, const void* vt_dev, const float* key_bias_dev,
+                             const int32_t* segments_host, int n_seg, int rows, int Tp, int H, int head_dim,
+                             int operand_dtype, const void* bias_k_dev, const void* bias_v_dev, void* ctx_out, float* lse_out,
+                             void* stream) {
+    const std::string w("esmk_op_attention_packed");
+    if (!q_dev || !k_dev || !vt_dev || !ctx_out) return fail(w + ": null argument");
+    if (bias_k_dev || bias_v_dev)
+        return fail(w + ": bias_k / bias_v must be null (the null key of the ESM-1 models has no token-packed form)");
+    if (H <= 0) return fail(w + ": H must be positive");
+    if (head_dim != 64 && head_dim != 128) return fail(w + ": head_dim must be 64 or 128");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16) return fail(w + ": operand_dtype must be fp16 or bf16");
+    PackedOpTables t;
+    if (packed_op_tables(w, segments_host, n_seg, rows, &t)) return 1;
+    if (Tp % 64 != 0 || Tp < rows + 64) return fail(w + ": Tp must be a multiple of 64 and >= rows + 64 (one spare key tile)");
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf d;
+    ESMK_TRY(hipMalloc(&d.p, t.host.size() * 4));
+    ESMK_TRY(hipMemcpy(d.p, t.host.data(), t.host.size() * 4, hipMemcpyHostToDevice));
+    int* tab = (int*)d.p;
+    AttnSegs segs;
+    segs.npad = tab + (size_t)2 * n_seg;
+    segs.work = tab + (size_t)3 * n_seg;
+    ESMK_TRY(launch_seg_npad(key_bias_dev, tab, n_seg, tab + (size_t)2 * n_seg, st));
+    if (head_dim == 128)
+        ESMK_TRY(launch_attention128_packed(q_dev, k_dev, vt_dev, key_bias_dev, ctx_out, lse_out, H, rows, Tp, segs, t.n_items,
+                                            operand_dtype, st));
+    else
+        ESMK_TRY(launch_attention_packed(q_dev, k_dev, vt_dev, key_bias_dev, ctx_out, lse_out, H, rows, Tp, segs, t.n_items,
+                                         operand_dtype, st));
+    // a segment of padding only has no key: the padded form skips it through seq_info, here its rows are cleared afterwards
+    ESMK_TRY(launch_zero_allpad_segments(ctx_out, lse_out, tab, segs.npad, n_seg, H, rows,
+                                         (size_t)H * head_dim * op_size(operand_dtype), st));
+    ESMK_TRY(hipStreamSynchronize(st));  // the work list is freed on return
+    return 0;
+}
+
+int esmk_op_attention_probs_packed(const void* q_dev, const void* k_dev, const float* lse_dev, const float* key_bias_dev,
+                                   const int32_t* segments_host, int n_seg, int rows, int H, int head_dim, int L_total,
+                                   int layer, int operand_dtype, int lowp, void* probs_out, size_t probs_elems, void* stream) {
+    const std::string w("esmk_op_attention_probs_packed");
+    if (!q_dev || !k_dev || !lse_dev) return fail(w + ": null argument");
+    if (H <= 0 || L_total <= 0) return fail(w + ": H and L_total must be positive");
+    if (head_dim != 64 && head_dim != 128) return fail(w + ": head_dim must be 64 or 128");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16) return fail(w + ": operand_dtype must be fp16 or bf16");
+    if (layer < 0 || layer >= L_total) return fail(w + ": layer out of range");
+    PackedOpTables t;
+    if (packed_op_tables(w, segments_host, n_seg, rows, &t)) return 1;
+    if (!probs_out) return fail(w + ": attention buffer missing");
+    const unsigned long long need = t.sum_len2 * (unsigned long long)L_total * (unsigned long long)H;
+    if ((unsigned long long)probs_elems < need)
+        return fail(w + ": attention buffer too small (" + std::to_string(probs_elems) + " elements, need " + std::to_string(need) +
+                    " = L H sum(len^2))");
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf d;
+    ESMK_TRY(hipMalloc(&d.p, t.host.size() * 4));
+    ESMK_TRY(hipMemcpy(d.p, t.host.data(), t.host.size() * 4, hipMemcpyHostToDevice));
+    int* tab = (int*)d.p;
+    AttnSegs segs;
+    segs.npad = tab + (size_t)2 * n_seg;
+    segs.work = tab + (size_t)3 * n_seg;
+    const unsigned long long* map_off = reinterpret_cast<const unsigned long long*>(tab + t.map_base);
+    ESMK_TRY(launch_seg_npad(key_bias_dev, tab, n_seg, tab + (size_t)2 * n_seg, st));
+    if (head_dim == 128)
+        ESMK_TRY(launch_attention_probs128_packed(q_dev, k_dev, lse_dev, key_bias_dev, probs_out, H, rows, layer, L_total, segs,
+                                                  map_off, t.n_items, operand_dtype, lowp != 0, st));
+    else
+        ESMK_TRY(launch_attention_probs_packed(q_dev, k_dev, lse_dev, key_bias_dev, probs_out, H, rows, layer, L_total, segs,
+                                               map_off, t.n_items, operand_dtype, lowp != 0, st));
+    ESMK_TRY(hipStreamSynchronize(st));  // the work list is freed on return
     return 0;
 }
 

@@ -293,6 +293,25 @@ hipError_t launch_attention_packed(const void* q, const void* k, const void* vt,
 hipError_t launch_attention128_packed(const void* q, const void* k, const void* vt, const float* key_bias, void* ctx,
                                       float* lse, int H, int rows, int Tp, AttnSegs segs, int n_items,
                                       int operand_dtype, hipStream_t st);
+// Attention maps of a token-packed batch (attn_probs_packed_kernel / attn_probs128_packed_kernel): one workgroup per
+// (work item, head).  q, k [H, rows, head_dim], lse [H, rows], key_bias [rows] (read only for segments with npad > 0).
+// Ragged output: segment s owns a [Ltot, H, len_s, len_s] block at element offset Ltot * H * map_off[s], map_off[s] =
+// sum_{s'<s} len_s'^2 (64-bit: four 650M sequences of 1022 tokens are already 2.8e9 elements).  lowp: maps in the operand
+// dtype.  Every element carries the bits attn_probs_kernel gives the same sequence in a padded batch.
+hipError_t launch_attention_probs_packed(const void* q, const void* k, const float* lse, const float* key_bias, void* probs,
+                                         int H, int rows, int layer, int num_layers_total, AttnSegs segs,
+                                         const unsigned long long* map_off, int n_items, int operand_dtype, bool lowp,
+                                         hipStream_t st);
+hipError_t launch_attention_probs128_packed(const void* q, const void* k, const float* lse, const float* key_bias,
+                                            void* probs, int H, int rows, int layer, int num_layers_total, AttnSegs segs,
+                                            const unsigned long long* map_off, int n_items, int operand_dtype, bool lowp,
+                                            hipStream_t st);
+// npad[s] = number of rows of segment s (seg [n_seg][2] = first row, length) whose key_bias is not 0; key_bias null: all 0.
+// What launch_packed_stats derives from the tokens, for callers that hold key_bias only (esmk_op_attention_packed)
+hipError_t launch_seg_npad(const float* key_bias, const int* seg, int n_seg, int* npad, hipStream_t st);
+// ctx rows ([rows, row_bytes]) and lse ([H, rows], optional) of segments with npad == length := 0 (esmk_op_attention_packed)
+hipError_t launch_zero_allpad_segments(void* ctx, float* lse, const int* seg, const int* npad, int n_seg, int H, int rows,
+                                       size_t row_bytes, hipStream_t st);
 hipError_t launch_attention(const void* q, const void* k, const void* vt, const float* key_bias,
                             const int* seq_info, void* ctx, float* lse, int B, int H, int T, int Tp,
                             int operand_dtype, hipStream_t st);

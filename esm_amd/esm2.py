@@ -518,9 +518,10 @@ class ESM2(nn.Module):
     supports_varlen = True  # ESM-2 (all sizes) and ESM-1b / ESM-1v; the MSA Transformer has no such path
     supports_contacts_only = True  # forward(contacts_only=True): contact maps without the attention tensor
     supports_varlen_contacts = True  # forward_varlen(contacts_only=True / return_contacts=True): packed contact maps
+    supports_varlen_maps = True  # forward_varlen(need_head_weights=True): per-sequence attention maps of a packed batch
 
     def forward_varlen(self, tokens, repr_layers=[], lengths=None, min_saving=0.08, unpack=True, return_contacts=False,
-                       contacts_only=False):
+                       contacts_only=False, need_head_weights=False):
         """Same results as ``forward(tokens, repr_layers)`` on the non-pad positions of a RIGHT-padded batch
         (what ``BatchConverter`` yields, reference esm/data.py:262-297), but the sequences are laid back to back
         in one row space and the engine does no work on padding.  Pad positions of the returned tensors are zero
@@ -536,7 +537,16 @@ class ESM2(nn.Module):
                     [B, T-2, T-2] like ``forward(contacts_only=True)``, sequence b's map in the top-left [S_b, S_b] block
                     (S_b = its length - 2), zeros elsewhere; unpack=False: a list of per-sequence [S_b, S_b] views.
 
-        Attention maps are per-sequence [T,T] objects: use ``forward`` for those."""
+        need_head_weights  also return "attentions", bit-equal per sequence to ``forward(need_head_weights=True)``.
+                    unpack=False: a list of per-sequence [L, H, len_b, len_b] views into ONE flat tensor (len_b includes
+                    <cls>/<eos>; no [B, L, H, T, T] tensor is ever allocated — the form to use for mixed lengths);
+                    unpack=True: the reference's [B, L, H, T, T] tensor, zero outside each sequence's corner, which is
+                    ``forward(tokens, need_head_weights=True)["attentions"]`` as a whole tensor.  Together with
+                    return_contacts the contacts stay the per-segment fused maps of ``contacts_only=True``.
+                    When the call falls back to ``forward`` (min_saving, f16x3, ESM-1) and asks for maps AND contacts,
+                    the model runs twice — once for the maps, once with ``contacts_only=True`` — so that the contacts
+                    are the fused ones on both routes and the maps can stay in the model dtype; the fall-back is taken
+                    where packing saves little, i.e. the second run costs one contacts-only forward of the same batch."""
         assert tokens.ndim == 2
         from . import _native as N
         from .packing import pack_plan
@@ -554,6 +564,14 @@ class ESM2(nn.Module):
         if unpack and ((min_saving is not None and plan.rows > (1.0 - min_saving) * B * T) or _weight_split() == 4
                        or getattr(self, "_engine_esm1", 0)):
             # (f16x3 and the ESM-1 models have no token-packed form)
+            if need_head_weights:
+                full = self.forward(tokens.to(dev), repr_layers=repr_layers, need_head_weights=True)
+                if return_contacts:
+                    ct = self.forward(tokens.to(dev), repr_layers=repr_layers if contacts_only else [], contacts_only=True)
+                    if contacts_only:
+                        return dict(ct, attentions=full["attentions"])
+                    full = dict(full, contacts=ct["contacts"])
+                return full
             if return_contacts:
                 out = self.forward(tokens.to(dev), repr_layers=repr_layers, contacts_only=True)
                 if not contacts_only:
@@ -574,12 +592,30 @@ class ESM2(nn.Module):
             seg_ptr = ctypes.cast(seg.data_ptr(), ctypes.POINTER(ctypes.c_int32))
             layers_arr = (ctypes.c_int32 * max(1, len(repr_set)))(*repr_set)
             outs_arr = (ctypes.c_void_p * max(1, len(repr_set)))(*[r.data_ptr() for r in reps])
+            flat_ct = flat_at = None
             if return_contacts:
                 pflags |= N.OUT_CONTACTS
                 # ragged fp32 maps: sequence b's [S_b, S_b] block at sum_{b'<b} S_b'^2 (include/esmk.h)
                 S = (plan.lengths.cpu().to(torch.int64) - int(self.prepend_bos) - int(self.append_eos)).clamp(min=0)
                 sq = S * S
                 flat_ct = torch.empty((max(1, int(sq.sum())),), **f32)
+            if need_head_weights:
+                # ragged maps: sequence b's [L, H, len_b, len_b] block at L H sum_{b'<b} len_b'^2 (include/esmk.h), in the
+                # model dtype directly when the engine's operand dtype is that dtype
+                H = self.attention_heads
+                at_lowp = _native_lowp(w.dtype, eng.operand_dtype)
+                pflags |= N.OUT_ATTN | (N.OUT_ATTN_LOWP if at_lowp else 0)
+                len2 = plan.lengths * plan.lengths
+                flat_at = torch.empty((L * H * int(len2.sum()),), dtype=w.dtype if at_lowp else torch.float32, device=dev)
+                need = ctypes.c_size_t()
+                N.check(N.lib.esmk_packed_workspace_bytes_maps(eng.handle, seg_ptr, B, plan.rows, pflags,
+                                                               ctypes.byref(need)))
+                ws = eng.workspace_for_bytes(need.value)
+                N.check(N.lib.esmk_forward_packed_maps(
+                    eng.handle, N.ptr(eng.packed), N.ptr(flat), seg_ptr, B, plan.rows, layers_arr, len(repr_set),
+                    outs_arr, pflags, N.ptr(logits), N.ptr(flat_at), flat_at.numel(), N.ptr(flat_ct), N.ptr(ws),
+                    ws.numel(), N.cur_stream()))
+            elif return_contacts:
                 need = ctypes.c_size_t()
                 N.check(N.lib.esmk_packed_workspace_bytes_ex(eng.handle, seg_ptr, B, plan.rows, pflags,
                                                              ctypes.byref(need)))
@@ -614,6 +650,18 @@ class ESM2(nn.Module):
                 out["contacts"] = contacts
             else:
                 out["contacts"] = views
+        if need_head_weights:
+            flat_at = cast(flat_at)
+            offs = [0] + (L * H * torch.cumsum(len2, 0)).tolist()
+            lens = plan.lengths.tolist()
+            views = [flat_at[offs[b]:offs[b + 1]].view(L, H, lens[b], lens[b]) for b in range(B)]
+            if unpack:
+                attn = torch.zeros((B, L, H, T, T), dtype=flat_at.dtype, device=dev)
+                for b, v in enumerate(views):
+                    attn[b, :, :, :lens[b], :lens[b]] = v
+                out["attentions"] = attn
+            else:
+                out["attentions"] = views
         return out
 
     def profile_begin(self):

@@ -175,6 +175,57 @@ def attention_probs(q, k, lse, key_bias=None, out=None, layer=0, num_layers=1, f
     return out
 
 
+def _segments_arg(segments):
+    seg = torch.as_tensor(segments, dtype=torch.int32).reshape(-1, 2).contiguous().cpu()
+    return seg, ctypes.cast(seg.data_ptr(), ctypes.POINTER(ctypes.c_int32))
+
+
+def attention_packed(q, k, vt, segments, key_bias=None, want_lse=False, bias_k=None, bias_v=None):
+    """The attention core of a token-packed batch (esmk_op_attention_packed): q, k [H,rows,D] (q in the LOG2 domain),
+    vt [H,D,Tp] with Tp >= rows + 64 (``make_vt_packed``), segments [n,2] = (first row, length) with starts at multiples
+    of 16, key_bias fp32 [rows] (0 / -inf) or None.  Returns ctx [rows, H*D] — rows outside every segment are zero here
+    (the kernel does not write them) — and, with want_lse, the natural-log row log-sum-exp [H,rows]."""
+    _req_cuda(q, k, vt, key_bias)
+    H, rows, D = q.shape
+    seg, seg_ptr = _segments_arg(segments)
+    ctx = torch.zeros((rows, H * D), dtype=q.dtype, device=q.device)
+    lse = torch.zeros((H, rows), dtype=torch.float32, device=q.device) if want_lse else None
+    N.check(N.lib.esmk_op_attention_packed(N.ptr(q), N.ptr(k), N.ptr(vt), N.ptr(key_bias), seg_ptr, seg.shape[0], rows,
+                                           vt.shape[-1], H, D, N.dtype_code(q.dtype), N.ptr(bias_k), N.ptr(bias_v),
+                                           N.ptr(ctx), N.ptr(lse), N.cur_stream()))
+    return (ctx, lse / LOG2E) if want_lse else ctx
+
+
+def attention_probs_packed(q, k, lse, segments, key_bias=None, layer=0, num_layers=1, out_dtype=torch.float32, out=None):
+    """The attention maps of a token-packed batch (esmk_op_attention_probs_packed): q, k, segments, key_bias as in
+    ``attention_packed``, lse the natural-log [H,rows] it returned.  Returns (flat, views): the ragged buffer and, per
+    segment, its [num_layers, H, len, len] view (slice `layer` is written)."""
+    _req_cuda(q, k, lse, key_bias, out)
+    H, rows, D = q.shape
+    seg, seg_ptr = _segments_arg(segments)
+    lens = seg[:, 1].to(torch.int64)
+    offs = [0] + (num_layers * H * torch.cumsum(lens * lens, 0)).tolist()
+    if out is None:
+        out = torch.zeros((offs[-1],), dtype=out_dtype, device=q.device)
+    assert out.dtype == out_dtype
+    lse2 = (lse * LOG2E).contiguous()
+    N.check(N.lib.esmk_op_attention_probs_packed(N.ptr(q), N.ptr(k), N.ptr(lse2), N.ptr(key_bias), seg_ptr, seg.shape[0],
+                                                 rows, H, D, num_layers, layer, N.dtype_code(q.dtype),
+                                                 int(out_dtype != torch.float32), N.ptr(out), out.numel(), N.cur_stream()))
+    views = [out[offs[s]:offs[s + 1]].view(num_layers, H, int(lens[s]), int(lens[s])) for s in range(seg.shape[0])]
+    return out, views
+
+
+def make_vt_packed(v):
+    """v [H,rows,D] of a packed row space -> vt [H,D,rows + 64]: ``make_vt``'s layout plus the spare (zero) key tile the
+    packed attention kernel may read behind the last row."""
+    H, rows, D = v.shape
+    assert rows % 64 == 0
+    vt = torch.zeros((H, D, rows + 64), dtype=v.dtype, device=v.device)
+    vt[:, :, :rows] = make_vt(v[None])[0]
+    return vt
+
+
 def contacts(attn, tokens, w, b, eos_idx=2, prepend_bos=True, append_eos=True):
     """ContactPredictionHead.forward (reference esm/modules.py:338-357)."""
     _req_cuda(attn, tokens, w, b)

@@ -164,8 +164,8 @@ int esmk_forward(esmk_model* m, const void* packed_dev, const int64_t* tokens_de
  *   segments_host   int32 [n_seg][2] on the HOST (first row, length incl. <cls>/<eos>)
  *   repr_out_dev[i] fp32 [rows,E]; logits_out_dev fp32 [rows,V] (iff ESMK_OUT_LOGITS); gap rows are undefined
  * ESM-1b / ESM-1v handles work the same way (learned positions restart at each segment, esm/modules.py:240-257).
- * esmk_packed_workspace_bytes / esmk_forward_packed refuse ESMK_OUT_ATTN and ESMK_OUT_CONTACTS: attention maps stay
- * with esmk_forward, contacts of a packed batch take the _ex entries below. */
+ * esmk_packed_workspace_bytes / esmk_forward_packed refuse ESMK_OUT_ATTN and ESMK_OUT_CONTACTS: contacts of a packed
+ * batch take the _ex entries below, attention maps (with or without contacts) the _maps entries behind them. */
 int esmk_packed_workspace_bytes(const esmk_model* m, int n_seg, int rows, uint32_t out_flags, size_t* bytes);
 int esmk_forward_packed(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev,
                         const int32_t* segments_host, int n_seg, int rows, const int32_t* repr_layers,
@@ -175,8 +175,8 @@ int esmk_forward_packed(esmk_model* m, const void* packed_dev, const int64_t* to
 /* The same with contact maps (ESMK_OUT_CONTACTS, predict_contacts' formula, no attention tensor): every segment's map
  * is the one esmk_forward(ESMK_OUT_CONTACTS) gives that sequence alone.  The workspace grows with sum(len^2) instead
  * of B*Tmax^2, so its size takes the segment table.  Accepted flags: ESMK_OUT_LOGITS (optional), ESMK_OUT_REPR_LOWP,
- * ESMK_OUT_CONTACTS; ESMK_OUT_ATTN / ESMK_OUT_ATTN_LOWP fail (attention maps stay padded-only), as does an MSA handle
- * or the f16x3 precision mode.  Without ESMK_OUT_CONTACTS both behave as the entries above.
+ * ESMK_OUT_CONTACTS; ESMK_OUT_ATTN / ESMK_OUT_ATTN_LOWP fail here (attention maps of a packed batch take the _maps
+ * entries below), as does an MSA handle or the f16x3 precision mode.  Without ESMK_OUT_CONTACTS both behave as the entries above.
  *   contacts_out_dev fp32, ragged: with S_s = len_s - prepend_bos - append_eos, segment s's [S_s,S_s] map is row-major
  *                    at element offset sum_{s'<s} max(S_s',0)^2 (segments with S_s <= 0 have an empty map); required
  *                    iff ESMK_OUT_CONTACTS, even when every map is empty */
@@ -186,6 +186,30 @@ int esmk_forward_packed_ex(esmk_model* m, const void* packed_dev, const int64_t*
                            const int32_t* segments_host, int n_seg, int rows, const int32_t* repr_layers,
                            int n_repr, void* const* repr_out_dev, uint32_t out_flags, void* logits_out_dev,
                            void* contacts_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The same with attention maps (need_head_weights=True: multihead_attention.py:396-403 per layer, stacked by
+ * esm2.py:132-139), per sequence instead of per padded batch: no [B,L,H,Tmax,Tmax] tensor exists anywhere, neither in
+ * the output nor in the workspace (which gains only the row log-sum-exp [H,rows] and the map offsets).
+ * Accepted flags: ESMK_OUT_LOGITS, ESMK_OUT_REPR_LOWP, ESMK_OUT_CONTACTS, ESMK_OUT_ATTN (fp32 maps) and ESMK_OUT_ATTN_LOWP
+ * (maps in the operand dtype; implies the maps, with or without ESMK_OUT_ATTN).  ESMK_OUT_CONTACTS is ALWAYS the fused
+ * per-segment form of the _ex entries — also together with the map flags, unlike esmk_forward, which then derives the
+ * contacts from the attention tensor; so ESMK_OUT_ATTN_LOWP and ESMK_OUT_CONTACTS combine freely here.  Without a map
+ * flag both entries behave as the _ex entries.  ESM-1 (no_rope = ESMK_ESM1) handles, the f16x3 precision mode and MSA
+ * handles are refused as there.
+ *   attn_out_dev    ragged: segment s owns a contiguous row-major [L,H,len_s,len_s] block at element offset
+ *                   L * H * sum_{s'<s} len_s'^2 (len includes <cls>/<eos>): exactly the [:, :, :len, :len] corner of that
+ *                   sequence's slice of esmk_forward's padded tensor, bit for bit; rows / columns of <pad> tokens inside a
+ *                   segment are zero.  fp32, or the operand dtype with ESMK_OUT_ATTN_LOWP.  Required iff a map flag is set.
+ *   attn_out_elems  elements the buffer holds; checked against L * H * sum(len^2) before anything is launched (the
+ *                   offsets pass 2^31 for ordinary batches, a short buffer would be written far out of bounds)
+ *   contacts_out_dev as in esmk_forward_packed_ex */
+int esmk_packed_workspace_bytes_maps(const esmk_model* m, const int32_t* segments_host, int n_seg, int rows,
+                                     uint32_t out_flags, size_t* bytes);
+int esmk_forward_packed_maps(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev,
+                             const int32_t* segments_host, int n_seg, int rows, const int32_t* repr_layers, int n_repr,
+                             void* const* repr_out_dev, uint32_t out_flags, void* logits_out_dev, void* attn_out_dev,
+                             size_t attn_out_elems, void* contacts_out_dev, void* workspace_dev, size_t workspace_bytes,
+                             void* stream);
 
 /* ---- MSA Transformer (reference esm/model/msa_transformer.py:20-238, esm/axial_attention.py) -------- */
 
@@ -401,6 +425,37 @@ int esmk_op_attention_biaskv(const void* q_dev, const void* k_dev, const void* v
 int esmk_op_attention_probs_ex(const void* q_dev, const void* k_dev, const float* lse_dev, const float* key_bias_dev,
                                const int32_t* any_pad_dev, void* probs_out, int B, int H, int T, int head_dim, int layer,
                                int num_layers_total, int msa_C, int out_dtype, int operand_dtype, void* stream);
+
+/* The attention core of a token-packed batch, one kernel at a time (multihead_attention.py:357-394 per segment; tests /
+ * micro-benchmarks).  q, k [H,rows,head_dim] and vt [H,head_dim,Tp] in the layouts and the score domain of
+ * esmk_op_attention_ex (B = 1, T = rows), Tp a multiple of 64 and >= rows + 64: the last key tile of a segment may reach
+ * 63 columns past the last row, and the columns of vt behind the segments' rows must be finite (zero).
+ * segments_host int32 [n_seg][2] = (first row, length): starts are ascending multiples of 16, segments disjoint, gaps
+ * allowed anywhere (also in front of the first segment); rows % 64 == 0.  key_bias fp32 [rows] (0 / -inf) or NULL; the
+ * per-segment <pad> counts the kernel wants are derived from it on the device.  ctx_out [rows, H*head_dim] operand dtype,
+ * rows outside every segment are not written; lse_out fp32 [H,rows] (log2 domain) or NULL.  Every segment's rows carry
+ * the bits esmk_op_attention_ex (mode 0) gives that segment alone — with seq_info when its <pad> tokens are interior,
+ * without when they trail (the engine never packs trailing pads: a segment ends at its last real token).  A segment of
+ * padding only has no key to attend to: its ctx and lse rows are cleared to 0 by a second small launch, the values the
+ * padded form gives such a sequence through seq_info.  That clearing step belongs to THIS entry only: esmk_forward_packed*
+ * do not launch it, so there the context row of an all-<pad> sequence (a one-row segment) is 1 / 0 = NaN, confined to that
+ * row — its attention map is still exactly zero (the query-row select), and no other row reads it.  head_dim 64 or 128.
+ * bias_k_dev / bias_v_dev must be NULL and are refused otherwise (the null key of the ESM-1 models has no packed form;
+ * the slot keeps the signature stable).  The entry uploads a small work list of its own, waits for the stream and
+ * frees it: it owns no persistent state.  Invalid arguments fail before the HIP runtime is touched. */
+int esmk_op_attention_packed(const void* q_dev, const void* k_dev, const void* vt_dev, const float* key_bias_dev,
+                             const int32_t* segments_host, int n_seg, int rows, int Tp, int H, int head_dim,
+                             int operand_dtype, const void* bias_k_dev, const void* bias_v_dev, void* ctx_out, float* lse_out,
+                             void* stream);
+/* The attention maps of a token-packed batch, one kernel at a time (multihead_attention.py:396-403 per segment, slice
+ * `layer` of the stack esm2.py:132-139 builds): q, k, key_bias and the segment table as above, lse fp32 [H,rows] from
+ * esmk_op_attention_packed.  probs_out is the ragged buffer of esmk_forward_packed_maps with L = L_total (segment s's
+ * [L_total,H,len_s,len_s] block at L_total * H * sum_{s'<s} len_s'^2), fp32 or, with lowp != 0, the operand dtype;
+ * probs_elems is checked against L_total * H * sum(len^2) before any launch.  Each map carries the bits
+ * esmk_op_attention_probs_ex gives that segment alone.  Same ownership rule as above. */
+int esmk_op_attention_probs_packed(const void* q_dev, const void* k_dev, const float* lse_dev, const float* key_bias_dev,
+                                   const int32_t* segments_host, int n_seg, int rows, int H, int head_dim, int L_total,
+                                   int layer, int operand_dtype, int lowp, void* probs_out, size_t probs_elems, void* stream);
 
 /* The fused contact pipeline of predict_contacts (contacts.hip: accumulate + reduce per layer, then rt + final) on
  * caller-supplied operands, one entry for the padded and the token-packed form.  Inputs are stacked over layers in the
