@@ -8,6 +8,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 namespace esmk {
 
@@ -759,7 +760,15 @@ __global__ __launch_bounds__(256) void convert2d_split_kernel(const S* __restric
         const size_t r = i / cols, c = i - r * cols;
         const size_t rr = row_map ? head_pad_index(r, d) : r;
         const size_t cc = col_map ? head_pad_index(c, d) : c;
-        const float w = (float)src[i];
+        float w;
+        if constexpr (std::is_same<S, __bf16>::value) {
+            // the bf16 value widened by its bits, not by a conversion: hipcc narrows (half)(fpext(bf16) - fpext(half)) to a
+            // half subtraction hi - hi, as if every bf16 were a half — lo came out +0 where w lies below fp16's normal
+            // range and w - hi is negative (-0 after the rounding), NaN instead of -inf above 65504
+            w = __builtin_bit_cast(float, (unsigned)__builtin_bit_cast(unsigned short, src[i]) << 16);
+        } else {
+            w = (float)src[i];
+        }
         const _Float16 hi = (_Float16)w;
         const _Float16 lo = (_Float16)(w - (float)hi);
         _Float16* q = dst + rr * (THIRD ? 3 : 2) * dst_ld + (cc >> 6) * (THIRD ? 192 : 128) + (cc & 63);

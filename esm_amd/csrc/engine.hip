@@ -1430,6 +1430,93 @@ int esmk_op_linear_split(const void* a_dev, const void* w2_dev, const float* bia
     return 0;
 }
 
+// ---- the kernels of the precision modes as single ops (tests/test_precision_ops_gpu.py) ---------------------------
+int esmk_op_linear_f32(const float* a_dev, int lda, const float* w_dev, const float* bias_dev, float* out_dev, int ldc, int M,
+                       int N, int K, int gelu, void* stream) {
+    if (!a_dev || !w_dev || !out_dev) return fail("esmk_op_linear_f32: null argument");
+    if (M <= 0 || N <= 0 || K <= 0) return fail("esmk_op_linear_f32: M, N and K must be positive");
+    if (K % 32 != 0) return fail("esmk_op_linear_f32: need K % 32 == 0");
+    if (lda % 4 != 0 || lda < K) return fail("esmk_op_linear_f32: need lda % 4 == 0 and lda >= K");
+    if (ldc < N) return fail("esmk_op_linear_f32: need ldc >= N");
+    ESMK_TRY(launch_gemm32(a_dev, lda, w_dev, bias_dev, out_dev, ldc, M, N, K, gelu != 0, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_layernorm_ex(const float* x_dev, const float* gamma_dev, const float* beta_dev, void* y_dev, float* y32_dev,
+                         int rows, int E, int operand_dtype, const float* row_keep_dev, int map_R, int map_C, int ldy, int x3,
+                         float eps, void* stream) {
+    if (!x_dev || !gamma_dev || !beta_dev || (!y_dev && !y32_dev)) return fail("esmk_op_layernorm_ex: null argument");
+    if (rows <= 0 || E <= 0) return fail("esmk_op_layernorm_ex: rows and E must be positive");
+    if (E % 4 != 0 || E > 5120) return fail("esmk_op_layernorm_ex: need E % 4 == 0 and E <= 5120");
+    const int dt = operand_dtype & 0xff;
+    if (dt != ESMK_DT_F16 && dt != ESMK_DT_BF16) return fail("esmk_op_layernorm_ex: operand_dtype must be ESMK_F16 or ESMK_BF16");
+    if (ldy < 0 || (ldy > 0 && ldy < E) || ldy % 4 != 0) return fail("esmk_op_layernorm_ex: ldy must be 0 or a multiple of 4 >= E");
+    if (x3 && (E % 64 != 0 || ldy < 3 * E || !y_dev || dt != ESMK_DT_F16))
+        return fail("esmk_op_layernorm_ex: x3 needs E % 64 == 0, ldy >= 3 E, y and fp16");
+    if (map_R < 0 || (map_R > 0 && (map_C <= 0 || rows % ((long long)map_R * map_C) != 0)))
+        return fail("esmk_op_layernorm_ex: the row map needs map_C > 0 and rows % (map_R map_C) == 0");
+    if (!(eps > 0.f)) return fail("esmk_op_layernorm_ex: eps must be positive");
+    LnExtra ex;
+    ex.row_keep = row_keep_dev;
+    ex.map_R = map_R;
+    ex.map_C = map_R > 0 ? map_C : 0;
+    ex.ldy = ldy;
+    ex.x3 = x3 != 0;
+    ex.eps = eps;
+    ESMK_TRY(launch_layernorm_ex(x_dev, gamma_dev, beta_dev, y_dev, y32_dev, rows, E, operand_dtype, ex, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_split_weight_ex(const void* w_dev, int w_dtype, void* dst_dev, int dst_dtype, int rows, int cols, int dst_ld,
+                            int parts, int row_map, int col_map, int head_dim, void* stream) {
+    auto is_dt = [](int d) { return d == ESMK_DT_F32 || d == ESMK_DT_F16 || d == ESMK_DT_BF16; };
+    if (!w_dev || !dst_dev) return fail("esmk_op_split_weight_ex: null argument");
+    if (rows <= 0 || cols <= 0) return fail("esmk_op_split_weight_ex: rows and cols must be positive");
+    if (parts < 1 || parts > 3) return fail("esmk_op_split_weight_ex: parts must be 1, 2 or 3");
+    if (!is_dt(w_dtype) || !is_dt(dst_dtype)) return fail("esmk_op_split_weight_ex: dtypes must be ESMK_F32, ESMK_F16 or ESMK_BF16");
+    if (parts >= 2 && dst_dtype != ESMK_DT_F16) return fail("esmk_op_split_weight_ex: parts 2 and 3 write fp16 (dst_dtype ESMK_F16)");
+    if ((row_map != 0 && row_map != 1) || (col_map != 0 && col_map != 1))
+        return fail("esmk_op_split_weight_ex: row_map and col_map must be 0 or 1");
+    int d = 64;  // identity maps: unused
+    if (row_map || col_map) {
+        d = head_dim;
+        if (!((d >= 1 && d <= 64) || d == 128)) return fail("esmk_op_split_weight_ex: head_dim must be 1..64 or 128");
+        if ((row_map && rows % d != 0) || (col_map && cols % d != 0))
+            return fail("esmk_op_split_weight_ex: head_dim must divide the mapped extent");
+    }
+    const long long col_extent = !col_map ? cols : d == 128 ? cols : (long long)(cols / d) * 64;
+    if (dst_ld < col_extent) return fail("esmk_op_split_weight_ex: dst_ld is smaller than the (mapped) column extent");
+    if (parts >= 2 && dst_ld % 64 != 0) return fail("esmk_op_split_weight_ex: parts 2 and 3 need dst_ld % 64 == 0");
+    if (parts == 1)
+        ESMK_TRY(launch_convert2d(w_dev, w_dtype, dst_dev, dst_dtype, (size_t)rows, (size_t)cols, (size_t)dst_ld, row_map, col_map,
+                                  d, (hipStream_t)stream));
+    else
+        ESMK_TRY(launch_convert2d_split(w_dev, w_dtype, dst_dev, (size_t)rows, (size_t)cols, (size_t)dst_ld, row_map, col_map, d,
+                                        (hipStream_t)stream, parts));
+    return 0;
+}
+
+int esmk_op_linear_gelu_x3(const void* a3_dev, const void* w3_dev, const float* bias_dev, void* out3_dev, int M, int N, int K3,
+                           void* stream) {
+    if (!a3_dev || !w3_dev || !bias_dev || !out3_dev) return fail("esmk_op_linear_gelu_x3: null argument");
+    if (M <= 0 || N <= 0 || K3 <= 0) return fail("esmk_op_linear_gelu_x3: M, N and K3 must be positive");
+    if (K3 % 192 != 0) return fail("esmk_op_linear_gelu_x3: need K3 % 192 == 0 (hi | hi | lo per 64-column K tile)");
+    GemmArgs g;
+    g.A = a3_dev;
+    g.W = w3_dev;
+    g.bias = bias_dev;
+    g.out = out3_dev;
+    g.M = M;
+    g.N = N;
+    g.K = K3;
+    g.x3_out = 1;
+    // the kernel's own contract (gemm9_supports): a 64-column block is stored as hi | hi | lo, 192 columns of a 3 N row
+    if (N % 64 != 0 || gemm_plan(g, EPI_GELU_T).kernel != 9)
+        return fail("esmk_op_linear_gelu_x3: need N % 64 == 0 (no kernel takes this call)");
+    ESMK_TRY(launch_gemm(g, EPI_GELU_T, ESMK_DT_F16, (hipStream_t)stream));
+    return 0;
+}
+
 int esmk_debug_linear_splitk(const void* a_dev, const void* w_dev, float* partials_dev, int M, int N, int K,
                              int S, int operand_dtype, void* stream) {
     if (S < 1 || K % S != 0 || (K / S) % 64 != 0) return fail("esmk_debug_linear_splitk: K/S must be a multiple of 64");
@@ -1536,7 +1623,9 @@ int esmk_debug_gemm_impl(int impl, int variant) {
 int esmk_debug_gemm_plan(int M, int N, int K, int epilogue, int flags, int32_t out[4]) {
     if (!out) return fail("esmk_debug_gemm_plan: null argument");
     if (epilogue < EPI_STORE_T || epilogue > EPI_QKV_ALL) return fail("esmk_debug_gemm_plan: bad epilogue");
-    if (flags & ~31) return fail("esmk_debug_gemm_plan: unknown flag");
+    if (flags & ~63) return fail("esmk_debug_gemm_plan: unknown flag");
+    if ((flags & 32) && (flags != 32 || epilogue != EPI_GELU_T))
+        return fail("esmk_debug_gemm_plan: the f16x3 output form (flag 32) exists for epilogue 2 alone, with no other flag");
     static const float fake = 0.f;  // stands for the pointers that select a form; gemm_plan dereferences nothing
     GemmArgs g;
     g.bias = &fake;
@@ -1557,6 +1646,7 @@ int esmk_debug_gemm_plan(int M, int N, int K, int epilogue, int flags, int32_t o
         g.a_kt_repeat = 1;
     }
     if (flags & 16) g.batch = 2;
+    if (flags & 32) g.x3_out = 1;  // as esmk_op_linear_gelu_x3
     const GemmPlan pl = gemm_plan(g, epilogue);
     out[0] = pl.kernel;
     out[1] = pl.half_m;

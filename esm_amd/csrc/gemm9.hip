@@ -965,6 +965,9 @@ bool gemm9_supports(const GemmArgs& p, int epi) {
         p.vt_rows > 0 || p.rowmap_R > 0 || epi == EPI_MSA_CTX || p.head_dim != 64)
         return false;
     if (gemm9_ln_fold(p, epi) && p.a_kt_repeat) return false;  // the fold has no split-weight form
+    // hi | hi | lo output rows: every 64-column block of a row becomes 192 columns of a 3 N row, so a last block of fewer
+    // than 64 columns would store past the row (past the buffer for the last row)
+    if (p.x3_out && (epi != EPI_GELU_T || p.N % 64 != 0)) return false;
     if (p.a_row_bytes && (p.a_row_bytes % 16 != 0)) return false;
     if ((epi == EPI_QKV_ROPE || epi == EPI_V_T) && p.N % 64 != 0) return false;
     // whole tiles on either side of column 2E; plain (not split) weights

@@ -92,6 +92,68 @@ def linear_split(a, w2, bias=None, epilogue=N.EPI_STORE_T, out=None):
     return out
 
 
+def linear_f32(a, w, bias=None, gelu=False, out=None, M=None):
+    """The exact-fp32 MFMA linear of the LM head (esmk_op_linear_f32): a fp32 [M,lda] (the first K columns are read), w fp32
+    [N,K], bias fp32 [N] or None -> act(a . w^T + bias) written into out fp32 [>= M, ldc >= N] (allocated [M,N] when None;
+    only the [M,N] corner is written)."""
+    _req_cuda(a, w, bias, out)
+    assert a.dtype == w.dtype == torch.float32 and a.dim() == w.dim() == 2
+    Nn, K = w.shape
+    M = a.shape[0] if M is None else M
+    if out is None:
+        out = torch.empty((M, Nn), dtype=torch.float32, device=a.device)
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] >= M and a.shape[0] >= M
+    N.check(N.lib.esmk_op_linear_f32(N.ptr(a), a.shape[1], N.ptr(w), N.ptr(bias), N.ptr(out), out.shape[1], M, Nn, K,
+                                     int(bool(gelu)), N.cur_stream()))
+    return out
+
+
+def layernorm_ex(x, gamma, beta, y=None, y32=None, operand_dtype=torch.float16, row_keep=None, map_R=0, map_C=0, x3=False,
+                 eps=1e-5, variant=None):
+    """Every form of the LayerNorm launch (esmk_op_layernorm_ex): x fp32 [rows,E] -> y (operand dtype, [>= rows, ldy]: its
+    row stride is taken from the tensor) and / or y32 fp32 [>= rows, E], both the caller's and written in place.  row_keep
+    fp32 [rows] scales the output rows; map_R / map_C write input row (b,r,c) to output row (b,c,r); x3: y rows hi | hi | lo
+    per 64 columns (fp16, ldy >= 3 E)."""
+    _req_cuda(x, gamma, beta, y, y32, row_keep)
+    assert x.dtype == torch.float32 and x.dim() == 2 and gamma.dtype == beta.dtype == torch.float32
+    rows, E = x.shape
+    assert y is None or (y.dim() == 2 and y.dtype == operand_dtype and y.shape[0] >= rows)
+    assert y32 is None or (y32.dtype == torch.float32 and tuple(y32.shape[1:]) == (E,) and y32.shape[0] >= rows)
+    assert row_keep is None or (row_keep.dtype == torch.float32 and row_keep.numel() == rows)
+    code = N.dtype_code(operand_dtype) | (0 if variant is None else (variant + 1) << 8)
+    N.check(N.lib.esmk_op_layernorm_ex(N.ptr(x), N.ptr(gamma), N.ptr(beta), N.ptr(y), N.ptr(y32), rows, E, code,
+                                       N.ptr(row_keep), map_R, map_C, 0 if y is None else y.shape[1], int(bool(x3)),
+                                       float(eps), N.cur_stream()))
+    return y, y32
+
+
+def split_weight_ex(w, dst, dst_ld, parts, row_map=False, col_map=False, head_dim=64):
+    """The weight images of the precision modes (esmk_op_split_weight_ex): w [rows,cols] (fp32 / fp16 / bf16) into the
+    caller's dst, rows of parts * dst_ld elements: parts 1 = conversion to dst.dtype, 2 = hi | lo, 3 = hi | lo | hi per
+    64-column K tile (fp16).  row_map / col_map spread heads of head_dim over 64 slots (128: the q / k slice order); slots
+    in between are left as they are."""
+    _req_cuda(w, dst)
+    rows, cols = w.shape
+    N.check(N.lib.esmk_op_split_weight_ex(N.ptr(w), N.dtype_code(w.dtype), N.ptr(dst), N.dtype_code(dst.dtype), rows, cols,
+                                          dst_ld, parts, int(bool(row_map)), int(bool(col_map)), head_dim, N.cur_stream()))
+    return dst
+
+
+def linear_gelu_x3(a3, w3, bias, out3=None, M=None):
+    """fc1 + GELU of the f16x3 mode (esmk_op_linear_gelu_x3): a3 fp16 [M,K3] rows hi | hi | lo, w3 fp16 [N,K3] rows
+    hi | lo | hi, bias fp32 [N] -> out3 fp16 [>= M, 3N] (allocated when None), gelu(a . w^T + bias) as hi | hi | lo."""
+    _req_cuda(a3, w3, bias, out3)
+    assert a3.dtype == w3.dtype == torch.float16 and bias is not None and bias.dtype == torch.float32
+    M = a3.shape[0] if M is None else M
+    Nn, K3 = w3.shape
+    assert a3.shape[1] == K3 and a3.shape[0] >= M
+    if out3 is None:
+        out3 = torch.empty((M, 3 * Nn), dtype=torch.float16, device=a3.device)
+    assert out3.dtype == torch.float16 and out3.shape[1] == 3 * Nn and out3.shape[0] >= M
+    N.check(N.lib.esmk_op_linear_gelu_x3(N.ptr(a3), N.ptr(w3), N.ptr(bias), N.ptr(out3), M, Nn, K3, N.cur_stream()))
+    return out3
+
+
 LOG2E = 1.4426950408889634
 
 

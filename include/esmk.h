@@ -308,6 +308,37 @@ int esmk_op_split_weight(const void* w_dev, int w_dtype, void* w2_dev, int N, in
 int esmk_op_linear_split(const void* a_dev, const void* w2_dev, const float* bias_dev, void* out_dev, int M, int N, int K,
                          int epilogue, void* stream);
 
+/* The kernels the precision modes (esmk_config::weight_split) are built from, one launch at a time (tests).  Each entry makes
+ * exactly the launch the engine makes and refuses, before any HIP call, what the kernel's address arithmetic does not cover;
+ * the extent of the buffers is the caller's.
+ * esmk_op_linear_f32: the exact-fp32 MFMA linear of the LM head (gemm32.hip): out[M,N] (row stride ldc) = act(a[M,K] (row
+ *   stride lda) . w[N,K]^T + bias), act = gelu (modules.py:17-24) when gelu != 0; all fp32, bias may be NULL.
+ *   K % 32 == 0, lda % 4 == 0, lda >= K, ldc >= N.
+ * esmk_op_layernorm_ex: esmk_op_layernorm with every field of the engine's LayerNorm launch: row_keep fp32 [rows] (output
+ *   rows multiplied by it, msa_transformer.py:171-172) or NULL; map_R > 0: input row (b,r,c) of [B,map_R,map_C] is written to
+ *   output row (b,c,r), rows % (map_R map_C) == 0; ldy = row stride of y in elements (0 = E, else >= E and a multiple of 4; y32
+ *   rows always have stride E); x3 != 0: y rows in the f16x3 operand layout, per 64-column K tile hi | hi | lo with hi = fp16(o),
+ *   lo = fp16(o - hi) (fp16 only, E % 64 == 0, ldy >= 3 E, y required); eps > 0 (1e-5; 1e-12 for ESM-1).  E % 4 == 0,
+ *   E <= 5120.  operand_dtype carries the kernel variant as in esmk_op_layernorm (bits 8..11 = variant + 1).
+ * esmk_op_split_weight_ex: the weight images: w [rows,cols] (any float dtype) -> parts = 1: dst [.., dst_ld] in dst_dtype, a
+ *   plain conversion; parts = 2 / 3: dst fp16 [.., parts dst_ld], 64-column K tile t of a row as hi | lo (f16x2) or
+ *   hi | lo | hi (f16x3) at columns 64 parts t, dst_ld % 64 == 0.  row_map / col_map = 1 spread heads of head_dim d over 64
+ *   slots: index h d + i -> 64 h + (i < d / 2 ? i : 32 + i - d / 2) (d in 1..64; slots in between are NOT written); d = 128:
+ *   128 h + the dims in the order [0,32) | [64,96) | [32,64) | [96,128).  d must divide the mapped extent; dst_ld >= the
+ *   mapped column extent.
+ * esmk_op_linear_gelu_x3: fc1 + GELU of the f16x3 mode (gemm9.hip): a3 fp16 [M,K3] rows hi | hi | lo, w3 fp16 [N,K3] rows
+ *   hi | lo | hi, bias fp32 [N] -> out3 fp16 [M,3N], gelu(a . w^T + bias) as hi | hi | lo per 64 columns.  K3 % 192 == 0,
+ *   N % 64 == 0 (the hi | hi | lo store of a 64-column block would leave a shorter row). */
+int esmk_op_linear_f32(const float* a_dev, int lda, const float* w_dev, const float* bias_dev, float* out_dev, int ldc, int M,
+                       int N, int K, int gelu, void* stream);
+int esmk_op_layernorm_ex(const float* x_dev, const float* gamma_dev, const float* beta_dev, void* y_dev, float* y32_dev,
+                         int rows, int E, int operand_dtype, const float* row_keep_dev, int map_R, int map_C, int ldy, int x3,
+                         float eps, void* stream);
+int esmk_op_split_weight_ex(const void* w_dev, int w_dtype, void* dst_dev, int dst_dtype, int rows, int cols, int dst_ld,
+                            int parts, int row_map, int col_map, int head_dim, void* stream);
+int esmk_op_linear_gelu_x3(const void* a3_dev, const void* w3_dev, const float* bias_dev, void* out3_dev, int M, int N, int K3,
+                           void* stream);
+
 /* Toolchain guard (no reference counterpart): the attention / contact kernels issue one MFMA per key tile through inline
  * asm (its C operand, the softmax offset broadcast, must survive); the compiler does not see that instruction's hazards.
  * Runs it beside the builtin on the same operands: a, b [64][8] operand dtype, c [64][16] fp32, out [3][64][16] fp32 =
@@ -330,7 +361,8 @@ int esmk_debug_gemm_impl(int impl, int variant);
  * q, k / v projections, 7 = the MSA row-attention context, 8 = q, k and v in one launch (N = 3E).  flags: 1 = the
  * force_generic and 2 = the force_old test hook of esmk_op_linear, 4 = the LayerNorm-fold form of the epilogue (producer
  * for 4, consumer for 2, 5, 6, 8; an error for the others), 8 = the split-weight form of esmk_op_linear_split (K as
- * there), 16 = a batched call (generalised addressing, batch = 2).  Follows ESMK_GEMM_IMPL / esmk_debug_gemm_impl. */
+ * there), 16 = a batched call (generalised addressing, batch = 2), 32 = the f16x3 output form of esmk_op_linear_gelu_x3 (epilogue
+ * 2 and no other flag; an error otherwise): kernel 9, or 0 where N % 64 != 0.  Follows ESMK_GEMM_IMPL / esmk_debug_gemm_impl. */
 int esmk_debug_gemm_plan(int M, int N, int K, int epilogue, int flags, int32_t out[4]);
 
 /* Measurement / A-B hook (no reference counterpart): named switches of the library, process wide.  No switch changes a

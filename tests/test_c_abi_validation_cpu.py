@@ -385,3 +385,107 @@ def test_msa_row_softmax_argument_checks():
         assert call(attn=FAKE, **kw) != 0 and "layer" in err(), kw
     for dt in (N.F32, 5):
         assert call(dt=dt) != 0 and "operand_dtype" in err(), dt
+
+
+def test_linear_f32_argument_checks():
+    """esmk_op_linear_f32 (gemm32.hip as a single op): every shape the kernel's 16-byte loads and its output stride do
+    not cover is refused before a launch (the buffers are fake)."""
+    def call(a=FAKE, w=FAKE, out=FAKE, M=5, N=33, K=64, lda=None, ldc=None, gelu=0):
+        return N_.esmk_op_linear_f32(a, K if lda is None else lda, w, None, out, N if ldc is None else ldc, M, N, K, gelu,
+                                     None)
+
+    N_ = N.lib
+    for kw in (dict(a=None), dict(w=None), dict(out=None)):
+        assert call(**kw) != 0 and "esmk_op_linear_f32: null" in err(), kw
+    for kw in (dict(M=0), dict(N=-1), dict(K=0)):
+        assert call(**kw) != 0 and "esmk_op_linear_f32" in err() and "positive" in err(), kw
+    for K in (16, 48, 100):
+        assert call(K=K) != 0 and "esmk_op_linear_f32" in err() and "K % 32" in err(), K
+    for lda in (66, 65, 32, 60):  # not a multiple of 4 / shorter than K
+        assert call(lda=lda) != 0 and "esmk_op_linear_f32" in err() and "lda" in err(), lda
+    assert call(ldc=32) != 0 and "esmk_op_linear_f32" in err() and "ldc" in err()
+
+
+def test_layernorm_ex_argument_checks():
+    """esmk_op_layernorm_ex: what the LayerNorm kernel's addressing does not cover — above all the hi | hi | lo rows of the
+    f16x3 mode — is refused before a launch (the buffers are fake)."""
+    f16, bf16 = N.dtype_code(torch.float16), N.dtype_code(torch.bfloat16)
+
+    def call(x=FAKE, g=FAKE, b=FAKE, y=FAKE, y32=None, rows=30, E=320, dt=f16, keep=None, map_R=0, map_C=0, ldy=0, x3=0,
+             eps=1e-5):
+        return N.lib.esmk_op_layernorm_ex(x, g, b, y, y32, rows, E, dt, keep, map_R, map_C, ldy, x3, eps, None)
+
+    who = "esmk_op_layernorm_ex"
+    for kw in (dict(x=None), dict(g=None), dict(b=None), dict(y=None, y32=None)):
+        assert call(**kw) != 0 and who + ": null" in err(), kw
+    for kw in (dict(rows=0), dict(E=0)):
+        assert call(**kw) != 0 and who in err() and "positive" in err(), kw
+    for E in (322, 5124, 8192):  # E % 4 != 0; E > 5120
+        assert call(E=E) != 0 and who in err() and "E % 4" in err(), E
+    assert call(dt=N.F32) != 0 and who in err() and "operand_dtype" in err()
+    x3 = dict(x3=1, ldy=960)
+    for kw in (dict(x3, E=96, ldy=288), dict(x3, ldy=959 // 4 * 4), dict(x3, ldy=0), dict(x3, y=None, y32=FAKE),
+               dict(x3, dt=bf16)):
+        assert call(**kw) != 0 and who + ": x3" in err(), kw
+    for ldy in (4, 316, -4, 322):  # inside (0, E); negative; no 8-byte stores
+        assert call(ldy=ldy) != 0 and who in err() and "ldy" in err(), ldy
+    for kw in (dict(map_R=4, map_C=5), dict(map_R=3, map_C=0), dict(map_R=-1, map_C=5), dict(map_R=3, map_C=7)):
+        assert call(**kw) != 0 and who in err() and "row map" in err(), kw
+    for eps in (0.0, -1e-5, float("nan")):
+        assert call(eps=eps) != 0 and who in err() and "eps" in err(), eps
+
+
+def test_split_weight_ex_argument_checks():
+    """esmk_op_split_weight_ex: parts, the head-spreading maps and the row stride of the image are checked before a launch
+    (the buffers are fake)."""
+    f16 = N.dtype_code(torch.float16)
+
+    def call(w=FAKE, dst=FAKE, wdt=N.F32, ddt=f16, rows=48, cols=128, ld=128, parts=3, rmap=0, cmap=0, d=16):
+        return N.lib.esmk_op_split_weight_ex(w, wdt, dst, ddt, rows, cols, ld, parts, rmap, cmap, d, None)
+
+    who = "esmk_op_split_weight_ex"
+    for kw in (dict(w=None), dict(dst=None)):
+        assert call(**kw) != 0 and who + ": null" in err(), kw
+    for kw in (dict(rows=0), dict(cols=-64)):
+        assert call(**kw) != 0 and who in err() and "positive" in err(), kw
+    for parts in (0, 4, -1):
+        assert call(parts=parts) != 0 and who in err() and "parts must be" in err(), parts
+    for kw in (dict(wdt=3), dict(ddt=7, parts=1)):
+        assert call(**kw) != 0 and who in err() and "dtypes" in err(), kw
+    for kw in (dict(parts=2, ddt=N.F32), dict(parts=3, ddt=N.dtype_code(torch.bfloat16))):
+        assert call(**kw) != 0 and who in err() and "fp16" in err(), kw
+    assert call(rmap=2) != 0 and who in err() and "row_map" in err()
+    for d in (0, -16, 65, 96, 127, 256):
+        assert call(rmap=1, d=d) != 0 and who in err() and "head_dim must be" in err(), d
+    for kw in (dict(rmap=1, rows=50), dict(cmap=1, cols=72, ld=320), dict(rmap=1, d=128, rows=192)):
+        assert call(**kw) != 0 and who in err() and "divide" in err(), kw
+    for kw in (dict(ld=64), dict(cmap=1, cols=48, ld=128), dict(cmap=1, d=128, cols=256, ld=192), dict(parts=1, ld=127)):
+        assert call(**kw) != 0 and who in err() and "dst_ld is smaller" in err(), kw  # 3 heads of 16 spread to 192
+    for kw in (dict(parts=2, ld=160), dict(parts=3, cols=100, ld=100)):
+        assert call(**kw) != 0 and who in err() and "dst_ld % 64" in err(), kw
+
+
+def test_linear_gelu_x3_argument_checks():
+    """esmk_op_linear_gelu_x3, and the kernel-level contract behind it: the hi | hi | lo store of a 64-column block would
+    leave a row of 3 N columns when N % 64 != 0 (and the buffer, for the last row), so neither the entry nor gemm_plan
+    takes such a call — the engine's ffn_dim % 64 == 0 rule is no longer the only guard."""
+    def call(a=FAKE, w=FAKE, bias=FAKE, out=FAKE, M=300, N=256, K3=192):
+        return N_.esmk_op_linear_gelu_x3(a, w, bias, out, M, N, K3, None)
+
+    N_ = N.lib
+    who = "esmk_op_linear_gelu_x3"
+    for kw in (dict(a=None), dict(w=None), dict(bias=None), dict(out=None)):
+        assert call(**kw) != 0 and who + ": null" in err(), kw
+    for kw in (dict(M=0), dict(N=0), dict(K3=-192)):
+        assert call(**kw) != 0 and who in err() and "positive" in err(), kw
+    for K3 in (64, 128, 320, 200):
+        assert call(K3=K3) != 0 and who in err() and "K3 % 192" in err(), K3
+    for n in (264, 8, 100, 1288):
+        assert call(N=n) != 0 and who in err() and "N % 64" in err(), n
+    # the plan itself (flag 32 = the x3_out form): gemm9 or nothing
+    out = (ctypes.c_int32 * 4)()
+    assert N_.esmk_debug_gemm_plan(300, 256, 192, N.EPI_GELU_T, 32, out) == 0 and out[0] == 9 and out[1] == 0
+    assert N_.esmk_debug_gemm_plan(300, 264, 192, N.EPI_GELU_T, 32, out) == 0 and out[0] == 0
+    assert N_.esmk_debug_gemm_plan(300, 264, 192, N.EPI_GELU_T, 0, out) == 0 and out[0] == 9  # the plain form takes N % 8
+    for epi, flags in ((N.EPI_STORE_T, 32), (N.EPI_GELU_T, 32 | 4), (N.EPI_GELU_T, 64)):
+        assert N_.esmk_debug_gemm_plan(300, 256, 192, epi, flags, out) != 0 and "esmk_debug_gemm_plan" in err()
