@@ -95,6 +95,9 @@ SIGNATURES = {
             c_void_p, c_size_t, c_void_p,
         ],
     ),
+    "esmk_rows_workspace_bytes": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
+    "esmk_forward_rows": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "esmk_packed_workspace_bytes": (c_int, [c_void_p, c_int, c_int, c_uint32, POINTER(c_size_t)]),
     "esmk_forward_packed": (
         c_int,
@@ -221,6 +224,8 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
          c_void_p],
     ),
+    "esmk_op_mask_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "esmk_op_log_softmax_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "esmk_op_contacts": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

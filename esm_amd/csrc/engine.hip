@@ -113,6 +113,15 @@ struct PackedCtx {
     bool maps = false, maps_lowp = false;
     void* maps_out = nullptr;
 };
+// Row selection (esmk_forward_rows): the layer stack runs on all B*T rows, the head of the model — final LayerNorm, LM head,
+// vocabulary GEMM — on the n_sel gathered rows only, and a log-softmax turns their logits into logprobs_out.  The gathered
+// rows and the head's intermediates live behind the forward's own workspace (plan_rows).
+struct RowSel {
+    const int32_t* sel_dev = nullptr;  // int32 [n_sel] flat row indices b*T + t, device data: clamped by the gather kernel
+    int n_sel = 0;
+    float* logprobs_out = nullptr;     // fp32 [n_sel, V]
+    size_t x = 0, h = 0, g32 = 0, logits = 0;  // byte offsets into the workspace
+};
 // query blocks of 128 rows: sum over segments of ceil(len / 128) <= rows / 128 + n_seg
 inline size_t packed_items_bound(int n_seg, int rows) { return (size_t)rows / 128 + (size_t)n_seg; }
 // int32 slots of the packed batch's table in front of the contact tables (kept 8-byte aligned for their offsets)
@@ -194,6 +203,20 @@ Workspace plan_workspace(const esmk_model* m, int B, int T, uint32_t flags, int 
     }
     w.total = c.off;
     return w;
+}
+
+// esmk_forward_rows: the forward's workspace, then the selected rows of the stream (fp32), their operand-dtype rows, the fp32
+// scratch of the head and the selected logits.  No pad rows: every GEMM kernel clamps its A-row reads to row M - 1 and stores
+// rows below M only, so M = n_sel is launched as it is.
+size_t plan_rows(const esmk_model* m, int B, int T, int n_sel, RowSel* rs) {
+    Carve c;
+    c.take(plan_workspace(m, B, T, ESMK_OUT_LOGITS).total);
+    const size_t n = (size_t)n_sel;
+    rs->x = c.take(n * m->E * 4);
+    rs->h = c.take(n * std::max(m->Kp, m->EA) * op_size(m->cfg.operand_dtype));
+    rs->g32 = c.take(n * m->E * 4);
+    rs->logits = c.take(n * m->V * 4);
+    return c.off;
 }
 
 int ensure_rope(esmk_model* m, int T, hipStream_t st) {
@@ -586,7 +609,7 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
                         const int32_t* repr_layers, int n_repr, void* const* repr_out_dev,
                         uint32_t out_flags, void* logits_out_dev, void* attn_out_dev,
                         void* contacts_out_dev, void* workspace_dev, size_t workspace_bytes,
-                        void* stream, const PackedCtx* pc);
+                        void* stream, const PackedCtx* pc, const RowSel* rs = nullptr);
 
 int esmk_forward(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev, int B, int T,
                  const int32_t* repr_layers, int n_repr, void* const* repr_out_dev,
@@ -596,6 +619,44 @@ int esmk_forward(esmk_model* m, const void* packed_dev, const int64_t* tokens_de
     return forward_impl(m, packed_dev, tokens_dev, B, T, repr_layers, n_repr, repr_out_dev, out_flags,
                         logits_out_dev, attn_out_dev, contacts_out_dev, workspace_dev, workspace_bytes, stream,
                         nullptr);
+}
+
+// ---- variant scoring: log-probabilities of selected rows (examples/variant-prediction/predict.py) ---------
+static int check_rows(const char* who, const esmk_model* m, int B, int T, int n_sel) {
+    const std::string w(who);
+    if (m->is_msa) return fail(w + ": MSA handle (the MSA Transformer has no row-selected forward)");
+    if (B <= 0 || T <= 0) return fail(w + ": B and T must be positive");
+    if ((long long)B * T > ESMK_MAX_ROWS) return fail(w + ": B*T exceeds 2^24 rows");
+    if (n_sel <= 0) return fail(w + ": n_sel must be positive");
+    if (n_sel > ESMK_MAX_ROWS) return fail(w + ": n_sel exceeds 2^24 rows");
+    if (m->V > 64) return fail(w + ": vocabulary above 64 entries (the log-softmax holds one entry per lane)");
+    return 0;
+}
+
+int esmk_rows_workspace_bytes(const esmk_model* m, int B, int T, int n_sel, size_t* bytes, size_t* logits_offset) {
+    if (!m || !bytes) return fail("esmk_rows_workspace_bytes: null argument");
+    if (check_rows("esmk_rows_workspace_bytes", m, B, T, n_sel)) return 1;
+    RowSel rs;
+    *bytes = plan_rows(m, B, T, n_sel, &rs);
+    if (logits_offset) *logits_offset = rs.logits;
+    return 0;
+}
+
+int esmk_forward_rows(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev, int B, int T,
+                      const int32_t* sel_rows_dev, int n_sel, float* logprobs_out_dev, void* workspace_dev,
+                      size_t workspace_bytes, void* stream) {
+    if (!m || !packed_dev || !tokens_dev || !sel_rows_dev || !logprobs_out_dev || !workspace_dev)
+        return fail("esmk_forward_rows: null argument");
+    if (check_rows("esmk_forward_rows", m, B, T, n_sel)) return 1;
+    RowSel rs;
+    if (workspace_bytes < plan_rows(m, B, T, n_sel, &rs)) return fail("esmk_forward_rows: workspace too small");
+    if (!m->cfg.no_rope && m->inv_freq.empty()) return fail("esmk_forward_rows: esmk_set_rope_inv_freq was not called");
+    rs.sel_dev = sel_rows_dev;
+    rs.n_sel = n_sel;
+    rs.logprobs_out = logprobs_out_dev;
+    return forward_impl(m, packed_dev, tokens_dev, B, T, nullptr, 0, nullptr, ESMK_OUT_LOGITS,
+                        (char*)workspace_dev + rs.logits, nullptr, nullptr, workspace_dev, workspace_bytes, stream, nullptr,
+                        &rs);
 }
 
 // ---- token-packed batches (no compute on padding) --------------------------------------
@@ -796,12 +857,13 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
                         const int32_t* repr_layers, int n_repr, void* const* repr_out_dev,
                         uint32_t out_flags, void* logits_out_dev, void* attn_out_dev,
                         void* contacts_out_dev, void* workspace_dev, size_t workspace_bytes,
-                        void* stream, const PackedCtx* pc) {
-    if (!m || !packed_dev || !tokens_dev || !workspace_dev) return fail("esmk_forward: null argument");
-    if (m->is_msa) return fail("esmk_forward: MSA handle (use esmk_msa_forward)");
-    if (B <= 0 || T <= 0) return fail("esmk_forward: B and T must be positive");
-    if ((long long)B * T > ESMK_MAX_ROWS) return fail("esmk_forward: B*T exceeds 2^24 rows");
-    if (n_repr > 0 && (!repr_layers || !repr_out_dev)) return fail("esmk_forward: null repr arrays");
+                        void* stream, const PackedCtx* pc, const RowSel* rs) {
+    const std::string who(rs ? "esmk_forward_rows" : "esmk_forward");  // every message names the entry that was called
+    if (!m || !packed_dev || !tokens_dev || !workspace_dev) return fail(who + ": null argument");
+    if (m->is_msa) return fail(who + ": MSA handle (use esmk_msa_forward)");
+    if (B <= 0 || T <= 0) return fail(who + ": B and T must be positive");
+    if ((long long)B * T > ESMK_MAX_ROWS) return fail(who + ": B*T exceeds 2^24 rows");
+    if (n_repr > 0 && (!repr_layers || !repr_out_dev)) return fail(who + ": null repr arrays");
     const bool want_logits = out_flags & ESMK_OUT_LOGITS;
     const bool want_contacts = out_flags & ESMK_OUT_CONTACTS;
     // contacts alone (predict_contacts, esm2.py:146-147): accumulated layer by layer, no attention tensor
@@ -810,16 +872,16 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
     const int S_ct = T - (m->cfg.prepend_bos ? 1 : 0) - (m->cfg.append_eos ? 1 : 0);
     const bool repr_lowp = out_flags & ESMK_OUT_REPR_LOWP, attn_lowp = out_flags & ESMK_OUT_ATTN_LOWP;
     if (attn_lowp && want_attn && want_contacts)
-        return fail("esmk_forward: ESMK_OUT_ATTN_LOWP cannot be combined with contacts computed from the attention tensor");
-    if (want_logits && !logits_out_dev) return fail("esmk_forward: logits buffer missing");
-    if (want_attn && !attn_out_dev) return fail("esmk_forward: attention buffer missing");
-    if (want_contacts && !contacts_out_dev) return fail("esmk_forward: contacts buffer missing");
+        return fail(who + ": ESMK_OUT_ATTN_LOWP cannot be combined with contacts computed from the attention tensor");
+    if (want_logits && !logits_out_dev) return fail(who + ": logits buffer missing");
+    if (want_attn && !attn_out_dev) return fail(who + ": attention buffer missing");
+    if (want_contacts && !contacts_out_dev) return fail(who + ": contacts buffer missing");
     for (int i = 0; i < n_repr; ++i)
         if (repr_layers[i] < 0 || repr_layers[i] > m->L || !repr_out_dev[i])
-            return fail("esmk_forward: bad repr layer request");
+            return fail(who + ": bad repr layer request");
     const bool packed_maps = pc != nullptr && pc->maps;
     const Workspace w = plan_workspace(m, B, T, out_flags, pc ? pc->n_seg : 0, pc ? pc->ct : nullptr, packed_maps);
-    if (workspace_bytes < w.total) return fail("esmk_forward: workspace too small");
+    if (workspace_bytes < w.total) return fail(who + ": workspace too small");
 
     hipStream_t st = (hipStream_t)stream;
     const int op = m->cfg.operand_dtype;
@@ -925,7 +987,7 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
     // ffn3 from fc1's GELU epilogue (GemmArgs::x3_out)
     const bool x3 = split_x3(m);
     if (x3 && (pc != nullptr || m->D != 64 || Kp != E || EA != E))
-        return fail("esmk_forward: the f16x3 precision mode runs padded batches of head_dim-64 models (no token-packed form)");
+        return fail(who + ": the f16x3 precision mode runs padded batches of head_dim-64 models (no token-packed form)");
     void* a3 = x3 ? (void*)(ws + w.a3) : nullptr;
     void* ffn3 = x3 ? (void*)(ws + w.ffn3) : nullptr;
     auto layer_gemm = [&](int cls, GemmArgs a, int epi, double out_bytes_per_elem) -> int {
@@ -939,12 +1001,14 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
         ESMK_TRY(launch_gemm(a, epi, op, st));
         return 0;
     };
-    auto lnorm = [&](const float* in, size_t go, size_t bo, void* y, float* y32) -> int {
-        ProfScope ps(m, st, PC_LAYERNORM, 8 * NE, NE * (4 + (y ? os : 0) + (y32 ? 4 : 0)));
+    auto lnorm = [&](const float* in, size_t go, size_t bo, void* y, float* y32, int rows = 0) -> int {
+        if (rows <= 0) rows = N;  // (the head of esmk_forward_rows runs on its selection)
+        const double RE = (double)rows * E;
+        ProfScope ps(m, st, PC_LAYERNORM, 8 * RE, RE * (4 + (y ? os : 0) + (y32 ? 4 : 0)));
         LnExtra ex;
         ex.ldy = Kp;  // normalised rows are K operands: row stride = E rounded up to the 64-wide K tile
         if (esm1) ex.eps = 1e-12f;  // ESM1LayerNorm (modules.py:44-65)
-        ESMK_TRY(launch_layernorm_ex(in, (const float*)(pk + go), (const float*)(pk + bo), y, y32, N, E, op, ex, st));
+        ESMK_TRY(launch_layernorm_ex(in, (const float*)(pk + go), (const float*)(pk + bo), y, y32, rows, E, op, ex, st));
         return 0;
     };
     auto ln_x3 = [&](size_t go, size_t bo) -> int {  // LayerNorm(x) -> hi | hi | lo operand rows (LnExtra::x3)
@@ -959,12 +1023,12 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
     // layer 0, then by the residual epilogues), hB = attention context; without the fold both are `h`
     const bool fold = m->fold;
     if (fold && m->fold_image != packed_dev)
-        return fail("esmk_forward: LayerNorm fold: this packed image is not the one the handle's weights were last packed "
+        return fail(who + ": LayerNorm fold: this packed image is not the one the handle's weights were last packed "
                     "into (one image per handle at a time: re-pack, or use a second handle)");
     if (fold)
         for (int l = 0; l < L; ++l)
             if ((m->fold_state[l] & FB_ALL_W) != FB_ALL_W)
-                return fail("esmk_forward: LayerNorm fold: the q/k/v or fc1 weights of layer " + std::to_string(l) +
+                return fail(who + ": LayerNorm fold: the q/k/v or fc1 weights of layer " + std::to_string(l) +
                             " were not packed after the layer's LayerNorm parameters");
     void* hA = h;
     void* hB = fold ? (void*)(ws + w.h2) : h;
@@ -1014,7 +1078,7 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
         if (esm1b) {
             // esm1.py:133-139: + learned positions, emb_layer_norm_before, padded positions zeroed
             if (T_rope > m->cfg.num_positions - m->cfg.pad_idx - 1)
-                return fail("esmk_forward: sequence length above the maximum of the positional embedding");
+                return fail(who + ": sequence length above the maximum of the positional embedding");
             if (pc)
                 ESMK_TRY(launch_add_positions(tokens_dev, (const float*)(pk + m->pos_emb), x, pc->n_seg, pc->max_len, E,
                                               m->cfg.pad_idx, m->cfg.num_positions, st, (const int*)(ws + w.tables)));
@@ -1212,19 +1276,35 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
         if ((l + 1 < L || esm1) && repr_copy(l + 1, x)) return 1;  // esm2.py:117-118; ESM-1: layer L too (no final LayerNorm)
     }
 
+    // The head of the model runs on the rows it is asked for: all N of them, or (esmk_forward_rows) the selection gathered
+    // out of the final stream.  Every kernel below computes a row from that row alone, so a selected row carries the bits
+    // the same row has in esmk_forward.
+    int Nt = N;
+    float* xt = x;
+    void* ht = h;
+    float* g32t = g32;
+    if (rs) {
+        Nt = rs->n_sel;
+        xt = (float*)(ws + rs->x);
+        ht = ws + rs->h;
+        g32t = (float*)(ws + rs->g32);
+        ProfScope ps(m, st, PC_COPY, 0, 8.0 * Nt * E);
+        ESMK_TRY(launch_gather_rows(x, rs->sel_dev, xt, N, E, Nt, st));
+        if (Kp != E) ESMK_TRY(hipMemsetAsync(ht, 0, (size_t)Nt * std::max(Kp, EA) * os, st));  // finite pad columns, as above
+    }
     if (esm1) {
         // esm1.py:173-175: no final LayerNorm; logits = x . embed_out^T (+ embed_out_bias): one GEMM on the rounded stream
         if (want_logits) {
             {
-                ProfScope ps(m, st, PC_COPY, 0, (4 + os) * NE);
-                ESMK_TRY(launch_convert(x, ESMK_DT_F32, h, op, (size_t)N * E, st));  // head_dim 64: Kp == E
+                ProfScope ps(m, st, PC_COPY, 0, (4 + os) * (double)Nt * E);
+                ESMK_TRY(launch_convert(xt, ESMK_DT_F32, ht, op, (size_t)Nt * E, st));  // head_dim 64: Kp == E
             }
             g = GemmArgs();
-            g.A = h;
+            g.A = ht;
             g.W = pk + m->out_w;
             g.bias = m->final_bias ? (const float*)(pk + m->out_b) : nullptr;
             g.out = logits_out_dev;
-            g.M = N;
+            g.M = Nt;
             g.N = m->V;
             g.K = Kp;
             if (gemm(PC_LM_LOGITS, g, EPI_STORE_F32, 4)) return 1;
@@ -1252,7 +1332,7 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
             if (repr_layers[i] == L && repr_out_dev[i] != rep_lp)
                 ESMK_TRY(hipMemcpyAsync(repr_out_dev[i], rep_lp, (size_t)N * E * os, hipMemcpyDeviceToDevice, st));
     } else if (want_logits || wants_repr(L)) {
-        if (lnorm(x, m->fin_g, m->fin_b, want_logits ? h : nullptr, rep_last)) return 1;
+        if (lnorm(xt, m->fin_g, m->fin_b, want_logits ? ht : nullptr, rep_last, Nt)) return 1;
         for (int i = 0; i < n_repr; ++i)  // duplicates of layer L, if any
             if (repr_layers[i] == L && repr_out_dev[i] != rep_last)
                 ESMK_TRY(launch_copy_f32(rep_last, (float*)repr_out_dev[i], (size_t)N * E, st));
@@ -1261,40 +1341,46 @@ static int forward_impl(esmk_model* m, const void* packed_dev, const int64_t* to
         // f16x2 precision mode: the head (modules.py:308-314) in fp32 on the exact-fp32 MFMA path — two small GEMMs per
         // forward; neither its weights nor its activations are rounded to fp16, so the logits carry only the error of
         // the representation itself
-        float* a32 = (!repr_lowp && rep_last != nullptr) ? rep_last : g32;
-        if (a32 == g32 && lnorm(x, m->fin_g, m->fin_b, nullptr, g32)) return 1;  // the normalised stream in fp32
+        const double NtE = (double)Nt * E;
+        float* a32 = (!repr_lowp && rep_last != nullptr) ? rep_last : g32t;
+        if (a32 == g32t && lnorm(xt, m->fin_g, m->fin_b, nullptr, g32t, Nt)) return 1;  // the normalised stream in fp32
         {
-            ProfScope ps(m, st, PC_LM_DENSE, 2.0 * N * (double)E * E, (2.0 * NE + (double)E * E) * 4);
-            ESMK_TRY(launch_gemm32(a32, E, (const float*)(pk + m->lm_w32), (const float*)(pk + m->lm_b), x, E, N, E, E, true, st));
+            ProfScope ps(m, st, PC_LM_DENSE, 2.0 * Nt * (double)E * E, (2.0 * NtE + (double)E * E) * 4);
+            ESMK_TRY(launch_gemm32(a32, E, (const float*)(pk + m->lm_w32), (const float*)(pk + m->lm_b), xt, E, Nt, E, E, true, st));
         }
-        if (lnorm(x, m->lm_lng, m->lm_lnb, nullptr, g32)) return 1;  // x (the residual stream) is dead: dense output
+        if (lnorm(xt, m->lm_lng, m->lm_lnb, nullptr, g32t, Nt)) return 1;  // xt (the residual stream) is dead: dense output
         {
-            ProfScope ps(m, st, PC_LM_LOGITS, 2.0 * N * (double)E * m->V, (NE + (double)m->V * E + (double)N * m->V) * 4);
-            ESMK_TRY(launch_gemm32(g32, E, (const float*)(pk + m->embed_f32), (const float*)(pk + m->lm_bias),
-                                   (float*)logits_out_dev, m->V, N, m->V, E, false, st));
+            ProfScope ps(m, st, PC_LM_LOGITS, 2.0 * Nt * (double)E * m->V, (NtE + (double)m->V * E + (double)Nt * m->V) * 4);
+            ESMK_TRY(launch_gemm32(g32t, E, (const float*)(pk + m->embed_f32), (const float*)(pk + m->lm_bias),
+                                   (float*)logits_out_dev, m->V, Nt, m->V, E, false, st));
         }
     } else if (want_logits) {  // modules.py:308-314
         g = GemmArgs();
-        g.A = h;
+        g.A = ht;
         g.W = pk + m->lm_w;
         g.bias = (const float*)(pk + m->lm_b);
-        g.out = g32;
-        g.M = N;
+        g.out = g32t;
+        g.M = Nt;
         g.N = E;
         g.K = Kp;
         if (gemm(PC_LM_DENSE, g, EPI_GELU_F32, 4)) return 1;
-        if (lnorm(g32, m->lm_lng, m->lm_lnb, h, nullptr)) return 1;
+        if (lnorm(g32t, m->lm_lng, m->lm_lnb, ht, nullptr, Nt)) return 1;
         g = GemmArgs();
-        g.A = h;
+        g.A = ht;
         g.W = pk + m->embed_op;
         g.bias = (const float*)(pk + m->lm_bias);
         g.out = logits_out_dev;
-        g.M = N;
+        g.M = Nt;
         g.N = m->V;
         g.K = Kp;
         if (gemm(PC_LM_LOGITS, g, EPI_STORE_F32, 4)) return 1;
     }
     }  // !esm1
+    if (rs) {  // torch.log_softmax(logits, dim=-1) of the selected rows.  Profiles of this entry have no classes of their own:
+        // the log-softmax is counted under "lm_head_logits", the gather (and its pad-column memset) under "repr_copy"
+        ProfScope ps(m, st, PC_LM_LOGITS, 0, 8.0 * Nt * m->V);
+        ESMK_TRY(launch_log_softmax_rows((const float*)logits_out_dev, rs->logprobs_out, nullptr, nullptr, Nt, m->V, st));
+    }
     if (fused_ct && pc) {
         const CtPackedPlan& cp = *pc->ct;
         ProfScope ps(m, st, PC_CONTACTS, 0, 4.0 * ((double)cp.sum_len2 * 2 + 3.0 * L * H * T));
@@ -2175,6 +2261,27 @@ int esmk_op_msa_row_softmax(const float* scores_dev, const float* keep_dev, cons
         return fail("esmk_op_msa_row_softmax: operand_dtype must be fp16 or bf16");
     ESMK_TRY(launch_msa_row_softmax(scores_dev, keep_dev, any_pad_dev, probs_out, attn_out, B, H, R, C, ldp, layer,
                                     num_layers_total, operand_dtype, (hipStream_t)stream, nslice));
+    return 0;
+}
+
+int esmk_op_mask_rows(const int64_t* tokens_dev, const int32_t* src_row_dev, const int32_t* pos_dev, int64_t* out_dev, int B,
+                      int T, int n, int mask_idx, void* stream) {
+    if (!tokens_dev || !pos_dev || !out_dev) return fail("esmk_op_mask_rows: null argument");
+    if (B <= 0 || T <= 0 || n <= 0) return fail("esmk_op_mask_rows: B, T and n must be positive");
+    if ((long long)B * T > ESMK_MAX_ROWS || (long long)n * T > ESMK_MAX_ROWS)
+        return fail("esmk_op_mask_rows: B*T or n*T exceeds 2^24 rows");
+    ESMK_TRY(launch_mask_rows(tokens_dev, src_row_dev, pos_dev, out_dev, B, T, n, mask_idx, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_log_softmax_rows(const float* logits_dev, float* out_dev, const int32_t* target_dev, float* target_out_dev, int n,
+                             int V, void* stream) {
+    if (!logits_dev || !out_dev) return fail("esmk_op_log_softmax_rows: null argument");
+    if ((target_dev != nullptr) != (target_out_dev != nullptr))
+        return fail("esmk_op_log_softmax_rows: target_dev and target_out_dev go together");
+    if (n <= 0 || n > ESMK_MAX_ROWS) return fail("esmk_op_log_softmax_rows: n must be in 1 .. 2^24");
+    if (V <= 0 || V > 64) return fail("esmk_op_log_softmax_rows: V must be in 1 .. 64 (one vocabulary entry per lane)");
+    ESMK_TRY(launch_log_softmax_rows(logits_dev, out_dev, target_dev, target_out_dev, n, V, (hipStream_t)stream));
     return 0;
 }
 

@@ -200,6 +200,15 @@ hipError_t launch_copy_f32(const float* src, float* dst, size_t n, hipStream_t s
 // out[b,:] = mean of rows [first, first + min(count[b], T - first)) of x[b] ([B,T,E], any dtype code); NaN if empty
 hipError_t launch_masked_row_mean(const void* x, int x_dtype, const int* count, float* out, int B, int T, int E,
                                   int first, hipStream_t st);
+// scoring.hip — variant scoring (esmk_forward_rows).  out int64 [n,T]: row i = tokens[src_row[i]] (row 0 when src_row is
+// null) with position pos[i] set to mask_idx
+hipError_t launch_mask_rows(const int64_t* tokens, const int* src_row, const int* pos, int64_t* out, int B, int T, int n,
+                            int mask_idx, hipStream_t st);
+// out [n,E] = rows sel[i] (clamped to [0,N)) of x [N,E], fp32, E % 4 == 0
+hipError_t launch_gather_rows(const float* x, const int* sel, float* out, int N, int E, int n, hipStream_t st);
+// out [n,V] = log_softmax(logits [n,V]), V <= 64; target (optional, int32 [n]): tgt_out[i] = out[i, target[i]]
+hipError_t launch_log_softmax_rows(const float* logits, float* out, const int* target, float* tgt_out, int n, int V,
+                                   hipStream_t st);
 // contact head (modules.py:27-41,338-357)
 hipError_t launch_contacts(const float* attn, const int64_t* tokens, const float* w,
                            const float* b, float* scratch, float* out, int B, int C, int T,

@@ -664,6 +664,29 @@ class ESM2(nn.Module):
                 out["attentions"] = views
         return out
 
+    # ------------------------------------------------------------------------------------------
+    # zero-shot variant scoring (esm_amd/scoring.py; reference examples/variant-prediction/predict.py)
+    supports_scoring = True  # esmk_forward_rows: ESM-2, ESM-1b / ESM-1v, ESM-1; not the MSA Transformer
+
+    def masked_marginals(self, tokens, positions=None, chunk=None):
+        """``esm_amd.scoring.masked_marginals``: [B, T, V] fp32 log-probabilities, row (b, i) from the forward with token
+        (b, i) alone masked."""
+        from . import scoring
+
+        return scoring.masked_marginals(self, tokens, positions=positions, chunk=chunk)
+
+    def wt_marginals(self, tokens):
+        """``esm_amd.scoring.wt_marginals``: [B, T, V] fp32 log-probabilities of the unmasked forward, non-pad rows."""
+        from . import scoring
+
+        return scoring.wt_marginals(self, tokens)
+
+    def pseudo_log_likelihood(self, tokens, positions=None, chunk=None):
+        """``esm_amd.scoring.pseudo_log_likelihood``: [B] fp64, sum of the masked-marginal log-probability of the true token."""
+        from . import scoring
+
+        return scoring.pseudo_log_likelihood(self, tokens, positions=positions, chunk=chunk)
+
     def profile_begin(self):
         """Arm per-kernel-class HIP-event timing of the following forward calls (bench.py)."""
         from . import _native as N

@@ -262,6 +262,15 @@ class MSATransformer(nn.Module):
     def predict_contacts(self, tokens):
         return self(tokens, return_contacts=True)["contacts"]
 
+    supports_scoring = False  # esmk_forward_rows takes single-sequence models only
+
+    def masked_marginals(self, tokens, positions=None, chunk=None):
+        from . import scoring
+
+        scoring._refuse_msa(self)
+
+    wt_marginals = pseudo_log_likelihood = masked_marginals
+
     def profile_begin(self):
         """Arm per-kernel-class HIP-event timing of the following forward calls (bench.py --workload msa1b)."""
         from .esm2 import ESM2

@@ -437,3 +437,32 @@ class QkvHandle:
         if getattr(self, "h", None):
             N.lib.esmk_destroy(self.h)
             self.h = None
+
+
+def mask_rows(tokens, positions, src_rows=None, mask_idx=32):
+    """[n,T] int64: row i = tokens[src_rows[i]] (row 0 of [B,T] / the only row of [T] when ``src_rows`` is None) with
+    position ``positions[i]`` set to ``mask_idx`` — the masked batch of the masked-marginal strategy (reference
+    examples/variant-prediction/predict.py:208-209), built on the device.  positions / src_rows int32 [n]."""
+    _req_cuda(tokens, positions, src_rows)
+    tokens = tokens.view(1, -1) if tokens.dim() == 1 else tokens
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and positions.dtype == torch.int32
+    assert src_rows is None or (src_rows.dtype == torch.int32 and src_rows.numel() == positions.numel())
+    B, T = tokens.shape
+    n = positions.numel()
+    out = torch.empty((n, T), dtype=torch.int64, device=tokens.device)
+    N.check(N.lib.esmk_op_mask_rows(N.ptr(tokens), N.ptr(src_rows), N.ptr(positions), N.ptr(out), B, T, n, int(mask_idx),
+                                    N.cur_stream()))
+    return out
+
+
+def log_softmax_rows(logits, target=None):
+    """torch.log_softmax(logits, -1) of fp32 [n,V] rows, V <= 64 (one wavefront per row).  ``target`` int32 [n]: also returns
+    the log-probability at that column of every row, the same bits as the gathered entry of the full output."""
+    _req_cuda(logits, target)
+    assert logits.dtype == torch.float32 and logits.dim() == 2
+    assert target is None or (target.dtype == torch.int32 and target.numel() == logits.shape[0])
+    n, V = logits.shape
+    out = torch.empty_like(logits)
+    tgt = torch.empty((n,), dtype=torch.float32, device=logits.device) if target is not None else None
+    N.check(N.lib.esmk_op_log_softmax_rows(N.ptr(logits), N.ptr(out), N.ptr(target), N.ptr(tgt), n, V, N.cur_stream()))
+    return out if target is None else (out, tgt)

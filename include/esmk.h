@@ -211,6 +211,27 @@ int esmk_forward_packed_maps(esmk_model* m, const void* packed_dev, const int64_
                              size_t attn_out_elems, void* contacts_out_dev, void* workspace_dev, size_t workspace_bytes,
                              void* stream);
 
+/* ---- variant scoring: log-probabilities of selected rows (examples/variant-prediction/predict.py) -------
+ * The reference scores a protein with one forward per masked position at B = 1, builds [1,T,V] logits each time and keeps
+ * one row (predict.py:205-215, :138-143).  Here the caller runs those sequences as ONE padded batch and names the rows it
+ * wants: the layer stack runs on all B*T rows; the final LayerNorm, the LM head (ESM-1: the embed_out GEMM; split-weight
+ * modes: the fp32 head) and the vocabulary GEMM run on the n_sel selected rows only, and a log-softmax over the vocabulary
+ * (torch.log_softmax(logits, dim=-1)) is written for exactly those rows.  No [B,T,V] tensor exists.  Every kernel of the
+ * head computes a row from that row alone, so a selected row's logits are the bits esmk_forward gives that row.
+ *   tokens_dev       int64 [B,T], padded as for esmk_forward
+ *   sel_rows_dev     int32 [n_sel] on the DEVICE, flat row indices b*T + t in any order, repeats allowed.  Not validated on
+ *                    the host: the gather clamps each index to [0, B*T), so a wrong index reads a valid row
+ *   logprobs_out_dev fp32 [n_sel, V]
+ *   workspace        esmk_rows_workspace_bytes(m, B, T, n_sel, &bytes, &logits_offset); after the call the selected logits
+ *                    (fp32 [n_sel, V]) stay at byte offset *logits_offset of the workspace (logits_offset may be NULL)
+ * vocab <= 64.  ESM-2, ESM-1b / ESM-1v and ESM-1 handles, with whatever operand dtype and precision mode esmk_forward runs
+ * that handle in (the f16x3 mode keeps its restriction to head_dim-64 models here too); MSA handles are refused.  The whole
+ * call runs on `stream`; error messages name esmk_forward_rows. */
+int esmk_rows_workspace_bytes(const esmk_model* m, int B, int T, int n_sel, size_t* bytes, size_t* logits_offset);
+int esmk_forward_rows(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev, int B, int T,
+                      const int32_t* sel_rows_dev, int n_sel, float* logprobs_out_dev, void* workspace_dev,
+                      size_t workspace_bytes, void* stream);
+
 /* ---- MSA Transformer (reference esm/model/msa_transformer.py:20-238, esm/axial_attention.py) -------- */
 
 /* Constructor arguments of MSATransformer (msa_transformer.py:88-144) + alphabet ids. */
@@ -559,6 +580,17 @@ int esmk_op_gemm_ex(const esmk_gemm_ex_args* args, void* stream);
 int esmk_op_msa_row_softmax(const float* scores_dev, const float* keep_dev, const int32_t* any_pad_dev, void* probs_out,
                             float* attn_out, int B, int H, int R, int C, int ldp, int layer, int num_layers_total,
                             int nslice, int operand_dtype, void* stream);
+
+/* The kernels of esmk_forward_rows' callers, one launch at a time (tests).
+ * esmk_op_mask_rows: the masked batch of the masked-marginal strategy (predict.py:208-209 for n positions at once):
+ *   out int64 [n,T], row i = tokens[src_row[i], :] (tokens int64 [B,T]; src_row int32 [n] or NULL = row 0, clamped to
+ *   [0,B)) with position pos[i] (int32 [n]) replaced by mask_idx; a position outside [0,T) masks nothing.
+ * esmk_op_log_softmax_rows: out fp32 [n,V] = log_softmax(logits fp32 [n,V]) = x - max - log(sum exp(x - max)), V <= 64;
+ *   target int32 [n] (with target_out fp32 [n], both or neither): target_out[i] = out[i, clamp(target[i], 0, V-1)]. */
+int esmk_op_mask_rows(const int64_t* tokens_dev, const int32_t* src_row_dev, const int32_t* pos_dev, int64_t* out_dev, int B,
+                      int T, int n, int mask_idx, void* stream);
+int esmk_op_log_softmax_rows(const float* logits_dev, float* out_dev, const int32_t* target_dev, float* target_out_dev, int n,
+                             int V, void* stream);
 
 /* ContactPredictionHead.forward (modules.py:338-357) incl. symmetrize/apc (modules.py:27-41).
  * attn fp32 [B,C=L*H,T,T]; w fp32 [C]; b fp32 [1]; scratch fp32 >= B*C*(T+1) floats;
