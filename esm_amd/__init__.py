@@ -9,6 +9,7 @@ from .alphabet import Alphabet, BatchConverter, MSABatchConverter  # noqa: F401
 from .fasta import FastaBatchedDataset, read_alignment_lines, read_fasta  # noqa: F401
 from .esm2 import ESM2  # noqa: F401
 from . import checkpoint as pretrained  # noqa: F401
-from .scoring import masked_marginals, pseudo_log_likelihood, score_mutations, wt_marginals  # noqa: F401
+from .scoring import (masked_joint, masked_marginals, parse_variant, pseudo_log_likelihood, score_mutations,  # noqa: F401
+                      score_variants, wt_marginals)
 
 __version__ = "0.1.0"

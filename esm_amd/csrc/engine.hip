@@ -2274,6 +2274,26 @@ int esmk_op_mask_rows(const int64_t* tokens_dev, const int32_t* src_row_dev, con
     return 0;
 }
 
+int esmk_op_mask_rows_multi(const int64_t* tokens_dev, const int32_t* src_row_dev, const int32_t* pos_off_dev,
+                            const int32_t* pos_dev, int64_t* out_dev, int B, int T, int n, int total, int mask_idx, void* stream) {
+    if (!tokens_dev || !pos_off_dev || !pos_dev || !out_dev) return fail("esmk_op_mask_rows_multi: null argument");
+    if (B <= 0 || T <= 0 || n <= 0) return fail("esmk_op_mask_rows_multi: B, T and n must be positive");
+    if (total < 0) return fail("esmk_op_mask_rows_multi: total must not be negative");
+    if ((long long)B * T > ESMK_MAX_ROWS || (long long)n * T > ESMK_MAX_ROWS)
+        return fail("esmk_op_mask_rows_multi: B*T or n*T exceeds 2^24 rows");
+    ESMK_TRY(launch_mask_rows_multi(tokens_dev, src_row_dev, pos_off_dev, pos_dev, out_dev, B, T, n, total, mask_idx,
+                                    (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_score_rows(const float* logprobs_dev, const int32_t* wt_dev, const int32_t* mt_dev, const int32_t* var_off_dev,
+                       double* out_dev, int n_rows, int n_var, int V, void* stream) {
+    if (!logprobs_dev || !wt_dev || !mt_dev || !var_off_dev || !out_dev) return fail("esmk_op_score_rows: null argument");
+    if (n_rows <= 0 || n_var <= 0 || V <= 0) return fail("esmk_op_score_rows: n_rows, n_var and V must be positive");
+    ESMK_TRY(launch_score_rows(logprobs_dev, wt_dev, mt_dev, var_off_dev, out_dev, n_rows, n_var, V, (hipStream_t)stream));
+    return 0;
+}
+
 int esmk_op_log_softmax_rows(const float* logits_dev, float* out_dev, const int32_t* target_dev, float* target_out_dev, int n,
                              int V, void* stream) {
     if (!logits_dev || !out_dev) return fail("esmk_op_log_softmax_rows: null argument");

@@ -204,11 +204,19 @@ hipError_t launch_masked_row_mean(const void* x, int x_dtype, const int* count, 
 // null) with position pos[i] set to mask_idx
 hipError_t launch_mask_rows(const int64_t* tokens, const int* src_row, const int* pos, int64_t* out, int B, int T, int n,
                             int mask_idx, hipStream_t st);
+// the same with a LIST of positions per copy (multi-mutant variants): pos[pos_off[i] : pos_off[i+1]] of row i set to mask_idx;
+// pos_off int32 [n+1] (clamped to [0,total]; hi < lo: no position), pos int32 [total] (outside [0,T): masks nothing)
+hipError_t launch_mask_rows_multi(const int64_t* tokens, const int* src_row, const int* pos_off, const int* pos, int64_t* out,
+                                  int B, int T, int n, int total, int mask_idx, hipStream_t st);
 // out [n,E] = rows sel[i] (clamped to [0,N)) of x [N,E], fp32, E % 4 == 0
 hipError_t launch_gather_rows(const float* x, const int* sel, float* out, int N, int E, int n, hipStream_t st);
 // out [n,V] = log_softmax(logits [n,V]), V <= 64; target (optional, int32 [n]): tgt_out[i] = out[i, target[i]]
 hipError_t launch_log_softmax_rows(const float* logits, float* out, const int* target, float* tgt_out, int n, int V,
                                    hipStream_t st);
+// out fp64 [n_var]: out[v] = sum, r ascending in [var_off[v], var_off[v+1]), of the fp32 difference lp[r,mt[r]] - lp[r,wt[r]], added
+// in fp64 by one lane per variant (no atomics); lp fp32 [n_rows,V], columns clamped to [0,V), offsets to [0,n_rows]
+hipError_t launch_score_rows(const float* lp, const int* wt, const int* mt, const int* var_off, double* out, int n_rows,
+                             int n_var, int V, hipStream_t st);
 // contact head (modules.py:27-41,338-357)
 hipError_t launch_contacts(const float* attn, const int64_t* tokens, const float* w,
                            const float* b, float* scratch, float* out, int B, int C, int T,

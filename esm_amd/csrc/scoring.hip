@@ -1,6 +1,8 @@
-// scoring.hip — the three small kernels of variant scoring (esmk_forward_rows, include/esmk.h): the masked batch of the
-// masked-marginal strategy built on the device, the row gather that lets the head of the model run on the selected rows
-// only, and the log-softmax over the vocabulary.  None of them is a hot loop: the layer stack in front of them is the time.
+// scoring.hip — the small kernels of variant scoring (esmk_forward_rows, include/esmk.h): the masked batch of the
+// masked-marginal strategy built on the device (one position per copy, or a list of positions per copy for multi-mutant
+// variants), the row gather that lets the head of the model run on the selected rows only, the log-softmax over the
+// vocabulary and the per-variant sum of log p(mt) - log p(wt).  None of them is a hot loop: the layer stack in front of
+// them is the time.
 #include "common.h"
 #include "kernels.h"
 #include <algorithm>
@@ -28,6 +30,38 @@ hipError_t launch_mask_rows(const int64_t* tokens, const int* src_row, const int
     const size_t total = (size_t)n * T;
     const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 8192);
     hipLaunchKernelGGL(mask_rows_kernel, dim3(blocks), dim3(256), 0, st, tokens, src_row, pos, out, B, T, n, (int64_t)mask_idx);
+    return hipGetLastError();
+}
+
+// out[i, :] = tokens[src_row[i], :] with every position of pos[pos_off[i] : pos_off[i + 1]] replaced by mask_idx: the joint
+// mask of a multi-mutant variant (all mutated positions masked in one forward).  One workgroup per copy, copies strided over
+// the grid; the row is copied, then (behind the barrier, so that the mask lands on top of the copy) the lanes stride over the
+// copy's position list.  All of the lists are device data the host never saw: a source row outside [0, B) is clamped, the
+// offsets are clamped to [0, total] (hi < lo: an empty list, a plain copy), a position outside [0, T) masks nothing, and a
+// repeated position stores the same value twice.
+__global__ __launch_bounds__(256) void mask_rows_multi_kernel(const int64_t* __restrict__ tokens, const int* __restrict__ src_row,
+                                                              const int* __restrict__ pos_off, const int* __restrict__ pos,
+                                                              int64_t* __restrict__ out, int B, int T, int n, int total,
+                                                              int64_t mask_idx) {
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {  // workgroup uniform: every lane reaches the barrier
+        const int b = src_row ? min(max(src_row[i], 0), B - 1) : 0;
+        const int64_t* in = tokens + (size_t)b * T;
+        int64_t* o = out + (size_t)i * T;
+        for (int t = threadIdx.x; t < T; t += 256) o[t] = in[t];
+        __syncthreads();
+        const int lo = min(max(pos_off[i], 0), total), hi = min(max(pos_off[i + 1], 0), total);
+        for (int j = lo + (int)threadIdx.x; j < hi; j += 256) {
+            const int p = pos[j];
+            if (p >= 0 && p < T) o[p] = mask_idx;
+        }
+    }
+}
+
+hipError_t launch_mask_rows_multi(const int64_t* tokens, const int* src_row, const int* pos_off, const int* pos, int64_t* out,
+                                  int B, int T, int n, int total, int mask_idx, hipStream_t st) {
+    if (!tokens || !pos_off || !pos || !out || B <= 0 || T <= 0 || n <= 0 || total < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mask_rows_multi_kernel, dim3((unsigned)std::min(n, 8192)), dim3(256), 0, st, tokens, src_row, pos_off, pos,
+                       out, B, T, n, total, (int64_t)mask_idx);
     return hipGetLastError();
 }
 
@@ -80,6 +114,35 @@ hipError_t launch_log_softmax_rows(const float* logits, float* out, const int* t
     if (n <= 0 || V <= 0 || V > 64 || (target != nullptr && tgt_out == nullptr)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(log_softmax_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, logits, out, target, tgt_out,
                        n, V);
+    return hipGetLastError();
+}
+
+// out[v] = sum over r in [var_off[v], var_off[v + 1]), ascending, of (lp[r, mt[r]] - lp[r, wt[r]]): the masked-marginal score of
+// variant v from its rows of log-probabilities.  Each term is the fp32 difference (the bits score_mutations gives a single
+// mutant), the terms are added in fp64 in index order by ONE lane per variant: the result does not depend on the launch
+// geometry, which a sum through atomics (torch.index_add_ on the device) would.  Columns are clamped to [0, V), offsets to
+// [0, n_rows]; an empty range (hi <= lo) gives 0.0.
+__global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ lp, const int* __restrict__ wt,
+                                                         const int* __restrict__ mt, const int* __restrict__ var_off,
+                                                         double* __restrict__ out, int n_rows, int n_var, int V) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < (size_t)n_var; v += stride) {
+        const int lo = min(max(var_off[v], 0), n_rows), hi = min(max(var_off[v + 1], 0), n_rows);
+        double sum = 0.0;
+        for (int r = lo; r < hi; ++r) {
+            const float* row = lp + (size_t)r * V;
+            const float term = row[min(max(mt[r], 0), V - 1)] - row[min(max(wt[r], 0), V - 1)];
+            sum += (double)term;
+        }
+        out[v] = sum;
+    }
+}
+
+hipError_t launch_score_rows(const float* lp, const int* wt, const int* mt, const int* var_off, double* out, int n_rows,
+                             int n_var, int V, hipStream_t st) {
+    if (!lp || !wt || !mt || !var_off || !out || n_rows <= 0 || n_var <= 0 || V <= 0) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)std::min<size_t>(((size_t)n_var + 255) / 256, 8192);
+    hipLaunchKernelGGL(score_rows_kernel, dim3(blocks), dim3(256), 0, st, lp, wt, mt, var_off, out, n_rows, n_var, V);
     return hipGetLastError();
 }
 

@@ -687,6 +687,20 @@ class ESM2(nn.Module):
 
         return scoring.pseudo_log_likelihood(self, tokens, positions=positions, chunk=chunk)
 
+    def masked_joint(self, tokens, position_sets, src=None, chunk=None, return_logits=False):
+        """``esm_amd.scoring.masked_joint``: one forward per position set with ALL its positions masked; (offsets, pos,
+        logprobs [n_rows, V]) of the masked rows."""
+        from . import scoring
+
+        return scoring.masked_joint(self, tokens, position_sets, src=src, chunk=chunk, return_logits=return_logits)
+
+    def score_variants(self, alphabet, sequence, variants, strategy="masked-marginals", offset_idx=0, sep=":", chunk=None):
+        """``esm_amd.scoring.score_variants``: floats, one per variant of one or more substitutions ('A42G:K50R')."""
+        from . import scoring
+
+        return scoring.score_variants(self, alphabet, sequence, variants, strategy=strategy, offset_idx=offset_idx, sep=sep,
+                                      chunk=chunk)
+
     def profile_begin(self):
         """Arm per-kernel-class HIP-event timing of the following forward calls (bench.py)."""
         from . import _native as N

@@ -271,6 +271,13 @@ class MSATransformer(nn.Module):
 
     wt_marginals = pseudo_log_likelihood = masked_marginals
 
+    def masked_joint(self, *args, **kwargs):
+        from . import scoring
+
+        scoring._refuse_msa(self)
+
+    score_variants = masked_joint
+
     def profile_begin(self):
         """Arm per-kernel-class HIP-event timing of the following forward calls (bench.py --workload msa1b)."""
         from .esm2 import ESM2

@@ -466,3 +466,43 @@ def log_softmax_rows(logits, target=None):
     tgt = torch.empty((n,), dtype=torch.float32, device=logits.device) if target is not None else None
     N.check(N.lib.esmk_op_log_softmax_rows(N.ptr(logits), N.ptr(out), N.ptr(target), N.ptr(tgt), n, V, N.cur_stream()))
     return out if target is None else (out, tgt)
+
+
+def mask_rows_multi(tokens, pos_offsets, positions, src_rows=None, mask_idx=32):
+    """[n,T] int64: row i = tokens[src_rows[i]] (row 0 / the only row when ``src_rows`` is None) with EVERY position of
+    ``positions[pos_offsets[i] : pos_offsets[i + 1]]`` set to ``mask_idx`` — the joint mask of a multi-mutant variant.
+    pos_offsets int32 [n + 1], positions int32 [total], src_rows int32 [n].  The lists are device data: offsets are clamped to
+    [0, total] (a descending pair is an empty list: a plain copy), a position outside [0, T) masks nothing, a repeated
+    position is harmless, a source row outside [0, B) is clamped."""
+    _req_cuda(tokens, pos_offsets, positions, src_rows)
+    tokens = tokens.view(1, -1) if tokens.dim() == 1 else tokens
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2
+    assert pos_offsets.dtype == torch.int32 and pos_offsets.dim() == 1 and pos_offsets.numel() >= 2
+    assert positions.dtype == torch.int32 and positions.dim() == 1
+    n = pos_offsets.numel() - 1
+    assert src_rows is None or (src_rows.dtype == torch.int32 and src_rows.numel() == n)
+    B, T = tokens.shape
+    total = positions.numel()
+    if total == 0:  # nothing to mask anywhere; the entry still wants a pointer it will not read
+        positions = torch.zeros((1,), dtype=torch.int32, device=tokens.device)
+    out = torch.empty((n, T), dtype=torch.int64, device=tokens.device)
+    N.check(N.lib.esmk_op_mask_rows_multi(N.ptr(tokens), N.ptr(src_rows), N.ptr(pos_offsets), N.ptr(positions), N.ptr(out),
+                                          B, T, n, total, int(mask_idx), N.cur_stream()))
+    return out
+
+
+def score_rows(logprobs, wt, mt, var_offsets):
+    """fp64 [n_var]: entry v = the sum over the rows r of ``var_offsets[v] : var_offsets[v + 1]``, ascending, of the fp32
+    difference ``logprobs[r, mt[r]] - logprobs[r, wt[r]]``, added in fp64 by one lane per variant (a fixed order: no
+    atomics).  logprobs fp32 [n_rows, V]; wt, mt int32 [n_rows] (clamped to [0, V)); var_offsets int32 [n_var + 1] (clamped
+    to [0, n_rows]; an empty range gives 0.0)."""
+    _req_cuda(logprobs, wt, mt, var_offsets)
+    assert logprobs.dtype == torch.float32 and logprobs.dim() == 2
+    n_rows, V = logprobs.shape
+    assert wt.dtype == torch.int32 and mt.dtype == torch.int32 and wt.numel() == n_rows and mt.numel() == n_rows
+    assert var_offsets.dtype == torch.int32 and var_offsets.dim() == 1 and var_offsets.numel() >= 2
+    n_var = var_offsets.numel() - 1
+    out = torch.empty((n_var,), dtype=torch.float64, device=logprobs.device)
+    N.check(N.lib.esmk_op_score_rows(N.ptr(logprobs), N.ptr(wt), N.ptr(mt), N.ptr(var_offsets), N.ptr(out), n_rows, n_var, V,
+                                     N.cur_stream()))
+    return out

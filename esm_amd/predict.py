@@ -14,6 +14,11 @@ The reference's ``compute_pppl`` (predict.py:143) looks the target up as ``seque
 <cls> token is the NEXT residue, so its column differs from this one.  wt-marginals and masked-marginals give the reference's
 numbers.
 
+A row may hold several substitutions joined by ``--mutation-sep`` (default ':', e.g. 'A42G:K50R').  Such a variant gets the
+masked-marginal score of the ESM-1v paper: all of its positions masked in one forward, log p(mutant) - log p(wild type) summed
+over them (``esm_amd.scoring.score_variants``); wt-marginals sums the same terms from the wild-type table, pseudo-ppl scores
+the sequence with all substitutions made.  A table without the separator is scored exactly as before.
+
 The MSA Transformer (``--msa-path``) is not served by the engine's scoring path: asking for it is an error.
 """
 import argparse
@@ -33,6 +38,8 @@ def create_parser():
     p.add_argument("--dms-input", type=pathlib.Path, required=True, help="CSV file of the deep mutational scan")
     p.add_argument("--mutation-col", type=str, default="mutant", help="column holding the mutation as 'A42G'")
     p.add_argument("--dms-output", type=pathlib.Path, required=True, help="CSV file to write: the input plus the scores")
+    p.add_argument("--mutation-sep", type=str, default=":",
+                   help="separator of the substitutions of a multi-mutant row, as in 'A42G:K50R'")
     p.add_argument("--offset-idx", type=int, default=0, help="index of the first residue in the mutation column's numbering")
     p.add_argument("--scoring-strategy", type=str, default="wt-marginals", choices=STRATEGIES)
     p.add_argument("--msa-path", type=pathlib.Path, default=None,
@@ -60,17 +67,25 @@ def write_table(path, fields, rows):
             w.writerow([i] + [row.get(f, "") for f in fields])
 
 
-def score_table(model, alphabet, sequence, mutations, strategy, offset_idx=0):
-    """One score per mutation string.  wt-marginals / masked-marginals: log p(mutant) - log p(wild type) at the position,
-    from one table of log-probabilities of the wild-type sequence; pseudo-ppl: the pseudo-log-likelihood of every MUTATED
-    sequence over the reference's positions (``esm_amd.scoring.pseudo_log_likelihood``), all mutants in one batch — the
-    log-probability of the masked token itself, not of ``sequence[i]`` one residue behind it as the reference's ``compute_pppl``
-    reads it (module docstring)."""
+def score_table(model, alphabet, sequence, mutations, strategy, offset_idx=0, sep=":"):
+    """One score per mutation string.
+
+    A table of single substitutions: wt-marginals / masked-marginals give log p(mutant) - log p(wild type) at the position,
+    from one table of log-probabilities of the wild-type sequence; pseudo-ppl gives the pseudo-log-likelihood of every
+    MUTATED sequence over the reference's positions (``esm_amd.scoring.pseudo_log_likelihood``), all mutants in one batch —
+    the log-probability of the masked token itself, not of ``sequence[i]`` one residue behind it as the reference's
+    ``compute_pppl`` reads it (module docstring).
+
+    A table in which some row joins several substitutions with ``sep`` ('A42G:K50R') is scored, every row of it, by
+    ``esm_amd.scoring.score_variants``: joint masks, summed marginals."""
     import torch
 
     from . import scoring
 
     scoring._refuse_msa(model)
+    mutations = list(mutations)
+    if sep and any(sep in mutation for mutation in mutations):
+        return scoring.score_variants(model, alphabet, sequence, mutations, strategy, offset_idx, sep)
     convert = alphabet.get_batch_converter()
     if strategy == "pseudo-ppl":
         mutated = []
@@ -89,7 +104,7 @@ def score_table(model, alphabet, sequence, mutations, strategy, offset_idx=0):
     _, _, tokens = convert([("protein1", sequence)])
     with torch.no_grad():
         table = model.wt_marginals(tokens) if strategy == "wt-marginals" else model.masked_marginals(tokens)
-    return scoring.score_mutations(table.cpu(), sequence, list(mutations), alphabet, offset_idx)
+    return scoring.score_mutations(table.cpu(), sequence, mutations, alphabet, offset_idx)
 
 
 def main(argv=None):
@@ -111,7 +126,8 @@ def main(argv=None):
         if not torch.cuda.is_available():
             raise SystemExit("esm_amd.predict: no GPU: the engine has no CPU path")
         model = model.eval().cuda()
-        scores = score_table(model, alphabet, args.sequence, mutations, args.scoring_strategy, args.offset_idx)
+        scores = score_table(model, alphabet, args.sequence, mutations, args.scoring_strategy, args.offset_idx,
+                             args.mutation_sep)
         for row, s in zip(rows, scores):
             row[location] = repr(float(s))
         fields.append(location)

@@ -9,6 +9,11 @@ batches that fill the GPU, and the head of the model — final LayerNorm, LM hea
 one masked row of every copy only.  Every kernel of the forward is batch-invariant bit for bit, so row (b, i) carries the
 bits of the reference's loop run on this model's own ``forward``.
 
+Variants with several substitutions ('A42G:K50R') take the masked-marginal score of the ESM-1v paper: ALL mutated
+positions of the variant are masked in one forward (``masked_joint``, ``esmk_op_mask_rows_multi``) and
+log p(mutant) - log p(wild type) is summed over them (``score_variants``, ``esmk_op_score_rows``: fp32 terms added in fp64
+in a fixed order).
+
 The functions are also methods of ``ESM2`` / ``ProteinBertModel`` (``model.masked_marginals(tokens)`` ...).  The MSA
 Transformer has no row-selected forward: its methods raise ``NotImplementedError``.
 """
@@ -192,6 +197,74 @@ def pseudo_log_likelihood(model, tokens, positions=None, chunk=None):
     return out
 
 
+@torch.no_grad()
+def masked_joint(model, tokens, position_sets, src=None, chunk=None, return_logits=False):
+    """Joint masks: for every set s of ``position_sets`` (an iterable of token positions of sequence ``src[s]``; ``src`` None:
+    sequence 0, and then B must be 1) ONE forward with all positions of the set replaced by <mask>, and the log-probabilities
+    at those positions.  Returns ``(offsets, pos, logprobs)``:
+
+    offsets   int64 [n_sets + 1] on the host: set s owns rows offsets[s] : offsets[s + 1]
+    pos       int64 [n_rows] on the device: the token position of every row, ascending inside a set
+    logprobs  fp32 [n_rows, V] on the device: log_softmax of the logits at that position
+    ``return_logits``: a fourth value, the selected fp32 logits (the bits ``forward`` of the masked sequence gives those rows).
+
+    An empty set, a position outside [0, T) or on a <pad> token raises ValueError.  ``chunk``: masked copies (sets) per
+    forward call; default what fills the GPU (about 65536 tokens).  The position lists are uploaded once for all chunks."""
+    from . import ops
+
+    tok = _device_tokens(model, tokens)
+    B, T = tok.shape
+    dev = tok.device
+    sets = [sorted({int(p) for p in ps}) for ps in position_sets]
+    if src is None:
+        if B != 1:
+            raise ValueError(f"masked_joint: tokens hold {B} sequences: say which one every position set refers to (src)")
+        src = [0] * len(sets)
+    src = [int(b) for b in (src.tolist() if torch.is_tensor(src) else src)]
+    if len(src) != len(sets):
+        raise ValueError(f"{len(src)} source sequences for {len(sets)} position sets")
+    if chunk is None:
+        chunk = max(1, CHUNK_TOKENS // T)
+    if chunk <= 0:
+        raise ValueError("chunk must be positive")
+    real = tok.ne(model.padding_idx).cpu()
+    for s, (b, ps) in enumerate(zip(src, sets)):
+        if not 0 <= b < B:
+            raise ValueError(f"position set {s}: sequence {b} is outside [0, {B})")
+        if not ps:
+            raise ValueError(f"position set {s} of sequence {b} is empty: there is nothing to score")
+        for p in ps:
+            if not 0 <= p < T:
+                raise ValueError(f"position {p} of sequence {b} is outside [0, {T})")
+            if not bool(real[b, p]):
+                raise ValueError(f"position {p} of sequence {b} is a <pad> token: there is nothing to score")
+    V = model.alphabet_size
+    counts = torch.tensor([len(ps) for ps in sets], dtype=torch.int64)
+    offsets = torch.zeros((len(sets) + 1,), dtype=torch.int64)
+    offsets[1:] = counts.cumsum(0)
+    pos = torch.tensor([p for ps in sets for p in ps], dtype=torch.int64)
+    if not sets:
+        empty = torch.empty((0, V), dtype=torch.float32, device=dev)
+        return (offsets, pos.to(dev), empty) + ((empty.clone(),) if return_logits else ())
+    # one upload for all chunks: the offsets index the whole position list, the chunks are slices of these
+    pos_d = pos.to(dev)
+    pos32, off32 = pos_d.to(torch.int32), offsets.to(device=dev, dtype=torch.int32)
+    src32 = torch.tensor(src, dtype=torch.int32).to(dev)
+    copy32 = torch.repeat_interleave(torch.arange(len(sets), dtype=torch.int32), counts).to(dev)  # the set of every row
+    lps, logits = [], []
+    for lo in range(0, len(sets), chunk):
+        hi = min(lo + chunk, len(sets))
+        masked = ops.mask_rows_multi(tok, off32[lo:hi + 1], pos32, src32[lo:hi], model.mask_idx)
+        r0, r1 = int(offsets[lo]), int(offsets[hi])
+        sel = (copy32[r0:r1] - lo) * T + pos32[r0:r1]
+        got = forward_rows(model, masked, sel, return_logits=return_logits)
+        lps.append(got[0] if return_logits else got)
+        if return_logits:
+            logits.append(got[1])
+    out = (offsets, pos_d, lps[0] if len(lps) == 1 else torch.cat(lps))
+    return out + ((logits[0] if len(logits) == 1 else torch.cat(logits),) if return_logits else ())
+
+
 def parse_mutation(mutation, offset_idx=0):
     """'A42G' -> ('A', 42 - offset_idx, 'G'): wild type, 0-based index into the sequence, mutant."""
     mutation = mutation.strip()
@@ -224,3 +297,92 @@ def score_mutations(token_logprobs, sequence, mutations, alphabet, offset_idx=0)
         row = lp[shift + idx]
         scores.append((row[alphabet.get_idx(mt)] - row[alphabet.get_idx(wt)]).item())
     return scores[0] if single else scores
+
+
+def parse_variant(variant, offset_idx=0, sep=":"):
+    """'A42G:K50R' -> [('A', 42 - offset_idx, 'G'), ('K', 50 - offset_idx, 'R')]: one ``parse_mutation`` per substitution of
+    the variant, in the order written.  A position named twice raises ValueError."""
+    parts = [parse_mutation(m, offset_idx) for m in variant.split(sep)]
+    seen = set()
+    for _, idx, _ in parts:
+        if idx in seen:
+            raise ValueError(f"variant {variant!r} names position {idx + offset_idx} twice")
+        seen.add(idx)
+    return parts
+
+
+def _checked_variant(variant, sequence, offset_idx, sep):
+    """``parse_variant`` plus the checks of ``score_mutations`` against the sequence, sorted by position."""
+    parts = parse_variant(variant, offset_idx, sep)
+    for wt, idx, _ in parts:
+        if not 0 <= idx < len(sequence):
+            raise ValueError(f"{variant}: position {idx + offset_idx} is outside the sequence (offset {offset_idx}, "
+                             f"length {len(sequence)})")
+        if sequence[idx] != wt:
+            raise ValueError(f"{variant}: the listed wild type {wt!r} does not match the sequence, which has "
+                             f"{sequence[idx]!r} at that position")
+    return sorted(parts, key=lambda part: part[1])
+
+
+@torch.no_grad()
+def score_variants(model, alphabet, sequence, variants, strategy="masked-marginals", offset_idx=0, sep=":", chunk=None):
+    """Zero-shot scores of variants with one OR MORE substitutions ('A42G', 'A42G:K50R'; positions ``offset_idx``-based,
+    joined by ``sep``) of ``sequence``: a list of Python floats, one per variant.
+
+    masked-marginals  the ESM-1v paper's score: all mutated positions of the variant masked at once, one forward, the sum over
+                      them of log p(mutant) - log p(wild type).  Variants that share a position set share one forward (the
+                      distinct sets run in order of first appearance, ``chunk`` of them per engine call).
+    wt-marginals      the same sum read from ONE table of the unmasked wild-type sequence.
+    pseudo-ppl        the pseudo-log-likelihood of every mutated sequence over the reference's positions, as
+                      ``esm_amd.predict.score_table`` does for single substitutions.
+    The marginal strategies sum on the device (``esmk_op_score_rows``): each term is the fp32 difference ``score_mutations``
+    gives a single substitution, the terms of a variant are added in fp64 in ascending order of position by one lane — a
+    single mutant's score is the float ``score_mutations`` returns, and the order in which a variant lists its substitutions
+    does not matter.  Raises ValueError where a listed wild type does not match the sequence, a position is outside it or
+    named twice, or a substitution is not of the form 'A42G'."""
+    from . import ops
+
+    _refuse_msa(model)
+    if strategy not in ("masked-marginals", "wt-marginals", "pseudo-ppl"):
+        raise ValueError(f"unknown scoring strategy {strategy!r}")
+    parsed = [_checked_variant(v, sequence, offset_idx, sep) for v in variants]
+    convert = alphabet.get_batch_converter()
+    if strategy == "pseudo-ppl":
+        mutated = []
+        for variant, parts in zip(variants, parsed):
+            residues = list(sequence)
+            for _, idx, mt in parts:
+                residues[idx] = mt
+            mutated.append((variant, "".join(residues)))
+        scores = []
+        per_call = 256  # mutants per call; their masked copies are chunked to the GPU's size inside
+        for lo in range(0, len(mutated), per_call):
+            _, _, tokens = convert(mutated[lo:lo + per_call])
+            scores += pseudo_log_likelihood(model, tokens, positions=range(1, len(sequence) - 1), chunk=chunk).tolist()
+        return scores
+    _, _, tokens = convert([("protein1", sequence)])
+    tok = _device_tokens(model, tokens)
+    if not parsed:
+        return []
+    shift = 1 if alphabet.prepend_bos else 0  # token position of residue idx: behind <cls>
+    if strategy == "masked-marginals":
+        first_row = {}  # position set -> its first row in the joint-mask table; distinct sets in order of first appearance
+        sets, n_rows = [], 0
+        for parts in parsed:
+            key = tuple(shift + idx for _, idx, _ in parts)
+            if key not in first_row:
+                first_row[key] = n_rows
+                sets.append(key)
+                n_rows += len(key)
+        _, _, table = masked_joint(model, tok, sets, chunk=chunk)
+        rows = [first_row[tuple(shift + idx for _, idx, _ in parts)] + j for parts in parsed for j in range(len(parts))]
+    else:
+        table = wt_marginals(model, tok)[0]
+        rows = [shift + idx for parts in parsed for _, idx, _ in parts]
+    dev = tok.device
+    lp = table.index_select(0, torch.tensor(rows, dtype=torch.int64).to(dev))  # one row per term, variant-major
+    wt = torch.tensor([alphabet.get_idx(w) for parts in parsed for w, _, _ in parts], dtype=torch.int32).to(dev)
+    mt = torch.tensor([alphabet.get_idx(m) for parts in parsed for _, _, m in parts], dtype=torch.int32).to(dev)
+    var_off = torch.zeros((len(parsed) + 1,), dtype=torch.int64)
+    var_off[1:] = torch.tensor([len(parts) for parts in parsed]).cumsum(0)
+    return ops.score_rows(lp, wt, mt, var_off.to(device=dev, dtype=torch.int32)).tolist()

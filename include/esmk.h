@@ -592,6 +592,23 @@ int esmk_op_mask_rows(const int64_t* tokens_dev, const int32_t* src_row_dev, con
 int esmk_op_log_softmax_rows(const float* logits_dev, float* out_dev, const int32_t* target_dev, float* target_out_dev, int n,
                              int V, void* stream);
 
+/* Multi-mutant variants (the ESM-1v paper's masked-marginal score of a variant with several substitutions: mask ALL of its
+ * positions at once, one forward, sum log p(mt) - log p(wt) over them).
+ * esmk_op_mask_rows_multi: out int64 [n,T], row i = tokens[src_row[i], :] (as esmk_op_mask_rows) with every position of
+ *   pos[pos_off[i] : pos_off[i+1]] replaced by mask_idx; pos_off int32 [n+1], pos int32 [total].  All lists are device
+ *   data: a source row outside [0,B) is clamped, the offsets are clamped to [0,total], a pair with hi < lo is an empty
+ *   list (a plain copy), a position outside [0,T) masks nothing, a repeated position is harmless.
+ * esmk_op_score_rows: out fp64 [n_var], out[v] = sum over r in [var_off[v], var_off[v+1]), r ascending, of
+ *   (logprobs[r, mt[r]] - logprobs[r, wt[r]]); logprobs fp32 [n_rows,V], wt / mt int32 [n_rows], var_off int32 [n_var+1].
+ *   Each term is the fp32 difference; the terms are added in fp64 in index order by one lane per variant (no atomics), so
+ *   the result does not depend on the launch geometry.  Columns are clamped to [0,V), offsets to [0,n_rows]; an empty
+ *   range gives 0.0.
+ * Refused before any HIP call: null pointers (src_row_dev may be NULL), B, T, n, n_rows, n_var or V <= 0, total < 0. */
+int esmk_op_mask_rows_multi(const int64_t* tokens_dev, const int32_t* src_row_dev, const int32_t* pos_off_dev,
+                            const int32_t* pos_dev, int64_t* out_dev, int B, int T, int n, int total, int mask_idx, void* stream);
+int esmk_op_score_rows(const float* logprobs_dev, const int32_t* wt_dev, const int32_t* mt_dev, const int32_t* var_off_dev,
+                       double* out_dev, int n_rows, int n_var, int V, void* stream);
+
 /* ContactPredictionHead.forward (modules.py:338-357) incl. symmetrize/apc (modules.py:27-41).
  * attn fp32 [B,C=L*H,T,T]; w fp32 [C]; b fp32 [1]; scratch fp32 >= B*C*(T+1) floats;
  * out fp32 [B,T-2,T-2] (crop follows prepend_bos/append_eos). */

@@ -5,11 +5,18 @@ batches that fill the GPU, the head of the model on the one masked row of every 
 [1, T, V] logits and keeping one row.
 
   python tools/score_throughput.py [--model 650M] [--lengths 510 1020] [--rounds 5] [--out profiles/scoring_throughput.log]
+  python tools/score_throughput.py --variants 512 [--lengths 510] --out profiles/scoring_variants.log
 
 Same library and same process for both sides; one warm-up of each side per shape, then --rounds timed rounds alternating the
 two sides, each round ending in a device synchronise; medians and the spread.  Residues/s counts the scored positions (all T
 tokens of the row).  Also recorded: the engine workspace each side grew to, the bytes of logits / log-probabilities each side
 writes over the whole protein, and the largest difference between the two tables (the loop's log_softmax is torch's).
+
+--variants N: N random double mutants of one protein ('A42G:K50R' rows of a deep mutational scan) scored with the
+masked-marginal score of the ESM-1v paper (both positions masked in one forward, log p(mt) - log p(wt) summed over them):
+``model.score_variants`` (joint masks built on the device, batches that fill the GPU, the head on the masked rows, the sums
+by ``esmk_op_score_rows``) against what a user had before it: one B = 1 ``model.forward`` per distinct position set,
+log_softmax of its logits, the two rows kept, the terms summed on the host.  Variants/s counts the scored table rows.
 """
 import argparse
 import os
@@ -36,34 +43,88 @@ def loop_rows(model, toks):
     return torch.cat(rows, dim=0)
 
 
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return time.perf_counter() - t0, out
+def random_doubles(seq, n, seed):
+    """n double mutants of ``seq`` in 1-based numbering, positions and mutant residues uniformly at random."""
+    g = torch.Generator().manual_seed(seed)
+    letters = "ACDEFGHIKLMNPQRSTVWY"
+    out = []
+    for _ in range(n):
+        i, j = sorted(torch.randperm(len(seq), generator=g)[:2].tolist())
+        parts = []
+        for idx in (i, j):
+            choice = [c for c in letters if c != seq[idx]]
+            parts.append("%s%d%s" % (seq[idx], idx + 1, choice[int(torch.randint(0, len(choice), (1,), generator=g))]))
+        out.append(":".join(parts))
+    return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="650M")
-    ap.add_argument("--lengths", type=int, nargs="+", default=[510, 1020], help="residues; T = length + 2")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("score_throughput: needs the GPU (a CPU run measures nothing)")
-    name = next(k for k in ESM2_DIMS if args.model in k)
-    L, E, H = ESM2_DIMS[name]
-    with skip_param_init():
-        model = esm.ESM2(L, E, H).eval()
-    model.load_state_dict(synth_esm2_state_dict(L, E, H, seed=0))
-    model = model.cuda()
+def loop_variant_scores(model, alphabet, toks, variants):
+    """One B = 1 forward per distinct position set (first appearance first), log_softmax of its logits, the set's rows kept;
+    fp32 terms gathered on the device, summed per variant on the host in fp64."""
+    from esm_amd.scoring import parse_variant
+
+    parsed = [sorted(parse_variant(v, 1), key=lambda part: part[1]) for v in variants]
+    first_row, rows, n_rows = {}, [], 0
+    for parts in parsed:
+        key = tuple(1 + idx for _, idx, _ in parts)
+        if key in first_row:
+            continue
+        first_row[key] = n_rows
+        n_rows += len(key)
+        masked = toks.clone()
+        masked[0, list(key)] = model.mask_idx
+        rows.append(torch.log_softmax(model(masked)["logits"], dim=-1)[0, list(key)])
+    table = torch.cat(rows, dim=0)
+    idx = torch.tensor([first_row[tuple(1 + i for _, i, _ in parts)] + j for parts in parsed for j in range(len(parts))])
+    wt = torch.tensor([alphabet.get_idx(w) for parts in parsed for w, _, _ in parts])
+    mt = torch.tensor([alphabet.get_idx(m) for parts in parsed for _, _, m in parts])
+    sub = table[idx.to(table.device)]
+    terms = (sub.gather(1, mt.to(table.device).unsqueeze(1)) - sub.gather(1, wt.to(table.device).unsqueeze(1))).view(-1).tolist()
+    scores, at = [], 0
+    for parts in parsed:
+        scores.append(sum(terms[at:at + len(parts)], 0.0))
+        at += len(parts)
+    return scores
+
+
+def variants_mode(args, model):
+    """--variants N: the lines of the report, one block per length."""
+    from esm_amd.scoring import CHUNK_TOKENS, parse_variant
+
+    alphabet = esm.Alphabet.from_architecture("ESM-1b")
+    lines = []
     with torch.no_grad():
-        model(synth_tokens(1, 30).cuda())  # the engine exists from here on: its LayerNorm-fold mode can be read
-    lines = ["%s (L %d, E %d, H %d) on %s; LayerNorm fold %s; %d rounds after one warm-up, medians [min .. max]" % (
-        name, L, E, H, torch.cuda.get_device_name(0), "on" if model.ln_fold_active() else "off", args.rounds)]
+        for n_res in args.lengths:
+            toks = synth_tokens(1, n_res, seed=n_res)
+            seq = "".join(alphabet.get_tok(int(t)) for t in toks[0, 1:-1])
+            toks = toks.cuda()
+            T = toks.shape[1]
+            variants = random_doubles(seq, args.variants, seed=n_res)
+            sides = {"loop": lambda: loop_variant_scores(model, alphabet, toks, variants),
+                     "score_variants": lambda: model.score_variants(alphabet, seq, variants, offset_idx=1)}
+            n_sets = len({tuple(sorted(idx for _, idx, _ in parse_variant(v, 1))) for v in variants})
+            ref = {side: fn() for side, fn in sides.items()}  # warm-up of both sides; their scores
+            diff = max(abs(a - b) for a, b in zip(ref["loop"], ref["score_variants"]))
+            times = {side: [] for side in sides}
+            for _ in range(args.rounds):
+                for side, fn in sides.items():
+                    times[side].append(timed(fn)[0])
+            med = {side: statistics.median(t) for side, t in times.items()}
+            lines.append("T = %d (%d residues), %d random double mutants, %d distinct position sets, chunk %d copies per forward" % (
+                T, n_res, len(variants), n_sets, max(1, CHUNK_TOKENS // T)))
+            for side in sides:
+                lines.append("  %-15s %8.1f ms [%.1f .. %.1f]  %8.0f variants/s  %8.2f ms per distinct set" % (
+                    side, 1e3 * med[side], 1e3 * min(times[side]), 1e3 * max(times[side]), len(variants) / med[side],
+                    1e3 * med[side] / n_sets))
+            lines.append("  ratio loop / score_variants: %.2f x; max |difference| of the two score columns %.3e" % (
+                med["loop"] / med["score_variants"], diff))
+    return lines
+
+
+def masks_mode(args, model):
+    """The default mode: ``model.masked_marginals`` against the loop; the lines of the report, one block per length."""
     V = model.alphabet_size
+    lines = []
     with torch.no_grad():
         for n_res in args.lengths:
             toks = synth_tokens(1, n_res, seed=n_res).cuda()
@@ -91,6 +152,43 @@ def main():
                     out_bytes[side] / 2 ** 20))
             lines.append("  ratio loop / masked_marginals: %.2f x; max |difference| of the two tables %.3e" % (
                 med["loop"] / med["masked_marginals"], diff))
+    return lines
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="650M")
+    ap.add_argument("--lengths", type=int, nargs="+", default=None,
+                    help="residues; T = length + 2 (default 510 1020; with --variants 510)")
+    ap.add_argument("--variants", type=int, default=0, metavar="N",
+                    help="score N random double mutants of one protein: model.score_variants against one B = 1 forward per "
+                         "distinct position set")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.lengths is None:
+        args.lengths = [510] if args.variants else [510, 1020]
+    if not torch.cuda.is_available():
+        raise SystemExit("score_throughput: needs the GPU (a CPU run measures nothing)")
+    name = next(k for k in ESM2_DIMS if args.model in k)
+    L, E, H = ESM2_DIMS[name]
+    with skip_param_init():
+        model = esm.ESM2(L, E, H).eval()
+    model.load_state_dict(synth_esm2_state_dict(L, E, H, seed=0))
+    model = model.cuda()
+    with torch.no_grad():
+        model(synth_tokens(1, 30).cuda())  # the engine exists from here on: its LayerNorm-fold mode can be read
+    lines = ["%s (L %d, E %d, H %d) on %s; LayerNorm fold %s; %d rounds after one warm-up, medians [min .. max]" % (
+        name, L, E, H, torch.cuda.get_device_name(0), "on" if model.ln_fold_active() else "off", args.rounds)]
+    lines += variants_mode(args, model) if args.variants else masks_mode(args, model)
     text = "\n".join(lines)
     print(text)
     if args.out:
