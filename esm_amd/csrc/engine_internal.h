@@ -1,5 +1,6 @@
-// engine_internal.h — state shared by the host-side translation units of libesmk.so (engine.hip: ESM-2 /
-// ESM-1b path and the generic C ABI; engine_msa.hip: MSA Transformer path).  Not part of the public ABI.
+// engine_internal.h — state and launch helpers shared by the host-side translation units of libesmk.so (engine.hip: ESM-2 /
+// ESM-1b / ESM-1 path and the generic C ABI; engine_msa.hip: MSA Transformer path; engine_ops.hip: single-kernel and debug
+// entries).  Not part of the public ABI.
 #pragma once
 #include "../../include/esmk.h"
 #include "kernels.h"
@@ -173,8 +174,96 @@ enum FoldBits : uint32_t {
 };
 
 namespace esmk_host {
+constexpr float kLog2e = 1.4426950408889634f;
+// head width inside the engine: 128, or 64 slots (heads with head_dim < 64 are spread over them)
+inline int head_slots(const esmk_model* m) { return m->D == 128 ? 128 : 64; }
+
+// rotary tables for rows 0 .. T-1 (engine.hip)
+int ensure_rope(esmk_model* m, int T, hipStream_t st);
 // "unit" rotary tables (cos = 1, sin = 0) for models without RoPE (MSA Transformer, ESM-1b)
 int ensure_unit_rope(esmk_model* m, int T, hipStream_t st);
 // packed image layout of the MSA Transformer (engine_msa.hip)
 void plan_packed_msa(esmk_model* m);
+
+// ---- host launch helpers of both engines (engine.hip): one launch with its profiler record ------------------
+struct Stack {
+    esmk_model* m;
+    hipStream_t st;
+    int op;          // operand dtype
+    size_t os;       // and its size
+    const char* pk;  // packed parameter image
+    int N;           // rows of the residual stream
+    // requested representations (esmk_forward / esmk_msa_forward arguments)
+    const int32_t* repr_layers;
+    int n_repr;
+    void* const* repr_out;
+
+    void* repr_of(int layer) const {  // the first buffer that takes `layer`, or null
+        for (int i = 0; i < n_repr; ++i)
+            if (repr_layers[i] == layer) return repr_out[i];
+        return nullptr;
+    }
+    // algorithmic work of one (batched) GEMM launch: operands read once, result written once (residual: read + written)
+    int gemm(int cls, const esmk::GemmArgs& a, int epi, double out_bytes_per_elem) const;
+    // a GEMM against a weight matrix of the layer stack: with split weights (f16x2) the same kernel runs over
+    // the [N, 2K] hi | lo image, the activations' K tile kt / 2 meeting W_hi (kt even) and W_lo (kt odd); FLOP / byte
+    // accounting stays algorithmic
+    int weight_gemm(int cls, esmk::GemmArgs a, int epi, double out_bytes_per_elem) const;
+    int lnorm(const float* in, size_t gamma_off, size_t beta_off, void* y, float* y32, int rows, const esmk::LnExtra& ex) const;
+    // copies of the stream for every request of `layer`: fp32, or (lowp) the operand dtype
+    int repr_copy(int layer, const float* src, bool lowp = false) const;
+};
+// Final LayerNorm (esm2.py:123-128: representation L is the normalised stream, fp32) and the LM head (modules.py:308-314) on
+// `rows` rows of x; h, g32: operand-dtype and fp32 scratch rows.  With split weights the head runs in fp32 on the exact-fp32
+// MFMA path.  repr_lowp: representations leave in the operand dtype — the caller has then run the final LayerNorm itself
+// if layer L was requested.
+int lm_head(const Stack& s, int rows, float* x, void* h, float* g32, int Kp, const esmk::LnExtra& ex, bool repr_lowp,
+            bool want_logits, void* logits_out);
+
+// The q / k (EPI_QKV_ROPE) and v (EPI_V_T) projections of one attention block: what differs between their callers
+struct QkvProj {
+    const void* A = nullptr;  // operand rows, K columns each (3 Kp in the f16x3 mode)
+    int K = 0;
+    const void* W = nullptr;  // q | k | v weight rows; the v rows start behind 2 EA rows of `split` * Kp elements
+    int split = 1;
+    const float *bias = nullptr, *bias2 = nullptr, *ln_rstd = nullptr;
+    void *q = nullptr, *k = nullptr, *vt = nullptr;
+    const float *cos = nullptr, *sin = nullptr;
+    int rows = 0, T = 0, Tp = 0;
+    float scaling = 1.f;
+    const int* row_pos = nullptr;      // token-packed batches
+    const float* row_keep = nullptr;   // MSA row attention
+    int vt_rows = 0;
+};
+void qkv_gemm_args(const esmk_model* m, const QkvProj& p, esmk::GemmArgs* qk, esmk::GemmArgs* v);
+
+// ---- token-packed row spaces: the segment table and the int32 tables behind the workspace -------------------
+// The segment table of a packed row space, shared by the engine entries and the single-kernel entries: the layout rules,
+// and the tables every packed attention launch reads.  lead_gap: the first segment may start behind row 0 (op entries).
+struct SegTableInfo {
+    int max_len = 0;
+    size_t items = 0;                // 128-query blocks = entries of the attention work list
+    unsigned long long sum_len2 = 0;
+};
+int check_seg_table(const std::string& w, const int32_t* seg, int n_seg, int rows, bool lead_gap, SegTableInfo* info);
+// dst: [seg 2 n][npad n (zero: filled on the device)][work 4 items] — query blocks of 128 rows, longest segments first
+void fill_attn_tables(const int32_t* seg, int n_seg, int32_t* dst);
+// dst: uint64 [n_seg] (as int32 pairs, 8-byte aligned): map offset of segment s = sum of len^2 of the segments in front
+void fill_map_offsets(const int32_t* seg, int n_seg, int32_t* dst);
+// The one layout of that table, in int32 slots: [seg 2n][npad n][work 4 items][pad][contact tables (kernels.h,
+// CtPackedPlan)][pad][map offsets uint64 n] — the contact tables and the map offsets 8-byte aligned, each only if asked for
+struct PackedTables {
+    size_t npad, work, ct_base, map_base, ints;
+};
+inline PackedTables packed_tables(int n_seg, size_t items, size_t ct_table_ints, bool maps) {
+    PackedTables t;
+    t.npad = (size_t)2 * n_seg;
+    t.work = (size_t)3 * n_seg;
+    const size_t lists = t.work + 4 * items;
+    t.ct_base = (lists + 1) & ~(size_t)1;
+    const size_t end = ct_table_ints ? t.ct_base + ct_table_ints : lists;
+    t.map_base = (end + 1) & ~(size_t)1;
+    t.ints = maps ? t.map_base + 2 * (size_t)n_seg : end;
+    return t;
+}
 }  // namespace esmk_host

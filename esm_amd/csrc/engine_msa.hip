@@ -224,42 +224,7 @@ int esmk_msa_forward(esmk_model* m, const void* packed_dev, const int64_t* token
     if (ensure_unit_rope(m, std::max(R, C), st)) return 1;
 
     const double NE = (double)N * E;
-    auto repr_copy = [&](int layer, const float* src) -> int {
-        for (int i = 0; i < n_repr; ++i)
-            if (repr_layers[i] == layer) {
-                ProfScope ps(m, st, PC_COPY, 0, 8 * NE);
-                ESMK_TRY(launch_copy_f32(src, (float*)repr_out_dev[i], (size_t)N * E, st));
-            }
-        return 0;
-    };
-    // algorithmic work of one (batched) GEMM launch: operands read once, result written once
-    auto gemm = [&](int cls, const GemmArgs& a, int epi, double out_bytes_per_elem) -> int {
-        const double z = a.batch > 0 ? a.batch : 1;
-        const double fl = 2.0 * z * a.M * (double)(a.n_valid ? a.n_valid : a.N) * a.K;
-        const double by = z * (((double)a.M * a.K + (double)a.N * a.K) * os + (double)a.M * a.N * out_bytes_per_elem);
-        ProfScope ps(m, st, cls, fl, by);
-        ESMK_TRY(launch_gemm(a, epi, op, st));
-        return 0;
-    };
-    // a GEMM against a weight matrix of the layer stack: with split weights (f16x2) the same kernel runs over
-    // the [N, 2K] hi | lo image, the activations' K tile kt / 2 meeting W_hi (kt even) and W_lo (kt odd)
-    const int wsf = split_plan(m).qk;            // q / k weights: the v rows of the image start behind 2 E rows of this length
-    auto wgemm = [&](int cls, GemmArgs a, int epi, double out_bytes_per_elem) -> int {
-        if (split_factor(m, cls, epi) == 1) return gemm(cls, a, epi, out_bytes_per_elem);
-        const double fl = 2.0 * a.M * (double)a.N * a.K;
-        const double by = ((double)a.M * a.K + 2.0 * a.N * a.K) * os + (double)a.M * a.N * out_bytes_per_elem;
-        a.a_row_bytes = (long long)a.K * (long long)os;
-        a.a_kt_repeat = 1;
-        a.K *= 2;
-        ProfScope ps(m, st, cls, fl, by);
-        ESMK_TRY(launch_gemm(a, epi, op, st));
-        return 0;
-    };
-    auto lnorm = [&](const float* in, size_t go, size_t bo, void* y, float* y32, LnExtra ex) -> int {
-        ProfScope ps(m, st, PC_LAYERNORM, 8 * NE, NE * (4 + (y ? os : 0) + (y32 ? 4 : 0)));
-        ESMK_TRY(launch_layernorm_ex(in, (const float*)(pk + go), (const float*)(pk + bo), y, y32, N, E, op, ex, st));
-        return 0;
-    };
+    const Stack s{m, st, op, os, pk, N, repr_layers, n_repr, repr_out_dev};
 
     // msa_transformer.py:152-172: token + position + MSA-row embeddings, LayerNorm, pads zeroed
     {
@@ -271,38 +236,29 @@ int esmk_msa_forward(esmk_model* m, const void* packed_dev, const int64_t* token
     {
         LnExtra ex;
         ex.row_keep = keep;
-        if (lnorm(x, m->lnb_g, m->lnb_b, nullptr, x, ex)) return 1;
+        if (s.lnorm(x, m->lnb_g, m->lnb_b, nullptr, x, N, ex)) return 1;
     }
-    if (repr_copy(0, x)) return 1;
+    if (s.repr_copy(0, x)) return 1;
 
     // q/k/v projections of one axial attention block on `rows` = N rows grouped in sequences of T tokens
     auto qkv = [&](const AttnOff& a, int T, int Tp, float scaling, const float* row_keep, int vt_rows) -> int {
-        GemmArgs g;
-        g.A = h;
-        g.W = pk + a.wqkv;
-        g.bias = (const float*)(pk + a.bqkv);
-        g.M = N;
-        g.N = 2 * E;
-        g.K = E;
-        g.q = q;
-        g.k = k;
-        g.vt = vt;
-        g.cos = m->d_ucos;
-        g.sin = m->d_usin;
-        g.T = T;
-        g.H = H;
-        g.E = E;
-        g.Tp = Tp;
-        g.scaling = scaling;
-        g.row_keep = row_keep;
-        GemmArgs gv = g;
-        gv.row_keep = nullptr;
-        gv.W = pk + a.wqkv + (size_t)2 * E * E * os * wsf;
-        gv.bias = (const float*)(pk + a.bqkv) + 2 * E;
-        gv.N = E;
-        gv.vt_rows = vt_rows;
-        if (wgemm(PC_GEMM_QKV, g, EPI_QKV_ROPE, os)) return 1;
-        return wgemm(PC_GEMM_QKV, gv, EPI_V_T, os);
+        QkvProj p;
+        p.A = h;
+        p.K = E;
+        p.W = pk + a.wqkv;
+        p.split = split_plan(m).qk;
+        p.bias = (const float*)(pk + a.bqkv);
+        p.q = q, p.k = k, p.vt = vt;
+        p.cos = m->d_ucos;
+        p.sin = m->d_usin;
+        p.rows = N, p.T = T, p.Tp = Tp;
+        p.scaling = scaling;
+        p.row_keep = row_keep;
+        p.vt_rows = vt_rows;
+        GemmArgs g, gv;
+        qkv_gemm_args(m, p, &g, &gv);
+        if (s.weight_gemm(PC_GEMM_QKV, g, EPI_QKV_ROPE, os)) return 1;
+        return s.weight_gemm(PC_GEMM_QKV, gv, EPI_V_T, os);
     };
     auto out_proj = [&](const AttnOff& a, int map_R, int map_C) -> int {
         GemmArgs g;
@@ -315,13 +271,13 @@ int esmk_msa_forward(esmk_model* m, const void* packed_dev, const int64_t* token
         g.K = E;
         g.rowmap_R = map_R;
         g.rowmap_C = map_C;
-        return wgemm(PC_GEMM_OUT, g, EPI_RESID_F32, 8);
+        return s.weight_gemm(PC_GEMM_OUT, g, EPI_RESID_F32, 8);
     };
 
     for (int l = 0; l < L; ++l) {
         const MsaLayerOff& o = m->mlayer[l];
         // ---- tied row attention (axial_attention.py:75-130; NormalizedResidualBlock modules.py:376-392) ----
-        if (lnorm(x, o.row.lng, o.row.lnb, h, nullptr, LnExtra())) return 1;
+        if (s.lnorm(x, o.row.lng, o.row.lnb, h, nullptr, N, LnExtra())) return 1;
         if (Cp != C) ESMK_TRY(hipMemsetAsync(vt, 0, (size_t)B * H * R * 64 * Cp * os, st));
         // sequences = MSA rows (b,r) of C tokens; q scaled by d^-1/2 / sqrt(R) (axial_attention.py:36-38)
         if (qkv(o.row, C, Cp, (1.0f / sqrtf(64.0f)) / sqrtf((float)R), keep, R)) return 1;
@@ -346,7 +302,7 @@ int esmk_msa_forward(esmk_model* m, const void* packed_dev, const int64_t* token
             g.a_bi = g.w_bi = (long long)C * 64 * os;
             g.o_bo = (long long)H * C * Cp * 4;
             g.o_bi = (long long)C * Cp * 4;
-            if (gemm(PC_MSA_ROW_SCORES, g, EPI_STORE_F32, 4)) return 1;
+            if (s.gemm(PC_MSA_ROW_SCORES, g, EPI_STORE_F32, 4)) return 1;
         }
         {
             const double sc = (double)B * H * C * C;
@@ -373,7 +329,7 @@ int esmk_msa_forward(esmk_model* m, const void* packed_dev, const int64_t* token
             g.w_bi = (long long)R * 64 * Cp * os;
             g.ctx_R = R;
             g.ctx_C = C;
-            if (gemm(PC_MSA_ROW_CTX, g, EPI_MSA_CTX, os)) return 1;
+            if (s.gemm(PC_MSA_ROW_CTX, g, EPI_MSA_CTX, os)) return 1;
         }
         if (out_proj(o.row, 0, 0)) return 1;
 
@@ -383,11 +339,11 @@ int esmk_msa_forward(esmk_model* m, const void* packed_dev, const int64_t* token
             LnExtra ex;
             ex.map_R = R;
             ex.map_C = C;
-            if (lnorm(x, o.col.lng, o.col.lnb, h, nullptr, ex)) return 1;
+            if (s.lnorm(x, o.col.lng, o.col.lnb, h, nullptr, N, ex)) return 1;
         }
         if (Rp != R) ESMK_TRY(hipMemsetAsync(vt, 0, (size_t)B * C * H * 64 * Rp * os, st));
         // log2(e) folded into the q scale: the flash / map kernels work on log2-domain scores (attention.hip)
-        if (qkv(o.col, R, Rp, 1.4426950408889634f / sqrtf(64.0f), nullptr, 0)) return 1;
+        if (qkv(o.col, R, Rp, kLog2e / sqrtf(64.0f), nullptr, 0)) return 1;
         float* lse = want_col ? (float*)(ws + w.lse) : nullptr;
         {
             ProfScope ps(m, st, PC_MSA_COL_ATTN, 4.0 * N * (double)R * E, 4 * NE * os);
@@ -401,7 +357,7 @@ int esmk_msa_forward(esmk_model* m, const void* packed_dev, const int64_t* token
         if (out_proj(o.col, R, C)) return 1;
 
         // ---- feed forward (modules.py:395-418) ----
-        if (lnorm(x, o.flng, o.flnb, h, nullptr, LnExtra())) return 1;
+        if (s.lnorm(x, o.flng, o.flnb, h, nullptr, N, LnExtra())) return 1;
         {
             GemmArgs g;
             g.A = h;
@@ -411,7 +367,7 @@ int esmk_msa_forward(esmk_model* m, const void* packed_dev, const int64_t* token
             g.M = N;
             g.N = F;
             g.K = E;
-            if (wgemm(PC_GEMM_FC1, g, EPI_GELU_T, os)) return 1;
+            if (s.weight_gemm(PC_GEMM_FC1, g, EPI_GELU_T, os)) return 1;
             g = GemmArgs();
             g.A = ffn;
             g.W = pk + o.w2;
@@ -420,60 +376,13 @@ int esmk_msa_forward(esmk_model* m, const void* packed_dev, const int64_t* token
             g.M = N;
             g.N = E;
             g.K = F;
-            if (wgemm(PC_GEMM_FC2, g, EPI_RESID_F32, 8)) return 1;
+            if (s.weight_gemm(PC_GEMM_FC2, g, EPI_RESID_F32, 8)) return 1;
         }
-        if (l + 1 < L && repr_copy(l + 1, x)) return 1;  // msa_transformer.py:197-198
+        if (l + 1 < L && s.repr_copy(l + 1, x)) return 1;  // msa_transformer.py:197-198
     }
 
     // msa_transformer.py:200-206: final LayerNorm (representation L is the normalised stream), LM head
-    float* rep_last = nullptr;
-    bool wants_last = false;
-    for (int i = 0; i < n_repr; ++i)
-        if (repr_layers[i] == L) {
-            wants_last = true;
-            if (!rep_last) rep_last = (float*)repr_out_dev[i];
-        }
-    if (want_logits || wants_last) {
-        if (lnorm(x, m->fin_g, m->fin_b, want_logits ? h : nullptr, rep_last, LnExtra())) return 1;
-        for (int i = 0; i < n_repr; ++i)
-            if (repr_layers[i] == L && repr_out_dev[i] != rep_last)
-                ESMK_TRY(launch_copy_f32(rep_last, (float*)repr_out_dev[i], (size_t)N * E, st));
-    }
-    if (want_logits && m->cfg.weight_split && E % 32 == 0) {
-        // f16x2: the head (modules.py:308-314) in fp32 on the exact-fp32 MFMA path, as in esmk_forward
-        float* a32 = rep_last != nullptr ? rep_last : g32;
-        if (a32 == g32 && lnorm(x, m->fin_g, m->fin_b, nullptr, g32, LnExtra())) return 1;
-        {
-            ProfScope ps(m, st, PC_LM_DENSE, 2.0 * N * (double)E * E, (2.0 * NE + (double)E * E) * 4);
-            ESMK_TRY(launch_gemm32(a32, E, (const float*)(pk + m->lm_w32), (const float*)(pk + m->lm_b), x, E, N, E, E, true, st));
-        }
-        if (lnorm(x, m->lm_lng, m->lm_lnb, nullptr, g32, LnExtra())) return 1;  // x (the residual stream) is dead: dense output
-        {
-            ProfScope ps(m, st, PC_LM_LOGITS, 2.0 * N * (double)E * m->V, (NE + (double)m->V * E + (double)N * m->V) * 4);
-            ESMK_TRY(launch_gemm32(g32, E, (const float*)(pk + m->embed_f32), (const float*)(pk + m->lm_bias),
-                                   (float*)logits_out_dev, m->V, N, m->V, E, false, st));
-        }
-    } else if (want_logits) {  // modules.py:308-314
-        GemmArgs g;
-        g.A = h;
-        g.W = pk + m->lm_w;
-        g.bias = (const float*)(pk + m->lm_b);
-        g.out = g32;
-        g.M = N;
-        g.N = E;
-        g.K = E;
-        if (gemm(PC_LM_DENSE, g, EPI_GELU_F32, 4)) return 1;
-        if (lnorm(g32, m->lm_lng, m->lm_lnb, h, nullptr, LnExtra())) return 1;
-        g = GemmArgs();
-        g.A = h;
-        g.W = pk + m->embed_op;
-        g.bias = (const float*)(pk + m->lm_bias);
-        g.out = logits_out_dev;
-        g.M = N;
-        g.N = m->V;
-        g.K = E;
-        if (gemm(PC_LM_LOGITS, g, EPI_STORE_F32, 4)) return 1;
-    }
+    if (lm_head(s, N, x, h, g32, E, LnExtra(), false, want_logits, logits_out_dev)) return 1;
     if (want_contacts) {  // msa_transformer.py:215-217 -> modules.py:338-357 on the row attentions
         // the contact head reads tokens only for the <eos> mask, which the MSA alphabet does not append
         ProfScope ps(m, st, PC_CONTACTS, 0, 2.0 * 4 * B * (double)L * H * C * C);

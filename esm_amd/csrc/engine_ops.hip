@@ -1,0 +1,872 @@
+// engine_ops.hip — the single-kernel and debug entry points of libesmk.so (declared in include/esmk.h): validation,
+// then the launchers the engines use themselves.  Tests and tools call these; esmk_forward / esmk_msa_forward do not.
+#include "engine_internal.h"
+
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+using namespace esmk;
+using namespace esmk_host;
+
+extern "C" {
+
+// ---------------------------------------------------------------------------------------------
+// single-kernel entry points
+// ---------------------------------------------------------------------------------------------
+int esmk_op_layernorm(const float* x_dev, const float* gamma_dev, const float* beta_dev,
+                      void* y_dev, float* y32_dev, int rows, int E, int operand_dtype,
+                      void* stream) {
+    ESMK_TRY(launch_layernorm(x_dev, gamma_dev, beta_dev, y_dev, y32_dev, rows, E, operand_dtype,
+                              (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_masked_row_mean(const void* x_dev, int x_dtype, const int32_t* count_dev, float* out_dev, int B, int T,
+                            int E, int first_row, void* stream) {
+    if (!x_dev || !count_dev || !out_dev) return fail("esmk_op_masked_row_mean: null argument");
+    if (B <= 0 || T <= 0 || E <= 0 || E % 4 != 0 || first_row < 0 || first_row > T)
+        return fail("esmk_op_masked_row_mean: need B, T > 0, E a positive multiple of 4, 0 <= first_row <= T");
+    if (x_dtype != ESMK_DT_F32 && x_dtype != ESMK_DT_F16 && x_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_masked_row_mean: x_dtype must be ESMK_F32, ESMK_F16 or ESMK_BF16");
+    ESMK_TRY(launch_masked_row_mean(x_dev, x_dtype, count_dev, out_dev, B, T, E, first_row, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_linear(const void* a_dev, const void* w_dev, const float* bias_dev, void* out_dev,
+                   int M, int N, int K, int epilogue, int operand_dtype, void* stream) {
+    if (epilogue < 0 || epilogue > 4) return fail("esmk_op_linear: bad epilogue");
+    GemmArgs g;
+    g.A = a_dev;
+    g.W = w_dev;
+    g.bias = bias_dev;
+    g.out = out_dev;
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    if (operand_dtype & 0x100) g.force_generic = 1;  // test hook: force the generic 64x64 kernel
+    if (operand_dtype & 0x200) g.force_old = 1;      // test hook: one-tile-per-workgroup 256x256 kernel
+    g.panel_c = (operand_dtype >> 20) & 0x3f;         // tile-order experiments (tools/microbench.py)
+    g.half_m = ((operand_dtype >> 28) & 3) == 1 ? 1 : (((operand_dtype >> 28) & 3) == 2 ? -1 : 0);  // 128-row tiles: force / never
+    g.dbg = (operand_dtype >> 12) & 0xff;             // timing experiments (tools/microbench.py)
+    operand_dtype &= 0xff;
+    ESMK_TRY(launch_gemm(g, epilogue, operand_dtype, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_split_weight(const void* w_dev, int w_dtype, void* w2_dev, int N, int K, void* stream) {
+    if (!w_dev || !w2_dev) return fail("esmk_op_split_weight: null argument");
+    if (N <= 0 || K <= 0 || K % 64 != 0) return fail("esmk_op_split_weight: need N > 0 and K a positive multiple of 64");
+    ESMK_TRY(launch_convert2d_split(w_dev, w_dtype, w2_dev, (size_t)N, (size_t)K, (size_t)K, 0, 0, 64, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_linear_split(const void* a_dev, const void* w2_dev, const float* bias_dev, void* out_dev, int M, int N, int K,
+                         int epilogue, void* stream) {
+    if (epilogue < 0 || epilogue > 4 || epilogue == EPI_GELU_F32) return fail("esmk_op_linear_split: epilogue must be 0, 1, 2 or 4");
+    if (K % 64 != 0 || N % 8 != 0) return fail("esmk_op_linear_split: need K % 64 == 0 and N % 8 == 0");
+    GemmArgs g;
+    g.A = a_dev;
+    g.W = w2_dev;
+    g.bias = bias_dev;
+    g.out = out_dev;
+    g.M = M;
+    g.N = N;
+    g.K = 2 * K;
+    g.a_row_bytes = (long long)K * 2;
+    g.a_kt_repeat = 1;
+    ESMK_TRY(launch_gemm(g, epilogue, ESMK_DT_F16, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- the kernels of the precision modes as single ops (tests/test_precision_ops_gpu.py) ---------------------------
+int esmk_op_linear_f32(const float* a_dev, int lda, const float* w_dev, const float* bias_dev, float* out_dev, int ldc, int M,
+                       int N, int K, int gelu, void* stream) {
+    if (!a_dev || !w_dev || !out_dev) return fail("esmk_op_linear_f32: null argument");
+    if (M <= 0 || N <= 0 || K <= 0) return fail("esmk_op_linear_f32: M, N and K must be positive");
+    if (K % 32 != 0) return fail("esmk_op_linear_f32: need K % 32 == 0");
+    if (lda % 4 != 0 || lda < K) return fail("esmk_op_linear_f32: need lda % 4 == 0 and lda >= K");
+    if (ldc < N) return fail("esmk_op_linear_f32: need ldc >= N");
+    ESMK_TRY(launch_gemm32(a_dev, lda, w_dev, bias_dev, out_dev, ldc, M, N, K, gelu != 0, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_layernorm_ex(const float* x_dev, const float* gamma_dev, const float* beta_dev, void* y_dev, float* y32_dev,
+                         int rows, int E, int operand_dtype, const float* row_keep_dev, int map_R, int map_C, int ldy, int x3,
+                         float eps, void* stream) {
+    if (!x_dev || !gamma_dev || !beta_dev || (!y_dev && !y32_dev)) return fail("esmk_op_layernorm_ex: null argument");
+    if (rows <= 0 || E <= 0) return fail("esmk_op_layernorm_ex: rows and E must be positive");
+    if (E % 4 != 0 || E > 5120) return fail("esmk_op_layernorm_ex: need E % 4 == 0 and E <= 5120");
+    const int dt = operand_dtype & 0xff;
+    if (dt != ESMK_DT_F16 && dt != ESMK_DT_BF16) return fail("esmk_op_layernorm_ex: operand_dtype must be ESMK_F16 or ESMK_BF16");
+    if (ldy < 0 || (ldy > 0 && ldy < E) || ldy % 4 != 0) return fail("esmk_op_layernorm_ex: ldy must be 0 or a multiple of 4 >= E");
+    if (x3 && (E % 64 != 0 || ldy < 3 * E || !y_dev || dt != ESMK_DT_F16))
+        return fail("esmk_op_layernorm_ex: x3 needs E % 64 == 0, ldy >= 3 E, y and fp16");
+    if (map_R < 0 || (map_R > 0 && (map_C <= 0 || rows % ((long long)map_R * map_C) != 0)))
+        return fail("esmk_op_layernorm_ex: the row map needs map_C > 0 and rows % (map_R map_C) == 0");
+    if (!(eps > 0.f)) return fail("esmk_op_layernorm_ex: eps must be positive");
+    LnExtra ex;
+    ex.row_keep = row_keep_dev;
+    ex.map_R = map_R;
+    ex.map_C = map_R > 0 ? map_C : 0;
+    ex.ldy = ldy;
+    ex.x3 = x3 != 0;
+    ex.eps = eps;
+    ESMK_TRY(launch_layernorm_ex(x_dev, gamma_dev, beta_dev, y_dev, y32_dev, rows, E, operand_dtype, ex, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_split_weight_ex(const void* w_dev, int w_dtype, void* dst_dev, int dst_dtype, int rows, int cols, int dst_ld,
+                            int parts, int row_map, int col_map, int head_dim, void* stream) {
+    auto is_dt = [](int d) { return d == ESMK_DT_F32 || d == ESMK_DT_F16 || d == ESMK_DT_BF16; };
+    if (!w_dev || !dst_dev) return fail("esmk_op_split_weight_ex: null argument");
+    if (rows <= 0 || cols <= 0) return fail("esmk_op_split_weight_ex: rows and cols must be positive");
+    if (parts < 1 || parts > 3) return fail("esmk_op_split_weight_ex: parts must be 1, 2 or 3");
+    if (!is_dt(w_dtype) || !is_dt(dst_dtype)) return fail("esmk_op_split_weight_ex: dtypes must be ESMK_F32, ESMK_F16 or ESMK_BF16");
+    if (parts >= 2 && dst_dtype != ESMK_DT_F16) return fail("esmk_op_split_weight_ex: parts 2 and 3 write fp16 (dst_dtype ESMK_F16)");
+    if ((row_map != 0 && row_map != 1) || (col_map != 0 && col_map != 1))
+        return fail("esmk_op_split_weight_ex: row_map and col_map must be 0 or 1");
+    int d = 64;  // identity maps: unused
+    if (row_map || col_map) {
+        d = head_dim;
+        if (!((d >= 1 && d <= 64) || d == 128)) return fail("esmk_op_split_weight_ex: head_dim must be 1..64 or 128");
+        if ((row_map && rows % d != 0) || (col_map && cols % d != 0))
+            return fail("esmk_op_split_weight_ex: head_dim must divide the mapped extent");
+    }
+    const long long col_extent = !col_map ? cols : d == 128 ? cols : (long long)(cols / d) * 64;
+    if (dst_ld < col_extent) return fail("esmk_op_split_weight_ex: dst_ld is smaller than the (mapped) column extent");
+    if (parts >= 2 && dst_ld % 64 != 0) return fail("esmk_op_split_weight_ex: parts 2 and 3 need dst_ld % 64 == 0");
+    if (parts == 1)
+        ESMK_TRY(launch_convert2d(w_dev, w_dtype, dst_dev, dst_dtype, (size_t)rows, (size_t)cols, (size_t)dst_ld, row_map, col_map,
+                                  d, (hipStream_t)stream));
+    else
+        ESMK_TRY(launch_convert2d_split(w_dev, w_dtype, dst_dev, (size_t)rows, (size_t)cols, (size_t)dst_ld, row_map, col_map, d,
+                                        (hipStream_t)stream, parts));
+    return 0;
+}
+
+int esmk_op_linear_gelu_x3(const void* a3_dev, const void* w3_dev, const float* bias_dev, void* out3_dev, int M, int N, int K3,
+                           void* stream) {
+    if (!a3_dev || !w3_dev || !bias_dev || !out3_dev) return fail("esmk_op_linear_gelu_x3: null argument");
+    if (M <= 0 || N <= 0 || K3 <= 0) return fail("esmk_op_linear_gelu_x3: M, N and K3 must be positive");
+    if (K3 % 192 != 0) return fail("esmk_op_linear_gelu_x3: need K3 % 192 == 0 (hi | hi | lo per 64-column K tile)");
+    GemmArgs g;
+    g.A = a3_dev;
+    g.W = w3_dev;
+    g.bias = bias_dev;
+    g.out = out3_dev;
+    g.M = M;
+    g.N = N;
+    g.K = K3;
+    g.x3_out = 1;
+    // the kernel's own contract (gemm9_supports): a 64-column block is stored as hi | hi | lo, 192 columns of a 3 N row
+    if (N % 64 != 0 || gemm_plan(g, EPI_GELU_T).kernel != 9)
+        return fail("esmk_op_linear_gelu_x3: need N % 64 == 0 (no kernel takes this call)");
+    ESMK_TRY(launch_gemm(g, EPI_GELU_T, ESMK_DT_F16, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_debug_linear_splitk(const void* a_dev, const void* w_dev, float* partials_dev, int M, int N, int K,
+                             int S, int operand_dtype, void* stream) {
+    if (S < 1 || K % S != 0 || (K / S) % 64 != 0) return fail("esmk_debug_linear_splitk: K/S must be a multiple of 64");
+    GemmArgs g;
+    g.A = a_dev;
+    g.W = w_dev;
+    g.out = partials_dev;
+    g.M = M;
+    g.N = N;
+    g.K = K / S;
+    g.a_row_bytes = g.w_row_bytes = (long long)K * 2;  // rows keep the full-K stride
+    g.batch = S;
+    g.a_bo = g.w_bo = (long long)(K / S) * 2;           // slice s starts K/S operand elements further right
+    g.o_bo = (long long)M * N * 4;
+    ESMK_TRY(launch_gemm(g, EPI_STORE_F32, operand_dtype, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_debug_gemm_timing(void* stamps_dev) {
+    gemm8_set_timing((unsigned long long*)stamps_dev);
+    gemm9_set_timing((unsigned long long*)stamps_dev);
+    return 0;
+}
+
+int esmk_debug_mma_selftest(const void* a_dev, const void* b_dev, const float* c_dev, float* out_dev, int operand_dtype,
+                            void* stream) {
+    if (!a_dev || !b_dev || !c_dev || !out_dev) return fail("esmk_debug_mma_selftest: null argument");
+    ESMK_TRY(launch_mma_keep_c_selftest(a_dev, b_dev, c_dev, out_dev, operand_dtype, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- LayerNorm fold as single ops (tests/test_ln_fold_gpu.py) ----------------------------------------------------
+int esmk_op_rowstats(const float* x_dev, void* y_dev, float* mean_dev, float* rstd_dev, int rows, int E, int ldy,
+                     int operand_dtype, void* stream) {
+    if (!x_dev || !y_dev || !mean_dev || !rstd_dev) return fail("esmk_op_rowstats: null argument");
+    ESMK_TRY(launch_rowstats(x_dev, y_dev, mean_dev, rstd_dev, rows, E, ldy, operand_dtype, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_ln_finalize(const float* part_dev, float* mean_dev, float* rstd_dev, int rows, int parts, int E, void* stream) {
+    if (!part_dev || !mean_dev || !rstd_dev) return fail("esmk_op_ln_finalize: null argument");
+    ESMK_TRY(launch_ln_finalize(part_dev, mean_dev, rstd_dev, rows, parts, E, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_fold_weight(const void* w_dev, int w_dtype, const float* gamma_dev, const float* beta_dev, void* dst_dev,
+                        int dst_dtype, float* bias2_dev, int N, int K, int ld, void* stream) {
+    if (!w_dev || !gamma_dev || !beta_dev || !dst_dev || !bias2_dev) return fail("esmk_op_fold_weight: null argument");
+    if (N <= 0 || K <= 0 || ld < K) return fail("esmk_op_fold_weight: need N, K > 0 and ld >= K");
+    ESMK_TRY(launch_fold_weight(w_dev, w_dtype, gamma_dev, beta_dev, dst_dev, dst_dtype, bias2_dev, (size_t)N, (size_t)K,
+                                (size_t)ld, 0, 64, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_linear_ln(const void* a_dev, const void* w_dev, const float* bias_dev, const float* bias2_dev, void* out_dev,
+                      int M, int N, int K, int epilogue, int operand_dtype, const float* ln_rstd_dev, void* h16_dev, int ldh,
+                      float* ln_part_dev, int ln_parts, const float* ln_mean_dev, int half_m, void* stream) {
+    if (epilogue != EPI_GELU_T && epilogue != EPI_RESID_F32)
+        return fail("esmk_op_linear_ln: epilogue must be 2 (consumer: gelu) or 4 (producer: residual)");
+    GemmArgs g;
+    g.A = a_dev;
+    g.W = w_dev;
+    g.bias = bias_dev;
+    g.bias2 = bias2_dev;
+    g.out = out_dev;
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    g.half_m = half_m;
+    if (epilogue == EPI_GELU_T) {
+        if (!ln_rstd_dev || !bias_dev) return fail("esmk_op_linear_ln: the consumer needs ln_rstd and bias");
+        g.ln_rstd = ln_rstd_dev;
+    } else {
+        if (!h16_dev || !ln_part_dev || !ln_mean_dev) return fail("esmk_op_linear_ln: the producer needs h16, ln_part and ln_mean");
+        g.h16 = h16_dev;
+        g.ldh = ldh;
+        g.ln_part = ln_part_dev;
+        g.ln_parts = ln_parts;
+        g.ln_mean = ln_mean_dev;
+    }
+    ESMK_TRY(launch_gemm(g, epilogue, operand_dtype, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_debug_set(const char* key, double value) {
+    if (!key) return fail("esmk_debug_set: null key");
+    if (gemm_set_knob(key, value)) return 0;
+#ifdef ESMK_EXPERIMENTS
+    if (strcmp(key, "attn_stagger") == 0) {
+        attention_set_stagger((int)value);
+        return 0;
+    }
+#endif
+    return fail("esmk_debug_set: unknown key");
+}
+
+int esmk_debug_gemm_impl(int impl, int variant) {
+    if (impl != 8 && impl != 9 && impl != 0) return fail("esmk_debug_gemm_impl: impl must be 8, 9 or 0 (automatic choice)");
+    if (!gemm_set_impl(impl, variant))
+        return fail("esmk_debug_gemm_impl: variant must be 0 (the gemm9 variants exist in ESMK_EXPERIMENTS builds only)");
+    return 0;
+}
+
+int esmk_debug_gemm_plan(int M, int N, int K, int epilogue, int flags, int32_t out[4]) {
+    if (!out) return fail("esmk_debug_gemm_plan: null argument");
+    if (epilogue < EPI_STORE_T || epilogue > EPI_QKV_ALL) return fail("esmk_debug_gemm_plan: bad epilogue");
+    if (flags & ~63) return fail("esmk_debug_gemm_plan: unknown flag");
+    if ((flags & 32) && (flags != 32 || epilogue != EPI_GELU_T))
+        return fail("esmk_debug_gemm_plan: the f16x3 output form (flag 32) exists for epilogue 2 alone, with no other flag");
+    static const float fake = 0.f;  // stands for the pointers that select a form; gemm_plan dereferences nothing
+    GemmArgs g;
+    g.bias = &fake;
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    if (epilogue == EPI_QKV_ALL) g.E = N % 3 == 0 ? N / 3 : 0;
+    if (flags & 1) g.force_generic = 1;
+    if (flags & 2) g.force_old = 1;
+    if (flags & 4) {  // LayerNorm fold: producer form of the residual epilogue, consumer form of q / k, v, fc1
+        if (epilogue == EPI_RESID_F32) g.ln_part = const_cast<float*>(&fake);
+        else g.ln_rstd = &fake;
+        if (!gemm9_ln_fold(g, epilogue)) return fail("esmk_debug_gemm_plan: this epilogue has no LayerNorm-fold form");
+    }
+    if (flags & 8) {  // as esmk_op_linear_split: the GEMM runs over the [N,2K] hi | lo image of the weight
+        g.K = 2 * K;
+        g.a_row_bytes = (long long)K * 2;
+        g.a_kt_repeat = 1;
+    }
+    if (flags & 16) g.batch = 2;
+    if (flags & 32) g.x3_out = 1;  // as esmk_op_linear_gelu_x3
+    const GemmPlan pl = gemm_plan(g, epilogue);
+    out[0] = pl.kernel;
+    out[1] = pl.half_m;
+    out[2] = pl.variant;
+    out[3] = 0;
+    return 0;
+}
+
+static int qkv_rope_impl(esmk_model* m, const void* a_dev, const void* wqkv_dev, const float* bias_dev,
+                         const float* bias2_dev, const float* ln_rstd_dev, void* q_out, void* k_out, void* vt_out, int B, int T,
+                         int log2_domain, void* stream);
+
+int esmk_op_qkv_rope2(esmk_model* m, const void* a_dev, const void* wqkv_dev,
+                      const float* bias_dev, void* q_out, void* k_out, void* vt_out, int B, int T,
+                      int log2_domain, void* stream) {
+    return qkv_rope_impl(m, a_dev, wqkv_dev, bias_dev, nullptr, nullptr, q_out, k_out, vt_out, B, T, log2_domain, stream);
+}
+
+int esmk_op_qkv_rope_ln(esmk_model* m, const void* a_dev, const void* wqkv_dev, const float* bias_dev,
+                        const float* bias2_dev, const float* ln_rstd_dev, void* q_out, void* k_out, void* vt_out, int B, int T,
+                        int log2_domain, void* stream) {
+    if (!ln_rstd_dev || !bias_dev) return fail("esmk_op_qkv_rope_ln: ln_rstd and bias are required");
+    return qkv_rope_impl(m, a_dev, wqkv_dev, bias_dev, bias2_dev, ln_rstd_dev, q_out, k_out, vt_out, B, T, log2_domain, stream);
+}
+
+static int qkv_rope_impl(esmk_model* m, const void* a_dev, const void* wqkv_dev, const float* bias_dev,
+                         const float* bias2_dev, const float* ln_rstd_dev, void* q_out, void* k_out, void* vt_out, int B, int T,
+                         int log2_domain, void* stream) {
+    if (!m) return fail("esmk_op_qkv_rope: null model");
+    if (m->D != 64 || m->Kp != m->E) return fail("esmk_op_qkv_rope: single-op entry point needs head_dim 64");
+    hipStream_t st = (hipStream_t)stream;
+    if (ensure_rope(m, T, st)) return 1;
+    const int Tp = (T + 63) / 64 * 64;
+    if (Tp != T)
+        ESMK_TRY(hipMemsetAsync(vt_out, 0, (size_t)B * m->H * 64 * Tp * op_size(m->cfg.operand_dtype),
+                                st));
+    QkvProj p;
+    p.A = a_dev;
+    p.K = m->E;
+    p.W = wqkv_dev;
+    p.bias = bias_dev, p.bias2 = bias2_dev, p.ln_rstd = ln_rstd_dev;
+    p.q = q_out, p.k = k_out, p.vt = vt_out;
+    p.cos = m->d_cos;
+    p.sin = m->d_sin;
+    p.rows = B * T, p.T = T, p.Tp = Tp;
+    // log2_domain: q also carries log2(e), the form esmk_op_attention / esmk_op_attention_probs take (esmk_forward's own)
+    p.scaling = (log2_domain ? kLog2e : 1.0f) / sqrtf((float)m->D);
+    GemmArgs g, gv;
+    qkv_gemm_args(m, p, &g, &gv);
+    if (gemm_qkv_one_launch(g)) {  // as esmk_forward: one launch where it saves rounds of tiles
+        g.N = 3 * m->E;
+        ESMK_TRY(launch_gemm(g, EPI_QKV_ALL, m->cfg.operand_dtype, st));
+        return 0;
+    }
+    ESMK_TRY(launch_gemm(g, EPI_QKV_ROPE, m->cfg.operand_dtype, st));
+    ESMK_TRY(launch_gemm(gv, EPI_V_T, m->cfg.operand_dtype, st));
+    return 0;
+}
+
+int esmk_op_qkv_rope(esmk_model* m, const void* a_dev, const void* wqkv_dev,
+                     const float* bias_dev, void* q_out, void* k_out, void* vt_out, int B, int T,
+                     void* stream) {
+    return esmk_op_qkv_rope2(m, a_dev, wqkv_dev, bias_dev, q_out, k_out, vt_out, B, T, 0, stream);
+}
+
+int esmk_op_attention(const void* q_dev, const void* k_dev, const void* vt_dev,
+                      const float* key_bias_dev, void* ctx_out, float* lse_out, int B, int H,
+                      int T, int operand_dtype, void* stream) {
+    const int Tp = (T + 63) / 64 * 64;
+    ESMK_TRY(launch_attention(q_dev, k_dev, vt_dev, key_bias_dev, nullptr, ctx_out, lse_out, B, H, T,
+                              Tp, operand_dtype, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_attention_probs(const void* q_dev, const void* k_dev, const float* lse_dev,
+                            const float* key_bias_dev, float* probs_out, int B, int H, int T,
+                            int layer, int num_layers_total, int operand_dtype, void* stream) {
+    ESMK_TRY(launch_attention_probs(q_dev, k_dev, lse_dev, key_bias_dev, probs_out, B, H, T, layer,
+                                    num_layers_total, operand_dtype, (hipStream_t)stream));
+    return 0;
+}
+
+// Every form of the attention core that esmk_forward / esmk_msa_forward launch, reachable one kernel at a time
+// (tests/test_attention_variants_gpu.py).  Validation only, then the engine's own launchers.
+int esmk_op_attention_ex(const void* q_dev, const void* k_dev, const void* vt_dev, const float* key_bias_dev,
+                         const int32_t* seq_info_dev, const int32_t* any_pad_dev, void* ctx_out, float* lse_out, int B,
+                         int H, int T, int Tp, int head_dim, int mode, int operand_dtype, void* stream) {
+    if (!q_dev || !k_dev || !vt_dev || !ctx_out) return fail("esmk_op_attention_ex: null argument");
+    if (B <= 0 || H <= 0 || T <= 0) return fail("esmk_op_attention_ex: B, H and T must be positive");
+    if (Tp < T || Tp % 64 != 0) return fail("esmk_op_attention_ex: Tp must be a multiple of 64 and >= T");
+    if (head_dim != 64 && head_dim != 128) return fail("esmk_op_attention_ex: head_dim must be 64 or 128");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_attention_ex: operand_dtype must be fp16 or bf16");
+    if (mode < 0 || mode > 2) return fail("esmk_op_attention_ex: mode must be 0, 1 or 2");
+    if (mode != 0 && head_dim != 64) return fail("esmk_op_attention_ex: modes 1 and 2 need head_dim 64");
+    if (mode == 2 && operand_dtype != ESMK_DT_F16) return fail("esmk_op_attention_ex: mode 2 (f16x3) needs fp16");
+    if (seq_info_dev && (mode == 1 || !key_bias_dev))
+        return fail("esmk_op_attention_ex: seq_info needs key_bias and mode 0 or 2");
+    if (any_pad_dev && mode != 1) return fail("esmk_op_attention_ex: any_pad belongs to mode 1");
+    hipStream_t st = (hipStream_t)stream;
+    if (head_dim == 128)
+        ESMK_TRY(launch_attention128(q_dev, k_dev, vt_dev, key_bias_dev, seq_info_dev, ctx_out, lse_out, B, H, T, Tp,
+                                     operand_dtype, st));
+    else if (mode == 1)
+        ESMK_TRY(launch_attention_fill(q_dev, k_dev, vt_dev, key_bias_dev, any_pad_dev, ctx_out, lse_out, B, H, T, Tp,
+                                       operand_dtype, st));
+    else if (mode == 2)
+        ESMK_TRY(launch_attention_x3(q_dev, k_dev, vt_dev, key_bias_dev, seq_info_dev, ctx_out, lse_out, B, H, T, Tp,
+                                     operand_dtype, st));
+    else
+        ESMK_TRY(launch_attention(q_dev, k_dev, vt_dev, key_bias_dev, seq_info_dev, ctx_out, lse_out, B, H, T, Tp,
+                                  operand_dtype, st));
+    return 0;
+}
+
+int esmk_op_attention_biaskv(const void* q_dev, const void* k_dev, const void* vt_dev, const float* key_bias_dev,
+                             const int32_t* seq_info_dev, const void* bias_k_dev, const void* bias_v_dev, void* ctx_out,
+                             float* lse_out, int B, int H, int T, int Tp, int operand_dtype, void* stream) {
+    if (!q_dev || !k_dev || !vt_dev || !bias_k_dev || !bias_v_dev || !ctx_out) return fail("esmk_op_attention_biaskv: null argument");
+    if (B <= 0 || H <= 0 || T <= 0) return fail("esmk_op_attention_biaskv: B, H and T must be positive");
+    if (Tp < T || Tp % 64 != 0) return fail("esmk_op_attention_biaskv: Tp must be a multiple of 64 and >= T");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_attention_biaskv: operand_dtype must be fp16 or bf16");
+    if (seq_info_dev && !key_bias_dev) return fail("esmk_op_attention_biaskv: seq_info needs key_bias");
+    ESMK_TRY(launch_attention_biaskv(q_dev, k_dev, vt_dev, key_bias_dev, seq_info_dev, bias_k_dev, bias_v_dev, ctx_out, lse_out, B,
+                                     H, T, Tp, operand_dtype, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_attention_probs_ex(const void* q_dev, const void* k_dev, const float* lse_dev, const float* key_bias_dev,
+                               const int32_t* any_pad_dev, void* probs_out, int B, int H, int T, int head_dim, int layer,
+                               int num_layers_total, int msa_C, int out_dtype, int operand_dtype, void* stream) {
+    if (!q_dev || !k_dev || !lse_dev || !probs_out) return fail("esmk_op_attention_probs_ex: null argument");
+    if (B <= 0 || H <= 0 || T <= 0) return fail("esmk_op_attention_probs_ex: B, H and T must be positive");
+    if (head_dim != 64 && head_dim != 128) return fail("esmk_op_attention_probs_ex: head_dim must be 64 or 128");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_attention_probs_ex: operand_dtype must be fp16 or bf16");
+    if (out_dtype != ESMK_DT_F32 && out_dtype != operand_dtype)
+        return fail("esmk_op_attention_probs_ex: out_dtype must be fp32 or the operand dtype");
+    if (layer < 0 || layer >= num_layers_total) return fail("esmk_op_attention_probs_ex: layer out of range");
+    if (msa_C < 0) return fail("esmk_op_attention_probs_ex: msa_C must be >= 0");
+    if (msa_C > 0 && (head_dim != 64 || out_dtype != ESMK_DT_F32 || B % msa_C != 0))
+        return fail("esmk_op_attention_probs_ex: the MSA layout needs head_dim 64, fp32 maps and B a multiple of msa_C");
+    if (any_pad_dev && msa_C == 0) return fail("esmk_op_attention_probs_ex: any_pad belongs to the MSA layout");
+    hipStream_t st = (hipStream_t)stream;
+    const bool lowp = out_dtype != ESMK_DT_F32;
+    if (msa_C > 0)
+        ESMK_TRY(launch_attention_probs_msa(q_dev, k_dev, lse_dev, key_bias_dev, any_pad_dev, (float*)probs_out, B / msa_C,
+                                            msa_C, H, T, layer, num_layers_total, operand_dtype, st));
+    else if (head_dim == 128)
+        ESMK_TRY(launch_attention_probs128(q_dev, k_dev, lse_dev, key_bias_dev, (float*)probs_out, B, H, T, layer,
+                                           num_layers_total, operand_dtype, st, lowp));
+    else
+        ESMK_TRY(launch_attention_probs(q_dev, k_dev, lse_dev, key_bias_dev, (float*)probs_out, B, H, T, layer,
+                                        num_layers_total, operand_dtype, st, lowp));
+    return 0;
+}
+
+// The packed attention core and the packed map kernel one kernel at a time (tests/test_attention_packed_ops_gpu.py).
+// Validation first, before the HIP runtime is touched; then a work list of the entry's own — [seg 2 n][npad n][work 4 items]
+// [map offsets uint64 n], the layout esmk_forward_packed_maps uploads — is built, uploaded, used and freed: no state stays.
+namespace {
+struct PackedOpTables {
+    std::vector<int32_t> host;
+    int n_items = 0;
+    size_t map_base = 0;
+    unsigned long long sum_len2 = 0;
+};
+struct DevBuf {  // freed on every way out of the entry
+    void* p = nullptr;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+};
+int packed_op_tables(const std::string& w, const int32_t* seg, int n_seg, int rows, PackedOpTables* t) {
+    if (!seg) return fail(w + ": null segment table");
+    SegTableInfo info;
+    if (check_seg_table(w, seg, n_seg, rows, true, &info)) return 1;
+    t->n_items = (int)info.items;
+    t->sum_len2 = info.sum_len2;
+    const PackedTables lay = packed_tables(n_seg, info.items, 0, true);
+    t->map_base = lay.map_base;
+    t->host.assign(lay.ints, 0);
+    fill_attn_tables(seg, n_seg, t->host.data());
+    fill_map_offsets(seg, n_seg, t->host.data() + t->map_base);
+    return 0;
+}
+}  // namespace
+
+int esmk_op_attention_packed(const void* q_dev, const void* k_dev, const void* vt_dev, const float* key_bias_dev,
+                             const int32_t* segments_host, int n_seg, int rows, int Tp, int H, int head_dim,
+                             int operand_dtype, const void* bias_k_dev, const void* bias_v_dev, void* ctx_out, float* lse_out,
+                             void* stream) {
+    const std::string w("esmk_op_attention_packed");
+    if (!q_dev || !k_dev || !vt_dev || !ctx_out) return fail(w + ": null argument");
+    if (bias_k_dev || bias_v_dev)
+        return fail(w + ": bias_k / bias_v must be null (the null key of the ESM-1 models has no token-packed form)");
+    if (H <= 0) return fail(w + ": H must be positive");
+    if (head_dim != 64 && head_dim != 128) return fail(w + ": head_dim must be 64 or 128");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16) return fail(w + ": operand_dtype must be fp16 or bf16");
+    PackedOpTables t;
+    if (packed_op_tables(w, segments_host, n_seg, rows, &t)) return 1;
+    if (Tp % 64 != 0 || Tp < rows + 64) return fail(w + ": Tp must be a multiple of 64 and >= rows + 64 (one spare key tile)");
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf d;
+    ESMK_TRY(hipMalloc(&d.p, t.host.size() * 4));
+    ESMK_TRY(hipMemcpy(d.p, t.host.data(), t.host.size() * 4, hipMemcpyHostToDevice));
+    int* tab = (int*)d.p;
+    AttnSegs segs;
+    segs.npad = tab + (size_t)2 * n_seg;
+    segs.work = tab + (size_t)3 * n_seg;
+    ESMK_TRY(launch_seg_npad(key_bias_dev, tab, n_seg, tab + (size_t)2 * n_seg, st));
+    if (head_dim == 128)
+        ESMK_TRY(launch_attention128_packed(q_dev, k_dev, vt_dev, key_bias_dev, ctx_out, lse_out, H, rows, Tp, segs, t.n_items,
+                                            operand_dtype, st));
+    else
+        ESMK_TRY(launch_attention_packed(q_dev, k_dev, vt_dev, key_bias_dev, ctx_out, lse_out, H, rows, Tp, segs, t.n_items,
+                                         operand_dtype, st));
+    // a segment of padding only has no key: the padded form skips it through seq_info, here its rows are cleared afterwards
+    ESMK_TRY(launch_zero_allpad_segments(ctx_out, lse_out, tab, segs.npad, n_seg, H, rows,
+                                         (size_t)H * head_dim * op_size(operand_dtype), st));
+    ESMK_TRY(hipStreamSynchronize(st));  // the work list is freed on return
+    return 0;
+}
+
+int esmk_op_attention_probs_packed(const void* q_dev, const void* k_dev, const float* lse_dev, const float* key_bias_dev,
+                                   const int32_t* segments_host, int n_seg, int rows, int H, int head_dim, int L_total,
+                                   int layer, int operand_dtype, int lowp, void* probs_out, size_t probs_elems, void* stream) {
+    const std::string w("esmk_op_attention_probs_packed");
+    if (!q_dev || !k_dev || !lse_dev) return fail(w + ": null argument");
+    if (H <= 0 || L_total <= 0) return fail(w + ": H and L_total must be positive");
+    if (head_dim != 64 && head_dim != 128) return fail(w + ": head_dim must be 64 or 128");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16) return fail(w + ": operand_dtype must be fp16 or bf16");
+    if (layer < 0 || layer >= L_total) return fail(w + ": layer out of range");
+    PackedOpTables t;
+    if (packed_op_tables(w, segments_host, n_seg, rows, &t)) return 1;
+    if (!probs_out) return fail(w + ": attention buffer missing");
+    const unsigned long long need = t.sum_len2 * (unsigned long long)L_total * (unsigned long long)H;
+    if ((unsigned long long)probs_elems < need)
+        return fail(w + ": attention buffer too small (" + std::to_string(probs_elems) + " elements, need " + std::to_string(need) +
+                    " = L H sum(len^2))");
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf d;
+    ESMK_TRY(hipMalloc(&d.p, t.host.size() * 4));
+    ESMK_TRY(hipMemcpy(d.p, t.host.data(), t.host.size() * 4, hipMemcpyHostToDevice));
+    int* tab = (int*)d.p;
+    AttnSegs segs;
+    segs.npad = tab + (size_t)2 * n_seg;
+    segs.work = tab + (size_t)3 * n_seg;
+    const unsigned long long* map_off = reinterpret_cast<const unsigned long long*>(tab + t.map_base);
+    ESMK_TRY(launch_seg_npad(key_bias_dev, tab, n_seg, tab + (size_t)2 * n_seg, st));
+    if (head_dim == 128)
+        ESMK_TRY(launch_attention_probs128_packed(q_dev, k_dev, lse_dev, key_bias_dev, probs_out, H, rows, layer, L_total, segs,
+                                                  map_off, t.n_items, operand_dtype, lowp != 0, st));
+    else
+        ESMK_TRY(launch_attention_probs_packed(q_dev, k_dev, lse_dev, key_bias_dev, probs_out, H, rows, layer, L_total, segs,
+                                               map_off, t.n_items, operand_dtype, lowp != 0, st));
+    ESMK_TRY(hipStreamSynchronize(st));  // the work list is freed on return
+    return 0;
+}
+
+// Contact pipeline of the fused path (contacts.hip) on caller-supplied q, k and lse, stacked over layers
+// (tests/test_contacts_kernels_gpu.py).  Validation and planning shared by the two entries below; the launches are
+// the engine's own.  Packed form (seg != NULL): B = 1, T = rows; segments may leave gaps, start anywhere, come in any
+// order and be empty, but must not overlap.  G: 0 = the engine's head-group count, else a forced one, raised to the
+// count whose groups all hold a head (ceil(H / ceil(H / G))).
+struct CtOpLayout {
+    int G = 0;
+    CtPackedPlan plan;
+    size_t acc = 0, row = 0, col = 0, rowp = 0, colp = 0, wt = 0, tables = 0, total = 0;
+    size_t ct_base = 0, n_int = 0;  // packed: int32 slot of the contact tables, int32 slots uploaded
+};
+
+static int contacts_op_plan(const char* who, int B, int H, int T, int L, int head_dim, const int32_t* seg, int n_seg,
+                            int prepend_bos, int append_eos, int G_req, CtOpLayout* lay) {
+    const std::string w(who);
+    if (B <= 0 || H <= 0 || T <= 0 || L <= 0) return fail(w + ": B, H, T and num_layers must be positive");
+    if (head_dim != 64 && head_dim != 128) return fail(w + ": head_dim must be 64 or 128");
+    if ((prepend_bos != 0 && prepend_bos != 1) || (append_eos != 0 && append_eos != 1))
+        return fail(w + ": prepend_bos and append_eos must be 0 or 1");
+    if ((long long)B * T > ESMK_MAX_ROWS) return fail(w + ": B*T exceeds 2^24 rows");
+    if ((long long)L * H > (1 << 20)) return fail(w + ": num_layers * H is too large");
+    if (G_req < 0 || G_req > H) return fail(w + ": head_groups must be 0 (engine's choice) or in [1, H]");
+    if (G_req > 0 && head_dim == 128 && (H + G_req - 1) / G_req > 20)
+        return fail(w + ": head_dim 128 takes at most 20 heads per group");
+    const size_t C = (size_t)L * H;
+    Carve c;
+    if (seg == nullptr) {
+        if (n_seg != 0) return fail(w + ": n_seg without a segment table");
+        if (T - prepend_bos - append_eos <= 0) return fail(w + ": no contact map: T - prepend_bos - append_eos <= 0");
+        const long long nQ = (T + 127) / 128;
+        lay->G = contacts_head_groups((long long)B * nQ * nQ, H, head_dim);
+        if (G_req > 0) {
+            const int hg = (H + G_req - 1) / G_req;
+            lay->G = (H + hg - 1) / hg;
+        }
+        lay->acc = c.take((size_t)lay->G * B * T * T * 4);
+        lay->row = c.take((size_t)B * C * T * 4);
+        lay->col = c.take((size_t)B * C * T * 4);
+        lay->rowp = c.take((size_t)B * nQ * H * T * 4);
+        lay->colp = c.take((size_t)B * ((T + 31) / 32) * H * T * 4);
+        lay->wt = c.take((size_t)B * C * 4);
+    } else {
+        if (B != 1) return fail(w + ": the packed form takes B = 1 (T = rows)");
+        if (n_seg <= 0) return fail(w + ": n_seg must be positive");
+        std::vector<std::pair<long long, long long>> span;
+        for (int s = 0; s < n_seg; ++s) {
+            const long long start = seg[2 * s], len = seg[2 * s + 1];
+            if (start < 0 || len < 0 || start + len > T)
+                return fail(w + ": segment table: every segment must lie inside [0, rows)");
+            if (len > 0) span.emplace_back(start, start + len);
+        }
+        std::sort(span.begin(), span.end());
+        for (size_t i = 1; i < span.size(); ++i)
+            if (span[i].first < span[i - 1].second) return fail(w + ": segment table: segments overlap");
+        lay->plan = contacts_packed_plan(seg, n_seg, H, head_dim, prepend_bos, append_eos);
+        if (G_req > 0) {
+            const int hg = (H + G_req - 1) / G_req;
+            lay->plan.G = (H + hg - 1) / hg;
+        }
+        lay->G = lay->plan.G;
+        const CtPackedPlan& p = lay->plan;
+        lay->acc = c.take((size_t)p.G * p.sum_len2 * 4);
+        lay->row = c.take(C * T * 4);
+        lay->col = c.take(C * T * 4);
+        lay->rowp = c.take((size_t)p.rowp * 4);
+        lay->colp = c.take((size_t)p.colp * 4);
+        lay->wt = c.take((size_t)n_seg * C * 4);
+        lay->ct_base = ((size_t)2 * n_seg + 1) & ~(size_t)1;  // [seg 2 n_seg] | contact tables (8-byte aligned)
+        lay->n_int = lay->ct_base + p.table_ints();
+        lay->tables = c.take(lay->n_int * 4);
+    }
+    lay->total = c.off;
+    return 0;
+}
+
+int esmk_op_contacts_fused_workspace_bytes_ex(int B, int H, int T, int num_layers, int head_dim,
+                                              const int32_t* segments_host, int n_seg, int prepend_bos, int append_eos,
+                                              int head_groups, size_t* bytes) {
+    if (!bytes) return fail("esmk_op_contacts_fused_workspace_bytes_ex: null argument");
+    CtOpLayout lay;
+    if (contacts_op_plan("esmk_op_contacts_fused_workspace_bytes_ex", B, H, T, num_layers, head_dim, segments_host,
+                         n_seg, prepend_bos, append_eos, head_groups, &lay))
+        return 1;
+    *bytes = lay.total;
+    return 0;
+}
+
+int esmk_op_contacts_fused_ex(const void* q_dev, const void* k_dev, const float* lse_dev, const float* key_bias_dev,
+                              const int64_t* tokens_dev, const float* w_dev, const float* b_dev,
+                              const int32_t* segments_host, int n_seg, float* out_dev, void* workspace_dev,
+                              size_t workspace_bytes, int B, int H, int T, int num_layers, int head_dim, int pad_idx,
+                              int eos_idx, int prepend_bos, int append_eos, int head_groups, int* head_groups_used,
+                              int operand_dtype, void* stream) {
+    const char* who = "esmk_op_contacts_fused_ex";
+    if (!q_dev || !k_dev || !lse_dev || !tokens_dev || !w_dev || !out_dev || !workspace_dev)
+        return fail("esmk_op_contacts_fused_ex: null argument");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_contacts_fused_ex: operand_dtype must be fp16 or bf16");
+    CtOpLayout lay;
+    if (contacts_op_plan(who, B, H, T, num_layers, head_dim, segments_host, n_seg, prepend_bos, append_eos,
+                         head_groups, &lay))
+        return 1;
+    if (workspace_bytes < lay.total) return fail("esmk_op_contacts_fused_ex: workspace too small");
+    if (head_groups_used) *head_groups_used = lay.G;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace_dev;
+    const int L = num_layers, C = L * H;
+    const size_t os = op_size(operand_dtype);
+    // one layer of q / k: [B, H, T, D] padded, [H, rows, D] packed (B = 1, T = rows): the same stride
+    const size_t qk_layer = (size_t)B * H * T * head_dim * os, lse_layer = (size_t)B * H * T;
+    float* acc = (float*)(ws + lay.acc);
+    float* row = (float*)(ws + lay.row);
+    float* col = (float*)(ws + lay.col);
+    float* rowp = (float*)(ws + lay.rowp);
+    float* colp = (float*)(ws + lay.colp);
+    float* wt = (float*)(ws + lay.wt);
+    if (segments_host == nullptr) {
+        for (int l = 0; l < L; ++l)
+            ESMK_TRY(launch_contacts_fused_layer((const char*)q_dev + l * qk_layer, (const char*)k_dev + l * qk_layer,
+                                                 lse_dev + l * lse_layer, key_bias_dev, tokens_dev, w_dev, acc, row,
+                                                 col, rowp, colp, B, H, T, C, l, head_dim, pad_idx, eos_idx,
+                                                 prepend_bos, append_eos, operand_dtype, st, lay.G));
+        ESMK_TRY(launch_contacts_fused_final(acc, row, col, wt, tokens_dev, w_dev, b_dev, out_dev, B, H, C, T, head_dim,
+                                             pad_idx, eos_idx, prepend_bos, append_eos, st, lay.G));
+        return 0;
+    }
+    // the segment table and the contact tables, uploaded as esmk_forward_packed_ex does (tables behind the workspace)
+    std::vector<int32_t> host(lay.n_int, 0);
+    memcpy(host.data(), segments_host, (size_t)2 * n_seg * 4);
+    contacts_packed_tables(lay.plan, segments_host, prepend_bos, append_eos, H, host.data() + lay.ct_base);
+    int* tab = (int*)(ws + lay.tables);
+    ESMK_TRY(hipMemcpyAsync(tab, host.data(), lay.n_int * 4, hipMemcpyHostToDevice, st));
+    ESMK_TRY(hipStreamSynchronize(st));  // `host` goes out of scope below
+    const CtPackedPlan& p = lay.plan;
+    CtPackedDev d;
+    d.seg = tab;
+    d.off = reinterpret_cast<const long long*>(tab + lay.ct_base);
+    d.acc_work = tab + lay.ct_base + 8 * (size_t)n_seg;
+    d.red_work = d.acc_work + 4 * p.n_acc;
+    d.rt_work = d.red_work + 2 * p.n_red;
+    d.fin_work = d.rt_work + p.n_rt;
+    d.rows = T;
+    for (int l = 0; l < L; ++l)
+        ESMK_TRY(launch_contacts_packed_layer((const char*)q_dev + l * qk_layer, (const char*)k_dev + l * qk_layer,
+                                              lse_dev + l * lse_layer, key_bias_dev, tokens_dev, w_dev, acc, row, col,
+                                              rowp, colp, p, d, H, C, l, head_dim, pad_idx, eos_idx, prepend_bos,
+                                              append_eos, operand_dtype, st));
+    ESMK_TRY(launch_contacts_packed_final(acc, row, col, wt, tokens_dev, w_dev, b_dev, out_dev, p, d, C, pad_idx,
+                                          eos_idx, prepend_bos, append_eos, st));
+    return 0;
+}
+
+// The generalised-addressing GEMM forms esmk_forward / esmk_msa_forward launch, one launch at a time
+// (tests/test_gemm_forms_gpu.py).  Validation only, then launch_gemm unchanged.
+int esmk_op_gemm_ex(const esmk_gemm_ex_args* a, void* stream) {
+    if (!a) return fail("esmk_op_gemm_ex: null argument");
+    if (a->size != sizeof(esmk_gemm_ex_args)) return fail("esmk_op_gemm_ex: size must be sizeof(esmk_gemm_ex_args)");
+    const int epi = a->epilogue;
+    if (epi < EPI_STORE_T || epi > EPI_MSA_CTX) return fail("esmk_op_gemm_ex: epilogue must be 0 ... 7");
+    if (a->operand_dtype != ESMK_DT_F16 && a->operand_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_gemm_ex: operand_dtype must be fp16 or bf16");
+    const bool qk = epi == EPI_QKV_ROPE, vt = epi == EPI_V_T, ctx = epi == EPI_MSA_CTX;
+    if (!a->A || !a->W) return fail("esmk_op_gemm_ex: null operand");
+    if (qk && (!a->q || !a->k || !a->cos || !a->sin)) return fail("esmk_op_gemm_ex: epilogue 5 needs q, k, cos and sin");
+    if (vt && !a->vt) return fail("esmk_op_gemm_ex: epilogue 6 needs vt");
+    if (!qk && !vt && !a->out) return fail("esmk_op_gemm_ex: null output");
+    if (a->M <= 0 || a->N <= 0 || a->K <= 0) return fail("esmk_op_gemm_ex: M, N and K must be positive");
+    if (a->K % 64 != 0 || a->N % 8 != 0) return fail("esmk_op_gemm_ex: need K % 64 == 0 and N % 8 == 0");
+    if ((qk || vt || ctx) && a->N % 64 != 0) return fail("esmk_op_gemm_ex: epilogues 5, 6 and 7 need N % 64 == 0");
+    if (a->head_dim != 64 && a->head_dim != 128) return fail("esmk_op_gemm_ex: head_dim must be 64 or 128");
+    if (a->head_dim == 128 && !qk && !vt) return fail("esmk_op_gemm_ex: head_dim 128 belongs to epilogues 5 and 6");
+    if (a->batch < 1 || a->batch_inner < 1 || a->batch % a->batch_inner != 0)
+        return fail("esmk_op_gemm_ex: batch and batch_inner must be >= 1 and batch_inner must divide batch");
+    if (a->a_row_bytes < 0 || a->w_row_bytes < 0 || a->a_kt_bytes < 0 || a->w_kt_bytes < 0 || a->a_bo < 0 ||
+        a->a_bi < 0 || a->w_bo < 0 || a->w_bi < 0 || a->o_bo < 0 || a->o_bi < 0 || a->n_valid < 0 || a->ldc < 0 ||
+        a->vt_rows < 0 || a->rowmap_R < 0 || a->rowmap_C < 0 || a->ctx_R < 0 || a->ctx_C < 0)
+        return fail("esmk_op_gemm_ex: strides, offsets and counts must not be negative");
+    if (a->a_kt_repeat != 0 && (a->a_kt_repeat != 1 || a->K % 128 != 0))
+        return fail("esmk_op_gemm_ex: a_kt_repeat is 0 or 1, and 1 needs K % 128 == 0");
+    if (a->n_valid > a->N) return fail("esmk_op_gemm_ex: n_valid must be <= N");
+    if (a->ldc > 0 && !ctx && a->ldc < a->N) return fail("esmk_op_gemm_ex: ldc must be >= N");
+    if ((a->row_keep || a->row_pos) && !qk) return fail("esmk_op_gemm_ex: row_keep and row_pos belong to epilogue 5");
+    if (a->vt_rows > 0 && !vt) return fail("esmk_op_gemm_ex: vt_rows belongs to epilogue 6");
+    if (a->vt_rows > 0 && a->head_dim == 128) return fail("esmk_op_gemm_ex: vt_rows needs head_dim 64");
+    if (qk || vt) {
+        if (a->T <= 0 || a->H <= 0 || a->E != a->H * a->head_dim || a->N != (qk ? 2 : 1) * a->E || a->M % a->T != 0)
+            return fail("esmk_op_gemm_ex: epilogues 5 and 6 need T, H > 0, E = H head_dim, N = 2E (5) or E (6), M % T == 0");
+        if (vt && (a->Tp < a->T || a->Tp % 64 != 0)) return fail("esmk_op_gemm_ex: Tp must be a multiple of 64 and >= T");
+        if (a->vt_rows > 0 && (a->M / a->T) % a->vt_rows != 0)
+            return fail("esmk_op_gemm_ex: vt_rows must divide the number of sequences M / T");
+    }
+    if ((a->rowmap_R > 0 || a->rowmap_C > 0) &&
+        (epi != EPI_RESID_F32 || a->rowmap_R <= 0 || a->rowmap_C <= 0 || a->M % (a->rowmap_R * a->rowmap_C) != 0))
+        return fail("esmk_op_gemm_ex: the row map needs epilogue 4, rowmap_R, rowmap_C > 0 and M % (R C) == 0");
+    if ((a->ctx_R > 0 || a->ctx_C > 0) && !ctx) return fail("esmk_op_gemm_ex: ctx_R and ctx_C belong to epilogue 7");
+    if (ctx && (a->ctx_R <= 0 || a->ctx_C < a->M || a->N != 64 * a->ctx_R || a->ldc < 64 * a->batch_inner))
+        return fail("esmk_op_gemm_ex: epilogue 7 needs N = 64 ctx_R, ctx_C >= M and ldc >= 64 batch_inner");
+    GemmArgs g;
+    g.A = a->A;
+    g.W = a->W;
+    g.bias = a->bias;
+    g.out = a->out;
+    g.M = a->M;
+    g.N = a->N;
+    g.K = a->K;
+    g.q = a->q;
+    g.k = a->k;
+    g.vt = a->vt;
+    g.cos = a->cos;
+    g.sin = a->sin;
+    g.T = a->T;
+    g.H = a->H;
+    g.E = a->E;
+    g.Tp = a->Tp;
+    g.scaling = a->scaling;
+    g.a_row_bytes = a->a_row_bytes;
+    g.w_row_bytes = a->w_row_bytes;
+    g.a_kt_bytes = a->a_kt_bytes;
+    g.w_kt_bytes = a->w_kt_bytes;
+    g.a_kt_repeat = a->a_kt_repeat;
+    g.batch = a->batch;
+    g.batch_inner = a->batch_inner;
+    g.a_bo = a->a_bo;
+    g.a_bi = a->a_bi;
+    g.w_bo = a->w_bo;
+    g.w_bi = a->w_bi;
+    g.o_bo = a->o_bo;
+    g.o_bi = a->o_bi;
+    g.n_valid = a->n_valid;
+    g.ldc = a->ldc;
+    g.row_keep = a->row_keep;
+    g.vt_rows = a->vt_rows;
+    g.rowmap_R = a->rowmap_R;
+    g.rowmap_C = a->rowmap_C;
+    g.ctx_R = a->ctx_R;
+    g.ctx_C = a->ctx_C;
+    g.head_dim = a->head_dim;
+    g.row_pos = a->row_pos;
+    if (epi == EPI_GELU_F32 && gemm8_generalised(g, epi))
+        return fail("esmk_op_gemm_ex: epilogue 3 (fp32 gelu) has no generalised form");
+    ESMK_TRY(launch_gemm(g, epi, a->operand_dtype, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_msa_row_softmax(const float* scores_dev, const float* keep_dev, const int32_t* any_pad_dev, void* probs_out,
+                            float* attn_out, int B, int H, int R, int C, int ldp, int layer, int num_layers_total,
+                            int nslice, int operand_dtype, void* stream) {
+    if (!scores_dev || !keep_dev || !any_pad_dev || !probs_out) return fail("esmk_op_msa_row_softmax: null argument");
+    if (B <= 0 || H <= 0 || R <= 0 || C <= 0) return fail("esmk_op_msa_row_softmax: B, H, R and C must be positive");
+    if (C > 1024 || ldp > 1024 || ldp < C) return fail("esmk_op_msa_row_softmax: need C <= ldp <= 1024");
+    if (nslice < 1) return fail("esmk_op_msa_row_softmax: nslice must be >= 1");
+    if (attn_out && (layer < 0 || layer >= num_layers_total)) return fail("esmk_op_msa_row_softmax: layer out of range");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_msa_row_softmax: operand_dtype must be fp16 or bf16");
+    ESMK_TRY(launch_msa_row_softmax(scores_dev, keep_dev, any_pad_dev, probs_out, attn_out, B, H, R, C, ldp, layer,
+                                    num_layers_total, operand_dtype, (hipStream_t)stream, nslice));
+    return 0;
+}
+
+int esmk_op_mask_rows(const int64_t* tokens_dev, const int32_t* src_row_dev, const int32_t* pos_dev, int64_t* out_dev, int B,
+                      int T, int n, int mask_idx, void* stream) {
+    if (!tokens_dev || !pos_dev || !out_dev) return fail("esmk_op_mask_rows: null argument");
+    if (B <= 0 || T <= 0 || n <= 0) return fail("esmk_op_mask_rows: B, T and n must be positive");
+    if ((long long)B * T > ESMK_MAX_ROWS || (long long)n * T > ESMK_MAX_ROWS)
+        return fail("esmk_op_mask_rows: B*T or n*T exceeds 2^24 rows");
+    ESMK_TRY(launch_mask_rows(tokens_dev, src_row_dev, pos_dev, out_dev, B, T, n, mask_idx, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_mask_rows_multi(const int64_t* tokens_dev, const int32_t* src_row_dev, const int32_t* pos_off_dev,
+                            const int32_t* pos_dev, int64_t* out_dev, int B, int T, int n, int total, int mask_idx, void* stream) {
+    if (!tokens_dev || !pos_off_dev || !pos_dev || !out_dev) return fail("esmk_op_mask_rows_multi: null argument");
+    if (B <= 0 || T <= 0 || n <= 0) return fail("esmk_op_mask_rows_multi: B, T and n must be positive");
+    if (total < 0) return fail("esmk_op_mask_rows_multi: total must not be negative");
+    if ((long long)B * T > ESMK_MAX_ROWS || (long long)n * T > ESMK_MAX_ROWS)
+        return fail("esmk_op_mask_rows_multi: B*T or n*T exceeds 2^24 rows");
+    ESMK_TRY(launch_mask_rows_multi(tokens_dev, src_row_dev, pos_off_dev, pos_dev, out_dev, B, T, n, total, mask_idx,
+                                    (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_score_rows(const float* logprobs_dev, const int32_t* wt_dev, const int32_t* mt_dev, const int32_t* var_off_dev,
+                       double* out_dev, int n_rows, int n_var, int V, void* stream) {
+    if (!logprobs_dev || !wt_dev || !mt_dev || !var_off_dev || !out_dev) return fail("esmk_op_score_rows: null argument");
+    if (n_rows <= 0 || n_var <= 0 || V <= 0) return fail("esmk_op_score_rows: n_rows, n_var and V must be positive");
+    ESMK_TRY(launch_score_rows(logprobs_dev, wt_dev, mt_dev, var_off_dev, out_dev, n_rows, n_var, V, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_log_softmax_rows(const float* logits_dev, float* out_dev, const int32_t* target_dev, float* target_out_dev, int n,
+                             int V, void* stream) {
+    if (!logits_dev || !out_dev) return fail("esmk_op_log_softmax_rows: null argument");
+    if ((target_dev != nullptr) != (target_out_dev != nullptr))
+        return fail("esmk_op_log_softmax_rows: target_dev and target_out_dev go together");
+    if (n <= 0 || n > ESMK_MAX_ROWS) return fail("esmk_op_log_softmax_rows: n must be in 1 .. 2^24");
+    if (V <= 0 || V > 64) return fail("esmk_op_log_softmax_rows: V must be in 1 .. 64 (one vocabulary entry per lane)");
+    ESMK_TRY(launch_log_softmax_rows(logits_dev, out_dev, target_dev, target_out_dev, n, V, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_contacts(const float* attn_dev, const int64_t* tokens_dev, const float* w_dev,
+                     const float* b_dev, float* scratch_dev, float* out_dev, int B, int C, int T,
+                     int eos_idx, int prepend_bos, int append_eos, void* stream) {
+    ESMK_TRY(launch_contacts(attn_dev, tokens_dev, w_dev, b_dev, scratch_dev, out_dev, B, C, T,
+                             eos_idx, prepend_bos, append_eos, (hipStream_t)stream));
+    return 0;
+}
+
+}  // extern "C"
+

@@ -56,6 +56,44 @@ def test_workspace_queries_and_row_limit():
     N.lib.esmk_destroy(h)
 
 
+# Byte counts of the packed-batch workspaces, recorded from the build in front of the split of the forward engine into stages:
+# the int32 tables behind the workspace ([seg 2n][npad n][work 4 items][pad][contact tables][pad][map offsets u64 n]) have ONE
+# layout function since then, and it must give what the three hand-written copies gave.  First table: three segments, an odd
+# slot count in front of the contact tables and of the map offsets (both alignment slots in use); second: 40 short segments,
+# tables of more than one 256-byte carving unit.
+PACKED_SEGS_A = ([0, 5, 16, 130, 160, 64], 256)
+PACKED_SEGS_B = ([v for s in range(40) for v in (16 * s, 9 + s % 8)], 640)
+_CT, _AT, _LG = N.OUT_CONTACTS, N.OUT_ATTN, N.OUT_LOGITS
+PACKED_WORKSPACE_BYTES = [
+    ("esmk_packed_workspace_bytes", PACKED_SEGS_A, _LG, 531968),
+    ("esmk_packed_workspace_bytes_ex", PACKED_SEGS_A, _LG, 531968),
+    ("esmk_packed_workspace_bytes_ex", PACKED_SEGS_A, _LG | _CT, 720384),
+    ("esmk_packed_workspace_bytes_maps", PACKED_SEGS_A, _LG, 531968),
+    ("esmk_packed_workspace_bytes_maps", PACKED_SEGS_A, _LG | _AT, 534016),
+    ("esmk_packed_workspace_bytes_maps", PACKED_SEGS_A, _AT | N.OUT_ATTN_LOWP, 534016),
+    ("esmk_packed_workspace_bytes_maps", PACKED_SEGS_A, _LG | _CT | _AT, 720384),
+    ("esmk_packed_workspace_bytes", PACKED_SEGS_B, _LG, 1332224),
+    ("esmk_packed_workspace_bytes_ex", PACKED_SEGS_B, _LG | _CT, 1421568),
+    ("esmk_packed_workspace_bytes_maps", PACKED_SEGS_B, _LG | _AT, 1337600),
+    ("esmk_packed_workspace_bytes_maps", PACKED_SEGS_B, _LG | _CT | _AT, 1421824),
+]
+
+
+@pytest.mark.parametrize("entry,table,flags,expect", PACKED_WORKSPACE_BYTES)
+def test_packed_workspace_bytes_are_those_of_the_parent_build(entry, table, flags, expect):
+    rc, h = make()
+    seg, rows = table
+    arr = (ctypes.c_int32 * len(seg))(*seg)
+    n = ctypes.c_size_t()
+    if entry == "esmk_packed_workspace_bytes":
+        rc = N.lib.esmk_packed_workspace_bytes(h, len(seg) // 2, rows, flags, ctypes.byref(n))
+    else:
+        rc = getattr(N.lib, entry)(h, arr, len(seg) // 2, rows, flags, ctypes.byref(n))
+    assert rc == 0, err()
+    assert n.value == expect
+    N.lib.esmk_destroy(h)
+
+
 def test_forward_argument_checks():
     rc, h = make()
     layers = (ctypes.c_int32 * 1)(2)

@@ -84,7 +84,7 @@ def bits_equal(a, b):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# tied row-attention scores (engine_msa.hip:348-370)
+# tied row-attention scores (engine_msa.hip:284-306)
 # ---------------------------------------------------------------------------------------------------------------------
 SCORE_CELLS = [  # (C, R, B, S); "e" = the engine's row_score_slices
     (1, 1, 1, 1), (2, 2, 2, 2), (63, 3, 1, 3), (64, 8, 2, 8), (65, 7, 1, 7), (255, 64, 1, 4), (256, 8, 2, "e"),
@@ -175,7 +175,7 @@ def test_row_softmax(ops, B, R, C, S, any_pad, pads, layer, Ltot, dt):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# row-attention context (engine_msa.hip:378-397)
+# row-attention context (engine_msa.hip:314-333)
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("C,R,B", [(1, 3, 1), (65, 256, 1), (257, 7, 2), (1000, 2, 1)])
 @pytest.mark.parametrize("dt", DT)
@@ -197,7 +197,7 @@ def test_row_context(ops, C, R, B, dt):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# MSA q / k / v (engine_msa.hip:290-326) and the row-mapped residual (engine_msa.hip:327-339), plain and split weights
+# MSA q / k / v (engine_msa.hip:244-262, engine.hip: qkv_gemm_args) and the row-mapped residual (engine_msa.hip:263-275), plain and split weights
 # ---------------------------------------------------------------------------------------------------------------------
 def linear_args(ops, a, w32, dt, split):
     """GemmArgs fields of A / W and the reference operands: plain W, or the split_weight image with a_kt_repeat, whose
@@ -337,7 +337,7 @@ def test_split_weights(ops, form):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# head_dim 128 (engine.hip:928) and rotary positions of token-packed batches (engine.hip:929)
+# head_dim 128 (engine.hip:402) and rotary positions of token-packed batches (engine.hip:404)
 # ---------------------------------------------------------------------------------------------------------------------
 def qkv128(ops, x, w, bias, B, T, H, dt, row_pos=None, Tp=None, with_v=True):
     """q / k with the head_pad_index weight order and the 64-slot rotary table, v in natural order; head_dim 128."""
