@@ -6,10 +6,12 @@ Importing this package does not load the HIP library; ``esm_amd._native`` does, 
 forward (or explicitly), and raises if libesmk.so is missing — there is no CPU fallback.
 """
 from .alphabet import Alphabet, BatchConverter, MSABatchConverter  # noqa: F401
-from .fasta import FastaBatchedDataset, read_alignment_lines, read_fasta  # noqa: F401
+from .fasta import FastaBatchedDataset, read_alignment_lines, read_fasta, read_msa  # noqa: F401
 from .esm2 import ESM2  # noqa: F401
 from . import checkpoint as pretrained  # noqa: F401
 from .scoring import (masked_joint, masked_marginals, parse_variant, pseudo_log_likelihood, score_mutations,  # noqa: F401
                       score_variants, wt_marginals)
+from .msa_scoring import (msa_forward_rows, msa_masked_joint, msa_masked_marginals, msa_score_variants,  # noqa: F401
+                          msa_wt_marginals)
 
 __version__ = "0.1.0"

@@ -136,6 +136,12 @@ SIGNATURES = {
             c_void_p, c_size_t, c_void_p,
         ],
     ),
+    "esmk_msa_rows_workspace_bytes": (
+        c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
+    "esmk_msa_forward_rows": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "esmk_debug_msa_row_slices": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int32)]),
     "esmk_profile_begin": (c_int, [c_void_p]),
     "esmk_profile_end": (c_int, [c_void_p, POINTER(EsmkProfileEntry), c_int, POINTER(c_int)]),
     "esmk_ln_fold_enabled": (c_int, [c_void_p]),

@@ -84,7 +84,9 @@ int row_score_slices(int B, int H, int R, int C) {
     return best;
 }
 
-MsaWorkspace plan_msa_workspace(const esmk_model* m, int B, int R, int C, uint32_t flags) {
+// slices_B: the batch size the slice count of the tied-score GEMM is chosen for — B itself (esmk_msa_forward), or 1
+// (esmk_msa_forward_rows: every copy of the batch then runs the launches and summation order of a B = 1 forward)
+MsaWorkspace plan_msa_workspace(const esmk_model* m, int B, int R, int C, uint32_t flags, int slices_B) {
     MsaWorkspace w{};
     const size_t os = op_size(m->cfg.operand_dtype);
     const size_t N = (size_t)B * R * C, E = m->E, F = m->F, H = m->H;
@@ -106,7 +108,7 @@ MsaWorkspace plan_msa_workspace(const esmk_model* m, int B, int R, int C, uint32
     w.q = w.big;
     w.k = w.big + qb;
     w.vt = w.big + 2 * qb;
-    w.row_slices = row_score_slices(B, (int)H, R, C);
+    w.row_slices = row_score_slices(slices_B, (int)H, R, C);
     w.scores = c.take((size_t)w.row_slices * B * H * C * w.Cp * 4);
     w.probs = c.take((size_t)B * H * C * w.Cp * os);
     w.lse = c.take((flags & ESMK_OUT_COL_ATTN) ? (size_t)B * C * H * R * 4 : 0);
@@ -116,6 +118,71 @@ MsaWorkspace plan_msa_workspace(const esmk_model* m, int B, int R, int C, uint32
     w.total = c.off;
     return w;
 }
+
+// Row selection (esmk_msa_forward_rows): the layer stack runs on all B*R*C rows, the head of the model — final LayerNorm, LM
+// head, vocabulary GEMM — on the n_sel gathered rows only, and a log-softmax turns their logits into logprobs_out.
+struct MsaRowSel {
+    const int32_t* sel_dev = nullptr;  // int32 [n_sel] flat indices (b*R + r)*C + c, device data: clamped by the gather kernel
+    int n_sel = 0;
+    float* logprobs_out = nullptr;     // fp32 [n_sel, V]
+    size_t x = 0, h = 0, g32 = 0, logits = 0;  // byte offsets into the workspace
+};
+
+// esmk_msa_forward_rows: the forward's workspace with the slice count of B = 1 (it is never below the count of B: the scores
+// buffer only grows), then the selected rows of the stream (fp32), their operand-dtype rows, the fp32 scratch of the head
+// and the selected logits.  No pad rows: every GEMM kernel clamps its A-row reads to row M - 1.
+size_t plan_msa_rows(const esmk_model* m, int B, int R, int C, int n_sel, MsaRowSel* rs) {
+    Carve c;
+    c.take(plan_msa_workspace(m, B, R, C, ESMK_OUT_LOGITS, 1).total);
+    const size_t n = (size_t)n_sel;
+    rs->x = c.take(n * m->E * 4);
+    rs->h = c.take(n * m->E * op_size(m->cfg.operand_dtype) + 4096);
+    rs->g32 = c.take(n * m->E * 4);
+    rs->logits = c.take(n * m->V * 4);
+    return c.off;
+}
+
+// One call of the MSA forward: the arguments of esmk_msa_forward, or (rs) of esmk_msa_forward_rows
+struct MsaCall {
+    const char* who = "esmk_msa_forward";  // the entry error messages name
+    esmk_model* m = nullptr;
+    const void* packed = nullptr;
+    const int64_t* tokens = nullptr;
+    int B = 0, R = 0, C = 0;
+    const int32_t* repr_layers = nullptr;
+    int n_repr = 0;
+    void* const* repr_out = nullptr;
+    uint32_t flags = 0;
+    void *logits = nullptr, *row_attn = nullptr, *col_attn = nullptr, *contacts = nullptr;
+    void* workspace = nullptr;
+    size_t workspace_bytes = 0;
+    void* stream = nullptr;
+    const MsaRowSel* rs = nullptr;
+};
+
+// the shape limits of both entries (and of the rows entry's workspace query)
+int check_msa_shape(const std::string& w, const esmk_model* m, int B, int R, int C) {
+    if (B <= 0 || R <= 0 || C <= 0) return fail(w + ": B, R, C must be positive");
+    if ((long long)B * R * C > ESMK_MAX_ROWS) return fail(w + ": B*R*C exceeds 2^24 rows");
+    if (R > 1024 && m->has_msa_pos)
+        return fail(w + ": MSA position embedding covers a depth of 1024 alignments");  // msa_transformer.py:160-164
+    if (C > 1024) return fail(w + ": more than 1024 columns are not supported");
+    if (C > m->npos - m->cfg.pad_idx - 1)
+        return fail(w + ": sequence length above the maximum of the positional embedding");  // modules.py:243-247
+    return 0;
+}
+
+int check_msa_rows(const char* who, const esmk_model* m, int B, int R, int C, int n_sel) {
+    const std::string w(who);
+    if (!m->is_msa) return fail(w + ": not an MSA model handle (esmk_forward_rows takes the single-sequence models)");
+    if (check_msa_shape(w, m, B, R, C)) return 1;
+    if (n_sel <= 0) return fail(w + ": n_sel must be positive");
+    if (n_sel > ESMK_MAX_ROWS) return fail(w + ": n_sel exceeds 2^24 rows");
+    if (m->V > 64) return fail(w + ": vocabulary above 64 entries (the log-softmax holds one entry per lane)");
+    return 0;
+}
+
+int msa_forward_impl(const MsaCall& c);
 
 }  // namespace
 
@@ -170,7 +237,7 @@ int esmk_msa_workspace_bytes(const esmk_model* m, int B, int R, int C, uint32_t 
     if (!m || !bytes || !m->is_msa) return fail("esmk_msa_workspace_bytes: not an MSA model handle");
     if (B <= 0 || R <= 0 || C <= 0) return fail("esmk_msa_workspace_bytes: B, R, C must be positive");
     if ((long long)B * R * C > ESMK_MAX_ROWS) return fail("esmk_msa_workspace_bytes: B*R*C exceeds 2^24 rows");
-    *bytes = plan_msa_workspace(m, B, R, C, out_flags).total;
+    *bytes = plan_msa_workspace(m, B, R, C, out_flags, B).total;
     return 0;
 }
 
@@ -178,37 +245,94 @@ int esmk_msa_forward(esmk_model* m, const void* packed_dev, const int64_t* token
                      const int32_t* repr_layers, int n_repr, void* const* repr_out_dev, uint32_t out_flags,
                      void* logits_out_dev, void* row_attn_out_dev, void* col_attn_out_dev,
                      void* contacts_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
-    if (!m || !m->is_msa) return fail("esmk_msa_forward: not an MSA model handle");
-    if (!packed_dev || !tokens_dev || !workspace_dev) return fail("esmk_msa_forward: null argument");
-    if (B <= 0 || R <= 0 || C <= 0) return fail("esmk_msa_forward: B, R, C must be positive");
-    if ((long long)B * R * C > ESMK_MAX_ROWS) return fail("esmk_msa_forward: B*R*C exceeds 2^24 rows");
-    if (R > 1024 && m->has_msa_pos)
-        return fail("esmk_msa_forward: MSA position embedding covers a depth of 1024 alignments");  // msa_transformer.py:160-164
-    if (C > 1024) return fail("esmk_msa_forward: more than 1024 columns are not supported");
-    if (C > m->npos - m->cfg.pad_idx - 1)
-        return fail("esmk_msa_forward: sequence length above the maximum of the positional embedding");  // modules.py:243-247
+    MsaCall c;
+    c.m = m, c.packed = packed_dev, c.tokens = tokens_dev, c.B = B, c.R = R, c.C = C;
+    c.repr_layers = repr_layers, c.n_repr = n_repr, c.repr_out = repr_out_dev;
+    c.flags = out_flags, c.logits = logits_out_dev, c.row_attn = row_attn_out_dev, c.col_attn = col_attn_out_dev;
+    c.contacts = contacts_out_dev;
+    c.workspace = workspace_dev, c.workspace_bytes = workspace_bytes, c.stream = stream;
+    return msa_forward_impl(c);
+}
+
+// ---- variant scoring with the MSA Transformer: log-probabilities of selected rows (predict.py:161-184) ----
+int esmk_msa_rows_workspace_bytes(const esmk_model* m, int B, int R, int C, int n_sel, size_t* bytes, size_t* logits_offset) {
+    if (!m || !bytes) return fail("esmk_msa_rows_workspace_bytes: null argument");
+    if (check_msa_rows("esmk_msa_rows_workspace_bytes", m, B, R, C, n_sel)) return 1;
+    MsaRowSel rs;
+    *bytes = plan_msa_rows(m, B, R, C, n_sel, &rs);
+    if (logits_offset) *logits_offset = rs.logits;
+    return 0;
+}
+
+int esmk_msa_forward_rows(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev, int B, int R, int C,
+                          const int32_t* sel_rows_dev, int n_sel, float* logprobs_out_dev, void* workspace_dev,
+                          size_t workspace_bytes, void* stream) {
+    if (!m || !packed_dev || !tokens_dev || !sel_rows_dev || !logprobs_out_dev || !workspace_dev)
+        return fail("esmk_msa_forward_rows: null argument");
+    if (check_msa_rows("esmk_msa_forward_rows", m, B, R, C, n_sel)) return 1;
+    MsaRowSel rs;
+    if (workspace_bytes < plan_msa_rows(m, B, R, C, n_sel, &rs)) return fail("esmk_msa_forward_rows: workspace too small");
+    rs.sel_dev = sel_rows_dev;
+    rs.n_sel = n_sel;
+    rs.logprobs_out = logprobs_out_dev;
+    MsaCall c;
+    c.who = "esmk_msa_forward_rows";
+    c.m = m, c.packed = packed_dev, c.tokens = tokens_dev, c.B = B, c.R = R, c.C = C;
+    c.flags = ESMK_OUT_LOGITS, c.logits = (char*)workspace_dev + rs.logits;
+    c.workspace = workspace_dev, c.workspace_bytes = workspace_bytes, c.stream = stream;
+    c.rs = &rs;
+    return msa_forward_impl(c);
+}
+
+int esmk_debug_msa_row_slices(const esmk_model* m, int B, int R, int C, int rows_entry, int32_t* slices) {
+    if (!m || !slices || !m->is_msa) return fail("esmk_debug_msa_row_slices: not an MSA model handle");
+    if (check_msa_shape("esmk_debug_msa_row_slices", m, B, R, C)) return 1;
+    *slices = plan_msa_workspace(m, B, R, C, ESMK_OUT_LOGITS, rows_entry ? 1 : B).row_slices;
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The implementation of both entries: argument checks under the caller's name, then the launch sequence.  Whatever the
+// entry, copy b of the batch goes through the same kernels; what the rows entry changes is the slice count of the tied-score
+// GEMM (pinned to B = 1) and the rows the head of the model runs on.
+int msa_forward_impl(const MsaCall& c) {
+    esmk_model* m = c.m;
+    const std::string who(c.who);
+    const int B = c.B, R = c.R, C = c.C;
+    const uint32_t out_flags = c.flags;
+    const int32_t* repr_layers = c.repr_layers;
+    const int n_repr = c.n_repr;
+    void* const* repr_out_dev = c.repr_out;
+    const int64_t* tokens_dev = c.tokens;
+    void *row_attn_out_dev = c.row_attn, *col_attn_out_dev = c.col_attn, *contacts_out_dev = c.contacts;
+    if (!m || !m->is_msa) return fail(who + ": not an MSA model handle");
+    if (!c.packed || !tokens_dev || !c.workspace) return fail(who + ": null argument");
+    if (check_msa_shape(who, m, B, R, C)) return 1;
     if (out_flags & (ESMK_OUT_REPR_LOWP | ESMK_OUT_ATTN_LOWP))
-        return fail("esmk_msa_forward: outputs are fp32 (ESMK_OUT_*_LOWP is an esmk_forward flag)");
+        return fail(who + ": outputs are fp32 (ESMK_OUT_*_LOWP is an esmk_forward flag)");
     const bool want_logits = out_flags & ESMK_OUT_LOGITS;
     const bool want_contacts = out_flags & ESMK_OUT_CONTACTS;
     const bool want_attn = (out_flags & ESMK_OUT_ATTN) || want_contacts;
-    if (want_logits && !logits_out_dev) return fail("esmk_msa_forward: logits buffer missing");
-    if (want_attn && !row_attn_out_dev) return fail("esmk_msa_forward: row attention buffer missing");
-    if (want_contacts && !contacts_out_dev) return fail("esmk_msa_forward: contacts buffer missing");
+    if (want_logits && !c.logits) return fail(who + ": logits buffer missing");
+    if (want_attn && !row_attn_out_dev) return fail(who + ": row attention buffer missing");
+    if (want_contacts && !contacts_out_dev) return fail(who + ": contacts buffer missing");
     const bool want_col = out_flags & ESMK_OUT_COL_ATTN;
-    if (want_col && !col_attn_out_dev) return fail("esmk_msa_forward: column attention buffer missing");
+    if (want_col && !col_attn_out_dev) return fail(who + ": column attention buffer missing");
     for (int i = 0; i < n_repr; ++i)
         if (repr_layers[i] < 0 || repr_layers[i] > m->L || !repr_out_dev[i])
-            return fail("esmk_msa_forward: bad repr layer request");
-    const MsaWorkspace w = plan_msa_workspace(m, B, R, C, out_flags);
-    if (workspace_bytes < w.total) return fail("esmk_msa_forward: workspace too small");
+            return fail(who + ": bad repr layer request");
+    const MsaWorkspace w = plan_msa_workspace(m, B, R, C, out_flags, c.rs ? 1 : B);
+    if (c.workspace_bytes < w.total) return fail(who + ": workspace too small");
 
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)c.stream;
     const int op = m->cfg.operand_dtype;
     const size_t os = op_size(op);
     const int N = B * R * C, E = m->E, F = m->F, H = m->H, L = m->L, Cp = w.Cp, Rp = w.Rp;
-    char* ws = (char*)workspace_dev;
-    const char* pk = (const char*)packed_dev;
+    char* ws = (char*)c.workspace;
+    const char* pk = (const char*)c.packed;
     float* keep = (float*)(ws + w.keep);
     float* col_fill = (float*)(ws + w.col_fill);
     int* any_pad = (int*)(ws + w.any_pad);
@@ -382,7 +506,22 @@ int esmk_msa_forward(esmk_model* m, const void* packed_dev, const int64_t* token
     }
 
     // msa_transformer.py:200-206: final LayerNorm (representation L is the normalised stream), LM head
-    if (lm_head(s, N, x, h, g32, E, LnExtra(), false, want_logits, logits_out_dev)) return 1;
+    // The head runs on the rows it is asked for: all N of them, or (rows entry) the selection gathered out of the final stream.
+    // Every kernel of the head computes a row from that row alone: a selected row carries the bits esmk_msa_forward gives it.
+    if (const MsaRowSel* rs = c.rs) {
+        const int rows = rs->n_sel;
+        float* rx = (float*)(ws + rs->x);
+        {
+            ProfScope ps(m, st, PC_COPY, 0, 8.0 * rows * E);
+            ESMK_TRY(launch_gather_rows(x, rs->sel_dev, rx, N, E, rows, st));
+        }
+        if (lm_head(s, rows, rx, ws + rs->h, (float*)(ws + rs->g32), E, LnExtra(), false, true, c.logits)) return 1;
+        // torch.log_softmax(logits, dim=-1) of the selected rows (counted under "lm_head_logits", the gather under "repr_copy")
+        ProfScope ps(m, st, PC_LM_LOGITS, 0, 8.0 * rows * m->V);
+        ESMK_TRY(launch_log_softmax_rows((const float*)c.logits, rs->logprobs_out, nullptr, nullptr, rows, m->V, st));
+        return 0;
+    }
+    if (lm_head(s, N, x, h, g32, E, LnExtra(), false, want_logits, c.logits)) return 1;
     if (want_contacts) {  // msa_transformer.py:215-217 -> modules.py:338-357 on the row attentions
         // the contact head reads tokens only for the <eos> mask, which the MSA alphabet does not append
         ProfScope ps(m, st, PC_CONTACTS, 0, 2.0 * 4 * B * (double)L * H * C * C);
@@ -394,4 +533,4 @@ int esmk_msa_forward(esmk_model* m, const void* packed_dev, const int64_t* token
     return 0;
 }
 
-}  // extern "C"
+}  // namespace

@@ -95,3 +95,24 @@ def read_alignment_lines(lines, keep_gaps=True, keep_insertions=True, to_upper=F
 def read_fasta(path, keep_gaps=True, keep_insertions=True, to_upper=False):
     with open(path, "r") as fh:
         yield from read_alignment_lines(fh, keep_gaps=keep_gaps, keep_insertions=keep_insertions, to_upper=to_upper)
+
+
+_A3M_INSERTIONS = str.maketrans("", "", "abcdefghijklmnopqrstuvwxyz.*")
+
+
+def read_msa(path, nseq):
+    """The first ``nseq`` records of an a3m file as ``[(description, aligned sequence)]``, with the insertions relative to the
+    query removed: lowercase letters, '.' and '*' are deleted, so every row has the query's number of columns (what
+    ``read_msa`` / ``remove_insertions`` of the reference's examples/variant-prediction/predict.py:21-42 return).  Only the
+    first ``nseq`` records are parsed; text in front of the first header (a comment line) is dropped, as a FASTA parser does."""
+    import itertools
+
+    msa = []
+    if nseq <= 0:
+        return msa
+    with open(path, "r") as fh:
+        for _, head, body in _iter_records(itertools.dropwhile(lambda line: not line.startswith(">"), fh)):
+            msa.append((head.strip(), "".join(part.strip() for part in body).translate(_A3M_INSERTIONS)))
+            if len(msa) == nseq:
+                break
+    return msa

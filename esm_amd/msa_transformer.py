@@ -122,6 +122,12 @@ class _MsaEngine:
                                            N.ptr(t), N.dtype_code(t.dtype), shape, t.dim(), stream))
         self.fingerprint = fp
 
+    def workspace_for_bytes(self, n):
+        if self.workspace is None or self.workspace.numel() < n:
+            self.workspace = None
+            self.workspace = torch.empty(n, dtype=torch.uint8, device=self.device)
+        return self.workspace
+
     def workspace_for(self, B, R, C, flags):
         N = self.N
         need = ctypes.c_size_t()
@@ -262,7 +268,7 @@ class MSATransformer(nn.Module):
     def predict_contacts(self, tokens):
         return self(tokens, return_contacts=True)["contacts"]
 
-    supports_scoring = False  # esmk_forward_rows takes single-sequence models only
+    supports_scoring = False  # esmk_forward_rows takes single-sequence models only; MSAs: the msa_* methods below
 
     def masked_marginals(self, tokens, positions=None, chunk=None):
         from . import scoring
@@ -277,6 +283,34 @@ class MSATransformer(nn.Module):
         scoring._refuse_msa(self)
 
     score_variants = masked_joint
+
+    # Variant scoring of one MSA (esm_amd/msa_scoring.py over esmk_msa_forward_rows): an MSA plus a query row is another
+    # argument shape than a batch of sequences, hence names of their own; the single-sequence names above keep refusing
+    def msa_forward_rows(self, tokens, sel_rows, return_logits=False):
+        from . import msa_scoring
+
+        return msa_scoring.msa_forward_rows(self, tokens, sel_rows, return_logits=return_logits)
+
+    def msa_masked_marginals(self, tokens, positions=None, row=0, chunk=None):
+        from . import msa_scoring
+
+        return msa_scoring.msa_masked_marginals(self, tokens, positions=positions, row=row, chunk=chunk)
+
+    def msa_wt_marginals(self, tokens, row=0):
+        from . import msa_scoring
+
+        return msa_scoring.msa_wt_marginals(self, tokens, row=row)
+
+    def msa_masked_joint(self, tokens, position_sets, row=0, chunk=None, return_logits=False):
+        from . import msa_scoring
+
+        return msa_scoring.msa_masked_joint(self, tokens, position_sets, row=row, chunk=chunk, return_logits=return_logits)
+
+    def msa_score_variants(self, alphabet, msa, variants, strategy="masked-marginals", offset_idx=0, sep=":", chunk=None):
+        from . import msa_scoring
+
+        return msa_scoring.msa_score_variants(self, alphabet, msa, variants, strategy=strategy, offset_idx=offset_idx, sep=sep,
+                                              chunk=chunk)
 
     def profile_begin(self):
         """Arm per-kernel-class HIP-event timing of the following forward calls (bench.py --workload msa1b)."""

@@ -19,7 +19,8 @@ masked-marginal score of the ESM-1v paper: all of its positions masked in one fo
 over them (``esm_amd.scoring.score_variants``); wt-marginals sums the same terms from the wild-type table, pseudo-ppl scores
 the sequence with all substitutions made.  A table without the separator is scored exactly as before.
 
-The MSA Transformer (``--msa-path``) is not served by the engine's scoring path: asking for it is an error.
+The MSA Transformer (``--msa-path``) is not served here: asking for it is an error that points to
+``python -m esm_amd.predict_msa``, which scores a table with an MSA (``esm_amd.msa_scoring``).
 """
 import argparse
 import csv
@@ -43,7 +44,7 @@ def create_parser():
     p.add_argument("--offset-idx", type=int, default=0, help="index of the first residue in the mutation column's numbering")
     p.add_argument("--scoring-strategy", type=str, default="wt-marginals", choices=STRATEGIES)
     p.add_argument("--msa-path", type=pathlib.Path, default=None,
-                   help="(MSA Transformer only; not supported by the engine's scoring path)")
+                   help="(MSA Transformer only; not served here: use python -m esm_amd.predict_msa)")
     p.add_argument("--msa-samples", type=int, default=400, help="(MSA Transformer only)")
     p.add_argument("--nogpu", action="store_true", help="accepted for compatibility; the engine has no CPU path")
     return p
@@ -111,7 +112,8 @@ def main(argv=None):
     args = create_parser().parse_args(argv)
     if args.msa_path is not None:
         raise SystemExit("esm_amd.predict: the MSA Transformer (--msa-path) is not supported: the engine's scoring path "
-                         "(esmk_forward_rows) takes ESM-2, ESM-1b / ESM-1v and ESM-1 models")
+                         "(esmk_forward_rows) takes ESM-2, ESM-1b / ESM-1v and ESM-1 models; score a table with an MSA through "
+                         "python -m esm_amd.predict_msa")
     import torch
 
     from . import pretrained
@@ -122,7 +124,8 @@ def main(argv=None):
     for location in args.model_location:
         model, alphabet = pretrained.load_model_and_alphabet(location)
         if isinstance(model, MSATransformer):
-            raise SystemExit(f"esm_amd.predict: {location} is an MSA Transformer, which the engine's scoring path does not serve")
+            raise SystemExit(f"esm_amd.predict: {location} is an MSA Transformer, which the engine's scoring path does not serve here: "
+                             "use python -m esm_amd.predict_msa")
         if not torch.cuda.is_available():
             raise SystemExit("esm_amd.predict: no GPU: the engine has no CPU path")
         model = model.eval().cuda()

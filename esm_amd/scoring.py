@@ -14,8 +14,9 @@ positions of the variant are masked in one forward (``masked_joint``, ``esmk_op_
 log p(mutant) - log p(wild type) is summed over them (``score_variants``, ``esmk_op_score_rows``: fp32 terms added in fp64
 in a fixed order).
 
-The functions are also methods of ``ESM2`` / ``ProteinBertModel`` (``model.masked_marginals(tokens)`` ...).  The MSA
-Transformer has no row-selected forward: its methods raise ``NotImplementedError``.
+The functions are also methods of ``ESM2`` / ``ProteinBertModel`` (``model.masked_marginals(tokens)`` ...).  They refuse the
+MSA Transformer (``NotImplementedError``): one MSA plus a query row is another argument shape, served by
+``esm_amd.msa_scoring`` under names of its own.
 """
 import ctypes
 import numbers
@@ -31,7 +32,8 @@ def _refuse_msa(model):
     if isinstance(model, MSATransformer):
         raise NotImplementedError(
             "esm_amd.scoring: the MSA Transformer has no row-selected forward on the MI355X engine (esmk_forward_rows takes "
-            "ESM-2, ESM-1b / ESM-1v and ESM-1 models); masked marginals of an MSA are the reference's loop over model.forward")
+            "ESM-2, ESM-1b / ESM-1v and ESM-1 models) under the single-sequence names; one MSA plus a query row is scored by "
+            "esm_amd.msa_scoring (msa_masked_marginals, msa_wt_marginals, msa_masked_joint, msa_score_variants)")
 
 
 def _device_tokens(model, tokens):

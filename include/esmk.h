@@ -269,6 +269,37 @@ int esmk_msa_forward(esmk_model* m, const void* packed_dev, const int64_t* token
                      void* logits_out_dev, void* row_attn_out_dev, void* col_attn_out_dev,
                      void* contacts_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- variant scoring with the MSA Transformer: log-probabilities of selected rows (predict.py:161-184) -------
+ * The reference masks position i of the first row of an MSA, runs one forward of the whole MSA per column at B = 1 and keeps
+ * log_softmax(logits)[0, 0, i].  Here the caller runs the masked copies of the MSA as ONE batch [B,R,C] and names the rows it
+ * wants, as esmk_forward_rows does for the single-sequence models: the layer stack of esmk_msa_forward runs on all B*R*C
+ * rows; the final LayerNorm, the LM head and the vocabulary GEMM run on the n_sel selected rows only, and their log-softmax
+ * is written.  No [B,R,C,V] tensor exists.
+ *   tokens_dev       int64 [B,R,C]
+ *   sel_rows_dev     int32 [n_sel] on the DEVICE, flat indices (b*R + r)*C + c in any order, repeats allowed.  Not validated
+ *                    on the host: the gather clamps each index to [0, B*R*C), so a wrong index reads a valid row
+ *   logprobs_out_dev fp32 [n_sel, V]
+ *   workspace        esmk_msa_rows_workspace_bytes(m, B, R, C, n_sel, &bytes, &logits_offset); after the call the selected
+ *                    logits (fp32 [n_sel, V]) stay at byte offset *logits_offset of the workspace (logits_offset may be NULL)
+ * The slice pin: esmk_msa_forward cuts the tied-row score contraction over the R rows into a number of K slices that it
+ * chooses from B (more slices where few output tiles would leave compute units idle), and the row softmax adds the partial
+ * maps in slice order — so the summation order of a copy's scores depends on the batch it runs in.  This entry always takes
+ * the slice count of B = 1 (its workspace holds the score maps of that count): copy b of the batch is computed with the
+ * launches and the summation order of esmk_msa_forward at B = 1 on that copy, and a selected row carries the bits of that
+ * forward whatever B is.  esmk_msa_forward keeps its own choice.  The guarantee is for a batch of masked copies of ONE MSA
+ * (the pad flag of the attention kernels is one per batch).  The price is workspace: the fp32 score maps take
+ * S(1)*B*H*C*Cp*4 bytes, where esmk_msa_forward takes S(B) of them — up to 8 x its buffer at a large B on a small MSA (S(1) <= 8,
+ * S(B) falls to 1 once B*H*ceil(C/256)^2 tiles fill the GPU); ask esmk_msa_rows_workspace_bytes, not esmk_msa_workspace_bytes.
+ * vocab <= 64, MSA handles only (esmk_forward_rows serves the single-sequence models), the shape limits of
+ * esmk_msa_forward.  The whole call runs on `stream`; error messages name esmk_msa_forward_rows. */
+int esmk_msa_rows_workspace_bytes(const esmk_model* m, int B, int R, int C, int n_sel, size_t* bytes, size_t* logits_offset);
+int esmk_msa_forward_rows(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev, int B, int R, int C,
+                          const int32_t* sel_rows_dev, int n_sel, float* logprobs_out_dev, void* workspace_dev,
+                          size_t workspace_bytes, void* stream);
+/* The number of K slices the workspace plan of an MSA forward takes for the tied-row score GEMM (no GPU needed):
+ * rows_entry 0 = esmk_msa_forward at this B, 1 = esmk_msa_forward_rows (the count of B = 1, whatever B is). */
+int esmk_debug_msa_row_slices(const esmk_model* m, int B, int R, int C, int rows_entry, int32_t* slices);
+
 /* Per-kernel-class timing of esmk_forward with HIP events recorded on the launch stream
  * (measurement support for bench.py; the reference has no counterpart).
  * esmk_profile_begin() arms it; every launch of the following esmk_forward() calls is bracketed

@@ -6,6 +6,7 @@ batches that fill the GPU, the head of the model on the one masked row of every 
 
   python tools/score_throughput.py [--model 650M] [--lengths 510 1020] [--rounds 5] [--out profiles/scoring_throughput.log]
   python tools/score_throughput.py --variants 512 [--lengths 510] --out profiles/scoring_variants.log
+  python tools/score_throughput.py --msa [--msa-shapes 16x257 400x301] --out profiles/msa_scoring_throughput.log
 
 Same library and same process for both sides; one warm-up of each side per shape, then --rounds timed rounds alternating the
 two sides, each round ending in a device synchronise; medians and the spread.  Residues/s counts the scored positions (all T
@@ -17,6 +18,13 @@ masked-marginal score of the ESM-1v paper (both positions masked in one forward,
 ``model.score_variants`` (joint masks built on the device, batches that fill the GPU, the head on the masked rows, the sums
 by ``esmk_op_score_rows``) against what a user had before it: one B = 1 ``model.forward`` per distinct position set,
 log_softmax of its logits, the two rows kept, the terms summed on the host.  Variants/s counts the scored table rows.
+
+--msa: masked marginals of the first row of one MSA with the MSA Transformer (dimensions of esm_msa1b_t12_100M):
+``model.msa_masked_marginals`` (esm_amd/msa_scoring.py: masked copies of the MSA batched until the GPU is full, the head on
+the one masked cell of every copy) against the reference's MSA loop (predict.py:167-178) on the same model's ``forward``: C
+forwards at B = 1, each building [1, R, C, V] logits and keeping one cell.  Two shapes R x C: a shallow MSA, where batching
+should pay, and a deep one at the reference's default scale (--msa-samples 400), where one copy already fills the GPU and
+what remains is the smaller head and the logits tensor that is not built.
 """
 import argparse
 import os
@@ -155,6 +163,75 @@ def masks_mode(args, model):
     return lines
 
 
+def msa_loop_rows(model, toks):
+    """The reference's MSA loop: one B = 1 forward of the whole MSA per column, log_softmax of its logits, one cell kept."""
+    rows = []
+    for i in range(toks.shape[2]):
+        masked = toks.clone()
+        masked[0, 0, i] = model.mask_idx
+        rows.append(torch.log_softmax(model(masked)["logits"], dim=-1)[:, 0, i])
+    return torch.cat(rows, dim=0)
+
+
+def msa_mode(args):
+    """--msa: the lines of the report, one block per shape."""
+    from esm_amd.scoring import CHUNK_TOKENS
+    from esm_amd.synth import MSA_DIMS, synth_msa_state_dict, synth_msa_tokens
+
+    name = "esm_msa1b_t12_100M_UR50S"
+    L, E, H, F = MSA_DIMS[name]
+    margs = argparse.Namespace(layers=L, embed_dim=E, ffn_embed_dim=F, attention_heads=H, dropout=0.1, attention_dropout=0.1,
+                               activation_dropout=0.1, max_positions=1024, embed_positions_msa=True, embed_positions_msa_dim=E,
+                               max_tokens=2 ** 14, max_tokens_per_msa=2 ** 14)
+    with skip_param_init():
+        model = esm.MSATransformer(margs, esm.Alphabet.from_architecture("msa_transformer")).eval()
+    model.load_state_dict(synth_msa_state_dict(L, E, H, F, seed=0))
+    model = model.cuda()
+    V = model.alphabet_size
+    lines = ["%s (L %d, E %d, H %d) on %s; %d rounds after one warm-up, medians [min .. max]" % (
+        name, L, E, H, torch.cuda.get_device_name(0), args.rounds)]
+    with torch.no_grad():
+        for shape in args.msa_shapes:
+            R, C = (int(v) for v in shape.lower().split("x"))
+            toks = synth_msa_tokens(1, R, C, seed=R).cuda()
+            sides = {"loop": lambda: msa_loop_rows(model, toks), "msa_masked_marginals": lambda: model.msa_masked_marginals(toks)}
+            ws = {}
+            for side, fn in sides.items():  # warm-up; the workspace each side grows to, from an engine without one
+                if model._engine is not None:
+                    model._engine.workspace = None
+                ref = fn()
+                ws[side] = model._engine.workspace.numel()
+                sides[side] = (fn, ref)
+            same = torch.equal(sides["loop"][1], sides["msa_masked_marginals"][1])
+            diff = (sides["loop"][1].double() - sides["msa_masked_marginals"][1].double()).abs().max().item()
+            times = {side: [] for side in sides}
+            for _ in range(args.rounds):
+                for side, (fn, _) in sides.items():
+                    times[side].append(timed(fn)[0])
+            med = {side: statistics.median(t) for side, t in times.items()}
+            chunk = max(1, CHUNK_TOKENS // (R * C))
+            # logits + log-probabilities written over the whole MSA: C forwards of [R, C, V] logits and their log_softmax
+            # against C rows of logits and log-probabilities (and the table they are scattered into)
+            out_bytes = {"loop": C * R * C * V * 4 * 2, "msa_masked_marginals": C * V * 4 * 3}
+            lines.append("MSA %d x %d (%d tokens), chunk %d copies per forward" % (R, C, R * C, chunk))
+            for side in sides:
+                lines.append("  %-21s %9.1f ms [%.1f .. %.1f]  %8.1f columns/s   workspace %8.1f MiB   logits + log-prob bytes %10.2f MiB" % (
+                    side, 1e3 * med[side], 1e3 * min(times[side]), 1e3 * max(times[side]), C / med[side], ws[side] / 2 ** 20,
+                    out_bytes[side] / 2 ** 20))
+            spread = {side: max(t) - min(t) for side, t in times.items()}
+            extra = med["msa_masked_marginals"] - med["loop"]
+            lines.append("  ratio loop / msa_masked_marginals: %.2f x; msa_masked_marginals - loop = %+.1f ms; spread (max - min) of the "
+                         "%d rounds: loop %.1f ms, msa_masked_marginals %.1f ms; tables %s (max |difference| %.3e)" % (
+                             med["loop"] / med["msa_masked_marginals"], 1e3 * extra, args.rounds, 1e3 * spread["loop"],
+                             1e3 * spread["msa_masked_marginals"], "bit-identical" if same else "DIFFER", diff))
+            # the gate of a shape where one copy fills the GPU: not slower than the loop by more than the rounds scatter
+            bound = max(spread.values())
+            lines.append("  verdict: msa_masked_marginals is %s (%+.1f ms against a spread of %.1f ms, the larger of the two sides)" % (
+                "NOT SLOWER than the loop beyond the spread of the rounds" if extra <= bound
+                else "SLOWER than the loop by more than the spread of the rounds", 1e3 * extra, 1e3 * bound))
+    return lines
+
+
 def timed(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -171,6 +248,9 @@ def main():
     ap.add_argument("--variants", type=int, default=0, metavar="N",
                     help="score N random double mutants of one protein: model.score_variants against one B = 1 forward per "
                          "distinct position set")
+    ap.add_argument("--msa", action="store_true",
+                    help="MSA Transformer (100M dims): model.msa_masked_marginals against one B = 1 forward per column")
+    ap.add_argument("--msa-shapes", nargs="+", default=["16x257", "400x301"], metavar="RxC", help="MSA depth x columns (with <cls>)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -178,6 +258,8 @@ def main():
         args.lengths = [510] if args.variants else [510, 1020]
     if not torch.cuda.is_available():
         raise SystemExit("score_throughput: needs the GPU (a CPU run measures nothing)")
+    if args.msa:
+        return report(msa_mode(args), args.out)
     name = next(k for k in ESM2_DIMS if args.model in k)
     L, E, H = ESM2_DIMS[name]
     with skip_param_init():
@@ -189,11 +271,15 @@ def main():
     lines = ["%s (L %d, E %d, H %d) on %s; LayerNorm fold %s; %d rounds after one warm-up, medians [min .. max]" % (
         name, L, E, H, torch.cuda.get_device_name(0), "on" if model.ln_fold_active() else "off", args.rounds)]
     lines += variants_mode(args, model) if args.variants else masks_mode(args, model)
+    report(lines, args.out)
+
+
+def report(lines, out):
     text = "\n".join(lines)
     print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as fh:
             fh.write(text + "\n")
 
 
