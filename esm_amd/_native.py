@@ -236,6 +236,26 @@ SIGNATURES = {
     "esmk_op_mask_rows_multi": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "esmk_op_score_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    # the token front end, one launch at a time (tests/test_frontend_ops_gpu.py); segment tables are host arrays
+    "esmk_op_seq_stats": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "esmk_op_packed_stats": (
+        c_int, [c_void_p, POINTER(c_int32), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                c_void_p]),
+    "esmk_op_zero_gap_rows": (c_int, [c_void_p, POINTER(c_int32), c_int, c_int, c_size_t, c_void_p]),
+    "esmk_op_embed": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "esmk_op_embed_esm1": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                c_void_p]),
+    "esmk_op_add_positions": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_int32), c_int, c_int, c_void_p]),
+    "esmk_op_scale_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "esmk_op_msa_embed": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                c_int, c_int, c_int, c_void_p]),
+    "esmk_op_sinus_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "esmk_op_rope_table": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "esmk_op_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "esmk_op_contacts": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

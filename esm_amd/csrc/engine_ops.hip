@@ -860,6 +860,178 @@ int esmk_op_log_softmax_rows(const float* logits_dev, float* out_dev, const int3
     return 0;
 }
 
+// ---- the token front end as single ops (tests/test_frontend_ops_gpu.py) -------------------------------------------
+// Validation of what the engines guarantee their own calls, then the launchers of embed_stage (engine.hip), msa_embed_stage
+// (engine_msa.hip), ensure_rope / ensure_sinus and the row gather of the scoring paths.  Segment tables arrive as host arrays
+// and are checked with check_seg_table (lead_gap = false: the rules of esmk_forward_packed), uploaded, used and freed.
+namespace {
+constexpr long long kDynLdsDefault = 64 * 1024;  // dynamic LDS a kernel may ask for without hipFuncSetAttribute
+constexpr long long kMaxIndex = 0x7fffffffLL - 256;  // int element indices of the kernels, rounded up to a workgroup
+
+int bad_width(const std::string& w, const char* name, int E) {
+    if (E <= 0 || E % 4 != 0) return fail(w + ": " + name + " must be a positive multiple of 4");
+    return 0;
+}
+// (T + 4) ints of dynamic LDS: the position scan of add_positions_kernel / msa_embed_kernel
+int bad_scan_row(const std::string& w, const char* name, int T, int D, int pad_idx, int npos) {
+    if (npos <= 0 || pad_idx < 0) return fail(w + ": npos must be positive and pad_idx must not be negative");
+    if (((long long)T + 4) * 4 > kDynLdsDefault)
+        return fail(w + ": " + name + " needs (" + name + " + 4) * 4 bytes of dynamic LDS, above the default limit of 64 KiB");
+    if (T > npos - pad_idx - 1) return fail(w + ": sequence length above the maximum of the positional embedding");
+    if ((long long)T * (D / 4) > kMaxIndex) return fail(w + ": " + name + " * width / 4 exceeds 2^31");
+    return 0;
+}
+int check_op_segments(const std::string& w, const int32_t* seg, int n_seg, int rows, SegTableInfo* info) {
+    if (!seg) return fail(w + ": null segment table");
+    return check_seg_table(w, seg, n_seg, rows, false, info);
+}
+int upload_segments(const int32_t* seg, int n_seg, DevBuf* d) {
+    ESMK_TRY(hipMalloc(&d->p, (size_t)2 * n_seg * 4));
+    ESMK_TRY(hipMemcpy(d->p, seg, (size_t)2 * n_seg * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+}  // namespace
+
+int esmk_op_seq_stats(const int64_t* tokens_dev, int B, int T, int pad_idx, int mask_idx, int token_dropout, float* scale_dev,
+                      float* key_bias_dev, int32_t* seq_info_dev, float* keep_dev, void* stream) {
+    if (!tokens_dev || !scale_dev || !key_bias_dev || !seq_info_dev) return fail("esmk_op_seq_stats: null argument");
+    if (B <= 0 || T <= 0) return fail("esmk_op_seq_stats: B and T must be positive");
+    if ((long long)B * T > ESMK_MAX_ROWS) return fail("esmk_op_seq_stats: B*T exceeds 2^24 rows");
+    ESMK_TRY(launch_seq_stats(tokens_dev, B, T, pad_idx, mask_idx, token_dropout, scale_dev, key_bias_dev, seq_info_dev,
+                              (hipStream_t)stream, keep_dev));
+    return 0;
+}
+
+int esmk_op_packed_stats(const int64_t* tokens_dev, const int32_t* segments_host, int n_seg, int rows, int pad_idx,
+                         int mask_idx, float* scale_row_dev, float* key_bias_dev, int32_t* row_pos_dev, int32_t* seg_npad_dev,
+                         float* keep_dev, void* stream) {
+    const std::string w("esmk_op_packed_stats");
+    if (!tokens_dev || !scale_row_dev || !key_bias_dev || !row_pos_dev || !seg_npad_dev) return fail(w + ": null argument");
+    SegTableInfo info;
+    if (check_op_segments(w, segments_host, n_seg, rows, &info)) return 1;
+    DevBuf d;
+    if (upload_segments(segments_host, n_seg, &d)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    ESMK_TRY(launch_packed_stats(tokens_dev, (const int*)d.p, n_seg, rows, pad_idx, mask_idx, scale_row_dev, key_bias_dev,
+                                 row_pos_dev, seg_npad_dev, st, keep_dev));
+    ESMK_TRY(hipStreamSynchronize(st));  // the table is freed on return
+    return 0;
+}
+
+int esmk_op_zero_gap_rows(void* buf_dev, const int32_t* segments_host, int n_seg, int rows, size_t row_bytes, void* stream) {
+    const std::string w("esmk_op_zero_gap_rows");
+    if (!buf_dev) return fail(w + ": null argument");
+    if (row_bytes == 0 || row_bytes % 16 != 0 || row_bytes > 0x7fffffff)
+        return fail(w + ": row_bytes must be a positive multiple of 16 (below 2^31)");
+    SegTableInfo info;
+    if (check_op_segments(w, segments_host, n_seg, rows, &info)) return 1;
+    DevBuf d;
+    if (upload_segments(segments_host, n_seg, &d)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    ESMK_TRY(launch_zero_gap_rows(buf_dev, (const int*)d.p, n_seg, rows, row_bytes, st));
+    ESMK_TRY(hipStreamSynchronize(st));  // the table is freed on return
+    return 0;
+}
+
+int esmk_op_embed(const int64_t* tokens_dev, const float* table_dev, const float* scale_dev, float* x_dev, int B, int T, int E,
+                  int vocab, int pad_idx, int mask_idx, int token_dropout, void* stream) {
+    const std::string w("esmk_op_embed");
+    if (!tokens_dev || !table_dev || !x_dev || (token_dropout && !scale_dev)) return fail(w + ": null argument");
+    if (B <= 0 || T <= 0 || vocab <= 0) return fail(w + ": B, T and vocab must be positive");
+    if (bad_width(w, "E", E)) return 1;
+    if ((long long)B * T > ESMK_MAX_ROWS) return fail(w + ": B*T exceeds 2^24 rows");
+    ESMK_TRY(launch_embed(tokens_dev, table_dev, scale_dev, x_dev, B, T, E, vocab, pad_idx, mask_idx, token_dropout,
+                          (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_embed_esm1(const int64_t* tokens_dev, const float* table_dev, const float* scale_dev, const float* sinus_dev,
+                       float* x_dev, int B, int T, int E, int vocab, int pad_idx, int mask_idx, int token_dropout,
+                       float embed_scale, void* stream) {
+    const std::string w("esmk_op_embed_esm1");
+    if (!tokens_dev || !table_dev || !sinus_dev || !x_dev || (token_dropout && !scale_dev)) return fail(w + ": null argument");
+    if (B <= 0 || T <= 0 || vocab <= 0) return fail(w + ": B, T and vocab must be positive");
+    if (bad_width(w, "E", E)) return 1;
+    if ((long long)B * T > ESMK_MAX_ROWS) return fail(w + ": B*T exceeds 2^24 rows");
+    ESMK_TRY(launch_embed_esm1(tokens_dev, table_dev, scale_dev, sinus_dev, x_dev, B, T, E, vocab, pad_idx, mask_idx,
+                               token_dropout, embed_scale, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_add_positions(const int64_t* tokens_dev, const float* pos_emb_dev, float* x_dev, int B, int T, int E, int pad_idx,
+                          int npos, const int32_t* segments_host, int n_seg, int rows, void* stream) {
+    const std::string w("esmk_op_add_positions");
+    if (!tokens_dev || !pos_emb_dev || !x_dev) return fail(w + ": null argument");
+    if (B <= 0 || T <= 0) return fail(w + ": B and T must be positive");
+    if (bad_width(w, "E", E)) return 1;
+    if (bad_scan_row(w, "T", T, E, pad_idx, npos)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    if (segments_host == nullptr) {
+        if (n_seg != 0 || rows != 0) return fail(w + ": n_seg and rows without a segment table");
+        if ((long long)B * T > ESMK_MAX_ROWS) return fail(w + ": B*T exceeds 2^24 rows");
+        ESMK_TRY(launch_add_positions(tokens_dev, pos_emb_dev, x_dev, B, T, E, pad_idx, npos, st));
+        return 0;
+    }
+    SegTableInfo info;
+    if (check_op_segments(w, segments_host, n_seg, rows, &info)) return 1;
+    if (B != n_seg || T < info.max_len)
+        return fail(w + ": the packed form takes B = n_seg and T >= the longest segment (it sizes the LDS scan)");
+    DevBuf d;
+    if (upload_segments(segments_host, n_seg, &d)) return 1;
+    ESMK_TRY(launch_add_positions(tokens_dev, pos_emb_dev, x_dev, n_seg, T, E, pad_idx, npos, st, (const int*)d.p));
+    ESMK_TRY(hipStreamSynchronize(st));  // the table is freed on return
+    return 0;
+}
+
+int esmk_op_scale_rows(float* x_dev, const float* keep_dev, int rows, int E, void* stream) {
+    const std::string w("esmk_op_scale_rows");
+    if (!x_dev || !keep_dev) return fail(w + ": null argument");
+    if (rows <= 0 || rows > ESMK_MAX_ROWS) return fail(w + ": rows must be positive (at most 2^24)");
+    if (bad_width(w, "E", E)) return 1;
+    ESMK_TRY(launch_scale_rows(x_dev, keep_dev, rows, E, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_msa_embed(const int64_t* tokens_dev, const float* tok_emb_dev, const float* pos_emb_dev, const float* msa_pos_dev,
+                      float* x_dev, float* keep_dev, float* col_fill_dev, int32_t* any_pad_dev, int B, int R, int C, int D,
+                      int vocab, int pad_idx, int npos, void* stream) {
+    const std::string w("esmk_op_msa_embed");
+    if (!tokens_dev || !tok_emb_dev || !pos_emb_dev || !x_dev || !keep_dev || !col_fill_dev || !any_pad_dev)
+        return fail(w + ": null argument");
+    if (B <= 0 || R <= 0 || C <= 0 || vocab <= 0) return fail(w + ": B, R, C and vocab must be positive");
+    if (bad_width(w, "D", D)) return 1;
+    if (bad_scan_row(w, "C", C, D, pad_idx, npos)) return 1;
+    if ((long long)B * R * C > ESMK_MAX_ROWS) return fail(w + ": B*R*C exceeds 2^24 rows");
+    ESMK_TRY(launch_msa_embed(tokens_dev, tok_emb_dev, pos_emb_dev, msa_pos_dev, x_dev, keep_dev, col_fill_dev, any_pad_dev, B, R,
+                              C, D, vocab, pad_idx, npos, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_sinus_table(const float* freq_dev, float* table_dev, int T, int half, int pos0, void* stream) {
+    if (!freq_dev || !table_dev) return fail("esmk_op_sinus_table: null argument");
+    if (T <= 0 || half <= 0) return fail("esmk_op_sinus_table: T and half must be positive");
+    if ((long long)T * half > kMaxIndex) return fail("esmk_op_sinus_table: T * half exceeds 2^31");
+    ESMK_TRY(launch_sinus_table(freq_dev, table_dev, T, half, pos0, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_rope_table(const float* inv_freq_dev, float* cos_dev, float* sin_dev, int T, int half, void* stream) {
+    if (!inv_freq_dev || !cos_dev || !sin_dev) return fail("esmk_op_rope_table: null argument");
+    if (T <= 0 || half <= 0) return fail("esmk_op_rope_table: T and half must be positive");
+    if ((long long)T * half > kMaxIndex) return fail("esmk_op_rope_table: T * half exceeds 2^31");
+    ESMK_TRY(launch_rope_table(inv_freq_dev, cos_dev, sin_dev, T, half, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_gather_rows(const float* x_dev, const int32_t* sel_dev, float* out_dev, int N, int E, int n, void* stream) {
+    const std::string w("esmk_op_gather_rows");
+    if (!x_dev || !sel_dev || !out_dev) return fail(w + ": null argument");
+    if (N <= 0 || n <= 0 || N > ESMK_MAX_ROWS || n > ESMK_MAX_ROWS) return fail(w + ": N and n must be positive (at most 2^24)");
+    if (bad_width(w, "E", E)) return 1;
+    ESMK_TRY(launch_gather_rows(x_dev, sel_dev, out_dev, N, E, n, (hipStream_t)stream));
+    return 0;
+}
+
 int esmk_op_contacts(const float* attn_dev, const int64_t* tokens_dev, const float* w_dev,
                      const float* b_dev, float* scratch_dev, float* out_dev, int B, int C, int T,
                      int eos_idx, int prepend_bos, int append_eos, void* stream) {

@@ -506,3 +506,169 @@ def score_rows(logprobs, wt, mt, var_offsets):
     N.check(N.lib.esmk_op_score_rows(N.ptr(logprobs), N.ptr(wt), N.ptr(mt), N.ptr(var_offsets), N.ptr(out), n_rows, n_var, V,
                                      N.cur_stream()))
     return out
+
+
+# ---- the token front end, one launch at a time (include/esmk.h: esmk_op_seq_stats ... esmk_op_gather_rows) -----------------
+def _out(t, shape, dtype, device):
+    """The caller's output buffer (checked), or a fresh one: callers that look at the memory behind an output pass their own."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _req_cuda(t)
+    n = 1
+    for s in shape:
+        n *= s
+    assert t.dtype == dtype and t.numel() == n, (t.dtype, tuple(t.shape), shape)
+    return t
+
+
+def seq_stats(tokens, pad_idx=1, mask_idx=32, want_keep=True, scale=None, key_bias=None, seq_info=None, keep=None):
+    """Per-sequence statistics of tokens int64 [B,T] (esmk_op_seq_stats): scale fp32 [B] = 1 - n_mask / n_nonpad, key_bias
+    fp32 [B,T] = 0 / -inf, seq_info int32 [B,2] = (#pads, 1 + last non-pad index), keep fp32 [B,T] = 1 - pad (None without
+    want_keep)."""
+    _req_cuda(tokens)
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2
+    B, T = tokens.shape
+    dev = tokens.device
+    scale = _out(scale, (B,), torch.float32, dev)
+    key_bias = _out(key_bias, (B, T), torch.float32, dev)
+    seq_info = _out(seq_info, (B, 2), torch.int32, dev)
+    keep = _out(keep, (B, T), torch.float32, dev) if want_keep else None
+    N.check(N.lib.esmk_op_seq_stats(N.ptr(tokens), B, T, pad_idx, mask_idx, 1, N.ptr(scale), N.ptr(key_bias), N.ptr(seq_info),
+                                    N.ptr(keep), N.cur_stream()))
+    return scale, key_bias, seq_info, keep
+
+
+def packed_stats(tokens, segments, pad_idx=1, mask_idx=32, want_keep=True, scale_row=None, key_bias=None, row_pos=None,
+                 seg_npad=None, keep=None):
+    """The same per segment of a packed row space (esmk_op_packed_stats): tokens int64 [rows], segments [n,2] = (first row,
+    length) on the host -> scale_row, key_bias fp32 [rows], row_pos int32 [rows], seg_npad int32 [n], keep fp32 [rows] or
+    None; rows outside every segment get (1, -inf, 0, 0)."""
+    _req_cuda(tokens)
+    assert tokens.dtype == torch.int64 and tokens.dim() == 1
+    rows, dev = tokens.numel(), tokens.device
+    seg, seg_ptr = _segments_arg(segments)
+    scale_row = _out(scale_row, (rows,), torch.float32, dev)
+    key_bias = _out(key_bias, (rows,), torch.float32, dev)
+    row_pos = _out(row_pos, (rows,), torch.int32, dev)
+    seg_npad = _out(seg_npad, (seg.shape[0],), torch.int32, dev)
+    keep = _out(keep, (rows,), torch.float32, dev) if want_keep else None
+    N.check(N.lib.esmk_op_packed_stats(N.ptr(tokens), seg_ptr, seg.shape[0], rows, pad_idx, mask_idx, N.ptr(scale_row),
+                                       N.ptr(key_bias), N.ptr(row_pos), N.ptr(seg_npad), N.ptr(keep), N.cur_stream()))
+    return scale_row, key_bias, row_pos, seg_npad, keep
+
+
+def zero_gap_rows(buf, segments, rows, row_bytes):
+    """Rows outside every segment of buf (any dtype, at least rows * row_bytes bytes, in place) := 0 (esmk_op_zero_gap_rows)."""
+    _req_cuda(buf)
+    assert buf.numel() * buf.element_size() >= rows * row_bytes
+    seg, seg_ptr = _segments_arg(segments)
+    N.check(N.lib.esmk_op_zero_gap_rows(N.ptr(buf), seg_ptr, seg.shape[0], rows, row_bytes, N.cur_stream()))
+    return buf
+
+
+def embed(tokens, table, scale=None, pad_idx=1, mask_idx=32, token_dropout=True, out=None):
+    """ESM-2 / ESM-1b embedding (esmk_op_embed): tokens int64 [B,T], table fp32 [vocab,E], scale fp32 [B] (seq_stats; with
+    T = 1 the per-row scale of packed_stats) -> fp32 [B,T,E]."""
+    _req_cuda(tokens, table, scale)
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and table.dtype == torch.float32 and table.dim() == 2
+    B, T = tokens.shape
+    vocab, E = table.shape
+    assert scale is None or (scale.dtype == torch.float32 and scale.numel() == B)
+    out = _out(out, (B, T, E), torch.float32, tokens.device)
+    N.check(N.lib.esmk_op_embed(N.ptr(tokens), N.ptr(table), N.ptr(scale), N.ptr(out), B, T, E, vocab, pad_idx, mask_idx,
+                                int(bool(token_dropout)), N.cur_stream()))
+    return out
+
+
+def embed_esm1(tokens, table, sinus, embed_scale, scale=None, pad_idx=1, mask_idx=32, token_dropout=False, out=None):
+    """ESM-1 embedding (esmk_op_embed_esm1): embed_scale * table[tok], token dropout, + sinus[t] (fp32 [>= T, E]) on non-pad
+    tokens -> fp32 [B,T,E]."""
+    _req_cuda(tokens, table, sinus, scale)
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and table.dtype == sinus.dtype == torch.float32
+    B, T = tokens.shape
+    vocab, E = table.shape
+    assert sinus.dim() == 2 and sinus.shape[0] >= T and sinus.shape[1] == E
+    assert scale is None or (scale.dtype == torch.float32 and scale.numel() == B)
+    out = _out(out, (B, T, E), torch.float32, tokens.device)
+    N.check(N.lib.esmk_op_embed_esm1(N.ptr(tokens), N.ptr(table), N.ptr(scale), N.ptr(sinus), N.ptr(out), B, T, E, vocab,
+                                     pad_idx, mask_idx, int(bool(token_dropout)), float(embed_scale), N.cur_stream()))
+    return out
+
+
+def add_positions(tokens, pos_emb, x, pad_idx=1, segments=None, longest=None):
+    """x += the learned positions of ESM-1b (esmk_op_add_positions), in place.  Padded: tokens int64 [B,T], x fp32 [B,T,E].
+    Packed: tokens [rows], x [rows,E], segments [n,2] on the host, longest = the longest segment (default: from the table)."""
+    _req_cuda(tokens, pos_emb, x)
+    assert tokens.dtype == torch.int64 and pos_emb.dtype == x.dtype == torch.float32 and pos_emb.dim() == 2
+    npos, E = pos_emb.shape
+    assert x.numel() == tokens.numel() * E
+    if segments is None:
+        B, T = tokens.shape
+        N.check(N.lib.esmk_op_add_positions(N.ptr(tokens), N.ptr(pos_emb), N.ptr(x), B, T, E, pad_idx, npos, None, 0, 0,
+                                            N.cur_stream()))
+    else:
+        seg, seg_ptr = _segments_arg(segments)
+        T = int(seg[:, 1].max()) if longest is None else longest
+        N.check(N.lib.esmk_op_add_positions(N.ptr(tokens), N.ptr(pos_emb), N.ptr(x), seg.shape[0], T, E, pad_idx, npos,
+                                            seg_ptr, seg.shape[0], tokens.numel(), N.cur_stream()))
+    return x
+
+
+def scale_rows(x, keep):
+    """x fp32 [rows,E] row r *= keep[r], in place (esmk_op_scale_rows)."""
+    _req_cuda(x, keep)
+    assert x.dtype == keep.dtype == torch.float32 and x.dim() == 2 and keep.numel() == x.shape[0]
+    N.check(N.lib.esmk_op_scale_rows(N.ptr(x), N.ptr(keep), x.shape[0], x.shape[1], N.cur_stream()))
+    return x
+
+
+def msa_embed(tokens, tok_emb, pos_emb, msa_pos=None, pad_idx=1, x=None, keep=None, col_fill=None, any_pad=None):
+    """MSA Transformer embedding (esmk_op_msa_embed): tokens int64 [B,R,C], tok_emb fp32 [vocab,D], pos_emb fp32 [npos,D],
+    msa_pos fp32 [>= R, D] or None -> x fp32 [B,R,C,D], keep fp32 [B,R,C], col_fill fp32 [B,C,R], any_pad int32 [1]."""
+    _req_cuda(tokens, tok_emb, pos_emb, msa_pos)
+    assert tokens.dtype == torch.int64 and tokens.dim() == 3 and tok_emb.dtype == pos_emb.dtype == torch.float32
+    B, R, C = tokens.shape
+    vocab, D = tok_emb.shape
+    npos = pos_emb.shape[0]
+    assert pos_emb.shape[1] == D
+    assert msa_pos is None or (msa_pos.dtype == torch.float32 and msa_pos.shape[-1] == D and msa_pos.numel() >= R * D)
+    dev = tokens.device
+    x = _out(x, (B, R, C, D), torch.float32, dev)
+    keep = _out(keep, (B, R, C), torch.float32, dev)
+    col_fill = _out(col_fill, (B, C, R), torch.float32, dev)
+    any_pad = _out(any_pad, (1,), torch.int32, dev)
+    N.check(N.lib.esmk_op_msa_embed(N.ptr(tokens), N.ptr(tok_emb), N.ptr(pos_emb), N.ptr(msa_pos), N.ptr(x), N.ptr(keep),
+                                    N.ptr(col_fill), N.ptr(any_pad), B, R, C, D, vocab, pad_idx, npos, N.cur_stream()))
+    return x, keep, col_fill, any_pad
+
+
+def sinus_table(freq, T, pos0, out=None):
+    """fp32 [T, 2 half]: row t = sin | cos of fp32(pos0 + t) * freq[i] (esmk_op_sinus_table); freq fp32 [half]."""
+    _req_cuda(freq)
+    assert freq.dtype == torch.float32 and freq.dim() == 1
+    half = freq.numel()
+    out = _out(out, (T, 2 * half), torch.float32, freq.device)
+    N.check(N.lib.esmk_op_sinus_table(N.ptr(freq), N.ptr(out), T, half, pos0, N.cur_stream()))
+    return out
+
+
+def rope_table(inv_freq, T, cos=None, sin=None):
+    """(cos, sin) fp32 [T, half] of fp32(t) * inv_freq[i] (esmk_op_rope_table); inv_freq fp32 [half]."""
+    _req_cuda(inv_freq)
+    assert inv_freq.dtype == torch.float32 and inv_freq.dim() == 1
+    half = inv_freq.numel()
+    cos = _out(cos, (T, half), torch.float32, inv_freq.device)
+    sin = _out(sin, (T, half), torch.float32, inv_freq.device)
+    N.check(N.lib.esmk_op_rope_table(N.ptr(inv_freq), N.ptr(cos), N.ptr(sin), T, half, N.cur_stream()))
+    return cos, sin
+
+
+def gather_rows(x, sel, out=None):
+    """fp32 [n,E] = x[clamp(sel, 0, N - 1)] (esmk_op_gather_rows); x fp32 [N,E], sel int32 [n] on the device."""
+    _req_cuda(x, sel)
+    assert x.dtype == torch.float32 and x.dim() == 2 and sel.dtype == torch.int32 and sel.dim() == 1
+    Nr, E = x.shape
+    n = sel.numel()
+    out = _out(out, (n, E), torch.float32, x.device)
+    N.check(N.lib.esmk_op_gather_rows(N.ptr(x), N.ptr(sel), N.ptr(out), Nr, E, n, N.cur_stream()))
+    return out

@@ -640,6 +640,61 @@ int esmk_op_mask_rows_multi(const int64_t* tokens_dev, const int32_t* src_row_de
 int esmk_op_score_rows(const float* logprobs_dev, const int32_t* wt_dev, const int32_t* mt_dev, const int32_t* var_off_dev,
                        double* out_dev, int n_rows, int n_var, int V, void* stream);
 
+/* The token front end — the kernels that turn tokens into the layer-0 activation and into the bookkeeping every later kernel
+ * trusts — one launch at a time (tests/test_frontend_ops_gpu.py).  Validation, then the launchers the engines call.  Refused
+ * before any HIP call: null pointers (the ones named optional below may be NULL), B, T, R, C, n, rows, N, vocab or npos <= 0,
+ * E / D not a positive multiple of 4, a bad segment table.  Segment tables (segments_host int32 [n_seg][2] = (first row,
+ * length)) follow the rules of esmk_forward_packed — rows % 64 == 0, the first segment starts at row 0, starts ascending
+ * multiples of 16, segments disjoint, lengths > 0, inside rows — and are host arrays: the entry uploads them, waits for the
+ * stream and frees the copy.
+ * esmk_op_seq_stats (esm2.py:82,86-92,108-109; multihead_attention.py:368-374): tokens int64 [B,T] -> scale fp32 [B] =
+ *   1 - n_mask / n_nonpad (NaN for a row of padding only), key_bias fp32 [B,T] = 0 / -inf, seq_info int32 [B,2] = (#pads,
+ *   1 + index of the last non-pad token; 0 when there is none), keep fp32 [B,T] = 1 - pad (optional).  token_dropout is
+ *   the launcher's argument of that name: the statistics do not depend on it.
+ * esmk_op_packed_stats: the same per segment of a packed row space, tokens int64 [rows]: scale_row, key_bias, keep (optional)
+ *   fp32 [rows], row_pos int32 [rows] = row - segment start, seg_npad int32 [n_seg]; rows outside every segment get
+ *   (1, -inf, 0, 0).
+ * esmk_op_zero_gap_rows: rows outside every segment of buf [rows][row_bytes] := 0; row_bytes a positive multiple of 16.
+ * esmk_op_embed (esm2.py:84-95): x fp32 [B,T,E] = table[tok] (a zero row for tok outside [0,vocab)); with token_dropout
+ *   <mask> rows are zeroed and every row becomes (x * fp32(0.88)) / scale[b]; <pad> rows are zeroed.  The packed engine
+ *   calls it as B = rows, T = 1 with the per-row scale of esmk_op_packed_stats.  scale may be NULL without token_dropout.
+ * esmk_op_embed_esm1 (esm1.py:123-133): x = embed_scale * table[tok], token dropout as above, + sinus[t] (fp32 [T,E]) on
+ *   non-pad tokens; pad rows are NOT zeroed.
+ * esmk_op_add_positions (modules.py:240-257): x[b,t,:] += pos_emb[min(cumsum(nonpad)[t] * nonpad[t] + pad_idx, npos - 1)],
+ *   pos_emb fp32 [npos,E].  segments_host NULL: tokens [B,T]; n_seg and rows must be 0.  Otherwise tokens [rows], segment s
+ *   is a sequence, B = n_seg and T >= the longest segment (the engine passes the longest); rows outside every segment are not
+ *   touched.  T must not exceed npos - pad_idx - 1 (the engine's rule), and (T + 4) * 4 bytes must fit the default dynamic
+ *   LDS limit of 64 KiB.
+ * esmk_op_scale_rows (esm1.py:138-139): x fp32 [rows,E] row r *= keep[r].
+ * esmk_op_msa_embed (msa_transformer.py:152-165): tokens int64 [B,R,C] -> x fp32 [B,R,C,D] = (tok_emb[tok] + pos_emb[p]) +
+ *   msa_pos[r] (msa_pos fp32 [R,D], optional), keep fp32 [B,R,C] = 1 - pad, col_fill fp32 [B,C,R] = pad, any_pad int32 [1] =
+ *   1 iff the batch holds a pad (reset by every call).  C <= npos - pad_idx - 1; (C + 4) * 4 bytes of dynamic LDS as above.
+ * esmk_op_sinus_table (modules.py:283-295): table fp32 [T, 2 half], row t = sin | cos of fp32(pos0 + t) * freq[i], precise
+ *   sinf / cosf.  esmk_op_rope_table (rotary_embedding.py:47-61): cos, sin fp32 [T,half] of fp32(t) * inv_freq[i].
+ *   T * half < 2^31.
+ * esmk_op_gather_rows: out fp32 [n,E] = x[clamp(sel[i], 0, N - 1)], x fp32 [N,E], sel int32 [n] (device data, hence the
+ *   clamp). */
+int esmk_op_seq_stats(const int64_t* tokens_dev, int B, int T, int pad_idx, int mask_idx, int token_dropout, float* scale_dev,
+                      float* key_bias_dev, int32_t* seq_info_dev, float* keep_dev, void* stream);
+int esmk_op_packed_stats(const int64_t* tokens_dev, const int32_t* segments_host, int n_seg, int rows, int pad_idx,
+                         int mask_idx, float* scale_row_dev, float* key_bias_dev, int32_t* row_pos_dev, int32_t* seg_npad_dev,
+                         float* keep_dev, void* stream);
+int esmk_op_zero_gap_rows(void* buf_dev, const int32_t* segments_host, int n_seg, int rows, size_t row_bytes, void* stream);
+int esmk_op_embed(const int64_t* tokens_dev, const float* table_dev, const float* scale_dev, float* x_dev, int B, int T, int E,
+                  int vocab, int pad_idx, int mask_idx, int token_dropout, void* stream);
+int esmk_op_embed_esm1(const int64_t* tokens_dev, const float* table_dev, const float* scale_dev, const float* sinus_dev,
+                       float* x_dev, int B, int T, int E, int vocab, int pad_idx, int mask_idx, int token_dropout,
+                       float embed_scale, void* stream);
+int esmk_op_add_positions(const int64_t* tokens_dev, const float* pos_emb_dev, float* x_dev, int B, int T, int E, int pad_idx,
+                          int npos, const int32_t* segments_host, int n_seg, int rows, void* stream);
+int esmk_op_scale_rows(float* x_dev, const float* keep_dev, int rows, int E, void* stream);
+int esmk_op_msa_embed(const int64_t* tokens_dev, const float* tok_emb_dev, const float* pos_emb_dev, const float* msa_pos_dev,
+                      float* x_dev, float* keep_dev, float* col_fill_dev, int32_t* any_pad_dev, int B, int R, int C, int D,
+                      int vocab, int pad_idx, int npos, void* stream);
+int esmk_op_sinus_table(const float* freq_dev, float* table_dev, int T, int half, int pos0, void* stream);
+int esmk_op_rope_table(const float* inv_freq_dev, float* cos_dev, float* sin_dev, int T, int half, void* stream);
+int esmk_op_gather_rows(const float* x_dev, const int32_t* sel_dev, float* out_dev, int N, int E, int n, void* stream);
+
 /* ContactPredictionHead.forward (modules.py:338-357) incl. symmetrize/apc (modules.py:27-41).
  * attn fp32 [B,C=L*H,T,T]; w fp32 [C]; b fp32 [1]; scratch fp32 >= B*C*(T+1) floats;
  * out fp32 [B,T-2,T-2] (crop follows prepend_bos/append_eos). */

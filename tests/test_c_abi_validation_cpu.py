@@ -527,3 +527,149 @@ def test_linear_gelu_x3_argument_checks():
     assert N_.esmk_debug_gemm_plan(300, 264, 192, N.EPI_GELU_T, 0, out) == 0 and out[0] == 9  # the plain form takes N % 8
     for epi, flags in ((N.EPI_STORE_T, 32), (N.EPI_GELU_T, 32 | 4), (N.EPI_GELU_T, 64)):
         assert N_.esmk_debug_gemm_plan(300, 256, 192, epi, flags, out) != 0 and "esmk_debug_gemm_plan" in err()
+
+
+# ---- the token front end (esmk_op_seq_stats ... esmk_op_gather_rows): refused before any HIP call, on fake pointers ----------
+def _segs(table):
+    return (ctypes.c_int32 * len(table))(*table), len(table) // 2
+
+
+BAD_SEGMENT_TABLES = [([0, 20, 32, 5], 100, "multiple of 64"), ([0, 0], 128, "empty segment"),
+                      ([0, 20, 24, 5], 128, "multiples of 16"), ([16, 20], 128, "start at row 0"),
+                      ([0, 40, 32, 5], 128, "disjoint"), ([32, 5, 0, 20], 128, "start at row 0"),
+                      ([0, 20, 112, 30], 128, "past the last row"), ([], 128, "positive"), ([0, 20], 0, "positive")]
+
+
+def test_frontend_stats_argument_checks():
+    L = N.lib
+
+    def stats(tok=FAKE, B=3, T=70, scale=FAKE, kb=FAKE, info=FAKE, keep=None):
+        return L.esmk_op_seq_stats(tok, B, T, 1, 32, 1, scale, kb, info, keep, None)
+
+    for kw in (dict(tok=None), dict(scale=None), dict(kb=None), dict(info=None)):
+        assert stats(**kw) != 0 and "esmk_op_seq_stats: null" in err(), kw
+    for kw in (dict(B=0), dict(T=0), dict(T=-3)):
+        assert stats(**kw) != 0 and "esmk_op_seq_stats" in err() and "positive" in err(), kw
+    assert stats(B=1 << 14, T=1 << 11) != 0 and "2^24" in err()
+
+    def packed(table=PACKED_SEGS_A[0], rows=PACKED_SEGS_A[1], tok=FAKE, scale=FAKE, kb=FAKE, pos=FAKE, npad=FAKE, seg=True):
+        arr, n = _segs(table)
+        return L.esmk_op_packed_stats(tok, arr if seg else None, n, rows, 1, 32, scale, kb, pos, npad, None, None)
+
+    for kw in (dict(tok=None), dict(scale=None), dict(kb=None), dict(pos=None), dict(npad=None)):
+        assert packed(**kw) != 0 and "esmk_op_packed_stats: null argument" in err(), kw
+    assert packed(seg=False) != 0 and "esmk_op_packed_stats: null segment table" in err()
+    for table, rows, msg in BAD_SEGMENT_TABLES:
+        assert packed(table=table, rows=rows) != 0 and "esmk_op_packed_stats" in err() and msg in err(), (table, err())
+
+    def gaps(table=PACKED_SEGS_A[0], rows=PACKED_SEGS_A[1], buf=FAKE, row_bytes=640, seg=True):
+        arr, n = _segs(table)
+        return L.esmk_op_zero_gap_rows(buf, arr if seg else None, n, rows, ctypes.c_size_t(row_bytes), None)
+
+    assert gaps(buf=None) != 0 and "esmk_op_zero_gap_rows: null argument" in err()
+    assert gaps(seg=False) != 0 and "esmk_op_zero_gap_rows: null segment table" in err()
+    for rb in (0, 8, 24, 636, 1 << 31):
+        assert gaps(row_bytes=rb) != 0 and "esmk_op_zero_gap_rows: row_bytes" in err(), rb
+    for table, rows, msg in BAD_SEGMENT_TABLES:
+        assert gaps(table=table, rows=rows) != 0 and "esmk_op_zero_gap_rows" in err() and msg in err(), (table, err())
+
+
+def test_frontend_embedding_argument_checks():
+    L = N.lib
+
+    def embed(tok=FAKE, table=FAKE, scale=FAKE, x=FAKE, B=2, T=9, E=96, vocab=33, dropout=1):
+        return L.esmk_op_embed(tok, table, scale, x, B, T, E, vocab, 1, 32, dropout, None)
+
+    def esm1(tok=FAKE, table=FAKE, scale=None, sinus=FAKE, x=FAKE, B=2, T=9, E=96, vocab=35, dropout=0):
+        return L.esmk_op_embed_esm1(tok, table, scale, sinus, x, B, T, E, vocab, 1, 33, dropout, 9.8, None)
+
+    for fn, who, nulls in ((embed, "esmk_op_embed", (dict(tok=None), dict(table=None), dict(x=None), dict(scale=None))),
+                           (esm1, "esmk_op_embed_esm1", (dict(tok=None), dict(table=None), dict(x=None), dict(sinus=None),
+                                                         dict(scale=None, dropout=1)))):
+        for kw in nulls:
+            assert fn(**kw) != 0 and who + ": null argument" in err(), (who, kw)
+        for kw in (dict(B=0), dict(T=0), dict(vocab=0)):
+            assert fn(**kw) != 0 and who + ":" in err() and "positive" in err(), (who, kw)
+        for E in (0, -4, 2, 98, 321):
+            assert fn(E=E) != 0 and who + ": E must be a positive multiple of 4" in err(), (who, E)
+        assert fn(B=1 << 14, T=1 << 11) != 0 and who in err() and "2^24" in err()
+
+    def addpos(tok=FAKE, pos=FAKE, x=FAKE, B=2, T=600, E=96, pad=1, npos=1026, table=None, rows=0, n_seg=None):
+        arr, n = _segs(table) if table is not None else (None, 0)
+        return L.esmk_op_add_positions(tok, pos, x, B, T, E, pad, npos, arr, n if n_seg is None else n_seg, rows, None)
+
+    who = "esmk_op_add_positions"
+    for kw in (dict(tok=None), dict(pos=None), dict(x=None)):
+        assert addpos(**kw) != 0 and who + ": null argument" in err(), kw
+    for kw in (dict(B=0), dict(T=0)):
+        assert addpos(**kw) != 0 and who in err() and "positive" in err(), kw
+    for E in (0, 6, 98):
+        assert addpos(E=E) != 0 and who + ": E must be a positive multiple of 4" in err(), E
+    assert addpos(npos=0) != 0 and who + ": npos" in err()
+    for T in (16381, 100000):  # (T + 4) * 4 > 65536
+        assert addpos(T=T, npos=1 << 20) != 0 and who in err() and "dynamic LDS" in err(), T
+    for kw in (dict(T=1025), dict(T=600, npos=601), dict(T=5, npos=8, pad=3)):  # T > npos - pad_idx - 1
+        assert addpos(**kw) != 0 and who in err() and "above the maximum of the positional embedding" in err(), kw
+    assert addpos(n_seg=2) != 0 and who in err() and "without a segment table" in err()
+    assert addpos(rows=64) != 0 and who in err() and "without a segment table" in err()
+    for table, rows, msg in BAD_SEGMENT_TABLES:
+        assert addpos(table=table, rows=rows, B=len(table) // 2 or 1, T=40) != 0 and who in err() and msg in err(), (table, err())
+    ok_table = [0, 300, 304, 7]
+    for kw in (dict(B=3, T=300), dict(B=2, T=299)):  # B != n_seg; T below the longest segment
+        assert addpos(table=ok_table, rows=320, **kw) != 0 and who in err() and "longest segment" in err(), kw
+    assert addpos(table=ok_table, rows=320, B=2, T=300, npos=300) != 0 and "above the maximum" in err()
+
+    def scale_rows(x=FAKE, keep=FAKE, rows=77, E=96):
+        return L.esmk_op_scale_rows(x, keep, rows, E, None)
+
+    for kw in (dict(x=None), dict(keep=None)):
+        assert scale_rows(**kw) != 0 and "esmk_op_scale_rows: null argument" in err(), kw
+    for rows in (0, -1, (1 << 24) + 1):
+        assert scale_rows(rows=rows) != 0 and "esmk_op_scale_rows: rows" in err(), rows
+    for E in (0, 6):
+        assert scale_rows(E=E) != 0 and "esmk_op_scale_rows: E must be a positive multiple of 4" in err(), E
+
+    def msa(tok=FAKE, te=FAKE, pe=FAKE, mp=None, x=FAKE, keep=FAKE, fill=FAKE, anyp=FAKE, B=1, R=3, C=130, D=96, vocab=33,
+            pad=1, npos=1026):
+        return L.esmk_op_msa_embed(tok, te, pe, mp, x, keep, fill, anyp, B, R, C, D, vocab, pad, npos, None)
+
+    who = "esmk_op_msa_embed"
+    for kw in (dict(tok=None), dict(te=None), dict(pe=None), dict(x=None), dict(keep=None), dict(fill=None), dict(anyp=None)):
+        assert msa(**kw) != 0 and who + ": null argument" in err(), kw
+    for kw in (dict(B=0), dict(R=0), dict(C=0), dict(vocab=0)):
+        assert msa(**kw) != 0 and who in err() and "positive" in err(), kw
+    for D in (0, 6, 770):
+        assert msa(D=D) != 0 and who + ": D must be a positive multiple of 4" in err(), D
+    assert msa(C=16381, npos=1 << 20) != 0 and who in err() and "dynamic LDS" in err()
+    for kw in (dict(C=1025), dict(C=130, npos=131)):
+        assert msa(**kw) != 0 and who in err() and "above the maximum of the positional embedding" in err(), kw
+    assert msa(B=1 << 8, R=1 << 8, C=1 << 9, npos=1 << 20) != 0 and who in err() and "2^24" in err()
+
+
+def test_frontend_table_and_gather_argument_checks():
+    L = N.lib
+
+    def sinus(freq=FAKE, table=FAKE, T=1030, half=160):
+        return L.esmk_op_sinus_table(freq, table, T, half, 2, None)
+
+    def rope(freq=FAKE, cos=FAKE, sin=FAKE, T=1030, half=32):
+        return L.esmk_op_rope_table(freq, cos, sin, T, half, None)
+
+    for fn, who, nulls in ((sinus, "esmk_op_sinus_table", (dict(freq=None), dict(table=None))),
+                           (rope, "esmk_op_rope_table", (dict(freq=None), dict(cos=None), dict(sin=None)))):
+        for kw in nulls:
+            assert fn(**kw) != 0 and who + ": null argument" in err(), (who, kw)
+        for kw in (dict(T=0), dict(half=0), dict(T=-5)):
+            assert fn(**kw) != 0 and who + ": T and half must be positive" in err(), (who, kw)
+        assert fn(T=1 << 24, half=128) != 0 and who in err() and "2^31" in err()
+
+    def gather(x=FAKE, sel=FAKE, out=FAKE, Nr=37, E=320, n=300):
+        return L.esmk_op_gather_rows(x, sel, out, Nr, E, n, None)
+
+    who = "esmk_op_gather_rows"
+    for kw in (dict(x=None), dict(sel=None), dict(out=None)):
+        assert gather(**kw) != 0 and who + ": null argument" in err(), kw
+    for kw in (dict(Nr=0), dict(n=0), dict(n=-2), dict(Nr=(1 << 24) + 1)):
+        assert gather(**kw) != 0 and who + ": N and n" in err(), kw
+    for E in (0, 2, 322):
+        assert gather(E=E) != 0 and who + ": E must be a positive multiple of 4" in err(), E

@@ -1,7 +1,13 @@
-"""Single-kernel parity tests on the MI355X: every HIP kernel of libesmk.so, called through the
-C ABI (esm_amd.ops -> ctypes), against a plain PyTorch fp32 reference of the same op evaluated on
-the SAME operand values (inputs are rounded to the operand dtype first, so the tolerance only has
-to cover fp32 accumulation order and the final rounding of the output)."""
+"""Single-kernel parity tests on the MI355X: the LayerNorm, GEMM, QKV + RoPE, attention and contact-head kernels of
+libesmk.so, called through the C ABI (esm_amd.ops -> ctypes), against a plain PyTorch fp32 reference of the same op
+evaluated on the SAME operand values (inputs are rounded to the operand dtype first, so the tolerance only has
+to cover fp32 accumulation order and the final rounding of the output).
+
+Together with this file, every HIP kernel of the library has a single-op test: test_attention_variants_gpu.py,
+test_attention_biaskv_gpu.py and test_attention_packed_ops_gpu.py (attention forms), test_gemm_forms_gpu.py (generalised
+GEMM forms, MSA row softmax), test_contacts_kernels_gpu.py (fused and packed contacts), test_ln_fold_gpu.py (LayerNorm
+fold), test_precision_ops_gpu.py (precision modes), test_scoring_ops_gpu.py and test_scoring_variant_ops_gpu.py (scoring)
+and test_frontend_ops_gpu.py (token statistics, embeddings, positions, position tables, row gather)."""
 import math
 
 import pytest
