@@ -98,6 +98,12 @@ SIGNATURES = {
     "esmk_rows_workspace_bytes": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "esmk_forward_rows": (
         c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # token-packed batch + row selection (mixed-length libraries of masked copies); the segment table is a host array
+    "esmk_packed_rows_workspace_bytes": (
+        c_int, [c_void_p, POINTER(c_int32), c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
+    "esmk_forward_packed_rows": (
+        c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                c_void_p]),
     "esmk_packed_workspace_bytes": (c_int, [c_void_p, c_int, c_int, c_uint32, POINTER(c_size_t)]),
     "esmk_forward_packed": (
         c_int,
@@ -236,6 +242,11 @@ SIGNATURES = {
     "esmk_op_mask_rows_multi": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "esmk_op_score_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    # packed masked copies (esmk_forward_packed_rows' input); fp64 sums of the fp32 log p(true token) per sequence
+    "esmk_op_mask_rows_packed": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                c_int, c_void_p]),
+    "esmk_op_sum_target_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     # the token front end, one launch at a time (tests/test_frontend_ops_gpu.py); segment tables are host arrays
     "esmk_op_seq_stats": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "esmk_op_packed_stats": (

@@ -200,9 +200,10 @@ Workspace plan_workspace(const esmk_model* m, int B, int T, uint32_t flags, int 
 // esmk_forward_rows: the forward's workspace, then the selected rows of the stream (fp32), their operand-dtype rows, the fp32
 // scratch of the head and the selected logits.  No pad rows: every GEMM kernel clamps its A-row reads to row M - 1 and stores
 // rows below M only, so M = n_sel is launched as it is.
-size_t plan_rows(const esmk_model* m, int B, int T, int n_sel, RowSel* rs) {
+// packed_segs > 0 (esmk_forward_packed_rows): the token-packed forward's workspace (B = 1, T = rows) in front.
+size_t plan_rows(const esmk_model* m, int B, int T, int n_sel, RowSel* rs, int packed_segs = 0) {
     Carve c;
-    c.take(plan_workspace(m, B, T, ESMK_OUT_LOGITS).total);
+    c.take(plan_workspace(m, B, T, ESMK_OUT_LOGITS, packed_segs).total);
     const size_t n = (size_t)n_sel;
     rs->x = c.take(n * m->E * 4);
     rs->h = c.take(n * std::max(m->Kp, m->EA) * op_size(m->cfg.operand_dtype));
@@ -493,7 +494,7 @@ struct ForwardCall {
     size_t workspace_bytes = 0;
     void* stream = nullptr;
     const PackedCtx* pc = nullptr;  // token-packed batch: B = 1, T = rows
-    const RowSel* rs = nullptr;     // esmk_forward_rows
+    const RowSel* rs = nullptr;     // esmk_forward_rows, esmk_forward_packed_rows
 };
 
 // What the stages share: the call, the launch helpers, the workspace and the form the model runs in
@@ -614,7 +615,7 @@ int check_forward(const ForwardCall& c, Workspace* w) {
 // sinusoidal (ESM-1), rotary or unit tables for the longest run of positions
 int position_tables(const Fwd& f) {
     esmk_model* m = f.m;
-    if (f.esm1 && f.pc) return fail("esmk_forward_packed: ESM-1 (no_rope = ESMK_ESM1) has no token-packed form yet");
+    if (f.esm1 && f.pc) return fail(f.who() + ": ESM-1 (no_rope = ESMK_ESM1) has no token-packed form yet");
     if (f.esm1 && ensure_sinus(m, f.T, f.s.st)) return 1;
     const int T_rope = f.pc ? f.pc->max_len : f.T;
     return m->cfg.no_rope ? ensure_unit_rope(m, T_rope, f.s.st) : ensure_rope(m, T_rope, f.s.st);
@@ -1484,6 +1485,49 @@ int esmk_forward_packed(esmk_model* m, const void* packed_dev, const int64_t* to
         return fail("esmk_forward_packed: attention maps and contacts take padded batches (esmk_forward)");
     return forward_impl(packed_call(m, packed_dev, tokens_dev, rows, repr_layers, n_repr, repr_out_dev, out_flags,
                                     logits_out_dev, nullptr, workspace_dev, workspace_bytes, stream, &pc));
+}
+
+// ---- token-packed batch + row selection: mixed-length libraries of masked copies (predict.py:138-143,205-215) -------------
+static int check_packed_rows(const char* who, const esmk_model* m, const int32_t* seg, int n_seg, int rows, int n_sel,
+                             PackedCtx* pc) {
+    if (check_segments(who, m, seg, n_seg, rows, pc)) return 1;
+    if (split_x3(m))
+        return fail(std::string(who) + ": the f16x3 precision mode runs padded batches of head_dim-64 models (no token-packed form)");
+    return check_rows(who, m, 1, rows, n_sel);
+}
+
+int esmk_packed_rows_workspace_bytes(const esmk_model* m, const int32_t* segments_host, int n_seg, int rows, int n_sel,
+                                     size_t* bytes, size_t* logits_offset) {
+    if (!m || !bytes) return fail("esmk_packed_rows_workspace_bytes: null argument");
+    PackedCtx pc;
+    if (check_packed_rows("esmk_packed_rows_workspace_bytes", m, segments_host, n_seg, rows, n_sel, &pc)) return 1;
+    RowSel rs;
+    *bytes = plan_rows(m, 1, rows, n_sel, &rs, n_seg);
+    if (logits_offset) *logits_offset = rs.logits;
+    return 0;
+}
+
+int esmk_forward_packed_rows(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev, const int32_t* segments_host,
+                             int n_seg, int rows, const int32_t* sel_rows_dev, int n_sel, float* logprobs_out_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!m || !packed_dev || !tokens_dev || !segments_host || !sel_rows_dev || !logprobs_out_dev || !workspace_dev)
+        return fail("esmk_forward_packed_rows: null argument");
+    PackedCtx pc;
+    if (check_packed_rows("esmk_forward_packed_rows", m, segments_host, n_seg, rows, n_sel, &pc)) return 1;
+    RowSel rs;
+    if (workspace_bytes < plan_rows(m, 1, rows, n_sel, &rs, n_seg)) return fail("esmk_forward_packed_rows: workspace too small");
+    if (!m->cfg.no_rope && m->inv_freq.empty()) return fail("esmk_forward_packed_rows: esmk_set_rope_inv_freq was not called");
+    rs.sel_dev = sel_rows_dev;
+    rs.n_sel = n_sel;
+    rs.logprobs_out = logprobs_out_dev;
+    ForwardCall c;
+    c.who = "esmk_forward_packed_rows";
+    c.m = m, c.packed = packed_dev, c.tokens = tokens_dev, c.B = 1, c.T = rows;
+    c.flags = ESMK_OUT_LOGITS, c.logits = (char*)workspace_dev + rs.logits;
+    c.workspace = workspace_dev, c.workspace_bytes = workspace_bytes, c.stream = stream;
+    c.pc = &pc;
+    c.rs = &rs;
+    return forward_impl(c);
 }
 
 int esmk_ln_fold_enabled(const esmk_model* m) { return (!m || m->is_msa) ? -1 : (m->fold ? 1 : 0); }

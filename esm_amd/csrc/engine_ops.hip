@@ -849,6 +849,29 @@ int esmk_op_score_rows(const float* logprobs_dev, const int32_t* wt_dev, const i
     return 0;
 }
 
+int esmk_op_mask_rows_packed(const int64_t* tokens_dev, const int32_t* src_row_dev, const int32_t* seg_start_dev,
+                             const int32_t* seg_len_dev, const int32_t* pos_off_dev, const int32_t* pos_dev, int64_t* out_dev, int B,
+                             int T, int n, int total, int rows, int mask_idx, int pad_idx, void* stream) {
+    if (!tokens_dev || !src_row_dev || !seg_start_dev || !seg_len_dev || !pos_off_dev || !pos_dev || !out_dev)
+        return fail("esmk_op_mask_rows_packed: null argument");
+    if (B <= 0 || T <= 0 || n <= 0) return fail("esmk_op_mask_rows_packed: B, T and n must be positive");
+    if (total < 0) return fail("esmk_op_mask_rows_packed: total must not be negative");
+    if (rows <= 0 || rows % 64 != 0 || rows > ESMK_MAX_ROWS)
+        return fail("esmk_op_mask_rows_packed: need 0 < rows <= 2^24, rows % 64 == 0");
+    if ((long long)B * T > ESMK_MAX_ROWS) return fail("esmk_op_mask_rows_packed: B*T exceeds 2^24 rows");
+    ESMK_TRY(launch_mask_rows_packed(tokens_dev, src_row_dev, seg_start_dev, seg_len_dev, pos_off_dev, pos_dev, out_dev, B, T, n,
+                                     total, rows, mask_idx, pad_idx, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_sum_target_rows(const float* logprobs_dev, const int32_t* target_dev, const int32_t* off_dev, double* out_dev,
+                            int n_rows, int n_seq, int V, void* stream) {
+    if (!logprobs_dev || !target_dev || !off_dev || !out_dev) return fail("esmk_op_sum_target_rows: null argument");
+    if (n_rows <= 0 || n_seq <= 0 || V <= 0) return fail("esmk_op_sum_target_rows: n_rows, n_seq and V must be positive");
+    ESMK_TRY(launch_sum_target_rows(logprobs_dev, target_dev, off_dev, out_dev, n_rows, n_seq, V, (hipStream_t)stream));
+    return 0;
+}
+
 int esmk_op_log_softmax_rows(const float* logits_dev, float* out_dev, const int32_t* target_dev, float* target_out_dev, int n,
                              int V, void* stream) {
     if (!logits_dev || !out_dev) return fail("esmk_op_log_softmax_rows: null argument");

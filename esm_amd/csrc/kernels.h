@@ -208,6 +208,12 @@ hipError_t launch_mask_rows(const int64_t* tokens, const int* src_row, const int
 // pos_off int32 [n+1] (clamped to [0,total]; hi < lo: no position), pos int32 [total] (outside [0,T): masks nothing)
 hipError_t launch_mask_rows_multi(const int64_t* tokens, const int* src_row, const int* pos_off, const int* pos, int64_t* out,
                                   int B, int T, int n, int total, int mask_idx, hipStream_t st);
+// the same into ONE packed row space of `rows` rows (esmk_forward_packed_rows): copy i = the first seg_len[i] tokens of
+// tokens[src_row[i]] at out[seg_start[i] ...], its positions masked, the gap up to seg_start[i+1] (rows for the last copy) filled
+// with pad_idx; src_row, seg_start, seg_len int32 [n] (clamped: row to [0,B), length to [0,T], written range to [0,rows))
+hipError_t launch_mask_rows_packed(const int64_t* tokens, const int* src_row, const int* seg_start, const int* seg_len,
+                                   const int* pos_off, const int* pos, int64_t* out, int B, int T, int n, int total, int rows,
+                                   int mask_idx, int pad_idx, hipStream_t st);
 // out [n,E] = rows sel[i] (clamped to [0,N)) of x [N,E], fp32, E % 4 == 0
 hipError_t launch_gather_rows(const float* x, const int* sel, float* out, int N, int E, int n, hipStream_t st);
 // out [n,V] = log_softmax(logits [n,V]), V <= 64; target (optional, int32 [n]): tgt_out[i] = out[i, target[i]]
@@ -217,6 +223,10 @@ hipError_t launch_log_softmax_rows(const float* logits, float* out, const int* t
 // in fp64 by one lane per variant (no atomics); lp fp32 [n_rows,V], columns clamped to [0,V), offsets to [0,n_rows]
 hipError_t launch_score_rows(const float* lp, const int* wt, const int* mt, const int* var_off, double* out, int n_rows,
                              int n_var, int V, hipStream_t st);
+// out fp64 [n_seq]: out[s] = sum, r ascending in [off[s], off[s+1]), of the fp32 lp[r,target[r]], added in fp64 by one lane per
+// sequence (no atomics); target clamped to [0,V), offsets to [0,n_rows]
+hipError_t launch_sum_target_rows(const float* lp, const int* target, const int* off, double* out, int n_rows, int n_seq, int V,
+                                  hipStream_t st);
 // contact head (modules.py:27-41,338-357)
 hipError_t launch_contacts(const float* attn, const int64_t* tokens, const float* w,
                            const float* b, float* scratch, float* out, int B, int C, int T,

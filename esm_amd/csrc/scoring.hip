@@ -65,6 +65,49 @@ hipError_t launch_mask_rows_multi(const int64_t* tokens, const int* src_row, con
     return hipGetLastError();
 }
 
+// The packed counterpart of mask_rows_multi_kernel (esmk_forward_packed_rows): copy i is the first seg_len[i] tokens of
+// tokens[src_row[i]], written to out[seg_start[i] : seg_start[i] + seg_len[i]] of ONE row space of `rows` rows, with every
+// position of pos[pos_off[i] : pos_off[i + 1]] replaced by mask_idx; the gap behind the copy — up to seg_start[i + 1], or to
+// `rows` behind the last copy — is filled with pad_idx (esmk_forward_packed wants pad_idx in gap rows; nothing is assumed
+// about what `out` held).  One workgroup per copy, copies strided over the grid: copy and gap fill, barrier, then the mask
+// on top.  The copies' row ranges are disjoint by contract, so no two workgroups write the same row.  The lists are device
+// data the host never saw: a source row outside [0, B) is clamped, seg_len to [0, T], the written range to [0, rows), the
+// offsets to [0, total] (hi < lo: an empty list), a position outside [0, seg_len) masks nothing, and a repeated position
+// stores the same value twice.
+__global__ __launch_bounds__(256) void mask_rows_packed_kernel(const int64_t* __restrict__ tokens, const int* __restrict__ src_row,
+                                                               const int* __restrict__ seg_start, const int* __restrict__ seg_len,
+                                                               const int* __restrict__ pos_off, const int* __restrict__ pos,
+                                                               int64_t* __restrict__ out, int B, int T, int n, int total, int rows,
+                                                               int64_t mask_idx, int64_t pad_idx) {
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {  // workgroup uniform: every lane reaches the barrier
+        const int b = min(max(src_row[i], 0), B - 1);
+        const int64_t* in = tokens + (size_t)b * T;
+        const int start = min(max(seg_start[i], 0), rows);
+        const int len = min(min(max(seg_len[i], 0), T), rows - start);
+        const int end = i + 1 < n ? min(max(seg_start[i + 1], start), rows) : rows;  // the gap's end; below start + len: no gap
+        int64_t* o = out + start;
+        for (int t = threadIdx.x; t < len; t += 256) o[t] = in[t];
+        for (int r = start + len + (int)threadIdx.x; r < end; r += 256) out[r] = pad_idx;
+        __syncthreads();
+        const int lo = min(max(pos_off[i], 0), total), hi = min(max(pos_off[i + 1], 0), total);
+        for (int j = lo + (int)threadIdx.x; j < hi; j += 256) {
+            const int p = pos[j];
+            if (p >= 0 && p < len) o[p] = mask_idx;
+        }
+    }
+}
+
+hipError_t launch_mask_rows_packed(const int64_t* tokens, const int* src_row, const int* seg_start, const int* seg_len,
+                                   const int* pos_off, const int* pos, int64_t* out, int B, int T, int n, int total, int rows,
+                                   int mask_idx, int pad_idx, hipStream_t st) {
+    if (!tokens || !src_row || !seg_start || !seg_len || !pos_off || !pos || !out || B <= 0 || T <= 0 || n <= 0 || total < 0 ||
+        rows <= 0)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mask_rows_packed_kernel, dim3((unsigned)std::min(n, 8192)), dim3(256), 0, st, tokens, src_row, seg_start,
+                       seg_len, pos_off, pos, out, B, T, n, total, rows, (int64_t)mask_idx, (int64_t)pad_idx);
+    return hipGetLastError();
+}
+
 // out[i, :] = x[clamp(sel[i], 0, N - 1), :]: fp32 rows of E values, E % 4 == 0, 16 bytes per lane.  The clamp makes an index
 // the host never saw (it is device data) read a valid row instead of faulting.
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ x, const int* __restrict__ sel,
@@ -143,6 +186,30 @@ hipError_t launch_score_rows(const float* lp, const int* wt, const int* mt, cons
     if (!lp || !wt || !mt || !var_off || !out || n_rows <= 0 || n_var <= 0 || V <= 0) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)std::min<size_t>(((size_t)n_var + 255) / 256, 8192);
     hipLaunchKernelGGL(score_rows_kernel, dim3(blocks), dim3(256), 0, st, lp, wt, mt, var_off, out, n_rows, n_var, V);
+    return hipGetLastError();
+}
+
+// out[s] = sum over r in [off[s], off[s + 1]), ascending, of lp[r, target[r]]: the pseudo-log-likelihood of sequence s from its
+// rows of log-probabilities.  The terms are fp32, added in fp64 in index order by ONE lane per sequence, as score_rows_kernel
+// adds a variant's: no atomics, a result that does not depend on the launch geometry.  target is clamped to [0, V), the
+// offsets to [0, n_rows]; an empty range (hi <= lo) gives 0.0.
+__global__ __launch_bounds__(256) void sum_target_rows_kernel(const float* __restrict__ lp, const int* __restrict__ target,
+                                                              const int* __restrict__ off, double* __restrict__ out, int n_rows,
+                                                              int n_seq, int V) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t s = (size_t)blockIdx.x * 256 + threadIdx.x; s < (size_t)n_seq; s += stride) {
+        const int lo = min(max(off[s], 0), n_rows), hi = min(max(off[s + 1], 0), n_rows);
+        double sum = 0.0;
+        for (int r = lo; r < hi; ++r) sum += (double)lp[(size_t)r * V + min(max(target[r], 0), V - 1)];
+        out[s] = sum;
+    }
+}
+
+hipError_t launch_sum_target_rows(const float* lp, const int* target, const int* off, double* out, int n_rows, int n_seq, int V,
+                                  hipStream_t st) {
+    if (!lp || !target || !off || !out || n_rows <= 0 || n_seq <= 0 || V <= 0) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)std::min<size_t>(((size_t)n_seq + 255) / 256, 8192);
+    hipLaunchKernelGGL(sum_target_rows_kernel, dim3(blocks), dim3(256), 0, st, lp, target, off, out, n_rows, n_seq, V);
     return hipGetLastError();
 }
 

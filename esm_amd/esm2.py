@@ -107,6 +107,16 @@ def _weight_split():
     return {"f16x2": 1, "fp16x2": 1, "f16x2a": 2, "fp16x2a": 2, "f16x2v": 3, "fp16x2v": 3, "f16x3": 4, "fp16x3": 4}.get(env, 0)
 
 
+def _varlen_kw(varlen, chunk_rows):
+    """The keywords the scoring methods add to their ``esm_amd.scoring`` call: none for the default, so that the call is the one
+    of before keyword for keyword; ``chunk_rows`` without ``varlen=True`` would be dropped silently, so it is refused."""
+    if not varlen:
+        if chunk_rows is not None:
+            raise ValueError("chunk_rows sizes the packed row spaces of varlen=True; the padded path takes chunk")
+        return {}
+    return dict(varlen=True, chunk_rows=chunk_rows)
+
+
 def _ln_fold():
     """``ESM_AMD_LN_FOLD=1|0``: LayerNorm fold of the engine (esmk_config.ln_fold) on / off; unset = the
     library's default.  ESM-2 / ESM-1b engines with plain fp16 / bf16 operands and head_dim <= 64."""
@@ -546,7 +556,10 @@ class ESM2(nn.Module):
                     When the call falls back to ``forward`` (min_saving, f16x3, ESM-1) and asks for maps AND contacts,
                     the model runs twice — once for the maps, once with ``contacts_only=True`` — so that the contacts
                     are the fused ones on both routes and the maps can stay in the model dtype; the fall-back is taken
-                    where packing saves little, i.e. the second run costs one contacts-only forward of the same batch."""
+                    where packing saves little, i.e. the second run costs one contacts-only forward of the same batch.
+
+        The scoring methods follow the same rule (``esm_amd.scoring``): with ``varlen=True`` on an ESM-1 model or in the
+        f16x3 mode, which have no token-packed form, the padded path runs."""
         assert tokens.ndim == 2
         from . import _native as N
         from .packing import pack_plan
@@ -668,31 +681,34 @@ class ESM2(nn.Module):
     # zero-shot variant scoring (esm_amd/scoring.py; reference examples/variant-prediction/predict.py)
     supports_scoring = True  # esmk_forward_rows: ESM-2, ESM-1b / ESM-1v, ESM-1; not the MSA Transformer
 
-    def masked_marginals(self, tokens, positions=None, chunk=None):
+    # varlen=True: the masked copies run token-packed (esmk_forward_packed_rows) — the form for sequences of different lengths;
+    # the same bits.  The default call is the one of before, keyword for keyword.
+    def masked_marginals(self, tokens, positions=None, chunk=None, varlen=False, chunk_rows=None):
         """``esm_amd.scoring.masked_marginals``: [B, T, V] fp32 log-probabilities, row (b, i) from the forward with token
         (b, i) alone masked."""
         from . import scoring
 
-        return scoring.masked_marginals(self, tokens, positions=positions, chunk=chunk)
+        return scoring.masked_marginals(self, tokens, positions=positions, chunk=chunk, **_varlen_kw(varlen, chunk_rows))
 
-    def wt_marginals(self, tokens):
+    def wt_marginals(self, tokens, varlen=False, chunk_rows=None):
         """``esm_amd.scoring.wt_marginals``: [B, T, V] fp32 log-probabilities of the unmasked forward, non-pad rows."""
         from . import scoring
 
-        return scoring.wt_marginals(self, tokens)
+        return scoring.wt_marginals(self, tokens, **_varlen_kw(varlen, chunk_rows))
 
-    def pseudo_log_likelihood(self, tokens, positions=None, chunk=None):
+    def pseudo_log_likelihood(self, tokens, positions=None, chunk=None, varlen=False, chunk_rows=None):
         """``esm_amd.scoring.pseudo_log_likelihood``: [B] fp64, sum of the masked-marginal log-probability of the true token."""
         from . import scoring
 
-        return scoring.pseudo_log_likelihood(self, tokens, positions=positions, chunk=chunk)
+        return scoring.pseudo_log_likelihood(self, tokens, positions=positions, chunk=chunk, **_varlen_kw(varlen, chunk_rows))
 
-    def masked_joint(self, tokens, position_sets, src=None, chunk=None, return_logits=False):
+    def masked_joint(self, tokens, position_sets, src=None, chunk=None, return_logits=False, varlen=False, chunk_rows=None):
         """``esm_amd.scoring.masked_joint``: one forward per position set with ALL its positions masked; (offsets, pos,
         logprobs [n_rows, V]) of the masked rows."""
         from . import scoring
 
-        return scoring.masked_joint(self, tokens, position_sets, src=src, chunk=chunk, return_logits=return_logits)
+        return scoring.masked_joint(self, tokens, position_sets, src=src, chunk=chunk, return_logits=return_logits,
+                                    **_varlen_kw(varlen, chunk_rows))
 
     def score_variants(self, alphabet, sequence, variants, strategy="masked-marginals", offset_idx=0, sep=":", chunk=None):
         """``esm_amd.scoring.score_variants``: floats, one per variant of one or more substitutions ('A42G:K50R')."""

@@ -508,6 +508,51 @@ def score_rows(logprobs, wt, mt, var_offsets):
     return out
 
 
+def mask_rows_packed(tokens, src_rows, seg_starts, seg_lens, pos_offsets, positions, rows, mask_idx=32, pad_idx=1, out=None):
+    """[rows] int64, ONE packed row space: copy i = the first ``seg_lens[i]`` tokens of ``tokens[src_rows[i]]`` at
+    ``out[seg_starts[i] : seg_starts[i] + seg_lens[i]]`` with every position of ``positions[pos_offsets[i] : pos_offsets[i + 1]]``
+    set to ``mask_idx``; the gap behind the copy, up to ``seg_starts[i + 1]`` (``rows`` behind the last copy), is filled with
+    ``pad_idx`` — the token stream ``esmk_forward_packed_rows`` takes.  src_rows, seg_starts, seg_lens int32 [n], pos_offsets
+    int32 [n + 1], positions int32 [total], all device data: a source row outside [0, B) is clamped, a start to [0, rows], a
+    length to [0, T] and to the rows left, offsets to [0, total] (a descending pair is an empty list), a position outside
+    [0, length) masks nothing, a repeated position is harmless.  ``rows`` % 64 == 0.  ``out``: the caller's buffer of at least
+    ``rows`` int64 (tests that look at the memory around it)."""
+    _req_cuda(tokens, src_rows, seg_starts, seg_lens, pos_offsets, positions, out)
+    tokens = tokens.view(1, -1) if tokens.dim() == 1 else tokens
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.is_contiguous()
+    n = src_rows.numel()
+    for t in (src_rows, seg_starts, seg_lens, pos_offsets, positions):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
+    assert n >= 1 and seg_starts.numel() == n and seg_lens.numel() == n and pos_offsets.numel() == n + 1
+    B, T = tokens.shape
+    total = positions.numel()
+    if total == 0:  # nothing to mask anywhere; the entry still wants a pointer it will not read
+        positions = torch.zeros((1,), dtype=torch.int32, device=tokens.device)
+    if out is None:
+        out = torch.empty((rows,), dtype=torch.int64, device=tokens.device)
+    assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() >= rows
+    N.check(N.lib.esmk_op_mask_rows_packed(N.ptr(tokens), N.ptr(src_rows), N.ptr(seg_starts), N.ptr(seg_lens), N.ptr(pos_offsets),
+                                           N.ptr(positions), N.ptr(out), B, T, n, total, int(rows), int(mask_idx), int(pad_idx),
+                                           N.cur_stream()))
+    return out
+
+
+def sum_target_rows(logprobs, target, offsets):
+    """fp64 [n_seq]: entry s = the sum over the rows r of ``offsets[s] : offsets[s + 1]``, ascending, of the fp32
+    ``logprobs[r, target[r]]``, added in fp64 by one lane per sequence (a fixed order: no atomics).  logprobs fp32 [n_rows, V];
+    target int32 [n_rows] (clamped to [0, V)); offsets int32 [n_seq + 1] (clamped to [0, n_rows]; an empty range gives 0.0)."""
+    _req_cuda(logprobs, target, offsets)
+    assert logprobs.dtype == torch.float32 and logprobs.dim() == 2 and logprobs.is_contiguous()
+    n_rows, V = logprobs.shape
+    assert target.dtype == torch.int32 and target.numel() == n_rows
+    assert offsets.dtype == torch.int32 and offsets.dim() == 1 and offsets.numel() >= 2
+    n_seq = offsets.numel() - 1
+    out = torch.empty((n_seq,), dtype=torch.float64, device=logprobs.device)
+    N.check(N.lib.esmk_op_sum_target_rows(N.ptr(logprobs), N.ptr(target), N.ptr(offsets), N.ptr(out), n_rows, n_seq, V,
+                                          N.cur_stream()))
+    return out
+
+
 # ---- the token front end, one launch at a time (include/esmk.h: esmk_op_seq_stats ... esmk_op_gather_rows) -----------------
 def _out(t, shape, dtype, device):
     """The caller's output buffer (checked), or a fresh one: callers that look at the memory behind an output pass their own."""

@@ -14,6 +14,13 @@ positions of the variant are masked in one forward (``masked_joint``, ``esmk_op_
 log p(mutant) - log p(wild type) is summed over them (``score_variants``, ``esmk_op_score_rows``: fp32 terms added in fp64
 in a fixed order).
 
+Libraries of sequences of DIFFERENT lengths (ranking designs by pseudo-log-likelihood, insertion / deletion variants,
+wt-marginals over a FASTA file) can run token-packed: ``varlen=True`` lays the masked copies back to back in one row space
+(``esmk_op_mask_rows_packed``, chunks planned by ``plan_packed_chunks``) and runs ``esmk_forward_packed_rows``
+(``forward_rows_packed``), so the layer stack does no work on padding.  The packed forward gives every segment the bits of
+that sequence alone: the tables are those of the padded path bit for bit, and the pseudo-log-likelihood is summed in a fixed
+order (``esmk_op_sum_target_rows``).  ``python -m esm_amd.score_sequences`` scores a FASTA or CSV file that way.
+
 The functions are also methods of ``ESM2`` / ``ProteinBertModel`` (``model.masked_marginals(tokens)`` ...).  They refuse the
 MSA Transformer (``NotImplementedError``): one MSA plus a query row is another argument shape, served by
 ``esm_amd.msa_scoring`` under names of its own.
@@ -85,6 +92,132 @@ def forward_rows(model, tokens, sel_rows, return_logits=False):
     return out
 
 
+def forward_rows_packed(model, tokens_flat, segments, sel_rows, return_logits=False):
+    """``forward_rows`` for a token-packed batch (``esmk_forward_packed_rows``): fp32 ``[n, V]`` log-probabilities of the rows
+    ``sel_rows`` of ONE packed row space.  ``tokens_flat`` int64 ``[rows]`` on the model's device (``ops.mask_rows_packed``
+    builds it), rows % 64 == 0, gap rows holding the padding index; ``segments`` int32 ``[n_seg, 2]`` on the HOST (first row,
+    length incl. <cls> / <eos>): the first segment starts at row 0, starts are ascending multiples of 16, segments disjoint;
+    ``sel_rows`` int32 ``[n]`` flat indices into the row space, on the device (clamped by the engine to [0, rows)).  Every
+    segment carries the bits of that sequence alone, so a row equals the row ``forward_rows`` gives the same sequence in a
+    padded batch.  ``return_logits``: also the selected fp32 logits.  ESM-2 and ESM-1b / ESM-1v models; ESM-1 models and the
+    f16x3 precision mode have no token-packed forward and are refused by the engine."""
+    from . import _native as N
+
+    _refuse_msa(model)
+    w = model.embed_tokens.weight
+    if not w.is_cuda:
+        raise RuntimeError("esm_amd.scoring runs only on an MI355X (ROCm) device: move the model to 'cuda' first; the engine "
+                           "has no CPU fallback")
+    dev = w.device
+    assert tokens_flat.dtype == torch.int64 and tokens_flat.ndim == 1 and tokens_flat.device == dev and tokens_flat.is_contiguous()
+    assert sel_rows.dtype == torch.int32 and sel_rows.ndim == 1 and sel_rows.device == dev and sel_rows.is_contiguous()
+    seg = torch.as_tensor(segments)
+    assert seg.dtype == torch.int32 and not seg.is_cuda and seg.ndim == 2 and seg.shape[1] == 2 and seg.is_contiguous()
+    rows, n_seg, n = tokens_flat.numel(), seg.shape[0], sel_rows.numel()
+    V = model.alphabet_size
+    if n == 0:
+        empty = torch.empty((0, V), dtype=torch.float32, device=dev)
+        return (empty, empty.clone()) if return_logits else empty
+    seg_ptr = ctypes.cast(seg.data_ptr(), ctypes.POINTER(ctypes.c_int32))
+    with torch.cuda.device(dev):
+        eng = model._engine_ready(dev)
+        need, off = ctypes.c_size_t(), ctypes.c_size_t()
+        N.check(N.lib.esmk_packed_rows_workspace_bytes(eng.handle, seg_ptr, n_seg, rows, n, ctypes.byref(need), ctypes.byref(off)))
+        ws = eng.workspace_for_bytes(need.value)
+        out = torch.empty((n, V), dtype=torch.float32, device=dev)
+        N.check(N.lib.esmk_forward_packed_rows(eng.handle, N.ptr(eng.packed), N.ptr(tokens_flat), seg_ptr, n_seg, rows,
+                                               N.ptr(sel_rows), n, N.ptr(out), N.ptr(ws), ws.numel(), N.cur_stream()))
+        if return_logits:
+            logits = ws[off.value: off.value + n * V * 4].view(torch.float32).view(n, V).clone()
+            return out, logits
+    return out
+
+
+SEG_ALIGN = 16   # segment starts of a packed row space (esm_amd.packing, include/esmk.h)
+ROWS_ALIGN = 64  # rows of a packed row space
+
+
+def plan_packed_chunks(lengths_per_copy, budget=CHUNK_TOKENS):
+    """The packed row spaces of a list of copies, on the host: ``[(lo, hi, starts, rows)]`` — chunk c holds the copies
+    ``lo : hi`` of the input, IN INPUT ORDER, copy ``lo + j`` at rows ``starts[j] : starts[j] + length``.  Starts are ascending
+    multiples of 16, the first one 0; a chunk is filled greedily until the sum of the lengths, each rounded up to 16, would
+    pass ``budget`` rows (a copy that alone passes it gets a chunk of its own); ``rows`` is that sum rounded up to a multiple
+    of 64.  Lengths must be positive."""
+    if budget <= 0:
+        raise ValueError("plan_packed_chunks: the row budget must be positive")
+    chunks, lo, starts, used = [], 0, [], 0
+    for i, length in enumerate(lengths_per_copy):
+        length = int(length)
+        if length <= 0:
+            raise ValueError(f"plan_packed_chunks: copy {i} has length {length}: there is nothing to lay out")
+        need = (length + SEG_ALIGN - 1) // SEG_ALIGN * SEG_ALIGN
+        if starts and used + need > budget:
+            chunks.append((lo, i, starts, (used + ROWS_ALIGN - 1) // ROWS_ALIGN * ROWS_ALIGN))
+            lo, starts, used = i, [], 0
+        starts.append(used)
+        used += need
+    if starts:
+        chunks.append((lo, lo + len(starts), starts, (used + ROWS_ALIGN - 1) // ROWS_ALIGN * ROWS_ALIGN))
+    return chunks
+
+
+def _packs(model):
+    """False where ``forward_varlen`` would fall back to the padded forward whatever the batch: ESM-1 models and the f16x3
+    precision mode have no token-packed form.  ``varlen=True`` then runs the padded path."""
+    from .esm2 import _weight_split
+
+    return _weight_split() != 4 and not getattr(model, "_engine_esm1", 0)
+
+
+def _check_chunk_rows(varlen, chunk_rows):
+    if chunk_rows is not None and not varlen:
+        raise ValueError("chunk_rows sizes the packed row spaces of varlen=True; the padded path takes chunk")
+
+
+def _token_lengths(model, tok_cpu):
+    """int64 [B] on the host: 1 + the index of the last non-pad token of every sequence (0: nothing but padding) — the length
+    of its copies in a packed row space; interior <pad> tokens stay inside."""
+    T = tok_cpu.shape[1]
+    return (tok_cpu.ne(model.padding_idx) * torch.arange(1, T + 1)).amax(dim=1)
+
+
+def _packed_copies(model, tok, lengths, src, mask_off, mask_pos, sel_off, sel_pos, chunk_rows=None, return_logits=False):
+    """Token-packed masked copies: copy i is the first ``lengths[src[i]]`` tokens of sequence ``src[i]`` of ``tok`` with the
+    positions ``mask_pos[mask_off[i] : mask_off[i + 1]]`` replaced by <mask>, and the rows wanted from it are the positions
+    ``sel_pos[sel_off[i] : sel_off[i + 1]]``.  All arguments but ``tok`` are int64 vectors on the host.  Returns the
+    log-probabilities fp32 [n_rows, V] in the order of ``sel_pos`` (and the logits).  The lists of all chunks are uploaded
+    once; a chunk (``plan_packed_chunks``, ``chunk_rows`` rows at most, default ``CHUNK_TOKENS``) is a slice of them."""
+    from . import ops
+
+    dev = tok.device
+    V = model.alphabet_size
+    n = src.numel()
+    if n == 0 or sel_pos.numel() == 0:
+        empty = torch.empty((0, V), dtype=torch.float32, device=dev)
+        return (empty, empty.clone()) if return_logits else empty
+    copy_len = lengths[src]
+    chunks = plan_packed_chunks(copy_len.tolist(), CHUNK_TOKENS if chunk_rows is None else int(chunk_rows))
+    start = torch.tensor([s for _, _, starts, _ in chunks for s in starts], dtype=torch.int64)
+    seg_host = torch.stack([start, copy_len], dim=1).to(torch.int32).contiguous()
+    sel_count = sel_off[1:] - sel_off[:-1]
+    sel_rows = torch.repeat_interleave(start, sel_count) + sel_pos  # chunk-local flat rows
+    src32, start32, len32 = (t.to(torch.int32).to(dev) for t in (src, start, copy_len))
+    off32, pos32, sel32 = (t.to(torch.int32).to(dev) for t in (mask_off, mask_pos, sel_rows))
+    lps, logits = [], []
+    for lo, hi, _, rows in chunks:
+        r0, r1 = int(sel_off[lo]), int(sel_off[hi])
+        if r1 == r0:
+            continue
+        flat = ops.mask_rows_packed(tok, src32[lo:hi], start32[lo:hi], len32[lo:hi], off32[lo:hi + 1], pos32, rows,
+                                    model.mask_idx, model.padding_idx)
+        got = forward_rows_packed(model, flat, seg_host[lo:hi], sel32[r0:r1], return_logits=return_logits)
+        lps.append(got[0] if return_logits else got)
+        if return_logits:
+            logits.append(got[1])
+    lp = lps[0] if len(lps) == 1 else torch.cat(lps)
+    return (lp, logits[0] if len(logits) == 1 else torch.cat(logits)) if return_logits else lp
+
+
 def _position_rows(model, tok_cpu, positions, residues_only):
     """(src, pos): int64 CPU vectors of the (sequence, position) rows to score, in sequence-major order.
     positions None: every non-pad position (``residues_only``: without the <cls> / <eos> tokens the alphabet adds);
@@ -122,14 +255,21 @@ def _position_rows(model, tok_cpu, positions, residues_only):
     return src, pos
 
 
-def _masked_chunks(model, tokens, positions, chunk, residues_only):
+def _masked_chunks(model, tokens, positions, chunk, residues_only, varlen=False, chunk_rows=None):
     """Yields (src, pos, logprobs [n, V]) per chunk: device int64 vectors of the scored rows and the log-softmax of the
-    logits at ``pos`` from the forward in which that token alone is masked."""
+    logits at ``pos`` from the forward in which that token alone is masked.  ``varlen`` (on a model that has a token-packed
+    forward): the copies run token-packed, each as long as its own sequence, and ONE triple holds all rows."""
     from . import ops
 
     tok = _device_tokens(model, tokens)
     B, T = tok.shape
-    src, pos = _position_rows(model, tok.cpu(), positions, residues_only)
+    tok_cpu = tok.cpu()
+    src, pos = _position_rows(model, tok_cpu, positions, residues_only)
+    if varlen and _packs(model):
+        one = torch.arange(src.numel() + 1, dtype=torch.int64)  # one masked position, one selected row per copy
+        yield src.to(tok.device), pos.to(tok.device), _packed_copies(model, tok, _token_lengths(model, tok_cpu), src, one, pos,
+                                                                     one, pos, chunk_rows)
+        return
     if chunk is None:
         chunk = max(1, CHUNK_TOKENS // T)
     if chunk <= 0:
@@ -145,7 +285,7 @@ def _masked_chunks(model, tokens, positions, chunk, residues_only):
 
 
 @torch.no_grad()
-def masked_marginals(model, tokens, positions=None, chunk=None):
+def masked_marginals(model, tokens, positions=None, chunk=None, varlen=False, chunk_rows=None):
     """fp32 ``[B, T, V]``: row (b, i) is ``log_softmax`` of the logits at i from the forward in which token (b, i) alone is
     replaced by <mask> — ``all_token_probs`` of the reference's masked-marginals strategy (predict.py:205-215) for every
     sequence of the batch.
@@ -154,21 +294,41 @@ def masked_marginals(model, tokens, positions=None, chunk=None):
                iterable of ints (the same positions in every sequence) or one iterable per sequence.  A position on a <pad>
                token or outside the row raises ValueError; pad tokens are never scored.
     chunk      masked copies per forward call; default what fills the GPU (about 65536 tokens).
+    varlen     True: the copies run token-packed (module docstring), every copy as long as its own sequence (up to its last
+               non-pad token; interior <pad> tokens stay inside) instead of the batch's width — the form for sequences of
+               different lengths.  The table is the same, bit for bit.  ``chunk_rows``: rows of a packed row space (default
+               65536); ``chunk`` is then not used.  ESM-1 models and the f16x3 precision mode have no token-packed forward:
+               the padded path runs, as ``forward_varlen`` falls back to ``forward``.
     Rows that were not asked for are zero.  ``tokens`` may live on the CPU or the device; the result is on the model's device."""
+    _check_chunk_rows(varlen, chunk_rows)
     tok = _device_tokens(model, tokens)
     out = torch.zeros(tuple(tok.shape) + (model.alphabet_size,), dtype=torch.float32, device=tok.device)
-    for src, pos, lp in _masked_chunks(model, tok, positions, chunk, residues_only=False):
+    for src, pos, lp in _masked_chunks(model, tok, positions, chunk, residues_only=False, varlen=varlen, chunk_rows=chunk_rows):
         out[src, pos] = lp
     return out
 
 
 @torch.no_grad()
-def wt_marginals(model, tokens):
+def wt_marginals(model, tokens, varlen=False, chunk_rows=None):
     """fp32 ``[B, T, V]``: ``log_softmax(model(tokens)["logits"], -1)`` on the non-pad rows (the wt-marginals strategy,
-    predict.py:192-194), zero on <pad> rows: one forward per batch that fills the GPU, the head on the real rows only."""
+    predict.py:192-194), zero on <pad> rows: one forward per batch that fills the GPU, the head on the real rows only.
+    ``varlen`` / ``chunk_rows``: token-packed, as in ``masked_marginals``; the same table bit for bit."""
+    _check_chunk_rows(varlen, chunk_rows)
     tok = _device_tokens(model, tokens)
     B, T = tok.shape
     out = torch.zeros((B, T, model.alphabet_size), dtype=torch.float32, device=tok.device)
+    if varlen and _packs(model):
+        tok_cpu = tok.cpu()
+        lengths = _token_lengths(model, tok_cpu)
+        real = tok_cpu.ne(model.padding_idx)
+        src = lengths.nonzero().view(-1)  # a sequence of padding only contributes no segment
+        sel_off = torch.zeros((src.numel() + 1,), dtype=torch.int64)
+        sel_off[1:] = real.sum(1)[src].cumsum(0)
+        none = torch.zeros((src.numel() + 1,), dtype=torch.int64)  # nothing is masked
+        lp = _packed_copies(model, tok, lengths, src, none, torch.zeros((0,), dtype=torch.int64), sel_off,
+                            real.nonzero(as_tuple=True)[1], chunk_rows)
+        out[real.to(tok.device)] = lp  # both in (sequence, position) order
+        return out
     step = max(1, CHUNK_TOKENS // T)
     for lo in range(0, B, step):
         part = tok[lo:lo + step]
@@ -179,7 +339,7 @@ def wt_marginals(model, tokens):
 
 
 @torch.no_grad()
-def pseudo_log_likelihood(model, tokens, positions=None, chunk=None):
+def pseudo_log_likelihood(model, tokens, positions=None, chunk=None, varlen=False, chunk_rows=None):
     """fp64 ``[B]``: the sum over the scored positions of the masked-marginal log-probability of the TRUE token — the
     pseudo-log-likelihood of every sequence of the batch.
 
@@ -190,8 +350,22 @@ def pseudo_log_likelihood(model, tokens, positions=None, chunk=None):
     len(sequence) - 1 and len(sequence).  The default here scores every residue; ``positions=range(1, len(sequence) - 1)``
     scores the reference's positions.  The value summed is always the log-probability of the token that was masked
     (predict.py:143 looks it up as ``sequence[i]``, the residue one behind token position i).  The per-row values are
-    fp32, summed in fp64 as the reference sums Python floats."""
+    fp32, summed in fp64 as the reference sums Python floats.
+    ``varlen`` / ``chunk_rows``: token-packed, as in ``masked_marginals``.  The sum then runs through
+    ``esmk_op_sum_target_rows``: the rows of a sequence in ascending order of position, added by one lane — the sequential
+    fp64 sum of the true-token column of ``masked_marginals``, exactly, where the padded path's ``index_add_`` adds through
+    atomics in no fixed order."""
+    from . import ops
+
+    _check_chunk_rows(varlen, chunk_rows)
     tok = _device_tokens(model, tokens)
+    if varlen and _packs(model):
+        (src, pos, lp), = _masked_chunks(model, tok, positions, chunk, residues_only=True, varlen=True, chunk_rows=chunk_rows)
+        if src.numel() == 0:
+            return torch.zeros((tok.shape[0],), dtype=torch.float64, device=tok.device)
+        seq_off = torch.zeros((tok.shape[0] + 1,), dtype=torch.int64, device=tok.device)
+        seq_off[1:] = torch.bincount(src, minlength=tok.shape[0]).cumsum(0)  # rows are in (sequence, position) order
+        return ops.sum_target_rows(lp, tok[src, pos].to(torch.int32), seq_off.to(torch.int32))
     out = torch.zeros((tok.shape[0],), dtype=torch.float64, device=tok.device)
     for src, pos, lp in _masked_chunks(model, tok, positions, chunk, residues_only=True):
         true = tok[src, pos].unsqueeze(1)
@@ -200,7 +374,7 @@ def pseudo_log_likelihood(model, tokens, positions=None, chunk=None):
 
 
 @torch.no_grad()
-def masked_joint(model, tokens, position_sets, src=None, chunk=None, return_logits=False):
+def masked_joint(model, tokens, position_sets, src=None, chunk=None, return_logits=False, varlen=False, chunk_rows=None):
     """Joint masks: for every set s of ``position_sets`` (an iterable of token positions of sequence ``src[s]``; ``src`` None:
     sequence 0, and then B must be 1) ONE forward with all positions of the set replaced by <mask>, and the log-probabilities
     at those positions.  Returns ``(offsets, pos, logprobs)``:
@@ -211,9 +385,12 @@ def masked_joint(model, tokens, position_sets, src=None, chunk=None, return_logi
     ``return_logits``: a fourth value, the selected fp32 logits (the bits ``forward`` of the masked sequence gives those rows).
 
     An empty set, a position outside [0, T) or on a <pad> token raises ValueError.  ``chunk``: masked copies (sets) per
-    forward call; default what fills the GPU (about 65536 tokens).  The position lists are uploaded once for all chunks."""
+    forward call; default what fills the GPU (about 65536 tokens).  The position lists are uploaded once for all chunks.
+    ``varlen`` / ``chunk_rows``: token-packed, as in ``masked_marginals`` (sets of sequences of different lengths); the same
+    rows bit for bit."""
     from . import ops
 
+    _check_chunk_rows(varlen, chunk_rows)
     tok = _device_tokens(model, tokens)
     B, T = tok.shape
     dev = tok.device
@@ -248,6 +425,10 @@ def masked_joint(model, tokens, position_sets, src=None, chunk=None, return_logi
     if not sets:
         empty = torch.empty((0, V), dtype=torch.float32, device=dev)
         return (offsets, pos.to(dev), empty) + ((empty.clone(),) if return_logits else ())
+    if varlen and _packs(model):
+        got = _packed_copies(model, tok, _token_lengths(model, tok.cpu()), torch.tensor(src, dtype=torch.int64), offsets, pos,
+                             offsets, pos, chunk_rows, return_logits=return_logits)
+        return (offsets, pos.to(dev)) + (got if return_logits else (got,))
     # one upload for all chunks: the offsets index the whole position list, the chunks are slices of these
     pos_d = pos.to(dev)
     pos32, off32 = pos_d.to(torch.int32), offsets.to(device=dev, dtype=torch.int32)

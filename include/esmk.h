@@ -232,6 +232,32 @@ int esmk_forward_rows(esmk_model* m, const void* packed_dev, const int64_t* toke
                       const int32_t* sel_rows_dev, int n_sel, float* logprobs_out_dev, void* workspace_dev,
                       size_t workspace_bytes, void* stream);
 
+/* The same for a token-packed batch: the masked copies of a library of sequences of DIFFERENT lengths (pseudo-log-likelihood
+ * of designed sequences, insertion / deletion variants, wt-marginals over a FASTA file) laid back to back in one row space,
+ * so that the layer stack does no work on padding.  It is the reference's loop (predict.py:138-143,205-215: one B = 1 forward
+ * per masked position, one row kept) for every sequence of the library at once: the layer stack of esmk_forward_packed on
+ * the `rows` rows, the head of esmk_forward_rows on the n_sel selected ones.  Segment rules of esmk_forward_packed:
+ * rows % 64 == 0, 0 < rows <= 2^24; segment s occupies rows [segments_host[2s], segments_host[2s] + segments_host[2s+1]);
+ * segment 0 starts at row 0, starts are ascending multiples of 16, segments are disjoint with lengths > 0 inside `rows`;
+ * rows between segments hold pad_idx.  Every segment carries the bits of that sequence alone, so a selected row's logits
+ * and log-probabilities are bit for bit those esmk_forward_rows gives the same row of the same sequence in a padded batch.
+ *   tokens_dev       int64 [rows] (esmk_op_mask_rows_packed builds it on the device)
+ *   segments_host    int32 [n_seg][2] on the HOST (first row, length incl. <cls>/<eos>)
+ *   sel_rows_dev     int32 [n_sel] on the DEVICE: flat row indices into the packed row space, any order, repeats allowed;
+ *                    not validated on the host, the gather clamps each index to [0, rows)
+ *   logprobs_out_dev fp32 [n_sel, V]
+ *   workspace        esmk_packed_rows_workspace_bytes(m, segments_host, n_seg, rows, n_sel, &bytes, &logits_offset): the packed
+ *                    forward's workspace, then the gathered rows, their operand rows, the head scratch and the selected
+ *                    logits, which stay at byte offset *logits_offset (may be NULL) for the caller
+ * vocab <= 64.  ESM-2 at every head_dim and ESM-1b / ESM-1v handles, plain and LayerNorm-fold, fp16 / bf16 and the f16x2
+ * family.  MSA handles, ESM-1 (no_rope = ESMK_ESM1) handles and the f16x3 precision mode have no packed forward and are
+ * refused before any HIP call.  The whole call runs on `stream`; error messages name esmk_forward_packed_rows. */
+int esmk_packed_rows_workspace_bytes(const esmk_model* m, const int32_t* segments_host, int n_seg, int rows, int n_sel,
+                                     size_t* bytes, size_t* logits_offset);
+int esmk_forward_packed_rows(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev, const int32_t* segments_host,
+                             int n_seg, int rows, const int32_t* sel_rows_dev, int n_sel, float* logprobs_out_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- MSA Transformer (reference esm/model/msa_transformer.py:20-238, esm/axial_attention.py) -------- */
 
 /* Constructor arguments of MSATransformer (msa_transformer.py:88-144) + alphabet ids. */
@@ -639,6 +665,27 @@ int esmk_op_mask_rows_multi(const int64_t* tokens_dev, const int32_t* src_row_de
                             const int32_t* pos_dev, int64_t* out_dev, int B, int T, int n, int total, int mask_idx, void* stream);
 int esmk_op_score_rows(const float* logprobs_dev, const int32_t* wt_dev, const int32_t* mt_dev, const int32_t* var_off_dev,
                        double* out_dev, int n_rows, int n_var, int V, void* stream);
+
+/* Mixed-length libraries scored token-packed (esmk_forward_packed_rows).
+ * esmk_op_mask_rows_packed: the packed counterpart of esmk_op_mask_rows_multi.  out int64 [rows] is ONE packed row space; copy i
+ *   is the first seg_len[i] tokens of tokens[src_row[i], :] (tokens int64 [B,T]) written to out[seg_start[i] : seg_start[i] +
+ *   seg_len[i]] with every position of pos[pos_off[i] : pos_off[i+1]] replaced by mask_idx, and the gap behind the copy — up to
+ *   seg_start[i+1], or to `rows` behind the last copy — filled with pad_idx: every row from seg_start[0] on is written, nothing
+ *   is assumed about what out held (esmk_forward_packed wants pad_idx in gap rows).  src_row, seg_start, seg_len int32 [n],
+ *   pos_off int32 [n+1], pos int32 [total], all on the device and never read by the host: a source row outside [0,B) is
+ *   clamped, seg_start to [0,rows], seg_len to [0,T] and to the rows left behind seg_start (nothing is written outside
+ *   [0,rows)), the offsets to [0,total], a pair with hi < lo is an empty list, a position outside [0,seg_len) masks nothing,
+ *   a repeated position is harmless.  The copies' row ranges must be ascending and disjoint.
+ * esmk_op_sum_target_rows: out fp64 [n_seq], out[s] = sum over r in [off[s], off[s+1]), r ascending, of logprobs[r, target[r]];
+ *   logprobs fp32 [n_rows,V], target int32 [n_rows], off int32 [n_seq+1].  fp32 terms added in fp64 in index order by one lane
+ *   per sequence (no atomics).  target is clamped to [0,V), offsets to [0,n_rows]; an empty range gives 0.0.
+ * Refused before any HIP call: null pointers, B, T, n, n_rows, n_seq or V <= 0, total < 0, rows <= 0, rows % 64 != 0,
+ * rows > 2^24, B*T > 2^24. */
+int esmk_op_mask_rows_packed(const int64_t* tokens_dev, const int32_t* src_row_dev, const int32_t* seg_start_dev,
+                             const int32_t* seg_len_dev, const int32_t* pos_off_dev, const int32_t* pos_dev, int64_t* out_dev, int B,
+                             int T, int n, int total, int rows, int mask_idx, int pad_idx, void* stream);
+int esmk_op_sum_target_rows(const float* logprobs_dev, const int32_t* target_dev, const int32_t* off_dev, double* out_dev,
+                            int n_rows, int n_seq, int V, void* stream);
 
 /* The token front end — the kernels that turn tokens into the layer-0 activation and into the bookkeeping every later kernel
  * trusts — one launch at a time (tests/test_frontend_ops_gpu.py).  Validation, then the launchers the engines call.  Refused

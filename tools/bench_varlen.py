@@ -34,6 +34,11 @@ import esm  # noqa: E402
 from esm_amd.synth import ESM2_DIMS, synth_esm2_state_dict  # noqa: E402
 
 
+def uniref_like_lengths(n, g):
+    """n residue counts of the UniRef50-like length mix (module docstring), drawn from the generator ``g``."""
+    return torch.exp(torch.randn(n, generator=g) * 0.7 + 5.6).clamp(30, 1022).long().tolist()
+
+
 def make_batches(lengths, toks_per_batch, sort):
     order = sorted(range(len(lengths)), key=lambda i: lengths[i]) if sort else list(range(len(lengths)))
     batches, cur, mx = [], [], 0
@@ -62,7 +67,7 @@ def bench_maps(model, name, L, H, args):
     import statistics
 
     g = torch.Generator().manual_seed(args.seed)
-    mix = torch.exp(torch.randn(args.n, generator=g) * 0.7 + 5.6).clamp(30, 1022).long().tolist()
+    mix = uniref_like_lengths(args.n, g)
     # mixed batch: file order, the largest prefix whose padded fp32 maps stay inside the budget
     lengths = []
     for n in mix:
@@ -166,7 +171,7 @@ def main():
         return bench_maps(model, name, L, H, args)
 
     g = torch.Generator().manual_seed(args.seed)
-    lengths = torch.exp(torch.randn(args.n, generator=g) * 0.7 + 5.6).clamp(30, 1022).long().tolist()
+    lengths = uniref_like_lengths(args.n, g)
     batches = make_batches(lengths, args.toks_per_batch, not args.unsorted)
     toks = []
     for idx in batches:

@@ -8,6 +8,8 @@ batches that fill the GPU, the head of the model on the one masked row of every 
   python tools/score_throughput.py --variants 512 [--lengths 510] --out profiles/scoring_variants.log
   python tools/score_throughput.py --msa [--msa-shapes 16x257 400x301] --out profiles/msa_scoring_throughput.log
 
+  python tools/score_throughput.py --varlen-library 256 --out profiles/scoring_varlen.log
+
 Same library and same process for both sides; one warm-up of each side per shape, then --rounds timed rounds alternating the
 two sides, each round ending in a device synchronise; medians and the spread.  Residues/s counts the scored positions (all T
 tokens of the row).  Also recorded: the engine workspace each side grew to, the bytes of logits / log-probabilities each side
@@ -25,6 +27,13 @@ the one masked cell of every copy) against the reference's MSA loop (predict.py:
 forwards at B = 1, each building [1, R, C, V] logits and keeping one cell.  Two shapes R x C: a shallow MSA, where batching
 should pay, and a deep one at the reference's default scale (--msa-samples 400), where one copy already fills the GPU and
 what remains is the smaller head and the logits tensor that is not built.
+
+--varlen-library N: the pseudo-log-likelihood of a library of N sequences of DIFFERENT lengths (N draws, seeded, from the
+UniRef-like length mix of tools/bench_varlen.py: log-normal, median ~270 residues, clipped to [30, 1022], in file order):
+``model.pseudo_log_likelihood(tokens, varlen=True)`` (masked copies token-packed, each as long as its own sequence) against
+``varlen=False`` (every copy padded to the longest sequence of its call) on the same model, --library-per-call sequences per
+call as ``python -m esm_amd.score_sequences`` makes them.  Every round of both sides is printed, with the medians and the
+spread; a ratio inside the spread of the rounds is reported as such, not as a gain.
 """
 import argparse
 import os
@@ -232,6 +241,56 @@ def msa_mode(args):
     return lines
 
 
+def library_mode(args, model):
+    """--varlen-library N: the lines of the report."""
+    g = torch.Generator().manual_seed(args.seed)
+    from bench_varlen import uniref_like_lengths  # tools/ is the script's directory: the one length mix of both tools
+
+    lengths = uniref_like_lengths(args.varlen_library, g)
+    calls = []
+    for lo in range(0, len(lengths), args.library_per_call):
+        part = lengths[lo:lo + args.library_per_call]
+        t = torch.full((len(part), max(part) + 2), 1, dtype=torch.int64)
+        for r, n in enumerate(part):
+            t[r, 0] = 0
+            t[r, 1:n + 1] = torch.randint(4, 24, (n,), generator=g)
+            t[r, n + 1] = 2
+        calls.append(t.cuda())
+    copies = sum(lengths)  # one masked copy per residue
+    packed_tokens = sum(n * (n + 2) for n in lengths)
+    padded_tokens = sum(sum(part) * (max(part) + 2) for part in
+                        (lengths[lo:lo + args.library_per_call] for lo in range(0, len(lengths), args.library_per_call)))
+    sides = {"padded": lambda: [model.pseudo_log_likelihood(t) for t in calls],
+             "packed": lambda: [model.pseudo_log_likelihood(t, varlen=True) for t in calls]}
+    lines = ["pseudo-log-likelihood of %d sequences (seed %d; %d .. %d residues, median %d), %d per call: %d masked copies; "
+             "tokens through the layer stack: packed %d, padded %d (%.1f %% of them padding)" % (
+                 len(lengths), args.seed, min(lengths), max(lengths), sorted(lengths)[len(lengths) // 2], args.library_per_call,
+                 copies, packed_tokens, padded_tokens, 100.0 * (padded_tokens - packed_tokens) / padded_tokens)]
+    with torch.no_grad():
+        ref = {side: torch.cat(fn()) for side, fn in sides.items()}  # warm-up of both sides; their scores
+        rel = ((ref["packed"] - ref["padded"]).abs() / ref["padded"].abs()).max().item()
+        times = {side: [] for side in sides}
+        for r in range(args.rounds):
+            for side, fn in sides.items():
+                times[side].append(timed(fn)[0])
+            lines.append("  round %d: padded %9.1f ms   packed %9.1f ms" % (r, 1e3 * times["padded"][-1], 1e3 * times["packed"][-1]))
+    med = {side: statistics.median(t) for side, t in times.items()}
+    for side in sides:
+        lines.append("  %-7s median %9.1f ms [%.1f .. %.1f]  %9.0f masked copies/s  %7.2f sequences/s" % (
+            side, 1e3 * med[side], 1e3 * min(times[side]), 1e3 * max(times[side]), copies / med[side], len(lengths) / med[side]))
+    spread = {side: max(t) - min(t) for side, t in times.items()}
+    gain = med["padded"] - med["packed"]
+    bound = max(spread.values())
+    lines.append("  ratio padded / packed: %.2f x; padded - packed = %+.1f ms; spread (max - min) of the %d rounds: padded %.1f ms, "
+                 "packed %.1f ms; largest relative difference of the two score columns %.3e (the padded sum has no fixed order)" % (
+                     med["padded"] / med["packed"], 1e3 * gain, args.rounds, 1e3 * spread["padded"], 1e3 * spread["packed"], rel))
+    lines.append("  verdict: packed is %s (%+.1f ms against a spread of %.1f ms, the larger of the two sides)" % (
+        "FASTER than padded beyond the spread of the rounds" if gain > bound
+        else "SLOWER than padded beyond the spread of the rounds" if -gain > bound
+        else "NOT DISTINGUISHABLE from padded: the difference is inside the spread of the rounds", 1e3 * gain, 1e3 * bound))
+    return lines
+
+
 def timed(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -251,6 +310,10 @@ def main():
     ap.add_argument("--msa", action="store_true",
                     help="MSA Transformer (100M dims): model.msa_masked_marginals against one B = 1 forward per column")
     ap.add_argument("--msa-shapes", nargs="+", default=["16x257", "400x301"], metavar="RxC", help="MSA depth x columns (with <cls>)")
+    ap.add_argument("--varlen-library", type=int, default=0, metavar="N",
+                    help="pseudo-log-likelihood of N sequences of the UniRef-like length mix: varlen=True against varlen=False")
+    ap.add_argument("--library-per-call", type=int, default=256, help="(with --varlen-library) sequences per call")
+    ap.add_argument("--seed", type=int, default=0, help="(with --varlen-library) seed of the length mix and the residues")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -270,7 +333,10 @@ def main():
         model(synth_tokens(1, 30).cuda())  # the engine exists from here on: its LayerNorm-fold mode can be read
     lines = ["%s (L %d, E %d, H %d) on %s; LayerNorm fold %s; %d rounds after one warm-up, medians [min .. max]" % (
         name, L, E, H, torch.cuda.get_device_name(0), "on" if model.ln_fold_active() else "off", args.rounds)]
-    lines += variants_mode(args, model) if args.variants else masks_mode(args, model)
+    if args.varlen_library:
+        lines += library_mode(args, model)
+    else:
+        lines += variants_mode(args, model) if args.variants else masks_mode(args, model)
     report(lines, args.out)
 
 
