@@ -14,4 +14,6 @@ from .scoring import (masked_joint, masked_marginals, parse_variant, pseudo_log_
 from .msa_scoring import (msa_forward_rows, msa_masked_joint, msa_masked_marginals, msa_score_variants,  # noqa: F401
                           msa_wt_marginals)
 
+from .sampling import gibbs_sample, inpaint  # noqa: F401
+
 __version__ = "0.1.0"

@@ -247,6 +247,13 @@ SIGNATURES = {
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                 c_int, c_void_p]),
     "esmk_op_sum_target_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    # sampling: per-chain shuffles, one token per row of log-probabilities, the write-back (seeds and masks are uint64)
+    "esmk_op_permute_positions": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_uint64, c_int, c_void_p]),
+    "esmk_op_sample_rows": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint64, c_float, ctypes.c_uint64, c_int, c_void_p, c_void_p,
+                c_void_p, c_int, c_int, c_void_p]),
+    "esmk_op_commit_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     # the token front end, one launch at a time (tests/test_frontend_ops_gpu.py); segment tables are host arrays
     "esmk_op_seq_stats": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "esmk_op_packed_stats": (

@@ -883,6 +883,42 @@ int esmk_op_log_softmax_rows(const float* logits_dev, float* out_dev, const int3
     return 0;
 }
 
+// ---- sampling (sampling.hip; esm_amd/sampling.py) ---------------------------------------------------------------------
+int esmk_op_permute_positions(const int32_t* pos_off_dev, const int32_t* pos_in_dev, const int32_t* chain_id_dev,
+                              int32_t* perm_out_dev, int n_chain, int total, uint64_t seed, int epoch, void* stream) {
+    if (!pos_off_dev || !pos_in_dev || !chain_id_dev || !perm_out_dev) return fail("esmk_op_permute_positions: null argument");
+    if (n_chain <= 0 || total <= 0) return fail("esmk_op_permute_positions: n_chain and total must be positive");
+    if (epoch < 0) return fail("esmk_op_permute_positions: epoch must not be negative");
+    ESMK_TRY(launch_permute_positions(pos_off_dev, pos_in_dev, chain_id_dev, perm_out_dev, n_chain, total,
+                                      (unsigned long long)seed, epoch, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_sample_rows(const float* logprobs_dev, const int32_t* row_chain_dev, const int32_t* row_index_dev,
+                        const int32_t* exclude_dev, uint64_t allowed_mask, float inv_temperature, uint64_t seed, int step,
+                        int32_t* token_out_dev, float* logq_out_dev, float* u_out_dev, int n, int V, void* stream) {
+    if (!logprobs_dev || !row_chain_dev || !row_index_dev || !token_out_dev || !logq_out_dev)
+        return fail("esmk_op_sample_rows: null argument");
+    if (n <= 0 || n > ESMK_MAX_ROWS) return fail("esmk_op_sample_rows: n must be in 1 .. 2^24");
+    if (V <= 0 || V > 64) return fail("esmk_op_sample_rows: V must be in 1 .. 64 (one vocabulary entry per lane)");
+    if (!(inv_temperature >= 0.f) || inv_temperature > 3.0e38f)
+        return fail("esmk_op_sample_rows: inv_temperature must be finite and not negative (0: greedy)");
+    if (step < 0) return fail("esmk_op_sample_rows: step must not be negative");
+    ESMK_TRY(launch_sample_rows(logprobs_dev, row_chain_dev, row_index_dev, exclude_dev, (unsigned long long)allowed_mask,
+                                inv_temperature, (unsigned long long)seed, step, token_out_dev, logq_out_dev, u_out_dev, n, V,
+                                (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_commit_tokens(int64_t* tokens_dev, const int32_t* row_chain_slot_dev, const int32_t* pos_dev,
+                          const int32_t* token_dev, int n, int B, int T, void* stream) {
+    if (!tokens_dev || !row_chain_slot_dev || !pos_dev || !token_dev) return fail("esmk_op_commit_tokens: null argument");
+    if (n <= 0 || B <= 0 || T <= 0) return fail("esmk_op_commit_tokens: n, B and T must be positive");
+    if ((long long)B * T > ESMK_MAX_ROWS || n > ESMK_MAX_ROWS) return fail("esmk_op_commit_tokens: B*T or n exceeds 2^24 rows");
+    ESMK_TRY(launch_commit_tokens(tokens_dev, row_chain_slot_dev, pos_dev, token_dev, n, B, T, (hipStream_t)stream));
+    return 0;
+}
+
 // ---- the token front end as single ops (tests/test_frontend_ops_gpu.py) -------------------------------------------
 // Validation of what the engines guarantee their own calls, then the launchers of embed_stage (engine.hip), msa_embed_stage
 // (engine_msa.hip), ensure_rope / ensure_sinus and the row gather of the scoring paths.  Segment tables arrive as host arrays

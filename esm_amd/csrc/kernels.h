@@ -227,6 +227,21 @@ hipError_t launch_score_rows(const float* lp, const int* wt, const int* mt, cons
 // sequence (no atomics); target clamped to [0,V), offsets to [0,n_rows]
 hipError_t launch_sum_target_rows(const float* lp, const int* target, const int* off, double* out, int n_rows, int n_seq, int V,
                                   hipStream_t st);
+// sampling.hip — drawing sequences on the device (esm_amd/sampling.py).  Random numbers are Philox4x32-10 words addressed by
+// key = seed and counter = (chain id, epoch or step, purpose, index); purpose 0 = permutation, 1 = token draw.
+// perm_out[pos_off[c] : pos_off[c+1]] = Fisher-Yates shuffle of the same slice of pos_in (int32 [total]), one lane per chain;
+// pos_off int32 [n_chain+1] (clamped to [0,total]; hi < lo: empty), chain_id int32 [n_chain]
+hipError_t launch_permute_positions(const int* pos_off, const int* pos_in, const int* chain_id, int* perm_out, int n_chain,
+                                    int total, unsigned long long seed, int epoch, hipStream_t st);
+// one token per row of lp fp32 [n,V], V <= 64, from the candidates (bits of `allowed` below V, minus exclude[i]): tempered
+// inverse-CDF draw with the uniform of counter (row_chain[i], step, 1, row_index[i]), or the argmax for inv_temperature == 0;
+// token_out int32 [n] (-1: no candidate), logq_out fp32 [n], u_out fp32 [n] (optional); exclude int32 [n] (optional)
+hipError_t launch_sample_rows(const float* lp, const int* row_chain, const int* row_index, const int* exclude,
+                              unsigned long long allowed, float inv_temperature, unsigned long long seed, int step,
+                              int* token_out, float* logq_out, float* u_out, int n, int V, hipStream_t st);
+// tokens[slot[i], pos[i]] = token[i] on int64 [B,T]; token < 0 or pos outside [0,T) writes nothing, slot clamped to [0,B)
+hipError_t launch_commit_tokens(int64_t* tokens, const int* slot, const int* pos, const int* token, int n, int B, int T,
+                                hipStream_t st);
 // contact head (modules.py:27-41,338-357)
 hipError_t launch_contacts(const float* attn, const int64_t* tokens, const float* w,
                            const float* b, float* scratch, float* out, int B, int C, int T,

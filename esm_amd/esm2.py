@@ -717,6 +717,23 @@ class ESM2(nn.Module):
         return scoring.score_variants(self, alphabet, sequence, variants, strategy=strategy, offset_idx=offset_idx, sep=sep,
                                       chunk=chunk)
 
+    # drawing sequences (esm_amd/sampling.py): Gibbs sweeps and mask in-painting, every step on the device
+    def gibbs_sample(self, tokens, sweeps, per_step=1, positions=None, temperature=1.0, allowed=None, force_new=False, seed=0,
+                     chain_ids=None, return_trajectory=False):
+        """``esm_amd.sampling.gibbs_sample``: the final tokens [B, T] of ``sweeps`` Gibbs sweeps over every chain's positions."""
+        from . import sampling
+
+        return sampling.gibbs_sample(self, tokens, sweeps, per_step=per_step, positions=positions, temperature=temperature,
+                                     allowed=allowed, force_new=force_new, seed=seed, chain_ids=chain_ids,
+                                     return_trajectory=return_trajectory)
+
+    def inpaint(self, tokens, per_step=1, temperature=1.0, allowed=None, seed=0, chain_ids=None, return_trajectory=False):
+        """``esm_amd.sampling.inpaint``: ``tokens`` [B, T] with every <mask> position filled by a draw from the model."""
+        from . import sampling
+
+        return sampling.inpaint(self, tokens, per_step=per_step, temperature=temperature, allowed=allowed, seed=seed,
+                                chain_ids=chain_ids, return_trajectory=return_trajectory)
+
     def profile_begin(self):
         """Arm per-kernel-class HIP-event timing of the following forward calls (bench.py)."""
         from . import _native as N

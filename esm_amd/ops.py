@@ -553,6 +553,75 @@ def sum_target_rows(logprobs, target, offsets):
     return out
 
 
+# ---- sampling (include/esmk.h: esmk_op_permute_positions, esmk_op_sample_rows, esmk_op_commit_tokens) -----------------------
+def _seed64(seed):
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed {seed} is outside [0, 2^64)")
+    return seed
+
+
+def permute_positions(pos_offsets, positions, chain_ids, seed=0, epoch=0):
+    """int32 [total]: chain c's slice ``pos_offsets[c] : pos_offsets[c + 1]`` is a Fisher-Yates shuffle of the same slice of
+    ``positions``, drawn from Philox counters (chain_ids[c], epoch, 0, i) under the key ``seed`` — it depends on nothing else,
+    so a chain gets the same order alone and in any batch.  pos_offsets int32 [n_chain + 1] (clamped to [0, total]; a
+    descending pair is an empty list), positions int32 [total], chain_ids int32 [n_chain], all on the device.  Elements outside
+    every slice are zero."""
+    _req_cuda(pos_offsets, positions, chain_ids)
+    for t in (pos_offsets, positions, chain_ids):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
+    n_chain = chain_ids.numel()
+    assert n_chain >= 1 and pos_offsets.numel() == n_chain + 1
+    total = positions.numel()
+    out = torch.zeros((total,), dtype=torch.int32, device=positions.device)
+    if total == 0:
+        return out
+    N.check(N.lib.esmk_op_permute_positions(N.ptr(pos_offsets), N.ptr(positions), N.ptr(chain_ids), N.ptr(out), n_chain, total,
+                                            _seed64(seed), int(epoch), N.cur_stream()))
+    return out
+
+
+def sample_rows(logprobs, row_chain, row_index, allowed_mask, inv_temperature=1.0, seed=0, step=0, exclude=None, want_u=True):
+    """One token per row of ``logprobs`` fp32 [n, V] (V <= 64): ``(token int32 [n], logq fp32 [n], u fp32 [n] or None)``.
+    The candidates of a row are the bits of the Python int ``allowed_mask`` below V, minus ``exclude[i]`` (int32 [n]; -1:
+    none).  ``inv_temperature`` > 0: the inverse-CDF draw of include/esmk.h from softmax(logprobs * inv_temperature) over the
+    candidates with the uniform of Philox counter (row_chain[i], step, 1, row_index[i]) under the key ``seed``; 0: the
+    candidate with the largest log-probability (ties: the lowest index).  No candidate: token -1.  ``logq`` is the
+    log-probability of the drawn token under the distribution it was drawn from."""
+    _req_cuda(logprobs, row_chain, row_index, exclude)
+    assert logprobs.dtype == torch.float32 and logprobs.dim() == 2 and logprobs.is_contiguous()
+    n, V = logprobs.shape
+    for t in (row_chain, row_index) + ((exclude,) if exclude is not None else ()):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.numel() == n and t.is_contiguous()
+    allowed_mask = int(allowed_mask)
+    if not 0 <= allowed_mask < 2 ** 64:
+        raise ValueError("allowed_mask is a bitset over at most 64 vocabulary entries")
+    dev = logprobs.device
+    token = torch.empty((n,), dtype=torch.int32, device=dev)
+    logq = torch.empty((n,), dtype=torch.float32, device=dev)
+    u = torch.empty((n,), dtype=torch.float32, device=dev) if want_u else None
+    N.check(N.lib.esmk_op_sample_rows(N.ptr(logprobs), N.ptr(row_chain), N.ptr(row_index), N.ptr(exclude), allowed_mask,
+                                      float(inv_temperature), _seed64(seed), int(step), N.ptr(token), N.ptr(logq), N.ptr(u), n,
+                                      V, N.cur_stream()))
+    return token, logq, u
+
+
+def commit_tokens(tokens, slots, positions, token):
+    """In place: ``tokens[slots[i], positions[i]] = token[i]`` on int64 [B, T]; slots, positions, token int32 [n] on the
+    device.  A row with token < 0 or a position outside [0, T) writes nothing; a slot outside [0, B) is clamped.  The (slot,
+    position) pairs must be distinct.  Returns ``tokens``."""
+    _req_cuda(tokens, slots, positions, token)
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.is_contiguous()
+    n = token.numel()
+    for t in (slots, positions, token):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.numel() == n and t.is_contiguous()
+    B, T = tokens.shape
+    if n == 0:
+        return tokens
+    N.check(N.lib.esmk_op_commit_tokens(N.ptr(tokens), N.ptr(slots), N.ptr(positions), N.ptr(token), n, B, T, N.cur_stream()))
+    return tokens
+
+
 # ---- the token front end, one launch at a time (include/esmk.h: esmk_op_seq_stats ... esmk_op_gather_rows) -----------------
 def _out(t, shape, dtype, device):
     """The caller's output buffer (checked), or a fresh one: callers that look at the memory behind an output pass their own."""

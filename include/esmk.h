@@ -687,6 +687,40 @@ int esmk_op_mask_rows_packed(const int64_t* tokens_dev, const int32_t* src_row_d
 int esmk_op_sum_target_rows(const float* logprobs_dev, const int32_t* target_dev, const int32_t* off_dev, double* out_dev,
                             int n_rows, int n_seq, int V, void* stream);
 
+/* Drawing sequences from the model (esm_amd/sampling.py: Gibbs sweeps, mask in-painting).  A sampling step is
+ * esmk_op_mask_rows_multi -> esmk_forward_rows -> esmk_op_sample_rows -> esmk_op_commit_tokens on one stream; the host reads
+ * nothing in between.  Random numbers are plain Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key bumps 0x9E3779B9 /
+ * 0xBB67AE85, ten rounds) with key = (seed & 0xffffffff, seed >> 32) and counter = (chain id, epoch or step, purpose, index),
+ * purpose 0 = permutation, 1 = token draw.  A number depends on these words alone — never on a thread or block index, the
+ * batch size or the launch geometry — so a chain draws the same tokens alone and inside any batch.  A uniform is
+ * u = (word0 >> 8) * 2^-24: exact in fp32, in [0,1).  No atomics; all list data is device data the host never reads.
+ * esmk_op_permute_positions: per chain c the slice [pos_off[c], pos_off[c+1]) of perm_out int32 [total] is a Fisher-Yates
+ *   shuffle of the same slice of pos_in int32 [total]: for i = len-1 .. 1, j = mulhi32(word0 at counter (chain_id[c], epoch,
+ *   0, i), i+1), swap elements i and j.  pos_off int32 [n_chain+1] (clamped to [0,total]; a pair with hi < lo is an empty
+ *   list), chain_id int32 [n_chain].  One lane per chain; integer arithmetic only.  pos_in and perm_out must not overlap.
+ * esmk_op_sample_rows: one token per row of logprobs fp32 [n,V], V <= 64.  row_chain / row_index int32 [n]: counter words 0
+ *   and 3 of the row's uniform (word 1 = step).  The candidates are the bits of allowed_mask below V, minus the token
+ *   exclude[i] (exclude int32 [n] or NULL; -1 or any value outside [0,V): none).  inv_temperature > 0: z_v = logprobs[v] *
+ *   inv_temperature, m = max z, w_v = expf(z_v - m) over the candidates, added in fp32 in ascending token order; the token is
+ *   the first candidate whose running sum exceeds u * total, the last candidate if none does; logq = z_tok - m - log(total),
+ *   that value taken in fp64 from the fp32 inputs and rounded to fp32 once.
+ *   inv_temperature == 0: the candidate with the largest logprobs, ties to the lowest index; logq = 0.  No candidate: token
+ *   -1, logq 0.  A row whose candidates all hold -inf (no log_softmax of finite logits gives one) has no distribution: with
+ *   inv_temperature > 0 it returns the last candidate and logq = NaN, greedy the lowest candidate.  token_out int32 [n],
+ *   logq_out fp32 [n], u_out fp32 [n] or NULL.
+ * esmk_op_commit_tokens: tokens[slot[i], pos[i]] = token[i] on tokens int64 [B,T]; slot, pos, token int32 [n].  A row with
+ *   token < 0 or a position outside [0,T) writes nothing; a slot outside [0,B) is clamped.  The (slot, pos) pairs of one
+ *   call must be distinct.
+ * Refused before any HIP call: null pointers (exclude_dev and u_out_dev may be NULL), n_chain, total, n, B or T <= 0,
+ * V outside 1 .. 64, a negative epoch or step, an inv_temperature that is negative or not finite, n or B*T > 2^24. */
+int esmk_op_permute_positions(const int32_t* pos_off_dev, const int32_t* pos_in_dev, const int32_t* chain_id_dev,
+                              int32_t* perm_out_dev, int n_chain, int total, uint64_t seed, int epoch, void* stream);
+int esmk_op_sample_rows(const float* logprobs_dev, const int32_t* row_chain_dev, const int32_t* row_index_dev,
+                        const int32_t* exclude_dev, uint64_t allowed_mask, float inv_temperature, uint64_t seed, int step,
+                        int32_t* token_out_dev, float* logq_out_dev, float* u_out_dev, int n, int V, void* stream);
+int esmk_op_commit_tokens(int64_t* tokens_dev, const int32_t* row_chain_slot_dev, const int32_t* pos_dev,
+                          const int32_t* token_dev, int n, int B, int T, void* stream);
+
 /* The token front end — the kernels that turn tokens into the layer-0 activation and into the bookkeeping every later kernel
  * trusts — one launch at a time (tests/test_frontend_ops_gpu.py).  Validation, then the launchers the engines call.  Refused
  * before any HIP call: null pointers (the ones named optional below may be NULL), B, T, R, C, n, rows, N, vocab or npos <= 0,
