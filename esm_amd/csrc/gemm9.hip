@@ -229,7 +229,7 @@ ESMK_DEV void epilogue9_f32(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base,
     }
 }
 
-// operand-dtype outputs (EPI_STORE_T, EPI_GELU_T, EPI_QKV_ROPE): 8 rounds of 32 rows x 64 columns.  A round's 8 KiB
+// operand-dtype outputs (EPI_STORE_T, EPI_GELU_T, EPI_QKV_ROPE): 8 rounds of 32 rows x 64 columns (V^T: epilogue9_vt below).  A round's 8 KiB
 // fp32 image has 256-byte rows, 16-byte chunk c of row r at slot c ^ (r & 7): conflict free for the quad writes
 // (8 lanes = 8 rows of one chunk; lane l of a 16 x 16 block holds row l & 15, chunk 4 nq + (l >> 4)) and for the
 // row-major reads (16 lanes = 16 different chunks).
@@ -245,7 +245,7 @@ template <typename T, int EPI, bool FULL, bool NT = false, int NMI = 8, int RR =
 ESMK_DEV void epilogue9_t(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base, int n_base, int lane, char* wl) {
     static_assert(!X3O || (EPI == EPI_GELU_T && !LNF), "hi | hi | lo output rows: the plain GELU epilogue");
     using V8 = typename Op<T>::v8;
-    float bs1[8], bs2[8];  // LNF: bias + bias2 of the lane's columns in the current 64-column half (q: times the scale)
+    float bs1[8];  // LNF, STORE / GELU: bias + bias2 of the lane's columns in the current 64-column half
     // LNF: rstd of every row this lane visits (row RR i + RPI it + lane / LPR of the block), all loads in flight at once —
     // one dependent load per row visit cost ~7 k cycles per tile (profiles/r4_ln_fold_first.log)
     constexpr int LPR = EPI == EPI_QKV_ROPE ? 4 : 8;  // lanes per row of a round
@@ -265,13 +265,87 @@ ESMK_DEV void epilogue9_t(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base, i
         }
     }
     constexpr int NI = NMI * 16 / RR;  // row blocks of RR rows
-    constexpr int NR = 2 * NI;         // rounds: [64-column half][row block]
+    constexpr int NR = 2 * NI;         // rounds: [64-column half][row block]; RoPE: [row block][64-column half]
     constexpr int MB = RR / 16;        // 16-row MFMA blocks per round
     const int g4 = lane >> 4, l16 = lane & 15;
     if constexpr (!FULL)
         if (m_base >= p.M) return;  // wave uniform
+    // RoPE: everything a row visit needs from memory is on its way before the stores of the visit before it, so no wait
+    // ever covers the wave's own output stores (stores count in the same in-order vmcnt as loads: a table load issued
+    // BEHIND a store and needed at once waits for that store's acknowledgement first — 32 such round trips per tile).
+    //   * the rows' positions (sequence index, place in the sequence, rotary position / row_pos) are formed once per row,
+    //     up front, for both 64-column halves;
+    //   * the rounds run [row block][half]: a row's cos / sin (16 floats per lane) are fetched once and serve both halves;
+    //     the tables of row block i + 1 replace those of block i right after their last use (second half of block i),
+    //     ahead of that visit's stores — a full round before they are needed, with no register beyond the NIT x 16;
+    //   * LNF: (bias + bias2) * scale of both halves is formed before the first round.
+    constexpr bool ROPE = EPI == EPI_QKV_ROPE;
+    constexpr int NV = ROPE ? NI * NIT : 1;  // row visits of a lane per half
+    int rtt[NV];                             // rotary position of the row
+    unsigned rro[NV];                        // row of q / k [B,H,T,64] for head 0: b H T + (m - b T)
+    f32x4 tab[ROPE ? NIT : 1][4];            // current row block: cos (dims 8 g4 .., + 4), sin (same)
+    float bsq1[ROPE && LNF ? 2 : 1][8], bsq2[ROPE && LNF ? 2 : 1][8];
+    float sch[2] = {1.0f, 1.0f};
+    T* qkh[2] = {nullptr, nullptr};
+    int headh[2] = {0, 0};
+    auto load_tab = [&](int it, int i) ESMK_INL {
+        const size_t o = (size_t)rtt[i * NIT + it] * 32 + 8 * (lane & 3);
+#pragma unroll
+        for (int e2 = 0; e2 < 2; ++e2) {
+            tab[it][e2] = *reinterpret_cast<const f32x4*>(p.cos + o + 4 * e2);
+            tab[it][2 + e2] = *reinterpret_cast<const f32x4*>(p.sin + o + 4 * e2);
+        }
+    };
+    if constexpr (ROPE) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const int mm = m_base + RR * (v / NIT) + 16 * (v % NIT) + (lane >> 2);
+            const int m = FULL ? mm : min(mm, p.M - 1);
+            const int b = m / p.T;
+            rtt[v] = m - b * p.T;
+            rro[v] = (unsigned)(b * p.H) * (unsigned)p.T + (unsigned)rtt[v];
+        }
+        if (p.row_pos != nullptr) {  // token-packed batches: the row's place in its segment
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                const int mm = m_base + RR * (v / NIT) + 16 * (v % NIT) + (lane >> 2);
+                rtt[v] = p.row_pos[FULL ? mm : min(mm, p.M - 1)];
+            }
+        }
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+            const int nb = n_base + 64 * hf;
+            const bool live = FULL || nb < p.N;  // wave uniform
+            // the 64 columns are one head (head_dim 64)
+            const int which = nb / p.E;  // 0 q, 1 k (wave uniform)
+            headh[hf] = (nb - which * p.E) >> 6;
+            qkh[hf] = reinterpret_cast<T*>(which == 0 ? p.q : p.k);
+            sch[hf] = which == 0 ? p.scaling : 1.0f;
+            if constexpr (LNF) {
+                const int c0 = (live ? nb : n_base) + 8 * (lane & 3);
+                f32x4 a[2], b[2];
+#pragma unroll
+                for (int e2 = 0; e2 < 2; ++e2)
+                    a[e2] = *reinterpret_cast<const f32x4*>(p.bias + c0 + 4 * e2), b[e2] = *reinterpret_cast<const f32x4*>(p.bias + c0 + 32 + 4 * e2);
+                if (p.bias2 != nullptr) {
+#pragma unroll
+                    for (int e2 = 0; e2 < 2; ++e2) {
+                        const f32x4 a2 = *reinterpret_cast<const f32x4*>(p.bias2 + c0 + 4 * e2), b2 = *reinterpret_cast<const f32x4*>(p.bias2 + c0 + 32 + 4 * e2);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) a[e2][e] += a2[e], b[e2][e] += b2[e];
+                    }
+                }
+#pragma unroll
+                for (int e2 = 0; e2 < 2; ++e2)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) bsq1[hf][4 * e2 + e] = a[e2][e] * sch[hf], bsq2[hf][4 * e2 + e] = b[e2][e] * sch[hf];
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) load_tab(it, 0);
+    }
     auto write_round = [&](int r) ESMK_INL {
-        const int hf = r / NI, i = r % NI;
+        const int hf = ROPE ? r % 2 : r / NI, i = ROPE ? r / 2 : r % NI;
 #pragma unroll
         for (int mi2 = 0; mi2 < MB; ++mi2)
 #pragma unroll
@@ -306,64 +380,44 @@ ESMK_DEV void epilogue9_t(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base, i
         }
     };
     auto finish_round = [&](int rd, const f32x4 (&raw)[8]) ESMK_INL {
-        const int hf = rd / NI, i = rd % NI;
+        const int hf = ROPE ? rd % 2 : rd / NI, i = ROPE ? rd / 2 : rd % NI;
         const int nb = n_base + 64 * hf;
-        if constexpr (!FULL)
-            if (nb >= p.N) return;  // wave uniform
-        if constexpr (EPI == EPI_QKV_ROPE) {
-            // the 64 columns are one head (head_dim 64): dims d and d + 32 rotate together
+        if constexpr (ROPE) {
+            // dims d and d + 32 rotate together
             // (multihead_attention.py:261 q scaling, rotary_embedding.py:11-20 x*cos + rotate_half(x)*sin)
-            const int which = nb / p.E;  // 0 q, 1 k (wave uniform)
-            const int head = (nb - which * p.E) >> 6;
-            T* qk = reinterpret_cast<T*>(which == 0 ? p.q : p.k);
-            const float sc = which == 0 ? p.scaling : 1.0f;
-            if constexpr (LNF) {
-                if (i == 0) {  // first round of this 64-column half
-                    const int c0 = nb + 8 * (lane & 3);
+            const bool live = FULL || nb < p.N;  // wave uniform
+            const float sc = sch[hf];
 #pragma unroll
-                    for (int e2 = 0; e2 < 2; ++e2) {
-                        f32x4 a = *reinterpret_cast<const f32x4*>(p.bias + c0 + 4 * e2), b = *reinterpret_cast<const f32x4*>(p.bias + c0 + 32 + 4 * e2);
-                        if (p.bias2 != nullptr) {
-                            const f32x4 a2 = *reinterpret_cast<const f32x4*>(p.bias2 + c0 + 4 * e2), b2 = *reinterpret_cast<const f32x4*>(p.bias2 + c0 + 32 + 4 * e2);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) a[e] += a2[e], b[e] += b2[e];
-                        }
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) bs1[4 * e2 + e] = a[e] * sc, bs2[4 * e2 + e] = b[e] * sc;
-                    }
-                }
-            }
-#pragma unroll
-            for (int it = 0; it < RR / 16; ++it) {
-                const int slot = it * 64 + lane;
-                const int r = slot >> 2, g4 = slot & 3;  // row of the round, dims [8 g4, 8 g4 + 8)
-                const int mm = m_base + RR * i + r;
-                const int m = FULL ? mm : min(mm, p.M - 1);
-                const int b = m / p.T;
-                // rotary position: the row's place in its sequence, or (token-packed batches) in its segment
-                const int tt = p.row_pos != nullptr ? p.row_pos[m] : m - b * p.T;
+            for (int it = 0; it < NIT; ++it) {
+                const int g4 = lane & 3;  // row (64 it + lane) / 4 of the round, dims [8 g4, 8 g4 + 8)
+                const int mm = m_base + RR * i + 16 * it + (lane >> 2);
                 float rs = sc;
                 if constexpr (LNF) rs = rsv[i][it] * sc;
-                float y1[8], y2[8];
-#pragma unroll
-                for (int e2 = 0; e2 < 2; ++e2) {
-                    const f32x4 c = *reinterpret_cast<const f32x4*>(p.cos + (size_t)tt * 32 + 8 * g4 + 4 * e2);
-                    const f32x4 s = *reinterpret_cast<const f32x4*>(p.sin + (size_t)tt * 32 + 8 * g4 + 4 * e2);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        // the contraction hipcc chose for epilogue8's `a1*c - a2*s`, `a2*c + a1*s`, spelled out:
-                        // bit-identical q / k whichever kernel ran (packed == padded == alone stays exact)
-                        const float x1 = LNF ? __builtin_fmaf(raw[4 * it + e2][e], rs, bs1[4 * e2 + e]) : raw[4 * it + e2][e] * sc;
-                        const float x2 = LNF ? __builtin_fmaf(raw[4 * it + 2 + e2][e], rs, bs2[4 * e2 + e]) : raw[4 * it + 2 + e2][e] * sc;
-                        y1[4 * e2 + e] = __builtin_fmaf(x1, c[e], -(x2 * s[e]));
-                        y2[4 * e2 + e] = __builtin_fmaf(x2, c[e], x1 * s[e]);
-                    }
-                }
                 V8 o1, o2;
+                if (live) {
+                    float y1[8], y2[8];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) o1[e] = Op<T>::from(y1[e]), o2[e] = Op<T>::from(y2[e]);
-                if (FULL || mm < p.M) {
-                    T* dst = qk + ((size_t)(b * p.H + head) * p.T + (m - b * p.T)) * 64 + 8 * g4;
+                    for (int e2 = 0; e2 < 2; ++e2) {
+                        const f32x4 c = tab[it][e2], s = tab[it][2 + e2];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            // the contraction hipcc chose for epilogue8's `a1*c - a2*s`, `a2*c + a1*s`, spelled out:
+                            // bit-identical q / k whichever kernel ran (packed == padded == alone stays exact)
+                            const float x1 = LNF ? __builtin_fmaf(raw[4 * it + e2][e], rs, bsq1[LNF ? hf : 0][4 * e2 + e]) : raw[4 * it + e2][e] * sc;
+                            const float x2 = LNF ? __builtin_fmaf(raw[4 * it + 2 + e2][e], rs, bsq2[LNF ? hf : 0][4 * e2 + e]) : raw[4 * it + 2 + e2][e] * sc;
+                            y1[4 * e2 + e] = __builtin_fmaf(x1, c[e], -(x2 * s[e]));
+                            y2[4 * e2 + e] = __builtin_fmaf(x2, c[e], x1 * s[e]);
+                        }
+                    }
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) o1[e] = Op<T>::from(y1[e]), o2[e] = Op<T>::from(y2[e]);
+                }
+                // the next row block's tables take the place of this block's after their last use, AHEAD of the stores
+                __builtin_amdgcn_sched_barrier(0);
+                if (hf == 1 && i + 1 < NI) load_tab(it, i + 1);
+                __builtin_amdgcn_sched_barrier(0);
+                if (live && (FULL || mm < p.M)) {
+                    T* dst = qkh[hf] + ((size_t)rro[i * NIT + it] + (size_t)headh[hf] * p.T) * 64 + 8 * g4;
                     if constexpr (NT) {
                         __builtin_nontemporal_store(o1, reinterpret_cast<V8*>(dst));
                         __builtin_nontemporal_store(o2, reinterpret_cast<V8*>(dst + 32));
@@ -374,6 +428,8 @@ ESMK_DEV void epilogue9_t(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base, i
                 }
             }
         } else {
+            if constexpr (!FULL)
+                if (nb >= p.N) return;  // wave uniform
             T* out = reinterpret_cast<T*>(p.out);
             if constexpr (LNF) {
                 if (i == 0) {  // first round of this 64-column half
@@ -433,6 +489,160 @@ ESMK_DEV void epilogue9_t(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base, i
 #pragma unroll
     for (int rd = 0; rd < NR; ++rd) {
         f32x4 raw[8];
+        read_round(raw);
+        if (rd + 1 < NR) write_round(rd + 1);
+        __builtin_amdgcn_sched_barrier(0);  // the next round's LDS traffic is issued before this round's arithmetic
+        finish_round(rd, raw);
+    }
+}
+
+// V^T (EPI_V_T and the v tiles of EPI_QKV_ALL): vt[b][head][dv][Tp], keys permuted inside groups of 16 (4-groups 1 and 2
+// swapped) — the values, addresses and rounding of epilogue8m's EPI_V_T branch (gemm_epi.h), in gemm9's own scheme.
+// V^T tiles run the MFMAs the other way round: acc[nj][mi][r]: n = n_base + 16 nj + (lane & 15), m = m_base + 16 mi +
+// 4 (lane >> 4) + r — a quad is 4 consecutive tokens of one channel.  A round's image is CH channels x 64 tokens of fp32
+// (256-byte rows, chunk c of row r at slot c ^ (r & 7): epilogue9_t's geometry with channels for rows), CH = 32 (8 KiB
+// slice) or 16 (4 KiB: half-height kernel); rounds run [64-token half][channel group].  Written from the AGPRs by
+// ds_write_b128 (conflict free: 8 lanes = 8 rows of one chunk); read back 8 lanes per channel, lane c8 taking the two
+// token quads that make output positions [8 c8, 8 c8 + 8) of the piece — quads (c8 & 1) and (c8 & 1) + 2 of 16-group
+// c8 >> 1, which IS the key permutation — so a channel's 64 tokens leave as one whole 128-byte line per 8 lanes.  (The
+// ds_read_b128 lane groups {0-3, 12-15, 20-27}, ... meet rows 4k .. 4k + 3 with chunk sets that differ in bit 1 of
+// row & 7 pairwise: conflict free.)  The next round's writes are issued behind this round's reads; every ln_rstd, bias
+// and bias2 load of the block is in flight before the first round, so the rounds hold nothing but stores in the vector
+// memory queue and no wait covers them.
+// Aligned form (T % 32 == 0): a lane's 8 tokens lie in one sequence and one 16-group.  Any T: per-element stores, the
+// key permutation applied per token (offsets formed once per 64-token half).
+// LNF: value = fmaf(acc, ln_rstd[token], bias + bias2), else acc + bias; then ONE conversion (see epilogue8m on
+// v_fma_mixlo_f16: every element rounds the same way whatever its lane or register).
+// COL0: the v block starts at column col0 of the launch's N and bias; n_base is counted from there.
+template <typename T, bool FULL, bool NT, int NMI, bool LNF, bool COL0>
+ESMK_DEV void epilogue9_vt(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base, int n_base, int lane, char* wl, int col0) {
+    using V8 = typename Op<T>::v8;
+    constexpr int NTH = NMI / 4;        // 64-token halves of the block
+    constexpr int CH = NMI == 8 ? 32 : 16;  // channels per round
+    constexpr int NCG = 128 / CH;       // channel groups
+    constexpr int NR = NTH * NCG;
+    constexpr int NIT = CH / 8;         // 8-channel passes of a round
+    const int g4 = lane >> 4, l16 = lane & 15;
+    const int c8 = lane & 7, r8 = lane >> 3;
+    const int ncols = COL0 ? p.N - col0 : p.N;  // channels of the v block
+    if constexpr (!FULL)
+        if (m_base >= p.M || n_base >= ncols) return;  // wave uniform
+    T* vt = reinterpret_cast<T*>(p.vt);
+    const bool aligned = FULL || (p.T % 32 == 0);
+    // bias (+ bias2) of the lane's channels: CH cg + 8 it + lane / 8
+    float bvc[NCG][NIT];
+#pragma unroll
+    for (int cg = 0; cg < NCG; ++cg)
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int n = n_base + CH * cg + 8 * it + r8;
+            bvc[cg][it] = p.bias[(COL0 ? col0 : 0) + (FULL ? n : min(n, ncols - 1))];
+        }
+    if constexpr (LNF) {
+        if (p.bias2 != nullptr) {
+#pragma unroll
+            for (int cg = 0; cg < NCG; ++cg)
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    const int n = n_base + CH * cg + 8 * it + r8;
+                    bvc[cg][it] += p.bias2[(COL0 ? col0 : 0) + (FULL ? n : min(n, ncols - 1))];
+                }
+        }
+    }
+    // rstd of the lane's 8 tokens per half: quads (c8 & 1) + 2 e2 of 16-group c8 >> 1 (the buffer is padded to whole
+    // 256-row tiles, so the 4-token loads never leave it)
+    f32x4 rs[LNF ? NTH : 1][2];
+    if constexpr (LNF) {
+#pragma unroll
+        for (int th = 0; th < NTH; ++th)
+#pragma unroll
+            for (int e2 = 0; e2 < 2; ++e2)
+                rs[th][e2] = *reinterpret_cast<const f32x4*>(p.ln_rstd + m_base + 64 * th + 16 * (c8 >> 1) + 4 * ((c8 & 1) + 2 * e2));
+    }
+    // aligned form: element offset of the lane's 8-token run in channel 0 of the v block, (b H 64) Tp + t
+    size_t run[NTH];
+#pragma unroll
+    for (int th = 0; th < NTH; ++th) {
+        const int m = m_base + 64 * th + 8 * c8;
+        const int mc = FULL ? m : min(m, p.M - 1);
+        const int b = mc / p.T;
+        run[th] = (size_t)(b * p.H * 64) * p.Tp + (mc - b * p.T);
+    }
+    auto write_round = [&](int r) ESMK_INL {
+        const int th = r / NCG, cg = r % NCG;
+#pragma unroll
+        for (int nj2 = 0; nj2 < CH / 16; ++nj2)
+#pragma unroll
+            for (int mq = 0; mq < 4; ++mq) {
+                const int row = 16 * nj2 + l16, chunk = 4 * mq + g4;
+                *reinterpret_cast<f32x4*>(wl + row * 256 + ((chunk ^ (row & 7)) << 4)) = acc[(CH / 16) * cg + nj2][4 * th + mq];
+            }
+    };
+    auto read_round = [&](f32x4 (&raw)[2 * NIT]) ESMK_INL {
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int r = 8 * it + r8;
+#pragma unroll
+            for (int e2 = 0; e2 < 2; ++e2)
+                raw[2 * it + e2] = *reinterpret_cast<const f32x4*>(wl + r * 256 + (((4 * (c8 >> 1) + (c8 & 1) + 2 * e2) ^ (r & 7)) << 4));
+        }
+    };
+    size_t eo[8];  // any T: element offsets of the lane's 8 tokens of the current half (~0: past the last row)
+    auto finish_round = [&](int rd, const f32x4 (&raw)[2 * NIT]) ESMK_INL {
+        const int th = rd / NCG, cg = rd % NCG;
+        if constexpr (!FULL) {
+            if (n_base + CH * cg >= ncols) return;  // wave uniform (N is a multiple of 64)
+            if (!aligned && cg == 0) {
+#pragma unroll
+                for (int e2 = 0; e2 < 2; ++e2)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int m = m_base + 64 * th + 16 * (c8 >> 1) + 4 * ((c8 & 1) + 2 * e2) + e;
+                        const int mc = min(m, p.M - 1);
+                        const int b = mc / p.T, t = mc - b * p.T;
+                        const int t16 = t & 15;
+                        const int tp = (t & ~15) | ((((t16 >> 2) & 1) << 3) | (((t16 >> 3) & 1) << 2) | (t16 & 3));
+                        eo[4 * e2 + e] = m < p.M ? (size_t)(b * p.H * 64) * p.Tp + tp : ~(size_t)0;
+                    }
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int n = n_base + CH * cg + 8 * it + r8;  // channel of the v block = row (b H 64 + n) of vt
+            const float bv = bvc[cg][it];
+            float x[8];
+#pragma unroll
+            for (int e2 = 0; e2 < 2; ++e2)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if constexpr (LNF) x[4 * e2 + e] = __builtin_fmaf(raw[2 * it + e2][e], rs[th][e2][e], bv);
+                    else x[4 * e2 + e] = raw[2 * it + e2][e] + bv;
+                }
+            // opaque to the compiler before the conversion: fp32 result, then one rounding to the operand dtype, for
+            // every element alike (epilogue8m)
+            asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]));
+            V8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = Op<T>::from(x[e]);
+            if (aligned) {
+                if (FULL || (m_base + 64 * th + 8 * c8 < p.M && n < ncols)) {
+                    T* dst = vt + run[th] + (size_t)n * p.Tp;
+                    if constexpr (NT) __builtin_nontemporal_store(o, reinterpret_cast<V8*>(dst));
+                    else *reinterpret_cast<V8*>(dst) = o;
+                }
+            } else if constexpr (!FULL) {
+                if (n < ncols) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        if (eo[e] != ~(size_t)0) vt[eo[e] + (size_t)n * p.Tp] = o[e];
+                }
+            }
+        }
+    };
+    write_round(0);
+#pragma unroll
+    for (int rd = 0; rd < NR; ++rd) {
+        f32x4 raw[2 * NIT];
         read_round(raw);
         if (rd + 1 < NR) write_round(rd + 1);
         __builtin_amdgcn_sched_barrier(0);  // the next round's LDS traffic is issued before this round's arithmetic
@@ -878,25 +1088,13 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
             if (full) epilogue9_f32<T, EPI, true, RD, NTS, NMI, HM, LNF>(p, acc, m_base, n_base, lane, slice);
             else epilogue9_f32<T, EPI, false, RD, NTS, NMI, HM, LNF>(p, acc, m_base, n_base, lane, slice);
         } else if constexpr (EPI == EPI_V_T) {
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                const int nb = n_base + 64 * hf;
-                const bool f2 = (m_base + WRM <= p.M) && (nb + 64 <= p.N) && (p.T % 32 == 0);
-                char* sl2 = slice + (HM ? 0 : hf * 4096);
-                if (f2) epilogue8m<T, EPI, true, false, false, NMI / 2, 8, NTS, NMI, LNF>(p, acc, 4 * hf, m_base, nb, lane, sl2, 0, 0, 0);
-                else epilogue8m<T, EPI, false, false, false, NMI / 2, 8, NTS, NMI, LNF>(p, acc, 4 * hf, m_base, nb, lane, sl2, 0, 0, 0);
-            }
+            if (full && p.T % 32 == 0) epilogue9_vt<T, true, NTS, NMI, LNF, false>(p, acc, m_base, n_base, lane, slice, 0);
+            else epilogue9_vt<T, false, NTS, NMI, LNF, false>(p, acc, m_base, n_base, lane, slice, 0);
         } else if constexpr (EPI == EPI_QKV_ALL) {
             if (v_tile) {  // the v launch's epilogue: columns and bias counted from 2E
                 const int col0 = 2 * p.E;
-#pragma unroll
-                for (int hf = 0; hf < 2; ++hf) {
-                    const int nb = n_base - col0 + 64 * hf;
-                    const bool f2 = (m_base + WRM <= p.M) && (nb + 64 <= p.N - col0) && (p.T % 32 == 0);
-                    char* sl2 = slice + (HM ? 0 : hf * 4096);
-                    if (f2) epilogue8m<T, EPI_V_T, true, false, false, NMI / 2, 8, NTS, NMI, LNF, true>(p, acc, 4 * hf, m_base, nb, lane, sl2, 0, 0, 0, col0);
-                    else epilogue8m<T, EPI_V_T, false, false, false, NMI / 2, 8, NTS, NMI, LNF, true>(p, acc, 4 * hf, m_base, nb, lane, sl2, 0, 0, 0, col0);
-                }
+                if (full && p.T % 32 == 0) epilogue9_vt<T, true, NTS, NMI, LNF, true>(p, acc, m_base, n_base - col0, lane, slice, col0);
+                else epilogue9_vt<T, false, NTS, NMI, LNF, true>(p, acc, m_base, n_base - col0, lane, slice, col0);
             } else {
                 if (full) epilogue9_t<T, EPI_QKV_ROPE, true, NTS, NMI, HM ? 16 : 32, LNF>(p, acc, m_base, n_base, lane, slice);
                 else epilogue9_t<T, EPI_QKV_ROPE, false, NTS, NMI, HM ? 16 : 32, LNF>(p, acc, m_base, n_base, lane, slice);
