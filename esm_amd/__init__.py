@@ -15,5 +15,6 @@ from .msa_scoring import (msa_forward_rows, msa_masked_joint, msa_masked_margina
                           msa_wt_marginals)
 
 from .sampling import gibbs_sample, inpaint  # noqa: F401
+from .jacobian import categorical_jacobian, jacobian_contacts  # noqa: F401
 
 __version__ = "0.1.0"

@@ -254,6 +254,12 @@ SIGNATURES = {
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint64, c_float, ctypes.c_uint64, c_int, c_void_p, c_void_p,
                 c_void_p, c_int, c_int, c_void_p]),
     "esmk_op_commit_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    # the categorical Jacobian: substituted copies, the scatter of logit differences into J, centring, contact map, APC
+    "esmk_op_substitute_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "esmk_op_jacobian_scatter": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "esmk_op_jacobian_center": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "esmk_op_jacobian_contacts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "esmk_op_apc": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     # the token front end, one launch at a time (tests/test_frontend_ops_gpu.py); segment tables are host arrays
     "esmk_op_seq_stats": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "esmk_op_packed_stats": (

@@ -242,6 +242,24 @@ hipError_t launch_sample_rows(const float* lp, const int* row_chain, const int* 
 // tokens[slot[i], pos[i]] = token[i] on int64 [B,T]; token < 0 or pos outside [0,T) writes nothing, slot clamped to [0,B)
 hipError_t launch_commit_tokens(int64_t* tokens, const int* slot, const int* pos, const int* token, int n, int B, int T,
                                 hipStream_t st);
+// jacobian.hip — the categorical Jacobian J[i,a,j,b] fp32 [L,nA,L,nA] of one protein (esm_amd/jacobian.py); nA <= 32, every
+// index into J 64 bit, every sum fp64 in a fixed order, no atomics.
+// out int64 [n,T]: row i = tokens[src_row[i]] (row 0 when src_row is null; clamped to [0,B)) with position pos[i] set to
+// tok[i]; a position outside [0,T) or a token outside [0,V) substitutes nothing
+hipError_t launch_substitute_rows(const int64_t* tokens, const int* src_row, const int* pos, const int* tok, int64_t* out, int B,
+                                  int T, int n, int V, hipStream_t st);
+// out [n_copies,L,nA] (the slice of J at the chunk's first copy): out[c,j,b] = logits[c*L+j, cols[b]] - wt[j, cols[b]] in fp32;
+// logits fp32 [n_copies*L,V], wt fp32 [L,V], cols int32 [nA] clamped to [0,V)
+hipError_t launch_jacobian_scatter(const float* logits, const float* wt, const int* cols, float* out, int n_copies, int L, int nA,
+                                   int V, hipStream_t st);
+// in place, four passes in the order b, j, a, i: x = (float)((double)x - mean), mean = the fp64 sum of the fp32 line in ascending
+// index order / n
+hipError_t launch_jacobian_center(float* J, int L, int nA, hipStream_t st);
+// S fp32 [L,L]: S[i,j] = S[j,i] = sqrt(sum_ab (0.5 (Jc[i,a,j,b] + Jc[j,b,i,a]))^2), fp64 terms in a fixed order, rounded once
+hipError_t launch_jacobian_contacts(const float* Jc, float* S, int L, int nA, hipStream_t st);
+// in place on S fp32 [L,L]: diagonal := 0, S[i,j] -= r_i c_j / s (fp64 row, column and total sums; s == 0: no correction);
+// work: 2 L + 1 doubles
+hipError_t launch_apc(float* S, double* work, int L, hipStream_t st);
 // contact head (modules.py:27-41,338-357)
 hipError_t launch_contacts(const float* attn, const int64_t* tokens, const float* w,
                            const float* b, float* scratch, float* out, int B, int C, int T,

@@ -734,6 +734,20 @@ class ESM2(nn.Module):
         return sampling.inpaint(self, tokens, per_step=per_step, temperature=temperature, allowed=allowed, seed=seed,
                                 chain_ids=chain_ids, return_trajectory=return_trajectory)
 
+    # the categorical Jacobian (esm_amd/jacobian.py): substituted copies in batches that fill the GPU, J kept on the device
+    def categorical_jacobian(self, tokens, allowed=None, chunk=None, center=False, max_bytes=8 << 30):
+        """``esm_amd.jacobian.categorical_jacobian``: fp32 [L, nA, L, nA], the change of every candidate's logit at every
+        residue under every single substitution of ONE sequence."""
+        from . import jacobian
+
+        return jacobian.categorical_jacobian(self, tokens, allowed=allowed, chunk=chunk, center=center, max_bytes=max_bytes)
+
+    def jacobian_contacts(self, tokens, allowed=None, chunk=None, return_jacobian=False):
+        """``esm_amd.jacobian.jacobian_contacts``: fp32 [L, L], the contact map of the centred categorical Jacobian."""
+        from . import jacobian
+
+        return jacobian.jacobian_contacts(self, tokens, allowed=allowed, chunk=chunk, return_jacobian=return_jacobian)
+
     def profile_begin(self):
         """Arm per-kernel-class HIP-event timing of the following forward calls (bench.py)."""
         from . import _native as N

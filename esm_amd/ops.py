@@ -622,6 +622,83 @@ def commit_tokens(tokens, slots, positions, token):
     return tokens
 
 
+# ---- the categorical Jacobian (include/esmk.h: esmk_op_substitute_rows ... esmk_op_apc) ------------------------------------
+def substitute_rows(tokens, positions, tok, src_rows=None, vocab=33):
+    """[n,T] int64: row i = tokens[src_rows[i]] (row 0 of [B,T] / the only row of [T] when ``src_rows`` is None) with position
+    ``positions[i]`` set to ``tok[i]`` — the substituted copies of the categorical Jacobian, built on the device.  positions,
+    tok, src_rows int32 [n], all device data: a source row outside [0, B) is clamped, a position outside [0, T) or a token
+    outside [0, vocab) substitutes nothing."""
+    _req_cuda(tokens, positions, tok, src_rows)
+    tokens = tokens.view(1, -1) if tokens.dim() == 1 else tokens
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.is_contiguous()
+    n = positions.numel()
+    for t in (positions, tok) + ((src_rows,) if src_rows is not None else ()):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.numel() == n and t.is_contiguous()
+    B, T = tokens.shape
+    out = torch.empty((n, T), dtype=torch.int64, device=tokens.device)
+    N.check(N.lib.esmk_op_substitute_rows(N.ptr(tokens), N.ptr(src_rows), N.ptr(positions), N.ptr(tok), N.ptr(out), B, T, n,
+                                          int(vocab), N.cur_stream()))
+    return out
+
+
+def jacobian_scatter(logits, wt, cols, J, copy0=0):
+    """In place: ``J.view(L * nA, L, nA)[copy0 + c, j, b] = logits[c * L + j, cols[b]] - wt[j, cols[b]]`` (fp32) for the
+    ``logits.shape[0] // L`` copies of a chunk.  logits fp32 [n_copies * L, V], wt fp32 [L, V], cols int32 [nA] on the device
+    (clamped to [0, V)), J fp32 [L, nA, L, nA].  Returns ``J``."""
+    _req_cuda(logits, wt, cols, J)
+    assert J.dtype == torch.float32 and J.dim() == 4 and J.is_contiguous()
+    L, nA = J.shape[0], J.shape[1]
+    assert tuple(J.shape) == (L, nA, L, nA)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
+    V = logits.shape[1]
+    assert wt.dtype == torch.float32 and tuple(wt.shape) == (L, V) and wt.is_contiguous()
+    assert cols.dtype == torch.int32 and cols.dim() == 1 and cols.numel() == nA and cols.is_contiguous()
+    assert logits.shape[0] % L == 0
+    n_copies, copy0 = logits.shape[0] // L, int(copy0)
+    assert n_copies >= 1 and 0 <= copy0 and copy0 + n_copies <= L * nA, (copy0, n_copies, L * nA)
+    out = ctypes.c_void_p(J.data_ptr() + copy0 * L * nA * 4)
+    N.check(N.lib.esmk_op_jacobian_scatter(N.ptr(logits), N.ptr(wt), N.ptr(cols), out, n_copies, L, nA, V, N.cur_stream()))
+    return J
+
+
+def _jacobian_dims(J):
+    assert J.dtype == torch.float32 and J.dim() == 4 and J.is_contiguous()
+    L, nA = J.shape[0], J.shape[1]
+    assert tuple(J.shape) == (L, nA, L, nA)
+    return L, nA
+
+
+def jacobian_center(J):
+    """In place on fp32 [L, nA, L, nA]: the mean along each of the four axes removed, as four passes in the order b, j, a, i
+    (last axis first); in every pass the mean is the fp64 sum of the fp32 line in ascending index order, divided by n, and
+    every element becomes ``(float)((double)x - mean)``.  Returns ``J``."""
+    _req_cuda(J)
+    L, nA = _jacobian_dims(J)
+    N.check(N.lib.esmk_op_jacobian_center(N.ptr(J), L, nA, N.cur_stream()))
+    return J
+
+
+def jacobian_contacts(Jc):
+    """fp32 [L, L]: ``S[i, j] = sqrt(sum_ab (0.5 * (Jc[i, a, j, b] + Jc[j, b, i, a])) ** 2)``, the terms in fp64 in a fixed
+    order, rounded to fp32 once; symmetric bit for bit.  Jc fp32 [L, nA, L, nA] (``jacobian_center``'s result)."""
+    _req_cuda(Jc)
+    L, nA = _jacobian_dims(Jc)
+    S = torch.empty((L, L), dtype=torch.float32, device=Jc.device)
+    N.check(N.lib.esmk_op_jacobian_contacts(N.ptr(Jc), N.ptr(S), L, nA, N.cur_stream()))
+    return S
+
+
+def apc(S):
+    """In place on fp32 [L, L]: the diagonal set to zero, then ``S[i, j] - r_i * c_j / s`` with the row, column and total sums
+    of S in fp64 (rounded to fp32 once; ``s == 0``: no correction), the diagonal zero again.  Returns ``S``."""
+    _req_cuda(S)
+    assert S.dtype == torch.float32 and S.dim() == 2 and S.shape[0] == S.shape[1] and S.is_contiguous()
+    L = S.shape[0]
+    work = torch.empty((2 * L + 1,), dtype=torch.float64, device=S.device)
+    N.check(N.lib.esmk_op_apc(N.ptr(S), N.ptr(work), L, N.cur_stream()))
+    return S
+
+
 # ---- the token front end, one launch at a time (include/esmk.h: esmk_op_seq_stats ... esmk_op_gather_rows) -----------------
 def _out(t, shape, dtype, device):
     """The caller's output buffer (checked), or a fresh one: callers that look at the memory behind an output pass their own."""

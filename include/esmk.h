@@ -721,6 +721,40 @@ int esmk_op_sample_rows(const float* logprobs_dev, const int32_t* row_chain_dev,
 int esmk_op_commit_tokens(int64_t* tokens_dev, const int32_t* row_chain_slot_dev, const int32_t* pos_dev,
                           const int32_t* token_dev, int n, int B, int T, void* stream);
 
+/* The categorical Jacobian of one protein (esm_amd/jacobian.py): every candidate token t_a of a list of nA <= 32 put at every
+ * residue position p_i of ONE sequence, J[i,a,j,b] = logits(copy(i,a))[p_j, t_b] - logits(x)[p_j, t_b], fp32 [L,nA,L,nA] — the
+ * fp32 difference of two fp32 logits.  A chunk of copies is esmk_op_substitute_rows -> esmk_forward_rows (the L residue rows of
+ * every copy selected) -> esmk_op_jacobian_scatter on one stream; the host reads nothing in between, and J stays on the
+ * device: esmk_op_jacobian_center, esmk_op_jacobian_contacts and esmk_op_apc turn it into an [L,L] contact map there.  No
+ * atomics; every sum is fp64 in a fixed order, so no result depends on the launch geometry or on how the copies were chunked.
+ * Every index into J is 64 bit (the 1600 L^2 bytes of 20 candidates pass 2^31 at L = 1159).
+ * esmk_op_substitute_rows: out int64 [n,T], row i = tokens[src_row[i], :] (tokens int64 [B,T]; src_row int32 [n] or NULL = row
+ *   0) with position pos[i] replaced by tok[i] (int32 [n] each).  All lists are device data: a source row outside [0,B) is
+ *   clamped, a position outside [0,T) or a token outside [0,V) substitutes nothing.
+ * esmk_op_jacobian_scatter: out[c,j,b] = logits[c*L + j, cols[b]] - wt[j, cols[b]] for the n_copies copies of a chunk; logits
+ *   fp32 [n_copies*L, V], wt fp32 [L,V], cols int32 [nA] (device data, clamped to [0,V)), out = J + copy0*L*nA, the slice of J
+ *   at the chunk's first copy (copy c = i*nA + a).
+ * esmk_op_jacobian_center: Jc = (P_i x P_a x P_j x P_b) J, P = I - 11'/n along that axis, as four passes IN PLACE in the order
+ *   b, j, a, i.  In every pass the mean of a line is the fp64 sum of its fp32 values in ascending index order, divided by n, and
+ *   every element becomes (float)((double)x - mean): one rounding per pass.  One lane owns a line; the lanes of a wavefront
+ *   run along the contiguous index.
+ * esmk_op_jacobian_contacts: S_out fp32 [L,L], S[i,j] = sqrt(sum over (a,b) of (0.5 (Jc[i,a,j,b] + Jc[j,b,i,a]))^2): the terms
+ *   in fp64, lane l of one wavefront per pair i <= j adding the terms l, l + 64, ... (index a*nA + b) by fused multiply-add, the
+ *   64 partial sums added in a butterfly, the fp64 square root rounded to fp32 once and stored to S[i,j] and S[j,i]: S is
+ *   symmetric bit for bit.
+ * esmk_op_apc: in place on S fp32 [L,L]: S[i,i] = 0; C[i,j] = (float)((double)S[i,j] - r_i * c_j / s) with r, c, s the row,
+ *   column and total sums of S (diagonal as zero) in fp64; s == 0: S stays (diagonal zero); C[i,i] = 0.  work_dev: 2 L + 1
+ *   doubles of scratch (r, c, s), the caller's.
+ * Refused before any HIP call: null pointers (src_row_dev may be NULL), L, nA, n, n_copies, B, T or V <= 0, nA > 32,
+ * L*nA*L*nA >= 2^40, L*nA, n_copies*L, B*T or n*T > 2^24, n_copies > L*nA. */
+int esmk_op_substitute_rows(const int64_t* tokens_dev, const int32_t* src_row_dev, const int32_t* pos_dev, const int32_t* tok_dev,
+                            int64_t* out_dev, int B, int T, int n, int V, void* stream);
+int esmk_op_jacobian_scatter(const float* logits_dev, const float* wt_dev, const int32_t* cols_dev, float* out_dev, int n_copies,
+                             int L, int nA, int V, void* stream);
+int esmk_op_jacobian_center(float* J_dev, int L, int nA, void* stream);
+int esmk_op_jacobian_contacts(const float* Jc_dev, float* S_out_dev, int L, int nA, void* stream);
+int esmk_op_apc(float* S_dev, double* work_dev, int L, void* stream);
+
 /* The token front end — the kernels that turn tokens into the layer-0 activation and into the bookkeeping every later kernel
  * trusts — one launch at a time (tests/test_frontend_ops_gpu.py).  Validation, then the launchers the engines call.  Refused
  * before any HIP call: null pointers (the ones named optional below may be NULL), B, T, R, C, n, rows, N, vocab or npos <= 0,
