@@ -214,13 +214,29 @@ int esmk_op_ln_finalize(const float* part_dev, float* mean_dev, float* rstd_dev,
     return 0;
 }
 
-int esmk_op_fold_weight(const void* w_dev, int w_dtype, const float* gamma_dev, const float* beta_dev, void* dst_dev,
-                        int dst_dtype, float* bias2_dev, int N, int K, int ld, void* stream) {
+// the checks and the launch of both fold_weight entries; row_map: rows of heads of d dims spread over 64 slots
+static int fold_weight_op(const void* w_dev, int w_dtype, const float* gamma_dev, const float* beta_dev, void* dst_dev,
+                          int dst_dtype, float* bias2_dev, int N, int K, int ld, int row_map, int d, void* stream) {
     if (!w_dev || !gamma_dev || !beta_dev || !dst_dev || !bias2_dev) return fail("esmk_op_fold_weight: null argument");
     if (N <= 0 || K <= 0 || ld < K) return fail("esmk_op_fold_weight: need N, K > 0 and ld >= K");
     ESMK_TRY(launch_fold_weight(w_dev, w_dtype, gamma_dev, beta_dev, dst_dev, dst_dtype, bias2_dev, (size_t)N, (size_t)K,
-                                (size_t)ld, 0, 64, (hipStream_t)stream));
+                                (size_t)ld, row_map, d, (hipStream_t)stream));
     return 0;
+}
+
+int esmk_op_fold_weight_ex(const void* w_dev, int w_dtype, const float* gamma_dev, const float* beta_dev, void* dst_dev,
+                           int dst_dtype, float* bias2_dev, int N, int K, int ld, int head_dim, void* stream) {
+    if (head_dim != 16 && head_dim != 24 && head_dim != 32 && head_dim != 64)
+        return fail("esmk_op_fold_weight_ex: head_dim must be 16, 24, 32 or 64");
+    if (N > 0 && N % head_dim != 0) return fail("esmk_op_fold_weight_ex: need N % head_dim == 0 (whole heads)");
+    return fold_weight_op(w_dev, w_dtype, gamma_dev, beta_dev, dst_dev, dst_dtype, bias2_dev, N, K, ld, head_dim < 64, head_dim,
+                          stream);
+}
+
+// the entry without head_dim: the identity row map for any N (head_dim 64 without the whole-heads condition)
+int esmk_op_fold_weight(const void* w_dev, int w_dtype, const float* gamma_dev, const float* beta_dev, void* dst_dev,
+                        int dst_dtype, float* bias2_dev, int N, int K, int ld, void* stream) {
+    return fold_weight_op(w_dev, w_dtype, gamma_dev, beta_dev, dst_dev, dst_dtype, bias2_dev, N, K, ld, 0, 64, stream);
 }
 
 int esmk_op_linear_ln(const void* a_dev, const void* w_dev, const float* bias_dev, const float* bias2_dev, void* out_dev,

@@ -482,6 +482,11 @@ int esmk_op_rowstats(const float* x_dev, void* y_dev, float* mean_dev, float* rs
 int esmk_op_ln_finalize(const float* part_dev, float* mean_dev, float* rstd_dev, int rows, int parts, int E, void* stream);
 int esmk_op_fold_weight(const void* w_dev, int w_dtype, const float* gamma_dev, const float* beta_dev, void* dst_dev,
                         int dst_dtype, float* bias2_dev, int N, int K, int ld, void* stream);
+/* esmk_op_fold_weight with the head spread of models whose head_dim is below 64 (q / k / v rows): head_dim 16 / 24 / 32:
+ * row head * d + i of w goes to row head * 64 + (i < d / 2 ? i : 32 + i - d / 2) of dst and bias2 (N / d * 64 rows; the rows
+ * in between are left as they are); head_dim 64: the identity.  N must hold whole heads. */
+int esmk_op_fold_weight_ex(const void* w_dev, int w_dtype, const float* gamma_dev, const float* beta_dev, void* dst_dev,
+                           int dst_dtype, float* bias2_dev, int N, int K, int ld, int head_dim, void* stream);
 int esmk_op_linear_ln(const void* a_dev, const void* w_dev, const float* bias_dev, const float* bias2_dev, void* out_dev,
                       int M, int N, int K, int epilogue, int operand_dtype, const float* ln_rstd_dev, void* h16_dev, int ldh,
                       float* ln_part_dev, int ln_parts, const float* ln_mean_dev, int half_m, void* stream);

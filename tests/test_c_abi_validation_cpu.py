@@ -473,6 +473,31 @@ def test_layernorm_ex_argument_checks():
         assert call(eps=eps) != 0 and who in err() and "eps" in err(), eps
 
 
+def test_fold_weight_ex_argument_checks():
+    """esmk_op_fold_weight_ex: head_dim and whole heads are checked before a launch, after them the checks of
+    esmk_op_fold_weight, which stays as it was for any N (the buffers are fake)."""
+    f16 = N.dtype_code(torch.float16)
+
+    def call(w=FAKE, gamma=FAKE, beta=FAKE, dst=FAKE, b2=FAKE, n=96, k=64, ld=64, d=16):
+        return N.lib.esmk_op_fold_weight_ex(w, N.F32, gamma, beta, dst, f16, b2, n, k, ld, d, None)
+
+    who = "esmk_op_fold_weight"
+    for d in (0, -16, 8, 48, 65, 128):
+        assert call(d=d) != 0 and who + "_ex: head_dim" in err(), d
+    for kw in (dict(n=100, d=16), dict(n=96, d=64), dict(n=40, d=24), dict(n=16, d=32)):
+        assert call(**kw) != 0 and who + "_ex" in err() and "whole heads" in err(), kw
+    for kw in (dict(w=None), dict(gamma=None), dict(beta=None), dict(dst=None), dict(b2=None)):
+        assert call(**kw) != 0 and who + ": null" in err(), kw
+    for kw in (dict(n=0), dict(n=-16), dict(k=0), dict(ld=63)):
+        assert call(**kw) != 0 and who in err() and "ld >= K" in err(), kw
+    # the entry without head_dim: the same checks, no condition on N
+    old = lambda **kw: N.lib.esmk_op_fold_weight(kw.get("w", FAKE), N.F32, FAKE, FAKE, FAKE, f16, FAKE, kw.get("n", 130), 64,
+                                                 kw.get("ld", 64), None)
+    assert old(w=None) != 0 and who + ": null" in err()
+    assert old(n=0) != 0 and "ld >= K" in err()
+    assert old(ld=32) != 0 and "ld >= K" in err()
+
+
 def test_split_weight_ex_argument_checks():
     """esmk_op_split_weight_ex: parts, the head-spreading maps and the row stride of the image are checked before a launch
     (the buffers are fake)."""

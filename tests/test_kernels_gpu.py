@@ -5,8 +5,9 @@ to cover fp32 accumulation order and the final rounding of the output).
 
 Together with this file, every HIP kernel of the library has a single-op test: test_attention_variants_gpu.py,
 test_attention_biaskv_gpu.py and test_attention_packed_ops_gpu.py (attention forms), test_gemm_forms_gpu.py (generalised
-GEMM forms, MSA row softmax), test_contacts_kernels_gpu.py (fused and packed contacts), test_ln_fold_gpu.py (LayerNorm
-fold), test_precision_ops_gpu.py (precision modes), test_scoring_ops_gpu.py and test_scoring_variant_ops_gpu.py (scoring)
+GEMM forms, MSA row softmax), test_contacts_kernels_gpu.py (fused and packed contacts), test_ln_fold_gpu.py and
+test_ln_fold_ops_gpu.py (LayerNorm fold: at model shapes, and at the edges in both dtypes), test_gelu_epilogue_gpu.py (the GELU
+of every launcher on exact pre-activations), test_precision_ops_gpu.py (precision modes), test_scoring_ops_gpu.py and test_scoring_variant_ops_gpu.py (scoring)
 and test_frontend_ops_gpu.py (token statistics, embeddings, positions, position tables, row gather)."""
 import math
 

@@ -45,6 +45,7 @@ import math
 import pytest
 import torch
 
+from _ln_fold_ref import gelu64
 from esm_amd import _native as nat
 from esm_amd import ops
 
@@ -71,10 +72,6 @@ def untouched(t):
 
 def bits(t):
     return t.contiguous().view(BITS[t.dtype])
-
-
-def gelu64(x):
-    return x * 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0)))
 
 
 def gen(seed):
