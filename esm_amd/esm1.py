@@ -14,7 +14,6 @@ learned null key / value pair per layer, ``bias_k`` / ``bias_v``) and the output
 this family: ``forward_varlen`` runs ``forward``.
 """
 import math
-import os
 
 import torch
 import torch.nn as nn
@@ -80,10 +79,6 @@ class ProteinBertModel(ESM2):
         self.emb_layer_norm_after = nn.LayerNorm(E)
         self.lm_head = RobertaLMHead(E, self.alphabet_size, self.embed_tokens.weight)
         self._engine = None
-        # picked up by esm_amd.esm2._Engine
-        self._engine_no_rope = 1
-        self._engine_num_positions = self.embed_positions.weight.shape[0]
-        self._engine_ln_before = int(ln_before)
 
     def _init_submodules_esm1(self, args):
         """reference esm1.py:67-89,107-114 with add_bias_kv=True and ESM1LayerNorm (weight / bias, eps 1e-12)."""
@@ -104,23 +99,21 @@ class ProteinBertModel(ESM2):
         self.embed_positions = SinusoidalPositionalEmbedding(E, self.padding_idx)
         self.embed_out = nn.Parameter(torch.zeros((self.alphabet_size, E)))
         self.embed_out_bias = nn.Parameter(torch.zeros(self.alphabet_size)) if args.final_bias else None
-        # picked up by esm_amd.esm2._Engine (esmk_config.no_rope = ESMK_ESM1 | ESMK_ESM1_FINAL_BIAS)
-        self._engine_esm1 = 1
-        self._engine_final_bias = int(bool(args.final_bias))
 
-    def _get_engine(self, device):
+    def _engine_config(self):
+        """What esm_amd.engine.Esm2Engine sets in esmk_config besides the dimensions: ESM-1 -> no_rope = ESMK_ESM1
+        (| ESMK_ESM1_FINAL_BIAS); ESM-1b / ESM-1v -> no_rope, the size of the position table, the embedding LayerNorm."""
         if self.model_version == "ESM-1":
-            from .esm2 import _weight_split
+            return dict(esm1=True, final_bias=self.embed_out_bias is not None)
+        return dict(no_rope=1, num_positions=self.embed_positions.weight.shape[0],
+                    ln_before=self.emb_layer_norm_before is not None)
 
-            if _weight_split():  # before the current engine is touched
-                raise RuntimeError(
-                    f"ESM_AMD_OPERAND={os.environ.get('ESM_AMD_OPERAND', '')}: the split-operand precision modes (f16x2*, f16x3) "
-                    "are not available for ESM-1 models (bias_kv attention); use f16 or bf16")
-        return super()._get_engine(device)
+    def _packs(self):
+        return self.model_version != "ESM-1" and super()._packs()
 
-    def _fold_setting(self):
+    def _fold_setting(self, gains_known=False):
         # ESM-1 has no LayerNorm fold (eps 1e-12, no final LayerNorm to fold): off whatever ESM_AMD_LN_FOLD says
-        return -1 if self.model_version == "ESM-1" else super()._fold_setting()
+        return -1 if self.model_version == "ESM-1" else super()._fold_setting(gains_known)
 
     @property
     def num_layers(self):

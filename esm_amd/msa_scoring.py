@@ -17,8 +17,6 @@ their own: ``msa_masked_marginals``, ``msa_wt_marginals``, ``msa_masked_joint``,
 is an extension: the reference refuses every strategy but masked-marginals for MSAs (predict.py:163-165); pseudo-ppl is not
 offered for MSAs.
 """
-import ctypes
-
 import torch
 
 from .scoring import CHUNK_TOKENS, _checked_variant
@@ -69,30 +67,10 @@ def msa_forward_rows(model, tokens, sel_rows, return_logits=False):
     per batch (with <pad> anywhere, columns padded in row 0 are masked out of the row attention of every entry): an unpadded MSA
     next to a padded one in which its row 0 has no <pad> still gets the same result, yet the bit claim is made and tested for
     copies of one MSA only."""
-    from . import _native as N
-
     tok = _to_device(model, _check_msa(model, tokens, batched=True))
     dev = tok.device
     assert sel_rows.dtype == torch.int32 and sel_rows.ndim == 1 and sel_rows.device == dev and sel_rows.is_contiguous()
-    B, R, C = tok.shape
-    n = sel_rows.numel()
-    V = model.alphabet_size
-    if n == 0:
-        empty = torch.empty((0, V), dtype=torch.float32, device=dev)
-        return (empty, empty.clone()) if return_logits else empty
-    with torch.cuda.device(dev):
-        eng = model._get_engine(dev)
-        eng.sync_weights(model)
-        need, off = ctypes.c_size_t(), ctypes.c_size_t()
-        N.check(N.lib.esmk_msa_rows_workspace_bytes(eng.handle, B, R, C, n, ctypes.byref(need), ctypes.byref(off)))
-        ws = eng.workspace_for_bytes(need.value)
-        out = torch.empty((n, V), dtype=torch.float32, device=dev)
-        N.check(N.lib.esmk_msa_forward_rows(eng.handle, N.ptr(eng.packed), N.ptr(tok), B, R, C, N.ptr(sel_rows), n, N.ptr(out),
-                                            N.ptr(ws), ws.numel(), N.cur_stream()))
-        if return_logits:
-            logits = ws[off.value: off.value + n * V * 4].view(torch.float32).view(n, V).clone()
-            return out, logits
-    return out
+    return model._selected_rows(tok, sel_rows, return_logits)
 
 
 def _check_row(tok, row):

@@ -12,14 +12,13 @@ There is no CPU path.
 reference does (the latter is 58 GB in fp32 for a 12-layer 128x513 MSA: it fits the MI355X's 288 GB).  Set
 ``model.return_col_attentions = False`` to skip it, e.g. for ``predict_contacts`` on deep MSAs.
 """
-import ctypes
 import re
 
 import torch
 import torch.nn as nn
 
-from .esm2 import (ContactPredictionHead, RobertaLMHead, _Container, _operand_dtype_for, _weight_split, live_tensors,
-                   warn_if_grad_expected)
+from .engine import MsaEngine, _EngineHost, warn_if_grad_expected
+from .esm2 import ContactPredictionHead, RobertaLMHead, _Container
 
 _AXIS = re.compile(r"row|column")
 
@@ -73,72 +72,10 @@ class LearnedPositionalEmbedding(nn.Embedding):
         self.max_positions = num_embeddings
 
 
-class _MsaEngine:
-    def __init__(self, model, device, operand_dtype, weight_split=0):
-        from . import _native as N
+class MSATransformer(_EngineHost, nn.Module):
+    _engine_class = MsaEngine
+    _cpu_refusal = "esm_amd.MSATransformer runs only on an MI355X (ROCm) device; there is no CPU fallback"
 
-        self.N, self.device, self.operand_dtype = N, device, operand_dtype
-        self.weight_split = int(weight_split)  # ESM_AMD_OPERAND=f16x2 / f16x2a (esmk_msa_config.weight_split: 1 / 2)
-        a = model.args
-        cfg = N.EsmkMsaConfig(
-            a.layers, a.embed_dim, a.attention_heads, a.ffn_embed_dim, model.alphabet_size, model.padding_idx,
-            model.mask_idx, model.cls_idx, model.eos_idx if model.eos_idx is not None else -1,
-            int(bool(model.prepend_bos)), int(bool(model.append_eos)), model.embed_positions.weight.shape[0],
-            int(model.msa_position_embedding is not None), N.dtype_code(operand_dtype), int(self.weight_split))
-        self.handle = ctypes.c_void_p()
-        with torch.cuda.device(device):
-            N.check(N.lib.esmk_msa_create(ctypes.byref(cfg), ctypes.byref(self.handle)))
-            nbytes = ctypes.c_size_t()
-            N.check(N.lib.esmk_packed_bytes(self.handle, ctypes.byref(nbytes)))
-            self.packed = torch.zeros(nbytes.value, dtype=torch.uint8, device=device)
-        self.fingerprint, self.workspace, self._named = None, None, None
-
-    def close(self):
-        if self.handle:
-            self.N.lib.esmk_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def sync_weights(self, model):
-        """See esm_amd.esm2._Engine.sync_weights (same detection rules; ``refresh_engine()`` after ``.data`` edits)."""
-        N = self.N
-        named = live_tensors(self, model, skip=lambda k: k == "lm_head.weight")
-        fp = tuple((id(t), t.data_ptr(), t._version, t.dtype) for _, t in named)
-        if fp == self.fingerprint:
-            return
-        stream = N.cur_stream()
-        for key, t in named:
-            t = t.detach()
-            if key == "msa_position_embedding":  # [1,1024,1,D] (or [1,1024,1,1] in the first release) -> [1024,D]
-                t = t.expand(1, t.shape[1], 1, model.args.embed_dim).reshape(t.shape[1], model.args.embed_dim)
-            t = t.contiguous()
-            shape = (ctypes.c_int64 * t.dim())(*t.shape)
-            N.check(N.lib.esmk_pack_weight(self.handle, N.ptr(self.packed), self.packed.numel(), key.encode(),
-                                           N.ptr(t), N.dtype_code(t.dtype), shape, t.dim(), stream))
-        self.fingerprint = fp
-
-    def workspace_for_bytes(self, n):
-        if self.workspace is None or self.workspace.numel() < n:
-            self.workspace = None
-            self.workspace = torch.empty(n, dtype=torch.uint8, device=self.device)
-        return self.workspace
-
-    def workspace_for(self, B, R, C, flags):
-        N = self.N
-        need = ctypes.c_size_t()
-        N.check(N.lib.esmk_msa_workspace_bytes(self.handle, B, R, C, flags, ctypes.byref(need)))
-        if self.workspace is None or self.workspace.numel() < need.value:
-            self.workspace = None
-            self.workspace = torch.empty(need.value, dtype=torch.uint8, device=self.device)
-        return self.workspace
-
-
-class MSATransformer(nn.Module):
     @classmethod
     def add_args(cls, parser):
         # reference esm/model/msa_transformer.py:21-86
@@ -195,28 +132,13 @@ class MSATransformer(nn.Module):
             if isinstance(module, (RowSelfAttention, ColumnSelfAttention)):
                 module.max_tokens_per_msa = value
 
-    def _get_engine(self, device):
-        odt = _operand_dtype_for(self.embed_tokens.weight.dtype)
-        split = _weight_split()
-        eng = self._engine
-        if eng is None or eng.device != device or eng.operand_dtype != odt or eng.weight_split != split:
-            if eng is not None:
-                eng.close()
-            eng = _MsaEngine(self, device, odt, split)
-            object.__setattr__(self, "_engine", eng)
-        return eng
-
     def forward(self, tokens, repr_layers=[], need_head_weights=False, return_contacts=False):
         if return_contacts:
             need_head_weights = True
         assert tokens.ndim == 3
         if self.training and (self.args.dropout or self.args.attention_dropout or self.args.activation_dropout):
             raise RuntimeError("esm_amd.MSATransformer is forward-only: call .eval() (dropout is not implemented)")
-        if not tokens.is_cuda:
-            raise RuntimeError("esm_amd.MSATransformer runs only on an MI355X (ROCm) device; there is no CPU fallback")
-        w = self.embed_tokens.weight
-        if w.device != tokens.device:
-            raise RuntimeError(f"model parameters are on {w.device} but tokens on {tokens.device}")
+        w = self._check_devices(tokens)
         warn_if_grad_expected(self)
         from . import _native as N
 
@@ -228,10 +150,9 @@ class MSATransformer(nn.Module):
         if C > self.embed_positions.max_positions:
             raise ValueError(f"Sequence length {C} above maximum  sequence length of {self.embed_positions.max_positions}")
         L, E, H, V = self.args.layers, self.args.embed_dim, self.args.attention_heads, self.alphabet_size
-        repr_set = sorted({int(i) for i in repr_layers if 0 <= int(i) <= L})
+        repr_set = self._repr_set(repr_layers)
         with torch.cuda.device(dev):
-            eng = self._get_engine(dev)
-            eng.sync_weights(self)
+            eng = self._engine_ready(dev)
             tok = tokens.to(torch.int64).contiguous()
             flags = N.OUT_LOGITS
             f32 = dict(dtype=torch.float32, device=dev)
@@ -248,14 +169,8 @@ class MSATransformer(nn.Module):
                 flags |= N.OUT_CONTACTS
                 S = C - int(self.prepend_bos) - int(self.append_eos)
                 contacts = torch.empty((B, S, S), **f32)
-            ws = eng.workspace_for(B, R, C, flags)
-            layers_arr = (ctypes.c_int32 * max(1, len(repr_set)))(*repr_set)
-            outs_arr = (ctypes.c_void_p * max(1, len(repr_set)))(*[r.data_ptr() for r in reps])
-            N.check(N.lib.esmk_msa_forward(
-                eng.handle, N.ptr(eng.packed), N.ptr(tok), B, R, C, layers_arr, len(repr_set), outs_arr, flags,
-                N.ptr(logits), N.ptr(row_attn), N.ptr(col_attn), N.ptr(contacts), N.ptr(ws), ws.numel(), N.cur_stream()))
-        out_dt = w.dtype
-        cast = (lambda t: t) if out_dt == torch.float32 else (lambda t: t.to(out_dt))
+            eng.forward(tok, repr_set, reps, flags, logits, row_attn, col_attn, contacts)
+        cast = self._cast_to(w.dtype)
         result = {"logits": cast(logits), "representations": {l: cast(r) for l, r in zip(repr_set, reps)}}
         if need_head_weights:
             if col_attn is not None:
@@ -313,27 +228,6 @@ class MSATransformer(nn.Module):
 
         return msa_scoring.msa_score_variants(self, alphabet, msa, variants, strategy=strategy, offset_idx=offset_idx, sep=sep,
                                               chunk=chunk)
-
-    def profile_begin(self):
-        """Arm per-kernel-class HIP-event timing of the following forward calls (bench.py --workload msa1b)."""
-        from .esm2 import ESM2
-
-        ESM2.profile_begin(self)
-
-    def profile_end(self):
-        from .esm2 import ESM2
-
-        return ESM2.profile_end(self)
-
-    def refresh_engine(self):
-        if self._engine is not None:
-            self._engine.close()
-        object.__setattr__(self, "_engine", None)
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state["_engine"] = None
-        return state
 
 
 def build_from_checkpoint(model_data):

@@ -9,6 +9,7 @@ import ctypes
 import torch
 
 from . import _native as N
+from .packing import ragged_views
 
 
 def _req_cuda(*ts):
@@ -265,17 +266,15 @@ def attention_probs_packed(q, k, lse, segments, key_bias=None, layer=0, num_laye
     _req_cuda(q, k, lse, key_bias, out)
     H, rows, D = q.shape
     seg, seg_ptr = _segments_arg(segments)
-    lens = seg[:, 1].to(torch.int64)
-    offs = [0] + (num_layers * H * torch.cumsum(lens * lens, 0)).tolist()
+    lens = seg[:, 1].tolist()
     if out is None:
-        out = torch.zeros((offs[-1],), dtype=out_dtype, device=q.device)
+        out = torch.zeros((num_layers * H * sum(n * n for n in lens),), dtype=out_dtype, device=q.device)
     assert out.dtype == out_dtype
     lse2 = (lse * LOG2E).contiguous()
     N.check(N.lib.esmk_op_attention_probs_packed(N.ptr(q), N.ptr(k), N.ptr(lse2), N.ptr(key_bias), seg_ptr, seg.shape[0],
                                                  rows, H, D, num_layers, layer, N.dtype_code(q.dtype),
                                                  int(out_dtype != torch.float32), N.ptr(out), out.numel(), N.cur_stream()))
-    views = [out[offs[s]:offs[s + 1]].view(num_layers, H, int(lens[s]), int(lens[s])) for s in range(seg.shape[0])]
-    return out, views
+    return out, ragged_views(out, lens, (num_layers, H))
 
 
 def make_vt_packed(v):

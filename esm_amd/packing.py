@@ -64,3 +64,26 @@ def pack_plan(tokens, padding_idx, lengths=None):
     rows = int((int(padded.sum()) + ROWS_ALIGN - 1) // ROWS_ALIGN * ROWS_ALIGN)
     segments = torch.stack([starts, lengths], dim=1).to(torch.int32).contiguous()
     return PackPlan(B, T, rows, lengths, segments)
+
+
+def ragged_views(flat, sides, lead=()):
+    """The per-sequence views of a ragged flat buffer (include/esmk.h: the packed contact and attention maps): sequence b's
+    ``[*lead, sides[b], sides[b]]`` block lies behind the blocks of the sequences before it.  ``sides``: ints on the host."""
+    per_cell = 1
+    for n in lead:
+        per_cell *= n
+    views, lo = [], 0
+    for side in sides:
+        hi = lo + per_cell * side * side
+        views.append(flat[lo:hi].view(*lead, side, side))
+        lo = hi
+    return views
+
+
+def dense_from_views(views, lead, side, like):
+    """``[len(views), *lead, side, side]`` in the dtype and on the device of ``like``: view b in the top-left corner of
+    entry b, zeros elsewhere."""
+    out = torch.zeros((len(views),) + tuple(lead) + (side, side), dtype=like.dtype, device=like.device)
+    for b, v in enumerate(views):
+        out[b, ..., :v.shape[-2], :v.shape[-1]] = v
+    return out

@@ -25,7 +25,6 @@ The functions are also methods of ``ESM2`` / ``ProteinBertModel`` (``model.maske
 MSA Transformer (``NotImplementedError``): one MSA plus a query row is another argument shape, served by
 ``esm_amd.msa_scoring`` under names of its own.
 """
-import ctypes
 import numbers
 
 import torch
@@ -43,15 +42,20 @@ def _refuse_msa(model):
             "esm_amd.msa_scoring (msa_masked_marginals, msa_wt_marginals, msa_masked_joint, msa_score_variants)")
 
 
+def _device_weight(model):
+    w = model.embed_tokens.weight
+    if not w.is_cuda:
+        raise RuntimeError("esm_amd.scoring runs only on an MI355X (ROCm) device: move the model to 'cuda' first; the engine "
+                           "has no CPU fallback")
+    return w
+
+
 def _device_tokens(model, tokens):
     _refuse_msa(model)
     if tokens.ndim == 1:
         tokens = tokens.unsqueeze(0)
     assert tokens.ndim == 2, "tokens: [B, T] (or [T])"
-    w = model.embed_tokens.weight
-    if not w.is_cuda:
-        raise RuntimeError("esm_amd.scoring runs only on an MI355X (ROCm) device: move the model to 'cuda' first; the engine "
-                           "has no CPU fallback")
+    w = _device_weight(model)
     pos_table = getattr(model, "embed_positions", None)
     max_positions = getattr(pos_table, "max_positions", None)
     if max_positions is not None and tokens.size(1) > max_positions:  # ESM-1b / ESM-1v, as ProteinBertModel.forward
@@ -66,30 +70,10 @@ def forward_rows(model, tokens, sel_rows, return_logits=False):
     engine, never read out of bounds).  ``return_logits``: also the selected fp32 logits (the bits ``forward`` gives those
     rows).  One stream: the two-stream forward (``ESM_AMD_DUAL_STREAM``) is not used here, and since every kernel is
     batch-invariant the bits do not depend on that."""
-    from . import _native as N
-
     tok = _device_tokens(model, tokens)
     dev = tok.device
     assert sel_rows.dtype == torch.int32 and sel_rows.ndim == 1 and sel_rows.device == dev and sel_rows.is_contiguous()
-    B, T = tok.shape
-    n = sel_rows.numel()
-    V = model.alphabet_size
-    if n == 0:
-        empty = torch.empty((0, V), dtype=torch.float32, device=dev)
-        return (empty, empty.clone()) if return_logits else empty
-    with torch.cuda.device(dev):
-        eng = model._engine_ready(dev)
-        need, off = ctypes.c_size_t(), ctypes.c_size_t()
-        N.check(N.lib.esmk_rows_workspace_bytes(eng.handle, B, T, n, ctypes.byref(need), ctypes.byref(off)))
-        ws = eng.workspace_for_bytes(need.value)
-        out = torch.empty((n, V), dtype=torch.float32, device=dev)
-        N.check(N.lib.esmk_forward_rows(eng.handle, N.ptr(eng.packed), N.ptr(tok), B, T, N.ptr(sel_rows), n, N.ptr(out),
-                                        N.ptr(ws), ws.numel(), N.cur_stream()))
-        eng.max_T = max(eng.max_T, T)
-        if return_logits:
-            logits = ws[off.value: off.value + n * V * 4].view(torch.float32).view(n, V).clone()
-            return out, logits
-    return out
+    return model._selected_rows(tok, sel_rows, return_logits)
 
 
 def forward_rows_packed(model, tokens_flat, segments, sel_rows, return_logits=False):
@@ -101,36 +85,14 @@ def forward_rows_packed(model, tokens_flat, segments, sel_rows, return_logits=Fa
     segment carries the bits of that sequence alone, so a row equals the row ``forward_rows`` gives the same sequence in a
     padded batch.  ``return_logits``: also the selected fp32 logits.  ESM-2 and ESM-1b / ESM-1v models; ESM-1 models and the
     f16x3 precision mode have no token-packed forward and are refused by the engine."""
-    from . import _native as N
-
     _refuse_msa(model)
-    w = model.embed_tokens.weight
-    if not w.is_cuda:
-        raise RuntimeError("esm_amd.scoring runs only on an MI355X (ROCm) device: move the model to 'cuda' first; the engine "
-                           "has no CPU fallback")
+    w = _device_weight(model)
     dev = w.device
     assert tokens_flat.dtype == torch.int64 and tokens_flat.ndim == 1 and tokens_flat.device == dev and tokens_flat.is_contiguous()
     assert sel_rows.dtype == torch.int32 and sel_rows.ndim == 1 and sel_rows.device == dev and sel_rows.is_contiguous()
     seg = torch.as_tensor(segments)
     assert seg.dtype == torch.int32 and not seg.is_cuda and seg.ndim == 2 and seg.shape[1] == 2 and seg.is_contiguous()
-    rows, n_seg, n = tokens_flat.numel(), seg.shape[0], sel_rows.numel()
-    V = model.alphabet_size
-    if n == 0:
-        empty = torch.empty((0, V), dtype=torch.float32, device=dev)
-        return (empty, empty.clone()) if return_logits else empty
-    seg_ptr = ctypes.cast(seg.data_ptr(), ctypes.POINTER(ctypes.c_int32))
-    with torch.cuda.device(dev):
-        eng = model._engine_ready(dev)
-        need, off = ctypes.c_size_t(), ctypes.c_size_t()
-        N.check(N.lib.esmk_packed_rows_workspace_bytes(eng.handle, seg_ptr, n_seg, rows, n, ctypes.byref(need), ctypes.byref(off)))
-        ws = eng.workspace_for_bytes(need.value)
-        out = torch.empty((n, V), dtype=torch.float32, device=dev)
-        N.check(N.lib.esmk_forward_packed_rows(eng.handle, N.ptr(eng.packed), N.ptr(tokens_flat), seg_ptr, n_seg, rows,
-                                               N.ptr(sel_rows), n, N.ptr(out), N.ptr(ws), ws.numel(), N.cur_stream()))
-        if return_logits:
-            logits = ws[off.value: off.value + n * V * 4].view(torch.float32).view(n, V).clone()
-            return out, logits
-    return out
+    return model._selected_rows(tokens_flat, sel_rows, return_logits, seg)
 
 
 SEG_ALIGN = 16   # segment starts of a packed row space (esm_amd.packing, include/esmk.h)
@@ -159,14 +121,6 @@ def plan_packed_chunks(lengths_per_copy, budget=CHUNK_TOKENS):
     if starts:
         chunks.append((lo, lo + len(starts), starts, (used + ROWS_ALIGN - 1) // ROWS_ALIGN * ROWS_ALIGN))
     return chunks
-
-
-def _packs(model):
-    """False where ``forward_varlen`` would fall back to the padded forward whatever the batch: ESM-1 models and the f16x3
-    precision mode have no token-packed form.  ``varlen=True`` then runs the padded path."""
-    from .esm2 import _weight_split
-
-    return _weight_split() != 4 and not getattr(model, "_engine_esm1", 0)
 
 
 def _check_chunk_rows(varlen, chunk_rows):
@@ -265,7 +219,7 @@ def _masked_chunks(model, tokens, positions, chunk, residues_only, varlen=False,
     B, T = tok.shape
     tok_cpu = tok.cpu()
     src, pos = _position_rows(model, tok_cpu, positions, residues_only)
-    if varlen and _packs(model):
+    if varlen and model._packs():
         one = torch.arange(src.numel() + 1, dtype=torch.int64)  # one masked position, one selected row per copy
         yield src.to(tok.device), pos.to(tok.device), _packed_copies(model, tok, _token_lengths(model, tok_cpu), src, one, pos,
                                                                      one, pos, chunk_rows)
@@ -317,7 +271,7 @@ def wt_marginals(model, tokens, varlen=False, chunk_rows=None):
     tok = _device_tokens(model, tokens)
     B, T = tok.shape
     out = torch.zeros((B, T, model.alphabet_size), dtype=torch.float32, device=tok.device)
-    if varlen and _packs(model):
+    if varlen and model._packs():
         tok_cpu = tok.cpu()
         lengths = _token_lengths(model, tok_cpu)
         real = tok_cpu.ne(model.padding_idx)
@@ -359,7 +313,7 @@ def pseudo_log_likelihood(model, tokens, positions=None, chunk=None, varlen=Fals
 
     _check_chunk_rows(varlen, chunk_rows)
     tok = _device_tokens(model, tokens)
-    if varlen and _packs(model):
+    if varlen and model._packs():
         (src, pos, lp), = _masked_chunks(model, tok, positions, chunk, residues_only=True, varlen=True, chunk_rows=chunk_rows)
         if src.numel() == 0:
             return torch.zeros((tok.shape[0],), dtype=torch.float64, device=tok.device)
@@ -425,7 +379,7 @@ def masked_joint(model, tokens, position_sets, src=None, chunk=None, return_logi
     if not sets:
         empty = torch.empty((0, V), dtype=torch.float32, device=dev)
         return (offsets, pos.to(dev), empty) + ((empty.clone(),) if return_logits else ())
-    if varlen and _packs(model):
+    if varlen and model._packs():
         got = _packed_copies(model, tok, _token_lengths(model, tok.cpu()), torch.tensor(src, dtype=torch.int64), offsets, pos,
                              offsets, pos, chunk_rows, return_logits=return_logits)
         return (offsets, pos.to(dev)) + (got if return_logits else (got,))

@@ -421,3 +421,48 @@ def test_ln_fold_is_not_chosen_for_checkpoints_with_small_layernorm_gains(monkey
     assert esm2.ln_fold_hazard(g) == 0.0
     g[1, 5] = 0.0
     assert esm2.ln_fold_hazard(g) > 1e6
+
+
+def _fold_models():
+    """A plain L=6, E=320, H=20 model whose fold decision has been taken (cache filled), and the outlier weights to load."""
+    from esm_amd.synth import add_outlier_channels, skip_param_init
+
+    L, E, H = 6, 320, 20
+    with skip_param_init():
+        model = esm.ESM2(L, E, H).eval()
+    model.load_state_dict(synth_esm2_state_dict(L, E, H, seed=0))
+    assert model._fold_setting() == 0 and model._fold_hazard == 0.0
+    outliers = synth_esm2_state_dict(L, E, H, seed=0)
+    add_outlier_channels(outliers, L, E, magnitude=500.0)
+    return model, outliers
+
+
+@pytest.mark.parametrize("how", ["deepcopy", "in_place", "pickle"])
+def test_fold_decision_follows_the_current_gains(monkeypatch, how):
+    """ESM2._fold_setting is taken from the gains the model holds NOW (the hazard cache is keyed on the gain tensors): weights
+    that need the fold off, loaded without ``refresh_engine()`` into a copy of a model that has already decided (deepcopy,
+    pickle round trip) or into that model itself, turn it off — and a copy's decision leaves the original's alone."""
+    import copy
+    import pickle
+
+    monkeypatch.delenv("ESM_AMD_LN_FOLD", raising=False)
+    model, outliers = _fold_models()
+    target = {"deepcopy": copy.deepcopy, "in_place": lambda m: m, "pickle": lambda m: pickle.loads(pickle.dumps(m))}[how](model)
+    target.load_state_dict(outliers)
+    assert target._fold_setting() == -1 and target._fold_hazard > 0.5
+    if target is not model:
+        assert model._fold_setting() == 0 and model._fold_hazard == 0.0
+
+
+def test_fold_hazard_is_computed_once_per_set_of_gains(monkeypatch):
+    """ln_fold_hazard ends in ``.item()`` (a device sync on a GPU model): unchanged weights must not compute it again."""
+    from esm_amd import esm2
+
+    monkeypatch.delenv("ESM_AMD_LN_FOLD", raising=False)
+    model, outliers = _fold_models()
+    calls = []
+    hazard = esm2.ln_fold_hazard
+    monkeypatch.setattr(esm2, "ln_fold_hazard", lambda gains: calls.append(1) or hazard(gains))
+    assert model._fold_setting() == 0 and model._fold_setting() == 0 and not calls
+    model.load_state_dict(outliers)
+    assert model._fold_setting() == -1 and model._fold_setting() == -1 and len(calls) == 1
