@@ -102,11 +102,52 @@ ESMK_DEV void epilogue9_f32(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base,
     const int ldc = p.N;
     const int g4 = lane >> 4, l16 = lane & 15;
     f32x4 old[D][4];
-    auto load_old = [&](f32x4 (&dst)[4], int piece) ESMK_INL {
-        const int i = piece >> 2, jb = piece & 3;
+    // LNF, full blocks: every address is a wave-uniform base of the wave's block (scalar registers; the block's place in the
+    // launch goes there, so the lane part stays small at any batch size) + one 32-bit byte offset per lane and row pass it
+    // + an immediate.  As 64-bit per-lane pointers the address state of out, h16, ln_mean and ln_part did not fit next to
+    // the three residual pieces: 176 bytes of scratch, an accumulator quad spilled around the epilogue and seven address
+    // reloads in a row at its entry, each draining the queue the residual loads had just entered.
+    // The lane as the address arithmetic sees it is opaque and formed here, per tile: left to the compiler, the per-lane
+    // offsets (loop invariants) were hoisted out of the tile loop and lived — or were spilled — across the K loop.
+    constexpr bool SADDR = LNF && FULL;
+    int la = lane;
+    if constexpr (LNF) asm volatile("" : "+v"(la));
+    typedef unsigned long long u64;
+    u64 ob = 0, hb = 0, pb = 0, mb = 0;  // row 0, column 0 of the wave's block of out / h16 / ln_part, row 0 of ln_mean
+    unsigned ov[4], hv[4];  // rows 8 it + lane / 8: out columns 4 (lane & 7) .., h16 bytes of the pair-swapped 16-byte half
+    unsigned o_rb = 0, h_rb = 0, p_rb = 0;  // bytes per 8 rows
+    if constexpr (SADDR) {
+        ob = (u64)out + ((u64)m_base * (u64)ldc + (u64)n_base) * 4;
+        hb = (u64)h16 + ((u64)m_base * (u64)p.ldh + (u64)n_base) * sizeof(T);
+        pb = (u64)p.ln_part + ((u64)m_base * (u64)p.ln_parts + (u64)(n_base >> 7)) * 8;
+        mb = (u64)(p.ln_mean + m_base);
+        o_rb = 32u * (unsigned)ldc, h_rb = 8u * (unsigned)sizeof(T) * (unsigned)p.ldh, p_rb = 64u * (unsigned)p.ln_parts;
+        const unsigned r8 = la >> 3, c8 = la & 7;
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-            const int pc = it * 64 + lane;
+            ov[it] = (8u * it + r8) * 4u * (unsigned)ldc + 16u * c8;
+            // even lane: columns 4 c8 .. of the pair's first piece; odd lane: columns 4 (c8 - 1) .. of the second (+ 32)
+            hv[it] = (8u * it + r8) * (unsigned)sizeof(T) * (unsigned)p.ldh + (unsigned)sizeof(T) * ((c8 & 1) ? 32u + 4u * (c8 - 1) : 4u * c8);
+        }
+    }
+    // out: rows 32 i + 8 it + lane / 8, columns 32 jb + 4 (lane & 7) .. of the block
+    // base (pinned to scalar registers) + immediate + zero-extended lane offset, in the global address space
+    auto gaddr = [](u64 base, int imm, unsigned off, auto* as) ESMK_INL {
+        asm("" : "+s"(base));
+        typedef typename std::remove_pointer<decltype(as)>::type E;
+        return (__attribute__((address_space(1))) E*)(base + (u64)imm + (u64)off);
+    };
+    auto out_at = [&](int i, int jb, int it) ESMK_INL { return gaddr(ob + (u64)(4 * i) * o_rb, 128 * jb, ov[it], (f32x4*)nullptr); };
+    auto load_old = [&](f32x4 (&dst)[4], int piece) ESMK_INL {
+        const int i = piece >> 2, jb = piece & 3;
+        if constexpr (SADDR) {
+#pragma unroll
+            for (int it = 0; it < 4; ++it) dst[it] = *out_at(i, jb, it);
+            return;
+        }
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const int pc = it * 64 + la;
             const int m = FULL ? m_base + 32 * i + (pc >> 3) : min(m_base + 32 * i + (pc >> 3), p.M - 1);
             const int n = FULL ? n_base + 32 * jb + (pc & 7) * 4 : min(n_base + 32 * jb + (pc & 7) * 4, p.N - 4);
             dst[it] = *reinterpret_cast<const f32x4*>(out + (size_t)m * ldc + n);
@@ -119,8 +160,11 @@ ESMK_DEV void epilogue9_f32(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base,
     auto load_means = [&](int i) ESMK_INL {
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-            const int m = m_base + 32 * i + it * 8 + (lane >> 3);
-            cmv[i & 1][it] = (kExperiments && (p.lnf_dbg & 4)) ? 0.f : p.ln_mean[FULL ? m : min(m, p.M - 1)];
+            const int m = m_base + 32 * i + it * 8 + (la >> 3);
+            if constexpr (SADDR)
+                cmv[i & 1][it] = (kExperiments && (p.lnf_dbg & 4)) ? 0.f : *gaddr(mb, 4 * (32 * i + 8 * it), 4u * (unsigned)(la >> 3), (const float*)nullptr);
+            else
+                cmv[i & 1][it] = (kExperiments && (p.lnf_dbg & 4)) ? 0.f : p.ln_mean[FULL ? m : min(m, p.M - 1)];
         }
     };
     if constexpr (LNF)
@@ -153,7 +197,7 @@ ESMK_DEV void epilogue9_f32(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base,
         }
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-            const int pc = it * 64 + lane;
+            const int pc = it * 64 + la;
             const int r = pc >> 3, cc = pc & 7;
             f32x4 v = vv[it];
             if constexpr (EPI == EPI_RESID_F32) {
@@ -165,8 +209,13 @@ ESMK_DEV void epilogue9_f32(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base,
             if (inside) {
                 // non-temporal: a tile's output is not read again by this launch; kept out of the way of the operand
                 // panels in the XCD's L2 (profiles/r3_gemm9_mi16_variants.log: +4 .. 7 % on the K = 1280 shapes)
-                if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out + (size_t)m * ldc + n));
-                else *reinterpret_cast<f32x4*>(out + (size_t)m * ldc + n) = v;
+                if constexpr (SADDR) {
+                    if constexpr (NT) __builtin_nontemporal_store(v, out_at(i, jb, it));
+                    else *out_at(i, jb, it) = v;
+                } else {
+                    if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out + (size_t)m * ldc + n));
+                    else *reinterpret_cast<f32x4*>(out + (size_t)m * ldc + n) = v;
+                }
             }
             if (LNF && lnp) {
                 const float c = cmv[i & 1][it];
@@ -194,11 +243,17 @@ ESMK_DEV void epilogue9_f32(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base,
                     recv.x = (unsigned)__builtin_amdgcn_update_dpp(0, (int)send.x, 0xB1, 0xf, 0xf, true);
                     recv.y = (unsigned)__builtin_amdgcn_update_dpp(0, (int)send.y, 0xB1, 0xf, 0xf, true);
                     const u32x4 o = odd ? u32x4{recv.x, recv.y, cur.x, cur.y} : u32x4{prev.x, prev.y, recv.x, recv.y};
-                    const int col = n_base + (odd ? 32 * jb + 4 * (cc - 1) : 32 * (jb - 1) + 4 * cc);
+                    const int col = n_base + ((la & 1) ? 32 * jb + 4 * (cc - 1) : 32 * (jb - 1) + 4 * cc);
                     if ((FULL || (m < p.M && col < p.N)) && !(kExperiments && (p.lnf_dbg & 1))) {
-                        auto* hd = reinterpret_cast<u32x4*>(h16 + (size_t)m * p.ldh + col);
-                        if constexpr (NT) __builtin_nontemporal_store(o, hd);
-                        else *hd = o;
+                        if constexpr (SADDR) {
+                            auto* hd = gaddr(hb + (u64)(4 * i) * h_rb, 32 * (jb - 1) * (int)sizeof(T), hv[it], (u32x4*)nullptr);
+                            if constexpr (NT) __builtin_nontemporal_store(o, hd);
+                            else *hd = o;
+                        } else {
+                            auto* hd = reinterpret_cast<u32x4*>(h16 + (size_t)m * p.ldh + col);
+                            if constexpr (NT) __builtin_nontemporal_store(o, hd);
+                            else *hd = o;
+                        }
                     }
                 }
             }
@@ -218,10 +273,14 @@ ESMK_DEV void epilogue9_f32(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base,
                     b += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, b), 0x112, 0xf, 0xf, true));
                     a += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a), 0x114, 0xf, 0xf, true));
                     b += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, b), 0x114, 0xf, 0xf, true));
-                    const int m = m_base + 32 * i + it * 8 + (lane >> 3);
+                    const int m = m_base + 32 * i + it * 8 + (la >> 3);
                     if ((lane & 7) == 7 && (FULL || m < p.M)) {
                         f32x2 st = {a, b};
-                        *reinterpret_cast<f32x2*>(p.ln_part + ((size_t)m * p.ln_parts + (n_base >> 7)) * 2) = st;
+                        if constexpr (SADDR) {
+                            *gaddr(pb + (u64)(4 * i + it) * p_rb, 0, (unsigned)(la >> 3) * 8u * (unsigned)p.ln_parts, (f32x2*)nullptr) = st;
+                        } else {
+                            *reinterpret_cast<f32x2*>(p.ln_part + ((size_t)m * p.ln_parts + (n_base >> 7)) * 2) = st;
+                        }
                     }
                 }
             }
@@ -869,7 +928,11 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
             bool want = p.bias != nullptr;
             if constexpr (EPI == EPI_QKV_ALL) want = want && n_base < 2 * p.E;  // v tiles: the epilogue adds the bias
             if (want) {
-                const int g4 = lane >> 4;
+                // (LayerNorm-fold producer: formed here, per tile, from an opaque lane — hoisted out of the tile loop the
+                // lane's bias address had no register left and was reloaded from scratch behind every epilogue)
+                int lb = lane;
+                if constexpr (LNF && EPI == EPI_RESID_F32) asm volatile("" : "+v"(lb));
+                const int g4 = lb >> 4;
                 if (n_base + 128 <= p.N) {
 #pragma unroll
                     for (int nj = 0; nj < 8; ++nj) bv[nj] = *reinterpret_cast<const f32x4*>(p.bias + n_base + 16 * nj + 4 * g4);
@@ -1070,6 +1133,11 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
                 int tm2, tn2;
                 tile_coords(it + 1, tm2, tn2);
                 load_bias(tn2 * 256 + wc * 128);
+            } else if constexpr (LNF && EPI == EPI_RESID_F32) {
+                // last tile: without a value on this path the dead bias quads count as live through the whole tile —
+                // 32 registers the LayerNorm-fold producer's epilogue does not have (it spilled them)
+#pragma unroll
+                for (int nj = 0; nj < 8; ++nj) bv[nj] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
         };
         if constexpr (BIAS_EARLY) next_bias();
