@@ -256,6 +256,12 @@ SIGNATURES = {
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint64, c_float, ctypes.c_uint64, c_int, c_void_p, c_void_p,
                 c_void_p, c_int, c_int, c_void_p]),
     "esmk_op_commit_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    # decoding: the draw behind a top-k / nucleus filter with a per-row confidence; the per-chain choice of the best rows
+    "esmk_op_sample_rows_ex": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint64, c_float, ctypes.c_uint64, c_int, c_int, c_float, c_int,
+                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "esmk_op_select_rows": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     # the categorical Jacobian: substituted copies, the scatter of logit differences into J, centring, contact map, APC
     "esmk_op_substitute_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "esmk_op_jacobian_scatter": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

@@ -926,6 +926,43 @@ int esmk_op_sample_rows(const float* logprobs_dev, const int32_t* row_chain_dev,
     return 0;
 }
 
+int esmk_op_sample_rows_ex(const float* logprobs_dev, const int32_t* row_chain_dev, const int32_t* row_index_dev,
+                           const int32_t* exclude_dev, uint64_t allowed_mask, float inv_temperature, uint64_t seed, int step,
+                           int top_k, float top_p, int score_kind, int32_t* token_out_dev, float* logq_out_dev, float* u_out_dev,
+                           float* score_out_dev, uint64_t* kept_out_dev, int n, int V, void* stream) {
+    if (!logprobs_dev || !row_chain_dev || !row_index_dev || !token_out_dev || !logq_out_dev)
+        return fail("esmk_op_sample_rows_ex: null argument");
+    if (n <= 0 || n > ESMK_MAX_ROWS) return fail("esmk_op_sample_rows_ex: n must be in 1 .. 2^24");
+    if (V <= 0 || V > 64) return fail("esmk_op_sample_rows_ex: V must be in 1 .. 64 (one vocabulary entry per lane)");
+    if (!(inv_temperature >= 0.f) || inv_temperature > 3.0e38f)
+        return fail("esmk_op_sample_rows_ex: inv_temperature must be finite and not negative (0: greedy)");
+    if (step < 0) return fail("esmk_op_sample_rows_ex: step must not be negative");
+    if (top_k < 0 || top_k > 64) return fail("esmk_op_sample_rows_ex: top_k must be in 0 .. 64 (0: off)");
+    if (!(top_p > 0.f && top_p <= 1.f)) return fail("esmk_op_sample_rows_ex: top_p must be in (0, 1] (1: off)");
+    if (score_kind < 0 || score_kind > 2)
+        return fail("esmk_op_sample_rows_ex: score_kind must be 0 (none), 1 (confidence) or 2 (negative entropy)");
+    if (score_kind != 0 && !score_out_dev) return fail("esmk_op_sample_rows_ex: a score_kind other than 0 needs score_out_dev");
+    ESMK_TRY(launch_sample_rows_ex(logprobs_dev, row_chain_dev, row_index_dev, exclude_dev, (unsigned long long)allowed_mask,
+                                   inv_temperature, (unsigned long long)seed, step, top_k, top_p, score_kind, token_out_dev,
+                                   logq_out_dev, u_out_dev, score_out_dev, (unsigned long long*)kept_out_dev, n, V,
+                                   (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_select_rows(const float* score_dev, const int32_t* row_off_dev, const int32_t* sel_off_dev,
+                        const int32_t* rest_off_dev, int32_t* sel_out_dev, int32_t* rest_out_dev, int n_chain, int n, int n_sel,
+                        int n_rest, void* stream) {
+    if (!score_dev || !row_off_dev || !sel_off_dev || !sel_out_dev) return fail("esmk_op_select_rows: null argument");
+    if (n_chain <= 0 || n_chain > ESMK_MAX_ROWS || n <= 0 || n > ESMK_MAX_ROWS || n_sel <= 0 || n_sel > ESMK_MAX_ROWS)
+        return fail("esmk_op_select_rows: n_chain, n and n_sel must be in 1 .. 2^24");
+    if (n_rest < 0 || n_rest > ESMK_MAX_ROWS) return fail("esmk_op_select_rows: n_rest must be in 0 .. 2^24");
+    if (n_rest > 0 && (!rest_off_dev || !rest_out_dev))
+        return fail("esmk_op_select_rows: n_rest > 0 needs rest_off_dev and rest_out_dev");
+    ESMK_TRY(launch_select_rows(score_dev, row_off_dev, sel_off_dev, rest_off_dev, sel_out_dev, rest_out_dev, n_chain, n, n_sel,
+                                n_rest, (hipStream_t)stream));
+    return 0;
+}
+
 int esmk_op_commit_tokens(int64_t* tokens_dev, const int32_t* row_chain_slot_dev, const int32_t* pos_dev,
                           const int32_t* token_dev, int n, int B, int T, void* stream) {
     if (!tokens_dev || !row_chain_slot_dev || !pos_dev || !token_dev) return fail("esmk_op_commit_tokens: null argument");

@@ -239,6 +239,17 @@ hipError_t launch_permute_positions(const int* pos_off, const int* pos_in, const
 hipError_t launch_sample_rows(const float* lp, const int* row_chain, const int* row_index, const int* exclude,
                               unsigned long long allowed, float inv_temperature, unsigned long long seed, int step,
                               int* token_out, float* logq_out, float* u_out, int n, int V, hipStream_t st);
+// launch_sample_rows with a top-k / nucleus filter in front of the draw (rank by the fp32 inputs, fp32 weights added in rank
+// order; top_k == 0 and top_p == 1: off, the bits of launch_sample_rows) and a per-row score over the unfiltered candidates
+// (score_kind 0 none, 1 max log q, 2 sum q log q; fp64, rounded once); score_out fp32 [n], kept_out uint64 [n] (optional)
+hipError_t launch_sample_rows_ex(const float* lp, const int* row_chain, const int* row_index, const int* exclude,
+                                 unsigned long long allowed, float inv_temperature, unsigned long long seed, int step, int top_k,
+                                 float top_p, int score_kind, int* token_out, float* logq_out, float* u_out, float* score_out,
+                                 unsigned long long* kept_out, int n, int V, hipStream_t st);
+// per chain c (rows row_off[c] : row_off[c+1] of score fp32 [n]) the sel_off[c+1] - sel_off[c] rows of the largest score, best
+// first, into sel_out[sel_off[c] ..], the others in ascending row order into rest_out[rest_off[c] ..]; one workgroup per chain
+hipError_t launch_select_rows(const float* score, const int* row_off, const int* sel_off, const int* rest_off, int* sel_out,
+                              int* rest_out, int n_chain, int n, int n_sel, int n_rest, hipStream_t st);
 // tokens[slot[i], pos[i]] = token[i] on int64 [B,T]; token < 0 or pos outside [0,T) writes nothing, slot clamped to [0,B)
 hipError_t launch_commit_tokens(int64_t* tokens, const int* slot, const int* pos, const int* token, int n, int B, int T,
                                 hipStream_t st);

@@ -392,20 +392,22 @@ class ESM2(_EngineHost, nn.Module):
 
     # drawing sequences (esm_amd/sampling.py): Gibbs sweeps and mask in-painting, every step on the device
     def gibbs_sample(self, tokens, sweeps, per_step=1, positions=None, temperature=1.0, allowed=None, force_new=False, seed=0,
-                     chain_ids=None, return_trajectory=False):
+                     chain_ids=None, return_trajectory=False, top_k=0, top_p=1.0, order="random"):
         """``esm_amd.sampling.gibbs_sample``: the final tokens [B, T] of ``sweeps`` Gibbs sweeps over every chain's positions."""
         from . import sampling
 
         return sampling.gibbs_sample(self, tokens, sweeps, per_step=per_step, positions=positions, temperature=temperature,
                                      allowed=allowed, force_new=force_new, seed=seed, chain_ids=chain_ids,
-                                     return_trajectory=return_trajectory)
+                                     return_trajectory=return_trajectory, top_k=top_k, top_p=top_p, order=order)
 
-    def inpaint(self, tokens, per_step=1, temperature=1.0, allowed=None, seed=0, chain_ids=None, return_trajectory=False):
-        """``esm_amd.sampling.inpaint``: ``tokens`` [B, T] with every <mask> position filled by a draw from the model."""
+    def inpaint(self, tokens, per_step=1, temperature=1.0, allowed=None, seed=0, chain_ids=None, return_trajectory=False,
+                top_k=0, top_p=1.0, order="random"):
+        """``esm_amd.sampling.inpaint``: ``tokens`` [B, T] with every <mask> position filled by a draw from the model, in a
+        random order or the most confident positions first (``order``), behind an optional top-k / nucleus filter."""
         from . import sampling
 
         return sampling.inpaint(self, tokens, per_step=per_step, temperature=temperature, allowed=allowed, seed=seed,
-                                chain_ids=chain_ids, return_trajectory=return_trajectory)
+                                chain_ids=chain_ids, return_trajectory=return_trajectory, top_k=top_k, top_p=top_p, order=order)
 
     # the categorical Jacobian (esm_amd/jacobian.py): substituted copies in batches that fill the GPU, J kept on the device
     def categorical_jacobian(self, tokens, allowed=None, chunk=None, center=False, max_bytes=8 << 30):

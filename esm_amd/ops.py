@@ -552,7 +552,7 @@ def sum_target_rows(logprobs, target, offsets):
     return out
 
 
-# ---- sampling (include/esmk.h: esmk_op_permute_positions, esmk_op_sample_rows, esmk_op_commit_tokens) -----------------------
+# ---- sampling (include/esmk.h: esmk_op_permute_positions, esmk_op_sample_rows[_ex], esmk_op_select_rows, esmk_op_commit_tokens)
 def _seed64(seed):
     seed = int(seed)
     if not 0 <= seed < 2 ** 64:
@@ -603,6 +603,83 @@ def sample_rows(logprobs, row_chain, row_index, allowed_mask, inv_temperature=1.
                                       float(inv_temperature), _seed64(seed), int(step), N.ptr(token), N.ptr(logq), N.ptr(u), n,
                                       V, N.cur_stream()))
     return token, logq, u
+
+
+SCORE_KINDS = {None: 0, "none": 0, "confidence": 1, "entropy": 2}  # score_kind of esmk_op_sample_rows_ex
+
+
+def check_filters(top_k, top_p):
+    """``(int top_k, float top_p)`` of esmk_op_sample_rows_ex, or ValueError: top_k in 0 .. 64 (0: off), top_p in (0, 1] (1: off)."""
+    if int(top_k) != top_k or not 0 <= int(top_k) <= 64:
+        raise ValueError(f"top_k {top_k!r} must be an integer in 0 .. 64 (0: no top-k filter)")
+    top_p = float(top_p)
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p {top_p!r} must lie in (0, 1] (1: no nucleus filter)")
+    return int(top_k), top_p
+
+
+def sample_rows_ex(logprobs, row_chain, row_index, allowed_mask, inv_temperature=1.0, seed=0, step=0, exclude=None, want_u=True,
+                   top_k=0, top_p=1.0, score=None, want_kept=True):
+    """``sample_rows`` behind a top-k / nucleus filter, with a per-row score: ``(token int32 [n], logq fp32 [n], u fp32 [n] or
+    None, score fp32 [n] or None, kept int64 [n] or None)``.  The candidates are ranked by their fp32 log-probability (ties: the
+    lower token; NaN last); rank r is kept when ``(top_k == 0 or r < top_k) and (top_p >= 1 or E_r < top_p * W)``, E_r the fp32
+    sum of the weights ``expf(z - max z)`` of the ranks before r, W the sum of all (include/esmk.h); the best candidate is
+    always kept, and the draw and ``logq`` are those of ``sample_rows`` over the kept set.  ``top_k=0, top_p=1.0``: no filter,
+    the bits of ``sample_rows``.  ``score``: None, ``"confidence"`` (max log q) or ``"entropy"`` (sum q log q, the negative
+    entropy), q = softmax(logprobs * inv_temperature) over the candidates before filtering (greedy: inv_temperature 1); -inf
+    for a row without candidates.  ``kept``: the kept set of every row as the 64-bit pattern of an int64 (bit 63 is the sign)."""
+    _req_cuda(logprobs, row_chain, row_index, exclude)
+    assert logprobs.dtype == torch.float32 and logprobs.dim() == 2 and logprobs.is_contiguous()
+    n, V = logprobs.shape
+    for t in (row_chain, row_index) + ((exclude,) if exclude is not None else ()):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.numel() == n and t.is_contiguous()
+    allowed_mask = int(allowed_mask)
+    if not 0 <= allowed_mask < 2 ** 64:
+        raise ValueError("allowed_mask is a bitset over at most 64 vocabulary entries")
+    top_k, top_p = check_filters(top_k, top_p)
+    if score not in SCORE_KINDS:
+        raise ValueError(f"score {score!r}: None, 'confidence' or 'entropy'")
+    kind = SCORE_KINDS[score]
+    dev = logprobs.device
+    token = torch.empty((n,), dtype=torch.int32, device=dev)
+    logq = torch.empty((n,), dtype=torch.float32, device=dev)
+    u = torch.empty((n,), dtype=torch.float32, device=dev) if want_u else None
+    score_out = torch.empty((n,), dtype=torch.float32, device=dev) if kind else None
+    kept = torch.empty((n,), dtype=torch.int64, device=dev) if want_kept else None
+    N.check(N.lib.esmk_op_sample_rows_ex(N.ptr(logprobs), N.ptr(row_chain), N.ptr(row_index), N.ptr(exclude), allowed_mask,
+                                         float(inv_temperature), _seed64(seed), int(step), top_k, top_p, kind, N.ptr(token),
+                                         N.ptr(logq), N.ptr(u), N.ptr(score_out), N.ptr(kept), n, V, N.cur_stream()))
+    return token, logq, u, score_out, kept
+
+
+def select_rows(score, row_offsets, sel_offsets, rest_offsets=None, n_sel=None, n_rest=0, sel_out=None, rest_out=None):
+    """Per chain the rows of the largest score: ``(sel int32 [n_sel], rest int32 [n_rest] or None)``.  Chain c owns the rows
+    ``row_offsets[c] : row_offsets[c + 1]`` of ``score`` fp32 [n] (offsets clamped to [0, n]; a descending pair is an empty
+    list); ``sel[sel_offsets[c] : sel_offsets[c + 1]]`` receives the row indices of its best rows, best first (ties: the lower
+    row; NaN below everything), at most as many as the chain has; ``rest[rest_offsets[c] : rest_offsets[c + 1]]`` the other rows
+    in ascending order, at most as many as the slice holds.  All offsets int32 [n_chain + 1] on the device; the host never
+    reads them, so it passes the lengths ``n_sel`` / ``n_rest`` of the outputs (or the outputs themselves: elements outside
+    every slice are left as they are; fresh outputs are filled with -1)."""
+    _req_cuda(score, row_offsets, sel_offsets, rest_offsets, sel_out, rest_out)
+    assert score.dtype == torch.float32 and score.dim() == 1 and score.is_contiguous()
+    n = score.numel()
+    n_chain = row_offsets.numel() - 1
+    assert n >= 1 and n_chain >= 1
+    for t in (row_offsets, sel_offsets) + ((rest_offsets,) if rest_offsets is not None else ()):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.numel() == n_chain + 1 and t.is_contiguous()
+    dev = score.device
+    if sel_out is None:
+        sel_out = torch.full((int(n_sel),), -1, dtype=torch.int32, device=dev)
+    if rest_out is None and rest_offsets is not None and int(n_rest) > 0:
+        rest_out = torch.full((int(n_rest),), -1, dtype=torch.int32, device=dev)
+    for t in (sel_out,) + ((rest_out,) if rest_out is not None else ()):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
+    assert sel_out.numel() >= 1
+    N.check(N.lib.esmk_op_select_rows(N.ptr(score), N.ptr(row_offsets), N.ptr(sel_offsets),
+                                      N.ptr(rest_offsets if rest_out is not None else None), N.ptr(sel_out), N.ptr(rest_out),
+                                      n_chain, n, sel_out.numel(), rest_out.numel() if rest_out is not None else 0,
+                                      N.cur_stream()))
+    return sel_out, rest_out
 
 
 def commit_tokens(tokens, slots, positions, token):

@@ -7,6 +7,9 @@
 gibbs    (default) ``--sweeps`` Gibbs sweeps around every input sequence: each sweep visits all residues once in a random
          order, ``--per-step`` of them masked and redrawn together (``esm_amd.sampling.gibbs_sample``).
 inpaint  ``_`` or ``<mask>`` in the input marks the positions to fill; everything else stays (``esm_amd.sampling.inpaint``).
+         ``--order confidence`` (or ``entropy``) fills the most confident positions first instead of a random order.
+
+``--top-k`` / ``--top-p`` put a top-k / nucleus filter in front of every draw, in either mode.
 
 Every input record is run as ``--num-chains`` chains.  Chain ids count through the output (record r, copy c: r * num_chains +
 c), and a draw depends on (seed, chain id) alone, so one record of the output can be drawn again by itself.  The output is a
@@ -17,6 +20,7 @@ import pathlib
 import sys
 
 MODES = ("gibbs", "inpaint")
+ORDERS = ("random", "confidence", "entropy")
 PER_CALL = 64  # chains per call
 
 
@@ -31,6 +35,10 @@ def create_parser():
     p.add_argument("--sweeps", type=int, default=1, help="Gibbs sweeps (gibbs only)")
     p.add_argument("--per-step", type=int, default=1, help="positions masked and drawn together in one step")
     p.add_argument("--temperature", type=float, default=1.0, help="0: the argmax")
+    p.add_argument("--top-k", type=int, default=0, help="draw from the k most probable candidates only (0: all)")
+    p.add_argument("--top-p", type=float, default=1.0, help="draw from the nucleus of this probability mass only (1: all)")
+    p.add_argument("--order", type=str, default="random", choices=ORDERS,
+                   help="inpaint only: a random order, or the most confident positions first (max log q / negative entropy)")
     p.add_argument("--num-chains", type=int, default=1, help="chains per input sequence")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--output", type=pathlib.Path, required=True, help="FASTA file to write")
@@ -50,6 +58,12 @@ def parse_args(argv=None):
         parser.error("--temperature must be finite and not negative")
     if not 0 <= args.seed < 2 ** 64:
         parser.error("--seed must lie in [0, 2^64)")
+    if not 0 <= args.top_k <= 64:
+        parser.error("--top-k must lie in 0 .. 64 (0: no top-k filter)")
+    if not 0.0 < args.top_p <= 1.0:
+        parser.error("--top-p must lie in (0, 1] (1: no nucleus filter)")
+    if args.order != "random" and args.mode != "inpaint":
+        parser.error("--order applies to --mode inpaint only: a Gibbs sweep has no masked positions to rank")
     return args
 
 
@@ -97,9 +111,10 @@ def sample_records(model, alphabet, chains, args):
         ids = [cid for _, cid, _ in part]
         if args.mode == "gibbs":
             final = model.gibbs_sample(tokens, args.sweeps, per_step=args.per_step, temperature=args.temperature, seed=args.seed,
-                                       chain_ids=ids)
+                                       chain_ids=ids, top_k=args.top_k, top_p=args.top_p)
         else:
-            final = model.inpaint(tokens, per_step=args.per_step, temperature=args.temperature, seed=args.seed, chain_ids=ids)
+            final = model.inpaint(tokens, per_step=args.per_step, temperature=args.temperature, seed=args.seed, chain_ids=ids,
+                                  top_k=args.top_k, top_p=args.top_p, order=args.order)
         out += [decode(alphabet, row) for row in final.cpu().tolist()]
     return out
 

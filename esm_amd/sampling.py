@@ -21,8 +21,27 @@ and every kernel of the forward is batch-invariant bit for bit, so a chain follo
 batch: ``chain_ids`` names the chains, not their place in the batch.  Chains of different lengths finish an epoch at different
 steps; the ones that are done leave the batch until the next epoch begins.
 
+``top_k`` / ``top_p`` put a filter in front of every draw (``esmk_op_sample_rows_ex``): the candidates are ranked by their
+log-probability, and only the ``top_k`` best, and of those only the ranks whose preceding mass is below ``top_p`` of the total
+(the nucleus), are drawn from; the best candidate always stays.  With both off (0 and 1.0, the defaults) the calls and the bits
+are those of the plain draw.
+
+``inpaint(order="confidence" | "entropy")`` unmasks the most confident positions first instead of a random order.  At step s
+every chain still at work has its remaining <mask> positions in the state, and the step is
+
+    esmk_forward_rows          head + log-softmax on ALL remaining <mask> rows of the chains still at work
+    esmk_op_sample_rows_ex     a token and a score per row: max log q ("confidence") or sum q log q ("entropy")
+    esmk_op_select_rows        per chain the min(per_step, remaining) rows of the largest score, best first; the others
+    esmk_op_commit_tokens      the chosen rows' tokens; the others are the next step's row list
+
+    token draw    (chain_id, s, 1, token position)      the position is the index: a draw does not depend on how many rows
+                                                        a step has
+
+The host knows every COUNT in advance (a chain of n holes has n - s * per_step left at step s) and uploads the offset tables
+once; it never learns WHICH positions were chosen.  Chains that are done leave the batch.
+
 The functions are also methods of ``ESM2`` / ``ProteinBertModel``.  They refuse the MSA Transformer (``NotImplementedError``),
-and token-packed chains, nucleus / top-p filtering and confidence-ordered unmasking are not built.
+and token-packed chains are not built.
 """
 import torch
 
@@ -31,6 +50,7 @@ from .scoring import _device_tokens, _refuse_msa, forward_rows
 STEP_STRIDE = 1 << 20  # counter word 1 of a token draw = epoch * STEP_STRIDE + step inside the epoch
 STANDARD_RESIDUES = "ACDEFGHIKLMNPQRSTVWY"
 TRAJECTORY_FIELDS = ("chain", "step", "pos", "token", "logq", "u", "logprobs")
+ORDERS = ("random", "confidence", "entropy")
 
 
 def allowed_mask(model, allowed=None):
@@ -153,10 +173,19 @@ def _check_common(per_step, temperature, chain_ids, B, dev):
     return int(per_step), (1.0 / temperature if temperature > 0.0 else 0.0), ids.to(dev)
 
 
-def _run(model, state, lists, epochs, per_step, inv_temperature, mask, force_new, seed, chain_ids, return_trajectory):
-    """The step loop: ``state`` int64 [B, T] on the device is updated in place.  Nothing inside the loop waits for the device."""
+def _check_filters(top_k, top_p):
     from . import ops
 
+    return ops.check_filters(top_k, top_p)
+
+
+def _run(model, state, lists, epochs, per_step, inv_temperature, mask, force_new, seed, chain_ids, return_trajectory, top_k=0,
+         top_p=1.0):
+    """The step loop: ``state`` int64 [B, T] on the device is updated in place.  Nothing inside the loop waits for the device.
+    A filter (``top_k`` != 0 or ``top_p`` < 1) makes the draw ``esmk_op_sample_rows_ex`` and adds ``kept`` to the trajectory."""
+    from . import ops
+
+    filtered = top_k != 0 or top_p < 1.0
     dev = state.device
     B, T = state.shape
     plan = _Plan([len(ps) for ps in lists], per_step, T, chain_ids, dev)
@@ -166,7 +195,8 @@ def _run(model, state, lists, epochs, per_step, inv_temperature, mask, force_new
         raise ValueError(f"{epochs} epochs: the counter layout holds fewer than {2 ** 31 // STEP_STRIDE}")
     pos_in = torch.tensor([p for ps in lists for p in ps], dtype=torch.int32).to(dev)
     flat_state = state.view(-1)
-    traj = {name: [] for name in TRAJECTORY_FIELDS}
+    fields = TRAJECTORY_FIELDS + (("kept",) if filtered else ())
+    traj = {name: [] for name in fields}
     for epoch in range(epochs if plan.total else 0):
         perm = ops.permute_positions(plan.pos_off, pos_in, chain_ids, seed=seed, epoch=epoch)
         pos = perm[plan.order]  # the epoch's draws, step-major
@@ -179,31 +209,120 @@ def _run(model, state, lists, epochs, per_step, inv_temperature, mask, force_new
             exclude = None
             if force_new:  # the token this draw replaces gets no mass
                 exclude = flat_state[slot.long() * T + step_pos.long()].to(torch.int32)
-            token, logq, u = ops.sample_rows(lp, plan.chain[r0:r1], plan.index[r0:r1], mask, inv_temperature, seed=seed,
-                                             step=step, exclude=exclude, want_u=return_trajectory)
+            kept = None
+            if filtered:
+                token, logq, u, _, kept = ops.sample_rows_ex(lp, plan.chain[r0:r1], plan.index[r0:r1], mask, inv_temperature,
+                                                             seed=seed, step=step, exclude=exclude, want_u=return_trajectory,
+                                                             top_k=top_k, top_p=top_p, want_kept=return_trajectory)
+            else:
+                token, logq, u = ops.sample_rows(lp, plan.chain[r0:r1], plan.index[r0:r1], mask, inv_temperature, seed=seed,
+                                                 step=step, exclude=exclude, want_u=return_trajectory)
             ops.commit_tokens(state, slot, step_pos, token)
             if return_trajectory:
-                for name, value in zip(TRAJECTORY_FIELDS, (plan.chain[r0:r1], torch.full_like(token, step), step_pos, token,
-                                                           logq, u, lp)):
+                for name, value in zip(fields, (plan.chain[r0:r1], torch.full_like(token, step), step_pos, token, logq, u, lp,
+                                                kept)):
                     traj[name].append(value)
     if not return_trajectory:
         return state
-    V = model.alphabet_size
-    empty = dict(chain=torch.int32, step=torch.int32, pos=torch.int32, token=torch.int32, logq=torch.float32, u=torch.float32)
+    return state, _joined(traj, model.alphabet_size, dev)
+
+
+_FIELD_DTYPES = dict(chain=torch.int32, step=torch.int32, pos=torch.int32, token=torch.int32, logq=torch.float32,
+                     u=torch.float32, score=torch.float32, kept=torch.int64)
+
+
+def _joined(traj, V, dev):
+    """The per-step lists of a trajectory as one tensor per field (an empty one of the field's type when nothing was drawn)."""
     out = {}
-    for name in TRAJECTORY_FIELDS:
-        if traj[name]:
-            out[name] = torch.cat(traj[name])
+    for name, parts in traj.items():
+        if parts:
+            out[name] = torch.cat(parts)
         elif name == "logprobs":
             out[name] = torch.empty((0, V), dtype=torch.float32, device=dev)
         else:
-            out[name] = torch.empty((0,), dtype=empty[name], device=dev)
+            out[name] = torch.empty((0,), dtype=_FIELD_DTYPES[name], device=dev)
+    return out
+
+
+class _OrderedPlan:
+    """The offset tables of confidence-ordered unmasking, built on the host from the hole counts alone and uploaded ONCE.  At
+    step s a chain of n holes has ``n - s * per_step`` rows left, commits ``min(per_step, left)`` of them and hands the others
+    on; the chains with rows left are the step's batch, in chain order.  Every step owns a slice of ``n_active + 1`` offsets in
+    ``row_off`` (its rows, chain-major), ``sel_off`` (the committed ones) and ``rest_off`` (the next step's rows)."""
+
+    def __init__(self, lengths, per_step, chain_ids, dev):
+        k = per_step
+        self.n_steps = max((n + k - 1) // k for n in lengths) if lengths else 0
+        self.steps = []  # (first offset, n_active, rows, committed, left over)
+        row_off, sel_off, rest_off, src, left = [], [], [], [], []
+        for s in range(self.n_steps):
+            o0 = len(row_off)
+            rows = sel = rest = 0
+            for b, n in enumerate(lengths):
+                have = n - s * k
+                if have <= 0:
+                    continue  # this chain is done: it leaves the batch
+                row_off.append(rows), sel_off.append(sel), rest_off.append(rest)
+                src.append(b), left.append(have)
+                rows, sel, rest = rows + have, sel + min(k, have), rest + have - min(k, have)
+            row_off.append(rows), sel_off.append(sel), rest_off.append(rest)
+            self.steps.append((o0, len(row_off) - o0 - 1, rows, sel, rest))
+
+        def i32(x):
+            return torch.tensor(x, dtype=torch.int32).to(dev)
+
+        self.row_off, self.sel_off, self.rest_off = i32(row_off), i32(sel_off), i32(rest_off)
+        self.src = torch.tensor(src, dtype=torch.int64).to(dev)  # per step its active chains: slice [o0 - s : o0 - s + n_active]
+        self.left = torch.tensor(left, dtype=torch.int64).to(dev)  # ... and the rows each of them has left
+        self.chain = chain_ids[self.src].contiguous()
+
+
+def _run_ordered(model, state, lists, per_step, inv_temperature, mask, seed, chain_ids, return_trajectory, top_k, top_p, order):
+    """Confidence-ordered unmasking: ``state`` int64 [B, T] on the device, its <mask> positions ``lists``, is filled in place.
+    Nothing inside the loop waits for the device: which rows a step commits is device data from ``esmk_op_select_rows``."""
+    from . import ops
+
+    dev = state.device
+    B, T = state.shape
+    plan = _OrderedPlan([len(ps) for ps in lists], per_step, chain_ids, dev)
+    if plan.n_steps > STEP_STRIDE:
+        raise ValueError(f"{plan.n_steps} steps: the counter layout holds at most {STEP_STRIDE}")
+    fields = TRAJECTORY_FIELDS + ("score", "kept")
+    traj = {name: [] for name in fields}
+    scored = {name: [] for name in ("chain", "step", "pos", "score")}
+    pos = torch.tensor([p for ps in lists for p in ps], dtype=torch.int32).to(dev)  # the rows of step 0: chain-major, ascending
+    for s, (o0, n_active, n_rows, n_sel, n_rest) in enumerate(plan.steps):
+        a0 = o0 - s  # every earlier step owns one offset more than it has chains
+        src, left = plan.src[a0: a0 + n_active], plan.left[a0: a0 + n_active]
+        local = torch.repeat_interleave(torch.arange(n_active, device=dev), left, output_size=n_rows)  # row -> chain of the step
+        batch = state if n_active == B else state.index_select(0, src)
+        lp = forward_rows(model, batch, (local * T + pos).to(torch.int32))
+        chain = plan.chain[a0: a0 + n_active][local].contiguous()
+        token, logq, u, score, kept = ops.sample_rows_ex(lp, chain, pos, mask, inv_temperature, seed=seed, step=s,
+                                                         want_u=return_trajectory, top_k=top_k, top_p=top_p, score=order,
+                                                         want_kept=return_trajectory)
+        sel, rest = ops.select_rows(score, plan.row_off[o0: o0 + n_active + 1], plan.sel_off[o0: o0 + n_active + 1],
+                                    plan.rest_off[o0: o0 + n_active + 1], n_sel=n_sel, n_rest=n_rest)
+        pick = sel.long()
+        ops.commit_tokens(state, src[local[pick]].to(torch.int32), pos[pick], token[pick])
+        if return_trajectory:
+            for name, value in zip(fields, (chain[pick], torch.full_like(sel, s), pos[pick], token[pick], logq[pick], u[pick],
+                                            lp[pick], score[pick], kept[pick])):
+                traj[name].append(value)
+            for name, value in zip(scored, (chain, torch.full_like(pos, s), pos, score)):
+                scored[name].append(value)
+        if rest is not None:
+            pos = pos[rest.long()]
+    if not return_trajectory:
+        return state
+    out = _joined(traj, model.alphabet_size, dev)
+    out["scored"] = _joined(scored, model.alphabet_size, dev)
     return state, out
 
 
 @torch.no_grad()
 def gibbs_sample(model, tokens, sweeps, per_step=1, positions=None, temperature=1.0, allowed=None, force_new=False, seed=0,
-                 chain_ids=None, return_trajectory=False):
+                 chain_ids=None, return_trajectory=False, top_k=0, top_p=1.0, order="random"):
     """Gibbs sampling around ``tokens`` int64 ``[B, T]`` (padded as for ``forward``; every row is a chain): the final tokens
     ``[B, T]`` on the model's device.
 
@@ -220,25 +339,52 @@ def gibbs_sample(model, tokens, sweeps, per_step=1, positions=None, temperature=
     return_trajectory  also a dict of device tensors, one entry per draw in the order drawn (step-major, chain-major inside a
                  step): ``chain``, ``step`` (epoch * STEP_STRIDE + step inside the epoch), ``pos``, ``token`` int32, ``logq``
                  (log-probability of the token under the distribution it was drawn from), ``u`` fp32, and ``logprobs`` fp32
-                 [n, V]: the row every draw saw."""
+                 [n, V]: the row every draw saw.  With a filter also ``kept`` int64: the kept set of every draw as a bitset.
+    top_k, top_p the filter in front of every draw: only the ``top_k`` most probable candidates (0: all), and of those only the
+                 ranks whose preceding probability mass is below ``top_p`` (1.0: all); the best candidate always stays.  The
+                 draw, and ``logq``, are relative to what is kept.
+    order        only "random": between sweeps nothing is masked, so a confidence order has no meaning here (``inpaint``)."""
     _refuse_msa(model)
     if int(sweeps) < 0:
         raise ValueError("sweeps must not be negative")
+    if order != "random":
+        if order not in ORDERS:
+            raise ValueError(f"order {order!r}: one of {ORDERS}")
+        raise ValueError(f"order {order!r}: a Gibbs sweep revisits committed positions, only inpaint can unmask by confidence")
+    top_k, top_p = _check_filters(top_k, top_p)
     tok = _device_tokens(model, tokens)
     per_step, inv_t, ids = _check_common(per_step, temperature, chain_ids, tok.shape[0], tok.device)
     lists = _position_lists(model, tok.cpu(), positions)
     return _run(model, tok.clone(), lists, int(sweeps), per_step, inv_t, allowed_mask(model, allowed), bool(force_new), seed, ids,
-                return_trajectory)
+                return_trajectory, top_k, top_p)
 
 
 @torch.no_grad()
-def inpaint(model, tokens, per_step=1, temperature=1.0, allowed=None, seed=0, chain_ids=None, return_trajectory=False):
+def inpaint(model, tokens, per_step=1, temperature=1.0, allowed=None, seed=0, chain_ids=None, return_trajectory=False, top_k=0,
+            top_p=1.0, order="random"):
     """Fill the <mask> positions of ``tokens`` int64 ``[B, T]``: the final tokens ``[B, T]`` on the model's device.  One epoch
     over the <mask> positions of every chain in a random order, ``per_step`` at a time; positions not yet visited stay <mask>
     in the state, so every draw sees what was committed before it and the last step a fully committed context.  The other
-    arguments and the trajectory are those of ``gibbs_sample``."""
+    arguments and the trajectory are those of ``gibbs_sample``.
+
+    order        "random" (above); "confidence" / "entropy": most confident first.  Every step scores ALL remaining <mask>
+                 positions of a chain — a token is drawn for each (filter and temperature as given; Philox counter (chain id,
+                 step, 1, token position)) and the row's score is max log q ("confidence") or sum q log q ("entropy": the
+                 negative entropy) of its tempered distribution over the candidates before filtering — and commits the
+                 ``per_step`` rows of the largest score (ties: the lower position); the other draws are dropped and their
+                 positions scored again in the next step's context.  ``temperature=0`` is fully deterministic.
+    trajectory   with such an order: one entry per COMMITTED draw (step-major, chain-major, best first) with the fields above
+                 plus ``score`` fp32 and ``kept`` int64, and ``scored``: a dict ``chain``, ``step``, ``pos``, ``score`` with
+                 one entry per row scored at every step (step-major, chain-major, ascending position)."""
     _refuse_msa(model)
+    if order not in ORDERS:
+        raise ValueError(f"order {order!r}: one of {ORDERS}")
+    top_k, top_p = _check_filters(top_k, top_p)
     tok = _device_tokens(model, tokens)
     per_step, inv_t, ids = _check_common(per_step, temperature, chain_ids, tok.shape[0], tok.device)
     lists = [row.nonzero().view(-1).tolist() for row in tok.cpu().eq(model.mask_idx)]
-    return _run(model, tok.clone(), lists, 1, per_step, inv_t, allowed_mask(model, allowed), False, seed, ids, return_trajectory)
+    if order != "random":
+        return _run_ordered(model, tok.clone(), lists, per_step, inv_t, allowed_mask(model, allowed), seed, ids, return_trajectory,
+                            top_k, top_p, order)
+    return _run(model, tok.clone(), lists, 1, per_step, inv_t, allowed_mask(model, allowed), False, seed, ids, return_trajectory,
+                top_k, top_p)

@@ -694,7 +694,8 @@ int esmk_op_sum_target_rows(const float* logprobs_dev, const int32_t* target_dev
 
 /* Drawing sequences from the model (esm_amd/sampling.py: Gibbs sweeps, mask in-painting).  A sampling step is
  * esmk_op_mask_rows_multi -> esmk_forward_rows -> esmk_op_sample_rows -> esmk_op_commit_tokens on one stream; the host reads
- * nothing in between.  Random numbers are plain Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key bumps 0x9E3779B9 /
+ * nothing in between.  Confidence-ordered unmasking is esmk_forward_rows on every remaining <mask> row -> esmk_op_sample_rows_ex
+ * (a draw and a score per row) -> esmk_op_select_rows (the best rows of every chain) -> esmk_op_commit_tokens.  Random numbers are plain Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key bumps 0x9E3779B9 /
  * 0xBB67AE85, ten rounds) with key = (seed & 0xffffffff, seed >> 32) and counter = (chain id, epoch or step, purpose, index),
  * purpose 0 = permutation, 1 = token draw.  A number depends on these words alone — never on a thread or block index, the
  * batch size or the launch geometry — so a chain draws the same tokens alone and inside any batch.  A uniform is
@@ -716,8 +717,34 @@ int esmk_op_sum_target_rows(const float* logprobs_dev, const int32_t* target_dev
  * esmk_op_commit_tokens: tokens[slot[i], pos[i]] = token[i] on tokens int64 [B,T]; slot, pos, token int32 [n].  A row with
  *   token < 0 or a position outside [0,T) writes nothing; a slot outside [0,B) is clamped.  The (slot, pos) pairs of one
  *   call must be distinct.
- * Refused before any HIP call: null pointers (exclude_dev and u_out_dev may be NULL), n_chain, total, n, B or T <= 0,
- * V outside 1 .. 64, a negative epoch or step, an inv_temperature that is negative or not finite, n or B*T > 2^24. */
+ * esmk_op_sample_rows_ex: esmk_op_sample_rows with a top-k / nucleus filter in front of the draw and a per-row score.  The
+ *   candidates are as above.  Candidate v RANKS before w when logprobs[v] > logprobs[w], or they are equal and v < w; NaN
+ *   ranks last.  The rank comes from the fp32 inputs (inv_temperature > 0, so it is the order of the tempered values): exact
+ *   comparison logic.  w_v = expf(z_v - m) as above; E_r = the fp32 sum of the weights of the ranks before r, added in rank
+ *   order, W = that sum over all candidates.  The candidate of rank r is KEPT when (top_k == 0 || r < top_k) && (top_p >= 1 ||
+ *   E_r < top_p * W); rank 0 is always kept.  top_k == 0 and top_p == 1 switch the filters off outright: no such arithmetic,
+ *   kept = the candidates, and token, logq and u are the bits of esmk_op_sample_rows.  The draw runs as above over the kept
+ *   set: fp32 running sums in ascending token order, the first kept token whose sum exceeds u * total (the last kept one if
+ *   none does), logq in fp64 relative to the kept set, rounded once.  Greedy (inv_temperature == 0) ignores the filters — the
+ *   argmax is rank 0 — and computes kept and the score with z = logprobs.  kept_out uint64 [n] or NULL: the kept bitset (0:
+ *   no candidate).  The score is taken over the candidates BEFORE filtering, q = softmax(z): score_kind 1 (confidence) = max
+ *   log q, 2 (negative entropy) = sum of q log q with the terms of q == 0 counted as 0, both in fp64 from the fp32 inputs and
+ *   rounded to fp32 once; 0 = none (score_out_dev may be NULL and is not written).  No candidate: score = -inf.  A row whose
+ *   candidates all hold -inf has NaN weights: with top_p < 1 only rank 0 is kept, and logq and the score are NaN.
+ * esmk_op_select_rows: the per-chain choice of the best rows.  Chain c owns the rows [row_off[c], row_off[c+1]) of score fp32
+ *   [n] (row_off int32 [n_chain+1], clamped to [0,n]; a pair with hi < lo is an empty list).  k_c = clamp(sel_off[c+1] -
+ *   sel_off[c], 0, len_c).  sel_out[sel_off[c] ..] receives the row indices (into score) of the k_c rows of the chain with the
+ *   largest score, best first: equal scores go to the lower row, NaN ranks below everything including -inf, among NaNs the
+ *   lower row first.  rest_out[rest_off[c] ..] receives the other rows of the chain in ascending row order, at most
+ *   rest_off[c+1] - rest_off[c] of them.  sel_off, rest_off int32 [n_chain+1]; sel_out int32 [n_sel], rest_out int32 [n_rest];
+ *   elements outside every slice are left untouched and nothing is written outside [0,n_sel) / [0,n_rest) whatever the
+ *   offsets hold.  One workgroup per chain counts ranks (len_c^2 comparisons: no sort, no scratch) and compacts the rest list
+ *   in order.  Comparison logic only: the result is exact and does not depend on the launch.  n_rest may be 0, with
+ *   rest_off_dev and rest_out_dev NULL: no rest list.
+ * Refused before any HIP call: null pointers (exclude_dev, u_out_dev, kept_out_dev may be NULL; score_out_dev when score_kind
+ * == 0), n_chain, total, n, B or T <= 0, V outside 1 .. 64, a negative epoch or step, an inv_temperature that is negative or
+ * not finite, n or B*T > 2^24, top_k outside 0 .. 64, a top_p outside (0, 1] or not finite, score_kind outside 0 .. 2; for
+ * esmk_op_select_rows n_chain, n or n_sel outside 1 .. 2^24, n_rest outside 0 .. 2^24. */
 int esmk_op_permute_positions(const int32_t* pos_off_dev, const int32_t* pos_in_dev, const int32_t* chain_id_dev,
                               int32_t* perm_out_dev, int n_chain, int total, uint64_t seed, int epoch, void* stream);
 int esmk_op_sample_rows(const float* logprobs_dev, const int32_t* row_chain_dev, const int32_t* row_index_dev,
@@ -725,6 +752,13 @@ int esmk_op_sample_rows(const float* logprobs_dev, const int32_t* row_chain_dev,
                         int32_t* token_out_dev, float* logq_out_dev, float* u_out_dev, int n, int V, void* stream);
 int esmk_op_commit_tokens(int64_t* tokens_dev, const int32_t* row_chain_slot_dev, const int32_t* pos_dev,
                           const int32_t* token_dev, int n, int B, int T, void* stream);
+int esmk_op_sample_rows_ex(const float* logprobs_dev, const int32_t* row_chain_dev, const int32_t* row_index_dev,
+                           const int32_t* exclude_dev, uint64_t allowed_mask, float inv_temperature, uint64_t seed, int step,
+                           int top_k, float top_p, int score_kind, int32_t* token_out_dev, float* logq_out_dev, float* u_out_dev,
+                           float* score_out_dev, uint64_t* kept_out_dev, int n, int V, void* stream);
+int esmk_op_select_rows(const float* score_dev, const int32_t* row_off_dev, const int32_t* sel_off_dev,
+                        const int32_t* rest_off_dev, int32_t* sel_out_dev, int32_t* rest_out_dev, int n_chain, int n, int n_sel,
+                        int n_rest, void* stream);
 
 /* The categorical Jacobian of one protein (esm_amd/jacobian.py): every candidate token t_a of a list of nA <= 32 put at every
  * residue position p_i of ONE sequence, J[i,a,j,b] = logits(copy(i,a))[p_j, t_b] - logits(x)[p_j, t_b], fp32 [L,nA,L,nA] — the

@@ -8,13 +8,25 @@ chosen rows are gathered on the device and only ``[B, per_step, V]`` comes down.
 
   python tools/sample_throughput.py [--model 650M] [--length 510] [--chains 64] [--per-step 1 8] [--steps 16] [--rounds 5]
       [--out profiles/sampling_throughput.log]
+  python tools/sample_throughput.py --order confidence [--top-k K] [--top-p P] [--baseline-lib OTHER/libesmk.so]
+      [--out profiles/sampling_confidence.log]
 
 Same model, same process and the same number of steps for every side: every chain gets ``steps * per_step`` designable
 positions, so one sweep is ``steps`` steps of ``chains * per_step`` draws.  One warm-up of each side per shape, then --rounds
 timed rounds alternating the sides, each ending in a device synchronise; medians and the spread.  The sides draw from the same
 distributions with different random numbers: the sequences differ, the work per step does not.
+
+With ``--order`` the tool times ``model.inpaint`` instead: every chain gets ``steps * per_step`` <mask> positions, so filling them
+is ``steps`` steps, and the sides are ``order="random"`` (one masked copy per chain and step, head on the drawn rows) and the
+given order (head, draw and score on ALL remaining <mask> rows of every step, ``esmk_op_select_rows`` choosing what to commit);
+``--top-k`` / ``--top-p`` apply to every side.  ``--baseline-lib`` names another build of libesmk.so (the parent commit's): a
+second model is created under it, and ``order="random"`` (without a filter: an older build has none) is timed with that library
+as a further side of the same alternating rounds, the library swapped in around each of its calls.
 """
 import argparse
+import contextlib
+import ctypes
+import gc
 import os
 import statistics
 import sys
@@ -52,6 +64,98 @@ def host_loop(model, toks, order, per_step, allowed_idx, gen, device_gather):
     return state
 
 
+def load_library(path):
+    """Another build of libesmk.so under the signatures of esm_amd/_native.py (an older build lacks the newest entries)."""
+    from esm_amd import _native as N
+
+    lib = ctypes.CDLL(path)
+    for name, (res, argtypes) in N.SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, argtypes
+    return lib
+
+
+@contextlib.contextmanager
+def library(lib):
+    """Every engine call inside goes to ``lib`` (esm_amd looks ``_native.lib`` up at call time)."""
+    from esm_amd import _native as N
+
+    mine, N.lib = N.lib, lib
+    try:
+        yield
+    finally:
+        N.lib = mine
+
+
+def make_model(L, E, H):
+    with skip_param_init():
+        model = esm.ESM2(L, E, H).eval()
+    model.load_state_dict(synth_esm2_state_dict(L, E, H, seed=0))
+    return model.cuda()
+
+
+def inpaint_rounds(args, name, dims):
+    """``--order``: inpaint with the given order against the random order, of this library and of ``--baseline-lib``."""
+    L, E, H = dims
+    model = make_model(L, E, H)
+    toks = synth_tokens(args.chains, args.length, seed=1)
+    B, T = toks.shape
+    kw = dict(top_k=args.top_k, top_p=args.top_p, seed=7)
+    lines = ["%s (L %d, E %d, H %d) on %s; inpaint, %d chains, T = %d, %d steps per round, top_k %d, top_p %g; %d rounds after one "
+             "warm-up, medians [min .. max]" % (name, L, E, H, torch.cuda.get_device_name(0), B, T, args.steps, args.top_k,
+                                                  args.top_p, args.rounds)]
+    base = base_model = None
+    if args.baseline_lib:
+        base = load_library(args.baseline_lib)
+        with library(base):
+            base_model = make_model(L, E, H)
+            lines.append("baseline library: %s" % base.esmk_version().decode())
+        from esm_amd import _native as N
+
+        lines.append("this library:     %s" % N.lib.esmk_version().decode())
+    with torch.no_grad():
+        for k in args.per_step:
+            g = torch.Generator().manual_seed(k)
+            start = toks.clone()
+            for b in range(B):
+                start[b, 1 + torch.randperm(args.length, generator=g)[: args.steps * k]] = model.mask_idx
+            start = start.cuda()
+
+            def baseline():
+                with library(base):
+                    return base_model.inpaint(start, per_step=k, seed=7)  # an older build has no filter: the plain draw
+
+            sides = {}
+            if base is not None:
+                sides["random, baseline library"] = baseline
+            sides["random"] = lambda: model.inpaint(start, per_step=k, **kw)
+            sides[args.order] = lambda: model.inpaint(start, per_step=k, order=args.order, **kw)
+            outs = {side: fn() for side, fn in sides.items()}  # warm-up
+            if base is not None and args.top_k == 0 and args.top_p >= 1.0:  # the same calls under both libraries
+                lines.append("per_step = %d: random order, baseline library and this one: %s" % (
+                    k, "the same tokens" if torch.equal(outs["random, baseline library"], outs["random"]) else "DIFFERENT tokens"))
+            times = {side: [] for side in sides}
+            for _ in range(args.rounds):
+                for side, fn in sides.items():
+                    times[side].append(timed(fn)[0])
+            med = {side: statistics.median(t) for side, t in times.items()}
+            rows = sum(B * k * (args.steps - s) for s in range(args.steps))
+            lines.append("per_step = %d (%d tokens committed per step; %s scores %d rows over the %d steps, random %d)" % (
+                k, B * k, args.order, rows, args.steps, B * k * args.steps))
+            for side in sides:
+                lines.append("  %-25s %8.1f ms [%.1f .. %.1f]  %7.2f steps/s  %8.0f tokens/s" % (
+                    side, 1e3 * med[side], 1e3 * min(times[side]), 1e3 * max(times[side]), args.steps / med[side],
+                    args.steps * B * k / med[side]))
+            for side in list(sides)[:-1]:
+                lines.append("  ratio %s / %s: %.3f x" % (args.order, side, med[args.order] / med[side]))
+    if base is not None:  # the baseline model's engine is freed by the library that made it
+        with library(base):
+            base_model = None
+            gc.collect()
+    return lines
+
+
 def timed(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -69,15 +173,21 @@ def main():
     ap.add_argument("--steps", type=int, default=16, help="steps per timed round (one sweep over steps * per_step positions)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--order", default=None, choices=("random", "confidence", "entropy"),
+                    help="time model.inpaint with this order against the random order instead of the Gibbs comparison")
+    ap.add_argument("--top-k", type=int, default=0)
+    ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--baseline-lib", default=None, help="another build of libesmk.so: its random order is a further side")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sample_throughput: needs the GPU (a CPU run measures nothing)")
     name = next(k for k in ESM2_DIMS if args.model in k)
     L, E, H = ESM2_DIMS[name]
-    with skip_param_init():
-        model = esm.ESM2(L, E, H).eval()
-    model.load_state_dict(synth_esm2_state_dict(L, E, H, seed=0))
-    model = model.cuda()
+    if args.order is not None:
+        return report(inpaint_rounds(args, name, (L, E, H)), args.out)
+    if args.baseline_lib:
+        raise SystemExit("sample_throughput: --baseline-lib goes with --order")
+    model = make_model(L, E, H)
     toks = synth_tokens(args.chains, args.length, seed=1).cuda()
     B, T = toks.shape
     mask = sampling.allowed_mask(model)
@@ -92,7 +202,8 @@ def main():
             gen = torch.Generator().manual_seed(7)
             sides = {"host loop": lambda: host_loop(model, toks, order, k, allowed_idx, gen, False),
                      "host loop, device gather": lambda: host_loop(model, toks, order, k, allowed_idx, gen, True),
-                     "gibbs_sample": lambda: model.gibbs_sample(toks, 1, per_step=k, positions=positions, seed=7)}
+                     "gibbs_sample": lambda: model.gibbs_sample(toks, 1, per_step=k, positions=positions, seed=7,
+                                                                top_k=args.top_k, top_p=args.top_p)}
             for fn in sides.values():
                 fn()  # warm-up
             times = {side: [] for side in sides}
@@ -107,10 +218,14 @@ def main():
                     args.steps * B * k / med[side]))
             for side in list(sides)[:2]:
                 lines.append("  ratio %s / gibbs_sample: %.2f x" % (side, med[side] / med["gibbs_sample"]))
+    report(lines, args.out)
+
+
+def report(lines, out):
     text = "\n".join(lines)
     print(text)
-    if args.out:
-        with open(os.path.join(ROOT, args.out) if not os.path.isabs(args.out) else args.out, "w") as fh:
+    if out:
+        with open(os.path.join(ROOT, out) if not os.path.isabs(out) else out, "w") as fh:
             fh.write(text + "\n")
 
 
