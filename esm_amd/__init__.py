@@ -12,7 +12,9 @@ from . import checkpoint as pretrained  # noqa: F401
 from .scoring import (masked_joint, masked_marginals, parse_variant, pseudo_log_likelihood, score_mutations,  # noqa: F401
                       score_variants, wt_marginals)
 from .msa_scoring import (msa_forward_rows, msa_masked_joint, msa_masked_marginals, msa_score_variants,  # noqa: F401
-                          msa_wt_marginals)
+                          msa_score_variants_ensemble, msa_wt_marginals)
+from .msa_select import (encode_msa, msa_mismatches, msa_neff, msa_neighbor_counts, msa_sequence_weights,  # noqa: F401
+                         subsample_indices, subsample_msa)
 
 from .sampling import gibbs_sample, inpaint  # noqa: F401
 from .jacobian import categorical_jacobian, jacobian_contacts  # noqa: F401

@@ -262,6 +262,12 @@ SIGNATURES = {
                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "esmk_op_select_rows": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    # MSA row selection: mismatch rows, neighbour counts, the greedy pick, race keys and their ranks (msa uint8 [N, ld])
+    "esmk_op_msa_mismatch_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "esmk_op_msa_neighbor_counts": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "esmk_op_msa_greedy_select": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "esmk_op_msa_race_keys": (c_int, [c_void_p, c_int, ctypes.c_uint64, c_int, c_void_p, c_void_p]),
+    "esmk_op_rank_keys": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     # the categorical Jacobian: substituted copies, the scatter of logit differences into J, centring, contact map, APC
     "esmk_op_substitute_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "esmk_op_jacobian_scatter": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

@@ -100,15 +100,15 @@ def read_fasta(path, keep_gaps=True, keep_insertions=True, to_upper=False):
 _A3M_INSERTIONS = str.maketrans("", "", "abcdefghijklmnopqrstuvwxyz.*")
 
 
-def read_msa(path, nseq):
-    """The first ``nseq`` records of an a3m file as ``[(description, aligned sequence)]``, with the insertions relative to the
-    query removed: lowercase letters, '.' and '*' are deleted, so every row has the query's number of columns (what
+def read_msa(path, nseq=None):
+    """The first ``nseq`` records of an a3m file (None: every record) as ``[(description, aligned sequence)]``, with the
+    insertions relative to the query removed: lowercase letters, '.' and '*' are deleted, so every row has the query's number of columns (what
     ``read_msa`` / ``remove_insertions`` of the reference's examples/variant-prediction/predict.py:21-42 return).  Only the
     first ``nseq`` records are parsed; text in front of the first header (a comment line) is dropped, as a FASTA parser does."""
     import itertools
 
     msa = []
-    if nseq <= 0:
+    if nseq is not None and nseq <= 0:
         return msa
     with open(path, "r") as fh:
         for _, head, body in _iter_records(itertools.dropwhile(lambda line: not line.startswith(">"), fh)):

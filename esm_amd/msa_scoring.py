@@ -245,3 +245,37 @@ def msa_score_variants(model, alphabet, msa, variants, strategy="masked-marginal
     var_off = torch.zeros((len(parsed) + 1,), dtype=torch.int64)
     var_off[1:] = torch.tensor([len(parts) for parts in parsed]).cumsum(0)
     return ops.score_rows(lp, wt, mt, var_off.to(device=dev, dtype=torch.int32)).tolist()
+
+
+@torch.no_grad()
+def msa_score_variants_ensemble(model, alphabet, msa, variants, num_seqs, n_subsamples=5, subsample="weighted", theta=0.2, seed=0,
+                                strategy="masked-marginals", offset_idx=0, sep=":", chunk=None):
+    """``msa_score_variants`` averaged over subsamples of a deep MSA, as the ESM-1v paper scores with the MSA Transformer:
+    ``(mean, per_subsample)``.  Subsample s = 0 .. n_subsamples - 1 is ``esm_amd.msa_select.subsample_msa(msa, num_seqs,
+    subsample, theta, seed, s)`` — "weighted" (sequence reweighting at ``theta``) or "uniform"; the query always stays row 0 —
+    and is scored by ``msa_score_variants`` with the remaining arguments.  The neighbour counts of the full MSA are computed
+    once.  ``per_subsample`` is the fp64 ``[n_subsamples, n_variants]`` matrix of those scores on the host; ``mean`` the list of
+    Python floats ``sum over s ascending of per_subsample[s] / n_subsamples`` in fp64."""
+    from . import msa_select
+
+    if subsample not in msa_select.STRATEGIES:
+        raise ValueError(f"unknown subsampling strategy {subsample!r} (one of {', '.join(msa_select.STRATEGIES)})")
+    if int(n_subsamples) != n_subsamples or int(n_subsamples) < 1:
+        raise ValueError(f"n_subsamples {n_subsamples!r} must be a positive integer")
+    n_subsamples = int(n_subsamples)
+    msa = list(msa)
+    if not msa:
+        raise ValueError("msa is empty")
+    variants = list(variants)
+    counts = None
+    if subsample == "weighted" and len(msa) > int(num_seqs):
+        counts = msa_select.msa_neighbor_counts(msa, theta)
+    per = torch.zeros((n_subsamples, len(variants)), dtype=torch.float64)
+    for s in range(n_subsamples):
+        rows = msa_select.subsample_msa(msa, num_seqs, subsample, theta, seed, s, counts=counts)
+        got = msa_score_variants(model, alphabet, rows, variants, strategy, offset_idx, sep, chunk)
+        per[s] = torch.tensor(got, dtype=torch.float64)
+    total = torch.zeros((len(variants),), dtype=torch.float64)
+    for s in range(n_subsamples):
+        total += per[s]
+    return (total / n_subsamples).tolist(), per

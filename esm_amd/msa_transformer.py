@@ -229,6 +229,14 @@ class MSATransformer(_EngineHost, nn.Module):
         return msa_scoring.msa_score_variants(self, alphabet, msa, variants, strategy=strategy, offset_idx=offset_idx, sep=sep,
                                               chunk=chunk)
 
+    def msa_score_variants_ensemble(self, alphabet, msa, variants, num_seqs, n_subsamples=5, subsample="weighted", theta=0.2,
+                                    seed=0, strategy="masked-marginals", offset_idx=0, sep=":", chunk=None):
+        from . import msa_scoring
+
+        return msa_scoring.msa_score_variants_ensemble(self, alphabet, msa, variants, num_seqs, n_subsamples=n_subsamples,
+                                                       subsample=subsample, theta=theta, seed=seed, strategy=strategy,
+                                                       offset_idx=offset_idx, sep=sep, chunk=chunk)
+
 
 def build_from_checkpoint(model_data):
     """``{"args": Namespace(arch="msa_transformer", ...), "model": state}`` -> (model, alphabet), following

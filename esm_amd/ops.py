@@ -698,6 +698,73 @@ def commit_tokens(tokens, slots, positions, token):
     return tokens
 
 
+# ---- MSA row selection (include/esmk.h: esmk_op_msa_mismatch_rows ... esmk_op_rank_keys) --------------------------------------
+def _msa_dims(msa, L):
+    """(N, L, ld) of a device byte matrix uint8 [N, ld] of which the first ``L`` columns count (None: all)."""
+    _req_cuda(msa)
+    assert msa.dtype == torch.uint8 and msa.dim() == 2
+    N, ld = msa.shape
+    L = ld if L is None else int(L)
+    if N < 1 or not 1 <= L <= ld:
+        raise ValueError(f"msa: need at least one row and 1 <= L <= {ld} columns, got N = {N}, L = {L}")
+    return N, L, ld
+
+
+def msa_mismatch_rows(msa, query, L=None):
+    """int32 [nq, N]: ``out[q, j]`` = the number of columns below ``L`` in which rows ``query[q]`` and j of ``msa`` uint8
+    [N, ld] differ.  ``query`` int32 [nq] on the device; an index outside [0, N) is clamped.  Every byte value is legal."""
+    N_, L, ld = _msa_dims(msa, L)
+    _req_cuda(query)
+    assert query.dtype == torch.int32 and query.dim() == 1 and query.numel() >= 1
+    nq = query.numel()
+    out = torch.empty((nq, N_), dtype=torch.int32, device=msa.device)
+    N.check(N.lib.esmk_op_msa_mismatch_rows(N.ptr(msa), N_, L, ld, N.ptr(query), nq, N.ptr(out), N.cur_stream()))
+    return out
+
+
+def msa_neighbor_counts(msa, max_mismatch, L=None):
+    """int32 [N]: ``count[i]`` = the number of rows j (i itself included) that differ from row i in at most ``max_mismatch`` of
+    the first ``L`` columns of ``msa`` uint8 [N, ld].  A negative ``max_mismatch`` gives zeros."""
+    N_, L, ld = _msa_dims(msa, L)
+    out = torch.empty((N_,), dtype=torch.int32, device=msa.device)
+    N.check(N.lib.esmk_op_msa_neighbor_counts(N.ptr(msa), N_, L, ld, int(max_mismatch), N.ptr(out), N.cur_stream()))
+    return out
+
+
+def msa_greedy_select(msa, num, first=0, mode=0, L=None):
+    """int32 [num]: the greedy row pick of include/esmk.h in pick order: ``sel[0] = first``, then the not-yet-selected row with
+    the largest (``mode`` 0) or smallest (``mode`` 1) integer sum of mismatches to the rows picked so far, ties to the lowest
+    row.  All steps run on the device; the host reads nothing in between."""
+    N_, L, ld = _msa_dims(msa, L)
+    work = torch.empty((N_,), dtype=torch.int32, device=msa.device)
+    sel = torch.empty((max(int(num), 1),), dtype=torch.int32, device=msa.device)
+    N.check(N.lib.esmk_op_msa_greedy_select(N.ptr(msa), N_, L, ld, int(first), int(num), int(mode), N.ptr(work), N.ptr(sel),
+                                            N.cur_stream()))
+    return sel
+
+
+def msa_race_keys(n, seed=0, subsample=0, counts=None, device=None):
+    """fp64 [n]: ``key_i = -log(u_i) * counts[i]``, u_i the 24-bit uniform of Philox counter (subsample, 0, 2, i) under the key
+    ``seed``; ``counts`` int32 [n] on the device or None (all ones).  u_i == 0 or a count <= 0 gives +inf."""
+    if counts is not None:
+        _req_cuda(counts)
+        assert counts.dtype == torch.int32 and counts.dim() == 1 and counts.numel() == int(n)
+        device = counts.device
+    key = torch.empty((int(n),), dtype=torch.float64, device=device if device is not None else "cuda")
+    N.check(N.lib.esmk_op_msa_race_keys(N.ptr(counts), int(n), _seed64(seed), int(subsample), N.ptr(key), N.cur_stream()))
+    return key
+
+
+def rank_keys(key):
+    """int32 [n]: ``rank[i]`` = the number of keys that come before key i in ascending order (equal keys: the lower index first;
+    NaN after everything): a permutation of 0 .. n - 1.  ``key`` fp64 [n] on the device."""
+    _req_cuda(key)
+    assert key.dtype == torch.float64 and key.dim() == 1 and key.numel() >= 1
+    rank = torch.empty((key.numel(),), dtype=torch.int32, device=key.device)
+    N.check(N.lib.esmk_op_rank_keys(N.ptr(key), N.ptr(rank), key.numel(), N.cur_stream()))
+    return rank
+
+
 # ---- the categorical Jacobian (include/esmk.h: esmk_op_substitute_rows ... esmk_op_apc) ------------------------------------
 def substitute_rows(tokens, positions, tok, src_rows=None, vocab=33):
     """[n,T] int64: row i = tokens[src_rows[i]] (row 0 of [B,T] / the only row of [T] when ``src_rows`` is None) with position

@@ -760,6 +760,38 @@ int esmk_op_select_rows(const float* score_dev, const int32_t* row_off_dev, cons
                         const int32_t* rest_off_dev, int32_t* sel_out_dev, int32_t* rest_out_dev, int n_chain, int n, int n_sel,
                         int n_rest, void* stream);
 
+/* Choosing the rows of an MSA on the device (esm_amd/msa_select.py; csrc/msa_select.hip).  An MSA is msa uint8 [N,ld], row-major:
+ * L <= ld columns count, bytes in [L,ld) of a row are never counted whatever they hold, and every byte value 0 .. 255 is legal
+ * (a gap is a byte like any other).  mism(i,j) = #{c < L : msa[i,c] != msa[j,c]}.  Integer arithmetic and comparison logic
+ * only, so every result is exact and none depends on the launch geometry; the race keys are one fp64 product each.
+ * esmk_op_msa_mismatch_rows: out int32 [nq,N], out[q,j] = mism(query[q], j); query int32 [nq] is device data, an index outside
+ *   [0,N) is clamped.  One wavefront per pair.
+ * esmk_op_msa_neighbor_counts: count_out int32 [N], count[i] = #{j in [0,N) : mism(i,j) <= max_mismatch}, j = i included; a
+ *   negative max_mismatch gives all zeros.  The N^2 L hot path: 64 x 64 tiles of row pairs, the columns staged through LDS in
+ *   chunks of 128, 4 x 4 pairs per lane in registers, four columns per dword compare, the tail past L masked.  Every pair is
+ *   computed from both sides; count_out is zeroed on the stream and receives one integer atomic add per row and workgroup.
+ * esmk_op_msa_greedy_select: sel_out int32 [num]: sel[0] = first; for k = 1 .. num-1, S_k[j] = sum over t < k of mism(sel[t], j)
+ *   and sel[k] = the not-yet-selected j with the largest (mode 0) or smallest (mode 1) S_k[j], ties to the lowest j.  Integer
+ *   sums; the steps run back to back on the stream, step k reads sel[k-1] on the device and the host reads nothing in
+ *   between.  sum_work int32 [N] is the caller's scratch.
+ * esmk_op_msa_race_keys: key_out fp64 [N], key_i = -log(u_i) * count_i in fp64, u_i = (word0 >> 8) * 2^-24 with word0 the first
+ *   Philox4x32-10 word under the key seed at counter (subsample, 0, 2, i): purpose 2, next to the sampler's 0 and 1.  count
+ *   int32 [N] or NULL (all ones); u_i == 0 or count_i <= 0 gives +inf.  The rows of the smallest keys are a draw without
+ *   replacement with weights 1 / count.
+ * esmk_op_rank_keys: rank_out int32 [N], rank_i = #{j : key_j < key_i, or key_j == key_i and j < i}; NaN ranks after
+ *   everything, among NaNs the lower index first: a permutation of 0 .. N-1.  N^2 comparisons, no sort.
+ * Refused before any HIP call: null pointers (count_dev may be NULL), N, L or nq <= 0, ld < L, N*ld >= 2^31, L > 65535, nq*N >=
+ * 2^31, num outside 1 .. N, first outside [0,N), num*L >= 2^31, mode outside 0 .. 1, a negative subsample, and for the last two
+ * entries N > 2^24. */
+int esmk_op_msa_mismatch_rows(const uint8_t* msa_dev, int N, int L, int ld, const int32_t* query_dev, int nq, int32_t* out_dev,
+                              void* stream);
+int esmk_op_msa_neighbor_counts(const uint8_t* msa_dev, int N, int L, int ld, int max_mismatch, int32_t* count_out_dev,
+                                void* stream);
+int esmk_op_msa_greedy_select(const uint8_t* msa_dev, int N, int L, int ld, int first, int num, int mode, int32_t* sum_work_dev,
+                              int32_t* sel_out_dev, void* stream);
+int esmk_op_msa_race_keys(const int32_t* count_dev, int N, uint64_t seed, int subsample, double* key_out_dev, void* stream);
+int esmk_op_rank_keys(const double* key_dev, int32_t* rank_out_dev, int N, void* stream);
+
 /* The categorical Jacobian of one protein (esm_amd/jacobian.py): every candidate token t_a of a list of nA <= 32 put at every
  * residue position p_i of ONE sequence, J[i,a,j,b] = logits(copy(i,a))[p_j, t_b] - logits(x)[p_j, t_b], fp32 [L,nA,L,nA] — the
  * fp32 difference of two fp32 logits.  A chunk of copies is esmk_op_substitute_rows -> esmk_forward_rows (the L residue rows of
