@@ -5,10 +5,12 @@ to cover fp32 accumulation order and the final rounding of the output).
 
 Together with this file, every HIP kernel of the library has a single-op test: test_attention_variants_gpu.py,
 test_attention_biaskv_gpu.py and test_attention_packed_ops_gpu.py (attention forms), test_gemm_forms_gpu.py (generalised
-GEMM forms, MSA row softmax), test_contacts_kernels_gpu.py (fused and packed contacts), test_ln_fold_gpu.py and
+GEMM forms, MSA row softmax), test_dense_gemm_gpu.py (the dense GEMM kernels and their plain epilogues, per element against
+fp64, with the planned kernel asserted), test_contacts_kernels_gpu.py (fused and packed contacts), test_ln_fold_gpu.py and
 test_ln_fold_ops_gpu.py (LayerNorm fold: at model shapes, and at the edges in both dtypes), test_gelu_epilogue_gpu.py (the GELU
 of every launcher on exact pre-activations), test_precision_ops_gpu.py (precision modes), test_scoring_ops_gpu.py and test_scoring_variant_ops_gpu.py (scoring)
 and test_frontend_ops_gpu.py (token statistics, embeddings, positions, position tables, row gather)."""
+import ctypes
 import math
 
 import pytest
@@ -17,6 +19,24 @@ import torch
 pytestmark = pytest.mark.gpu
 
 DT = [torch.float16, torch.bfloat16]
+
+
+def _planned(M, N, K, epi, flags=0):
+    """the kernel launch_gemm picks for a dense call (esmk_debug_gemm_plan; flags 1 = force_generic, 2 = force_old)"""
+    from esm_amd import _native as nat
+
+    out = (ctypes.c_int32 * 4)()
+    nat.check(nat.lib.esmk_debug_gemm_plan(M, N, K, epi, flags, out))
+    return out[0]
+
+
+@pytest.fixture
+def persistent_impl():
+    """impl -> esmk_debug_gemm_impl(impl, 0); the automatic choice is restored afterwards"""
+    from esm_amd import _native as nat
+
+    yield lambda impl: nat.check(nat.lib.esmk_debug_gemm_impl(impl, 0))
+    nat.check(nat.lib.esmk_debug_gemm_impl(0, 0))
 
 
 def _eps(dt):
@@ -54,14 +74,19 @@ def test_layernorm(ops, E, rows, dt):
         (1024, 1280, 1280, False),
         (512, 1280, 5120, False),
         (64, 128, 64, False),
-        (77, 33, 320, False),     # K % 64 != 0 and N % 4 != 0 -> generic kernel
+        (77, 33, 320, False),     # N % 8 != 0 -> generic kernel
         (130, 200, 96, True),
         (256, 256, 128, True),
     ],
 )
 @pytest.mark.parametrize("dt", DT)
 def test_linear_epilogues(ops, M, N, K, generic, dt):
+    """The automatic choice (gemm9.hip; the generic kernel where N % 8 != 0) and the generic kernel on request, against an
+    fp32 matmul under one global tolerance; test_dense_gemm_gpu.py holds every element to an fp64 bound."""
     from esm_amd import _native as nat
+
+    for epi in range(nat.EPI_RESID_F32 + 1):
+        assert _planned(M, N, K, epi, int(generic)) == (64 if generic or N % 8 else 9)
 
     g = torch.Generator(device="cuda").manual_seed(2)
     a = torch.randn(M, K, device="cuda", generator=g).to(dt)
@@ -99,11 +124,12 @@ def test_linear_epilogues(ops, M, N, K, generic, dt):
     ],
 )
 @pytest.mark.parametrize("dt", DT)
-def test_persistent_gemm_bit_exact_vs_tile_kernel(ops, M, N, K, dt):
-    """gemm8.hip (persistent, ping-pong) accumulates the K products in the same order as the
-    one-tile-per-workgroup kernel of gemm.hip, so without a bias the two must agree BIT FOR BIT
-    (with a bias gemm8 starts from acc = bias instead of adding it last: compared with a tolerance);
-    repeated launches with different tile orders catch LDS-DMA races."""
+def test_persistent_gemm_bit_exact_vs_tile_kernel(ops, persistent_impl, M, N, K, dt):
+    """The persistent kernels — gemm9.hip under the automatic choice, which every dense ops.linear call takes, and
+    gemm8.hip under impl 8 (what ESMK_GEMM_IMPL=8 ships) — accumulate the K products in the same order as the
+    one-tile-per-workgroup kernel of gemm.hip, so without a bias they must agree with it BIT FOR BIT (with a bias they
+    start from acc = bias instead of adding it last: compared with a tolerance); repeated launches with different tile
+    orders catch LDS-DMA races.  The planned kernel is asserted, so neither pass silently runs the other's kernel."""
     from esm_amd import _native as nat
 
     g = torch.Generator(device="cuda").manual_seed(7)
@@ -112,47 +138,56 @@ def test_persistent_gemm_bit_exact_vs_tile_kernel(ops, M, N, K, dt):
     bias = torch.randn(N, device="cuda", generator=g)
     ref = a.float() @ w.float().t() + bias
     tol = 3e-5 * math.sqrt(K) * 4 + 1e-5
-    for epi in (nat.EPI_STORE_F32, nat.EPI_GELU_T, nat.EPI_STORE_T, nat.EPI_GELU_F32):
-        old = ops.linear(a, w, None, epi, force_old=True)
-        for rep in range(3):
-            new = ops.linear(a, w, None, epi, panel_c=(0, 4, 1)[rep])
-            assert torch.equal(new, old), (epi, rep, (new.float() - old.float()).abs().max().item())
-    new = ops.linear(a, w, bias, nat.EPI_STORE_F32)
-    assert (new - ref).abs().max().item() < tol
-    new = ops.linear(a, w, bias, nat.EPI_GELU_T)
-    assert (new.float() - _gelu(ref)).abs().max().item() < tol + _eps(dt) * ref.abs().max().item()
     resid = torch.randn(M, N, device="cuda", generator=g)
-    acc_old, acc_new = resid.clone(), resid.clone()
-    ops.linear(a, w, None, nat.EPI_RESID_F32, out=acc_old, force_old=True)
-    ops.linear(a, w, None, nat.EPI_RESID_F32, out=acc_new)
-    assert torch.equal(acc_new, acc_old)
-    acc_new = resid.clone()
-    ops.linear(a, w, bias, nat.EPI_RESID_F32, out=acc_new)
-    assert (acc_new - (resid + ref)).abs().max().item() < tol
+    for impl, kernel in ((0, 9), (8, 8)):
+        persistent_impl(impl)
+        for epi in (nat.EPI_STORE_F32, nat.EPI_GELU_T, nat.EPI_STORE_T, nat.EPI_GELU_F32):
+            assert _planned(M, N, K, epi) == kernel and _planned(M, N, K, epi, 2) == 256
+            old = ops.linear(a, w, None, epi, force_old=True)
+            for rep in range(3):
+                new = ops.linear(a, w, None, epi, panel_c=(0, 4, 1)[rep])
+                assert torch.equal(new, old), (kernel, epi, rep, (new.float() - old.float()).abs().max().item())
+        new = ops.linear(a, w, bias, nat.EPI_STORE_F32)
+        assert (new - ref).abs().max().item() < tol
+        new = ops.linear(a, w, bias, nat.EPI_GELU_T)
+        assert (new.float() - _gelu(ref)).abs().max().item() < tol + _eps(dt) * ref.abs().max().item()
+        assert _planned(M, N, K, nat.EPI_RESID_F32) == kernel and _planned(M, N, K, nat.EPI_RESID_F32, 2) == 256
+        acc_old, acc_new = resid.clone(), resid.clone()
+        ops.linear(a, w, None, nat.EPI_RESID_F32, out=acc_old, force_old=True)
+        ops.linear(a, w, None, nat.EPI_RESID_F32, out=acc_new)
+        assert torch.equal(acc_new, acc_old), kernel
+        acc_new = resid.clone()
+        ops.linear(a, w, bias, nat.EPI_RESID_F32, out=acc_new)
+        assert (acc_new - (resid + ref)).abs().max().item() < tol
 
 
 @pytest.mark.parametrize("M,N,K", [(4096, 1280, 1280), (4096, 1280, 5120), (1100, 2560, 1280), (4224, 5120, 320), (100, 264, 64)])
 @pytest.mark.parametrize("dt", DT)
-def test_half_height_tiles_bit_exact(ops, M, N, K, dt):
-    """gemm8_kernel<..., HM>: 128 x 256 tiles for shapes that leave most CUs idle with 256-row tiles.  Every output
-    element sees the same MFMA sequence over K as in the full-height kernel, so the results are bit-identical —
-    whichever tile height the batch size selects (small-batch forwards must not differ from large-batch ones)."""
+def test_half_height_tiles_bit_exact(ops, persistent_impl, M, N, K, dt):
+    """gemm9_kernel<..., HM> (the automatic choice) and gemm8_kernel<..., HM> (impl 8): 128 x 256 tiles for shapes that
+    leave most CUs idle with 256-row tiles.  Every output element sees the same MFMA sequence over K as in the
+    full-height kernel, so the results are bit-identical — whichever tile height the batch size selects (small-batch
+    forwards must not differ from large-batch ones).  The planned kernel is asserted for either pass."""
     from esm_amd import _native as nat
 
     g = torch.Generator(device="cuda").manual_seed(13)
     a = torch.randn(M, K, device="cuda", generator=g).to(dt)
     w = (torch.randn(N, K, device="cuda", generator=g) / math.sqrt(K)).to(dt)
     bias = torch.randn(N, device="cuda", generator=g)
-    for epi in (nat.EPI_STORE_F32, nat.EPI_GELU_T, nat.EPI_STORE_T, nat.EPI_GELU_F32):
-        full = ops.linear(a, w, bias, epi, half_m=-1)
-        for rep in range(2):
-            half = ops.linear(a, w, bias, epi, half_m=1, panel_c=(0, 2)[rep])
-            assert torch.equal(half, full), (epi, rep, (half.float() - full.float()).abs().max().item())
     resid = torch.randn(M, N, device="cuda", generator=g)
-    x_full, x_half = resid.clone(), resid.clone()
-    ops.linear(a, w, bias, nat.EPI_RESID_F32, out=x_full, half_m=-1)
-    ops.linear(a, w, bias, nat.EPI_RESID_F32, out=x_half, half_m=1)
-    assert torch.equal(x_half, x_full)
+    for impl, kernel in ((0, 9), (8, 8)):
+        persistent_impl(impl)
+        for epi in (nat.EPI_STORE_F32, nat.EPI_GELU_T, nat.EPI_STORE_T, nat.EPI_GELU_F32):
+            assert _planned(M, N, K, epi) == kernel
+            full = ops.linear(a, w, bias, epi, half_m=-1)
+            for rep in range(2):
+                half = ops.linear(a, w, bias, epi, half_m=1, panel_c=(0, 2)[rep])
+                assert torch.equal(half, full), (kernel, epi, rep, (half.float() - full.float()).abs().max().item())
+        assert _planned(M, N, K, nat.EPI_RESID_F32) == kernel
+        x_full, x_half = resid.clone(), resid.clone()
+        ops.linear(a, w, bias, nat.EPI_RESID_F32, out=x_full, half_m=-1)
+        ops.linear(a, w, bias, nat.EPI_RESID_F32, out=x_half, half_m=1)
+        assert torch.equal(x_half, x_full), kernel
 
 
 def test_small_batch_forward_equals_large_batch_rows():
