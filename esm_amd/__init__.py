@@ -19,4 +19,16 @@ from .msa_select import (encode_msa, msa_mismatches, msa_neff, msa_neighbor_coun
 from .sampling import gibbs_sample, inpaint  # noqa: F401
 from .jacobian import categorical_jacobian, jacobian_contacts  # noqa: F401
 
+
+def __getattr__(name):
+    # esm_amd.design is the design module, which is callable as its own main function (``esm_amd.design(model, tokens, ...)``
+    # is ``esm_amd.design.design``); loaded on first use, so that ``python -m esm_amd.design`` runs a module not yet imported
+    if name in ("design", "design_energy", "contacts_from_pdb"):
+        import importlib
+
+        module = importlib.import_module(".design", __name__)
+        return module if name == "design" else getattr(module, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 __version__ = "0.1.0"

@@ -98,6 +98,11 @@ SIGNATURES = {
     "esmk_rows_workspace_bytes": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "esmk_forward_rows": (
         c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # design: selected log-prob rows and contact maps with the head-group count of B = 1 in one forward
+    "esmk_rows_contacts_workspace_bytes": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
+    "esmk_forward_rows_contacts": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "esmk_debug_contact_groups": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_int32)]),
     # token-packed batch + row selection (mixed-length libraries of masked copies); the segment table is a host array
     "esmk_packed_rows_workspace_bytes": (
         c_int, [c_void_p, POINTER(c_int32), c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
@@ -262,6 +267,16 @@ SIGNATURES = {
                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "esmk_op_select_rows": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    # Metropolis-Hastings design: the proposal, the contact term of the energy, the acceptance, the LM proposal's correction
+    "esmk_op_propose_mutations": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint64, c_int, ctypes.c_uint64, c_int, c_void_p,
+                c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "esmk_op_contact_energy": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "esmk_op_mh_accept": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double,
+                c_double, ctypes.c_uint64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                c_void_p]),
+    "esmk_op_hastings_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p]),
     # MSA row selection: mismatch rows, neighbour counts, the greedy pick, race keys and their ranks (msa uint8 [N, ld])
     "esmk_op_msa_mismatch_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "esmk_op_msa_neighbor_counts": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

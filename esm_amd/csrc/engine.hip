@@ -126,8 +126,9 @@ inline size_t packed_items_bound(int n_seg, int rows) { return (size_t)rows / 12
 
 // ct: token-packed batch with ESMK_OUT_CONTACTS (flags must then hold it): per-segment contact scratch
 // packed_maps: token-packed batch with attention maps: lse and the 64-bit map offsets; nothing that grows with Tmax^2
+// ct_G > 0: the head-group count of the fused contact accumulators is given (esmk_forward_rows_contacts pins it to B = 1's)
 Workspace plan_workspace(const esmk_model* m, int B, int T, uint32_t flags, int packed_segs = 0,
-                         const CtPackedPlan* ct = nullptr, bool packed_maps = false) {
+                         const CtPackedPlan* ct = nullptr, bool packed_maps = false, int ct_G = 0) {
     Workspace w{};
     const size_t os = op_size(m->cfg.operand_dtype);
     const size_t N = (size_t)B * T, E = m->E, F = m->F, EA = m->EA, Kp = m->Kp;
@@ -181,7 +182,8 @@ Workspace plan_workspace(const esmk_model* m, int B, int T, uint32_t flags, int 
         w.ct_colp = c.take((size_t)ct->colp * 4);
         w.ct_wt = c.take((size_t)packed_segs * C * 4);
     } else {
-        w.ct_acc = c.take(fused_ct ? (size_t)contacts_head_groups((long long)B * nQ * nQ, m->H, head_slots(m)) * B * T * T * 4 : 0);
+        const int G = ct_G > 0 ? ct_G : contacts_head_groups((long long)B * nQ * nQ, m->H, head_slots(m));
+        w.ct_acc = c.take(fused_ct ? (size_t)G * B * T * T * 4 : 0);
         w.ct_row = c.take(fused_ct ? (size_t)B * C * T * 4 : 0);
         w.ct_col = c.take(fused_ct ? (size_t)B * C * T * 4 : 0);
         w.ct_rowp = c.take(fused_ct ? (size_t)B * ((T + 127) / 128) * m->H * T * 4 : 0);
@@ -201,9 +203,11 @@ Workspace plan_workspace(const esmk_model* m, int B, int T, uint32_t flags, int 
 // scratch of the head and the selected logits.  No pad rows: every GEMM kernel clamps its A-row reads to row M - 1 and stores
 // rows below M only, so M = n_sel is launched as it is.
 // packed_segs > 0 (esmk_forward_packed_rows): the token-packed forward's workspace (B = 1, T = rows) in front.
-size_t plan_rows(const esmk_model* m, int B, int T, int n_sel, RowSel* rs, int packed_segs = 0) {
+// flags, ct_G (esmk_forward_rows_contacts): the forward in front also accumulates contact maps, with ct_G head groups.
+size_t plan_rows(const esmk_model* m, int B, int T, int n_sel, RowSel* rs, int packed_segs = 0,
+                 uint32_t flags = ESMK_OUT_LOGITS, int ct_G = 0) {
     Carve c;
-    c.take(plan_workspace(m, B, T, ESMK_OUT_LOGITS, packed_segs).total);
+    c.take(plan_workspace(m, B, T, flags, packed_segs, nullptr, false, ct_G).total);
     const size_t n = (size_t)n_sel;
     rs->x = c.take(n * m->E * 4);
     rs->h = c.take(n * std::max(m->Kp, m->EA) * op_size(m->cfg.operand_dtype));
@@ -248,6 +252,8 @@ __global__ void fill_f32_kernel(float* p, float v, size_t n) {
 }
 
 namespace esmk_host {
+int g_rows_contacts_own_groups = 0;
+
 int ensure_rope(esmk_model* m, int T, hipStream_t st) {
     if (m->inv_freq.empty()) return fail("esmk_set_rope_inv_freq was not called");
     if (T <= m->rope_cap) return 0;
@@ -494,7 +500,8 @@ struct ForwardCall {
     size_t workspace_bytes = 0;
     void* stream = nullptr;
     const PackedCtx* pc = nullptr;  // token-packed batch: B = 1, T = rows
-    const RowSel* rs = nullptr;     // esmk_forward_rows, esmk_forward_packed_rows
+    const RowSel* rs = nullptr;     // esmk_forward_rows, esmk_forward_packed_rows, esmk_forward_rows_contacts
+    int ct_G = 0;                   // esmk_forward_rows_contacts: the pinned head-group count of the fused contact head (0: from B)
 };
 
 // What the stages share: the call, the launch helpers, the workspace and the form the model runs in
@@ -607,7 +614,7 @@ int check_forward(const ForwardCall& c, Workspace* w) {
     if (want_contacts && !c.contacts) return fail(who + ": contacts buffer missing");
     for (int i = 0; i < c.n_repr; ++i)
         if (c.repr_layers[i] < 0 || c.repr_layers[i] > m->L || !c.repr_out[i]) return fail(who + ": bad repr layer request");
-    *w = plan_workspace(m, c.B, c.T, c.flags, c.pc ? c.pc->n_seg : 0, c.pc ? c.pc->ct : nullptr, c.pc && c.pc->maps);
+    *w = plan_workspace(m, c.B, c.T, c.flags, c.pc ? c.pc->n_seg : 0, c.pc ? c.pc->ct : nullptr, c.pc && c.pc->maps, c.ct_G);
     if (c.workspace_bytes < w->total) return fail(who + ": workspace too small");
     return 0;
 }
@@ -819,7 +826,7 @@ int attention_stage(const Fwd& f, const LayerOff& o, int l) {
         ESMK_TRY(launch_contacts_fused_layer(f.q, f.k, f.lse, f.key_bias, f.c.tokens, ct_w, f.at<float>(f.w.ct_acc),
                                              f.at<float>(f.w.ct_row), f.at<float>(f.w.ct_col), f.at<float>(f.w.ct_rowp),
                                              f.at<float>(f.w.ct_colp), B, H, T, L * H, l, head_slots(m), cfg.pad_idx, cfg.eos_idx,
-                                             cfg.prepend_bos, cfg.append_eos, op, st));
+                                             cfg.prepend_bos, cfg.append_eos, op, st, f.c.ct_G));
     }
     if (f.packed_maps) {  // multihead_attention.py:396-403 per segment: [L, H, len, len] blocks, no padding anywhere
         ProfScope ps(f.m, st, PC_ATTN_PROBS, 2.0 * pc->sum_len2 * E, 2 * NE * os + (pc->maps_lowp ? (double)os : 4.0) * pc->sum_len2 * H);
@@ -895,6 +902,7 @@ int head_stage(const Fwd& f) {
     int rows = f.N;
     float *x = f.x, *g32 = f.g32;
     void* h = f.h;
+    if (rs && rs->n_sel == 0) return 0;  // esmk_forward_rows_contacts with no rows selected: no head runs
     if (rs) {
         rows = rs->n_sel;
         x = f.at<float>(rs->x);
@@ -965,7 +973,8 @@ int contacts_final(const Fwd& f) {
         ProfScope ps(f.m, st, PC_CONTACTS, 0, 4.0 * B * ((double)T * T * 2 + 3.0 * L * H * T));
         ESMK_TRY(launch_contacts_fused_final(f.at<float>(f.w.ct_acc), f.at<float>(f.w.ct_row), f.at<float>(f.w.ct_col),
                                              f.at<float>(f.w.ct_wt), f.c.tokens, ct_w, ct_b, (float*)f.c.contacts, B, H, L * H, T,
-                                             head_slots(m), cfg.pad_idx, cfg.eos_idx, cfg.prepend_bos, cfg.append_eos, st));
+                                             head_slots(m), cfg.pad_idx, cfg.eos_idx, cfg.prepend_bos, cfg.append_eos, st,
+                                             f.c.ct_G));
     } else if (f.want_contacts && f.S_ct > 0) {
         // (an empty sequence has an empty [B,0,0] contact map: nothing to compute)
         ProfScope ps(f.m, st, PC_CONTACTS, 0, 2.0 * 4 * B * (double)L * H * T * T);
@@ -1347,6 +1356,71 @@ int esmk_forward_rows(esmk_model* m, const void* packed_dev, const int64_t* toke
     c.workspace = workspace_dev, c.workspace_bytes = workspace_bytes, c.stream = stream;
     c.rs = &rs;
     return forward_impl(c);
+}
+
+// ---- design toward a target contact map: selected log-prob rows and pinned contact maps in one forward ----
+// The head-group count of B = 1, whatever B is (include/esmk.h: the pin); 0 = the batch's own under the measurement switch
+static int pinned_contact_groups(const esmk_model* m, int T) {
+    if (esmk_host::g_rows_contacts_own_groups) return 0;
+    const long long nQ = (T + 127) / 128;
+    return contacts_head_groups(nQ * nQ, m->H, head_slots(m));
+}
+
+static int check_rows_contacts(const char* who, const esmk_model* m, int B, int T, int n_sel) {
+    const std::string w(who);
+    if (m->is_msa) return fail(w + ": MSA handle (the MSA Transformer has no row-selected forward with contact maps)");
+    if (B <= 0 || T <= 0) return fail(w + ": B and T must be positive");
+    if ((long long)B * T > ESMK_MAX_ROWS) return fail(w + ": B*T exceeds 2^24 rows");
+    if (n_sel < 0) return fail(w + ": n_sel must not be negative");
+    if (n_sel > ESMK_MAX_ROWS) return fail(w + ": n_sel exceeds 2^24 rows");
+    if (n_sel > 0 && m->V > 64) return fail(w + ": vocabulary above 64 entries (the log-softmax holds one entry per lane)");
+    if (T - (m->cfg.prepend_bos ? 1 : 0) - (m->cfg.append_eos ? 1 : 0) <= 0)
+        return fail(w + ": no residue between <cls> and <eos>: the contact map is empty");
+    return 0;
+}
+
+int esmk_rows_contacts_workspace_bytes(const esmk_model* m, int B, int T, int n_sel, size_t* bytes, size_t* logits_offset) {
+    if (!m || !bytes) return fail("esmk_rows_contacts_workspace_bytes: null argument");
+    if (check_rows_contacts("esmk_rows_contacts_workspace_bytes", m, B, T, n_sel)) return 1;
+    RowSel rs;
+    *bytes = plan_rows(m, B, T, n_sel, &rs, 0, ESMK_OUT_CONTACTS, pinned_contact_groups(m, T));
+    if (logits_offset) *logits_offset = rs.logits;
+    return 0;
+}
+
+int esmk_forward_rows_contacts(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev, int B, int T,
+                               const int32_t* sel_rows_dev, int n_sel, float* logprobs_out_dev, float* contacts_out_dev,
+                               void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!m || !packed_dev || !tokens_dev || !contacts_out_dev || !workspace_dev || (n_sel > 0 && (!sel_rows_dev || !logprobs_out_dev)))
+        return fail("esmk_forward_rows_contacts: null argument");
+    if (check_rows_contacts("esmk_forward_rows_contacts", m, B, T, n_sel)) return 1;
+    RowSel rs;
+    const int G = pinned_contact_groups(m, T);
+    if (workspace_bytes < plan_rows(m, B, T, n_sel, &rs, 0, ESMK_OUT_CONTACTS, G))
+        return fail("esmk_forward_rows_contacts: workspace too small");
+    if (!m->cfg.no_rope && m->inv_freq.empty()) return fail("esmk_forward_rows_contacts: esmk_set_rope_inv_freq was not called");
+    rs.sel_dev = sel_rows_dev;
+    rs.n_sel = n_sel;
+    rs.logprobs_out = logprobs_out_dev;
+    ForwardCall c;
+    c.who = "esmk_forward_rows_contacts";
+    c.m = m, c.packed = packed_dev, c.tokens = tokens_dev, c.B = B, c.T = T;
+    c.flags = ESMK_OUT_CONTACTS | (n_sel > 0 ? ESMK_OUT_LOGITS : 0);
+    c.logits = n_sel > 0 ? (char*)workspace_dev + rs.logits : nullptr;
+    c.contacts = contacts_out_dev;
+    c.workspace = workspace_dev, c.workspace_bytes = workspace_bytes, c.stream = stream;
+    c.rs = &rs;
+    c.ct_G = G;
+    return forward_impl(c);
+}
+
+int esmk_debug_contact_groups(const esmk_model* m, int B, int T, int pinned, int32_t* groups) {
+    if (!m || !groups) return fail("esmk_debug_contact_groups: null argument");
+    if (m->is_msa) return fail("esmk_debug_contact_groups: MSA handle (its contact head reads the row attention maps)");
+    if (B <= 0 || T <= 0) return fail("esmk_debug_contact_groups: B and T must be positive");
+    const long long nQ = (T + 127) / 128;
+    *groups = contacts_head_groups((pinned ? 1 : (long long)B) * nQ * nQ, m->H, head_slots(m));
+    return 0;
 }
 
 // ---- token-packed batches (no compute on padding) --------------------------------------

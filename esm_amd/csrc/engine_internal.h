@@ -178,6 +178,9 @@ constexpr float kLog2e = 1.4426950408889634f;
 // head width inside the engine: 128, or 64 slots (heads with head_dim < 64 are spread over them)
 inline int head_slots(const esmk_model* m) { return m->D == 128 ? 128 : 64; }
 
+// esmk_debug_set("rows_contacts_own_groups", 1): esmk_forward_rows_contacts takes the batch's own head-group count instead of
+// the pinned one — the measurement of what the pin costs (tools/design_throughput.py); process wide, off by default
+extern int g_rows_contacts_own_groups;
 // rotary tables for rows 0 .. T-1 (engine.hip)
 int ensure_rope(esmk_model* m, int T, hipStream_t st);
 // "unit" rotary tables (cos = 1, sin = 0) for models without RoPE (MSA Transformer, ESM-1b)

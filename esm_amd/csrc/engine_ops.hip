@@ -272,6 +272,10 @@ int esmk_op_linear_ln(const void* a_dev, const void* w_dev, const float* bias_de
 int esmk_debug_set(const char* key, double value) {
     if (!key) return fail("esmk_debug_set: null key");
     if (gemm_set_knob(key, value)) return 0;
+    if (strcmp(key, "rows_contacts_own_groups") == 0) {
+        g_rows_contacts_own_groups = value != 0.0;
+        return 0;
+    }
 #ifdef ESMK_EXPERIMENTS
     if (strcmp(key, "attn_stagger") == 0) {
         attention_set_stagger((int)value);
@@ -969,6 +973,66 @@ int esmk_op_commit_tokens(int64_t* tokens_dev, const int32_t* row_chain_slot_dev
     if (n <= 0 || B <= 0 || T <= 0) return fail("esmk_op_commit_tokens: n, B and T must be positive");
     if ((long long)B * T > ESMK_MAX_ROWS || n > ESMK_MAX_ROWS) return fail("esmk_op_commit_tokens: B*T or n exceeds 2^24 rows");
     ESMK_TRY(launch_commit_tokens(tokens_dev, row_chain_slot_dev, pos_dev, token_dev, n, B, T, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- Metropolis-Hastings design (design.hip): everything is refused here before any HIP call ---------------------------
+int esmk_op_propose_mutations(const int64_t* tokens_dev, const int32_t* slot_dev, const int32_t* pos_off_dev, const int32_t* pos_dev,
+                              const int32_t* chain_id_dev, uint64_t allowed_mask, int force_new, uint64_t seed, int step,
+                              int32_t* site_out_dev, int32_t* old_out_dev, int32_t* tok_out_dev, int n_chain, int B, int T, int total,
+                              int V, void* stream) {
+    if (!tokens_dev || !pos_off_dev || !pos_dev || !chain_id_dev || !site_out_dev || !old_out_dev || !tok_out_dev)
+        return fail("esmk_op_propose_mutations: null argument");
+    if (n_chain <= 0 || B <= 0 || T <= 0) return fail("esmk_op_propose_mutations: n_chain, B and T must be positive");
+    if (total < 0) return fail("esmk_op_propose_mutations: total must not be negative");
+    if ((long long)B * T > ESMK_MAX_ROWS || n_chain > ESMK_MAX_ROWS) return fail("esmk_op_propose_mutations: B*T or n_chain exceeds 2^24 rows");
+    if (V <= 0 || V > 64) return fail("esmk_op_propose_mutations: V must be in 1 .. 64 (the candidate set is a 64-bit mask)");
+    if (step < 0) return fail("esmk_op_propose_mutations: step must not be negative");
+    ESMK_TRY(launch_propose_mutations(tokens_dev, slot_dev, pos_off_dev, pos_dev, chain_id_dev, (unsigned long long)allowed_mask,
+                                      force_new ? 1 : 0, (unsigned long long)seed, step, site_out_dev, old_out_dev, tok_out_dev,
+                                      n_chain, B, T, total, V, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_contact_energy(const float* contacts_dev, const uint8_t* target_dev, double* energy_out_dev, int32_t* count_out_dev, int B,
+                           int S, int min_sep, int kind, void* stream) {
+    if (!contacts_dev || !target_dev || !energy_out_dev || !count_out_dev) return fail("esmk_op_contact_energy: null argument");
+    if (B <= 0 || S <= 0) return fail("esmk_op_contact_energy: B and S must be positive");
+    if (S > 32768) return fail("esmk_op_contact_energy: S above 32768 (the pairs of a map are indexed in 32 bits)");
+    if (B > ESMK_MAX_ROWS) return fail("esmk_op_contact_energy: B exceeds 2^24");
+    if (min_sep < 1) return fail("esmk_op_contact_energy: min_sep must be at least 1");
+    if (kind < 0 || kind > 1) return fail("esmk_op_contact_energy: kind must be 0 (pos) or 1 (bce)");
+    ESMK_TRY(launch_contact_energy(contacts_dev, target_dev, energy_out_dev, count_out_dev, B, S, min_sep, kind, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_mh_accept(int64_t* tokens_dev, const int32_t* slot_dev, const int32_t* site_dev, const int32_t* tok_dev,
+                      const int32_t* chain_id_dev, const double* e_contact_dev, const double* lp_sum_dev, const int32_t* n_res_dev,
+                      const double* hastings_dev, double w_contact, double w_lm, double inv_temperature, uint64_t seed, int step,
+                      double* e_cur_dev, double* e_contact_cur_dev, double* e_lm_cur_dev, uint8_t* accepted_out_dev, double* u_out_dev,
+                      double* e_prop_out_dev, int n_chain, int B, int T, void* stream) {
+    if (!tokens_dev || !site_dev || !tok_dev || !chain_id_dev || !e_cur_dev || !accepted_out_dev)
+        return fail("esmk_op_mh_accept: null argument");
+    if (lp_sum_dev && !n_res_dev) return fail("esmk_op_mh_accept: lp_sum without n_res");
+    if (n_chain <= 0 || B <= 0 || T <= 0) return fail("esmk_op_mh_accept: n_chain, B and T must be positive");
+    if ((long long)B * T > ESMK_MAX_ROWS || n_chain > ESMK_MAX_ROWS) return fail("esmk_op_mh_accept: B*T or n_chain exceeds 2^24 rows");
+    if (!(inv_temperature >= 0.0)) return fail("esmk_op_mh_accept: inv_temperature must not be negative or NaN (+inf: greedy)");
+    if (!(w_contact == w_contact) || !(w_lm == w_lm) || std::isinf(w_contact) || std::isinf(w_lm))
+        return fail("esmk_op_mh_accept: the weights must be finite");
+    if (step < 0) return fail("esmk_op_mh_accept: step must not be negative");
+    ESMK_TRY(launch_mh_accept(tokens_dev, slot_dev, site_dev, tok_dev, chain_id_dev, e_contact_dev, lp_sum_dev, n_res_dev, hastings_dev,
+                              w_contact, w_lm, inv_temperature, (unsigned long long)seed, step, e_cur_dev, e_contact_cur_dev,
+                              e_lm_cur_dev, accepted_out_dev, u_out_dev, e_prop_out_dev, n_chain, B, T, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_hastings_rows(const float* logprobs_dev, const int32_t* old_dev, const int32_t* new_dev, float inv_t_prop,
+                          double* h_out_dev, int n, int V, void* stream) {
+    if (!logprobs_dev || !old_dev || !new_dev || !h_out_dev) return fail("esmk_op_hastings_rows: null argument");
+    if (n <= 0 || n > ESMK_MAX_ROWS) return fail("esmk_op_hastings_rows: n must be in 1 .. 2^24");
+    if (V <= 0 || V > 64) return fail("esmk_op_hastings_rows: V must be in 1 .. 64");
+    if (!(inv_t_prop >= 0.f) || inv_t_prop > 3.0e38f) return fail("esmk_op_hastings_rows: inv_t_prop must be finite and not negative");
+    ESMK_TRY(launch_hastings_rows(logprobs_dev, old_dev, new_dev, inv_t_prop, h_out_dev, n, V, (hipStream_t)stream));
     return 0;
 }
 

@@ -253,6 +253,28 @@ hipError_t launch_select_rows(const float* score, const int* row_off, const int*
 // tokens[slot[i], pos[i]] = token[i] on int64 [B,T]; token < 0 or pos outside [0,T) writes nothing, slot clamped to [0,B)
 hipError_t launch_commit_tokens(int64_t* tokens, const int* slot, const int* pos, const int* token, int n, int B, int T,
                                 hipStream_t st);
+// design.hip — Metropolis-Hastings design toward a target contact map (esm_amd/design.py).  Philox counters (chain id, step,
+// purpose, 0): purpose 2 = proposal (words x: site, y: token), 3 = acceptance.  No atomics; one lane per chain except the energy.
+// site = pos[pos_off[c] + mulhi32(x, len_c)], old = tokens[slot[c] or c, site], tok = set bit mulhi32(y, n_cand) of the candidates
+// (bits of `allowed` below V, minus old with force_new); an empty list: site = old = tok = -1; no candidate: tok = -1
+hipError_t launch_propose_mutations(const int64_t* tokens, const int* slot, const int* pos_off, const int* pos, const int* chain_id,
+                                    unsigned long long allowed, int force_new, unsigned long long seed, int step, int* site_out,
+                                    int* old_out, int* tok_out, int n_chain, int B, int T, int total, int V, hipStream_t st);
+// energy[b] = -mean of log p over the target contacts (kind 0) or of y log p + (1 - y) log(1 - p) over the counted pairs (kind 1)
+// of contacts fp32 [B,S,S] against target uint8 [S,S] (0 / 1 / 2 = ignore), pairs j - i >= min_sep; p clamped to [2^-24, 1 - 2^-24];
+// fp64, one workgroup per chain, fixed order; count[b] = the terms, 0 terms: energy 0
+hipError_t launch_contact_energy(const float* contacts, const unsigned char* target, double* energy_out, int* count_out, int B, int S,
+                                 int min_sep, int kind, hipStream_t st);
+// E' = w_contact * e_contact[c] + w_lm * -(lp_sum[c] / n_res[c]); accept iff tok >= 0 and (a >= 0 or u < exp(a)), a = -(E' - e_cur[c])
+// * inv_temperature + hastings[c]; +inf: iff E' <= e_cur[c].  On acceptance the token, e_cur and the component energies are written
+hipError_t launch_mh_accept(int64_t* tokens, const int* slot, const int* site, const int* tok, const int* chain_id,
+                            const double* e_contact, const double* lp_sum, const int* n_res, const double* hastings, double w_contact,
+                            double w_lm, double inv_temperature, unsigned long long seed, int step, double* e_cur,
+                            double* e_contact_cur, double* e_lm_cur, unsigned char* accepted_out, double* u_out, double* e_prop_out,
+                            int n_chain, int B, int T, hipStream_t st);
+// h[c] = (double)inv_t_prop * ((double)lp[c, old[c]] - (double)lp[c, new[c]]); a token outside [0,V): 0
+hipError_t launch_hastings_rows(const float* lp, const int* old_tok, const int* new_tok, float inv_t_prop, double* h_out, int n, int V,
+                                hipStream_t st);
 // jacobian.hip — the categorical Jacobian J[i,a,j,b] fp32 [L,nA,L,nA] of one protein (esm_amd/jacobian.py); nA <= 32, every
 // index into J 64 bit, every sum fp64 in a fixed order, no atomics.
 // out int64 [n,T]: row i = tokens[src_row[i]] (row 0 when src_row is null; clamped to [0,B)) with position pos[i] set to

@@ -401,6 +401,24 @@ class Esm2Engine(Engine):
         return self._rows(lib.esmk_packed_rows_workspace_bytes, lib.esmk_forward_packed_rows, (seg_ptr, seg.shape[0], tok.numel()),
                           tok, sel_rows, V, return_logits)
 
+    def rows_contacts_bytes(self, B, T, n_sel):
+        """The workspace ``esmk_forward_rows_contacts`` takes: the accumulators of the pinned head-group count included."""
+        return self._query(self.N.lib.esmk_rows_contacts_workspace_bytes, B, T, n_sel, offset=True)[0]
+
+    def forward_rows_contacts(self, tok, sel_rows, V, S):
+        """``esmk_forward_rows_contacts`` on ``tok`` int64 [B, T]: (fp32 [n, V] log-probabilities of ``sel_rows``, or None when
+        ``sel_rows`` is None or empty; fp32 [B, S, S] contact maps, each the bits of ``predict_contacts`` on that row alone)."""
+        N = self.N
+        B, T = tok.shape
+        n = 0 if sel_rows is None else sel_rows.numel()
+        ws = self.workspace_for_bytes(self.rows_contacts_bytes(B, T, n))
+        out = torch.empty((n, V), dtype=torch.float32, device=self.device) if n else None
+        contacts = torch.empty((B, S, S), dtype=torch.float32, device=self.device)  # S = T minus the <cls> / <eos> of the alphabet
+        N.check(N.lib.esmk_forward_rows_contacts(self.handle, N.ptr(self.packed), N.ptr(tok), B, T, N.ptr(sel_rows if n else None), n,
+                                                 N.ptr(out), N.ptr(contacts), N.ptr(ws), ws.numel(), N.cur_stream()))
+        self.max_T = max(self.max_T, T)
+        return out, contacts
+
 
 class MsaEngine(Engine):
     """The engine of ``MSATransformer``: ``esmk_msa_create`` and the ``esmk_msa_forward*`` entries."""

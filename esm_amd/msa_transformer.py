@@ -200,6 +200,7 @@ class MSATransformer(_EngineHost, nn.Module):
     score_variants = masked_joint
     gibbs_sample = inpaint = masked_joint  # esm_amd.sampling draws single sequences only
     categorical_jacobian = jacobian_contacts = masked_joint  # esm_amd.jacobian substitutes in single sequences only
+    design = design_energy = masked_joint  # esm_amd.design runs chains of single sequences only
 
     # Variant scoring of one MSA (esm_amd/msa_scoring.py over esmk_msa_forward_rows): an MSA plus a query row is another
     # argument shape than a batch of sequences, hence names of their own; the single-sequence names above keep refusing

@@ -698,6 +698,99 @@ def commit_tokens(tokens, slots, positions, token):
     return tokens
 
 
+# ---- Metropolis-Hastings design (include/esmk.h: esmk_op_propose_mutations ... esmk_op_hastings_rows) ---------------------------
+CONTACT_LOSSES = {"pos": 0, "bce": 1}  # kind of esmk_op_contact_energy
+
+
+def propose_mutations(tokens, pos_offsets, positions, chain_ids, allowed_mask, force_new=True, seed=0, step=0, slots=None):
+    """The uniform single-site proposal of every chain: ``(site, old, token)`` int32 [n_chain] each.  Chain c reads the Philox
+    words at counter (chain_ids[c], step, 2, 0) under the key ``seed``: the site is element ``mulhi32(word0, len_c)`` of its list
+    ``positions[pos_offsets[c] : pos_offsets[c + 1]]``, ``old`` the token ``tokens[slots[c], site]`` (``slots`` None: row c), the
+    proposed token the set bit number ``mulhi32(word1, n_cand)`` of the candidates — the bits of ``allowed_mask`` below V = 64,
+    minus ``old`` with ``force_new``.  An empty list: (-1, -1, -1); no candidate: token -1.  Everything on the device."""
+    _req_cuda(tokens, pos_offsets, positions, chain_ids, slots)
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.is_contiguous()
+    for t in (pos_offsets, positions, chain_ids) + ((slots,) if slots is not None else ()):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
+    n_chain = chain_ids.numel()
+    assert n_chain >= 1 and pos_offsets.numel() == n_chain + 1 and (slots is None or slots.numel() == n_chain)
+    B, T = tokens.shape
+    assert slots is not None or n_chain <= B
+    allowed_mask = int(allowed_mask)
+    if not 0 <= allowed_mask < 2 ** 64:
+        raise ValueError("allowed_mask is a bitset over at most 64 vocabulary entries")
+    total = positions.numel()
+    if total == 0:  # every list is empty; the entry still wants a pointer it will not read
+        positions = torch.zeros((1,), dtype=torch.int32, device=tokens.device)
+    site, old, tok = (torch.empty((n_chain,), dtype=torch.int32, device=tokens.device) for _ in range(3))
+    N.check(N.lib.esmk_op_propose_mutations(N.ptr(tokens), N.ptr(slots), N.ptr(pos_offsets), N.ptr(positions), N.ptr(chain_ids),
+                                            allowed_mask, int(bool(force_new)), _seed64(seed), int(step), N.ptr(site), N.ptr(old),
+                                            N.ptr(tok), n_chain, B, T, total, 64, N.cur_stream()))
+    return site, old, tok
+
+
+def contact_energy(contacts, target, min_sep=6, kind="pos"):
+    """``(energy fp64 [B], count int32 [B])``: the cross-entropy between the probabilities ``contacts`` fp32 [B, S, S] and
+    ``target`` uint8 [S, S] (0 = no contact, 1 = contact, 2 = ignore) over the pairs i < j with j - i >= ``min_sep`` and target
+    != 2, p clamped to [2^-24, 1 - 2^-24], in fp64.  ``"pos"``: -mean of log p over the target contacts; ``"bce"``: -mean of
+    y log p + (1 - y) log(1 - p) over the counted pairs.  The order of addition does not depend on B; no term: 0.0."""
+    _req_cuda(contacts, target)
+    assert contacts.dtype == torch.float32 and contacts.dim() == 3 and contacts.is_contiguous()
+    B, S, S2 = contacts.shape
+    assert S == S2 and target.dtype == torch.uint8 and tuple(target.shape) == (S, S) and target.is_contiguous()
+    if kind not in CONTACT_LOSSES:
+        raise ValueError(f"contact loss {kind!r}: one of {tuple(CONTACT_LOSSES)}")
+    energy = torch.empty((B,), dtype=torch.float64, device=contacts.device)
+    count = torch.empty((B,), dtype=torch.int32, device=contacts.device)
+    N.check(N.lib.esmk_op_contact_energy(N.ptr(contacts), N.ptr(target), N.ptr(energy), N.ptr(count), B, S, int(min_sep),
+                                         CONTACT_LOSSES[kind], N.cur_stream()))
+    return energy, count
+
+
+def mh_accept(tokens, site, tok, chain_ids, e_cur, e_contact=None, lp_sum=None, n_res=None, hastings=None, w_contact=1.0, w_lm=1.0,
+              inv_temperature=1.0, seed=0, step=0, slots=None, e_contact_cur=None, e_lm_cur=None):
+    """The Metropolis-Hastings test of every chain, in place on ``tokens`` int64 [B, T] and ``e_cur`` fp64 [n_chain]:
+    ``(accepted uint8, u fp64, e_prop fp64)`` [n_chain] each.  E' = w_contact * e_contact + w_lm * -(lp_sum / n_res) (a missing
+    term is 0); accept iff tok >= 0 and (a >= 0 or u < exp(a)) with a = -(E' - e_cur) * inv_temperature + hastings and u the
+    24-bit uniform of Philox counter (chain_ids[c], step, 3, 0); ``inv_temperature=inf``: iff E' <= e_cur.  An accepted chain
+    gets ``tokens[slots[c], site[c]] = tok[c]`` (``slots`` None: row c), ``e_cur = E'`` and its component energies in
+    ``e_contact_cur`` / ``e_lm_cur`` where given."""
+    f64 = (e_cur, e_contact, lp_sum, hastings, e_contact_cur, e_lm_cur)
+    i32 = (site, tok, chain_ids, n_res, slots)
+    _req_cuda(tokens, *f64, *i32)
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.is_contiguous()
+    n_chain = chain_ids.numel()
+    for t in f64:
+        assert t is None or (t.dtype == torch.float64 and t.dim() == 1 and t.numel() == n_chain and t.is_contiguous())
+    for t in i32:
+        assert t is None or (t.dtype == torch.int32 and t.dim() == 1 and t.numel() == n_chain and t.is_contiguous())
+    B, T = tokens.shape
+    assert n_chain >= 1 and (slots is not None or n_chain <= B) and (lp_sum is None or n_res is not None)
+    dev = tokens.device
+    accepted = torch.empty((n_chain,), dtype=torch.uint8, device=dev)
+    u = torch.empty((n_chain,), dtype=torch.float64, device=dev)
+    e_prop = torch.empty((n_chain,), dtype=torch.float64, device=dev)
+    N.check(N.lib.esmk_op_mh_accept(N.ptr(tokens), N.ptr(slots), N.ptr(site), N.ptr(tok), N.ptr(chain_ids), N.ptr(e_contact),
+                                    N.ptr(lp_sum), N.ptr(n_res), N.ptr(hastings), float(w_contact), float(w_lm),
+                                    float(inv_temperature), _seed64(seed), int(step), N.ptr(e_cur), N.ptr(e_contact_cur),
+                                    N.ptr(e_lm_cur), N.ptr(accepted), N.ptr(u), N.ptr(e_prop), n_chain, B, T, N.cur_stream()))
+    return accepted, u, e_prop
+
+
+def hastings_rows(logprobs, old, new, inv_t_prop=1.0):
+    """fp64 [n]: ``float64(float32(inv_t_prop)) * (float64(logprobs[c, old[c]]) - float64(logprobs[c, new[c]]))`` — the log ratio of
+    the reverse and the forward proposal of a draw from the row ``logprobs`` fp32 [n, V]; 0 where a token is outside [0, V)."""
+    _req_cuda(logprobs, old, new)
+    assert logprobs.dtype == torch.float32 and logprobs.dim() == 2 and logprobs.is_contiguous()
+    n, V = logprobs.shape
+    for t in (old, new):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.numel() == n and t.is_contiguous()
+    out = torch.empty((n,), dtype=torch.float64, device=logprobs.device)
+    N.check(N.lib.esmk_op_hastings_rows(N.ptr(logprobs), N.ptr(old), N.ptr(new), float(inv_t_prop), N.ptr(out), n, V,
+                                        N.cur_stream()))
+    return out
+
+
 # ---- MSA row selection (include/esmk.h: esmk_op_msa_mismatch_rows ... esmk_op_rank_keys) --------------------------------------
 def _msa_dims(msa, L):
     """(N, L, ld) of a device byte matrix uint8 [N, ld] of which the first ``L`` columns count (None: all)."""

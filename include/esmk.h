@@ -232,6 +232,33 @@ int esmk_forward_rows(esmk_model* m, const void* packed_dev, const int64_t* toke
                       const int32_t* sel_rows_dev, int n_sel, float* logprobs_out_dev, void* workspace_dev,
                       size_t workspace_bytes, void* stream);
 
+/* ---- design toward a target contact map: selected log-prob rows AND contact maps in one forward ----------------
+ * esmk_forward_rows plus ESMK_OUT_CONTACTS in the fused form (no [B,L,H,T,T] tensor): the layer stack runs once on all B*T rows,
+ * the head of the model on the n_sel selected rows as in esmk_forward_rows (the same bits), and the contact head accumulates
+ * contacts_out_dev fp32 [B,S,S] (S = T minus the <cls> / <eos> the alphabet adds) layer by layer.  It is the energy forward of
+ * esm_amd/design.py: one call gives the LM term's rows and the structure term's maps of a batch of proposals.
+ * The head-group pin: esmk_forward cuts the heads of a layer into a number of groups that it chooses from B (more groups where
+ * few (query block, key chunk) pairs would leave compute units idle), and a map is the sum of the group accumulators in group
+ * order — so the last bits of a sequence's map depend on the batch it runs in.  This entry always takes the group count of
+ * B = 1: map b of the batch is bit for bit what esmk_forward(ESMK_OUT_CONTACTS) gives tokens[b] alone at B = 1, whatever B is, and
+ * an acceptance test on an energy of that map makes the same decision alone and in any batch.  esmk_forward keeps its own
+ * choice.  The price is workspace: the accumulators take G(1)*B*T*T*4 bytes where esmk_forward takes G(B) of them — up to
+ * H*B*T*T*4 bytes (G(1) = min(H, ceil(1024 / ceil(T/128)^2)) for head_dim <= 64); ask esmk_rows_contacts_workspace_bytes, not
+ * esmk_workspace_bytes.
+ *   n_sel = 0 is allowed: no head runs, sel_rows_dev and logprobs_out_dev may be NULL (an energy with the contact term alone)
+ *   logits_offset    as in esmk_rows_workspace_bytes (nothing is kept there with n_sel = 0)
+ * ESM-2, ESM-1b / ESM-1v and ESM-1 handles (the fused contact head reads the bias_kv attention's q, k and row log-sum-exp like
+ * any other), in whatever operand dtype and precision mode esmk_forward runs contacts for that handle.  Refused before any HIP
+ * call: MSA handles, null pointers, B or T <= 0, B*T or n_sel > 2^24, n_sel < 0, vocab > 64 with n_sel > 0, a T that leaves no
+ * residue (S <= 0), a workspace that is too small.  The whole call runs on `stream`; messages name esmk_forward_rows_contacts. */
+int esmk_rows_contacts_workspace_bytes(const esmk_model* m, int B, int T, int n_sel, size_t* bytes, size_t* logits_offset);
+int esmk_forward_rows_contacts(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev, int B, int T,
+                               const int32_t* sel_rows_dev, int n_sel, float* logprobs_out_dev, float* contacts_out_dev,
+                               void* workspace_dev, size_t workspace_bytes, void* stream);
+/* The head-group count of the fused contact head for a padded batch (no GPU needed): pinned 0 = esmk_forward at this B,
+ * 1 = esmk_forward_rows_contacts (the count of B = 1, whatever B is). */
+int esmk_debug_contact_groups(const esmk_model* m, int B, int T, int pinned, int32_t* groups);
+
 /* The same for a token-packed batch: the masked copies of a library of sequences of DIFFERENT lengths (pseudo-log-likelihood
  * of designed sequences, insertion / deletion variants, wt-marginals over a FASTA file) laid back to back in one row space,
  * so that the layer stack does no work on padding.  It is the reference's loop (predict.py:138-143,205-215: one B = 1 forward
@@ -446,7 +473,10 @@ int esmk_debug_gemm_plan(int M, int N, int K, int epilogue, int flags, int32_t o
 /* Measurement / A-B hook (no reference counterpart): named switches of the library, process wide.  No switch changes a
  * result bit.  "qkv_one_launch": 1 / 0 = always / never run the q, k and v projections of a layer as ONE GEMM launch,
  * -1 = the library's choice (one launch where it needs fewer rounds of tiles over the CUs, i.e. small batches;
- * gemm_dispatch.hip; environment: ESMK_QKV_ONE_LAUNCH).  Any other key is an error ("unknown key").  Libraries built with
+ * gemm_dispatch.hip; environment: ESMK_QKV_ONE_LAUNCH).  The one exception to "no result bit" is "rows_contacts_own_groups":
+ * 1 makes esmk_forward_rows_contacts (and its workspace query) take the head-group count of the batch instead of the pinned
+ * one of B = 1, so that what the pin costs can be timed (tools/design_throughput.py); the maps then carry the bits of
+ * esmk_forward at that B.  0, the default, is the pin.  Any other key is an error ("unknown key").  Libraries built with
  * ESMK_HIPCC_EXTRA="-DESMK_EXPERIMENTS" add timing experiments, some of which DO break results (kernels with their
  * MFMAs, exponentials, DMA or epilogue stores removed): see common.h. */
 int esmk_debug_set(const char* key, double value);
@@ -759,6 +789,56 @@ int esmk_op_sample_rows_ex(const float* logprobs_dev, const int32_t* row_chain_d
 int esmk_op_select_rows(const float* score_dev, const int32_t* row_off_dev, const int32_t* sel_off_dev,
                         const int32_t* rest_off_dev, int32_t* sel_out_dev, int32_t* rest_out_dev, int n_chain, int n, int n_sel,
                         int n_rest, void* stream);
+
+/* Metropolis-Hastings design toward a target contact map (esm_amd/design.py; csrc/design.hip).  The state of a chain is its token
+ * row and its current energy E = w_contact * E_contact + w_lm * E_lm, both on the device.  A step with the uniform proposal is
+ *   esmk_op_propose_mutations -> esmk_op_substitute_rows -> esmk_forward_rows_contacts (the residue rows of every proposal
+ *   selected) -> esmk_op_sum_target_rows -> esmk_op_contact_energy -> esmk_op_mh_accept
+ * and with the LM proposal
+ *   esmk_op_propose_mutations (the site) -> esmk_op_mask_rows_multi -> esmk_forward_rows (the masked site's row) ->
+ *   esmk_op_sample_rows at counter (chain, step, 1, site) -> esmk_op_hastings_rows -> esmk_op_substitute_rows -> ... as above
+ * on one stream; the host reads nothing in between.  Philox as in the sampling section, counter (chain id, step, purpose, 0):
+ * purpose 2 = proposal (word 0: the site, word 1: the token), purpose 3 = acceptance.  No atomics; all list data is device data.
+ * esmk_op_propose_mutations: one lane per chain c.  site = pos[pos_off[c] + mulhi32(word0, len_c)], pos_off int32 [n_chain+1]
+ *   (clamped to [0,total]; a pair with hi < lo is an empty list), pos int32 [total].  old = tokens[slot[c], site] (tokens int64
+ *   [B,T]; slot int32 [n_chain] clamped to [0,B), or NULL: slot c).  The candidates are the bits of allowed_mask below V, minus
+ *   old when force_new; tok = the set bit number mulhi32(word1, n_cand) of the candidates in ascending token order.  An empty
+ *   list or a site outside [0,T): site = old = tok = -1.  No candidate: tok = -1.  Integer arithmetic only.
+ * esmk_op_contact_energy: contacts fp32 [B,S,S] probabilities, target uint8 [S,S] (0 = no contact, 1 = contact, 2 = ignore).
+ *   Only pairs i < j with j - i >= min_sep (>= 1) and target != 2 count.  p is clamped to [2^-24, 1 - 2^-24] and taken to fp64.
+ *   kind 0 ("pos"): energy = -mean over the counted target contacts of log p, count = their number; kind 1 ("bce"): energy =
+ *   -mean over the counted pairs of y log p + (1 - y) log(1 - p), count = their number.  One workgroup of 256 lanes per chain;
+ *   lane t adds the terms of the elements t, t + 256, ... of the row-major map in that order, the lane sums are added in a
+ *   butterfly per wavefront and the four wavefront sums in order: the order of addition depends on S, min_sep and the target
+ *   alone.  energy_out fp64 [B], count_out int32 [B]; a count of 0 gives energy 0.0.
+ * esmk_op_mh_accept: one lane per chain, fp64, every operation rounded once (no fused multiply-add).  E' = w_contact *
+ *   e_contact[c] + w_lm * (-(lp_sum[c] / n_res[c])): e_contact fp64 [n_chain] or NULL (0), lp_sum fp64 [n_chain]
+ *   (esmk_op_sum_target_rows over the chain's residue rows) or NULL (0), n_res int32 [n_chain] (<= 0: the LM term is 0).
+ *   dE = E' - e_cur[c]; h = hastings[c] or 0 (NULL); u = (word0 >> 8) * 2^-24 at counter (chain_id[c], step, 3, 0).  Accept iff
+ *   tok[c] >= 0 and (a >= 0 or u < exp(a)), a = -dE * inv_temperature + h; inv_temperature == +inf (greedy): iff tok[c] >= 0 and
+ *   dE <= 0.  On acceptance tokens[slot[c], site[c]] = tok[c] (slot as above; a site outside [0,T) writes no token), e_cur[c] =
+ *   E', and e_contact_cur[c] / e_lm_cur[c] (fp64 [n_chain] or NULL) receive the components.  accepted_out uint8 [n_chain];
+ *   u_out, e_prop_out fp64 [n_chain] or NULL: written for every chain.
+ * esmk_op_hastings_rows: h_out fp64 [n], h[c] = (double)inv_t_prop * ((double)logprobs[c, old[c]] - (double)logprobs[c, new[c]]),
+ *   logprobs fp32 [n,V]: the log ratio of the reverse and the forward LM proposal, which share the context and the candidate
+ *   set.  old or new outside [0,V): 0.
+ * Refused before any HIP call: null pointers (slot_dev, e_contact_dev, lp_sum_dev with n_res_dev, hastings_dev,
+ * e_contact_cur_dev, e_lm_cur_dev, u_out_dev, e_prop_out_dev may be NULL), n_chain, n, B, T or S <= 0, total < 0, V outside
+ * 1 .. 64, S > 32768, B*T, n_chain or n > 2^24, min_sep < 1, kind outside 0 .. 1, a negative step, an inv_temperature that is
+ * negative or NaN, weights that are not finite, an inv_t_prop that is negative or not finite. */
+int esmk_op_propose_mutations(const int64_t* tokens_dev, const int32_t* slot_dev, const int32_t* pos_off_dev, const int32_t* pos_dev,
+                              const int32_t* chain_id_dev, uint64_t allowed_mask, int force_new, uint64_t seed, int step,
+                              int32_t* site_out_dev, int32_t* old_out_dev, int32_t* tok_out_dev, int n_chain, int B, int T, int total,
+                              int V, void* stream);
+int esmk_op_contact_energy(const float* contacts_dev, const uint8_t* target_dev, double* energy_out_dev, int32_t* count_out_dev, int B,
+                           int S, int min_sep, int kind, void* stream);
+int esmk_op_mh_accept(int64_t* tokens_dev, const int32_t* slot_dev, const int32_t* site_dev, const int32_t* tok_dev,
+                      const int32_t* chain_id_dev, const double* e_contact_dev, const double* lp_sum_dev, const int32_t* n_res_dev,
+                      const double* hastings_dev, double w_contact, double w_lm, double inv_temperature, uint64_t seed, int step,
+                      double* e_cur_dev, double* e_contact_cur_dev, double* e_lm_cur_dev, uint8_t* accepted_out_dev, double* u_out_dev,
+                      double* e_prop_out_dev, int n_chain, int B, int T, void* stream);
+int esmk_op_hastings_rows(const float* logprobs_dev, const int32_t* old_dev, const int32_t* new_dev, float inv_t_prop,
+                          double* h_out_dev, int n, int V, void* stream);
 
 /* Choosing the rows of an MSA on the device (esm_amd/msa_select.py; csrc/msa_select.hip).  An MSA is msa uint8 [N,ld], row-major:
  * L <= ld columns count, bytes in [L,ld) of a row are never counted whatever they hold, and every byte value 0 .. 255 is legal
