@@ -254,6 +254,12 @@ SIGNATURES = {
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                 c_int, c_void_p]),
     "esmk_op_sum_target_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    # windows: window copies of long sequences, the owner / blend stitch of per-window rows, the stitch of per-window contact maps
+    "esmk_op_window_rows": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                c_void_p]),
+    "esmk_op_blend_rows": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "esmk_op_stitch_contacts": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     # sampling: per-chain shuffles, one token per row of log-probabilities, the write-back (seeds and masks are uint64)
     "esmk_op_permute_positions": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_uint64, c_int, c_void_p]),

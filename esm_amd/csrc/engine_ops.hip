@@ -892,6 +892,42 @@ int esmk_op_sum_target_rows(const float* logprobs_dev, const int32_t* target_dev
     return 0;
 }
 
+int esmk_op_window_rows(const int64_t* tokens_dev, const int32_t* src_row_dev, const int32_t* start_dev,
+                        const int32_t* mask_off_dev, const int32_t* mask_pos_dev, int64_t* out_dev, int B, int T, int n, int Tw,
+                        int total, int head_tok, int tail_tok, int mask_idx, void* stream) {
+    if (!tokens_dev || !src_row_dev || !start_dev || !mask_off_dev || !mask_pos_dev || !out_dev)
+        return fail("esmk_op_window_rows: null argument");
+    if (B <= 0 || T <= 0 || n <= 0 || Tw <= 0) return fail("esmk_op_window_rows: B, T, n and Tw must be positive");
+    if (total < 0) return fail("esmk_op_window_rows: total must not be negative");
+    if ((long long)B * T > ESMK_MAX_ROWS || (long long)n * Tw > ESMK_MAX_ROWS)
+        return fail("esmk_op_window_rows: B*T or n*Tw exceeds 2^24 rows");
+    ESMK_TRY(launch_window_rows(tokens_dev, src_row_dev, start_dev, mask_off_dev, mask_pos_dev, out_dev, B, T, n, Tw, total,
+                                head_tok, tail_tok, mask_idx, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_blend_rows(const void* x_dev, int x_dtype, const int32_t* off_dev, const int32_t* src_dev, const float* w_dev,
+                       float* out_dev, int N, int E, int n_out, int total, void* stream) {
+    if (!x_dev || !off_dev || !src_dev || !w_dev || !out_dev) return fail("esmk_op_blend_rows: null argument");
+    if (N <= 0 || n_out <= 0) return fail("esmk_op_blend_rows: N and n_out must be positive");
+    if (E <= 0 || E % 4 != 0) return fail("esmk_op_blend_rows: E must be a positive multiple of 4");
+    if (total < 0) return fail("esmk_op_blend_rows: total must not be negative");
+    if (x_dtype != ESMK_DT_F32 && x_dtype != ESMK_DT_F16 && x_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_blend_rows: x_dtype must be ESMK_F32, ESMK_F16 or ESMK_BF16");
+    ESMK_TRY(launch_blend_rows(x_dev, x_dtype, off_dev, src_dev, w_dev, out_dev, N, E, n_out, total, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_stitch_contacts(const float* maps_dev, const int32_t* start_dev, float* out_dev, int n_w, int R, int Lb, int body_lo,
+                            void* stream) {
+    if (!maps_dev || !start_dev || !out_dev) return fail("esmk_op_stitch_contacts: null argument");
+    if (n_w <= 0 || R <= 0 || Lb <= 0) return fail("esmk_op_stitch_contacts: n_w, R and Lb must be positive");
+    if ((long long)n_w * R * R > (1ll << 40) || Lb > (1 << 20))
+        return fail("esmk_op_stitch_contacts: n_w*R*R exceeds 2^40 entries or Lb exceeds 2^20");
+    ESMK_TRY(launch_stitch_contacts(maps_dev, start_dev, out_dev, n_w, R, Lb, body_lo, (hipStream_t)stream));
+    return 0;
+}
+
 int esmk_op_log_softmax_rows(const float* logits_dev, float* out_dev, const int32_t* target_dev, float* target_out_dev, int n,
                              int V, void* stream) {
     if (!logits_dev || !out_dev) return fail("esmk_op_log_softmax_rows: null argument");

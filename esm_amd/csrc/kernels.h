@@ -227,6 +227,21 @@ hipError_t launch_score_rows(const float* lp, const int* wt, const int* mt, cons
 // sequence (no atomics); target clamped to [0,V), offsets to [0,n_rows]
 hipError_t launch_sum_target_rows(const float* lp, const int* target, const int* off, double* out, int n_rows, int n_seq, int V,
                                   hipStream_t st);
+// windows.hip — proteins longer than the model's window (esm_amd/windows.py).  out int64 [n,Tw]: copy i, column c =
+// tokens[src_row[i], start[i] + c - h] (h = 1 if head_tok >= 0; row and column clamped), column 0 = head_tok and column Tw - 1 =
+// tail_tok where those are >= 0; the entries of pos[pos_off[i] : pos_off[i+1]] (SOURCE token coordinates) that land on a body
+// column become mask_idx
+hipError_t launch_window_rows(const int64_t* tokens, const int* src_row, const int* start, const int* pos_off, const int* pos,
+                              int64_t* out, int B, int T, int n, int Tw, int total, int head_tok, int tail_tok, int mask_idx,
+                              hipStream_t st);
+// out fp32 [n_out,E]: out[r] = (sum_k w[k] x[src[k]]) / sum_k w[k], k ascending in [off[r], off[r+1]), fp32, one lane per
+// element; ONE entry: the row exactly; none: zeros; x [N,E] of any dtype code, E % 4 == 0, src clamped to [0,N)
+hipError_t launch_blend_rows(const void* x, int x_dtype, const int* off, const int* src, const float* w, float* out, int N, int E,
+                             int n_out, int total, hipStream_t st);
+// out fp32 [Lb,Lb]: entry (i, j) from the window (maps [n_w,R,R], body start start[w] - body_lo) that holds both residues with
+// the least |2 s + R - 1 - (i + j)|, ties to the lower start; NaN where no window holds both
+hipError_t launch_stitch_contacts(const float* maps, const int* start, float* out, int n_w, int R, int Lb, int body_lo,
+                                  hipStream_t st);
 // sampling.hip — drawing sequences on the device (esm_amd/sampling.py).  Random numbers are Philox4x32-10 words addressed by
 // key = seed and counter = (chain id, epoch or step, purpose, index); purpose 0 = permutation, 1 = token draw.
 // perm_out[pos_off[c] : pos_off[c+1]] = Fisher-Yates shuffle of the same slice of pos_in (int32 [total]), one lane per chain;

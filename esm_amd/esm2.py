@@ -92,6 +92,11 @@ def _varlen_kw(varlen, chunk_rows):
     return dict(varlen=True, chunk_rows=chunk_rows)
 
 
+def _window_kw(window, wrap):
+    """The keywords of a windowed call (``esm_amd.windows``): none without ``window``, so that the call is the one of before."""
+    return {} if window is None else dict(window=window, wrap=wrap)
+
+
 class ESM2(_EngineHost, nn.Module):
     _engine_class = _Engine
     _cpu_refusal = ("esm_amd.ESM2 runs only on an MI355X (ROCm) device: move the model and tokens to "
@@ -356,39 +361,54 @@ class ESM2(_EngineHost, nn.Module):
 
     # varlen=True: the masked copies run token-packed (esmk_forward_packed_rows) — the form for sequences of different lengths;
     # the same bits.  The default call is the one of before, keyword for keyword.
-    def masked_marginals(self, tokens, positions=None, chunk=None, varlen=False, chunk_rows=None):
+    # window= (an int, or "max" on ESM-1b / ESM-1v): sequences longer than the window are scored inside model-sized windows
+    # (esm_amd/windows.py); without it the call is the one of before.
+    def masked_marginals(self, tokens, positions=None, chunk=None, varlen=False, chunk_rows=None, window=None, wrap=True):
         """``esm_amd.scoring.masked_marginals``: [B, T, V] fp32 log-probabilities, row (b, i) from the forward with token
         (b, i) alone masked."""
         from . import scoring
 
-        return scoring.masked_marginals(self, tokens, positions=positions, chunk=chunk, **_varlen_kw(varlen, chunk_rows))
+        return scoring.masked_marginals(self, tokens, positions=positions, chunk=chunk, **_varlen_kw(varlen, chunk_rows),
+                                        **_window_kw(window, wrap))
 
-    def wt_marginals(self, tokens, varlen=False, chunk_rows=None):
+    def wt_marginals(self, tokens, varlen=False, chunk_rows=None, window=None, wrap=True):
         """``esm_amd.scoring.wt_marginals``: [B, T, V] fp32 log-probabilities of the unmasked forward, non-pad rows."""
         from . import scoring
 
-        return scoring.wt_marginals(self, tokens, **_varlen_kw(varlen, chunk_rows))
+        return scoring.wt_marginals(self, tokens, **_varlen_kw(varlen, chunk_rows), **_window_kw(window, wrap))
 
-    def pseudo_log_likelihood(self, tokens, positions=None, chunk=None, varlen=False, chunk_rows=None):
+    def pseudo_log_likelihood(self, tokens, positions=None, chunk=None, varlen=False, chunk_rows=None, window=None, wrap=True):
         """``esm_amd.scoring.pseudo_log_likelihood``: [B] fp64, sum of the masked-marginal log-probability of the true token."""
         from . import scoring
 
-        return scoring.pseudo_log_likelihood(self, tokens, positions=positions, chunk=chunk, **_varlen_kw(varlen, chunk_rows))
+        return scoring.pseudo_log_likelihood(self, tokens, positions=positions, chunk=chunk, **_varlen_kw(varlen, chunk_rows),
+                                             **_window_kw(window, wrap))
 
-    def masked_joint(self, tokens, position_sets, src=None, chunk=None, return_logits=False, varlen=False, chunk_rows=None):
+    def masked_joint(self, tokens, position_sets, src=None, chunk=None, return_logits=False, varlen=False, chunk_rows=None,
+                     window=None, wrap=True):
         """``esm_amd.scoring.masked_joint``: one forward per position set with ALL its positions masked; (offsets, pos,
         logprobs [n_rows, V]) of the masked rows."""
         from . import scoring
 
         return scoring.masked_joint(self, tokens, position_sets, src=src, chunk=chunk, return_logits=return_logits,
-                                    **_varlen_kw(varlen, chunk_rows))
+                                    **_varlen_kw(varlen, chunk_rows), **_window_kw(window, wrap))
 
-    def score_variants(self, alphabet, sequence, variants, strategy="masked-marginals", offset_idx=0, sep=":", chunk=None):
+    def score_variants(self, alphabet, sequence, variants, strategy="masked-marginals", offset_idx=0, sep=":", chunk=None,
+                       window=None, wrap=True):
         """``esm_amd.scoring.score_variants``: floats, one per variant of one or more substitutions ('A42G:K50R')."""
         from . import scoring
 
         return scoring.score_variants(self, alphabet, sequence, variants, strategy=strategy, offset_idx=offset_idx, sep=sep,
-                                      chunk=chunk)
+                                      chunk=chunk, **_window_kw(window, wrap))
+
+    def forward_windows(self, tokens, repr_layers=[], window=None, stride=None, wrap=True, stitch="owner", return_contacts=False,
+                        chunk=None):
+        """``esm_amd.windows.forward_windows``: ``forward``'s dict in source coordinates for sequences longer than the model's
+        window — overlapping windows through ``forward``, logits / representations / contact maps stitched on the device."""
+        from . import windows
+
+        return windows.forward_windows(self, tokens, repr_layers=repr_layers, window=window, stride=stride, wrap=wrap,
+                                       stitch=stitch, return_contacts=return_contacts, chunk=chunk)
 
     # drawing sequences (esm_amd/sampling.py): Gibbs sweeps and mask in-painting, every step on the device
     def gibbs_sample(self, tokens, sweeps, per_step=1, positions=None, temperature=1.0, allowed=None, force_new=False, seed=0,

@@ -16,6 +16,12 @@ files: reference scripts/extract.py:15-131) and adds the data-parallel split of 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         -m esm_amd.extract model.pt seqs.fasta out/ --repr_layers 33 --include mean
 
+``--window N`` (``--window max`` on ESM-1b / ESM-1v) embeds sequences LONGER than the window instead of truncating them: after
+the regular batches every such sequence runs as overlapping model-sized windows (``model.forward_windows``, esm_amd/windows.py;
+``--window-stride``, default half a window's residues) and its per-token rows and contact map are stitched on the device —
+every row from the window it is most central in (``--window-stitch owner``) or the triangular-weight mean of all windows that
+hold it (``blend``).  ``--truncation_seq_length`` then defaults to no truncation.
+
 The model forward is ``esm_amd.ESM2`` on the MI355X (no CPU fallback); ``embed_fn`` exists so that the
 sharding / gather logic can be exercised by the world_size-2 gloo tests without a GPU.
 """
@@ -28,6 +34,9 @@ import threading
 from typing import Callable, Dict, List, Optional, Sequence
 
 import torch
+
+
+NO_TRUNCATION = 1 << 30  # --truncation_seq_length of a run with --window that does not set one
 
 
 def batch_cost(n_seqs: int, width: int, embed_dim: int) -> float:
@@ -196,13 +205,18 @@ def extract(dataset, alphabet, embed_fn: Callable[[torch.Tensor, List[int], bool
             output_dir: Optional[pathlib.Path] = None, toks_per_batch: int = 4096,
             truncation_seq_length: int = 1022, device: Optional[torch.device] = None,
             gather_mean: bool = True, log: Callable[[str], None] = print, writer_threads: int = 0,
-            writer_depth: int = 4, async_host: bool = False, chunk_rows: int = 8):
+            writer_depth: int = 4, async_host: bool = False, chunk_rows: int = 8, window: Optional[int] = None,
+            window_fn: Optional[Callable[[torch.Tensor, List[int], bool], Dict]] = None):
     """Run the sharded extraction.  ``embed_fn(tokens, repr_layers, return_contacts)`` is the model
     forward (``ESM2.__call__`` / ``ESM2.forward_varlen`` in production; an ``embed_fn.wants_lengths = True``
     attribute asks for the extra keyword ``lengths`` = per-row token counts, taken from the host copy).  Returns ``{layer: [n_sequences, E] mean embeddings}``
     in dataset order when ``gather_mean`` (every rank gets the full matrix), else ``{}``.
     ``async_host``: run the writer-thread pipeline also without a GPU (host-side scaling tests: 8 ranks x (tokeniser +
-    writers) on one host, tests/test_extract_sharded.py); ``chunk_rows``: sequences per writer job."""
+    writers) on one host, tests/test_extract_sharded.py); ``chunk_rows``: sequences per writer job.
+    ``window`` (tokens per window, resolved) with ``window_fn(tokens, repr_layers, return_contacts)`` (``make_window_fn``):
+    a sequence whose tokens do not fit into the window leaves the regular batches and runs alone through ``window_fn`` after
+    them, which returns ``forward``'s dict in the sequence's own coordinates; such sequences go to the ranks round-robin,
+    longest first."""
     dist, rank, world = _dist_info()
     assert all(-(num_layers + 1) <= i <= num_layers for i in repr_layers)
     # duplicates (e.g. --repr_layers -1 33) collapse, first occurrence wins: the reference builds dicts keyed by layer
@@ -210,6 +224,14 @@ def extract(dataset, alphabet, embed_fn: Callable[[torch.Tensor, List[int], bool
     return_contacts = "contacts" in include
     lengths = [min(len(s), truncation_seq_length) for s in dataset.sequence_strs]
     batches = dataset.get_batch_indices(toks_per_batch, extra_toks_per_seq=1)
+    windowed: List[int] = []
+    if window is not None:
+        if window_fn is None:
+            raise ValueError("extract: window needs window_fn (make_window_fn)")
+        ends = int(bool(alphabet.prepend_bos)) + int(bool(alphabet.append_eos))
+        too_long = {i for i, n in enumerate(lengths) if n + ends > window}
+        batches = [kept for kept in ([i for i in b if i not in too_long] for b in batches) if kept]
+        windowed = sorted(too_long, key=lambda i: (-lengths[i], i))[rank::world]
     plan = assign_batches(batches, lengths, world, embed_dim)
     convert = alphabet.get_batch_converter(truncation_seq_length)
     if output_dir is not None:
@@ -339,6 +361,16 @@ def extract(dataset, alphabet, embed_fn: Callable[[torch.Tensor, List[int], bool
             step = max(1, int(chunk_rows))
             # (chunk_job is bound NOW: the name is re-bound by the next batch before the writer threads run)
             writer.submit([(lambda r=range(a, min(a + step, len(ids))), f=chunk_job: f(r)) for a in range(0, len(ids), step)], done)
+        for n_done, i in enumerate(windowed):  # one long sequence per call: its windows fill the GPU
+            labels, strs, toks = convert([dataset[i]])
+            log(f"[rank {rank}] windowed sequence {n_done + 1}/{len(windowed)}: {toks.size(1)} tokens in windows of {window}")
+            if device is not None:
+                toks = toks.to(device=device)
+            out = window_fn(toks, layers, return_contacts)
+            reps = dict(out["representations"])
+            means_dev = batch_means(reps, strs)
+            finish([i], labels, strs, {l: t.to("cpu") for l, t in reps.items()},
+                   out["contacts"].to("cpu") if return_contacts else None, {l: m.to("cpu") for l, m in means_dev.items()})
     if writer is not None:
         writer.close()
     gathered: Dict[int, torch.Tensor] = {}
@@ -372,6 +404,15 @@ def make_embed_fn(model, varlen: bool = True):
     return embed_fn
 
 
+def make_window_fn(model, window, stride=None, stitch="owner"):
+    """The ``window_fn`` of :func:`extract`: ``model.forward_windows`` with the command line's window options."""
+    def window_fn(toks, layers, return_contacts):
+        return model.forward_windows(toks, repr_layers=layers, window=window, stride=stride, stitch=stitch,
+                                     return_contacts=return_contacts)
+
+    return window_fn
+
+
 def create_parser():
     p = argparse.ArgumentParser(description="Sharded per-token / mean representation extraction on MI355X GPUs")
     p.add_argument("model_location", type=str)
@@ -383,7 +424,18 @@ def create_parser():
                         "CUs: 615 k residues/s vs 351 k at 4096)")
     p.add_argument("--repr_layers", type=int, default=[-1], nargs="+")
     p.add_argument("--include", type=str, nargs="+", choices=["mean", "per_tok", "bos", "contacts"], required=True)
-    p.add_argument("--truncation_seq_length", type=int, default=1022)
+    p.add_argument("--truncation_seq_length", type=int, default=None,
+                   help="residues kept of every sequence (default 1022; with --window: no truncation)")
+    from .windows import window_arg
+
+    p.add_argument("--window", type=window_arg, default=None, metavar="{N,max}",
+                   help="tokens per window (special tokens included): sequences longer than this run as overlapping windows and "
+                        "are stitched instead of being truncated; 'max': the size of the position table of ESM-1b / ESM-1v")
+    p.add_argument("--window-stride", type=int, default=None,
+                   help="residues between the starts of neighbouring windows (default: half the residues of a window)")
+    p.add_argument("--window-stitch", type=str, default="owner", choices=["owner", "blend"],
+                   help="per-token rows from the window a residue is most central in, or the triangular-weight mean of all "
+                        "windows that hold it")
     p.add_argument("--gpus", type=int, default=1,
                    help="GPUs of this node to shard the FASTA over; from a plain shell the command re-executes itself "
                         "as that many ranks (torch.distributed.run, RCCL), under a launcher it joins the existing ranks")
@@ -435,11 +487,21 @@ def main(argv=None):
         print(f"Read {args.fasta_file} with {len(dataset)} sequences; {world} rank(s)")
 
     embed_fn = make_embed_fn(model, varlen=not args.no_varlen)
+    window, truncation = None, args.truncation_seq_length
+    if args.window is not None:
+        from .windows import resolve_window
+
+        window = resolve_window(model, args.window)
+    elif args.window_stride is not None or args.window_stitch != "owner":
+        raise SystemExit("esm_amd.extract: --window-stride / --window-stitch go with --window")
+    if truncation is None:
+        truncation = 1022 if window is None else NO_TRUNCATION
 
     means = extract(dataset, alphabet, embed_fn, model.num_layers, model.embed_dim, args.repr_layers, args.include,
                     output_dir=args.output_dir, toks_per_batch=args.toks_per_batch,
-                    truncation_seq_length=args.truncation_seq_length, device=dev,
-                    gather_mean=args.mean_matrix is not None, writer_threads=args.writer_threads)
+                    truncation_seq_length=truncation, device=dev,
+                    gather_mean=args.mean_matrix is not None, writer_threads=args.writer_threads, window=window,
+                    window_fn=None if window is None else make_window_fn(model, window, args.window_stride, args.window_stitch))
     if args.mean_matrix is not None and rank == 0:
         torch.save({"labels": dataset.sequence_labels, "mean_representations": {l: t.cpu() for l, t in means.items()}},
                    args.mean_matrix)

@@ -185,7 +185,7 @@ class MSATransformer(_EngineHost, nn.Module):
 
     supports_scoring = False  # esmk_forward_rows takes single-sequence models only; MSAs: the msa_* methods below
 
-    def masked_marginals(self, tokens, positions=None, chunk=None):
+    def masked_marginals(self, tokens, positions=None, chunk=None, **kwargs):
         from . import scoring
 
         scoring._refuse_msa(self)
@@ -201,6 +201,7 @@ class MSATransformer(_EngineHost, nn.Module):
     gibbs_sample = inpaint = masked_joint  # esm_amd.sampling draws single sequences only
     categorical_jacobian = jacobian_contacts = masked_joint  # esm_amd.jacobian substitutes in single sequences only
     design = design_energy = masked_joint  # esm_amd.design runs chains of single sequences only
+    forward_windows = masked_joint  # esm_amd.windows cuts single sequences into windows only
 
     # Variant scoring of one MSA (esm_amd/msa_scoring.py over esmk_msa_forward_rows): an MSA plus a query row is another
     # argument shape than a batch of sequences, hence names of their own; the single-sequence names above keep refusing

@@ -552,6 +552,65 @@ def sum_target_rows(logprobs, target, offsets):
     return out
 
 
+# ---- windows (include/esmk.h: esmk_op_window_rows, esmk_op_blend_rows, esmk_op_stitch_contacts; esm_amd/windows.py)
+def window_rows(tokens, src_rows, starts, mask_offsets, mask_positions, Tw, head_tok=-1, tail_tok=-1, mask_idx=32):
+    """[n,Tw] int64 window copies: copy i, column c = ``tokens[src_rows[i], starts[i] + c - h]`` (h = 1 if ``head_tok`` >= 0;
+    row and column clamped into ``tokens``), column 0 = ``head_tok`` and column Tw - 1 = ``tail_tok`` where those are >= 0 (a
+    wrapped window; both negative: a raw token slice).  ``mask_positions[mask_offsets[i] : mask_offsets[i + 1]]`` are token
+    coordinates of the SOURCE row: an entry that lands on a body column of the copy becomes ``mask_idx``; one outside the
+    copy's range or on an overridden column masks nothing; a repeated one is harmless.  src_rows, starts int32 [n],
+    mask_offsets int32 [n + 1] (clamped to [0, total]; a descending pair is an empty list), mask_positions int32 [total]."""
+    _req_cuda(tokens, src_rows, starts, mask_offsets, mask_positions)
+    tokens = tokens.view(1, -1) if tokens.dim() == 1 else tokens
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2
+    for t in (src_rows, starts, mask_offsets, mask_positions):
+        assert t.dtype == torch.int32 and t.dim() == 1
+    n = src_rows.numel()
+    assert n >= 1 and starts.numel() == n and mask_offsets.numel() == n + 1
+    B, T = tokens.shape
+    total = mask_positions.numel()
+    if total == 0:  # nothing to mask anywhere; the entry still wants a pointer it will not read
+        mask_positions = torch.zeros((1,), dtype=torch.int32, device=tokens.device)
+    out = torch.empty((n, int(Tw)), dtype=torch.int64, device=tokens.device)
+    N.check(N.lib.esmk_op_window_rows(N.ptr(tokens), N.ptr(src_rows), N.ptr(starts), N.ptr(mask_offsets), N.ptr(mask_positions),
+                                      N.ptr(out), B, T, n, int(Tw), total, int(head_tok), int(tail_tok), int(mask_idx),
+                                      N.cur_stream()))
+    return out
+
+
+def blend_rows(x, offsets, src, weights):
+    """fp32 [n_out,E]: row r = ``(sum_k weights[k] * x[src[k]]) / sum_k weights[k]`` over k in ``offsets[r] : offsets[r + 1]``,
+    ascending, accumulated in fp32 by one lane per element (a fixed order: no atomics).  A list of one entry copies the row
+    (converted to fp32) exactly, an empty list gives zeros.  x [N,E] fp32 / fp16 / bf16, E % 4 == 0; offsets int32 [n_out + 1]
+    (clamped to [0, total]), src int32 [total] (clamped to [0, N)), weights fp32 [total], positive."""
+    _req_cuda(x, offsets, src, weights)
+    assert x.dim() == 2 and offsets.dtype == torch.int32 and offsets.dim() == 1 and offsets.numel() >= 2
+    assert src.dtype == torch.int32 and weights.dtype == torch.float32 and src.dim() == 1 and weights.numel() == src.numel()
+    Nr, E = x.shape
+    n_out = offsets.numel() - 1
+    total = src.numel()
+    if total == 0:  # every list is empty; the entry still wants pointers it will not read
+        src = torch.zeros((1,), dtype=torch.int32, device=x.device)
+        weights = torch.ones((1,), dtype=torch.float32, device=x.device)
+    out = torch.empty((n_out, E), dtype=torch.float32, device=x.device)
+    N.check(N.lib.esmk_op_blend_rows(N.ptr(x), N.dtype_code(x.dtype), N.ptr(offsets), N.ptr(src), N.ptr(weights), N.ptr(out), Nr,
+                                     E, n_out, total, N.cur_stream()))
+    return out
+
+
+def stitch_contacts(maps, starts, Lb, body_lo=0):
+    """fp32 [Lb,Lb]: entry (i, j) copied from the window of ``maps`` fp32 [n_w,R,R] that owns the pair — among the windows that
+    hold both residues (window w covers ``starts[w] - body_lo`` .. + R - 1) the one with the least |2 s + R - 1 - (i + j)|, a tie
+    going to the lower start; NaN where no window holds both.  starts int32 [n_w] on the device."""
+    _req_cuda(maps, starts)
+    assert maps.dtype == torch.float32 and maps.dim() == 3 and maps.shape[1] == maps.shape[2]
+    assert starts.dtype == torch.int32 and starts.numel() == maps.shape[0]
+    n_w, R, _ = maps.shape
+    out = torch.empty((int(Lb), int(Lb)), dtype=torch.float32, device=maps.device)
+    N.check(N.lib.esmk_op_stitch_contacts(N.ptr(maps), N.ptr(starts), N.ptr(out), n_w, R, int(Lb), int(body_lo), N.cur_stream()))
+    return out
+
+
 # ---- sampling (include/esmk.h: esmk_op_permute_positions, esmk_op_sample_rows[_ex], esmk_op_select_rows, esmk_op_commit_tokens)
 def _seed64(seed):
     seed = int(seed)

@@ -19,6 +19,11 @@ masked-marginal score of the ESM-1v paper: all of its positions masked in one fo
 over them (``esm_amd.scoring.score_variants``); wt-marginals sums the same terms from the wild-type table, pseudo-ppl scores
 the sequence with all substitutions made.  A table without the separator is scored exactly as before.
 
+``--window N`` (or ``--window max`` on ESM-1b / ESM-1v: the size of the position table) scores a protein LONGER than the window:
+every mutated site inside a model-sized window centred on it, a multi-mutant row in one window that holds all of its sites
+(``esm_amd.windows``).  The windows are fragments tokenised like the whole (<cls> / <eos> of their own); ``--no-wrap`` cuts raw
+token slices instead.  A sequence that fits is scored exactly as without the option.
+
 The MSA Transformer (``--msa-path``) is not served here: asking for it is an error that points to
 ``python -m esm_amd.predict_msa``, which scores a table with an MSA (``esm_amd.msa_scoring``).
 """
@@ -47,6 +52,12 @@ def create_parser():
                    help="(MSA Transformer only; not served here: use python -m esm_amd.predict_msa)")
     p.add_argument("--msa-samples", type=int, default=400, help="(MSA Transformer only)")
     p.add_argument("--nogpu", action="store_true", help="accepted for compatibility; the engine has no CPU path")
+    from .windows import window_arg
+
+    p.add_argument("--window", type=window_arg, default=None, metavar="{N,max}",
+                   help="tokens per window (special tokens included) for a sequence longer than the model's window; 'max': the "
+                        "size of the position table of ESM-1b / ESM-1v")
+    p.add_argument("--no-wrap", action="store_true", help="with --window: raw token slices instead of tokenised fragments")
     return p
 
 
@@ -68,7 +79,7 @@ def write_table(path, fields, rows):
             w.writerow([i] + [row.get(f, "") for f in fields])
 
 
-def score_table(model, alphabet, sequence, mutations, strategy, offset_idx=0, sep=":"):
+def score_table(model, alphabet, sequence, mutations, strategy, offset_idx=0, sep=":", window=None, wrap=True):
     """One score per mutation string.
 
     A table of single substitutions: wt-marginals / masked-marginals give log p(mutant) - log p(wild type) at the position,
@@ -78,15 +89,18 @@ def score_table(model, alphabet, sequence, mutations, strategy, offset_idx=0, se
     ``compute_pppl`` reads it (module docstring).
 
     A table in which some row joins several substitutions with ``sep`` ('A42G:K50R') is scored, every row of it, by
-    ``esm_amd.scoring.score_variants``: joint masks, summed marginals."""
+    ``esm_amd.scoring.score_variants``: joint masks, summed marginals.
+
+    ``window`` / ``wrap``: a sequence longer than the window is scored inside model-sized windows (``esm_amd.windows``)."""
     import torch
 
     from . import scoring
 
     scoring._refuse_msa(model)
     mutations = list(mutations)
+    win = {} if window is None else dict(window=window, wrap=wrap)
     if sep and any(sep in mutation for mutation in mutations):
-        return scoring.score_variants(model, alphabet, sequence, mutations, strategy, offset_idx, sep)
+        return scoring.score_variants(model, alphabet, sequence, mutations, strategy, offset_idx, sep, **win)
     convert = alphabet.get_batch_converter()
     if strategy == "pseudo-ppl":
         mutated = []
@@ -99,12 +113,12 @@ def score_table(model, alphabet, sequence, mutations, strategy, offset_idx=0, se
         per_call = 256  # mutants per call; their masked copies are chunked to the GPU's size inside
         for lo in range(0, len(mutated), per_call):
             _, _, tokens = convert(mutated[lo:lo + per_call])
-            pll = model.pseudo_log_likelihood(tokens, positions=range(1, len(sequence) - 1))
+            pll = model.pseudo_log_likelihood(tokens, positions=range(1, len(sequence) - 1), **win)
             scores += pll.tolist()
         return scores
     _, _, tokens = convert([("protein1", sequence)])
     with torch.no_grad():
-        table = model.wt_marginals(tokens) if strategy == "wt-marginals" else model.masked_marginals(tokens)
+        table = model.wt_marginals(tokens, **win) if strategy == "wt-marginals" else model.masked_marginals(tokens, **win)
     return scoring.score_mutations(table.cpu(), sequence, mutations, alphabet, offset_idx)
 
 
@@ -130,7 +144,7 @@ def main(argv=None):
             raise SystemExit("esm_amd.predict: no GPU: the engine has no CPU path")
         model = model.eval().cuda()
         scores = score_table(model, alphabet, args.sequence, mutations, args.scoring_strategy, args.offset_idx,
-                             args.mutation_sep)
+                             args.mutation_sep, window=args.window, wrap=not args.no_wrap)
         for row, s in zip(rows, scores):
             row[location] = repr(float(s))
         fields.append(location)

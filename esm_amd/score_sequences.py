@@ -16,6 +16,10 @@ wt-marginals  ``pll`` is the sum of the log-probabilities of the true residues i
 The sequences of such a file differ in length, so the masked copies run token-packed (``varlen=True``: no compute on padding,
 sums in a fixed order).  ``--no-varlen`` runs the padded path: the same table of log-probabilities bit for bit, so the same
 file for wt-marginals; for pseudo-ppl the padded sum goes through atomics in no fixed order and may differ in the last digits.
+``--window N`` (``--window max`` on ESM-1b / ESM-1v) scores sequences LONGER than the window inside model-sized windows
+(``esm_amd.windows``: every residue in the window centred on it for pseudo-ppl, overlapping windows with every row from the window
+it is most central in for wt-marginals); ``--no-wrap`` cuts raw token slices instead of tokenised fragments.  Shorter sequences are
+scored as without the option.
 The CSV is read with the ``csv`` module; labels come from ``--label-col`` or are the 0-based row numbers.
 """
 import argparse
@@ -40,6 +44,12 @@ def create_parser():
     p.add_argument("--output", type=pathlib.Path, required=True, help="CSV file to write: label, length, pll, pseudo_perplexity")
     p.add_argument("--strategy", type=str, default="pseudo-ppl", choices=STRATEGIES)
     p.add_argument("--no-varlen", action="store_true", help="run the padded path instead of the token-packed one")
+    from .windows import window_arg
+
+    p.add_argument("--window", type=window_arg, default=None, metavar="{N,max}",
+                   help="tokens per window (special tokens included) for sequences longer than the model's window; 'max': the "
+                        "size of the position table of ESM-1b / ESM-1v")
+    p.add_argument("--no-wrap", action="store_true", help="with --window: raw token slices instead of tokenised fragments")
     return p
 
 
@@ -64,10 +74,11 @@ def read_records(args, parser):
     return [(row[args.label_col] if args.label_col else str(i), row[args.sequence_col].strip()) for i, row in enumerate(rows)]
 
 
-def score_records(model, alphabet, records, strategy="pseudo-ppl", varlen=True):
+def score_records(model, alphabet, records, strategy="pseudo-ppl", varlen=True, window=None, wrap=True):
     """One float per record: the pseudo-log-likelihood (pseudo-ppl) or the sum of the unmasked log-probabilities of the true
     residues (wt-marginals) of every sequence, ``PER_CALL`` sequences per call.  A sequence longer than an ESM-1b model's
-    positional limit raises the ValueError of ``esm_amd.scoring``."""
+    positional limit raises the ValueError of ``esm_amd.scoring`` unless ``window`` is given: then it is scored inside
+    model-sized windows (``esm_amd.windows``)."""
     import torch
 
     from . import ops, scoring
@@ -75,13 +86,14 @@ def score_records(model, alphabet, records, strategy="pseudo-ppl", varlen=True):
     if strategy not in STRATEGIES:
         raise ValueError(f"unknown scoring strategy {strategy!r}")
     convert = alphabet.get_batch_converter()
+    win = {} if window is None else dict(window=window, wrap=wrap)
     scores = []
     for lo in range(0, len(records), PER_CALL):
         _, _, tokens = convert(records[lo:lo + PER_CALL])
         if strategy == "pseudo-ppl":
-            scores += model.pseudo_log_likelihood(tokens, varlen=varlen).tolist()
+            scores += model.pseudo_log_likelihood(tokens, varlen=varlen, **win).tolist()
             continue
-        table = model.wt_marginals(tokens, varlen=varlen)
+        table = model.wt_marginals(tokens, varlen=varlen, **win)
         tok = tokens.to(table.device)
         want = tok.ne(model.padding_idx)  # the residues: no <cls>, no <eos>, no <pad>
         if model.prepend_bos:
@@ -124,7 +136,8 @@ def main(argv=None):
         raise SystemExit("esm_amd.score_sequences: no GPU: the engine has no CPU path")
     model = model.eval().cuda()
     with torch.no_grad():
-        scores = score_records(model, alphabet, records, args.strategy, varlen=not args.no_varlen)
+        scores = score_records(model, alphabet, records, args.strategy, varlen=not args.no_varlen, window=args.window,
+                               wrap=not args.no_wrap)
     write_scores(args.output, records, scores)
     return 0
 

@@ -21,6 +21,11 @@ wt-marginals over a FASTA file) can run token-packed: ``varlen=True`` lays the m
 that sequence alone: the tables are those of the padded path bit for bit, and the pseudo-log-likelihood is summed in a fixed
 order (``esmk_op_sum_target_rows``).  ``python -m esm_amd.score_sequences`` scores a FASTA or CSV file that way.
 
+A protein LONGER than the model's window (``window=N`` or ``window="max"``) is scored inside model-sized windows: every site in
+the window copy centred on it, built on the device (``esmk_op_window_rows``), the rows again those of the existing call on the
+window alone (``esm_amd.windows``, which also stitches embeddings and contact maps: ``forward_windows``).  Without ``window``
+every call is what it was, the length check of ESM-1b / ESM-1v included.
+
 The functions are also methods of ``ESM2`` / ``ProteinBertModel`` (``model.masked_marginals(tokens)`` ...).  They refuse the
 MSA Transformer (``NotImplementedError``): one MSA plus a query row is another argument shape, served by
 ``esm_amd.msa_scoring`` under names of its own.
@@ -50,7 +55,8 @@ def _device_weight(model):
     return w
 
 
-def _device_tokens(model, tokens):
+def _device_tokens(model, tokens, window=None):
+    """``window`` (resolved: tokens per window): the length check applies to the window copies, not to the batch's width."""
     _refuse_msa(model)
     if tokens.ndim == 1:
         tokens = tokens.unsqueeze(0)
@@ -58,8 +64,9 @@ def _device_tokens(model, tokens):
     w = _device_weight(model)
     pos_table = getattr(model, "embed_positions", None)
     max_positions = getattr(pos_table, "max_positions", None)
-    if max_positions is not None and tokens.size(1) > max_positions:  # ESM-1b / ESM-1v, as ProteinBertModel.forward
-        raise ValueError(f"Sequence length {tokens.size(1)} above maximum  sequence length of {max_positions}")
+    width = tokens.size(1) if window is None else window
+    if max_positions is not None and width > max_positions:  # ESM-1b / ESM-1v, as ProteinBertModel.forward
+        raise ValueError(f"Sequence length {width} above maximum  sequence length of {max_positions}")
     return tokens.to(device=w.device, dtype=torch.int64).contiguous()
 
 
@@ -239,7 +246,7 @@ def _masked_chunks(model, tokens, positions, chunk, residues_only, varlen=False,
 
 
 @torch.no_grad()
-def masked_marginals(model, tokens, positions=None, chunk=None, varlen=False, chunk_rows=None):
+def masked_marginals(model, tokens, positions=None, chunk=None, varlen=False, chunk_rows=None, window=None, wrap=True):
     """fp32 ``[B, T, V]``: row (b, i) is ``log_softmax`` of the logits at i from the forward in which token (b, i) alone is
     replaced by <mask> — ``all_token_probs`` of the reference's masked-marginals strategy (predict.py:205-215) for every
     sequence of the batch.
@@ -253,8 +260,18 @@ def masked_marginals(model, tokens, positions=None, chunk=None, varlen=False, ch
                different lengths.  The table is the same, bit for bit.  ``chunk_rows``: rows of a packed row space (default
                65536); ``chunk`` is then not used.  ESM-1 models and the f16x3 precision mode have no token-packed forward:
                the padded path runs, as ``forward_varlen`` falls back to ``forward``.
+    window     None: off.  An int (tokens per window, special tokens included) or "max" (ESM-1b / ESM-1v: the size of the
+               position table): a sequence LONGER than the window is scored position by position inside the window copy
+               centred on the position (``esm_amd.windows``: ``esmk_op_window_rows``; ``wrap``: the copies are tokenised
+               fragments with <cls> / <eos> of their own, or raw token slices) — the row the existing call gives that
+               window alone, bit for bit.  A sequence that fits takes the unwindowed path.  With ``varlen=True`` the short
+               sequences go packed, the long ones through the padded window path.
     Rows that were not asked for are zero.  ``tokens`` may live on the CPU or the device; the result is on the model's device."""
     _check_chunk_rows(varlen, chunk_rows)
+    if window is not None:
+        from . import windows
+
+        return windows.masked_marginals(model, tokens, positions, chunk, window, wrap, varlen, chunk_rows)
     tok = _device_tokens(model, tokens)
     out = torch.zeros(tuple(tok.shape) + (model.alphabet_size,), dtype=torch.float32, device=tok.device)
     for src, pos, lp in _masked_chunks(model, tok, positions, chunk, residues_only=False, varlen=varlen, chunk_rows=chunk_rows):
@@ -263,11 +280,17 @@ def masked_marginals(model, tokens, positions=None, chunk=None, varlen=False, ch
 
 
 @torch.no_grad()
-def wt_marginals(model, tokens, varlen=False, chunk_rows=None):
+def wt_marginals(model, tokens, varlen=False, chunk_rows=None, window=None, wrap=True):
     """fp32 ``[B, T, V]``: ``log_softmax(model(tokens)["logits"], -1)`` on the non-pad rows (the wt-marginals strategy,
     predict.py:192-194), zero on <pad> rows: one forward per batch that fills the GPU, the head on the real rows only.
-    ``varlen`` / ``chunk_rows``: token-packed, as in ``masked_marginals``; the same table bit for bit."""
+    ``varlen`` / ``chunk_rows``: token-packed, as in ``masked_marginals``; the same table bit for bit.
+    ``window`` / ``wrap``: a sequence longer than the window runs as overlapping grid windows (stride R // 2) and every row is
+    taken from the window that owns it — the one it is most central in (``esm_amd.windows``)."""
     _check_chunk_rows(varlen, chunk_rows)
+    if window is not None:
+        from . import windows
+
+        return windows.wt_marginals(model, tokens, window, wrap, varlen=varlen, chunk_rows=chunk_rows)
     tok = _device_tokens(model, tokens)
     B, T = tok.shape
     out = torch.zeros((B, T, model.alphabet_size), dtype=torch.float32, device=tok.device)
@@ -293,7 +316,7 @@ def wt_marginals(model, tokens, varlen=False, chunk_rows=None):
 
 
 @torch.no_grad()
-def pseudo_log_likelihood(model, tokens, positions=None, chunk=None, varlen=False, chunk_rows=None):
+def pseudo_log_likelihood(model, tokens, positions=None, chunk=None, varlen=False, chunk_rows=None, window=None, wrap=True):
     """fp64 ``[B]``: the sum over the scored positions of the masked-marginal log-probability of the TRUE token — the
     pseudo-log-likelihood of every sequence of the batch.
 
@@ -308,10 +331,15 @@ def pseudo_log_likelihood(model, tokens, positions=None, chunk=None, varlen=Fals
     ``varlen`` / ``chunk_rows``: token-packed, as in ``masked_marginals``.  The sum then runs through
     ``esmk_op_sum_target_rows``: the rows of a sequence in ascending order of position, added by one lane — the sequential
     fp64 sum of the true-token column of ``masked_marginals``, exactly, where the padded path's ``index_add_`` adds through
-    atomics in no fixed order."""
+    atomics in no fixed order.
+    ``window`` / ``wrap``: the windowed masked marginals (``masked_marginals``), summed through ``esmk_op_sum_target_rows`` too."""
     from . import ops
 
     _check_chunk_rows(varlen, chunk_rows)
+    if window is not None:
+        from . import windows
+
+        return windows.pseudo_log_likelihood(model, tokens, positions, chunk, window, wrap, varlen, chunk_rows)
     tok = _device_tokens(model, tokens)
     if varlen and model._packs():
         (src, pos, lp), = _masked_chunks(model, tok, positions, chunk, residues_only=True, varlen=True, chunk_rows=chunk_rows)
@@ -327,8 +355,38 @@ def pseudo_log_likelihood(model, tokens, positions=None, chunk=None, varlen=Fals
     return out
 
 
+def _parse_sets(tok, position_sets, src):
+    """(sets, src): every position set sorted and without repeats, and the sequence of every set as a list of ints."""
+    B = tok.shape[0]
+    sets = [sorted({int(p) for p in ps}) for ps in position_sets]
+    if src is None:
+        if B != 1:
+            raise ValueError(f"masked_joint: tokens hold {B} sequences: say which one every position set refers to (src)")
+        src = [0] * len(sets)
+    src = [int(b) for b in (src.tolist() if torch.is_tensor(src) else src)]
+    if len(src) != len(sets):
+        raise ValueError(f"{len(src)} source sequences for {len(sets)} position sets")
+    return sets, src
+
+
+def _validate_sets(model, tok, sets, src):
+    B, T = tok.shape
+    real = tok.ne(model.padding_idx).cpu()
+    for s, (b, ps) in enumerate(zip(src, sets)):
+        if not 0 <= b < B:
+            raise ValueError(f"position set {s}: sequence {b} is outside [0, {B})")
+        if not ps:
+            raise ValueError(f"position set {s} of sequence {b} is empty: there is nothing to score")
+        for p in ps:
+            if not 0 <= p < T:
+                raise ValueError(f"position {p} of sequence {b} is outside [0, {T})")
+            if not bool(real[b, p]):
+                raise ValueError(f"position {p} of sequence {b} is a <pad> token: there is nothing to score")
+
+
 @torch.no_grad()
-def masked_joint(model, tokens, position_sets, src=None, chunk=None, return_logits=False, varlen=False, chunk_rows=None):
+def masked_joint(model, tokens, position_sets, src=None, chunk=None, return_logits=False, varlen=False, chunk_rows=None,
+                 window=None, wrap=True):
     """Joint masks: for every set s of ``position_sets`` (an iterable of token positions of sequence ``src[s]``; ``src`` None:
     sequence 0, and then B must be 1) ONE forward with all positions of the set replaced by <mask>, and the log-probabilities
     at those positions.  Returns ``(offsets, pos, logprobs)``:
@@ -341,36 +399,26 @@ def masked_joint(model, tokens, position_sets, src=None, chunk=None, return_logi
     An empty set, a position outside [0, T) or on a <pad> token raises ValueError.  ``chunk``: masked copies (sets) per
     forward call; default what fills the GPU (about 65536 tokens).  The position lists are uploaded once for all chunks.
     ``varlen`` / ``chunk_rows``: token-packed, as in ``masked_marginals`` (sets of sequences of different lengths); the same
-    rows bit for bit."""
+    rows bit for bit.
+    ``window`` / ``wrap``: a set of a sequence longer than the window is masked in ONE window copy, placed so that the set sits
+    in its middle (``esm_amd.windows.set_start``); a set that spans as many tokens as a window has body tokens, or more, does
+    not fit and raises ValueError."""
     from . import ops
 
     _check_chunk_rows(varlen, chunk_rows)
+    if window is not None:
+        from . import windows
+
+        return windows.masked_joint(model, tokens, position_sets, src, chunk, return_logits, window, wrap, varlen, chunk_rows)
     tok = _device_tokens(model, tokens)
     B, T = tok.shape
     dev = tok.device
-    sets = [sorted({int(p) for p in ps}) for ps in position_sets]
-    if src is None:
-        if B != 1:
-            raise ValueError(f"masked_joint: tokens hold {B} sequences: say which one every position set refers to (src)")
-        src = [0] * len(sets)
-    src = [int(b) for b in (src.tolist() if torch.is_tensor(src) else src)]
-    if len(src) != len(sets):
-        raise ValueError(f"{len(src)} source sequences for {len(sets)} position sets")
+    sets, src = _parse_sets(tok, position_sets, src)
     if chunk is None:
         chunk = max(1, CHUNK_TOKENS // T)
     if chunk <= 0:
         raise ValueError("chunk must be positive")
-    real = tok.ne(model.padding_idx).cpu()
-    for s, (b, ps) in enumerate(zip(src, sets)):
-        if not 0 <= b < B:
-            raise ValueError(f"position set {s}: sequence {b} is outside [0, {B})")
-        if not ps:
-            raise ValueError(f"position set {s} of sequence {b} is empty: there is nothing to score")
-        for p in ps:
-            if not 0 <= p < T:
-                raise ValueError(f"position {p} of sequence {b} is outside [0, {T})")
-            if not bool(real[b, p]):
-                raise ValueError(f"position {p} of sequence {b} is a <pad> token: there is nothing to score")
+    _validate_sets(model, tok, sets, src)
     V = model.alphabet_size
     counts = torch.tensor([len(ps) for ps in sets], dtype=torch.int64)
     offsets = torch.zeros((len(sets) + 1,), dtype=torch.int64)
@@ -462,7 +510,8 @@ def _checked_variant(variant, sequence, offset_idx, sep):
 
 
 @torch.no_grad()
-def score_variants(model, alphabet, sequence, variants, strategy="masked-marginals", offset_idx=0, sep=":", chunk=None):
+def score_variants(model, alphabet, sequence, variants, strategy="masked-marginals", offset_idx=0, sep=":", chunk=None, window=None,
+                   wrap=True):
     """Zero-shot scores of variants with one OR MORE substitutions ('A42G', 'A42G:K50R'; positions ``offset_idx``-based,
     joined by ``sep``) of ``sequence``: a list of Python floats, one per variant.
 
@@ -476,10 +525,13 @@ def score_variants(model, alphabet, sequence, variants, strategy="masked-margina
     gives a single substitution, the terms of a variant are added in fp64 in ascending order of position by one lane — a
     single mutant's score is the float ``score_mutations`` returns, and the order in which a variant lists its substitutions
     does not matter.  Raises ValueError where a listed wild type does not match the sequence, a position is outside it or
-    named twice, or a substitution is not of the form 'A42G'."""
+    named twice, or a substitution is not of the form 'A42G'.
+    ``window`` / ``wrap``: for a sequence longer than the window, as in ``masked_joint`` / ``wt_marginals`` /
+    ``pseudo_log_likelihood``; a variant whose sites do not fit into one window raises ValueError."""
     from . import ops
 
     _refuse_msa(model)
+    win = {} if window is None else dict(window=window, wrap=wrap)
     if strategy not in ("masked-marginals", "wt-marginals", "pseudo-ppl"):
         raise ValueError(f"unknown scoring strategy {strategy!r}")
     parsed = [_checked_variant(v, sequence, offset_idx, sep) for v in variants]
@@ -495,10 +547,15 @@ def score_variants(model, alphabet, sequence, variants, strategy="masked-margina
         per_call = 256  # mutants per call; their masked copies are chunked to the GPU's size inside
         for lo in range(0, len(mutated), per_call):
             _, _, tokens = convert(mutated[lo:lo + per_call])
-            scores += pseudo_log_likelihood(model, tokens, positions=range(1, len(sequence) - 1), chunk=chunk).tolist()
+            scores += pseudo_log_likelihood(model, tokens, positions=range(1, len(sequence) - 1), chunk=chunk, **win).tolist()
         return scores
     _, _, tokens = convert([("protein1", sequence)])
-    tok = _device_tokens(model, tokens)
+    if window is not None:
+        from .windows import resolve_window
+
+        tok = _device_tokens(model, tokens, window=resolve_window(model, window))
+    else:
+        tok = _device_tokens(model, tokens)
     if not parsed:
         return []
     shift = 1 if alphabet.prepend_bos else 0  # token position of residue idx: behind <cls>
@@ -511,10 +568,10 @@ def score_variants(model, alphabet, sequence, variants, strategy="masked-margina
                 first_row[key] = n_rows
                 sets.append(key)
                 n_rows += len(key)
-        _, _, table = masked_joint(model, tok, sets, chunk=chunk)
+        _, _, table = masked_joint(model, tok, sets, chunk=chunk, **win)
         rows = [first_row[tuple(shift + idx for _, idx, _ in parts)] + j for parts in parsed for j in range(len(parts))]
     else:
-        table = wt_marginals(model, tok)[0]
+        table = wt_marginals(model, tok, **win)[0]
         rows = [shift + idx for parts in parsed for _, idx, _ in parts]
     dev = tok.device
     lp = table.index_select(0, torch.tensor(rows, dtype=torch.int64).to(dev))  # one row per term, variant-major

@@ -722,6 +722,35 @@ int esmk_op_mask_rows_packed(const int64_t* tokens_dev, const int32_t* src_row_d
 int esmk_op_sum_target_rows(const float* logprobs_dev, const int32_t* target_dev, const int32_t* off_dev, double* out_dev,
                             int n_rows, int n_seq, int V, void* stream);
 
+/* Proteins longer than the model's window (esm_amd/windows.py): window copies built on the device, per-window outputs stitched
+ * into full-length outputs.  A window of Tw tokens starting at source token s covers the source tokens s .. s + R - 1; wrapped
+ * (a fragment tokenised as the alphabet tokenises the substring) it carries <cls> in column 0 and / or <eos> in column Tw - 1
+ * and R = Tw minus those; raw it is a token slice, R = Tw.
+ * esmk_op_window_rows: out int64 [n,Tw]; copy i, column c = tokens[clamp(src_row[i]), clamp(start[i] + c - h)] (tokens int64
+ *   [B,T]; src_row, start int32 [n]; h = 1 if head_tok >= 0 else 0; the row is clamped to [0,B), the column to [0,T)); column
+ *   0 is head_tok when head_tok >= 0 and column Tw - 1 is tail_tok when tail_tok >= 0.  mask_off int32 [n+1], mask_pos int32
+ *   [total]: the entries mask_pos[mask_off[i] : mask_off[i+1]] are token coordinates of the SOURCE row; entry p becomes mask_idx at
+ *   column p - start[i] + h where that is a body column of the copy (h <= column < Tw - (tail_tok >= 0)); an entry outside the
+ *   copy's range or on an overridden column masks nothing, a repeated entry is harmless.  The offsets are clamped to [0,total],
+ *   a pair with hi < lo is an empty list, as in esmk_op_mask_rows_multi.
+ * esmk_op_blend_rows: out fp32 [n_out,E], out[r] = (sum_k w[k] x[src[k], :]) / sum_k w[k] over k in [off[r], off[r+1]), k
+ *   ascending; x [N,E] of dtype code x_dtype (ESMK_F32 / ESMK_F16 / ESMK_BF16, as esmk_op_masked_row_mean), off int32 [n_out+1],
+ *   src int32 [total], w fp32 [total] (positive).  Every element is accumulated in fp32 in list order by one lane (no atomics):
+ *   the result does not depend on the launch geometry.  A list of ONE entry copies the row, converted to fp32, exactly (the
+ *   owner stitch: w is not read); an empty list gives zeros.  src is clamped to [0,N), the offsets to [0,total].
+ * esmk_op_stitch_contacts: out fp32 [Lb,Lb]; maps fp32 [n_w,R,R], window w covering the residues s_w .. s_w + R - 1 with
+ *   s_w = start[w] - body_lo (start int32 [n_w], device data).  out[i,j] = maps[w, i - s_w, j - s_w] of the window that holds both
+ *   residues with the least |2 s_w + R - 1 - (i + j)| (integers), a tie going to the lower start; NaN where no window holds both.
+ * Refused before any HIP call: null pointers, B, T, n, Tw, N, n_out, n_w, R or Lb <= 0, total < 0, E <= 0 or E % 4 != 0, an
+ * unknown x_dtype, B*T or n*Tw > 2^24. */
+int esmk_op_window_rows(const int64_t* tokens_dev, const int32_t* src_row_dev, const int32_t* start_dev,
+                        const int32_t* mask_off_dev, const int32_t* mask_pos_dev, int64_t* out_dev, int B, int T, int n, int Tw,
+                        int total, int head_tok, int tail_tok, int mask_idx, void* stream);
+int esmk_op_blend_rows(const void* x_dev, int x_dtype, const int32_t* off_dev, const int32_t* src_dev, const float* w_dev,
+                       float* out_dev, int N, int E, int n_out, int total, void* stream);
+int esmk_op_stitch_contacts(const float* maps_dev, const int32_t* start_dev, float* out_dev, int n_w, int R, int Lb, int body_lo,
+                            void* stream);
+
 /* Drawing sequences from the model (esm_amd/sampling.py: Gibbs sweeps, mask in-painting).  A sampling step is
  * esmk_op_mask_rows_multi -> esmk_forward_rows -> esmk_op_sample_rows -> esmk_op_commit_tokens on one stream; the host reads
  * nothing in between.  Confidence-ordered unmasking is esmk_forward_rows on every remaining <mask> row -> esmk_op_sample_rows_ex
