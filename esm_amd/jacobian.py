@@ -29,7 +29,8 @@ One sequence per call: batches of sequences and token-packed copies of several s
 import torch
 
 from .sampling import STANDARD_RESIDUES, _residue_positions, allowed_mask
-from .scoring import CHUNK_TOKENS, _device_tokens, _refuse_msa, forward_rows
+from .copies import copies_per_call
+from .scoring import _device_tokens, _refuse_msa, forward_rows
 
 MAX_CANDIDATES = 32  # esmk_op_jacobian_*: nA <= 32
 
@@ -85,13 +86,8 @@ def categorical_jacobian(model, tokens, allowed=None, chunk=None, center=False, 
     if L * L * nA * nA * 4 > max_bytes:
         raise ValueError(f"the categorical Jacobian of {L} residues and {nA} candidates holds {L * L * nA * nA * 4} bytes, above "
                          f"max_bytes = {max_bytes}")
-    if chunk is None:
-        chunk = max(1, CHUNK_TOKENS // T)
-    chunk = int(chunk)
-    if chunk <= 0:
-        raise ValueError("chunk must be positive")
     n = L * nA
-    chunk = min(chunk, n)
+    chunk = min(copies_per_call(chunk if chunk is None else int(chunk), T), n)
     # one upload for all chunks: copy c = i * nA + a substitutes cols[a] at positions[i]; the chunks are slices of these
     pos32 = torch.tensor(positions, dtype=torch.int32).to(dev)
     cols32 = torch.tensor(cols, dtype=torch.int32).to(dev)

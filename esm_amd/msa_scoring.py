@@ -19,7 +19,8 @@ offered for MSAs.
 """
 import torch
 
-from .scoring import CHUNK_TOKENS, _checked_variant
+from .copies import Layout, copies_per_call, even_chunks, local_rows, run_copies, set_offsets
+from .scoring import _checked_variant
 
 STRATEGIES = ("masked-marginals", "wt-marginals")
 
@@ -108,10 +109,7 @@ def msa_masked_joint(model, tokens, position_sets, row=0, chunk=None, return_log
     R, C = tok.shape
     row = _check_row(tok, row)
     sets = [sorted({int(p) for p in ps}) for ps in position_sets]
-    if chunk is None:
-        chunk = max(1, CHUNK_TOKENS // (R * C))
-    if chunk <= 0:
-        raise ValueError("chunk must be positive")
+    chunk = copies_per_call(chunk, R * C)
     tok_row = tok[row].cpu()
     for s, ps in enumerate(sets):
         if not ps:
@@ -119,33 +117,22 @@ def msa_masked_joint(model, tokens, position_sets, row=0, chunk=None, return_log
         _check_positions(model, tok_row, row, ps)
     tok = _to_device(model, tok)
     dev = tok.device
-    V = model.alphabet_size
-    counts = torch.tensor([len(ps) for ps in sets], dtype=torch.int64)
-    offsets = torch.zeros((len(sets) + 1,), dtype=torch.int64)
-    offsets[1:] = counts.cumsum(0)
-    pos = torch.tensor([p for ps in sets for p in ps], dtype=torch.int64)
-    if not sets:
-        empty = torch.empty((0, V), dtype=torch.float32, device=dev)
-        return (offsets, pos.to(dev), empty) + ((empty.clone(),) if return_logits else ())
+    offsets, pos = set_offsets(sets)
     # one upload for all chunks.  The MSA is one "sequence" of R * C tokens to the mask kernel: cell (row, c) is position
     # row * C + c of the [1, R * C] view, and a chunk of masked copies comes back as [n, R * C] = [n, R, C]
     flat = tok.view(1, R * C)
     pos_d = pos.to(dev)
     cell32 = (pos_d + row * C).to(torch.int32)
     off32 = offsets.to(device=dev, dtype=torch.int32)
-    copy32 = torch.repeat_interleave(torch.arange(len(sets), dtype=torch.int32), counts).to(dev)  # the set of every row
-    lps, logits = [], []
-    for lo in range(0, len(sets), chunk):
-        hi = min(lo + chunk, len(sets))
-        masked = ops.mask_rows_multi(flat, off32[lo:hi + 1], cell32, None, model.mask_idx).view(hi - lo, R, C)
-        r0, r1 = int(offsets[lo]), int(offsets[hi])
-        sel = (copy32[r0:r1] - lo) * (R * C) + cell32[r0:r1]
-        got = msa_forward_rows(model, masked, sel, return_logits=return_logits)
-        lps.append(got[0] if return_logits else got)
-        if return_logits:
-            logits.append(got[1])
-    out = (offsets, pos_d, lps[0] if len(lps) == 1 else torch.cat(lps))
-    return out + ((logits[0] if len(logits) == 1 else torch.cat(logits),) if return_logits else ())
+
+    def build(lo, hi):
+        return ops.mask_rows_multi(flat, off32[lo:hi + 1], cell32, None, model.mask_idx).view(hi - lo, R, C)
+
+    layout = Layout(even_chunks(len(sets), chunk), build,
+                    lambda copies, sel, return_logits: msa_forward_rows(model, copies, sel, return_logits))
+    got = run_copies(layout, len(sets), offsets, local_rows(offsets, chunk, R * C, pos + row * C, dev), model.alphabet_size, dev,
+                     return_logits)
+    return (offsets, pos_d) + (got if return_logits else (got,))
 
 
 def _columns(model, tok, row, positions):

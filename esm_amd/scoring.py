@@ -26,6 +26,10 @@ the window copy centred on it, built on the device (``esmk_op_window_rows``), th
 window alone (``esm_amd.windows``, which also stitches embeddings and contact maps: ``forward_windows``).  Without ``window``
 every call is what it was, the length check of ESM-1b / ESM-1v included.
 
+Padded, token-packed, windowed and MSA copies all run through one loop, ``esm_amd.copies.run_copies``: a path uploads its
+lists once and says how its copies fall into chunks, how a chunk is built and how it is run (``_padded_copies``,
+``_packed_copies``, ``windows._run_copies``, ``msa_scoring.msa_masked_joint``).
+
 The functions are also methods of ``ESM2`` / ``ProteinBertModel`` (``model.masked_marginals(tokens)`` ...).  They refuse the
 MSA Transformer (``NotImplementedError``): one MSA plus a query row is another argument shape, served by
 ``esm_amd.msa_scoring`` under names of its own.
@@ -34,7 +38,7 @@ import numbers
 
 import torch
 
-CHUNK_TOKENS = 65536  # tokens per forward call that fill the GPU (the batch budget of esm_amd.extract)
+from .copies import CHUNK_TOKENS, Layout, copies_per_call, even_chunks, local_rows, run_copies, set_offsets
 
 
 def _refuse_msa(model):
@@ -151,32 +155,44 @@ def _packed_copies(model, tok, lengths, src, mask_off, mask_pos, sel_off, sel_po
     from . import ops
 
     dev = tok.device
-    V = model.alphabet_size
-    n = src.numel()
-    if n == 0 or sel_pos.numel() == 0:
-        empty = torch.empty((0, V), dtype=torch.float32, device=dev)
-        return (empty, empty.clone()) if return_logits else empty
     copy_len = lengths[src]
-    chunks = plan_packed_chunks(copy_len.tolist(), CHUNK_TOKENS if chunk_rows is None else int(chunk_rows))
+    budget = CHUNK_TOKENS if chunk_rows is None else int(chunk_rows)
+    chunks = plan_packed_chunks(copy_len.tolist(), budget) if src.numel() else []  # no copies: nothing is planned or refused
+    rows_of = {lo: rows for lo, _, _, rows in chunks}
     start = torch.tensor([s for _, _, starts, _ in chunks for s in starts], dtype=torch.int64)
     seg_host = torch.stack([start, copy_len], dim=1).to(torch.int32).contiguous()
-    sel_count = sel_off[1:] - sel_off[:-1]
-    sel_rows = torch.repeat_interleave(start, sel_count) + sel_pos  # chunk-local flat rows
+    sel_rows = torch.repeat_interleave(start, sel_off[1:] - sel_off[:-1]) + sel_pos  # chunk-local flat rows
     src32, start32, len32 = (t.to(torch.int32).to(dev) for t in (src, start, copy_len))
     off32, pos32, sel32 = (t.to(torch.int32).to(dev) for t in (mask_off, mask_pos, sel_rows))
-    lps, logits = [], []
-    for lo, hi, _, rows in chunks:
-        r0, r1 = int(sel_off[lo]), int(sel_off[hi])
-        if r1 == r0:
-            continue
-        flat = ops.mask_rows_packed(tok, src32[lo:hi], start32[lo:hi], len32[lo:hi], off32[lo:hi + 1], pos32, rows,
+
+    def build(lo, hi):  # the row space of the chunk and the host slice of its segment table
+        flat = ops.mask_rows_packed(tok, src32[lo:hi], start32[lo:hi], len32[lo:hi], off32[lo:hi + 1], pos32, rows_of[lo],
                                     model.mask_idx, model.padding_idx)
-        got = forward_rows_packed(model, flat, seg_host[lo:hi], sel32[r0:r1], return_logits=return_logits)
-        lps.append(got[0] if return_logits else got)
-        if return_logits:
-            logits.append(got[1])
-    lp = lps[0] if len(lps) == 1 else torch.cat(lps)
-    return (lp, logits[0] if len(logits) == 1 else torch.cat(logits)) if return_logits else lp
+        return flat, seg_host[lo:hi]
+
+    layout = Layout(lambda: [(lo, hi) for lo, hi, _, _ in chunks], build,
+                    lambda copies, sel, return_logits: forward_rows_packed(model, *copies, sel, return_logits=return_logits))
+    return run_copies(layout, src.numel(), sel_off, sel32, model.alphabet_size, dev, return_logits)
+
+
+def _padded_copies(model, tok, src32, pos32, off32, sel_off, sel_pos, chunk, return_logits=False):
+    """Padded masked copies: copy i is sequence ``src32[i]`` of ``tok`` with position ``pos32[i]`` (``off32`` None) or the
+    positions ``pos32[off32[i] : off32[i + 1]]`` replaced by <mask>; the rows wanted from it are the positions
+    ``sel_pos[sel_off[i] : sel_off[i + 1]]``.  int32 vectors on the device, ``sel_off`` / ``sel_pos`` int64 on the host;
+    ``chunk`` copies per call.  Returns what ``_packed_copies`` returns."""
+    from . import ops
+
+    T = tok.shape[1]
+
+    def build(lo, hi):
+        if off32 is None:
+            return ops.mask_rows(tok, pos32[lo:hi].contiguous(), src32[lo:hi].contiguous(), model.mask_idx)
+        return ops.mask_rows_multi(tok, off32[lo:hi + 1], pos32, src32[lo:hi], model.mask_idx)
+
+    n = src32.numel()
+    layout = Layout(even_chunks(n, chunk), build, lambda copies, sel, return_logits: forward_rows(model, copies, sel, return_logits))
+    return run_copies(layout, n, sel_off, local_rows(sel_off, chunk, T, sel_pos, tok.device), model.alphabet_size, tok.device,
+                      return_logits)
 
 
 def _position_rows(model, tok_cpu, positions, residues_only):
@@ -217,32 +233,20 @@ def _position_rows(model, tok_cpu, positions, residues_only):
 
 
 def _masked_chunks(model, tokens, positions, chunk, residues_only, varlen=False, chunk_rows=None):
-    """Yields (src, pos, logprobs [n, V]) per chunk: device int64 vectors of the scored rows and the log-softmax of the
-    logits at ``pos`` from the forward in which that token alone is masked.  ``varlen`` (on a model that has a token-packed
-    forward): the copies run token-packed, each as long as its own sequence, and ONE triple holds all rows."""
-    from . import ops
-
+    """(src, pos, logprobs [n, V]): device int64 vectors of the scored rows and the log-softmax of the logits at ``pos`` from
+    the forward in which that token alone is masked, the copies run in chunks.  ``varlen`` (on a model that has a
+    token-packed forward): the copies run token-packed, each as long as its own sequence."""
     tok = _device_tokens(model, tokens)
-    B, T = tok.shape
+    dev = tok.device
     tok_cpu = tok.cpu()
     src, pos = _position_rows(model, tok_cpu, positions, residues_only)
+    one = torch.arange(src.numel() + 1, dtype=torch.int64)  # one masked position, one selected row per copy
     if varlen and model._packs():
-        one = torch.arange(src.numel() + 1, dtype=torch.int64)  # one masked position, one selected row per copy
-        yield src.to(tok.device), pos.to(tok.device), _packed_copies(model, tok, _token_lengths(model, tok_cpu), src, one, pos,
-                                                                     one, pos, chunk_rows)
-        return
-    if chunk is None:
-        chunk = max(1, CHUNK_TOKENS // T)
-    if chunk <= 0:
-        raise ValueError("chunk must be positive")
-    # one upload for all chunks: the chunks are slices of these
-    src_d, pos_d = src.to(tok.device), pos.to(tok.device)
-    src32, pos32 = src_d.to(torch.int32), pos_d.to(torch.int32)
-    for lo in range(0, src.numel(), chunk):
-        hi = min(lo + chunk, src.numel())
-        masked = ops.mask_rows(tok, pos32[lo:hi].contiguous(), src32[lo:hi].contiguous(), model.mask_idx)
-        sel = torch.arange(hi - lo, dtype=torch.int32, device=tok.device) * T + pos32[lo:hi]
-        yield src_d[lo:hi], pos_d[lo:hi], forward_rows(model, masked, sel)
+        return src.to(dev), pos.to(dev), _packed_copies(model, tok, _token_lengths(model, tok_cpu), src, one, pos, one, pos,
+                                                        chunk_rows)
+    chunk = copies_per_call(chunk, tok.shape[1])
+    src_d, pos_d = src.to(dev), pos.to(dev)  # one upload for all chunks: the chunks are slices of these
+    return src_d, pos_d, _padded_copies(model, tok, src_d.to(torch.int32), pos_d.to(torch.int32), None, one, pos, chunk)
 
 
 @torch.no_grad()
@@ -274,8 +278,8 @@ def masked_marginals(model, tokens, positions=None, chunk=None, varlen=False, ch
         return windows.masked_marginals(model, tokens, positions, chunk, window, wrap, varlen, chunk_rows)
     tok = _device_tokens(model, tokens)
     out = torch.zeros(tuple(tok.shape) + (model.alphabet_size,), dtype=torch.float32, device=tok.device)
-    for src, pos, lp in _masked_chunks(model, tok, positions, chunk, residues_only=False, varlen=varlen, chunk_rows=chunk_rows):
-        out[src, pos] = lp
+    src, pos, lp = _masked_chunks(model, tok, positions, chunk, residues_only=False, varlen=varlen, chunk_rows=chunk_rows)
+    out[src, pos] = lp
     return out
 
 
@@ -306,7 +310,7 @@ def wt_marginals(model, tokens, varlen=False, chunk_rows=None, window=None, wrap
                             real.nonzero(as_tuple=True)[1], chunk_rows)
         out[real.to(tok.device)] = lp  # both in (sequence, position) order
         return out
-    step = max(1, CHUNK_TOKENS // T)
+    step = copies_per_call(None, T)
     for lo in range(0, B, step):
         part = tok[lo:lo + step]
         real = part.ne(model.padding_idx)
@@ -341,18 +345,15 @@ def pseudo_log_likelihood(model, tokens, positions=None, chunk=None, varlen=Fals
 
         return windows.pseudo_log_likelihood(model, tokens, positions, chunk, window, wrap, varlen, chunk_rows)
     tok = _device_tokens(model, tokens)
+    src, pos, lp = _masked_chunks(model, tok, positions, chunk, residues_only=True, varlen=varlen, chunk_rows=chunk_rows)
     if varlen and model._packs():
-        (src, pos, lp), = _masked_chunks(model, tok, positions, chunk, residues_only=True, varlen=True, chunk_rows=chunk_rows)
         if src.numel() == 0:
             return torch.zeros((tok.shape[0],), dtype=torch.float64, device=tok.device)
         seq_off = torch.zeros((tok.shape[0] + 1,), dtype=torch.int64, device=tok.device)
         seq_off[1:] = torch.bincount(src, minlength=tok.shape[0]).cumsum(0)  # rows are in (sequence, position) order
         return ops.sum_target_rows(lp, tok[src, pos].to(torch.int32), seq_off.to(torch.int32))
     out = torch.zeros((tok.shape[0],), dtype=torch.float64, device=tok.device)
-    for src, pos, lp in _masked_chunks(model, tok, positions, chunk, residues_only=True):
-        true = tok[src, pos].unsqueeze(1)
-        out.index_add_(0, src, lp.gather(1, true).squeeze(1).double())
-    return out
+    return out.index_add_(0, src, lp.gather(1, tok[src, pos].unsqueeze(1)).squeeze(1).double())
 
 
 def _parse_sets(tok, position_sets, src):
@@ -403,8 +404,6 @@ def masked_joint(model, tokens, position_sets, src=None, chunk=None, return_logi
     ``window`` / ``wrap``: a set of a sequence longer than the window is masked in ONE window copy, placed so that the set sits
     in its middle (``esm_amd.windows.set_start``); a set that spans as many tokens as a window has body tokens, or more, does
     not fit and raises ValueError."""
-    from . import ops
-
     _check_chunk_rows(varlen, chunk_rows)
     if window is not None:
         from . import windows
@@ -414,40 +413,17 @@ def masked_joint(model, tokens, position_sets, src=None, chunk=None, return_logi
     B, T = tok.shape
     dev = tok.device
     sets, src = _parse_sets(tok, position_sets, src)
-    if chunk is None:
-        chunk = max(1, CHUNK_TOKENS // T)
-    if chunk <= 0:
-        raise ValueError("chunk must be positive")
+    chunk = copies_per_call(chunk, T)
     _validate_sets(model, tok, sets, src)
-    V = model.alphabet_size
-    counts = torch.tensor([len(ps) for ps in sets], dtype=torch.int64)
-    offsets = torch.zeros((len(sets) + 1,), dtype=torch.int64)
-    offsets[1:] = counts.cumsum(0)
-    pos = torch.tensor([p for ps in sets for p in ps], dtype=torch.int64)
-    if not sets:
-        empty = torch.empty((0, V), dtype=torch.float32, device=dev)
-        return (offsets, pos.to(dev), empty) + ((empty.clone(),) if return_logits else ())
+    offsets, pos = set_offsets(sets)
+    pos_d = pos.to(dev)  # one upload for all chunks: the offsets index the whole position list, the chunks are slices of these
     if varlen and model._packs():
         got = _packed_copies(model, tok, _token_lengths(model, tok.cpu()), torch.tensor(src, dtype=torch.int64), offsets, pos,
                              offsets, pos, chunk_rows, return_logits=return_logits)
-        return (offsets, pos.to(dev)) + (got if return_logits else (got,))
-    # one upload for all chunks: the offsets index the whole position list, the chunks are slices of these
-    pos_d = pos.to(dev)
-    pos32, off32 = pos_d.to(torch.int32), offsets.to(device=dev, dtype=torch.int32)
-    src32 = torch.tensor(src, dtype=torch.int32).to(dev)
-    copy32 = torch.repeat_interleave(torch.arange(len(sets), dtype=torch.int32), counts).to(dev)  # the set of every row
-    lps, logits = [], []
-    for lo in range(0, len(sets), chunk):
-        hi = min(lo + chunk, len(sets))
-        masked = ops.mask_rows_multi(tok, off32[lo:hi + 1], pos32, src32[lo:hi], model.mask_idx)
-        r0, r1 = int(offsets[lo]), int(offsets[hi])
-        sel = (copy32[r0:r1] - lo) * T + pos32[r0:r1]
-        got = forward_rows(model, masked, sel, return_logits=return_logits)
-        lps.append(got[0] if return_logits else got)
-        if return_logits:
-            logits.append(got[1])
-    out = (offsets, pos_d, lps[0] if len(lps) == 1 else torch.cat(lps))
-    return out + ((logits[0] if len(logits) == 1 else torch.cat(logits),) if return_logits else ())
+    else:
+        got = _padded_copies(model, tok, torch.tensor(src, dtype=torch.int32).to(dev), pos_d.to(torch.int32),
+                             offsets.to(device=dev, dtype=torch.int32), offsets, pos, chunk, return_logits=return_logits)
+    return (offsets, pos_d) + (got if return_logits else (got,))
 
 
 def parse_mutation(mutation, offset_idx=0):

@@ -41,7 +41,8 @@ import bisect
 
 import torch
 
-CHUNK_TOKENS = 65536  # tokens per forward call that fill the GPU (esm_amd.scoring)
+from .copies import Layout, copies_per_call, even_chunks, local_rows, run_copies, set_offsets
+
 CONTACT_ATTN_BYTES = 8 << 30  # forward(return_contacts=True) builds [B, L, H, T, T] fp32 maps: default chunks stay below this
 
 
@@ -184,14 +185,6 @@ def plan_sequence(n, window, wrap, h, t, stride=None):
 
 
 # ---- orchestration ---------------------------------------------------------------------------------------------------------
-def _default_chunk(chunk, Tw):
-    if chunk is None:
-        return max(1, CHUNK_TOKENS // Tw)
-    if chunk <= 0:
-        raise ValueError("chunk must be positive")
-    return int(chunk)
-
-
 def _i32(values, dev):
     return torch.as_tensor(values, dtype=torch.int64).to(torch.int32).to(dev)
 
@@ -219,29 +212,18 @@ def _run_copies(model, tok, Tw, src, start, mask_off, mask_pos, sel_off, sel_col
     from . import ops, scoring
 
     dev = tok.device
-    V = model.alphabet_size
     n = len(src)
-    if n == 0 or len(sel_col) == 0:
-        empty = torch.empty((0, V), dtype=torch.float32, device=dev)
-        return (empty, empty.clone()) if return_logits else empty
-    chunk = _default_chunk(chunk, Tw)
+    chunk = int(copies_per_call(chunk, Tw))
     sel_off = torch.as_tensor(sel_off, dtype=torch.int64)
-    counts = sel_off[1:] - sel_off[:-1]
-    local = torch.repeat_interleave(torch.arange(n, dtype=torch.int64) % chunk, counts) * Tw + torch.as_tensor(sel_col, dtype=torch.int64)
-    src32, start32, off32, pos32, sel32 = (_i32(v, dev) for v in (src, start, mask_off, mask_pos, local))
-    lps, logits = [], []
-    for lo in range(0, n, chunk):
-        hi = min(lo + chunk, n)
-        r0, r1 = int(sel_off[lo]), int(sel_off[hi])
-        if r1 == r0:
-            continue
-        copies = ops.window_rows(tok, src32[lo:hi], start32[lo:hi], off32[lo:hi + 1], pos32, Tw, head_tok, tail_tok, model.mask_idx)
-        got = scoring.forward_rows(model, copies, sel32[r0:r1], return_logits=return_logits)
-        lps.append(got[0] if return_logits else got)
-        if return_logits:
-            logits.append(got[1])
-    lp = lps[0] if len(lps) == 1 else torch.cat(lps)
-    return (lp, logits[0] if len(logits) == 1 else torch.cat(logits)) if return_logits else lp
+    sel32 = local_rows(sel_off, chunk, Tw, torch.as_tensor(sel_col, dtype=torch.int64), dev)
+    src32, start32, off32, pos32 = (_i32(v, dev) for v in (src, start, mask_off, mask_pos))
+
+    def build(lo, hi):
+        return ops.window_rows(tok, src32[lo:hi], start32[lo:hi], off32[lo:hi + 1], pos32, Tw, head_tok, tail_tok, model.mask_idx)
+
+    layout = Layout(even_chunks(n, chunk), build,
+                    lambda copies, sel, return_logits: scoring.forward_rows(model, copies, sel, return_logits))
+    return run_copies(layout, n, sel_off, sel32, model.alphabet_size, dev, return_logits)
 
 
 def _masked_rows(model, tok, positions, chunk, Tw, wrap, residues_only, varlen=False, chunk_rows=None):
@@ -261,10 +243,8 @@ def _masked_rows(model, tok, positions, chunk, Tw, wrap, residues_only, varlen=F
         new_index[ids] = torch.arange(ids.numel())
         want = torch.zeros(tuple(sub.shape), dtype=torch.bool)
         want[new_index[src[~row_long]], pos[~row_long]] = True
-        ids_dev = ids.to(dev)
-        for c_src, c_pos, lp in scoring._masked_chunks(model, sub, want, chunk, residues_only=False, varlen=varlen,
-                                                       chunk_rows=chunk_rows):
-            yield ids_dev[c_src], c_pos, lp
+        c_src, c_pos, lp = scoring._masked_chunks(model, sub, want, chunk, residues_only=False, varlen=varlen, chunk_rows=chunk_rows)
+        yield ids.to(dev)[c_src], c_pos, lp
     if not bool(row_long.any()):
         return
     h, t, head_tok, tail_tok = _special(model, wrap)
@@ -381,13 +361,9 @@ def masked_joint(model, tokens, position_sets, src=None, chunk=None, return_logi
     dev = tok.device
     V = model.alphabet_size
     sets, src = scoring._parse_sets(tok, position_sets, src)
-    if chunk is not None and chunk <= 0:
-        raise ValueError("chunk must be positive")
+    copies_per_call(chunk, Tw)  # a chunk that is not positive is refused before the sets are looked at
     scoring._validate_sets(model, tok, sets, src)
-    counts = torch.tensor([len(ps) for ps in sets], dtype=torch.int64)
-    offsets = torch.zeros((len(sets) + 1,), dtype=torch.int64)
-    offsets[1:] = counts.cumsum(0)
-    pos = torch.tensor([p for ps in sets for p in ps], dtype=torch.int64)
+    offsets, pos = set_offsets(sets)
     n_rows = int(offsets[-1])
     lp = torch.empty((n_rows, V), dtype=torch.float32, device=dev)
     logits = torch.empty((n_rows, V), dtype=torch.float32, device=dev) if return_logits else None
@@ -462,11 +438,9 @@ def forward_windows(model, tokens, repr_layers=[], window=None, stride=None, wra
     is_long = lengths > Tw
     h, t, head_tok, tail_tok = _special(model, wrap)
     eh, et = _ends(model)
-    if chunk is None:
-        chunk = max(1, CHUNK_TOKENS // Tw)
-        if return_contacts:
-            chunk = max(1, min(chunk, CONTACT_ATTN_BYTES // (4 * model.num_layers * model.attention_heads * Tw * Tw)))
-    chunk = _default_chunk(chunk, Tw)
+    if chunk is None and return_contacts:
+        chunk = max(1, min(copies_per_call(None, Tw), CONTACT_ATTN_BYTES // (4 * model.num_layers * model.attention_heads * Tw * Tw)))
+    chunk = int(copies_per_call(chunk, Tw))
     kw = dict(return_contacts=True) if return_contacts else {}
     out = {}
 
