@@ -31,10 +31,11 @@
 // Softmax is fp32 (exp2; see LAZY below), P is rounded to the operand dtype for the PV MFMA,
 // accumulation is fp32.
 //
-// attn_probs_kernel: re-computes S tile by tile from q, k and the saved log-sum-exp and writes
+// attn_probs_rows (end of file): re-computes S tile by tile from q, k and the saved log-sum-exp and writes
 // normalised fp32 probabilities for need_head_weights=True / the contact head
-// (multihead_attention.py:396-403, esm2.py:119-121,132-139) with padded rows/cols zeroed.
-// attn_probs_packed_kernel: the same per segment of a token-packed batch, into ragged [L,H,len,len] blocks (end of file).
+// (multihead_attention.py:396-403, esm2.py:119-121,132-139) with padded rows/cols zeroed.  One loop for both head
+// dims; attn_probs_kernel / attn_probs128_kernel (padded batch) and attn_probs_packed_kernel /
+// attn_probs128_packed_kernel (per segment of a token-packed batch, into ragged [L,H,len,len] blocks) are its wrappers.
 #include "common.h"
 #include "kernels.h"
 #include <math.h>
@@ -685,67 +686,52 @@ static hipError_t launch_attention_impl(const void* q, const void* k, const void
 }
 
 // ---------------------------------------------------------------------------------------------
-// attention probabilities for need_head_weights / contacts
+// attention probabilities for need_head_weights / contacts (multihead_attention.py:396-403, esm2.py:132-139)
 // ---------------------------------------------------------------------------------------------
+// The map of one (sequence, head), 32 query rows [q0, q0 + 32) per wave: the ONE loop behind the four map kernels
+// (head_dim 64 / 128, padded / token-packed).  q, k [Tlen, HD], lse [Tlen], key_bias [Tlen] or null and out
+// [Tlen, Tlen] already point at the (sequence, head): the kernels below differ only in how they find them.  Per 32
+// keys: HD/16 MFMAs (D[row = query][col = key]), s + bias, exp2(s - lse) in the log2 domain of q.k and lse.
+// fill (wave uniform): the MSA column maps' masked_fill form — key_bias holds 0/1 flags, a flagged key's score is
+// REPLACED by -10000 and query rows are not zeroed (axial_attention.py:207-218).  Otherwise key_bias is 0 / -inf,
+// added, and a <pad> query row is written as zeros.
 // O = float (the reference's fp32 maps) or T (ESMK_OUT_ATTN_LOWP: `.half()` models, esmfold.py:61-67,131-135)
-template <typename T, typename O = float>
-__global__ __launch_bounds__(256) void attn_probs_kernel(const T* __restrict__ q,
-                                                          const T* __restrict__ k,
-                                                          const float* __restrict__ lse,
-                                                          const float* __restrict__ key_bias,
-                                                          O* __restrict__ probs, int H, int Tlen,
-                                                          int layer, int Ltot, int msa_C,
-                                                          const int* __restrict__ any_pad) {
-    // msa_C > 0: MSA column attention (axial_attention.py:207-218).  The "sequence" b is (batch, column),
-    // key_bias holds 0/1 masked_fill flags used when any_pad[0] != 0, query rows are NOT zeroed and the
-    // map goes to col_attentions[b_msa, layer, head, c, i, j] (msa_transformer.py:193-194).
+template <int HD, typename T, typename O>
+ESMK_DEV void attn_probs_rows(const T* __restrict__ q, const T* __restrict__ k, const float* __restrict__ lse,
+                              const float* __restrict__ key_bias, O* __restrict__ out, int Tlen, int q0, bool fill) {
     using V8 = typename Op<T>::v8;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int KS = HD / 16;
+    const int lane = threadIdx.x & 63;
     const int h = lane >> 5, lm = lane & 31;
-    const int nqb = (Tlen + 127) >> 7;
-    const int bh = blockIdx.x / nqb;  // 1-D grid: B*H can exceed the 65535 limit of grid.y (MSA columns)
-    const int b = bh / H, head = bh - b * H;
-    const int q0 = (blockIdx.x - bh * nqb) * 128 + wave * 32;
-    if (q0 >= Tlen) return;
-    const bool fill = msa_C > 0;
-    if (fill && (any_pad == nullptr || any_pad[0] == 0)) key_bias = nullptr;
-
-    V8 qf[4];
+    V8 qf[KS];
     {
         const int qr = min(q0 + lm, Tlen - 1);
-        const T* qp = q + ((size_t)bh * Tlen + qr) * 64 + 8 * h;
+        const T* qp = q + (size_t)qr * HD + 8 * h;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const V8*>(qp + 16 * ks);
+        for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const V8*>(qp + 16 * ks);
     }
     // per accumulator row: log-sum-exp and query-pad flag
     float row_lse[16];
     float row_keep[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int qr = q0 + mfma32_row(r, h);
-        const int qc = min(qr, Tlen - 1);
-        row_lse[r] = lse[(size_t)bh * Tlen + qc];
-        row_keep[r] = (!fill && key_bias != nullptr && key_bias[(size_t)b * Tlen + qc] != 0.f) ? 0.f : 1.f;
+        const int qc = min(q0 + mfma32_row(r, h), Tlen - 1);
+        row_lse[r] = lse[qc];
+        row_keep[r] = (!fill && key_bias != nullptr && key_bias[qc] != 0.f) ? 0.f : 1.f;
     }
-    O* out = probs + (((size_t)b * Ltot + layer) * H + head) * (size_t)Tlen * Tlen;
-    if (fill) {
-        const int bm = b / msa_C, c = b - bm * msa_C;
-        out = probs + ((((size_t)bm * Ltot + layer) * H + head) * msa_C + c) * (size_t)Tlen * Tlen;
-    }
-
     for (int k0 = 0; k0 < Tlen; k0 += 32) {
         const int key = k0 + lm;
         const int kc = min(key, Tlen - 1);
-        const T* kp = k + ((size_t)bh * Tlen + kc) * 64 + 8 * h;
+        const T* kp = k + (size_t)kc * HD + 8 * h;
         f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
+        for (int ks = 0; ks < KS; ++ks) {
             const V8 kf = *reinterpret_cast<const V8*>(kp + 16 * ks);
             s = Op<T>::mma(qf[ks], kf, s);  // D[row = query][col = key]
         }
-        const float kb = (key_bias != nullptr) ? key_bias[(size_t)b * Tlen + kc] : 0.f;
+        const float kb = (key_bias != nullptr) ? key_bias[kc] : 0.f;
         if (key < Tlen) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -762,30 +748,121 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const T* __restrict__ q
     }
 }
 
+// Padded batch, q, k [B,H,T,HD]: workgroup = (b, head, 128-query block), 1-D grid (B*H can exceed the 65535 limit of
+// grid.y: MSA columns); the map goes to probs[b, layer, head].  msa_C > 0: MSA column attention.  The "sequence" b is
+// (batch, column), key_bias holds the masked_fill flags, used when any_pad[0] != 0, and the map goes to
+// col_attentions[b_msa, layer, head, c, i, j] (msa_transformer.py:193-194).
+template <int HD, typename T, typename O>
+ESMK_DEV void attn_probs_padded(const T* __restrict__ q, const T* __restrict__ k, const float* __restrict__ lse,
+                                const float* __restrict__ key_bias, O* __restrict__ probs, int H, int Tlen, int layer,
+                                int Ltot, int msa_C, const int* __restrict__ any_pad) {
+    const int nqb = (Tlen + 127) >> 7;
+    const int bh = blockIdx.x / nqb;
+    const int b = bh / H, head = bh - b * H;
+    const int q0 = (blockIdx.x - bh * nqb) * 128 + (threadIdx.x >> 6) * 32;
+    if (q0 >= Tlen) return;
+    const bool fill = msa_C > 0;
+    if (fill && (any_pad == nullptr || any_pad[0] == 0)) key_bias = nullptr;
+    if (key_bias != nullptr) key_bias += (size_t)b * Tlen;
+    O* out = probs + (((size_t)b * Ltot + layer) * H + head) * (size_t)Tlen * Tlen;
+    if (fill) {
+        const int bm = b / msa_C, c = b - bm * msa_C;
+        out = probs + ((((size_t)bm * Ltot + layer) * H + head) * msa_C + c) * (size_t)Tlen * Tlen;
+    }
+    attn_probs_rows<HD>(q + (size_t)bh * Tlen * HD, k + (size_t)bh * Tlen * HD, lse + (size_t)bh * Tlen, key_bias, out,
+                        Tlen, q0, fill);
+}
+
+// Token-packed batch, q, k [H, rows, HD]: workgroup (head, item) takes work item `item` of the attention launch's list
+// (a 128-query block of one segment; longest segments first), the key loop covers the segment's own rows only, and the
+// map goes to the segment's ragged [Ltot, H, len, len] block at Ltot * H * map_off[segment].  lse is the packed
+// attention kernel's, which is the padded one's bit for bit: so is every probability.  key_bias is read only for
+// segments that contain <pad> tokens (adding the 0.0 of a real key changes no probability bit).  Consecutive
+// workgroups share (head, segment): the K rows of a segment stay in the L2 while its query blocks run.
+template <int HD, typename T, typename O>
+ESMK_DEV void attn_probs_packed(const T* __restrict__ q, const T* __restrict__ k, const float* __restrict__ lse,
+                                const float* __restrict__ key_bias, O* __restrict__ probs, int H, int rows, int layer,
+                                int Ltot, int n_items, const AttnSegs& segs,
+                                const unsigned long long* __restrict__ map_off) {
+    const int head = blockIdx.x / n_items, item = blockIdx.x - head * n_items;
+    const int row0 = __builtin_amdgcn_readfirstlane(segs.work[4 * item]);
+    const int Tseg = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 1]);
+    const int qrel = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 2]);
+    const int seg = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 3]);
+    const int q0 = qrel + (threadIdx.x >> 6) * 32;
+    if (q0 >= Tseg) return;
+    key_bias = (segs.npad[seg] <= 0 || key_bias == nullptr) ? nullptr : key_bias + row0;
+    const size_t rbase = (size_t)head * rows + row0;  // first row of the segment in the [H, rows] row spaces
+    const size_t plane = (size_t)Tseg * Tseg;
+    O* out = probs + (size_t)Ltot * H * (size_t)map_off[seg] + ((size_t)layer * H + head) * plane;
+    attn_probs_rows<HD>(q + rbase * HD, k + rbase * HD, lse + rbase, key_bias, out, Tseg, q0, false);
+}
+
+template <typename T, typename O = float>
+__global__ __launch_bounds__(256) void attn_probs_kernel(const T* __restrict__ q,
+                                                          const T* __restrict__ k,
+                                                          const float* __restrict__ lse,
+                                                          const float* __restrict__ key_bias,
+                                                          O* __restrict__ probs, int H, int Tlen,
+                                                          int layer, int Ltot, int msa_C,
+                                                          const int* __restrict__ any_pad) {
+    attn_probs_padded<64>(q, k, lse, key_bias, probs, H, Tlen, layer, Ltot, msa_C, any_pad);
+}
+
+// head_dim 128 (esm2_t48_15B; the dims of a head in the QKV epilogue's slice order, the same for q and k: attention128.hip)
+template <typename T, typename O = float>
+__global__ __launch_bounds__(256) void attn_probs128_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                             const float* __restrict__ lse,
+                                                             const float* __restrict__ key_bias,
+                                                             O* __restrict__ probs, int H, int Tlen, int layer,
+                                                             int Ltot) {
+    attn_probs_padded<128>(q, k, lse, key_bias, probs, H, Tlen, layer, Ltot, 0, nullptr);
+}
+
+template <typename T, typename O = float>
+__global__ __launch_bounds__(256) void attn_probs_packed_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                 const float* __restrict__ lse,
+                                                                 const float* __restrict__ key_bias, O* __restrict__ probs,
+                                                                 int H, int rows, int layer, int Ltot, int n_items,
+                                                                 AttnSegs segs,
+                                                                 const unsigned long long* __restrict__ map_off) {
+    attn_probs_packed<64>(q, k, lse, key_bias, probs, H, rows, layer, Ltot, n_items, segs, map_off);
+}
+
+template <typename T, typename O = float>
+__global__ __launch_bounds__(256) void attn_probs128_packed_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                    const float* __restrict__ lse,
+                                                                    const float* __restrict__ key_bias,
+                                                                    O* __restrict__ probs, int H, int rows, int layer,
+                                                                    int Ltot, int n_items, AttnSegs segs,
+                                                                    const unsigned long long* __restrict__ map_off) {
+    attn_probs_packed<128>(q, k, lse, key_bias, probs, H, rows, layer, Ltot, n_items, segs, map_off);
+}
+
+// the {fp16, bf16} x {fp32 maps, maps in the operand dtype} forms of a map kernel: `launch` gets q, k and probs
+// with their element types
+template <typename F>
+static hipError_t probs_dispatch(int operand_dtype, bool lowp, const void* q, const void* k, void* probs, F launch) {
+    if (operand_dtype == ESMK_DT_BF16) {
+        if (lowp) launch((const __bf16*)q, (const __bf16*)k, (__bf16*)probs);
+        else launch((const __bf16*)q, (const __bf16*)k, (float*)probs);
+    } else {
+        if (lowp) launch((const _Float16*)q, (const _Float16*)k, (_Float16*)probs);
+        else launch((const _Float16*)q, (const _Float16*)k, (float*)probs);
+    }
+    return hipGetLastError();
+}
+#define ESMK_PROBS_KERNEL(name, qt, out) name<std::decay_t<decltype(*qt)>, std::decay_t<decltype(*out)>>
+
 static hipError_t launch_probs_impl(const void* q, const void* k, const float* lse, const float* key_bias,
                                     float* probs, int B, int H, int T, int layer, int num_layers_total,
                                     int operand_dtype, int msa_C, const int* any_pad, hipStream_t st,
                                     bool lowp = false) {
     dim3 grid((unsigned)(((T + 127) / 128) * B * H));
-    if (lowp) {  // maps in the operand dtype
-        if (operand_dtype == ESMK_DT_BF16)
-            hipLaunchKernelGGL((attn_probs_kernel<__bf16, __bf16>), grid, dim3(256), 0, st, (const __bf16*)q,
-                               (const __bf16*)k, lse, key_bias, (__bf16*)probs, H, T, layer, num_layers_total, msa_C,
-                               any_pad);
-        else
-            hipLaunchKernelGGL((attn_probs_kernel<_Float16, _Float16>), grid, dim3(256), 0, st, (const _Float16*)q,
-                               (const _Float16*)k, lse, key_bias, (_Float16*)probs, H, T, layer, num_layers_total,
-                               msa_C, any_pad);
-        return hipGetLastError();
-    }
-    if (operand_dtype == ESMK_DT_BF16)
-        hipLaunchKernelGGL((attn_probs_kernel<__bf16>), grid, dim3(256), 0, st, (const __bf16*)q,
-                           (const __bf16*)k, lse, key_bias, probs, H, T, layer, num_layers_total, msa_C, any_pad);
-    else
-        hipLaunchKernelGGL((attn_probs_kernel<_Float16>), grid, dim3(256), 0, st,
-                           (const _Float16*)q, (const _Float16*)k, lse, key_bias, probs, H, T, layer,
-                           num_layers_total, msa_C, any_pad);
-    return hipGetLastError();
+    return probs_dispatch(operand_dtype, lowp, q, k, probs, [&](auto* qt, auto* kt, auto* out) {
+        hipLaunchKernelGGL((ESMK_PROBS_KERNEL(attn_probs_kernel, qt, out)), grid, dim3(256), 0, st, qt, kt, lse, key_bias,
+                           out, H, T, layer, num_layers_total, msa_C, any_pad);
+    });
 }
 
 hipError_t launch_attention_probs(const void* q, const void* k, const float* lse,
@@ -803,104 +880,46 @@ hipError_t launch_attention_probs_msa(const void* q, const void* k, const float*
                              C, any_pad, st);
 }
 
-// ---------------------------------------------------------------------------------------------
-// attention probabilities of a token-packed batch (multihead_attention.py:396-403, esm2.py:132-139 per sequence)
-// ---------------------------------------------------------------------------------------------
-// attn_probs_kernel on the packed row space: workgroup (head, item) takes work item `item` of the attention launch's
-// list (a 128-query block of one segment; longest segments first), its waves 32 query rows each from row0 + qrel, the
-// key loop covers the segment's own rows only, and the map goes to the segment's ragged [Ltot, H, len, len] block.  The
-// arithmetic per element is attn_probs_kernel's — the same four MFMAs over the 64 dims, s + bias, exp2(s - lse) — and
-// lse is the packed attention kernel's, which is the padded one's bit for bit: so is every probability.  key_bias is
-// read only for segments that contain <pad> tokens (adding the 0.0 of a real key changes no probability bit).
-// Consecutive workgroups share (head, segment): the K rows of a segment stay in the L2 while its query blocks run.
-template <typename T, typename O = float>
-__global__ __launch_bounds__(256) void attn_probs_packed_kernel(const T* __restrict__ q, const T* __restrict__ k,
-                                                                 const float* __restrict__ lse,
-                                                                 const float* __restrict__ key_bias, O* __restrict__ probs,
-                                                                 int H, int rows, int layer, int Ltot, int n_items,
-                                                                 AttnSegs segs,
-                                                                 const unsigned long long* __restrict__ map_off) {
-    using V8 = typename Op<T>::v8;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int h = lane >> 5, lm = lane & 31;
-    const int head = blockIdx.x / n_items, item = blockIdx.x - head * n_items;
-    const int row0 = __builtin_amdgcn_readfirstlane(segs.work[4 * item]);
-    const int Tseg = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 1]);
-    const int qrel = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 2]);
-    const int seg = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 3]);
-    const int q0 = qrel + wave * 32;
-    if (q0 >= Tseg) return;
-    if (segs.npad[seg] <= 0) key_bias = nullptr;
-    const size_t rbase = (size_t)head * rows + row0;  // first row of the segment in the [H, rows] row spaces
+hipError_t launch_attention_probs128(const void* q, const void* k, const float* lse, const float* key_bias,
+                                     float* probs, int B, int H, int T, int layer, int num_layers_total,
+                                     int operand_dtype, hipStream_t st, bool lowp) {
+    dim3 grid((unsigned)(((T + 127) / 128) * B * H));
+    return probs_dispatch(operand_dtype, lowp, q, k, probs, [&](auto* qt, auto* kt, auto* out) {
+        hipLaunchKernelGGL((ESMK_PROBS_KERNEL(attn_probs128_kernel, qt, out)), grid, dim3(256), 0, st, qt, kt, lse,
+                           key_bias, out, H, T, layer, num_layers_total);
+    });
+}
 
-    V8 qf[4];
-    {
-        const int qr = min(q0 + lm, Tseg - 1);
-        const T* qp = q + (rbase + qr) * 64 + 8 * h;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const V8*>(qp + 16 * ks);
-    }
-    float row_lse[16];
-    float row_keep[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int qc = min(q0 + mfma32_row(r, h), Tseg - 1);
-        row_lse[r] = lse[rbase + qc];
-        row_keep[r] = (key_bias != nullptr && key_bias[(size_t)row0 + qc] != 0.f) ? 0.f : 1.f;
-    }
-    const size_t plane = (size_t)Tseg * Tseg;
-    O* out = probs + (size_t)Ltot * H * (size_t)map_off[seg] + ((size_t)layer * H + head) * plane;
-
-    for (int k0 = 0; k0 < Tseg; k0 += 32) {
-        const int key = k0 + lm;
-        const int kc = min(key, Tseg - 1);
-        const T* kp = k + (rbase + kc) * 64 + 8 * h;
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const V8 kf = *reinterpret_cast<const V8*>(kp + 16 * ks);
-            s = Op<T>::mma(qf[ks], kf, s);  // D[row = query][col = key]
-        }
-        const float kb = (key_bias != nullptr) ? key_bias[(size_t)row0 + kc] : 0.f;
-        if (key < Tseg) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int qr = q0 + mfma32_row(r, h);
-                if (qr < Tseg) {
-                    // <pad> query rows: a select, not a multiply by 0 (see attn_probs_kernel)
-                    const float p = row_keep[r] != 0.f ? __builtin_amdgcn_exp2f(s[r] + kb - row_lse[r]) : 0.f;
-                    out[(size_t)qr * Tseg + key] = (O)p;
-                }
-            }
-        }
-    }
+static bool probs_packed_args_ok(const AttnSegs& segs, const unsigned long long* map_off, int n_items, int H, int rows,
+                                 int operand_dtype) {
+    return segs.work != nullptr && segs.npad != nullptr && map_off != nullptr && n_items > 0 && H > 0 && rows > 0 &&
+           (long long)n_items * H <= 0x7fffffffLL && (operand_dtype == ESMK_DT_BF16 || operand_dtype == ESMK_DT_F16);
 }
 
 hipError_t launch_attention_probs_packed(const void* q, const void* k, const float* lse, const float* key_bias, void* probs,
                                          int H, int rows, int layer, int num_layers_total, AttnSegs segs,
                                          const unsigned long long* map_off, int n_items, int operand_dtype, bool lowp,
                                          hipStream_t st) {
-    if (segs.work == nullptr || segs.npad == nullptr || map_off == nullptr || n_items <= 0 || H <= 0 || rows <= 0 ||
-        (long long)n_items * H > 0x7fffffffLL)
-        return hipErrorInvalidValue;
+    if (!probs_packed_args_ok(segs, map_off, n_items, H, rows, operand_dtype)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)n_items * (unsigned)H);
-#define ESMK_PROBS_PACKED(TT, OO)                                                                                     \
-    hipLaunchKernelGGL((attn_probs_packed_kernel<TT, OO>), grid, dim3(256), 0, st, (const TT*)q, (const TT*)k, lse,   \
-                       key_bias, (OO*)probs, H, rows, layer, num_layers_total, n_items, segs, map_off)
-    if (operand_dtype == ESMK_DT_BF16) {
-        if (lowp) ESMK_PROBS_PACKED(__bf16, __bf16);
-        else ESMK_PROBS_PACKED(__bf16, float);
-    } else if (operand_dtype == ESMK_DT_F16) {
-        if (lowp) ESMK_PROBS_PACKED(_Float16, _Float16);
-        else ESMK_PROBS_PACKED(_Float16, float);
-    } else {
-        return hipErrorInvalidValue;
-    }
-#undef ESMK_PROBS_PACKED
-    return hipGetLastError();
+    return probs_dispatch(operand_dtype, lowp, q, k, probs, [&](auto* qt, auto* kt, auto* out) {
+        hipLaunchKernelGGL((ESMK_PROBS_KERNEL(attn_probs_packed_kernel, qt, out)), grid, dim3(256), 0, st, qt, kt, lse,
+                           key_bias, out, H, rows, layer, num_layers_total, n_items, segs, map_off);
+    });
 }
+
+hipError_t launch_attention_probs128_packed(const void* q, const void* k, const float* lse, const float* key_bias,
+                                            void* probs, int H, int rows, int layer, int num_layers_total, AttnSegs segs,
+                                            const unsigned long long* map_off, int n_items, int operand_dtype, bool lowp,
+                                            hipStream_t st) {
+    if (!probs_packed_args_ok(segs, map_off, n_items, H, rows, operand_dtype)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)n_items * (unsigned)H);
+    return probs_dispatch(operand_dtype, lowp, q, k, probs, [&](auto* qt, auto* kt, auto* out) {
+        hipLaunchKernelGGL((ESMK_PROBS_KERNEL(attn_probs128_packed_kernel, qt, out)), grid, dim3(256), 0, st, qt, kt, lse,
+                           key_bias, out, H, rows, layer, num_layers_total, n_items, segs, map_off);
+    });
+}
+#undef ESMK_PROBS_KERNEL
 
 // npad of a packed batch from its key_bias alone (the engine counts <pad> tokens in launch_packed_stats)
 __global__ __launch_bounds__(64) void seg_npad_kernel(const float* __restrict__ key_bias, const int* __restrict__ seg,

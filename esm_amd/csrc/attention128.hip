@@ -12,6 +12,8 @@
 //   V^T tile  128 rows (dv) x 128 B, chunk index XOR-swizzled with (row >> 1) & 7 as in attention.hip
 //   one workgroup = 4 waves x 32 query rows; S^T = K.Q^T costs 8 MFMAs per 32 keys, O^T += V^T.P^T keeps four
 //   32x32 accumulators per wave.  LDS: 2 stages x (16 + 16 KiB + key bias) = 64.5 KiB (dynamic).
+// This file is the attention core only: the head_dim-128 attention maps (attn_probs128_kernel,
+// attn_probs128_packed_kernel) share their loop with the head_dim-64 ones and live in attention.hip.
 #include "common.h"
 #include "kernels.h"
 #include <math.h>
@@ -276,172 +278,6 @@ hipError_t launch_attention128(const void* q, const void* k, const void* vt, con
     if (B <= 0 || H <= 0 || T <= 0 || Tp < T || (Tp & 63)) return hipErrorInvalidValue;
     if (operand_dtype == ESMK_DT_BF16) return launch128<__bf16>(q, k, vt, key_bias, seq_info, ctx, lse, B, H, T, Tp, st);
     return launch128<_Float16>(q, k, vt, key_bias, seq_info, ctx, lse, B, H, T, Tp, st);
-}
-
-// ---------------------------------------------------------------------------------------------
-// attention probabilities for need_head_weights / contacts (multihead_attention.py:396-403)
-// ---------------------------------------------------------------------------------------------
-template <typename T, typename O = float>
-__global__ __launch_bounds__(256) void attn_probs128_kernel(const T* __restrict__ q, const T* __restrict__ k,
-                                                             const float* __restrict__ lse,
-                                                             const float* __restrict__ key_bias,
-                                                             O* __restrict__ probs, int H, int Tlen, int layer,
-                                                             int Ltot) {
-    using V8 = typename Op<T>::v8;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int h = lane >> 5, lm = lane & 31;
-    const int nqb = (Tlen + 127) >> 7;
-    const int bh = blockIdx.x / nqb;
-    const int b = bh / H, head = bh - b * H;
-    const int q0 = (blockIdx.x - bh * nqb) * 128 + wave * 32;
-    if (q0 >= Tlen) return;
-    V8 qf[8];
-    {
-        const int qr = min(q0 + lm, Tlen - 1);
-        const T* qp = q + ((size_t)bh * Tlen + qr) * HD + 8 * h;
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) qf[ks] = *reinterpret_cast<const V8*>(qp + 16 * ks);
-    }
-    float row_lse[16], row_keep[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int qc = min(q0 + mfma32_row(r, h), Tlen - 1);
-        row_lse[r] = lse[(size_t)bh * Tlen + qc];
-        row_keep[r] = (key_bias != nullptr && key_bias[(size_t)b * Tlen + qc] != 0.f) ? 0.f : 1.f;
-    }
-    O* out = probs + (((size_t)b * Ltot + layer) * H + head) * (size_t)Tlen * Tlen;
-    for (int k0 = 0; k0 < Tlen; k0 += 32) {
-        const int key = k0 + lm;
-        const int kc = min(key, Tlen - 1);
-        const T* kp = k + ((size_t)bh * Tlen + kc) * HD + 8 * h;
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-            const V8 kf = *reinterpret_cast<const V8*>(kp + 16 * ks);
-            s = Op<T>::mma(qf[ks], kf, s);
-        }
-        const float kbv = (key_bias != nullptr) ? key_bias[(size_t)b * Tlen + kc] : 0.f;
-        if (key < Tlen) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int qr = q0 + mfma32_row(r, h);
-                // padded query rows: a select, not a multiply by 0 (exp2 of a padded row's scores may overflow)
-                if (qr < Tlen)
-                    out[(size_t)qr * Tlen + key] = (O)(row_keep[r] != 0.f ? __builtin_amdgcn_exp2f(s[r] + kbv - row_lse[r]) : 0.f);
-            }
-        }
-    }
-}
-
-hipError_t launch_attention_probs128(const void* q, const void* k, const float* lse, const float* key_bias,
-                                     float* probs, int B, int H, int T, int layer, int num_layers_total,
-                                     int operand_dtype, hipStream_t st, bool lowp) {
-    dim3 grid((unsigned)(((T + 127) / 128) * B * H));
-    if (lowp) {  // maps in the operand dtype (ESMK_OUT_ATTN_LOWP)
-        if (operand_dtype == ESMK_DT_BF16)
-            hipLaunchKernelGGL((attn_probs128_kernel<__bf16, __bf16>), grid, dim3(256), 0, st, (const __bf16*)q,
-                               (const __bf16*)k, lse, key_bias, (__bf16*)probs, H, T, layer, num_layers_total);
-        else
-            hipLaunchKernelGGL((attn_probs128_kernel<_Float16, _Float16>), grid, dim3(256), 0, st, (const _Float16*)q,
-                               (const _Float16*)k, lse, key_bias, (_Float16*)probs, H, T, layer, num_layers_total);
-        return hipGetLastError();
-    }
-    if (operand_dtype == ESMK_DT_BF16)
-        hipLaunchKernelGGL((attn_probs128_kernel<__bf16>), grid, dim3(256), 0, st, (const __bf16*)q, (const __bf16*)k,
-                           lse, key_bias, probs, H, T, layer, num_layers_total);
-    else
-        hipLaunchKernelGGL((attn_probs128_kernel<_Float16>), grid, dim3(256), 0, st, (const _Float16*)q,
-                           (const _Float16*)k, lse, key_bias, probs, H, T, layer, num_layers_total);
-    return hipGetLastError();
-}
-
-// The same for a token-packed batch: attn_probs_packed_kernel (attention.hip) with the eight MFMAs of a 128-wide head.
-// One workgroup = (head, work item of the attention launch); ragged [Ltot, H, len, len] block per segment at
-// Ltot * H * map_off[segment]; every element carries attn_probs128_kernel's bits for the same sequence in a padded batch.
-template <typename T, typename O = float>
-__global__ __launch_bounds__(256) void attn_probs128_packed_kernel(const T* __restrict__ q, const T* __restrict__ k,
-                                                                    const float* __restrict__ lse,
-                                                                    const float* __restrict__ key_bias,
-                                                                    O* __restrict__ probs, int H, int rows, int layer,
-                                                                    int Ltot, int n_items, AttnSegs segs,
-                                                                    const unsigned long long* __restrict__ map_off) {
-    using V8 = typename Op<T>::v8;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int h = lane >> 5, lm = lane & 31;
-    const int head = blockIdx.x / n_items, item = blockIdx.x - head * n_items;
-    const int row0 = __builtin_amdgcn_readfirstlane(segs.work[4 * item]);
-    const int Tseg = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 1]);
-    const int qrel = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 2]);
-    const int seg = __builtin_amdgcn_readfirstlane(segs.work[4 * item + 3]);
-    const int q0 = qrel + wave * 32;
-    if (q0 >= Tseg) return;
-    if (segs.npad[seg] <= 0) key_bias = nullptr;
-    const size_t rbase = (size_t)head * rows + row0;
-    V8 qf[8];
-    {
-        const int qr = min(q0 + lm, Tseg - 1);
-        const T* qp = q + (rbase + qr) * HD + 8 * h;
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) qf[ks] = *reinterpret_cast<const V8*>(qp + 16 * ks);
-    }
-    float row_lse[16], row_keep[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int qc = min(q0 + mfma32_row(r, h), Tseg - 1);
-        row_lse[r] = lse[rbase + qc];
-        row_keep[r] = (key_bias != nullptr && key_bias[(size_t)row0 + qc] != 0.f) ? 0.f : 1.f;
-    }
-    const size_t plane = (size_t)Tseg * Tseg;
-    O* out = probs + (size_t)Ltot * H * (size_t)map_off[seg] + ((size_t)layer * H + head) * plane;
-    for (int k0 = 0; k0 < Tseg; k0 += 32) {
-        const int key = k0 + lm;
-        const int kc = min(key, Tseg - 1);
-        const T* kp = k + (rbase + kc) * HD + 8 * h;
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-            const V8 kf = *reinterpret_cast<const V8*>(kp + 16 * ks);
-            s = Op<T>::mma(qf[ks], kf, s);
-        }
-        const float kbv = (key_bias != nullptr) ? key_bias[(size_t)row0 + kc] : 0.f;
-        if (key < Tseg) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int qr = q0 + mfma32_row(r, h);
-                // <pad> query rows: a select, not a multiply by 0 (see attn_probs128_kernel)
-                if (qr < Tseg)
-                    out[(size_t)qr * Tseg + key] = (O)(row_keep[r] != 0.f ? __builtin_amdgcn_exp2f(s[r] + kbv - row_lse[r]) : 0.f);
-            }
-        }
-    }
-}
-
-hipError_t launch_attention_probs128_packed(const void* q, const void* k, const float* lse, const float* key_bias,
-                                            void* probs, int H, int rows, int layer, int num_layers_total, AttnSegs segs,
-                                            const unsigned long long* map_off, int n_items, int operand_dtype, bool lowp,
-                                            hipStream_t st) {
-    if (segs.work == nullptr || segs.npad == nullptr || map_off == nullptr || n_items <= 0 || H <= 0 || rows <= 0 ||
-        (long long)n_items * H > 0x7fffffffLL)
-        return hipErrorInvalidValue;
-    const dim3 grid((unsigned)n_items * (unsigned)H);
-#define ESMK_PROBS128_PACKED(TT, OO)                                                                                    \
-    hipLaunchKernelGGL((attn_probs128_packed_kernel<TT, OO>), grid, dim3(256), 0, st, (const TT*)q, (const TT*)k, lse, \
-                       key_bias, (OO*)probs, H, rows, layer, num_layers_total, n_items, segs, map_off)
-    if (operand_dtype == ESMK_DT_BF16) {
-        if (lowp) ESMK_PROBS128_PACKED(__bf16, __bf16);
-        else ESMK_PROBS128_PACKED(__bf16, float);
-    } else if (operand_dtype == ESMK_DT_F16) {
-        if (lowp) ESMK_PROBS128_PACKED(_Float16, _Float16);
-        else ESMK_PROBS128_PACKED(_Float16, float);
-    } else {
-        return hipErrorInvalidValue;
-    }
-#undef ESMK_PROBS128_PACKED
-    return hipGetLastError();
 }
 
 }  // namespace esmk

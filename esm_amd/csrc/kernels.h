@@ -332,8 +332,10 @@ hipError_t launch_contacts_fused_final(const float* acc, float* rowsum, const fl
                                        int B, int H, int C, int T, int head_dim, int pad_idx, int eos_idx,
                                        int prepend_bos, int append_eos, hipStream_t st, int G = 0);
 
-// Token-packed batch with contacts (esmk_forward_packed_ex).  Only segments with S = len - bos - eos > 0 get work
-// and scratch.  Per segment s, element offsets off[4s..4s+3] (int64) into: one head group's accumulator (the G
+// Token-packed batch with contacts (esmk_forward_packed_ex): the same device code as the padded launchers above — each
+// computation is one body in the coordinates of one sequence (contacts.hip), the two layouts differ in the kernels'
+// prologues (where the workgroup's sequence and its scratch are) and in two strides.  Only segments with
+// S = len - bos - eos > 0 get work and scratch.  Per segment s, element offsets off[4s..4s+3] (int64) into: one head group's accumulator (the G
 // accumulators are [G][sum len^2]), rowp ([ceil(len/128), H, len] per segment), colp ([ceil(len/32), H, len]), and
 // the ragged output (segment s's [S_s,S_s] map at sum_{s'<s} S_s'^2).  rowsum / colsum are [C, len] at C * (first
 // row of s), wt [n_seg, C].  The work lists of the four kernels follow the offsets in one int32 table:
@@ -405,7 +407,8 @@ hipError_t launch_attention128_packed(const void* q, const void* k, const void* 
 // (work item, head).  q, k [H, rows, head_dim], lse [H, rows], key_bias [rows] (read only for segments with npad > 0).
 // Ragged output: segment s owns a [Ltot, H, len_s, len_s] block at element offset Ltot * H * map_off[s], map_off[s] =
 // sum_{s'<s} len_s'^2 (64-bit: four 650M sequences of 1022 tokens are already 2.8e9 elements).  lowp: maps in the operand
-// dtype.  Every element carries the bits attn_probs_kernel gives the same sequence in a padded batch.
+// dtype.  Every element carries the bits attn_probs_kernel gives the same sequence in a padded batch: the four map kernels
+// (head_dim 64 / 128, padded / packed; all in attention.hip) are wrappers of one loop, attn_probs_rows<HD>.
 hipError_t launch_attention_probs_packed(const void* q, const void* k, const float* lse, const float* key_bias, void* probs,
                                          int H, int rows, int layer, int num_layers_total, AttnSegs segs,
                                          const unsigned long long* map_off, int n_items, int operand_dtype, bool lowp,
@@ -434,7 +437,8 @@ hipError_t launch_attention_biaskv(const void* q, const void* k, const void* vt,
 hipError_t launch_attention128(const void* q, const void* k, const void* vt, const float* key_bias,
                                const int* seq_info, void* ctx, float* lse, int B, int H, int T, int Tp,
                                int operand_dtype, hipStream_t st);
-// lowp: the maps are written in the operand dtype (probs points to fp16 / bf16 storage)
+// attention maps at head_dim 128 (attention.hip, next to the head_dim-64 ones).  lowp: the maps are written in the operand
+// dtype (probs points to fp16 / bf16 storage)
 hipError_t launch_attention_probs128(const void* q, const void* k, const float* lse, const float* key_bias,
                                      float* probs, int B, int H, int T, int layer, int num_layers_total,
                                      int operand_dtype, hipStream_t st, bool lowp = false);

@@ -125,6 +125,8 @@ _PADDED = [
     (128, 40, 1, 1, 257, 6, BF16, 4.0, False),  # 7 heads per group (6 groups, the last of 5)
     (128, 40, 48, 1, 130, 2, F16, 4.0, False),  # 20 heads per group (70 KiB LDS), C = 1920 (15B)
     (128, 40, 1, 2, 258, 2, BF16, 0.6, True),
+    # appended, so that the ids of the rows above keep their position index
+    (64, 11, 2, 3, 130, 4, F16, 4.0, True),    # B = 3, four groups, two query blocks: batch offset, group stride, chunk index
 ]
 
 
