@@ -13,10 +13,8 @@
 // attention (-10000, axial_attention.py:211-215) is scaled accordingly.
 //
 // attn_fwd_kernel: one workgroup = 4 waves = 128 query rows of one (batch, head); each wave
-// owns 32 query rows.  K / V^T tiles of 64 keys are staged HBM->LDS by global_load_lds_dwordx4
-// (double buffered; a three-buffer variant with a counted vmcnt measured 6 % slower in round 1 and was removed
-// together with the 64-rows-per-wave, 4-waves-per-SIMD and packed-fp32 variants — numbers in DESIGN.md §4.2;
-// 128-byte rows, 16-byte chunks XOR-swizzled with (row>>1)&7 on the source address and on
+// owns 32 query rows.  K / V^T tiles of 64 keys are staged HBM->LDS by LDS-DMA (buffer_load ... lds, 16 bytes per lane;
+// double buffered; 128-byte rows, 16-byte chunks XOR-swizzled with (row>>1)&7 on the source address and on
 // the read, so every ds_read_b128 is bank-conflict free).
 // The 1-D grid is mapped so that all query blocks of one (batch, head) run on ONE XCD (workgroup id
 // % 8): its K / V^T (2 x T x 128 B) is fetched into that XCD's L2 once instead of once per XCD
@@ -28,8 +26,8 @@
 //   the V^T A-operand uses the same (permuted) key order, so P goes registers -> MFMA with no
 //   LDS round trip and no lane permutation; O^T keeps the query in the lane (l&31) so the
 //   online-softmax rescale is a lane-local multiply.
-// Softmax is fp32 (exp2; see LAZY below), P is rounded to the operand dtype for the PV MFMA,
-// accumulation is fp32.
+// Softmax is fp32 (exp2, with a lazily moved exponent offset: see LAZY_LIMIT below), P is rounded to the operand
+// dtype for the PV MFMA, accumulation is fp32.
 //
 // attn_probs_rows (end of file): re-computes S tile by tile from q, k and the saved log-sum-exp and writes
 // normalised fp32 probabilities for need_head_weights=True / the contact head
@@ -39,17 +37,11 @@
 #include "common.h"
 #include "kernels.h"
 #include <math.h>
-#include <stdlib.h>
-#include <atomic>
-#include <mutex>
 #include <type_traits>
 
 namespace esmk {
 
 constexpr float LOG2E = 1.4426950408889634f;
-// round 1, end to end in one run (profiles/r1_v6_attention_variants.log): row-major grid 16.39 ms/step,
-// XCD-grouped grid 16.14 (kept), three LDS stages 17.45, split reductions 16.64 (both removed)
-constexpr int ATTN_DEFAULT_VARIANT = 1;
 constexpr int A_TILE = 64 * 128;  // bytes of one K (or V^T) tile: 64 rows x 128 B
 constexpr int A_STAGE = 2 * A_TILE + 256 + 16;  // K + V^T + 64 fp32 key-bias values + "tile has a masked key" flag
 
@@ -60,8 +52,7 @@ ESMK_DEV void attn_barrier() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// LAZY = 0: textbook online softmax (running maximum updated and O^T rescaled on every key tile).
-// LAZY = 1 (default): the exponent offset m_off is only moved when it has to be.  Scores arrive in the log2
+// Online softmax with a LAZY exponent offset: the offset m_off is only moved when it has to be.  Scores arrive in the log2
 // domain (the QKV epilogue folds log2(e) into the q scale), and -m_off rides into the accumulator as the C operand
 // of the first QK^T MFMA of each 32-key tile, so a score leaves the matrix pipe as s - m_off and the probability is
 // ONE v_exp_f32 away: no per-score subtract, no per-tile maximum, no rescale of O^T.  After the exponentials, a
@@ -74,25 +65,14 @@ ESMK_DEV void attn_barrier() {
 // exp + add + cvt (~4).
 constexpr float LAZY_LIMIT = 4096.f;
 
-// Round-2 experiments on top of LAZY = 1, measured on the bench shape and removed again (profiles/r2_attention_*):
-// alternating the two accumulators of a phase instead of two chains of four dependent MFMAs, s_setprio 1 around the
-// MFMA clusters (all within +-1 %), and a software-pipelined single-wave schedule (QK^T of tile t+1 and P.V of tile
-// t-1 issued in one basic block with the exponentials of tile t; 200+ VGPRs -> 2 waves per SIMD): 15.5 vs 13.1 ms
-// per step.  The PMC pass shows why: VALU-port time (711 cycles per wave and tile) plus matrix-pipe time (512)
-// add up to the kernel's duration — the limiter is how well the hardware interleaves the waves of a SIMD, which a
-// third resident wave helps more than in-wave scheduling.  Also measured and dropped: the row sum as 16 v_dot2c_f32_f16
-// against (1, 1) on the packed P instead of 32 v_add_f32 (481-487 vs 478.6 us on the micro-benchmark: a dot2c costs more
-// than the two adds it replaces); unrolling the key-tile loop by two so that the LDS buffer is a compile-time constant
-// (fragment addresses as lane base + immediate): 332 bytes of scratch at the 168-VGPR budget of 3 waves per SIMD; the
-// row sum on the matrix pipe (4 MFMAs of an all-ones A operand with the P fragments, Q re-read from an LDS image to free
-// the accumulator's 16 registers; exact, 168 VGPRs): 511 vs 452 us — the wave has to read the MFMA result back for the
-// overflow check before P.V may start, and that dependency costs more than the 32 adds.
-// Round 5: the same kernel with 64 query rows per wave (two 32-row blocks per wave sharing every K / V^T fragment read, one
-// barrier and one LDS-DMA round per 256 query rows, 256 registers -> 2 waves per SIMD; bit-identical, git bb4a853
-// attention_w64.hip): 13.9 vs 12.6 ms per step at B = 64, 1.48 vs 1.13 at B = 4 — the third resident wave is worth more than
-// half the LDS traffic (profiles/r5_attention_w64_and_resid_atomic_ab.log).  Removed.
-// HACK (timing experiments, results WRONG; ESMK_ATTN_HACK): 1 = no row-sum adds, 2 = no exponentials (p = score),
-// 4 = no P.V MFMAs, 8 = no QK^T MFMAs — which of VALU issue and the matrix pipe the kernel's time follows.
+// Measured and dropped (the code is in git history, the numbers in the profiles/ file named): the textbook online softmax
+// (running maximum and rescale on every key tile) this one replaced; a row-major grid, three LDS stages with a counted
+// vmcnt, split reductions, 64 rows per wave, 4 waves per SIMD, packed fp32 (r1_v6_attention_variants.log);
+// staging by global_load_lds with per-lane 64-bit addresses instead of buffer loads (~14 more VALU instructions per
+// tile); alternating accumulators, s_setprio around the MFMA clusters, a software-pipelined single-wave schedule, the row
+// sum by dot products or on the matrix pipe, the key-tile loop unrolled by two (r2_attention_*); 64 query rows per wave
+// with shared fragment reads (r5_attention_w64_and_resid_atomic_ab.log); a start-up stagger of the three workgroups that
+// share a CU, zero-sum; timing ablations that removed the row sums, the exponentials or either MFMA group (results wrong).
 // X3 (precision mode f16x3, esmk_config::weight_split 4): the context rows leave as the A operand of that mode's out-projection —
 // per head (= one 64-column K tile) hi | hi | lo, lo = T(v - T(v)), row stride 3 H 64 (the layout the LayerNorm kernel writes
 // with LnExtra::x3).  An instantiation of its own: the shipped kernel keeps its code.
@@ -110,37 +90,23 @@ struct NullKv {
     const T* v;  // [H, 64]
 };
 struct NoNullKv {};
-template <typename T, int LAZY, bool BUF, int HACK, bool X3, bool NK>
+template <typename T, bool X3, bool NK>
 ESMK_DEV void attn_fwd_body(
     const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ vt,
     const float* __restrict__ key_bias, const int* __restrict__ seq_info, T* __restrict__ ctx,
-    float* __restrict__ lse, int H, int BH, int nq, int Tlen, int Tp, int xcdmap, int fill_mode,
-    const int* __restrict__ any_pad, AttnSegs segs, int stagger, std::conditional_t<NK, NullKv<T>, NoNullKv> nkv) {
+    float* __restrict__ lse, int H, int BH, int nq, int Tlen, int Tp, int fill_mode,
+    const int* __restrict__ any_pad, AttnSegs segs, std::conditional_t<NK, NullKv<T>, NoNullKv> nkv) {
     __shared__ __attribute__((aligned(16))) char smem[2 * A_STAGE];
     using V8 = typename Op<T>::v8;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // Three workgroups share a CU, one wave of each per SIMD.  They are dispatched together and every key tile costs the
-    // same, so the three waves of a SIMD run in lockstep: all in their QK^T / PV MFMAs, then all in their exponentials —
-    // matrix pipe and VALU take turns instead of overlapping (PMC, DESIGN.md §4.2: VALU-port time + MFMA time = the
-    // kernel's duration).  `stagger` > 0 delays a workgroup by (its wave slot % 3) x stagger cycles once, at the start:
-    // the slot number (HW_ID.WAVE_ID) tells the co-resident workgroups apart.  Timing only — results do not change.
-    if (stagger > 0) {
-        __shared__ int s_slot;
-        if (tid == 0) s_slot = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4);  // HW_REG_HW_ID, bits 3:0 = wave slot
-        __syncthreads();
-        const long long wait = (long long)(s_slot % 3) * stagger;
-        if (wait > 0) {
-            const unsigned long long t0 = __builtin_readcyclecounter();
-            while ((long long)(__builtin_readcyclecounter() - t0) < wait) __builtin_amdgcn_s_sleep(8);
-        }
-    }
     const int h = lane >> 5, lm = lane & 31;
-    // workgroup id -> (batch*head, query block): ids with equal id % 8 (one XCD) share bh
+    // workgroup id -> (batch*head, query block): ids with equal id % 8 (one XCD) share bh, so the K / V^T of a
+    // (batch, head) is fetched into that XCD's L2 once
     int bh, qblk;
     {
         const int id = blockIdx.x;
-        const int bh8 = xcdmap ? (BH & ~7) : 0;  // heads covered by the XCD-grouped part of the grid
+        const int bh8 = BH & ~7;  // heads covered by the XCD-grouped part of the grid
         if (id < bh8 * nq) {
             const int r = id >> 3;
             qblk = r % nq;
@@ -212,8 +178,7 @@ ESMK_DEV void attn_fwd_body(
     // and of row r0 + 32 (round 1) — the swizzle (r >> 1) & 7 is the same for both rows.  The copies are
     // buffer_load ... lds with the per-lane byte offset FIXED and the tile advance in the scalar offset: the whole
     // per-tile address arithmetic is one s_mul on the scalar unit (instruction issue, not the matrix pipe, bounds this
-    // kernel — DESIGN.md §4.2 — and the global_load_lds form cost ~14 VALU instructions per tile for 64-bit
-    // addresses and row clamps).  K rows past the end of the sequence / segment are out of range of the K
+    // kernel: DESIGN.md §4.2).  K rows past the end of the sequence / segment are out of range of the K
     // descriptor and arrive as zeros (they are masked: use_mask is set whenever the length is not a multiple of 64).
     const int r0 = tid >> 3;
     const int kcol = ((tid & 7) ^ ((r0 >> 1) & 7)) * 8;  // element offset of the chunk inside a 64-element row
@@ -233,19 +198,10 @@ ESMK_DEV void attn_fwd_body(
         char* base = smem + buf * A_STAGE;
         const int k0 = kt * 64;
         const unsigned sk_off = (unsigned)kt * 8192u, sv_off = (unsigned)kt * 128u;
-        if constexpr (BUF) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(kdesc, (lds_ptr)(base + (wave * 64) * 16), 16, kvo0, sk_off, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(vdesc, (lds_ptr)(base + A_TILE + (wave * 64) * 16), 16, vvo0, sv_off, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(kdesc, (lds_ptr)(base + (256 + wave * 64) * 16), 16, kvo1, sk_off, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(vdesc, (lds_ptr)(base + A_TILE + (256 + wave * 64) * 16), 16, vvo1, sv_off, 0, 0);
-        } else {  // round-1 form (A/B: ESMK_ATTN bit 3): global_load_lds with per-lane 64-bit addresses, rows clamped
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int kr = min(k0 + r0 + 32 * j, Tseg - 1);
-                glds16(kb + (size_t)kr * 64 + kcol, base + (j * 256 + wave * 64) * 16);
-                glds16(vb + (size_t)(r0 * Tp + kcol + 32 * j * Tp) + k0, base + A_TILE + (j * 256 + wave * 64) * 16);
-            }
-        }
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(kdesc, (lds_ptr)(base + (wave * 64) * 16), 16, kvo0, sk_off, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(vdesc, (lds_ptr)(base + A_TILE + (wave * 64) * 16), 16, vvo0, sv_off, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(kdesc, (lds_ptr)(base + (256 + wave * 64) * 16), 16, kvo1, sk_off, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(vdesc, (lds_ptr)(base + A_TILE + (256 + wave * 64) * 16), 16, vvo1, sv_off, 0, 0);
         if (use_mask && tid < 64) {
             const int key = k0 + tid;
             float bv = -INFINITY;  // keys past the end of the row: excluded
@@ -275,11 +231,11 @@ ESMK_DEV void attn_fwd_body(
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
     // Scores are in the log2 domain.  m_off: the offset the probabilities of this row are currently expressed
-    // against (finite; LAZY = 0 keeps it at the running maximum); m_ok: the row has seen a finite score.
+    // against (finite); m_ok: the row has seen a finite score.
     float m_off = 0.f;
     bool m_ok = false;
     float lsum = 0.f;  // this lane's share of the running denominator
-    f32x16 negm;       // -m_off in every slot: C operand of the first MFMA of a score tile (LAZY)
+    f32x16 negm;       // -m_off in every slot: C operand of the first MFMA of a score tile
 #pragma unroll
     for (int r = 0; r < 16; ++r) negm[r] = 0.f;
 
@@ -300,33 +256,16 @@ ESMK_DEV void attn_fwd_body(
         f32x16 st[2];
 #pragma unroll
         for (int t2 = 0; t2 < 2; ++t2) {
-            if constexpr (HACK & 8) {
-                st[t2] = negm;
+            st[t2] = Op<T>::mma_keep_c(*reinterpret_cast<const V8*>(sk + t2 * 4096 + lrow + xo[0]), qf[0], negm);
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const V8 kf = *reinterpret_cast<const V8*>(sk + t2 * 4096 + lrow + xo[ks]);
-                    st[t2][ks] += (float)kf[0] * (float)qf[ks][0];
-                }
-            } else if constexpr (LAZY) {
-                st[t2] = Op<T>::mma_keep_c(*reinterpret_cast<const V8*>(sk + t2 * 4096 + lrow + xo[0]), qf[0], negm);
-#pragma unroll
-                for (int ks = 1; ks < 4; ++ks) {
-                    const V8 kf = *reinterpret_cast<const V8*>(sk + t2 * 4096 + lrow + xo[ks]);
-                    st[t2] = Op<T>::mma(kf, qf[ks], st[t2]);
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) st[t2][r] = 0.f;
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const V8 kf = *reinterpret_cast<const V8*>(sk + t2 * 4096 + lrow + xo[ks]);
-                    st[t2] = Op<T>::mma(kf, qf[ks], st[t2]);
-                }
+            for (int ks = 1; ks < 4; ++ks) {
+                const V8 kf = *reinterpret_cast<const V8*>(sk + t2 * 4096 + lrow + xo[ks]);
+                st[t2] = Op<T>::mma(kf, qf[ks], st[t2]);
             }
         }
         // ---- key padding / tail mask (multihead_attention.py:368-374) -----------------------
         if (use_mask && __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(sk + 2 * A_TILE + 256)) != 0) {
-            const float fillv = -10000.f * LOG2E - (LAZY ? m_off : 0.f);  // masked_fill(-10000), same domain as st
+            const float fillv = -10000.f * LOG2E - m_off;  // masked_fill(-10000), same domain as st
 #pragma unroll
             for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
@@ -340,30 +279,23 @@ ESMK_DEV void attn_fwd_body(
         // ---- softmax numerators (fp32) -----------------------------------------------------
         V8 pf[4];
         bool exact = true;
-        if constexpr (LAZY) {
-            // wave uniform: every row has a finite offset -> try the tile without touching the offset
-            if (__builtin_amdgcn_ballot_w64(!m_ok) == 0) {
-                // one dependent chain of plain v_add_f32: two chains get SLP-packed into v_pk_add_f32, which costs
-                // more issue time next to MFMAs than the two adds it replaces (MI355X_MICROARCH.md, price list)
-                float ps = 0.f;
+        // wave uniform: every row has a finite offset -> try the tile without touching the offset
+        if (__builtin_amdgcn_ballot_w64(!m_ok) == 0) {
+            // one dependent chain of plain v_add_f32: two chains get SLP-packed into v_pk_add_f32, which costs
+            // more issue time next to MFMAs than the two adds it replaces (MI355X_MICROARCH.md, price list)
+            float ps = 0.f;
 #pragma unroll
-                for (int t2 = 0; t2 < 2; ++t2)
+            for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
-                    for (int ks = 0; ks < 2; ++ks)
+                for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const float p = (HACK & 2) ? st[t2][8 * ks + e] : __builtin_amdgcn_exp2f(st[t2][8 * ks + e]);
-                            if constexpr (HACK & 1) {
-                                if (e == 0 && ks == 0) ps += p;
-                            } else {
-                                ps += p;
-                            }
-                            pf[2 * t2 + ks][e] = Op<T>::from(p);
-                        }
-                exact = __builtin_amdgcn_ballot_w64(!(ps <= LAZY_LIMIT)) != 0;  // also catches inf / NaN
-                if constexpr (HACK != 0) exact = false;
-                if (!exact) lsum += ps;
-            }
+                    for (int e = 0; e < 8; ++e) {
+                        const float p = __builtin_amdgcn_exp2f(st[t2][8 * ks + e]);
+                        ps += p;
+                        pf[2 * t2 + ks][e] = Op<T>::from(p);
+                    }
+            exact = __builtin_amdgcn_ballot_w64(!(ps <= LAZY_LIMIT)) != 0;  // also catches inf / NaN
+            if (!exact) lsum += ps;
         }
         if (exact) {
             // maximum of this tile's (offset) scores over the row: 32 in this lane, 32 in lane ^ 32
@@ -374,17 +306,8 @@ ESMK_DEV void attn_fwd_body(
                 for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[t2][r]);
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
             // shift of the offset: up to the new maximum; the first finite tile of a row sets it outright
-            float delta, alpha;
-            if constexpr (LAZY) {
-                delta = m_ok ? fmaxf(mx, 0.f) : (mx == -INFINITY ? 0.f : mx);
-                alpha = m_ok ? __builtin_amdgcn_exp2f(-delta) : 1.f;  // nothing accumulated yet: O^T = 0, lsum = 0
-            } else {
-                // st holds raw scores: the offset becomes the running maximum itself
-                const float m_new = m_ok ? fmaxf(m_off, mx) : (mx == -INFINITY ? 0.f : mx);
-                delta = m_new;  // subtracted from the raw scores below
-                alpha = m_ok ? __builtin_amdgcn_exp2f(m_off - m_new) : 1.f;
-                m_off = m_new;
-            }
+            const float delta = m_ok ? fmaxf(mx, 0.f) : (mx == -INFINITY ? 0.f : mx);
+            const float alpha = m_ok ? __builtin_amdgcn_exp2f(-delta) : 1.f;  // nothing accumulated yet: O^T = 0, lsum = 0
             m_ok = m_ok || (mx != -INFINITY);
             float ps = 0.f;
 #pragma unroll
@@ -400,17 +323,15 @@ ESMK_DEV void attn_fwd_body(
             lsum = lsum * alpha + ps;
             // the first tile of every row (alpha = 1 by definition) and exact tiles in which no row's offset moved
             // skip the 32 multiplies: multiplying by 1.0 changes no bit
-            if (!LAZY || __builtin_amdgcn_ballot_w64(alpha != 1.f) != 0) {
+            if (__builtin_amdgcn_ballot_w64(alpha != 1.f) != 0) {
 #pragma unroll
                 for (int d = 0; d < 2; ++d)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
             }
-            if constexpr (LAZY) {
-                m_off += delta;
+            m_off += delta;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) negm[r] = -m_off;
-            }
+            for (int r = 0; r < 16; ++r) negm[r] = -m_off;
         }
         // ---- O^T += V^T . P^T ----------------------------------------------------------------
 #pragma unroll
@@ -418,8 +339,7 @@ ESMK_DEV void attn_fwd_body(
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
                 const V8 vf = *reinterpret_cast<const V8*>(sv + d * 4096 + lrow + xo[kk]);
-                if constexpr (HACK & 4) o[d][kk] += (float)vf[0] * (float)pf[kk][0];
-                else o[d] = Op<T>::mma(vf, pf[kk], o[d]);
+                o[d] = Op<T>::mma(vf, pf[kk], o[d]);
             }
         }  // wave_active
         wait_vmcnt0();
@@ -502,24 +422,22 @@ ESMK_DEV void attn_fwd_body(
     if (lse != nullptr && h == 0 && qrow < Tseg) lse[rbase + qrow] = wave_active ? m_off + log2f(ltot) : 0.f;
 }
 
-template <typename T, int LAZY, bool BUF = true, int HACK = 0, bool X3 = false>
+template <typename T, bool X3 = false>
 __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
     const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ vt,
     const float* __restrict__ key_bias, const int* __restrict__ seq_info, T* __restrict__ ctx,
-    float* __restrict__ lse, int H, int BH, int nq, int Tlen, int Tp, int xcdmap, int fill_mode,
-    const int* __restrict__ any_pad, AttnSegs segs, int stagger) {
-    attn_fwd_body<T, LAZY, BUF, HACK, X3, false>(q, k, vt, key_bias, seq_info, ctx, lse, H, BH, nq, Tlen, Tp, xcdmap, fill_mode,
-                                                 any_pad, segs, stagger, NoNullKv());
+    float* __restrict__ lse, int H, int BH, int nq, int Tlen, int Tp, int fill_mode,
+    const int* __restrict__ any_pad, AttnSegs segs) {
+    attn_fwd_body<T, X3, false>(q, k, vt, key_bias, seq_info, ctx, lse, H, BH, nq, Tlen, Tp, fill_mode, any_pad, segs, NoNullKv());
 }
 
-// ESM-1: the shipped form (lazy offset, buffer-load staging) of a padded batch with the null key / value pair (NK above)
+// ESM-1: a padded batch with the null key / value pair (NK above)
 template <typename T>
 __global__ __launch_bounds__(256, 3) void attn_fwd_nullkv_kernel(
     const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ vt,
     const float* __restrict__ key_bias, const int* __restrict__ seq_info, T* __restrict__ ctx,
     float* __restrict__ lse, int H, int BH, int nq, int Tlen, int Tp, NullKv<T> nkv) {
-    attn_fwd_body<T, 1, true, 0, false, true>(q, k, vt, key_bias, seq_info, ctx, lse, H, BH, nq, Tlen, Tp, 1, 0, nullptr,
-                                              AttnSegs(), 0, nkv);
+    attn_fwd_body<T, false, true>(q, k, vt, key_bias, seq_info, ctx, lse, H, BH, nq, Tlen, Tp, 0, nullptr, AttnSegs(), nkv);
 }
 
 // Self-test of Op<T>::mma_keep_c (common.h): the inline-asm MFMA with an early-clobber destination that keeps its C
@@ -561,15 +479,6 @@ static hipError_t launch_attention_impl(const void* q, const void* k, const void
                                         const int* seq_info, void* ctx, float* lse, int B, int H, int T, int Tp,
                                         int operand_dtype, int fill_mode, const int* any_pad, hipStream_t st,
                                         AttnSegs segs = AttnSegs(), int n_items = 0, bool x3 = false);
-
-// start-up stagger of the co-resident workgroups in shader cycles per wave slot (attn_fwd_kernel): zero-sum on the GPU,
-// the shipped library passes 0
-constexpr int kAttnStaggerDefault = 0;
-#ifdef ESMK_EXPERIMENTS
-// < 0 = read ESMK_ATTN_STAGGER on the first launch; esmk_debug_set("attn_stagger", cycles)
-static std::atomic<int> g_attn_stagger{-1};
-void attention_set_stagger(int cycles) { g_attn_stagger = cycles < 0 ? 0 : cycles; }
-#endif
 
 hipError_t launch_attention(const void* q, const void* k, const void* vt, const float* key_bias,
                             const int* seq_info, void* ctx, float* lse, int B, int H, int T, int Tp,
@@ -630,57 +539,18 @@ static hipError_t launch_attention_impl(const void* q, const void* k, const void
     if (x3) {  // f16x3 precision mode: fp16 operands, padded batches (engine.hip)
         if (operand_dtype != ESMK_DT_F16 || segs.work != nullptr || fill_mode != 0) return hipErrorInvalidValue;
         const int nq3 = (T + 127) / 128;
-        hipLaunchKernelGGL((attn_fwd_kernel<_Float16, 1, true, 0, true>), dim3(nq3 * B * H), dim3(256), 0, st, (const _Float16*)q,
-                           (const _Float16*)k, (const _Float16*)vt, key_bias, seq_info, (_Float16*)ctx, lse, H, B * H, nq3, T, Tp, 1, 0,
-                           any_pad, segs, 0);
+        hipLaunchKernelGGL((attn_fwd_kernel<_Float16, true>), dim3(nq3 * B * H), dim3(256), 0, st, (const _Float16*)q,
+                           (const _Float16*)k, (const _Float16*)vt, key_bias, seq_info, (_Float16*)ctx, lse, H, B * H, nq3, T, Tp, 0,
+                           any_pad, segs);
         return hipGetLastError();
     }
     const int nq = segs.work != nullptr ? n_items : (T + 127) / 128;
     dim3 grid(nq * B * H);
-    // ESMK_ATTN (read once): bit 0 XCD-grouped grid (default on), bit 1 = textbook online softmax instead of the
-    // lazy-offset one, bit 3 = round-1 staging by global_load_lds (A/B measurements; all are exact softmax)
-    static const int var = [] {
-        const char* e = getenv("ESMK_ATTN");
-        return e ? atoi(e) : ATTN_DEFAULT_VARIANT;
-    }();
-#ifdef ESMK_EXPERIMENTS
-    static std::once_flag stagger_once;  // launches may come from several host threads
-    std::call_once(stagger_once, [] {
-        if (g_attn_stagger.load() < 0) {
-            const char* e = getenv("ESMK_ATTN_STAGGER");
-            g_attn_stagger = e ? atoi(e) : kAttnStaggerDefault;
-        }
-    });
-    const int stagger = g_attn_stagger.load();
-#else
-    const int stagger = kAttnStaggerDefault;
-#endif
-#define ESMK_ATTN_LAUNCH(TT, LZ, BF, ...)                                                                      \
-    hipLaunchKernelGGL((attn_fwd_kernel<TT, LZ, BF, ##__VA_ARGS__>), grid, dim3(256), 0, st, (const TT*)q, (const TT*)k,   \
-                       (const TT*)vt, key_bias, seq_info, (TT*)ctx, lse, H, B * H, nq, T, Tp, var & 1, fill_mode, any_pad, segs, stagger)
-    if (operand_dtype == ESMK_DT_BF16) {
-        if (var & 2) ESMK_ATTN_LAUNCH(__bf16, 0, true);
-        else ESMK_ATTN_LAUNCH(__bf16, 1, true);
-    } else {
-#ifdef ESMK_EXPERIMENTS  // parts of the kernel removed (results wrong): experiment builds only (common.h)
-        static const int hack = [] { const char* e = getenv("ESMK_ATTN_HACK"); return e ? atoi(e) : 0; }();
-#else
-        constexpr int hack = 0;
-#endif
-        if (hack != 0) {
-#ifdef ESMK_EXPERIMENTS
-            if (hack == 1) ESMK_ATTN_LAUNCH(_Float16, 1, true, 1);
-            else if (hack == 2) ESMK_ATTN_LAUNCH(_Float16, 1, true, 2);
-            else if (hack == 3) ESMK_ATTN_LAUNCH(_Float16, 1, true, 3);
-            else if (hack == 4) ESMK_ATTN_LAUNCH(_Float16, 1, true, 4);
-            else if (hack == 8) ESMK_ATTN_LAUNCH(_Float16, 1, true, 8);
-            else if (hack == 12) ESMK_ATTN_LAUNCH(_Float16, 1, true, 12);
-            else return hipErrorInvalidValue;
-#endif
-        } else if (var & 2) ESMK_ATTN_LAUNCH(_Float16, 0, true);
-        else if (var & 8) ESMK_ATTN_LAUNCH(_Float16, 1, false);
-        else ESMK_ATTN_LAUNCH(_Float16, 1, true);
-    }
+#define ESMK_ATTN_LAUNCH(TT)                                                                                         \
+    hipLaunchKernelGGL((attn_fwd_kernel<TT>), grid, dim3(256), 0, st, (const TT*)q, (const TT*)k, (const TT*)vt, key_bias, \
+                       seq_info, (TT*)ctx, lse, H, B * H, nq, T, Tp, fill_mode, any_pad, segs)
+    if (operand_dtype == ESMK_DT_BF16) ESMK_ATTN_LAUNCH(__bf16);
+    else ESMK_ATTN_LAUNCH(_Float16);
 #undef ESMK_ATTN_LAUNCH
     return hipGetLastError();
 }

@@ -15,18 +15,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define ESMK_DEV __device__ __forceinline__
 
-// Timing experiments that deliberately compute WRONG results (kernels with their MFMAs, exponentials, LDS-DMA, fragment
-// reads or epilogue removed: gemm8 DBG / gemm9 VAR bits 8 .. 128 and 1024, ESMK_ATTN_HACK, the producer's lnf_dbg) exist
-// only in builds made with ESMK_HIPCC_EXTRA="-DESMK_EXPERIMENTS" (esm_amd/build.py: part of the source hash, so such a
-// library never passes for the shipped one).  In the shipped library every run-time switch leaves results unchanged.
-// The same builds carry the result-neutral experiments the notebook closed as zero-sum: every gemm9 VAR
-// other than 0, the start-up delays of the residual GEMMs and of the attention workgroups with their esmk_debug_set keys.
-#ifdef ESMK_EXPERIMENTS
-constexpr bool kExperiments = true;
-#else
-constexpr bool kExperiments = false;
-#endif
-
 // Operand-type traits: T is the MFMA operand element (_Float16 or __bf16).
 template <typename T>
 struct Op;

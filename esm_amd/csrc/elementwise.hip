@@ -5,7 +5,6 @@
 #include "common.h"
 #include "kernels.h"
 #include <math.h>
-#include <stdlib.h>
 
 #include <algorithm>
 #include <type_traits>
@@ -332,18 +331,19 @@ hipError_t launch_sinus_table(const float* freq, float* table, int T, int half, 
 // lane), two-pass mean / variance in fp32, 16-byte loads and 8/16-byte stores.
 // Algorithmic traffic per row: 4E read + 2E (operand dtype) and/or 4E (fp32) written.
 // ---------------------------------------------------------------------------------------------
-// VAR (tools/microbench.py --only ln sweeps it; the engine uses LN_DEFAULT_VARIANT):
-//   bit 0: two rows per wave (both rows' loads in flight before the first reduction)
-//   bit 1: non-temporal stores (the normalised rows are consumed by the next kernel from HBM/MALL,
-//          not from this CU's cache)
-//   bit 2: non-temporal loads
-template <typename T, int NCH, int VAR>
+// FAST (the engine's form): two rows per wave (both rows' loads in flight before the first reduction), non-temporal
+// stores (the normalised rows are consumed by the next kernel from HBM/MALL, not from this CU's cache) and non-temporal
+// loads.  !FAST: one row per wave, plain loads and stores — the simple form the tests hold the engine's against
+// (selector 0 of the op entries).  Measured on MI355X, 65536 x 1280 rows (profiles/r1_v3_microbench.log): plain
+// 3.65 TB/s of algorithmic traffic, two rows per wave 5.34, + non-temporal stores 5.57, + non-temporal loads 6.02;
+// the in-between forms are in git history.
+template <typename T, int NCH, bool FAST>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x,
                                                          const float* __restrict__ gamma,
                                                          const float* __restrict__ beta,
                                                          T* __restrict__ y, float* __restrict__ y32,
                                                          int rows, int E, LnExtra ex) {
-    constexpr int RPW = (VAR & 1) ? 2 : 1;
+    constexpr int RPW = FAST ? 2 : 1;
     const int lane = threadIdx.x & 63;
     const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW;
     if (row0 >= rows) return;
@@ -358,7 +358,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         for (int i = 0; i < NCH; ++i) {
             const int c = lane + 64 * i;
             if (c < e4) {
-                if constexpr (VAR & 4) v[r][i] = __builtin_nontemporal_load(xr + c);
+                if constexpr (FAST) v[r][i] = __builtin_nontemporal_load(xr + c);
                 else v[r][i] = xr[c];
             } else {
                 v[r][i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -435,12 +435,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 #pragma unroll
                     for (int e = 0; e < 4; ++e) pk[e] = Op<T>::from(o[e]);
                     auto* dst = reinterpret_cast<typename Op<T>::v4*>(y + (size_t)row * (ex.ldy > 0 ? ex.ldy : E) + c * 4);
-                    if constexpr (VAR & 2) __builtin_nontemporal_store(pk, dst);
+                    if constexpr (FAST) __builtin_nontemporal_store(pk, dst);
                     else *dst = pk;
                 }
                 if (y32) {
                     auto* dst = reinterpret_cast<f32x4*>(y32 + (size_t)row * E + c * 4);
-                    if constexpr (VAR & 2) __builtin_nontemporal_store(o, dst);
+                    if constexpr (FAST) __builtin_nontemporal_store(o, dst);
                     else *dst = o;
                 }
             }
@@ -448,18 +448,14 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     }
 }
 
-// measured on MI355X, 65536 x 1280 rows (profiles/r1_v3_microbench.log): variant 0 3.65 TB/s,
-// 1 5.34, 3 5.57, 7 6.02 TB/s of algorithmic traffic
-constexpr int LN_DEFAULT_VARIANT = 7;
-
-template <typename T, int VAR>
-static hipError_t ln_dispatch_v(const float* x, const float* g, const float* b, void* y, float* y32,
-                                int rows, int E, LnExtra ex, hipStream_t st) {
-    constexpr int RPW = (VAR & 1) ? 2 : 1;
+template <typename T, bool FAST>
+static hipError_t ln_dispatch(const float* x, const float* g, const float* b, void* y, float* y32,
+                              int rows, int E, LnExtra ex, hipStream_t st) {
+    constexpr int RPW = FAST ? 2 : 1;
     const unsigned blocks = (unsigned)((rows + 4 * RPW - 1) / (4 * RPW));
     T* yt = reinterpret_cast<T*>(y);
 #define ESMK_LN(N)                                                                                   \
-    hipLaunchKernelGGL((layernorm_kernel<T, N, VAR>), dim3(blocks), dim3(256), 0, st, x, g, b, yt, y32, \
+    hipLaunchKernelGGL((layernorm_kernel<T, N, FAST>), dim3(blocks), dim3(256), 0, st, x, g, b, yt, y32, \
                        rows, E, ex)
     if (E <= 512) ESMK_LN(2);
     else if (E <= 1280) ESMK_LN(5);
@@ -468,21 +464,6 @@ static hipError_t ln_dispatch_v(const float* x, const float* g, const float* b, 
     else return hipErrorInvalidValue;
 #undef ESMK_LN
     return hipGetLastError();
-}
-
-template <typename T>
-static hipError_t ln_dispatch(const float* x, const float* g, const float* b, void* y, float* y32,
-                              int rows, int E, int variant, LnExtra ex, hipStream_t st) {
-    switch (variant) {
-        case 0: return ln_dispatch_v<T, 0>(x, g, b, y, y32, rows, E, ex, st);
-        case 1: return ln_dispatch_v<T, 1>(x, g, b, y, y32, rows, E, ex, st);
-        case 2: return ln_dispatch_v<T, 2>(x, g, b, y, y32, rows, E, ex, st);
-        case 3: return ln_dispatch_v<T, 3>(x, g, b, y, y32, rows, E, ex, st);
-        case 5: return ln_dispatch_v<T, 5>(x, g, b, y, y32, rows, E, ex, st);
-        case 6: return ln_dispatch_v<T, 6>(x, g, b, y, y32, rows, E, ex, st);
-        case 7: return ln_dispatch_v<T, 7>(x, g, b, y, y32, rows, E, ex, st);
-    }
-    return hipErrorInvalidValue;
 }
 
 hipError_t launch_layernorm(const float* x, const float* gamma, const float* beta, void* y,
@@ -494,17 +475,16 @@ hipError_t launch_layernorm_ex(const float* x, const float* gamma, const float* 
                                float* y32, int rows, int E, int operand_dtype, LnExtra ex,
                                hipStream_t st) {
     if (E % 4 != 0 || rows <= 0) return hipErrorInvalidValue;
-    // bits 8..11 of operand_dtype: kernel variant + 1 (micro-benchmarks); 0 = engine default
-    static const int env_variant = [] {
-        const char* e = getenv("ESMK_LN");
-        return e ? atoi(e) : LN_DEFAULT_VARIANT;
-    }();
+    // bits 8..11 of operand_dtype: 0 = the engine's form, else kernel form + 1 (tests): 1 = the plain form, 8 = the engine's
     const int vsel = (operand_dtype >> 8) & 0xf;
-    const int variant = vsel ? vsel - 1 : env_variant;
+    if (vsel != 0 && vsel != 1 && vsel != 8) return hipErrorInvalidValue;
+    const bool fast = vsel != 1;
     operand_dtype &= 0xff;
     if (operand_dtype == ESMK_DT_BF16)
-        return ln_dispatch<__bf16>(x, gamma, beta, y, y32, rows, E, variant, ex, st);
-    return ln_dispatch<_Float16>(x, gamma, beta, y, y32, rows, E, variant, ex, st);
+        return fast ? ln_dispatch<__bf16, true>(x, gamma, beta, y, y32, rows, E, ex, st)
+                    : ln_dispatch<__bf16, false>(x, gamma, beta, y, y32, rows, E, ex, st);
+    return fast ? ln_dispatch<_Float16, true>(x, gamma, beta, y, y32, rows, E, ex, st)
+                : ln_dispatch<_Float16, false>(x, gamma, beta, y, y32, rows, E, ex, st);
 }
 
 // ---------------------------------------------------------------------------------------------

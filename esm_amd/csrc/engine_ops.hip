@@ -17,9 +17,17 @@ extern "C" {
 // ---------------------------------------------------------------------------------------------
 // single-kernel entry points
 // ---------------------------------------------------------------------------------------------
+// LayerNorm has two kernel forms (elementwise.hip).  Bits 8..11 of operand_dtype: 0 = default (the engine's form), else
+// variant + 1 with variant 0 = the plain form and 7 = the engine's; variants 1 .. 6 were experiments that are gone.
+static bool ln_form_ok(int operand_dtype) {
+    const int sel = (operand_dtype >> 8) & 0xf;
+    return sel == 0 || sel == 1 || sel == 8;
+}
+
 int esmk_op_layernorm(const float* x_dev, const float* gamma_dev, const float* beta_dev,
                       void* y_dev, float* y32_dev, int rows, int E, int operand_dtype,
                       void* stream) {
+    if (!ln_form_ok(operand_dtype)) return fail("esmk_op_layernorm: variant must be default, 0 or 7 (operand_dtype bits 8..11 = variant + 1)");
     ESMK_TRY(launch_layernorm(x_dev, gamma_dev, beta_dev, y_dev, y32_dev, rows, E, operand_dtype,
                               (hipStream_t)stream));
     return 0;
@@ -51,7 +59,7 @@ int esmk_op_linear(const void* a_dev, const void* w_dev, const float* bias_dev, 
     if (operand_dtype & 0x200) g.force_old = 1;      // test hook: one-tile-per-workgroup 256x256 kernel
     g.panel_c = (operand_dtype >> 20) & 0x3f;         // tile-order experiments (tools/microbench.py)
     g.half_m = ((operand_dtype >> 28) & 3) == 1 ? 1 : (((operand_dtype >> 28) & 3) == 2 ? -1 : 0);  // 128-row tiles: force / never
-    g.dbg = (operand_dtype >> 12) & 0xff;             // timing experiments (tools/microbench.py)
+    if (operand_dtype & 0xff000) return fail("esmk_op_linear: bits 12..19 of operand_dtype must be 0 (they selected timing experiments that are gone)");
     operand_dtype &= 0xff;
     ESMK_TRY(launch_gemm(g, epilogue, operand_dtype, (hipStream_t)stream));
     return 0;
@@ -97,6 +105,7 @@ int esmk_op_linear_f32(const float* a_dev, int lda, const float* w_dev, const fl
 int esmk_op_layernorm_ex(const float* x_dev, const float* gamma_dev, const float* beta_dev, void* y_dev, float* y32_dev,
                          int rows, int E, int operand_dtype, const float* row_keep_dev, int map_R, int map_C, int ldy, int x3,
                          float eps, void* stream) {
+    if (!ln_form_ok(operand_dtype)) return fail("esmk_op_layernorm_ex: variant must be default, 0 or 7 (operand_dtype bits 8..11 = variant + 1)");
     if (!x_dev || !gamma_dev || !beta_dev || (!y_dev && !y32_dev)) return fail("esmk_op_layernorm_ex: null argument");
     if (rows <= 0 || E <= 0) return fail("esmk_op_layernorm_ex: rows and E must be positive");
     if (E % 4 != 0 || E > 5120) return fail("esmk_op_layernorm_ex: need E % 4 == 0 and E <= 5120");
@@ -276,19 +285,13 @@ int esmk_debug_set(const char* key, double value) {
         g_rows_contacts_own_groups = value != 0.0;
         return 0;
     }
-#ifdef ESMK_EXPERIMENTS
-    if (strcmp(key, "attn_stagger") == 0) {
-        attention_set_stagger((int)value);
-        return 0;
-    }
-#endif
     return fail("esmk_debug_set: unknown key");
 }
 
 int esmk_debug_gemm_impl(int impl, int variant) {
     if (impl != 8 && impl != 9 && impl != 0) return fail("esmk_debug_gemm_impl: impl must be 8, 9 or 0 (automatic choice)");
     if (!gemm_set_impl(impl, variant))
-        return fail("esmk_debug_gemm_impl: variant must be 0 (the gemm9 variants exist in ESMK_EXPERIMENTS builds only)");
+        return fail("esmk_debug_gemm_impl: variant must be 0 (gemm9 has one form)");
     return 0;
 }
 
@@ -322,7 +325,7 @@ int esmk_debug_gemm_plan(int M, int N, int K, int epilogue, int flags, int32_t o
     const GemmPlan pl = gemm_plan(g, epilogue);
     out[0] = pl.kernel;
     out[1] = pl.half_m;
-    out[2] = pl.variant;
+    out[2] = 0;  // was: the gemm9 variant
     out[3] = 0;
     return 0;
 }

@@ -42,9 +42,7 @@ constexpr int G_TILE_BYTES = G_BM * G_BK * 2;  // 32 KiB per operand per stage
 constexpr int G_STAGE_BYTES = 2 * G_TILE_BYTES;
 constexpr int G_LDS_BYTES = 2 * G_STAGE_BYTES;  // 128 KiB
 
-// DBG != 0 builds timing-experiment variants (tools/microbench.py --only dbg), results are wrong:
-// bit 0 no staging in the loop, bit 1 no vmcnt wait / barrier, bit 2 MFMA only (no LDS reads).
-template <typename T, int EPI, int DBG = 0>
+template <typename T, int EPI>
 __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -68,7 +66,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs p) {
     for (int j = 0; j < 4; ++j) {
         const int pos = j * 512 + tid;
         const int r = pos >> 3, s = pos & 7;
-        const int c = (DBG & 16) ? s : (s ^ ((r >> 1) & 7));
+        const int c = s ^ ((r >> 1) & 7);
         const int ra = min(m0 + r, p.M - 1);
         const int rw = min(n0 + r, p.N - 1);
         ga[j] = A + (size_t)ra * p.K + c * 8;
@@ -79,7 +77,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs p) {
     // instructions per wave, 16 KiB per workgroup); a K tile is 4 parts.
     auto stage_part = [&](int buf, int kt, int j) {
         char* base = smem + buf * G_STAGE_BYTES;
-        const int ko = (DBG & 32) ? 0 : kt * G_BK;  // DBG 32: re-read K slab 0 (all L2 hits)
+        const int ko = kt * G_BK;
         glds16(ga[j] + ko, base + (j * 512 + wave * 64) * 16);
         glds16(gw[j] + ko, base + G_TILE_BYTES + (j * 512 + wave * 64) * 16);
     };
@@ -159,11 +157,10 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs p) {
     };
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = kt & 1;
-        const bool more = (kt + 1 < nk) && !(DBG & 1);
-        // The LDS-DMA instructions of the next tile are spread over the MFMA groups (SCHED digits =
-        // parts issued in front of group 0..3): a burst of all 64 per CU at the top of the K step
-        // parks every wave in the memory-issue queue while the matrix pipe idles.
-        constexpr int SCHED = (DBG & 64) ? 0x4000 : ((DBG & 128) ? 0x2200 : 0x2110);
+        const bool more = kt + 1 < nk;
+        // The LDS-DMA instructions of the next tile are spread over the MFMA groups (2, 1, 1, 0 parts in front of
+        // group 0..3): a burst of all 64 per CU at the top of the K step parks every wave in the memory-issue queue
+        // while the matrix pipe idles.
         auto stage_some = [&](int first, int count) {
             if (more) {
 #pragma unroll
@@ -171,47 +168,28 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs p) {
                     if (j >= first && j < first + count) stage_part(cur ^ 1, kt + 1, j);
             }
         };
-        constexpr int C0 = (SCHED >> 12) & 15, C1 = (SCHED >> 8) & 15, C2 = (SCHED >> 4) & 15, C3 = SCHED & 15;
-        static_assert(C0 + C1 + C2 + C3 == 4, "every part exactly once");
         const char* sb = smem + cur * G_STAGE_BYTES;
-        if constexpr (DBG & 8) {  // timing experiment: staging only
-            stage_some(0, 4);
-            wait_vmcnt0();
-            __syncthreads();
-            continue;
-        }
-        if constexpr (DBG & 4) {  // timing experiment: MFMA only
-            mma8(f0, 0);
-            mma8(f0, 1);
-            mma8(f0, 2);
-            mma8(f0, 3);
-            if constexpr (!(DBG & 2)) __syncthreads();
-            continue;
-        }
         arrived(f0);
         read_frags(f1, sb, 1);
-        stage_some(0, C0);
+        stage_some(0, 2);
         __builtin_amdgcn_sched_barrier(0);
         mma8(f0, 0);
         __builtin_amdgcn_sched_barrier(0);
         arrived(f1);
         read_frags(f0, sb, 2);
-        stage_some(C0, C1);
+        stage_some(2, 1);
         __builtin_amdgcn_sched_barrier(0);
         mma8(f1, 1);
         __builtin_amdgcn_sched_barrier(0);
         arrived(f0);
         read_frags(f1, sb, 3);
-        stage_some(C0 + C1, C2);
+        stage_some(3, 1);
         __builtin_amdgcn_sched_barrier(0);
         mma8(f0, 2);
         __builtin_amdgcn_sched_barrier(0);
         arrived(f1);
-        stage_some(C0 + C1 + C2, C3);
-        if constexpr (!(DBG & 2)) {
-            wait_vmcnt0();     // next tile has landed (issued one whole K step ago)
-            __syncthreads();   // ... for every wave, and every wave is done reading this buffer
-        }
+        wait_vmcnt0();     // next tile has landed (issued one whole K step ago)
+        __syncthreads();   // ... for every wave, and every wave is done reading this buffer
         read_frags(f0, smem + (cur ^ 1) * G_STAGE_BYTES, 0);  // (harmless stale read after the last tile)
         __builtin_amdgcn_sched_barrier(0);
         mma8(f1, 3);
@@ -287,10 +265,10 @@ __global__ __launch_bounds__(256) void gemm64_kernel(GemmArgs p) {
 // --------------------------------------------------------------------------------------------
 // host launchers
 // --------------------------------------------------------------------------------------------
-template <typename T, int EPI, int DBG = 0>
+template <typename T, int EPI>
 static hipError_t launch_fast(const GemmArgs& p, hipStream_t st) {
     static bool attr_set = false;
-    auto kern = gemm256_kernel<T, EPI, DBG>;
+    auto kern = gemm256_kernel<T, EPI>;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS_BYTES);
@@ -319,26 +297,6 @@ int gemm_tile_kernel(const GemmArgs& p, int epi) {
 
 template <typename T>
 static hipError_t dispatch256(const GemmArgs& p, int epi, hipStream_t st) {
-#ifdef ESMK_EXPERIMENTS
-    if (p.dbg && epi == EPI_STORE_T) {  // timing experiments (results wrong)
-        switch (p.dbg) {
-            case 1: return launch_fast<T, EPI_STORE_T, 1>(p, st);
-            case 2: return launch_fast<T, EPI_STORE_T, 2>(p, st);
-            case 3: return launch_fast<T, EPI_STORE_T, 3>(p, st);
-            case 5: return launch_fast<T, EPI_STORE_T, 5>(p, st);
-            case 7: return launch_fast<T, EPI_STORE_T, 7>(p, st);
-            case 8: return launch_fast<T, EPI_STORE_T, 8>(p, st);
-            case 16: return launch_fast<T, EPI_STORE_T, 16>(p, st);
-            case 24: return launch_fast<T, EPI_STORE_T, 24>(p, st);
-            case 40: return launch_fast<T, EPI_STORE_T, 40>(p, st);
-            case 32: return launch_fast<T, EPI_STORE_T, 32>(p, st);
-            case 64: return launch_fast<T, EPI_STORE_T, 64>(p, st);
-            case 128: return launch_fast<T, EPI_STORE_T, 128>(p, st);
-            case 96: return launch_fast<T, EPI_STORE_T, 96>(p, st);
-            case 160: return launch_fast<T, EPI_STORE_T, 160>(p, st);
-        }
-    }
-#endif
     switch (epi) {
         case EPI_STORE_T: return launch_fast<T, EPI_STORE_T>(p, st);
         case EPI_STORE_F32: return launch_fast<T, EPI_STORE_F32>(p, st);
@@ -363,16 +321,15 @@ static hipError_t dispatch64(const GemmArgs& p, int epi, hipStream_t st) {
     return hipErrorInvalidValue;
 }
 
-// the dbg codes (timing experiments, results wrong) exist in ESMK_EXPERIMENTS builds only (common.h)
 hipError_t launch_gemm256(const GemmArgs& p, int epi, int operand_dtype, hipStream_t st) {
-    if (gemm_tile_kernel(p, epi) != 256 || (p.dbg && !kExperiments)) return hipErrorInvalidValue;
+    if (gemm_tile_kernel(p, epi) != 256) return hipErrorInvalidValue;
     if (operand_dtype == ESMK_DT_F16) return dispatch256<_Float16>(p, epi, st);
     if (operand_dtype == ESMK_DT_BF16) return dispatch256<__bf16>(p, epi, st);
     return hipErrorInvalidValue;
 }
 
 hipError_t launch_gemm64(const GemmArgs& p, int epi, int operand_dtype, hipStream_t st) {
-    if (gemm_tile_kernel(p, epi) != 64 || (p.dbg && !kExperiments)) return hipErrorInvalidValue;
+    if (gemm_tile_kernel(p, epi) != 64) return hipErrorInvalidValue;
     if (operand_dtype == ESMK_DT_F16) return dispatch64<_Float16>(p, epi, st);
     if (operand_dtype == ESMK_DT_BF16) return dispatch64<__bf16>(p, epi, st);
     return hipErrorInvalidValue;

@@ -45,16 +45,10 @@ namespace esmk {
 // --------------------------------------------------------------------------------------------
 // kernel
 // --------------------------------------------------------------------------------------------
-// SCHED 0: fragment reads per load section 12 / 4 / 8 / 0.   SCHED 1: 4 / 4 / 8 / 8 — the (i0,i1)
-// activation fragments of the NEXT stream position are read in section L3 into their own registers.
-// DBG != 0 builds timing experiments (tools/microbench.py --only dbg8; results are wrong):
-//   bit 0 no MFMA, bit 1 no LDS-DMA, bit 2 no fragment reads, bit 3 no epilogue,
-//   bit 4 epilogue without its global stores, bit 5 leave a FULL epilogue's stores in flight behind the
-//   next K tile (vmcnt(8 + S) for its waits; measured slower than waiting), bit 6 every DMA re-reads
-//   K slab 0 (L2 resident).
-// PF > 0: every wave touches one dword of 64 of the 512 cache lines of stream position s + PF per K
-// tile (an L2 prefetch: the LDS-DMA of that position then hits the XCD's L2 instead of paying the
-// fabric / HBM latency inside the two-K-tile-deep DMA window).
+// Fragment reads per load section: 12 / 4 / 8 / 0.  (Closed, in git history: reading the next position's (i0,i1)
+// activation fragments in section L3 into registers of their own, 4 / 4 / 8 / 8; an L2 prefetch stream touching the
+// cache lines of a later stream position; leaving a full epilogue's stores in flight behind the next K tile, measured
+// slower than waiting for them.)
 // GEN: generalised addressing (strides, batch, row remaps; GemmArgs fields after `scaling`) — a separate
 // instantiation so that the dense layer-stack kernels keep their register budget.
 // HM: half-height tiles (128 x 256).  Everything — LDS units, DMA stream, waits, barriers — stays as it is; the
@@ -63,9 +57,9 @@ namespace esmk {
 // there are twice as many: used when 256-row tiles leave most CUs without work (small batches: B = 4 x 1024 tokens has
 // 80 tiles for 256 CUs at N = 1280).  Every output element still sees the same MFMA sequence over K, so the results
 // are bit-identical to the full-height kernel — independent of the batch size.
-template <typename T, int EPI, int SCHED = 0, int DBG = 0, int PF = 0, bool GEN = false, bool HM = false>
+template <typename T, int EPI, bool GEN = false, bool HM = false>
 __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs p, unsigned long long* timing) {
-    static_assert(!HM || (SCHED == 0 && !GEN), "half-height tiles: dense layer-stack kernels, schedule 0 only");
+    static_assert(!HM || !GEN, "half-height tiles: dense layer-stack kernels only");
     constexpr int TM = HM ? 128 : 256;  // tile height
     constexpr int GM = TM / 2;          // rows per wave group
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -140,21 +134,17 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs p, unsigned long
     };
     auto issue = [&](Stream& s, int unit, int buf) {
         char* dst = smem + buf * P_BUF + unit * P_UNIT + wave * 2048;
-        if constexpr (!(DBG & 2)) {
-            glds16(s.base + s.off0, dst);
-            glds16(s.base + s.off1, dst + 1024);
-        }
+        glds16(s.base + s.off0, dst);
+        glds16(s.base + s.off1, dst + 1024);
         // advance to the next stream position; past the end of the workgroup's tile list the last
         // K tile is re-issued (into a dead buffer) so the vmcnt bookkeeping stays uniform
         if (s.kt + 1 < nk) {
             s.kt = __builtin_amdgcn_readfirstlane(s.kt + 1);
-            if constexpr (!(DBG & 64)) {
-                if (unit == 0 || unit == 3) {
-                    // split weights: the activations' K tile kt / 2 meets W_hi (kt even) and W_lo (kt odd)
-                    if (!(GEN && p.a_kt_repeat) || !(s.kt & 1)) s.base += a_kt;
-                } else {
-                    s.base += w_kt;
-                }
+            if (unit == 0 || unit == 3) {
+                // split weights: the activations' K tile kt / 2 meets W_hi (kt even) and W_lo (kt odd)
+                if (!(GEN && p.a_kt_repeat) || !(s.kt & 1)) s.base += a_kt;
+            } else {
+                s.base += w_kt;
             }
         } else if (s.it + 1 < n_my) {
             set_tile(s, unit, s.it + 1);
@@ -173,45 +163,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs p, unsigned long
     issue(sA0, 0, 1);
     issue(sW0, 1, 1);
 
-    // ---- L2 prefetch stream (PF > 0): waves 0-3 cover the 256 A rows, waves 4-7 the 256 W rows ----
-    Stream sP;
-    unsigned pf_dummy = 0;  // destination of the prefetch loads; never read
-    auto set_tile_pf = [&](int it) {
-        int tmi, tni, bz;
-        tile_coords(it, tmi, tni, bz);
-        sP.it = it;
-        sP.kt = 0;
-        const int row = (wave & 3) * 64 + lane;
-        if (wave < 4) {
-            sP.base = reinterpret_cast<const char*>(p.A) + (size_t)tmi * TM * a_rb;  // (HM: rows 128.. are the next tile's)
-            sP.off0 = (unsigned)min(row, p.M - tmi * TM - 1) * a_rb;
-        } else {
-            sP.base = reinterpret_cast<const char*>(p.W) + (size_t)tni * 256 * w_rb;
-            sP.off0 = (unsigned)min(row, p.N - tni * 256 - 1) * w_rb;
-        }
-    };
-    auto advance_pf = [&]() {
-        if (sP.kt + 1 < nk) {
-            sP.kt = __builtin_amdgcn_readfirstlane(sP.kt + 1);
-            sP.base += 128;
-        } else if (sP.it + 1 < n_my) {
-            set_tile_pf(sP.it + 1);
-        }
-    };
-    auto prefetch = [&]() {
-        if constexpr (PF > 0) {
-            // hipcc does not count an asm load: pf_dummy stays reserved ("+v" below) until a later counted
-            // wait has retired it (vmcnt is in order), and nothing ever consumes the value
-            asm volatile("global_load_dword %0, %1, %2" : "=v"(pf_dummy) : "v"(sP.off0), "s"(sP.base) : "memory");
-            advance_pf();
-        }
-    };
-    if constexpr (PF > 0) {
-        set_tile_pf(0);
-#pragma unroll 1
-        for (int k = 0; k < PF; ++k) advance_pf();
-    }
-
     // ---- fragment read offsets (16 x 16 x 32 MFMA blocks: lane l reads row l & 15 of a 16-row block, 16-byte chunk
     // 4 ks + (l >> 4) of its 128-byte row; ks = K half of the tile) ----------------------------------------------
     const int lrow = (lane & 15) * 128;
@@ -222,28 +173,16 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs p, unsigned long
     const int a_off = grp * (64 * 128) + lrow;
     const int w_off = wn * (32 * 128) + lrow;
 
-    V8 fa[4][2], fb[4][2], fw0[2][2], fw1[2][2];  // [16-row / 16-column block][K half]; fb: rows 64..127, SCHED 1 only
-    f32x4 acc[4][8];                              // [16-column block of the wave's 64][16-row block of its 128]
-    if constexpr (DBG & 4) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-#pragma unroll
-                for (int b = 0; b < 4; ++b) fa[b][ks][e] = fb[b][ks][e] = Op<T>::from(0.f);
-                fw0[0][ks][e] = fw0[1][ks][e] = fw1[0][ks][e] = fw1[1][ks][e] = Op<T>::from(0.f);
-            }
-    }
+    V8 fa[4][2], fw0[2][2], fw1[2][2];  // [16-row / 16-column block][K half]
+    f32x4 acc[4][8];                    // [16-column block of the wave's 64][16-row block of its 128]
 
     auto rdA = [&](V8 (&f)[4][2], const char* ub) {
-        if constexpr (DBG & 4) return;
 #pragma unroll
         for (int b = 0; b < 4; ++b)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) f[b][ks] = *reinterpret_cast<const V8*>(ub + a_off + b * 2048 + xo[ks]);
     };
     auto rdW = [&](V8 (&fw)[2][2], const char* ub) {
-        if constexpr (DBG & 4) return;
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -259,9 +198,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs p, unsigned long
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb) {
                     f32x4& c = acc[2 * jb + nb][4 * ib + mb];
-                    if constexpr (DBG & 1) {
-                        asm volatile("" ::"v"(fw[nb][ks]), "v"(f[mb][ks]));
-                    } else if constexpr (EPI == EPI_V_T) {  // lane owns 4 consecutive tokens of one channel
+                    if constexpr (EPI == EPI_V_T) {  // lane owns 4 consecutive tokens of one channel
                         c = Op<T>::mma16(f[mb][ks], fw[nb][ks], c);
                     } else {  // lane owns 4 consecutive channels of one token
                         c = Op<T>::mma16(fw[nb][ks], f[mb][ks], c);
@@ -321,22 +258,21 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs p, unsigned long
         }
     };
 
-    // One K tile = 4 phases.  WN = vmcnt immediate of the three counted waits: 8 in steady state
-    // (a unit is waited for 4 load sections = 8 DMA instructions after its issue), 8 + S for the first
-    // K tile after a FULL epilogue, whose S store instructions are younger than every DMA the tile
-    // waits for: they stay in flight behind the main loop instead of stalling it.
+    // One K tile = 4 phases.  The three counted waits are vmcnt(8): a unit is waited for 4 load sections = 8 DMA
+    // instructions after its issue.
     // EPI_RESID_F32: the epilogue reads the fp32 residual tile it adds to.  Its 8 pieces are latency
     // bound on those loads (HBM miss ~2.5k cycles each), so at the end of the tile's LAST K tile every
     // lane touches one dword of 4 of the wave's 256 residual cache lines: by the time the epilogue asks
     // for them they sit in the XCD's L2.  Measured (profiles/r1_v4_*): fc2 (80 K tiles per tile) -3 %,
     // out_proj (20 K tiles) +7 % because its epilogue burst is HBM-bandwidth bound, so it is only used for
-    // long K loops.  (DBG bit 7 switches it off for A/B runs.)
-    constexpr bool XPF = (EPI == EPI_RESID_F32) && !(DBG & 128);
+    // long K loops.
+    constexpr bool XPF = EPI == EPI_RESID_F32;
     unsigned x_dummy = 0;  // destination of those loads; never read
     int m_base_cur = 0, n_base_cur = 0;
     bool last_kt = false;
     auto prefetch_x = [&]() {
         if constexpr (XPF) {
+            if (!last_kt) return;
             const float* xo_ = reinterpret_cast<const float*>(p.out);
 #pragma unroll
             for (int q = 0; q < (HM ? 2 : 4); ++q) {  // 2 cache lines per row of the wave's 128 (HM: 64) rows
@@ -348,80 +284,42 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs p, unsigned long
             }
         }
     };
-    constexpr int S_EPI = epilogue_stores<EPI>();
-    constexpr int WBASE = PF > 0 ? 9 : 8;  // VM instructions a wave issues per K tile: 8 DMA (+ 1 prefetch)
-    bool young_stores = false;  // wave uniform: this K tile directly follows a FULL epilogue
-    auto wait_units = [&]() {
-        if ((DBG & 32) != 0 && young_stores) wait_vmcnt<WBASE + S_EPI>();
-        else wait_vmcnt<WBASE>();
-    };
+    auto wait_units = [&]() { wait_vmcnt<8>(); };  // VM instructions a wave issues per K tile: 8 DMA
     auto ktile = [&]() {
         const char* sb = smem + cur * P_BUF;
-        if constexpr (SCHED == 0) {
-            // ---- phase 0 -----------------------------------------------------------------------
-            rdA(fa, sb);
-            rdW(fw0, sb + P_UNIT);
-            issue(sW1, 2, cur ^ 1);
-            wait_units();
-            wg_barrier();
-            quad(0, 0, fw0, fa);
-            wg_barrier();
-            // ---- phase 1 -----------------------------------------------------------------------
-            rdW(fw1, sb + 2 * P_UNIT);
-            issue(sA1, 3, cur ^ 1);
-            wait_units();
-            wg_barrier();
-            quad(1, 0, fw1, fa);
-            wg_barrier();
-            // ---- phase 2 -----------------------------------------------------------------------
-            if constexpr (!HM) rdA(fa, sb + 3 * P_UNIT);
-            issue(sA0, 0, cur);
-            wg_barrier();
-            if constexpr (!HM) quad(1, 1, fw1, fa);
-            wg_barrier();
-            // ---- phase 3 -----------------------------------------------------------------------
-            issue(sW0, 1, cur);
-            wait_units();
-            if constexpr (PF > 0) asm volatile("" : "+v"(pf_dummy));  // the previous prefetch has retired
-            prefetch();
-            if constexpr (XPF)
-                if (last_kt) prefetch_x();  // after the K tile's last counted wait (last_kt: the K tile chosen for it)
-            wg_barrier();
-            if constexpr (!HM) quad(0, 1, fw0, fa);
-            wg_barrier();
-        } else {
-            // fa = (i0,i1) fragments of this position, read in L3 of the previous position
-            rdW(fw0, sb + P_UNIT);
-            issue(sW1, 2, cur ^ 1);
-            wait_units();  // U2 of cur
-            wg_barrier();
-            quad(0, 0, fw0, fa);
-            wg_barrier();
-            rdW(fw1, sb + 2 * P_UNIT);
-            issue(sA1, 3, cur ^ 1);
-            wait_units();  // U3 of cur
-            wg_barrier();
-            quad(1, 0, fw1, fa);
-            wg_barrier();
-            rdA(fb, sb + 3 * P_UNIT);
-            issue(sA0, 0, cur);
-            wait_units();  // U0 of cur^1 (next position)
-            wg_barrier();
-            quad(1, 1, fw1, fb);
-            wg_barrier();
-            rdA(fa, smem + (cur ^ 1) * P_BUF);
-            issue(sW0, 1, cur);
-            wait_units();  // U1 of cur^1
-            wg_barrier();
-            quad(0, 1, fw0, fb);
-            wg_barrier();
-        }
+        // ---- phase 0 -----------------------------------------------------------------------
+        rdA(fa, sb);
+        rdW(fw0, sb + P_UNIT);
+        issue(sW1, 2, cur ^ 1);
+        wait_units();
+        wg_barrier();
+        quad(0, 0, fw0, fa);
+        wg_barrier();
+        // ---- phase 1 -----------------------------------------------------------------------
+        rdW(fw1, sb + 2 * P_UNIT);
+        issue(sA1, 3, cur ^ 1);
+        wait_units();
+        wg_barrier();
+        quad(1, 0, fw1, fa);
+        wg_barrier();
+        // ---- phase 2 -----------------------------------------------------------------------
+        if constexpr (!HM) rdA(fa, sb + 3 * P_UNIT);
+        issue(sA0, 0, cur);
+        wg_barrier();
+        if constexpr (!HM) quad(1, 1, fw1, fa);
+        wg_barrier();
+        // ---- phase 3 -----------------------------------------------------------------------
+        issue(sW0, 1, cur);
+        wait_units();
+        prefetch_x();  // after the K tile's last counted wait
+        wg_barrier();
+        if constexpr (!HM) quad(0, 1, fw0, fa);
+        wg_barrier();
         cur ^= 1;
     };
 
     wait_vmcnt8();  // U0, U1 of position 0 have landed
     wg_barrier();
-    if constexpr (SCHED == 1) rdA(fa, smem);
     auto stamp = [&](int it, int k) {
         if (timing != nullptr && tid == 0) {
             unsigned long long* t = timing + ((size_t)blockIdx.x * 32 + (it & 31)) * 4;
@@ -446,30 +344,20 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs p, unsigned long
         for (int kt = 0; kt < nk; ++kt) {
             last_kt = (kt == p.xpf_kt);  // K tile after which the residual tile is prefetched (-1: never)
             ktile();
-            young_stores = false;
         }
         if (grp == 0) wg_barrier();  // re-align: both groups run the epilogue together
         stamp(it, 1);
 
         char* slice = smem + P_EPI + wave * P_SLICE;
-        if constexpr (DBG & 8) {
-#pragma unroll
-            for (int nj = 0; nj < 4; ++nj)
-#pragma unroll
-                for (int mi = 0; mi < 8; ++mi) asm volatile("" ::"v"(acc[nj][mi]));
-        } else {
-            bool full = (m_base + GM <= p.M) && (n_base + 64 <= p.N);
-            if constexpr (EPI == EPI_V_T) full = full && (p.T % 32 == 0);
-            constexpr int NI = HM ? 2 : 4;
-            if (full) epilogue8m<T, EPI, true, (DBG & 16) != 0, GEN, NI>(p, acc, 0, m_base, n_base, lane, slice, out_off, zo, zi);
-            else epilogue8m<T, EPI, false, (DBG & 16) != 0, GEN, NI>(p, acc, 0, m_base, n_base, lane, slice, out_off, zo, zi);
-            young_stores = full && !(DBG & 16) && !HM;
-        }
+        bool full = (m_base + GM <= p.M) && (n_base + 64 <= p.N);
+        if constexpr (EPI == EPI_V_T) full = full && (p.T % 32 == 0);
+        constexpr int NI = HM ? 2 : 4;
+        if (full) epilogue8m<T, EPI, true, false, GEN, NI>(p, acc, 0, m_base, n_base, lane, slice, out_off, zo, zi);
+        else epilogue8m<T, EPI, false, false, GEN, NI>(p, acc, 0, m_base, n_base, lane, slice, out_off, zo, zi);
         if constexpr (XPF) asm volatile("" : "+v"(x_dummy));  // the epilogue's own loads retired them
         stamp(it, 2);
     }
     wait_vmcnt0();  // the trailing (dummy) DMA writes must land before the LDS is released
-    if constexpr (PF > 0) asm volatile("" ::"v"(pf_dummy));
 }
 
 // --------------------------------------------------------------------------------------------
@@ -512,12 +400,10 @@ static int num_workgroups() {
 static unsigned long long* g_timing = nullptr;  // esmk_debug_gemm_timing()
 void gemm8_set_timing(unsigned long long* dev_buf) { g_timing = dev_buf; }
 
-constexpr int PF_DEFAULT = 0;
-
-template <typename T, int EPI, int SCHED = 0, int DBG = 0, int PF = PF_DEFAULT, bool GEN = false, bool HM = false>
+template <typename T, int EPI, bool GEN = false, bool HM = false>
 static hipError_t launch8(GemmArgs p, hipStream_t st) {
     static bool attr_set = false;
-    auto kern = gemm8_kernel<T, EPI, SCHED, DBG, PF, GEN, HM>;
+    auto kern = gemm8_kernel<T, EPI, GEN, HM>;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS);
@@ -551,54 +437,29 @@ static hipError_t launch8(GemmArgs p, hipStream_t st) {
 
 template <typename T>
 static hipError_t dispatch8(const GemmArgs& p, int epi, hipStream_t st) {
-    if (p.dbg) {  // timing experiments (tools/microbench.py; results wrong): ESMK_EXPERIMENTS builds only
-#ifdef ESMK_EXPERIMENTS
-        if constexpr (std::is_same<T, _Float16>::value) {
-            if (epi == EPI_STORE_T) {
-                switch (p.dbg) {
-                    case 0x10: return launch8<T, EPI_STORE_T, 1, 0>(p, st);
-                    case 0x01: return launch8<T, EPI_STORE_T, 0, 1>(p, st);
-                    case 0x02: return launch8<T, EPI_STORE_T, 0, 2>(p, st);
-                    case 0x04: return launch8<T, EPI_STORE_T, 0, 4>(p, st);
-                    case 0x08: return launch8<T, EPI_STORE_T, 0, 8>(p, st);
-                    case 0x06: return launch8<T, EPI_STORE_T, 0, 6>(p, st);
-                    case 0x07: return launch8<T, EPI_STORE_T, 0, 7>(p, st);
-                    case 0x0e: return launch8<T, EPI_STORE_T, 0, 14>(p, st);
-                    case 0x18: return launch8<T, EPI_STORE_T, 1, 8>(p, st);
-                    case 0x20: return launch8<T, EPI_STORE_T, 0, 16>(p, st);
-                    case 0x40: return launch8<T, EPI_STORE_T, 0, 32>(p, st);
-                    case 0x60: return launch8<T, EPI_STORE_T, 0, 64>(p, st);
-                    case 0x68: return launch8<T, EPI_STORE_T, 0, 64 + 8>(p, st);
-                }
-            }
-            if (p.dbg == 0x90 && epi == EPI_RESID_F32) return launch8<T, EPI_RESID_F32, 0, 128>(p, st);
-        }
-#endif
-        return hipErrorInvalidValue;
-    }
     // generalised addressing requested?  (MSA Transformer calls, batched / strided / remapped GEMMs)
     const bool gen = gemm8_generalised(p, epi);
     if (gen) {
         switch (epi) {
-            case EPI_STORE_T: return launch8<T, EPI_STORE_T, 0, 0, 0, true>(p, st);
-            case EPI_STORE_F32: return launch8<T, EPI_STORE_F32, 0, 0, 0, true>(p, st);
-            case EPI_GELU_T: return launch8<T, EPI_GELU_T, 0, 0, 0, true>(p, st);
-            case EPI_RESID_F32: return launch8<T, EPI_RESID_F32, 0, 0, 0, true>(p, st);
-            case EPI_QKV_ROPE: return launch8<T, EPI_QKV_ROPE, 0, 0, 0, true>(p, st);
-            case EPI_V_T: return launch8<T, EPI_V_T, 0, 0, 0, true>(p, st);
-            case EPI_MSA_CTX: return launch8<T, EPI_MSA_CTX, 0, 0, 0, true>(p, st);
+            case EPI_STORE_T: return launch8<T, EPI_STORE_T, true>(p, st);
+            case EPI_STORE_F32: return launch8<T, EPI_STORE_F32, true>(p, st);
+            case EPI_GELU_T: return launch8<T, EPI_GELU_T, true>(p, st);
+            case EPI_RESID_F32: return launch8<T, EPI_RESID_F32, true>(p, st);
+            case EPI_QKV_ROPE: return launch8<T, EPI_QKV_ROPE, true>(p, st);
+            case EPI_V_T: return launch8<T, EPI_V_T, true>(p, st);
+            case EPI_MSA_CTX: return launch8<T, EPI_MSA_CTX, true>(p, st);
         }
         return hipErrorInvalidValue;
     }
     if (gemm8_half_height(p)) {
         switch (epi) {
-            case EPI_STORE_T: return launch8<T, EPI_STORE_T, 0, 0, 0, false, true>(p, st);
-            case EPI_STORE_F32: return launch8<T, EPI_STORE_F32, 0, 0, 0, false, true>(p, st);
-            case EPI_GELU_T: return launch8<T, EPI_GELU_T, 0, 0, 0, false, true>(p, st);
-            case EPI_GELU_F32: return launch8<T, EPI_GELU_F32, 0, 0, 0, false, true>(p, st);
-            case EPI_RESID_F32: return launch8<T, EPI_RESID_F32, 0, 0, 0, false, true>(p, st);
-            case EPI_QKV_ROPE: return launch8<T, EPI_QKV_ROPE, 0, 0, 0, false, true>(p, st);
-            case EPI_V_T: return launch8<T, EPI_V_T, 0, 0, 0, false, true>(p, st);
+            case EPI_STORE_T: return launch8<T, EPI_STORE_T, false, true>(p, st);
+            case EPI_STORE_F32: return launch8<T, EPI_STORE_F32, false, true>(p, st);
+            case EPI_GELU_T: return launch8<T, EPI_GELU_T, false, true>(p, st);
+            case EPI_GELU_F32: return launch8<T, EPI_GELU_F32, false, true>(p, st);
+            case EPI_RESID_F32: return launch8<T, EPI_RESID_F32, false, true>(p, st);
+            case EPI_QKV_ROPE: return launch8<T, EPI_QKV_ROPE, false, true>(p, st);
+            case EPI_V_T: return launch8<T, EPI_V_T, false, true>(p, st);
         }
     }
     switch (epi) {

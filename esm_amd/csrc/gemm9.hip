@@ -162,9 +162,9 @@ ESMK_DEV void epilogue9_f32(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base,
         for (int it = 0; it < 4; ++it) {
             const int m = m_base + 32 * i + it * 8 + (la >> 3);
             if constexpr (SADDR)
-                cmv[i & 1][it] = (kExperiments && (p.lnf_dbg & 4)) ? 0.f : *gaddr(mb, 4 * (32 * i + 8 * it), 4u * (unsigned)(la >> 3), (const float*)nullptr);
+                cmv[i & 1][it] = *gaddr(mb, 4 * (32 * i + 8 * it), 4u * (unsigned)(la >> 3), (const float*)nullptr);
             else
-                cmv[i & 1][it] = (kExperiments && (p.lnf_dbg & 4)) ? 0.f : p.ln_mean[FULL ? m : min(m, p.M - 1)];
+                cmv[i & 1][it] = p.ln_mean[FULL ? m : min(m, p.M - 1)];
         }
     };
     if constexpr (LNF)
@@ -244,7 +244,7 @@ ESMK_DEV void epilogue9_f32(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base,
                     recv.y = (unsigned)__builtin_amdgcn_update_dpp(0, (int)send.y, 0xB1, 0xf, 0xf, true);
                     const u32x4 o = odd ? u32x4{recv.x, recv.y, cur.x, cur.y} : u32x4{prev.x, prev.y, recv.x, recv.y};
                     const int col = n_base + ((la & 1) ? 32 * jb + 4 * (cc - 1) : 32 * (jb - 1) + 4 * cc);
-                    if ((FULL || (m < p.M && col < p.N)) && !(kExperiments && (p.lnf_dbg & 1))) {
+                    if (FULL || (m < p.M && col < p.N)) {
                         if constexpr (SADDR) {
                             auto* hd = gaddr(hb + (u64)(4 * i) * h_rb, 32 * (jb - 1) * (int)sizeof(T), hv[it], (u32x4*)nullptr);
                             if constexpr (NT) __builtin_nontemporal_store(o, hd);
@@ -261,7 +261,7 @@ ESMK_DEV void epilogue9_f32(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base,
         if constexpr (EPI == EPI_RESID_F32)
             if (piece + D < NP) load_old(old[piece % D], piece + D);
         if constexpr (LNF) {
-            if (jb == 3 && lnp && !(kExperiments && (p.lnf_dbg & 2))) {  // the wave's 128 columns of rows 32 i .. 32 i + 31 are complete
+            if (jb == 3 && lnp) {  // the wave's 128 columns of rows 32 i .. 32 i + 31 are complete
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
                     // the row's eight lanes: lane l adds lanes l-1, then l-2, l-3, then l-4 .. l-7 (DPP row_shr, zeros
@@ -710,8 +710,7 @@ ESMK_DEV void epilogue9_vt(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base, 
 }
 
 // --------------------------------------------------------------------------------------------
-// kernel.  VAR = timing experiments (results are wrong): 16 no MFMA, 32 no LDS-DMA, 64 no fragment reads,
-// 128 no epilogue.
+// kernel
 // --------------------------------------------------------------------------------------------
 // HM: half-height tiles (128 x 256; wave blocks 64 x 128) for launches that leave CUs idle with 256-row tiles (small
 // batches).  Same LDS image (the activation half of a buffer is half used), 4 + 8 pieces per wave and K tile, 32 MFMA
@@ -719,9 +718,9 @@ ESMK_DEV void epilogue9_vt(const GemmArgs& p, f32x4 (&acc)[8][NMI], int m_base, 
 // LNF: LayerNorm fold (kernels.h): EPI_RESID_F32 = producer (second operand-dtype output + row statistics),
 // EPI_QKV_ROPE / EPI_V_T / EPI_GELU_T = consumer (accumulators start from 0, row scale + bias in the epilogue).
 // X3O: EPI_GELU_T with hi | hi | lo output rows (precision mode f16x3; an instantiation of its own, full height)
-template <typename T, int EPI, int VAR = 0, bool HM = false, bool LNF = false, bool X3O = false>
+template <typename T, int EPI, bool HM = false, bool LNF = false, bool X3O = false>
 __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long long* timing) {
-    static_assert(!X3O || (EPI == EPI_GELU_T && !HM && !LNF && VAR == 0), "hi | hi | lo output rows: plain full-height GELU kernel");
+    static_assert(!X3O || (EPI == EPI_GELU_T && !HM && !LNF), "hi | hi | lo output rows: plain full-height GELU kernel");
     static_assert(!LNF || EPI == EPI_RESID_F32 || EPI == EPI_QKV_ROPE || EPI == EPI_V_T || EPI == EPI_GELU_T || EPI == EPI_QKV_ALL,
                   "LayerNorm fold: epilogue");
     constexpr bool LNC = LNF && EPI != EPI_RESID_F32;  // consumer
@@ -740,51 +739,31 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
     constexpr int BUF = HM ? 49152 : Q_BUF, WOFF = HM ? 16384 : Q_WOFF;
     constexpr int SLICE = HM ? 4096 : Q_SLICE;
     static_assert(NST * BUF + 4 * SLICE <= Q_LDS, "LDS budget");
-    static_assert(!HM || (VAR & ~(8 | 16 | 32 | 64 | 128)) == 0, "half-height tiles: only the timing-experiment bits");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using V8 = typename Op<T>::v8;
     typedef __attribute__((address_space(3))) void* lds_ptr;
-    constexpr bool NO_MFMA = (VAR & 16) != 0, NO_DMA = (VAR & 32) != 0, NO_RD = (VAR & 64) != 0, NO_EPI = (VAR & 128) != 0;
-    // VAR & 4: odd waves issue their pieces one slot later than even waves (half the TA burst): +-0.
-    // VAR & 8: without the s_barrier (results wrong): +3 .. 7 %.
-    // VAR & 3 (issue pattern of the 16 pieces): 0 = first barrier at slot 16, one piece per 3 slots (16 .. 61);
-    // 1 = slots 24, 25, .. 39 (dense);  2 = 24 .. 61 evenly (one per 2.5 slots);  3 = 24, 26, .. 54.
-    // A piece that finds the CU's memory pipeline busy stalls the wave's MFMA issue with it (one wave per SIMD: nobody
-    // else issues), and 4 waves x 1 piece per 2 slots is the pipeline's peak rate; measured on the four layer shapes
-    // (profiles/r3_gemm9_mi16_variants.log): pattern 0 +8 .. 9 % over 3, 2 in between, 1 -5 %.
+    // Issue pattern of the 16 pieces: first barrier at slot 16, one piece per 3 slots (16 .. 61).  A piece that finds the
+    // CU's memory pipeline busy stalls the wave's MFMA issue with it (one wave per SIMD: nobody else issues), and 4 waves
+    // x 1 piece per 2 slots is the pipeline's peak rate.  Measured against it on the four layer shapes and dropped
+    // (profiles/r3_gemm9_mi16_variants.log): pieces from slot 24 on at one per 2 slots (this pattern is 8 .. 9 % faster),
+    // one per 2.5 slots (in between), one per slot (slowest); odd waves one slot behind even waves (+-0); a K offset
+    // staggered by workgroup or by tile column, the vendor kernel's "StaggerU" (+-0); non-temporal operand loads (worse).
     // HM (32 slots, three buffers): Y reads two per slot in slots 0 .. 5, first barrier at 8, the 12 pieces of position
     // s+3 at slots 8, 10, .. 30, second barrier at 16 (the pieces of position s+1 were issued two K tiles ago), X reads of
     // position s+1 one per slot in 16 .. 27.
-    constexpr int IMODE = VAR & 3;
-    constexpr int M_B1 = HM ? 8 : (IMODE == 0 ? 16 : 24);
+    constexpr int M_B1 = HM ? 8 : 16;
     constexpr int M_B2 = HM ? 16 : 52;
-    constexpr bool STAGGER = (VAR & 4) != 0;
-    constexpr bool NO_BAR = (VAR & 8) != 0;
     // first K tile of a full-height tile: its second K half accumulates through the tied inline-asm MFMA (common.h)
-#ifndef ESMK_G9_TIE1
-#define ESMK_G9_TIE1 1
-#endif
-    constexpr bool TIE1 = ESMK_G9_TIE1 && !HM && !NO_MFMA;
-    // VAR & 256 / 512 (timing experiments): the K loop of a tile starts at a K offset that depends on the workgroup
-    // (256) or on the tile's column block (512) and wraps — the vendor kernel's "StaggerU" against all CUs sweeping the
-    // same K offset of their operand rows at once.  256 changes the summation order with the tile -> workgroup map.
-    constexpr int KSTAG = (VAR & 256) ? 1 : (VAR & 512) ? 2 : 0;
-    // VAR & 1024: only the activation pieces are issued (half the DMA bytes: is the stream bound by bytes or by its
-    // round trip?);  VAR & 2048: the pieces carry the non-temporal cache policy.
-    constexpr bool HALF_DMA = (VAR & 1024) != 0;
-    constexpr int DMA_AUX = (VAR & 2048) ? 2 : 0;
+    constexpr bool TIE1 = !HM;
+    constexpr int DMA_AUX = 0;  // cache-policy bits of the pieces: default
+    auto piece_slot = [](int k) constexpr { return HM ? 8 + 2 * k : 16 + 3 * k; };
     // pieces of position s+2 issued before the second barrier
-    auto piece_slot = [](int k) constexpr {
-        if (HM) return 8 + 2 * k;
-        return IMODE == 3 ? 24 + 2 * k : IMODE == 1 ? 24 + k : IMODE == 2 ? 24 + (k * 40) / 16 : 16 + 3 * k;
-    };
     auto pieces_before = [piece_slot](int m) constexpr {
         int n = 0;
         for (int k = 0; k < NPC; ++k) n += piece_slot(k) < m ? 1 : 0;
         return n;
     };
-    constexpr int IN_FLIGHT0 = pieces_before(M_B2);
-    constexpr int IN_FLIGHT = HALF_DMA ? (IN_FLIGHT0 + 1) / 2 : IN_FLIGHT0 + (HM ? NPC : 0);  // HM: + position s+2
+    constexpr int IN_FLIGHT = pieces_before(M_B2) + (HM ? NPC : 0);  // HM: + position s+2
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -843,10 +822,8 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
         tile_coords(it, tmi, tni);
         s_it = it;
         s_kt = 0;
-        if constexpr (KSTAG == 1) s_koff = (unsigned)(((blockIdx.x >> 3) & 3) * (nk >> 2)) * 128u;
-        else if constexpr (KSTAG == 2) s_koff = (unsigned)((tni & 3) * (nk >> 2)) * 128u;
-        else s_koff = 0;
-        s_koff_a = a_rep ? 0u : s_koff;
+        s_koff = 0;
+        s_koff_a = 0;
         const unsigned rows_a = (unsigned)min(TM, p.M - tmi * TM), rows_w = (unsigned)min(256, p.N - tni * 256);
         d_a = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(reinterpret_cast<const char*>(p.A) + (size_t)tmi * TM * rb_a), 0,
                                                 (int)__builtin_amdgcn_readfirstlane(rows_a * rb_a), 0x00020000);
@@ -859,8 +836,6 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
         if (s_kt + 1 < nk) {
             s_kt = s_kt + 1;
             s_koff += 128u;
-            if constexpr (KSTAG != 0)
-                if (s_koff == (unsigned)nk * 128u) s_koff = 0;
             s_koff_a = a_rep ? (unsigned)(s_kt >> 1) * 128u : s_koff;
         } else if (s_it + 1 < n_my) {
             set_tile(s_it + 1);
@@ -869,16 +844,12 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
     // piece k = 0..15: operand k & 1 (0 activations, 1 weights), rows 8 (k >> 1) .. of the wave's 64
     // (HM: k = 0..3 activations, rows 8 k .. of the wave's 32; k = 4..11 weights)
     auto issue1 = [&](int k, int buf) ESMK_INL {
-        if constexpr (!NO_DMA) {
-            if constexpr (HALF_DMA)
-                if (k & 1) return;
-            const bool isw = HM ? (k >= 4) : ((k & 1) != 0);
-            const int q = HM ? (isw ? k - 4 : k) : (k >> 1);
-            char* dst = smem + buf * BUF + (isw ? WOFF + wave * 8192 : wave * (HM ? 4096 : 8192)) + q * 1024;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(isw ? d_w : d_a, (lds_ptr)dst, 16,
-                                                     isw ? ((q & 1) ? vo_odd : vo_even) : ((q & 1) ? va_odd : va_even),
-                                                     isw ? s_koff + (unsigned)q * rb8 : s_koff_a + (unsigned)q * rb8_a, 0, DMA_AUX);
-        }
+        const bool isw = HM ? (k >= 4) : ((k & 1) != 0);
+        const int q = HM ? (isw ? k - 4 : k) : (k >> 1);
+        char* dst = smem + buf * BUF + (isw ? WOFF + wave * 8192 : wave * (HM ? 4096 : 8192)) + q * 1024;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(isw ? d_w : d_a, (lds_ptr)dst, 16,
+                                                 isw ? ((q & 1) ? vo_odd : vo_even) : ((q & 1) ? va_odd : va_even),
+                                                 isw ? s_koff + (unsigned)q * rb8 : s_koff_a + (unsigned)q * rb8_a, 0, DMA_AUX);
     };
 
     // ---- fragments: X = K 0..31, Y = K 32..63 of a K tile (one 16 x 16 x 32 MFMA step each); [16-row block] ---------
@@ -891,27 +862,16 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
     const int a_off = wr * (NMI * 2048) + lrow;
     const int w_off = WOFF + wc * 16384 + lrow;
     V8 xa[NMI], xw[8], ya[NMI], yw[8];
-    if constexpr (NO_RD) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                xw[i][e] = yw[i][e] = Op<T>::from(0.f);
-                if (i < NMI) xa[i][e] = ya[i][e] = Op<T>::from(0.f);
-            }
-    }
     // read r = 0 .. NRD - 1 of a half: r < 2 NMI: block r >> 1, r even -> activations, odd -> weights; then the
     // remaining weight blocks
     auto rd1 = [&](V8 (&fa)[NMI], V8 (&fw)[8], const char* bp, int half, int r) ESMK_INL {
-        if constexpr (!NO_RD) {
-            if (r >= 2 * NMI) {
-                const int blk = r - NMI;
-                fw[blk] = *reinterpret_cast<const V8*>(bp + w_off + blk * 2048 + xo[half]);
-            } else {
-                const int blk = r >> 1;
-                if (r & 1) fw[blk] = *reinterpret_cast<const V8*>(bp + w_off + blk * 2048 + xo[half]);
-                else fa[blk] = *reinterpret_cast<const V8*>(bp + a_off + blk * 2048 + xo[half]);
-            }
+        if (r >= 2 * NMI) {
+            const int blk = r - NMI;
+            fw[blk] = *reinterpret_cast<const V8*>(bp + w_off + blk * 2048 + xo[half]);
+        } else {
+            const int blk = r >> 1;
+            if (r & 1) fw[blk] = *reinterpret_cast<const V8*>(bp + w_off + blk * 2048 + xo[half]);
+            else fa[blk] = *reinterpret_cast<const V8*>(bp + a_off + blk * 2048 + xo[half]);
         }
     };
 
@@ -966,10 +926,7 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
             const bool use_b = first && m < NS / 2;  // the tile's first K half: C operand = bias
             // the first K tile's second half, full-height tiles: accumulate in place (Op<T>::mma16_tied)
             constexpr bool tied = TIE1 && first && second_half;
-            if constexpr (NO_MFMA) {
-                asm volatile("" ::"v"(fa[mi]), "v"(fw[nj]));
-                if (use_b) c = bv[nj];
-            } else if constexpr (TIE1 && first) {
+            if constexpr (TIE1 && first) {
                 if constexpr (tied) {
                     if constexpr (decltype(vt)::value) Op<T>::mma16_tied(fa[mi], fw[nj], c);
                     else Op<T>::mma16_tied(fw[nj], fa[mi], c);
@@ -996,13 +953,11 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
 #pragma unroll
         for (int m = 0; m < NS; ++m) {
             if (m == M_B1) {  // every wave has read buffer cur completely
-                if constexpr (NO_BAR) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (m == M_B2) {  // every wave's pieces of position s+1 have landed; IN_FLIGHT younger ones stay in flight
-                if constexpr (NO_BAR) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IN_FLIGHT) : "memory");
-                else asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(IN_FLIGHT) : "memory");
+                asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(IN_FLIGHT) : "memory");
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (m < NS / 2) mma1(xa, xw, m, first, vt, std::false_type{});
@@ -1015,17 +970,9 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
             } else {
                 if (m < NRD) rd1(ya, yw, sb, 1, m);
             }
-            if constexpr (STAGGER) {  // (with pattern 3) even waves: slots M_B1, M_B1 + 2, ...; odd waves: one slot later
-                if (m >= M_B1 && m < M_B1 + 32 && ((m - M_B1) & 1) == 0) {
-                    if (!(wave & 1)) issue1((m - M_B1) >> 1, cur);
-                } else if (m > M_B1 && m < M_B1 + 33 && ((m - M_B1) & 1) == 1) {
-                    if (wave & 1) issue1((m - M_B1 - 1) >> 1, cur);
-                }
-            } else {
 #pragma unroll
-                for (int k = 0; k < NPC; ++k)
-                    if (piece_slot(k) == m) issue1(k, cur);
-            }
+            for (int k = 0; k < NPC; ++k)
+                if (piece_slot(k) == m) issue1(k, cur);
             if constexpr (M_B2 + NRD <= NS) {
                 if (m >= M_B2 && m < M_B2 + NRD) rd1(xa, xw, sn, 0, m - M_B2);
             } else {  // late second barrier: two reads per slot
@@ -1065,22 +1012,11 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
 #pragma unroll
         for (int k = 0; k < NPC; ++k) issue1(k, st);
     }
-    // Residual epilogues are an HBM-bound burst (a 256 KiB read-modify-write per workgroup, every workgroup of the launch
-    // at the same moment: 128 MB at the HBM's own rate with the matrix pipes idle — 40 % of the out-projection's tile
-    // time, profiles/r3_gemm9_epilogues_final.log).  Tiles all cost the same, so the workgroups stay in lockstep for the
-    // whole launch; one group starting late by a fraction of a tile's main loop keeps its bursts under the other group's
-    // main loops for every following round.  Pure timing: which tile a workgroup computes, and how, is unchanged.
-    if constexpr (EPI == EPI_RESID_F32 && !HM && VAR == 0) {
-        if (p.desync > 0) {
-            const int g = p.desync_group == 0 ? (int)(blockIdx.x & 1) : p.desync_group == 1 ? (int)((blockIdx.x >> 3) & 1) : (int)(blockIdx.x & 3);
-            const long long wait = p.desync_group == 2 ? (long long)g * p.desync / 2 : (long long)g * p.desync;
-            if (wait > 0) {
-                const unsigned long long t0 = __builtin_readcyclecounter();
-                while ((long long)(__builtin_readcyclecounter() - t0) < wait) __builtin_amdgcn_s_sleep(32);
-            }
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(HALF_DMA ? 8 : (NST - 1) * NPC) : "memory");
+    // (Residual epilogues are an HBM-bound burst — a 256 KiB read-modify-write per workgroup, every workgroup of the launch
+    // at the same moment, 40 % of the out-projection's tile time, profiles/r3_gemm9_epilogues_final.log.  A start-up delay
+    // of half of the workgroups here, to take the two groups' bursts out of lockstep, was zero-sum on the GPU and is gone:
+    // profiles/r4_resid_desync_ab.log.)
+    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((NST - 1) * NPC) : "memory");
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int r = 0; r < NRD; ++r) rd1(xa, xw, smem, 0, r);
@@ -1144,13 +1080,8 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
         char* slice = smem + NST * BUF + wave * SLICE;
         const bool full = (m_base + WRM <= p.M) && (n_base + 128 <= p.N);
         // small launches (HM): the next kernel finds the output in the L2 / MALL -> plain stores
-        constexpr bool NTS = !HM && (VAR & 4096) == 0;
-        if constexpr (NO_EPI) {
-#pragma unroll
-            for (int nj = 0; nj < 8; ++nj)
-#pragma unroll
-                for (int mi = 0; mi < NMI; ++mi) asm volatile("" ::"a"(acc[nj][mi]));
-        } else if constexpr (EPI == EPI_STORE_F32 || EPI == EPI_GELU_F32 || EPI == EPI_RESID_F32) {
+        constexpr bool NTS = !HM;
+        if constexpr (EPI == EPI_STORE_F32 || EPI == EPI_GELU_F32 || EPI == EPI_RESID_F32) {
             // residual pieces in flight: 4, or 3 next to the LayerNorm-fold producer's extra state
             constexpr int RD = LNF ? 3 : 4;
             if (full) epilogue9_f32<T, EPI, true, RD, NTS, NMI, HM, LNF>(p, acc, m_base, n_base, lane, slice);
@@ -1195,10 +1126,10 @@ static int num_workgroups9() {
     return n;
 }
 
-template <typename T, int EPI, int VAR = 0, bool HM = false, bool LNF = false, bool X3O = false>
+template <typename T, int EPI, bool HM = false, bool LNF = false, bool X3O = false>
 static hipError_t launch9(GemmArgs p, hipStream_t st) {
     static bool attr_set = false;
-    auto kern = gemm9_kernel<T, EPI, VAR, HM, LNF, X3O>;
+    auto kern = gemm9_kernel<T, EPI, HM, LNF, X3O>;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, Q_LDS);
@@ -1244,119 +1175,64 @@ bool gemm9_supports(const GemmArgs& p, int epi) {
 }
 
 template <typename T>
-static hipError_t dispatch9(const GemmArgs& p, int epi, int var, hipStream_t st) {
-#ifdef ESMK_EXPERIMENTS  // every VAR != 0: issue patterns (same results) and timing experiments (results wrong)
-#define ESMK_G9_ALL(V)                                                       \
-    switch (epi) {                                                            \
-        case EPI_STORE_T: return launch9<T, EPI_STORE_T, V>(p, st);           \
-        case EPI_STORE_F32: return launch9<T, EPI_STORE_F32, V>(p, st);       \
-        case EPI_GELU_T: return launch9<T, EPI_GELU_T, V>(p, st);             \
-        case EPI_GELU_F32: return launch9<T, EPI_GELU_F32, V>(p, st);         \
-        case EPI_RESID_F32: return launch9<T, EPI_RESID_F32, V>(p, st);       \
-        case EPI_QKV_ROPE: return launch9<T, EPI_QKV_ROPE, V>(p, st);         \
-        case EPI_V_T: return launch9<T, EPI_V_T, V>(p, st);                   \
-    }
-    if (var == 2) { ESMK_G9_ALL(2) }  // A/B of the issue patterns in the whole forward (ESMK_GEMM_IMPL=9:2 / 9:3)
-    if (var == 3) { ESMK_G9_ALL(3) }
-#undef ESMK_G9_ALL
-    if constexpr (std::is_same<T, _Float16>::value) {
-        if (p.half_m > 0 && epi == EPI_STORE_T) {  // timing experiments on the half-height kernel (results wrong)
-            switch (var) {
-                case 8: return launch9<T, EPI_STORE_T, 8, true>(p, st);
-                case 16: return launch9<T, EPI_STORE_T, 16, true>(p, st);
-                case 32: return launch9<T, EPI_STORE_T, 32, true>(p, st);
-                case 64: return launch9<T, EPI_STORE_T, 64, true>(p, st);
-                case 128: return launch9<T, EPI_STORE_T, 128, true>(p, st);
-                case 96: return launch9<T, EPI_STORE_T, 96, true>(p, st);
-                case 224: return launch9<T, EPI_STORE_T, 224, true>(p, st);
-            }
-        }
-    }
-#else
-    if (var != 0) return hipErrorInvalidValue;
-#endif
+static hipError_t dispatch9(const GemmArgs& p, int epi, hipStream_t st) {
     if (p.x3_out) {  // f16x3: fc1 + GELU with hi | hi | lo output rows — full height, fp16
         if constexpr (std::is_same<T, _Float16>::value) {
-            if (epi == EPI_GELU_T && var == 0 && !gemm9_ln_fold(p, epi)) return launch9<T, EPI_GELU_T, 0, false, false, true>(p, st);
+            if (epi == EPI_GELU_T && !gemm9_ln_fold(p, epi)) return launch9<T, EPI_GELU_T, false, false, true>(p, st);
         }
         return hipErrorInvalidValue;
     }
     if (gemm9_ln_fold(p, epi)) {  // LayerNorm fold: producer / consumer forms of the four epilogues, both tile heights
-        if (var != 0) return hipErrorInvalidValue;
         if (epi == EPI_RESID_F32 && (p.h16 == nullptr || p.ln_mean == nullptr || p.ldh < p.N || p.ln_parts < (p.N + 127) / 128))
             return hipErrorInvalidValue;
         if (epi != EPI_RESID_F32 && p.bias == nullptr) return hipErrorInvalidValue;
         if (p.half_m > 0) {
             switch (epi) {
-                case EPI_RESID_F32: return launch9<T, EPI_RESID_F32, 0, true, true>(p, st);
-                case EPI_QKV_ROPE: return launch9<T, EPI_QKV_ROPE, 0, true, true>(p, st);
-                case EPI_V_T: return launch9<T, EPI_V_T, 0, true, true>(p, st);
-                case EPI_GELU_T: return launch9<T, EPI_GELU_T, 0, true, true>(p, st);
-                case EPI_QKV_ALL: return launch9<T, EPI_QKV_ALL, 0, true, true>(p, st);
+                case EPI_RESID_F32: return launch9<T, EPI_RESID_F32, true, true>(p, st);
+                case EPI_QKV_ROPE: return launch9<T, EPI_QKV_ROPE, true, true>(p, st);
+                case EPI_V_T: return launch9<T, EPI_V_T, true, true>(p, st);
+                case EPI_GELU_T: return launch9<T, EPI_GELU_T, true, true>(p, st);
+                case EPI_QKV_ALL: return launch9<T, EPI_QKV_ALL, true, true>(p, st);
             }
         }
         switch (epi) {
-            case EPI_RESID_F32: return launch9<T, EPI_RESID_F32, 0, false, true>(p, st);
-            case EPI_QKV_ROPE: return launch9<T, EPI_QKV_ROPE, 0, false, true>(p, st);
-            case EPI_V_T: return launch9<T, EPI_V_T, 0, false, true>(p, st);
-            case EPI_GELU_T: return launch9<T, EPI_GELU_T, 0, false, true>(p, st);
+            case EPI_RESID_F32: return launch9<T, EPI_RESID_F32, false, true>(p, st);
+            case EPI_QKV_ROPE: return launch9<T, EPI_QKV_ROPE, false, true>(p, st);
+            case EPI_V_T: return launch9<T, EPI_V_T, false, true>(p, st);
+            case EPI_GELU_T: return launch9<T, EPI_GELU_T, false, true>(p, st);
             case EPI_QKV_ALL: return hipErrorInvalidValue;  // half-height tiles only (see gemm_qkv_one_launch)
         }
         return hipErrorInvalidValue;
     }
-    if (var == 0 && p.half_m > 0) {  // half-height tiles
+    if (p.half_m > 0) {  // half-height tiles
         switch (epi) {
-            case EPI_STORE_T: return launch9<T, EPI_STORE_T, 0, true>(p, st);
-            case EPI_STORE_F32: return launch9<T, EPI_STORE_F32, 0, true>(p, st);
-            case EPI_GELU_T: return launch9<T, EPI_GELU_T, 0, true>(p, st);
-            case EPI_GELU_F32: return launch9<T, EPI_GELU_F32, 0, true>(p, st);
-            case EPI_RESID_F32: return launch9<T, EPI_RESID_F32, 0, true>(p, st);
-            case EPI_QKV_ROPE: return launch9<T, EPI_QKV_ROPE, 0, true>(p, st);
-            case EPI_V_T: return launch9<T, EPI_V_T, 0, true>(p, st);
-            case EPI_QKV_ALL: return launch9<T, EPI_QKV_ALL, 0, true>(p, st);
+            case EPI_STORE_T: return launch9<T, EPI_STORE_T, true>(p, st);
+            case EPI_STORE_F32: return launch9<T, EPI_STORE_F32, true>(p, st);
+            case EPI_GELU_T: return launch9<T, EPI_GELU_T, true>(p, st);
+            case EPI_GELU_F32: return launch9<T, EPI_GELU_F32, true>(p, st);
+            case EPI_RESID_F32: return launch9<T, EPI_RESID_F32, true>(p, st);
+            case EPI_QKV_ROPE: return launch9<T, EPI_QKV_ROPE, true>(p, st);
+            case EPI_V_T: return launch9<T, EPI_V_T, true>(p, st);
+            case EPI_QKV_ALL: return launch9<T, EPI_QKV_ALL, true>(p, st);
         }
     }
-    if (var == 0) {
-        switch (epi) {
-            case EPI_STORE_T: return launch9<T, EPI_STORE_T>(p, st);
-            case EPI_STORE_F32: return launch9<T, EPI_STORE_F32>(p, st);
-            case EPI_GELU_T: return launch9<T, EPI_GELU_T>(p, st);
-            case EPI_GELU_F32: return launch9<T, EPI_GELU_F32>(p, st);
-            case EPI_RESID_F32: return launch9<T, EPI_RESID_F32>(p, st);
-            case EPI_QKV_ROPE: return launch9<T, EPI_QKV_ROPE>(p, st);
-            case EPI_V_T: return launch9<T, EPI_V_T>(p, st);
-            case EPI_QKV_ALL: return hipErrorInvalidValue;  // half-height tiles only (see gemm_qkv_one_launch)
-        }
+    switch (epi) {
+        case EPI_STORE_T: return launch9<T, EPI_STORE_T>(p, st);
+        case EPI_STORE_F32: return launch9<T, EPI_STORE_F32>(p, st);
+        case EPI_GELU_T: return launch9<T, EPI_GELU_T>(p, st);
+        case EPI_GELU_F32: return launch9<T, EPI_GELU_F32>(p, st);
+        case EPI_RESID_F32: return launch9<T, EPI_RESID_F32>(p, st);
+        case EPI_QKV_ROPE: return launch9<T, EPI_QKV_ROPE>(p, st);
+        case EPI_V_T: return launch9<T, EPI_V_T>(p, st);
+        case EPI_QKV_ALL: return hipErrorInvalidValue;  // half-height tiles only (see gemm_qkv_one_launch)
     }
-#ifdef ESMK_EXPERIMENTS
-    if constexpr (std::is_same<T, _Float16>::value) {
-        if (epi == EPI_STORE_T) {  // timing experiments (tools/bench_gemm9.py --dbg)
-            switch (var) {  // schedule variants: same results
-                case 1: return launch9<T, EPI_STORE_T, 1>(p, st);
-                case 7: return launch9<T, EPI_STORE_T, 7>(p, st);
-                case 512: return launch9<T, EPI_STORE_T, 512>(p, st);    // K stagger by column block
-                case 2048: return launch9<T, EPI_STORE_T, 2048>(p, st);  // non-temporal operand loads
-                case 4096: return launch9<T, EPI_STORE_T, 4096>(p, st);  // plain (temporal) stores
-                // parts of the kernel removed: results wrong
-                case 8: return launch9<T, EPI_STORE_T, 8>(p, st);
-                case 16: return launch9<T, EPI_STORE_T, 16>(p, st);
-                case 32: return launch9<T, EPI_STORE_T, 32>(p, st);
-                case 64: return launch9<T, EPI_STORE_T, 64>(p, st);
-                case 128: return launch9<T, EPI_STORE_T, 128>(p, st);
-                case 96: return launch9<T, EPI_STORE_T, 96>(p, st);
-                case 224: return launch9<T, EPI_STORE_T, 224>(p, st);
-                case 1040: return launch9<T, EPI_STORE_T, 1040>(p, st);  // no MFMAs, half the DMA bytes
-            }
-        }
-    }
-#endif
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_gemm9(const GemmArgs& p, int epi, int operand_dtype, int var, hipStream_t st) {
+hipError_t launch_gemm9(const GemmArgs& p, int epi, int operand_dtype, hipStream_t st) {
     if (!gemm9_supports(p, epi)) return hipErrorInvalidValue;
-    if (operand_dtype == ESMK_DT_F16) return dispatch9<_Float16>(p, epi, var, st);
-    if (operand_dtype == ESMK_DT_BF16) return dispatch9<__bf16>(p, epi, var, st);
+    if (operand_dtype == ESMK_DT_F16) return dispatch9<_Float16>(p, epi, st);
+    if (operand_dtype == ESMK_DT_BF16) return dispatch9<__bf16>(p, epi, st);
     return hipErrorInvalidValue;
 }
 

@@ -13,7 +13,7 @@
 // Process-wide switches, all in one record that is filled from the environment once:
 //     ESMK_GEMM_IMPL = 8 | 9 | auto     / esmk_debug_gemm_impl(impl, 0)         the persistent kernel of dense calls
 //     ESMK_QKV_ONE_LAUNCH = 0 | 1 | -1  / esmk_debug_set("qkv_one_launch", v)   q, k and v as one launch: never / always / by rounds
-// ESMK_EXPERIMENTS builds (common.h) add a gemm9 variant to ESMK_GEMM_IMPL and the switches of the #ifdef regions below.
+// The closed experiments (gemm9 issue-pattern variants, start-up delays of the residual GEMMs) are in git history and profiles/.
 #include "common.h"
 #include "kernels.h"
 #include <atomic>
@@ -26,51 +26,29 @@ namespace esmk {
 // Atomics: launches and esmk_debug_* calls may come from several host threads.  A debug call overrides the environment.
 struct GemmSettings {
     std::atomic<int> impl{0};      // 8 = gemm8 always, 9 = gemm9 wherever it applies (tile height as the caller says), 0 = by rule
-    std::atomic<int> variant{0};   // gemm9 VAR under impl 9 (0 in shipped builds; < 0 = by rule)
     std::atomic<int> qkv_one{-1};  // 1 / 0 = always / never, -1 = where it saves rounds of tiles
     int qkv_one_env = -1;
-#ifdef ESMK_EXPERIMENTS
-    // start-up delay of one workgroup group in the residual GEMMs (gemm9.hip), as a fraction of a tile's main loop
-    // (nk K tiles x ~2700 cycles); zero-sum on the GPU (profiles/r4_resid_desync_ab.log)
-    std::atomic<double> desync{0.0};
-    std::atomic<int> desync_group{0};
-    std::atomic<int> lnf_dbg{0};
-#endif
 };
 
 static GemmSettings& settings() {
     static GemmSettings s;
     static std::once_flag once;
     std::call_once(once, [] {
-        if (const char* e = getenv("ESMK_GEMM_IMPL")) {
-            s.impl = e[0] == '9' ? 9 : e[0] == '8' ? 8 : 0;
-            if (kExperiments && e[0] == '9' && e[1] == ':') s.variant = atoi(e + 2);
-        }
+        if (const char* e = getenv("ESMK_GEMM_IMPL")) s.impl = e[0] == '9' ? 9 : e[0] == '8' ? 8 : 0;
         if (const char* e = getenv("ESMK_QKV_ONE_LAUNCH")) s.qkv_one = s.qkv_one_env = atoi(e);
-#ifdef ESMK_EXPERIMENTS
-        if (const char* e = getenv("ESMK_RESID_DESYNC")) s.desync = atof(e);
-        if (const char* e = getenv("ESMK_RESID_DESYNC_GROUP")) s.desync_group = atoi(e);
-#endif
     });
     return s;
 }
 
 bool gemm_set_impl(int impl, int var) {
-    if (var != 0 && !kExperiments) return false;  // the gemm9 variants exist in ESMK_EXPERIMENTS builds only
-    GemmSettings& s = settings();
-    s.impl = impl;
-    s.variant = var;
+    if (var != 0) return false;  // gemm9 has one form
+    settings().impl = impl;
     return true;
 }
 
 bool gemm_set_knob(const char* key, double value) {
     GemmSettings& s = settings();
     if (strcmp(key, "qkv_one_launch") == 0) s.qkv_one = (int)value < -1 ? s.qkv_one_env : (int)value;
-#ifdef ESMK_EXPERIMENTS
-    else if (strcmp(key, "resid_desync") == 0) s.desync = value < 0 ? 0.0 : value;
-    else if (strcmp(key, "resid_desync_group") == 0) s.desync_group = (int)value;
-    else if (strcmp(key, "lnf_dbg") == 0) s.lnf_dbg = (int)value;  // removes parts of the producer epilogue
-#endif
     else return false;
     return true;
 }
@@ -90,7 +68,7 @@ GemmPlan gemm_plan(const GemmArgs& p, int epi) {
     const GemmPlan none;
     if (p.M <= 0 || p.N <= 0 || p.K <= 0) return none;
     const GemmSettings& s = settings();
-    const int impl = s.impl.load(), variant = s.variant.load();
+    const int impl = s.impl.load();
     const bool ok9 = gemm9_supports(p, epi);
     GemmPlan pl;
     if (p.x3_out) {  // the hi | hi | lo output form of the f16x3 mode exists in gemm9 only (full-height tiles)
@@ -101,31 +79,21 @@ GemmPlan gemm_plan(const GemmArgs& p, int epi) {
     // first) exist in gemm9 only: such a call never takes another kernel
     const bool lnf = gemm9_ln_fold(p, epi);
     const bool only9 = lnf || epi == EPI_QKV_ALL;
-    const bool hooks = p.force_old || p.force_generic || p.dbg;
+    const bool hooks = p.force_old || p.force_generic;
     if (only9 && (!ok9 || (epi == EPI_QKV_ALL && hooks))) return none;
     if (only9 || (ok9 && !hooks && impl != 8)) {
         pl.kernel = 9;
-        if (!only9 && impl == 9 && variant >= 0) {
+        if (!only9 && impl == 9) {
             pl.half_m = p.half_m > 0;
-            pl.variant = variant;
         } else {
             // EPI_QKV_ALL exists with HALF-height tiles only (see gemm_qkv_one_launch)
             pl.half_m = p.half_m > 0 || (p.half_m == 0 && gemm9_half_pays(p.M, p.N)) || epi == EPI_QKV_ALL;
         }
-#ifdef ESMK_EXPERIMENTS
-        // only launches of at least two rounds of tiles: the delay is paid once, a hidden burst is won per further round
-        const long long tiles = (long long)((p.M + 255) / 256) * ((p.N + 255) / 256);
-        const double ds = s.desync.load();
-        if (epi == EPI_RESID_F32 && !pl.half_m && pl.variant == 0 && !lnf && ds > 0 && tiles >= 512) {
-            pl.desync = (int)(ds * (double)(p.K / 64) * 2700.0);
-            pl.desync_group = s.desync_group.load();
-        }
-#endif
         return pl;
     }
     if (!p.force_old && !p.force_generic && gemm8_supports(p, epi)) {
-        pl.kernel = 8;  // the dbg codes and the generalised forms run full-height tiles (dispatch8)
-        pl.half_m = !p.dbg && !gemm8_generalised(p, epi) && gemm8_half_height(p);
+        pl.kernel = 8;  // the generalised forms run full-height tiles (dispatch8)
+        pl.half_m = !gemm8_generalised(p, epi) && gemm8_half_height(p);
         return pl;
     }
     if (gemm8_generalised(p, epi)) return none;  // the tile kernels only know dense calls
@@ -157,12 +125,7 @@ hipError_t launch_gemm(const GemmArgs& p, int epi, int operand_dtype, hipStream_
         case 9: {
             GemmArgs q = p;
             q.half_m = pl.half_m;
-#ifdef ESMK_EXPERIMENTS
-            q.lnf_dbg = settings().lnf_dbg.load();
-            q.desync = pl.desync;
-            q.desync_group = pl.desync_group;
-#endif
-            return launch_gemm9(q, epi, operand_dtype, pl.variant, st);
+            return launch_gemm9(q, epi, operand_dtype, st);
         }
         case 8: return launch_gemm8(p, epi, operand_dtype, st);  // asks gemm8_half_height itself, as the plan did
         case 256: return launch_gemm256(p, epi, operand_dtype, st);

@@ -33,7 +33,6 @@ struct GemmArgs {
     int panel_c = 0;    // gemm8: N tiles per column panel of the tile order (0 = choose)
     int half_m = 0;     // gemm8: 128-row tiles: 0 = decide from the tile count, 1 = force, -1 = never (A/B, tests)
     int xpf_kt = -1;    // gemm8, EPI_RESID_F32: K tile after which the residual tile is prefetched into the L2 (set by the launcher)
-    int dbg = 0;  // timing experiments only (tools/microbench.py): 1 no staging, 2 no barrier, 4 no LDS reads
     // EPI_QKV_ROPE only
     void* q = nullptr;   // [B,H,T,64]
     void* k = nullptr;   // [B,H,T,64]
@@ -77,11 +76,6 @@ struct GemmArgs {
     // Precision mode f16x3, EPI_GELU_T: the output rows leave as the A operand of that mode's fc2 — per 64-column K tile
     // hi | hi | lo, lo = T(v - T(v)), row stride 3 N; full-height gemm9 instantiation of its own
     int x3_out = 0;
-    int lnf_dbg = 0;  // timing experiments on the producer (results incomplete): 1 no h16 stores, 2 no statistics, 4 no mean loads
-    // gemm9, EPI_RESID_F32: start-up delay (shader cycles) of one workgroup group — takes the HBM-bound read-modify-write
-    // epilogues of the two groups out of lockstep (set by launch_gemm in ESMK_EXPERIMENTS builds; 0 = none).  desync_group: 0 = odd XCDs are late,
-    // 1 = every other workgroup of each XCD, 2 = four phases (blockIdx & 3) x desync / 2.  Results do not depend on it.
-    int desync = 0, desync_group = 0;
 };
 
 // gemm_dispatch.hip: the kernel choice.  gemm_plan is the pure decision (no HIP call), launch_gemm = gemm_plan + one
@@ -89,18 +83,14 @@ struct GemmArgs {
 struct GemmPlan {
     int kernel = 0;   // 9 (gemm9.hip), 8 (gemm8.hip), 256 / 64 (the tile kernels of gemm.hip), 0 = no kernel takes this call
     int half_m = 0;   // 1: 128-row tiles (the persistent kernels)
-    int variant = 0;  // gemm9 VAR (0 in shipped builds)
-#ifdef ESMK_EXPERIMENTS
-    int desync = 0, desync_group = 0;  // GemmArgs::desync / desync_group of the launch
-#endif
 };
 GemmPlan gemm_plan(const GemmArgs& p, int epi);
 hipError_t launch_gemm(const GemmArgs& p, int epi, int operand_dtype, hipStream_t st);
 bool gemm_qkv_one_launch(const GemmArgs& qk);  // q / k and v as one EPI_QKV_ALL launch: supported and fewer rounds of tiles?
-// which persistent kernel serves dense calls: 8, 9 or 0 = by rule (ESMK_GEMM_IMPL / esmk_debug_gemm_impl); false: a
-// non-zero gemm9 variant in a shipped build
+// which persistent kernel serves dense calls: 8, 9 or 0 = by rule (ESMK_GEMM_IMPL / esmk_debug_gemm_impl); false: var != 0
+// (gemm9 once had variants; the C ABI keeps the argument)
 bool gemm_set_impl(int impl, int var);
-// switches by name (esmk_debug_set): "qkv_one_launch", more in ESMK_EXPERIMENTS builds (gemm_dispatch.hip).  false: unknown key
+// switches by name (esmk_debug_set): "qkv_one_launch".  false: unknown key
 bool gemm_set_knob(const char* key, double value);
 // gemm.hip: one tile per workgroup — 256 x 256 (K % 64 == 0, N % 8 == 0) and the generic 64 x 64 (K % 32 == 0); dense calls
 int gemm_tile_kernel(const GemmArgs& p, int epi);  // 256, 64 or 0 = neither takes the call
@@ -117,15 +107,11 @@ hipError_t launch_gemm32(const float* A, int lda, const float* W, const float* b
                          int K, bool gelu, hipStream_t st);
 // measurement hook: per-tile s_memtime stamps of workgroup-leader lanes ([workgroup][tile & 31][4])
 void gemm8_set_timing(unsigned long long* dev_buf);
-// gemm9.hip: the same contract on one wave per SIMD (128 x 128 wave blocks); dense operands only.  var = the kernel's
-// VAR parameter: 0 in shipped builds, issue patterns and timing experiments in ESMK_EXPERIMENTS builds (gemm9.hip)
+// gemm9.hip: the same contract on one wave per SIMD (128 x 128 wave blocks); dense operands only
 bool gemm9_supports(const GemmArgs& p, int epi);
 bool gemm9_ln_fold(const GemmArgs& p, int epi);  // the call asks for the LayerNorm-fold form of its epilogue
-hipError_t launch_gemm9(const GemmArgs& p, int epi, int operand_dtype, int var, hipStream_t st);
+hipError_t launch_gemm9(const GemmArgs& p, int epi, int operand_dtype, hipStream_t st);
 void gemm9_set_timing(unsigned long long* dev_buf);
-#ifdef ESMK_EXPERIMENTS
-void attention_set_stagger(int cycles);  // attention.hip: start-up stagger of co-resident workgroups (timing only)
-#endif
 
 // ---- elementwise.hip -------------------------------------------------------------------
 // per-sequence statistics of the token matrix (esm2.py:82,86-92): scale[b] for token dropout,

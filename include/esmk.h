@@ -374,7 +374,9 @@ int esmk_ln_fold_enabled(const esmk_model* m);
 /* ---- single-kernel entry points (used by the parity tests and micro-benchmarks) -------- */
 
 /* ESM1bLayerNorm == torch.nn.LayerNorm(E, eps=1e-5) (esm/modules.py:68-81).
- * x fp32 [rows,E] -> y (operand dtype) [rows,E] and/or y32 fp32 [rows,E] (either may be NULL). */
+ * x fp32 [rows,E] -> y (operand dtype) [rows,E] and/or y32 fp32 [rows,E] (either may be NULL).
+ * Bits 8..11 of operand_dtype select the kernel form for tests: 0 = default (the engine's form), else variant + 1 with
+ * variant 0 = the plain one-row-per-wave form and 7 = the engine's form by name; any other variant is an error. */
 int esmk_op_layernorm(const float* x_dev, const float* gamma_dev, const float* beta_dev,
                       void* y_dev, float* y32_dev, int rows, int E, int operand_dtype,
                       void* stream);
@@ -390,7 +392,7 @@ int esmk_op_masked_row_mean(const void* x_dev, int x_dtype, const int32_t* count
  *   0 plain -> out operand dtype [M,N]           1 plain -> out fp32 [M,N]
  *   2 gelu (modules.py:17-24) -> operand dtype   3 gelu -> fp32
  *   4 residual: out fp32 [M,N] += result         (modules.py:134,140)
- * A, W operand dtype; bias fp32 (may be NULL). */
+ * A, W operand dtype; bias fp32 (may be NULL).  Bits 12..19 of operand_dtype must be 0. */
 int esmk_op_linear(const void* a_dev, const void* w_dev, const float* bias_dev, void* out_dev,
                    int M, int N, int K, int epilogue, int operand_dtype, void* stream);
 
@@ -424,7 +426,7 @@ int esmk_op_linear_split(const void* a_dev, const void* w2_dev, const float* bia
  *   output row (b,c,r), rows % (map_R map_C) == 0; ldy = row stride of y in elements (0 = E, else >= E and a multiple of 4; y32
  *   rows always have stride E); x3 != 0: y rows in the f16x3 operand layout, per 64-column K tile hi | hi | lo with hi = fp16(o),
  *   lo = fp16(o - hi) (fp16 only, E % 64 == 0, ldy >= 3 E, y required); eps > 0 (1e-5; 1e-12 for ESM-1).  E % 4 == 0,
- *   E <= 5120.  operand_dtype carries the kernel variant as in esmk_op_layernorm (bits 8..11 = variant + 1).
+ *   E <= 5120.  operand_dtype carries the kernel variant as in esmk_op_layernorm (bits 8..11 = variant + 1; default, 0 or 7).
  * esmk_op_split_weight_ex: the weight images: w [rows,cols] (any float dtype) -> parts = 1: dst [.., dst_ld] in dst_dtype, a
  *   plain conversion; parts = 2 / 3: dst fp16 [.., parts dst_ld], 64-column K tile t of a row as hi | lo (f16x2) or
  *   hi | lo | hi (f16x3) at columns 64 parts t, dst_ld % 64 == 0.  row_map / col_map = 1 spread heads of head_dim d over 64
@@ -455,13 +457,13 @@ int esmk_debug_mma_selftest(const void* a_dev, const void* b_dev, const float* c
 /* Measurement / A-B hook (no reference counterpart): which persistent GEMM kernel serves the dense nn.Linear calls
  * from now on — 8 = gemm8.hip (two waves per SIMD), 9 = gemm9.hip (one wave per SIMD, 128 x 128 wave blocks;
  * bit-identical results) wherever it applies, 0 = the library's own choice per call (default).  `variant` must be 0:
- * the gemm9 issue patterns and timing experiments it selects exist only in libraries built with
- * ESMK_HIPCC_EXTRA="-DESMK_EXPERIMENTS".  The environment variable ESMK_GEMM_IMPL=8|9|auto sets the same thing for a
+ * gemm9 has one form (the issue patterns and timing experiments the argument once selected are in the project's git
+ * history and profiles/).  The environment variable ESMK_GEMM_IMPL=8|9|auto sets the same thing for a
  * whole process. */
 int esmk_debug_gemm_impl(int impl, int variant);
 
 /* What the library would launch for a dense nn.Linear call (no reference counterpart, no GPU needed): out =
- * {kernel, half_m, variant, 0}; kernel 9 = gemm9.hip, 8 = gemm8.hip, 256 / 64 = the one-tile-per-workgroup kernels of
+ * {kernel, half_m, 0, 0}; kernel 9 = gemm9.hip, 8 = gemm8.hip, 256 / 64 = the one-tile-per-workgroup kernels of
  * gemm.hip, 0 = no kernel takes the call; half_m 1 = 128-row tiles.  epilogue: the codes of esmk_op_linear, 5 / 6 = the
  * q, k / v projections, 7 = the MSA row-attention context, 8 = q, k and v in one launch (N = 3E).  flags: 1 = the
  * force_generic and 2 = the force_old test hook of esmk_op_linear, 4 = the LayerNorm-fold form of the epilogue (producer
@@ -476,9 +478,7 @@ int esmk_debug_gemm_plan(int M, int N, int K, int epilogue, int flags, int32_t o
  * gemm_dispatch.hip; environment: ESMK_QKV_ONE_LAUNCH).  The one exception to "no result bit" is "rows_contacts_own_groups":
  * 1 makes esmk_forward_rows_contacts (and its workspace query) take the head-group count of the batch instead of the pinned
  * one of B = 1, so that what the pin costs can be timed (tools/design_throughput.py); the maps then carry the bits of
- * esmk_forward at that B.  0, the default, is the pin.  Any other key is an error ("unknown key").  Libraries built with
- * ESMK_HIPCC_EXTRA="-DESMK_EXPERIMENTS" add timing experiments, some of which DO break results (kernels with their
- * MFMAs, exponentials, DMA or epilogue stores removed): see common.h. */
+ * esmk_forward at that B.  0, the default, is the pin.  Any other key is an error ("unknown key"). */
 int esmk_debug_set(const char* key, double value);
 
 /* Fused q/k/v projection + scaling + rotary + head split (multihead_attention.py:256-284,

@@ -698,3 +698,41 @@ def test_frontend_table_and_gather_argument_checks():
         assert gather(**kw) != 0 and who + ": N and n" in err(), kw
     for E in (0, 2, 322):
         assert gather(E=E) != 0 and who + ": E must be a positive multiple of 4" in err(), E
+
+
+def test_linear_refuses_the_bits_of_the_closed_timing_experiments():
+    """esmk_op_linear: bits 12..19 of operand_dtype once selected kernels with parts removed; any of them set is refused
+    with a message of its own, before the call looks at a pointer or reaches a launch (the buffers are fake)."""
+    f16 = N.dtype_code(torch.float16)
+    for bit in range(12, 20):
+        for extra in (0, 0x200, 1 << 28):  # alone, with the force_old hook, with forced half-height tiles
+            rc = N.lib.esmk_op_linear(FAKE, FAKE, None, FAKE, 300, 320, 192, N.EPI_STORE_T, f16 | (1 << bit) | extra, None)
+            assert rc != 0 and "esmk_op_linear: bits 12..19" in err(), (bit, extra, err())
+    rc = N.lib.esmk_op_linear(FAKE, FAKE, None, FAKE, 300, 320, 192, N.EPI_STORE_T, f16 | 0xff000, None)
+    assert rc != 0 and "esmk_op_linear: bits 12..19" in err()
+    # without those bits the same call gets past that check: a bad epilogue is what it is refused for
+    rc = N.lib.esmk_op_linear(FAKE, FAKE, None, FAKE, 300, 320, 192, 5, f16, None)
+    assert rc != 0 and "bad epilogue" in err()
+
+
+def test_layernorm_variant_selector_checks():
+    """esmk_op_layernorm / esmk_op_layernorm_ex: the kernel has two forms, variant 0 (plain) and 7 (the engine's, also the
+    default); every other selector (operand_dtype bits 8..11 = variant + 1) is refused before any launch.  Selectors
+    default, 0 and 7 get past that check: with rows = 0 the calls are refused for the rows, not for the variant (still no
+    launch; the buffers are fake)."""
+    f16, bf16 = N.dtype_code(torch.float16), N.dtype_code(torch.bfloat16)
+
+    def plain(variant, rows=9, E=320, dt=f16):
+        code = dt | (0 if variant is None else (variant + 1) << 8)
+        return N.lib.esmk_op_layernorm(FAKE, FAKE, FAKE, FAKE, None, rows, E, code, None)
+
+    def ex(variant, rows=9, E=320, dt=f16):
+        code = dt | (0 if variant is None else (variant + 1) << 8)
+        return N.lib.esmk_op_layernorm_ex(FAKE, FAKE, FAKE, FAKE, None, rows, E, code, None, 0, 0, 0, 0, 1e-5, None)
+
+    for call, who in ((plain, "esmk_op_layernorm: variant"), (ex, "esmk_op_layernorm_ex: variant")):
+        for variant in (1, 2, 3, 4, 5, 6, 8, 14):
+            for dt in (f16, bf16):
+                assert call(variant, dt=dt) != 0 and who in err(), (variant, err())
+        for variant in (None, 0, 7):
+            assert call(variant, rows=0) != 0 and "variant" not in err(), (variant, err())

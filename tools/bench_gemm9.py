@@ -22,14 +22,8 @@ from esm_amd import _native as nat  # noqa: E402
 from esm_amd import ops  # noqa: E402
 
 
-def set_impl(impl, var=0, desync=0.0, group=0):
-    """False: the library refuses this arm — the gemm9 variants and the de-synchronisation knobs exist only in
-    -DESMK_EXPERIMENTS builds (common.h); the shipped library runs with variant 0 and no delay."""
-    if nat.lib.esmk_debug_gemm_impl(impl, var) != 0:
-        return False
-    knobs = (nat.lib.esmk_debug_set(b"resid_desync", float(desync)) == 0
-             and nat.lib.esmk_debug_set(b"resid_desync_group", float(group)) == 0)
-    return knobs or (desync == 0 and group == 0)
+def set_impl(impl):
+    nat.check(nat.lib.esmk_debug_gemm_impl(impl, 0))
 
 
 def linear_ln_producer(a, w, bias, out, h16, part, mean, half_m=0):
@@ -88,8 +82,8 @@ def check(dt):
         for epi in (nat.EPI_STORE_T, nat.EPI_STORE_F32, nat.EPI_GELU_T, nat.EPI_GELU_F32, nat.EPI_RESID_F32):
             for use_bias in (True, False):
                 outs = []
-                for impl, var in ((8, 0), (9, 0)):
-                    set_impl(impl, var)
+                for impl in (8, 9):
+                    set_impl(impl)
                     x0 = rnd(M, N) if epi == nat.EPI_RESID_F32 else None
                     if x0 is not None:
                         torch.manual_seed(0)
@@ -126,10 +120,8 @@ def main():
     ap.add_argument("--no-vendor", action="store_true")
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--tolerant", action="store_true", help="gemm9 == gemm8 up to the fp32 summation order instead of bit for bit")
-    ap.add_argument("--half", action="store_true", help="time the half-height kernels (small batches) and their experiment variants")
+    ap.add_argument("--half", action="store_true", help="time the half-height kernels (small batches)")
     ap.add_argument("--cases", default="", help="comma-separated substrings of case names to run (default: all)")
-    ap.add_argument("--dbg", action="store_true", help="also the timing-experiment variants of gemm9 (plain store only)")
-    ap.add_argument("--desync", default="", help="residual epilogues: comma-separated fraction:group arms, e.g. 0.25:0,0.5:0,0.5:1,0.5:2")
     args = ap.parse_args()
     print("device:", torch.cuda.get_device_name(0), flush=True)
     global EXACT
@@ -161,65 +153,33 @@ def main():
         bias = rnd(N)
         out = torch.zeros(M, N, device="cuda") if epi == nat.EPI_RESID_F32 else None
         flops = 2.0 * M * N * K
-        arms = [("gemm8", 8, 0), ("gemm9", 9, 0)]
-        hm = 0
-        if args.half:
-            hm = 1
-            arms = [("gemm8 half", 8, 0), ("gemm9 half", 9, 0)]
-            if epi == nat.EPI_STORE_T:
-                arms += [("g9h no-barrier", 9, 8), ("g9h no-mfma", 9, 16), ("g9h no-dma", 9, 32), ("g9h no-reads", 9, 64), ("g9h no-epi", 9, 128),
-                         ("g9h mfma-only", 9, 96), ("g9h skeleton", 9, 224)]
-        if args.dbg and epi == nat.EPI_STORE_T and not args.half:
-            arms += [("g9 dense", 9, 1), ("g9 spread24-61", 9, 2), ("g9 24+2k", 9, 3), ("g9 temporal-st", 9, 4096), ("g9 no-barrier", 9, 8),
-                     ("g9 no-mfma", 9, 16), ("g9 no-dma", 9, 32), ("g9 no-reads", 9, 64), ("g9 no-epi", 9, 128), ("g9 mfma-only", 9, 96)]
-        arms = [a + (0.0, 0) for a in arms]
-        if args.desync and epi == nat.EPI_RESID_F32 and not args.half:
-            for spec in args.desync.split(","):
-                frac, grp = spec.split(":")
-                arms.append((f"g9 desync {frac} g{grp}", 9, 0, float(frac), int(grp)))
-        refused = [a[0] for a in arms if not set_impl(*a[1:])]
-        if refused:
-            print(f"{name:12s} not in this build (needs -DESMK_EXPERIMENTS): {', '.join(refused)}", flush=True)
-            arms = [a for a in arms if a[0] not in refused]
+        hm = 1 if args.half else 0
+        arms = [("gemm8 half", 8), ("gemm9 half", 9)] if args.half else [("gemm8", 8), ("gemm9", 9)]
         times = {a[0]: [] for a in arms}
         if not args.no_vendor and epi == nat.EPI_STORE_T:
             times["vendor"] = []
             bias_t = bias.to(dt)
         for _ in range(args.rounds):
-            for n, impl, var, dsf, dsg in arms:
-                set_impl(impl, var, dsf, dsg)
+            for n, impl in arms:
+                set_impl(impl)
                 times[n].append(timeit(lambda: ops.linear(a, w, bias, epi, out=out, half_m=hm), args.iters))
             if "vendor" in times:
                 times["vendor"].append(timeit(lambda: torch.nn.functional.linear(a, w, bias_t), args.iters))
-        if args.desync and epi == nat.EPI_RESID_F32 and not args.half:  # a delayed start changes no bit
-            outs = []
-            for n, impl, var, dsf, dsg in arms[1:]:
-                set_impl(impl, var, dsf, dsg)
-                x0 = torch.arange(M * N, device="cuda", dtype=torch.float32).reshape(M, N).sin()
-                outs.append(ops.linear(a, w, bias, epi, out=x0))
-            same = all(torch.equal(o, outs[0]) for o in outs[1:])
-            print(f"{name:12s} desync arms bit-identical to the plain launch: {same}", flush=True)
-            bad += 0 if same else 1
-            del outs, x0
         if epi == nat.EPI_RESID_F32 and not args.half:  # the LayerNorm-fold producer next to the plain residual epilogue
             h16 = torch.zeros(M, N, dtype=dt, device="cuda")
             part = torch.zeros(M, (N + 127) // 128, 2, device="cuda")
             mean = torch.zeros(M, device="cuda")
-            set_impl(9, 0)
+            set_impl(9)
             fn = lambda: linear_ln_producer(a, w, bias, out, h16, part, mean)
-            for dbg, tag in ((0, "LN-fold producer"), (1, "  no h16 stores"), (2, "  no statistics"), (4, "  no mean loads"), (7, "  none of them")):
-                if nat.lib.esmk_debug_set(b"lnf_dbg", float(dbg)) != 0:
-                    break  # the producer ablations exist only in -DESMK_EXPERIMENTS builds (common.h)
-                ts = [timeit(fn, args.iters) for _ in range(args.rounds)]
-                loop, ep, seam, ghz = stamps(fn, min(32, (((M + 255) // 256) * ((N + 255) // 256)) // 256), K // 64)
-                ms = statistics.median(ts)
-                print(f"{name:12s} {tag:18s} {ms*1e3:8.1f} us (min {min(ts)*1e3:8.1f}) {flops/ms/1e9:7.1f} TFLOP/s | cycles/K-tile {loop:7.1f} "
-                      f"epilogue {ep:7.0f} seam {seam:6.0f} clock {ghz:4.2f} GHz", flush=True)
-            nat.lib.esmk_debug_set(b"lnf_dbg", 0.0)
+            ts = [timeit(fn, args.iters) for _ in range(args.rounds)]
+            loop, ep, seam, ghz = stamps(fn, min(32, (((M + 255) // 256) * ((N + 255) // 256)) // 256), K // 64)
+            ms = statistics.median(ts)
+            print(f"{name:12s} {'LN-fold producer':18s} {ms*1e3:8.1f} us (min {min(ts)*1e3:8.1f}) {flops/ms/1e9:7.1f} TFLOP/s | cycles/K-tile {loop:7.1f} "
+                  f"epilogue {ep:7.0f} seam {seam:6.0f} clock {ghz:4.2f} GHz", flush=True)
             del h16, part, mean
         nt = ((M + 255) // 256) * ((N + 255) // 256)
-        for n, impl, var, dsf, dsg in arms:
-            set_impl(impl, var, dsf, dsg)
+        for n, impl in arms:
+            set_impl(impl)
             loop, ep, seam, ghz = stamps(lambda: ops.linear(a, w, bias, epi, out=out, half_m=hm), min(32, nt // 256), K // 64)
             ms = statistics.median(times[n])
             print(f"{name:12s} {n:18s} {ms*1e3:8.1f} us (min {min(times[n])*1e3:8.1f}) {flops/ms/1e9:7.1f} TFLOP/s | cycles/K-tile {loop:7.1f} "
@@ -239,7 +199,7 @@ def main():
         res = {}
         for _ in range(args.rounds):
             for n, impl in (("gemm8", 8), ("gemm9", 9)):
-                set_impl(impl, 0)
+                set_impl(impl)
                 res.setdefault(n, []).append(timeit(lambda: qkv(a, wq, bq, args.B, T), args.iters))
         set_impl(8)
         for n, ts in res.items():
