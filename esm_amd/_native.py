@@ -283,6 +283,17 @@ SIGNATURES = {
                 c_double, ctypes.c_uint64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                 c_void_p]),
     "esmk_op_hastings_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p]),
+    # the n-gram term of the design energy, the acceptance with per-chain temperatures and a third term, the replica swap
+    "esmk_op_ngram_energy": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                c_int, c_void_p]),
+    "esmk_op_mh_accept_ex": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
+                c_double, c_double, c_void_p, c_void_p, c_int, ctypes.c_uint64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "esmk_op_replica_swap": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint64, c_int, c_void_p, c_void_p, c_int, c_int,
+                c_void_p]),
     # MSA row selection: mismatch rows, neighbour counts, the greedy pick, race keys and their ranks (msa uint8 [N, ld])
     "esmk_op_msa_mismatch_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "esmk_op_msa_neighbor_counts": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -1075,6 +1075,67 @@ int esmk_op_hastings_rows(const float* logprobs_dev, const int32_t* old_dev, con
     return 0;
 }
 
+// ---- the n-gram term and replica exchange (tempering.hip): everything is refused here before any HIP call ---------------
+int esmk_op_ngram_energy(const int64_t* tokens_dev, const int32_t* code_dev, const double* q1_dev, const double* q2_dev,
+                         const double* q3_dev, const double* q4_dev, int order_mask, double* energy_out_dev, int B, int T, int first,
+                         int S, int V, int A, void* stream) {
+    if (!tokens_dev || !code_dev || !energy_out_dev) return fail("esmk_op_ngram_energy: null argument");
+    if (B <= 0 || T <= 0) return fail("esmk_op_ngram_energy: B and T must be positive");
+    if ((long long)B * T > ESMK_MAX_ROWS) return fail("esmk_op_ngram_energy: B*T exceeds 2^24 rows");
+    if (S <= 0) return fail("esmk_op_ngram_energy: S must be positive");
+    if (S > 32768) return fail("esmk_op_ngram_energy: S above 32768 (the codes of a chain are staged in 32 KiB of LDS)");
+    if (first < 0 || (long long)first + S > T) return fail("esmk_op_ngram_energy: the residues first .. first + S - 1 must lie in [0, T)");
+    if (V <= 0 || V > 64) return fail("esmk_op_ngram_energy: V must be in 1 .. 64");
+    if (A <= 0 || A > 32) return fail("esmk_op_ngram_energy: A must be in 1 .. 32");
+    if ((order_mask & 15) == 0 || (order_mask & ~15) != 0)
+        return fail("esmk_op_ngram_energy: order_mask must choose at least one of the orders 1 .. 4 (bits 0 .. 3) and nothing else");
+    const NgramTables q{{q1_dev, q2_dev, q3_dev, q4_dev}};
+    for (int n = 1; n <= 4; ++n)
+        if (((order_mask >> (n - 1)) & 1) && !q.q[n - 1])
+            return fail("esmk_op_ngram_energy: order " + std::to_string(n) + " is chosen but its table is null");
+    ESMK_TRY(launch_ngram_energy(tokens_dev, code_dev, q, energy_out_dev, B, T, first, S, V, A, order_mask, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_mh_accept_ex(int64_t* tokens_dev, const int32_t* slot_dev, const int32_t* site_dev, const int32_t* tok_dev,
+                         const int32_t* chain_id_dev, const double* e_contact_dev, const double* lp_sum_dev, const int32_t* n_res_dev,
+                         const double* hastings_dev, const double* e_extra_dev, double w_contact, double w_lm, double w_extra,
+                         const double* inv_t_dev, const int32_t* rung_dev, int n_rung, uint64_t seed, int step, double* e_cur_dev,
+                         double* e_contact_cur_dev, double* e_lm_cur_dev, double* e_extra_cur_dev, uint8_t* accepted_out_dev,
+                         double* u_out_dev, double* e_prop_out_dev, int n_chain, int B, int T, void* stream) {
+    if (!tokens_dev || !site_dev || !tok_dev || !chain_id_dev || !e_cur_dev || !accepted_out_dev || !inv_t_dev)
+        return fail("esmk_op_mh_accept_ex: null argument");
+    if (lp_sum_dev && !n_res_dev) return fail("esmk_op_mh_accept_ex: lp_sum without n_res");
+    if (n_chain <= 0 || B <= 0 || T <= 0) return fail("esmk_op_mh_accept_ex: n_chain, B and T must be positive");
+    if ((long long)B * T > ESMK_MAX_ROWS || n_chain > ESMK_MAX_ROWS)
+        return fail("esmk_op_mh_accept_ex: B*T or n_chain exceeds 2^24 rows");
+    if (n_rung <= 0 || n_rung > ESMK_MAX_ROWS) return fail("esmk_op_mh_accept_ex: n_rung must be in 1 .. 2^24");
+    if (!std::isfinite(w_contact) || !std::isfinite(w_lm) || !std::isfinite(w_extra))
+        return fail("esmk_op_mh_accept_ex: the weights must be finite");
+    if (step < 0) return fail("esmk_op_mh_accept_ex: step must not be negative");
+    ESMK_TRY(launch_mh_accept_ex(tokens_dev, slot_dev, site_dev, tok_dev, chain_id_dev, e_contact_dev, lp_sum_dev, n_res_dev,
+                                 hastings_dev, e_extra_dev, w_contact, w_lm, w_extra, inv_t_dev, rung_dev, n_rung,
+                                 (unsigned long long)seed, step, e_cur_dev, e_contact_cur_dev, e_lm_cur_dev, e_extra_cur_dev,
+                                 accepted_out_dev, u_out_dev, e_prop_out_dev, n_chain, B, T, (hipStream_t)stream));
+    return 0;
+}
+
+int esmk_op_replica_swap(int32_t* rung_dev, const double* e_cur_dev, const double* inv_t_dev, const double* inv_t_host,
+                         const int32_t* ladder_id_dev, uint64_t seed, int round, uint8_t* accepted_out_dev, double* u_out_dev,
+                         int n_ladder, int K, void* stream) {
+    if (!rung_dev || !e_cur_dev || !inv_t_dev || !inv_t_host || !ladder_id_dev || !accepted_out_dev || !u_out_dev)
+        return fail("esmk_op_replica_swap: null argument");
+    if (K < 1 || K > 64) return fail("esmk_op_replica_swap: K must be in 1 .. 64");
+    if (n_ladder <= 0 || (long long)n_ladder * K > ESMK_MAX_ROWS) return fail("esmk_op_replica_swap: n_ladder * K must be in 1 .. 2^24");
+    if (round < 0) return fail("esmk_op_replica_swap: round must not be negative");
+    for (int k = 0; k < K; ++k)
+        if (!(inv_t_host[k] >= 0.0) || std::isinf(inv_t_host[k]))
+            return fail("esmk_op_replica_swap: every inv_t must be finite and not negative (a ladder has no greedy rung)");
+    ESMK_TRY(launch_replica_swap(rung_dev, e_cur_dev, inv_t_dev, ladder_id_dev, (unsigned long long)seed, round, accepted_out_dev,
+                                 u_out_dev, n_ladder, K, (hipStream_t)stream));
+    return 0;
+}
+
 // ---- the token front end as single ops (tests/test_frontend_ops_gpu.py) -------------------------------------------
 // Validation of what the engines guarantee their own calls, then the launchers of embed_stage (engine.hip), msa_embed_stage
 // (engine_msa.hip), ensure_rope / ensure_sinus and the row gather of the scoring paths.  Segment tables arrive as host arrays

@@ -276,6 +276,28 @@ hipError_t launch_mh_accept(int64_t* tokens, const int* slot, const int* site, c
 // h[c] = (double)inv_t_prop * ((double)lp[c, old[c]] - (double)lp[c, new[c]]); a token outside [0,V): 0
 hipError_t launch_hastings_rows(const float* lp, const int* old_tok, const int* new_tok, float inv_t_prop, double* h_out, int n, int V,
                                 hipStream_t st);
+// tempering.hip — the n-gram term of the design energy and replica exchange (esm_amd/design.py).  fp64, no atomics.
+// q[n - 1]: the dense background table fp64 [A^n] of order n (device memory), null for an order that is not chosen
+struct NgramTables {
+    const double* q[4];
+};
+// energy[b] = sum over the orders n of order_mask (bit n - 1), ascending, of KL_n = sum over the distinct keys of the chain's valid
+// windows of p log(p / q_n[key]); tokens int64 [B,T], residues first .. first + S - 1, code int32 [V] (-1: outside the alphabet of
+// A <= 32 letters; such a window is left out); one workgroup per chain, fixed order; S <= 32768
+hipError_t launch_ngram_energy(const int64_t* tokens, const int* code, const NgramTables& q, double* energy_out, int B, int T,
+                               int first, int S, int V, int A, int order_mask, hipStream_t st);
+// launch_mh_accept with inv_temperature = inv_t_tab[clamp(rung[c])] (rung null: entry 0) and E' = (w_contact * e_c + w_lm * e_lm) +
+// w_extra * e_extra[c] (e_extra null: the sum of two, the bits of launch_mh_accept); e_extra_cur written on acceptance
+hipError_t launch_mh_accept_ex(int64_t* tokens, const int* slot, const int* site, const int* tok, const int* chain_id,
+                               const double* e_contact, const double* lp_sum, const int* n_res, const double* hastings,
+                               const double* e_extra, double w_contact, double w_lm, double w_extra, const double* inv_t_tab,
+                               const int* rung, int n_rung, unsigned long long seed, int step, double* e_cur, double* e_contact_cur,
+                               double* e_lm_cur, double* e_extra_cur, unsigned char* accepted_out, double* u_out, double* e_prop_out,
+                               int n_chain, int B, int T, hipStream_t st);
+// swap round `round` of n_ladder ladders of K consecutive slots: the chains at rungs k and k + 1, k % 2 == round % 2, exchange
+// their rungs iff a >= 0 or u < exp(a), a = (inv_t[k] - inv_t[k+1]) * (e_cur[x] - e_cur[y]), u at counter (ladder_id, round, 4, k)
+hipError_t launch_replica_swap(int* rung, const double* e_cur, const double* inv_t, const int* ladder_id, unsigned long long seed,
+                               int round, unsigned char* accepted_out, double* u_out, int n_ladder, int K, hipStream_t st);
 // jacobian.hip — the categorical Jacobian J[i,a,j,b] fp32 [L,nA,L,nA] of one protein (esm_amd/jacobian.py); nA <= 32, every
 // index into J 64 bit, every sum fp64 in a fixed order, no atomics.
 // out int64 [n,T]: row i = tokens[src_row[i]] (row 0 when src_row is null; clamped to [0,B)) with position pos[i] set to

@@ -25,9 +25,10 @@ __host__ __device__ inline Philox4 philox4x32_10(unsigned c0, unsigned c1, unsig
 
 // counter word 2: 0 and 1 belong to the sampler (sampling.hip), 2 to the row race of an MSA subsample (msa_select.hip: counter
 // (subsample, 0, 2, row)); a design chain (design.hip) draws its proposal at (chain, step, 2, 0) and its acceptance at (chain,
-// step, 3, 0) — a chain and a subsample are never keyed by the same seed in one computation
+// step, 3, 0) — a chain and a subsample are never keyed by the same seed in one computation; a ladder of replicas
+// (tempering.hip) draws the swap of its rungs k and k + 1 in swap round r at (ladder id, r, 4, k)
 constexpr unsigned kPurposePermutation = 0, kPurposeToken = 1, kPurposeRace = 2;
-constexpr unsigned kPurposeProposal = 2, kPurposeAcceptance = 3;
+constexpr unsigned kPurposeProposal = 2, kPurposeAcceptance = 3, kPurposeSwap = 4;
 
 // First output word of the generator at counter (chain, epoch_or_step, purpose, index) under key (seed lo, seed hi).
 __device__ inline unsigned philox_word0(unsigned long long seed, int chain, int epoch_or_step, unsigned purpose, int index) {

@@ -35,8 +35,19 @@ difference inv_t_prop * (log q(old) - log q(new)) of two log-probabilities of th
 the same alone and in any batch: the random numbers depend on (seed, chain id, step) alone, every kernel computes a row from
 that row alone, and the contact maps carry the bits of ``predict_contacts`` on that sequence alone.
 
-Not built: replica exchange, multi-site proposals, chains of different lengths, token-packed chains, the n-gram term, the MSA
-Transformer (``NotImplementedError``).
+``w_ngram`` adds lm-design's third term, the n-gram term (``utils/ngram.py``): E = (w_contact * E_contact + w_lm * E_lm) + w_ngram *
+E_ngram, E_ngram the sum over the background's orders of the KL divergence between the n-gram frequencies of the sequence and
+the background's (``esm_amd.ngram.Background``, counted from sequences of the caller's choice; ``python -m esm_amd.ngram_table``).
+It is one more op per step on the proposed sequences, ``esmk_op_ngram_energy``, and the acceptance becomes ``esmk_op_mh_accept_ex``.
+
+``replicas=K`` runs the chains as ladders of K consecutive chains at K temperatures (replica exchange).  Chain b starts at rung b % K;
+the acceptance reads every chain's temperature from its rung (``esmk_op_mh_accept_ex``), and after every ``swap_every`` steps the chains
+at neighbouring rungs of a ladder exchange their rungs with probability min(1, exp((1/T_k - 1/T_k+1) * (E_x - E_y)))
+(``esmk_op_replica_swap``: even pairs in even rounds, odd pairs in odd ones; u from counter (chain id of the ladder's first slot,
+round, 4, k)).  Temperatures move, sequences and chain ids stay in their slots, and the forward is the one the batch ran anyway.
+With ``replicas=None`` and ``w_ngram=0`` the calls, the bits and the return values are those of the loop above.
+
+Not built: multi-site proposals, chains of different lengths, token-packed chains, the MSA Transformer (``NotImplementedError``).
 
     python -m esm_amd.design --model-location esm2_t33_650M_UR50D.pt --target-pdb 1abc.pdb --chain A --num-chains 16 \\
         --steps 2000 --anneal 1.0:0.01 --output designs.fasta --log trajectory.csv
@@ -54,6 +65,8 @@ from .scoring import _device_tokens, _refuse_msa, forward_rows
 PROPOSALS = ("uniform", "lm")
 CONTACT_LOSSES = ("pos", "bce")
 TRAJECTORY_FIELDS = ("site", "old", "new", "e_cur", "e_prop", "e_contact", "e_lm", "hastings", "u", "accepted")
+NGRAM_FIELDS = ("e_ngram",)  # the trajectory also holds these with w_ngram != 0 ...
+REPLICA_FIELDS = ("rung", "swapped", "swap_u")  # ... and these with replicas
 IGNORE = 2  # target value of a pair that does not count
 
 _THREE_TO_ONE = {"ALA": "A", "ARG": "R", "ASN": "N", "ASP": "D", "CYS": "C", "GLN": "Q", "GLU": "E", "GLY": "G", "HIS": "H",
@@ -153,11 +166,30 @@ def inverse_temperatures(temperature, steps):
     return [1.0 / t if t > 0.0 else float("inf") for t in temps]
 
 
+def ladder_inverse_temperatures(temperature, steps, K):
+    """fp64 ``[steps, K]`` of 1 / T from a length-``K`` ladder (rung 0 first) or ``steps`` such ladders.  Every temperature is
+    positive and finite: a ladder has no greedy rung."""
+    t = np.asarray(temperature.tolist() if hasattr(temperature, "tolist") else temperature, dtype=np.float64)
+    if t.shape == (K,):
+        t = np.broadcast_to(t, (steps, K))
+    elif t.shape != (steps, K):
+        raise ValueError(f"temperature with replicas = {K}: a ladder of {K} temperatures or {steps} of them, got shape {t.shape}")
+    if not bool((np.isfinite(t) & (t > 0.0)).all()):
+        raise ValueError("the temperatures of a ladder must be positive and finite (a ladder has no greedy rung)")
+    return np.ascontiguousarray(1.0 / t)
+
+
 class _Setup:
     """Everything the host checks and decides before a device is asked for."""
 
-    def __init__(self, model, tokens, target, w_contact, w_lm, contact_loss, min_sep):
+    def __init__(self, model, tokens, target, w_contact, w_lm, contact_loss, min_sep, w_ngram=0.0, ngram=None):
         _refuse_msa(model)
+        self.w_ngram = float(w_ngram)
+        if not math.isfinite(self.w_ngram):
+            raise ValueError("w_ngram must be finite")
+        if self.w_ngram != 0.0 and ngram is None:
+            raise ValueError("w_ngram != 0 needs ngram: an esm_amd.ngram.Background (Background.from_sequences, Background.load)")
+        self.ngram = ngram if self.w_ngram != 0.0 else None  # (w_ngram = 0: the term does not run)
         if tokens.ndim == 1:
             tokens = tokens.unsqueeze(0)
         if tokens.ndim != 2:
@@ -200,6 +232,13 @@ class _Energy:
         self.target = None if setup.target is None else setup.target.to(dev)
         self.V = model.alphabet_size
         self._tables = {}
+        self.ngram_code = self.ngram_q = None
+        if setup.ngram is not None:
+            code = np.full((self.V,), -1, dtype=np.int32)
+            known = setup.ngram.token_codes(model.alphabet)[: self.V]
+            code[: known.shape[0]] = known
+            self.ngram_code = torch.from_numpy(code).to(dev)
+            self.ngram_q = {n: torch.from_numpy(q).to(dev) for n, q in setup.ngram.tables.items()}
 
     def bytes_of(self, B):
         """Workspace of the energy forward of B chains."""
@@ -223,7 +262,8 @@ class _Energy:
         return self._tables[B]
 
     def terms(self, tok):
-        """``(e_contact fp64 [B] or None, lp_sum fp64 [B] or None, n_res int32 [B])`` of ``tok`` int64 [B, T] on the device."""
+        """``(e_contact fp64 [B] or None, lp_sum fp64 [B] or None, n_res int32 [B], e_ngram fp64 [B] or None)`` of ``tok`` int64
+        [B, T] on the device."""
         from . import ops
 
         su = self.su
@@ -237,29 +277,39 @@ class _Energy:
         else:
             lp, e_contact = forward_rows(self.model, tok, sel), None
         lp_sum = ops.sum_target_rows(lp, tok.view(-1)[sel_long].to(torch.int32), off) if want_lm else None
-        return e_contact, lp_sum, n_res
+        e_ngram = None
+        if self.ngram_q is not None:
+            e_ngram = ops.ngram_energy(tok, su.bos, su.S, self.ngram_code, len(su.ngram.alphabet), self.ngram_q)
+        return e_contact, lp_sum, n_res, e_ngram
 
-    def combine(self, e_contact, lp_sum, n_res):
-        """``(E, E_contact, E_lm)`` fp64 [B]: the arithmetic of esmk_op_mh_accept, one rounding per operation (a true division
-        by a device tensor, a product per weight, one sum)."""
+    def combine(self, e_contact, lp_sum, n_res, e_ngram=None):
+        """``(E, E_contact, E_lm)`` fp64 [B], with the n-gram term ``(E, E_contact, E_lm, E_ngram)``: the arithmetic of
+        esmk_op_mh_accept / esmk_op_mh_accept_ex, one rounding per operation (a true division by a device tensor, a product per
+        weight, one sum per further term)."""
         B = n_res.numel()
         zero = torch.zeros((B,), dtype=torch.float64, device=self.dev)
         e_c = zero if e_contact is None else e_contact
         e_lm = zero if lp_sum is None else -(lp_sum / n_res.to(torch.float64))
-        return (self.su.w_contact * e_c) + (self.su.w_lm * e_lm), e_c, e_lm
+        e = (self.su.w_contact * e_c) + (self.su.w_lm * e_lm)
+        if e_ngram is None:
+            return e, e_c, e_lm
+        return e + (self.su.w_ngram * e_ngram), e_c, e_lm, e_ngram
 
 
 @torch.no_grad()
-def design_energy(model, tokens, target, w_contact=1.0, w_lm=1.0, contact_loss="pos", min_sep=6, max_bytes=8 << 30):
+def design_energy(model, tokens, target, w_contact=1.0, w_lm=1.0, contact_loss="pos", min_sep=6, max_bytes=8 << 30, w_ngram=0.0,
+                  ngram=None):
     """The energy ``design`` minimises, for given sequences ``tokens`` int64 ``[B, T]`` (no padding, all of the target's length),
     through the same entry and kernels: a dict of fp64 ``[B]`` device tensors ``energy`` = w_contact * ``e_contact`` + w_lm *
-    ``e_lm``.  A sequence gets the same bits alone and in any batch."""
-    su = _Setup(model, tokens, target, w_contact, w_lm, contact_loss, min_sep)
+    ``e_lm``, with ``w_ngram != 0`` (and ``ngram``, an ``esm_amd.ngram.Background``) plus w_ngram * ``e_ngram``, which the dict
+    then holds too.  A sequence gets the same bits alone and in any batch."""
+    su = _Setup(model, tokens, target, w_contact, w_lm, contact_loss, min_sep, w_ngram, ngram)
     tok = _device_tokens(model, su.tok_cpu)
     en = _Energy(model, su, tok.device)
     step = batch_size(en.bytes_of, su.B, max_bytes)
     parts = [en.combine(*en.terms(tok[lo: lo + step].contiguous())) for lo in range(0, su.B, step)]
-    return {name: torch.cat([p[i] for p in parts]) for i, name in enumerate(("energy", "e_contact", "e_lm"))}
+    names = ("energy", "e_contact", "e_lm") + (NGRAM_FIELDS if su.ngram is not None else ())
+    return {name: torch.cat([p[i] for p in parts]) for i, name in enumerate(names)}
 
 
 def _chain_ids(chain_ids, B):
@@ -276,9 +326,10 @@ def _chain_ids(chain_ids, B):
 @torch.no_grad()
 def design(model, tokens, target, steps, positions=None, w_contact=1.0, w_lm=1.0, contact_loss="pos", min_sep=6, temperature=1.0,
            proposal="uniform", proposal_temperature=1.0, allowed=None, force_new=None, seed=0, chain_ids=None,
-           return_trajectory=False, max_bytes=8 << 30):
+           return_trajectory=False, max_bytes=8 << 30, w_ngram=0.0, ngram=None, replicas=None, swap_every=1):
     """Metropolis-Hastings chains from ``tokens`` int64 ``[B, T]`` (every row a chain; no padding, all of the target's length)
-    toward ``target``: ``(tokens [B, T], energy fp64 [B])`` on the model's device, plus the trajectory when asked for.
+    toward ``target``: ``(tokens [B, T], energy fp64 [B])`` on the model's device — with ``replicas`` ``(tokens, energy, rung int32
+    [B])`` —, plus the trajectory when asked for.
 
     target       ``[S, S]`` bool, uint8 (0 / 1 / 2 = ignore) or float (thresholded at 0.5, NaN = ignore), S = T minus the
                  <cls> / <eos> the alphabet adds (``contacts_from_pdb`` reads one from a PDB file); None with ``w_contact=0``.
@@ -298,10 +349,29 @@ def design(model, tokens, target, steps, positions=None, w_contact=1.0, w_lm=1.0
                  ``e_cur`` (before the step), ``e_prop``, ``e_contact``, ``e_lm`` (the proposal's energy and its terms),
                  ``hastings``, ``u`` fp64 and ``accepted`` uint8.
     max_bytes    chains run in batches whose energy forward, with the contact accumulators of the pinned head-group count, fits
-                 this much workspace."""
+                 this much workspace.  With ``replicas`` a batch holds whole ladders.
+    w_ngram, ngram  the weight of the n-gram term and its background (``esm_amd.ngram.Background``); the trajectory then also
+                 holds ``e_ngram`` (of the proposal).
+    replicas     K >= 2: every K consecutive chains are a ladder (B a multiple of K), chain b starting at rung b % K.
+                 ``temperature`` is then a length-K ladder, rung 0 first, or ``steps`` such ladders (``[steps, K]``), all positive
+                 and finite.  The trajectory also holds ``rung`` int32 (the rung a step ran at), ``swapped`` uint8 and ``swap_u``
+                 fp64 (-1: no swap attempted for that chain after that step).  A ladder runs the same trajectory alone and in any
+                 batch.
+    swap_every   after step s with (s + 1) % swap_every == 0, swap round (s + 1) // swap_every - 1 runs with the temperatures of
+                 step s; 0: never."""
     from . import ops
 
-    su = _Setup(model, tokens, target, w_contact, w_lm, contact_loss, min_sep)
+    su = _Setup(model, tokens, target, w_contact, w_lm, contact_loss, min_sep, w_ngram, ngram)
+    K = None
+    if replicas is not None:
+        K = int(replicas)
+        if K < 2 or K > 64:
+            raise ValueError("replicas: a ladder has 2 .. 64 rungs")
+        if su.B % K != 0:
+            raise ValueError(f"{su.B} chains are no multiple of replicas = {K}: every ladder holds one chain per rung")
+    swap_every = int(swap_every)
+    if swap_every < 0:
+        raise ValueError("swap_every must not be negative (0: no swaps)")
     steps = int(steps)
     if steps < 0 or steps >= 2 ** 31:
         raise ValueError("steps must lie in [0, 2^31)")
@@ -318,7 +388,7 @@ def design(model, tokens, target, steps, positions=None, w_contact=1.0, w_lm=1.0
         if not proposal_temperature > 0.0 or proposal_temperature == float("inf"):
             raise ValueError("proposal_temperature must be positive and finite")
         inv_t_prop = 1.0 / proposal_temperature
-    inv_t = inverse_temperatures(temperature, steps)
+    inv_t = ladder_inverse_temperatures(temperature, steps, K) if K else inverse_temperatures(temperature, steps)
     mask = allowed_mask(model, allowed)
     lists = _position_lists(model, su.tok_cpu, positions)
     if lm:
@@ -332,8 +402,20 @@ def design(model, tokens, target, steps, positions=None, w_contact=1.0, w_lm=1.0
     state = _device_tokens(model, su.tok_cpu).clone()
     dev = state.device
     en = _Energy(model, su, dev)
-    per = batch_size(en.bytes_of, su.B, max_bytes)
-    energies, trajs = [], []
+    ex = None  # the plain loop: esmk_op_mh_accept with the step's scalar temperature
+    if K or su.ngram is not None:
+        table = inv_t if K else np.asarray(inv_t, dtype=np.float64).reshape(steps, 1)
+        ex = dict(K=K, swap_every=swap_every, inv_t_host=table,
+                  inv_t=torch.from_numpy(table).to(dev) if steps else torch.zeros((0, K or 1), dtype=torch.float64, device=dev))
+    if K:
+        if en.bytes_of(K) > int(max_bytes):
+            raise ValueError(f"max_bytes = {int(max_bytes)}: the energy forward of one ladder of {K} chains takes {en.bytes_of(K)} "
+                             "bytes of workspace, and a batch holds whole ladders")
+        per = K * batch_size(lambda n: en.bytes_of(n * K), su.B // K, max_bytes)
+    else:
+        per = batch_size(en.bytes_of, su.B, max_bytes)
+    fields = TRAJECTORY_FIELDS + (NGRAM_FIELDS if su.ngram is not None else ()) + (REPLICA_FIELDS if K else ())
+    energies, trajs, rungs = [], [], []
     for lo in range(0, su.B, per):
         hi = min(lo + per, su.B)
         starts = [0]
@@ -342,33 +424,43 @@ def design(model, tokens, target, steps, positions=None, w_contact=1.0, w_lm=1.0
         pos_off = torch.tensor(starts, dtype=torch.int32).to(dev)
         pos = torch.tensor([p for ps in lists[lo:hi] for p in ps], dtype=torch.int32).to(dev)
         part = state[lo:hi]  # a view: rows of a contiguous matrix are contiguous
-        e, traj = _run(model, en, part, pos_off, pos, ids_cpu[lo:hi].to(dev), steps, inv_t, lm, inv_t_prop, mask, bool(force_new), seed,
-                       return_trajectory)
+        e, traj, rung = _run(model, en, part, pos_off, pos, ids_cpu[lo:hi].to(dev), steps, inv_t, lm, inv_t_prop, mask, bool(force_new),
+                             seed, return_trajectory, fields, ex)
         energies.append(e)
         trajs.append(traj)
-    energy = torch.cat(energies)
+        rungs.append(rung)
+    out = (state, torch.cat(energies)) + ((torch.cat(rungs),) if K else ())
     if not return_trajectory:
-        return state, energy
-    return state, energy, {name: torch.cat([t[name] for t in trajs], dim=1) for name in TRAJECTORY_FIELDS}
+        return out
+    return out + ({name: torch.cat([t[name] for t in trajs], dim=1) for name in fields},)
 
 
-_FIELD_DTYPES = dict(site=torch.int32, old=torch.int32, new=torch.int32, accepted=torch.uint8)
+_FIELD_DTYPES = dict(site=torch.int32, old=torch.int32, new=torch.int32, accepted=torch.uint8, rung=torch.int32, swapped=torch.uint8)
 
 
-def _run(model, en, state, pos_off, pos, ids, steps, inv_t, lm, inv_t_prop, mask, force_new, seed, return_trajectory):
+def _run(model, en, state, pos_off, pos, ids, steps, inv_t, lm, inv_t_prop, mask, force_new, seed, return_trajectory, fields, ex):
     """The step loop on one batch: ``state`` int64 [n, T] (a view of the caller's matrix) is updated in place; nothing inside
-    the loop waits for the device."""
+    the loop waits for the device.  ``ex`` None: the plain loop.  Else the per-step tables of inverse temperatures (``inv_t`` on the
+    device, ``inv_t_host`` [steps, n_rung]) of esmk_op_mh_accept_ex and, with ``K``, the ladders and their swaps."""
     from . import ops
 
     su = en.su
     n, T = state.shape
     dev = state.device
-    e_cur, e_contact_cur, e_lm_cur = (t.clone() for t in en.combine(*en.terms(state)))
+    e_cur, e_contact_cur, e_lm_cur, *rest = (t.clone() for t in en.combine(*en.terms(state)))
+    e_ngram_cur = rest[0] if rest else None
     rows = torch.arange(n, dtype=torch.int32, device=dev)
     row0 = rows * T
     one_each = torch.arange(n + 1, dtype=torch.int32, device=dev)
     zero = torch.zeros((n,), dtype=torch.float64, device=dev)
-    traj = {name: [] for name in TRAJECTORY_FIELDS}
+    K = ex["K"] if ex is not None else None
+    rung = None
+    if K:
+        rung = (rows % K).contiguous()
+        ladder_ids = ids.view(-1, K)[:, 0].contiguous()
+        no_swap = torch.zeros((n,), dtype=torch.uint8, device=dev)
+        no_u = torch.full((n,), -1.0, dtype=torch.float64, device=dev)
+    traj = {name: [] for name in fields}
     for s in range(steps):
         site, old, new = ops.propose_mutations(state, pos_off, pos, ids, mask, force_new=force_new, seed=seed, step=s)
         hastings = None
@@ -379,22 +471,38 @@ def _run(model, en, state, pos_off, pos, ids, steps, inv_t, lm, inv_t_prop, mask
             new = torch.where(site >= 0, drawn, torch.full_like(drawn, -1))
             hastings = ops.hastings_rows(lp_site, old, new, inv_t_prop)
         proposed = ops.substitute_rows(state, site, new, src_rows=rows, vocab=en.V)
-        e_contact, lp_sum, n_res = en.terms(proposed)
+        e_contact, lp_sum, n_res, e_ngram = en.terms(proposed)
         before = e_cur.clone() if return_trajectory else None
-        accepted, u, e_prop = ops.mh_accept(state, site, new, ids, e_cur, e_contact=e_contact, lp_sum=lp_sum, n_res=n_res,
-                                            hastings=hastings, w_contact=su.w_contact, w_lm=su.w_lm, inv_temperature=inv_t[s],
-                                            seed=seed, step=s, e_contact_cur=e_contact_cur, e_lm_cur=e_lm_cur)
+        if ex is None:
+            accepted, u, e_prop = ops.mh_accept(state, site, new, ids, e_cur, e_contact=e_contact, lp_sum=lp_sum, n_res=n_res,
+                                                hastings=hastings, w_contact=su.w_contact, w_lm=su.w_lm, inv_temperature=inv_t[s],
+                                                seed=seed, step=s, e_contact_cur=e_contact_cur, e_lm_cur=e_lm_cur)
+        else:
+            ran_at = rung.clone() if K and return_trajectory else None
+            accepted, u, e_prop = ops.mh_accept_ex(state, site, new, ids, e_cur, ex["inv_t"][s], rung=rung, e_contact=e_contact,
+                                                   lp_sum=lp_sum, n_res=n_res, hastings=hastings, e_extra=e_ngram,
+                                                   w_contact=su.w_contact, w_lm=su.w_lm, w_extra=su.w_ngram, seed=seed, step=s,
+                                                   e_contact_cur=e_contact_cur, e_lm_cur=e_lm_cur, e_extra_cur=e_ngram_cur)
+            swapped, swap_u = (no_swap, no_u) if K else (None, None)
+            if K and ex["swap_every"] > 0 and (s + 1) % ex["swap_every"] == 0:
+                swapped, swap_u = ops.replica_swap(rung, e_cur, ex["inv_t"][s], ex["inv_t_host"][s], ladder_ids, seed=seed,
+                                                   round=(s + 1) // ex["swap_every"] - 1)
         if return_trajectory:
             _, e_c, e_lm = en.combine(e_contact, lp_sum, n_res)
-            for name, value in zip(TRAJECTORY_FIELDS, (site, old, new, before, e_prop, e_c, e_lm,
-                                                       zero if hastings is None else hastings, u, accepted)):
-                traj[name].append(value)
+            values = dict(zip(TRAJECTORY_FIELDS, (site, old, new, before, e_prop, e_c, e_lm, zero if hastings is None else hastings,
+                                                  u, accepted)))
+            if e_ngram is not None:
+                values["e_ngram"] = e_ngram
+            if K:
+                values.update(rung=ran_at, swapped=swapped, swap_u=swap_u)
+            for name in fields:
+                traj[name].append(values[name])
     if not return_trajectory:
-        return e_cur, None
+        return e_cur, None, rung
     out = {}
     for name, parts in traj.items():
         out[name] = torch.stack(parts) if parts else torch.empty((0, n), dtype=_FIELD_DTYPES.get(name, torch.float64), device=dev)
-    return e_cur, out
+    return e_cur, out, rung
 
 
 # ---- python -m esm_amd.design ---------------------------------------------------------------------------------------------------
@@ -447,6 +555,13 @@ def parse_args(argv=None):
     s = p.add_mutually_exclusive_group()
     s.add_argument("--temperature", type=_at_least(0.0, float), default=None, help="constant temperature (default 1; 0: greedy)")
     s.add_argument("--anneal", type=_anneal, default=None, metavar="T0:T1", help="geometric ladder from T0 to T1")
+    s.add_argument("--ladder", type=_anneal, default=None, metavar="T0:T1",
+                   help="with --replicas K: K geometric temperatures, rung 0 = T0, held for the whole run")
+    p.add_argument("--replicas", type=_at_least(2), default=None, metavar="K",
+                   help="replica exchange: every K consecutive chains are a ladder (needs --ladder)")
+    p.add_argument("--swap-every", type=_at_least(0), default=1, metavar="N", help="steps between swap rounds (0: never)")
+    p.add_argument("--w-ngram", type=float, default=0.0, help="weight of the n-gram term (needs --ngram-table)")
+    p.add_argument("--ngram-table", default=None, help=".npz background of `python -m esm_amd.ngram_table`")
     p.add_argument("--proposal", choices=PROPOSALS, default="uniform")
     p.add_argument("--proposal-temperature", type=float, default=1.0)
     p.add_argument("--w-contact", type=float, default=1.0)
@@ -463,6 +578,12 @@ def parse_args(argv=None):
         p.error("--length goes with --no-target: the target sets the length")
     if a.chain is not None and a.target_pdb is None:
         p.error("--chain goes with --target-pdb")
+    if (a.replicas is None) != (a.ladder is None):
+        p.error("--replicas K and --ladder T0:T1 go together")
+    if a.replicas is not None and a.num_chains % a.replicas != 0:
+        p.error(f"--num-chains {a.num_chains} is no multiple of --replicas {a.replicas}")
+    if a.w_ngram != 0.0 and a.ngram_table is None:
+        p.error("--w-ngram needs --ngram-table")
     return a
 
 
@@ -472,20 +593,22 @@ def random_sequences(n, length, seed, residues="ACDEFGHIKLMNPQRSTVWY"):
     return ["".join(residues[i] for i in rng.integers(0, len(residues), size=length)) for _ in range(n)]
 
 
-def write_fasta(path, label, chain_ids, sequences, energies, seed):
+def write_fasta(path, label, chain_ids, sequences, energies, seed, rungs=None):
     with open(path, "w") as fh:
-        for cid, seq, e in zip(chain_ids, sequences, energies):
-            fh.write(f">{label}|chain={cid}|seed={seed}|energy={e:.6f}\n{seq}\n")
+        for i, (cid, seq, e) in enumerate(zip(chain_ids, sequences, energies)):
+            rung = "" if rungs is None else f"|rung={rungs[i]}"
+            fh.write(f">{label}|chain={cid}|seed={seed}|energy={e:.6f}{rung}\n{seq}\n")
 
 
 def write_log(path, traj, chain_ids):
     host = {k: v.cpu().numpy() for k, v in traj.items()}
+    fields = [k for k in TRAJECTORY_FIELDS + NGRAM_FIELDS + REPLICA_FIELDS if k in host]
     with open(path, "w") as fh:
-        fh.write("step,chain," + ",".join(TRAJECTORY_FIELDS) + "\n")
+        fh.write("step,chain," + ",".join(fields) + "\n")
         steps, n = host["site"].shape
         for s in range(steps):
             for c in range(n):
-                fh.write(f"{s},{chain_ids[c]}," + ",".join(repr(host[k][s, c].item()) for k in TRAJECTORY_FIELDS) + "\n")
+                fh.write(f"{s},{chain_ids[c]}," + ",".join(repr(host[k][s, c].item()) for k in fields) + "\n")
 
 
 def decode(alphabet, row, bos, eos):
@@ -520,15 +643,24 @@ def main(argv=None):
         starts = random_sequences(a.num_chains, length, a.seed)
     tokens = convert([(str(c), s) for c, s in enumerate(starts)])[2]
     temperature = anneal_ladder(*a.anneal, a.steps) if a.anneal else (1.0 if a.temperature is None else a.temperature)
+    extra = {}
+    if a.replicas is not None:
+        temperature = anneal_ladder(*a.ladder, a.replicas)
+        extra.update(replicas=a.replicas, swap_every=a.swap_every)
+    if a.w_ngram != 0.0:
+        from .ngram import Background
+
+        extra.update(w_ngram=a.w_ngram, ngram=Background.load(a.ngram_table))
     out = design(model, tokens, target, a.steps, w_contact=0.0 if a.no_target else a.w_contact, w_lm=a.w_lm,
                  contact_loss=a.contact_loss, min_sep=a.min_sep, temperature=temperature, proposal=a.proposal,
-                 proposal_temperature=a.proposal_temperature, seed=a.seed, return_trajectory=a.log is not None)
+                 proposal_temperature=a.proposal_temperature, seed=a.seed, return_trajectory=a.log is not None, **extra)
     final, energy = out[0].cpu(), out[1].cpu().tolist()
+    rungs = out[2].cpu().tolist() if a.replicas is not None else None
     bos, eos = int(bool(model.prepend_bos)), int(bool(model.append_eos))
     ids = list(range(a.num_chains))
-    write_fasta(a.output, label, ids, [decode(alphabet, row.tolist(), bos, eos) for row in final], energy, a.seed)
+    write_fasta(a.output, label, ids, [decode(alphabet, row.tolist(), bos, eos) for row in final], energy, a.seed, rungs)
     if a.log is not None:
-        write_log(a.log, out[2], ids)
+        write_log(a.log, out[-1], ids)
     print(f"{a.num_chains} chains, {a.steps} steps: energy {min(energy):.4f} .. {max(energy):.4f} -> {a.output}", file=sys.stderr)
 
 

@@ -432,22 +432,25 @@ class ESM2(_EngineHost, nn.Module):
     # design toward a target contact map (esm_amd/design.py): Metropolis-Hastings chains, every step on the device
     def design(self, tokens, target, steps, positions=None, w_contact=1.0, w_lm=1.0, contact_loss="pos", min_sep=6,
                temperature=1.0, proposal="uniform", proposal_temperature=1.0, allowed=None, force_new=None, seed=0, chain_ids=None,
-               return_trajectory=False, max_bytes=8 << 30):
+               return_trajectory=False, max_bytes=8 << 30, w_ngram=0.0, ngram=None, replicas=None, swap_every=1):
         """``esm_amd.design.design``: (final tokens [B, T], final energies fp64 [B]) of ``steps`` Metropolis-Hastings steps per
-        chain on E = w_contact * E_contact(predicted map, target) + w_lm * E_lm."""
+        chain on E = w_contact * E_contact(predicted map, target) + w_lm * E_lm (+ w_ngram * E_ngram); with ``replicas`` the chains
+        are temperature ladders that exchange their rungs, and the rungs are returned too."""
         from . import design as D
 
         return D.design(self, tokens, target, steps, positions=positions, w_contact=w_contact, w_lm=w_lm, contact_loss=contact_loss,
                         min_sep=min_sep, temperature=temperature, proposal=proposal, proposal_temperature=proposal_temperature,
                         allowed=allowed, force_new=force_new, seed=seed, chain_ids=chain_ids,
-                        return_trajectory=return_trajectory, max_bytes=max_bytes)
+                        return_trajectory=return_trajectory, max_bytes=max_bytes, w_ngram=w_ngram, ngram=ngram, replicas=replicas,
+                        swap_every=swap_every)
 
-    def design_energy(self, tokens, target, w_contact=1.0, w_lm=1.0, contact_loss="pos", min_sep=6, max_bytes=8 << 30):
-        """``esm_amd.design.design_energy``: the energy ``design`` minimises and its two terms, fp64 [B] each."""
+    def design_energy(self, tokens, target, w_contact=1.0, w_lm=1.0, contact_loss="pos", min_sep=6, max_bytes=8 << 30, w_ngram=0.0,
+                      ngram=None):
+        """``esm_amd.design.design_energy``: the energy ``design`` minimises and its terms, fp64 [B] each."""
         from . import design as D
 
         return D.design_energy(self, tokens, target, w_contact=w_contact, w_lm=w_lm, contact_loss=contact_loss, min_sep=min_sep,
-                               max_bytes=max_bytes)
+                               max_bytes=max_bytes, w_ngram=w_ngram, ngram=ngram)
 
     # the categorical Jacobian (esm_amd/jacobian.py): substituted copies in batches that fill the GPU, J kept on the device
     def categorical_jacobian(self, tokens, allowed=None, chunk=None, center=False, max_bytes=8 << 30):

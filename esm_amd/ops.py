@@ -851,6 +851,85 @@ def hastings_rows(logprobs, old, new, inv_t_prop=1.0):
     return out
 
 
+# ---- the n-gram term and replica exchange (include/esmk.h: esmk_op_ngram_energy ... esmk_op_replica_swap) -----------------------
+def ngram_energy(tokens, first, S, code, A, tables):
+    """fp64 [B]: lm-design's n-gram term of every chain of ``tokens`` int64 [B, T], whose residues are the positions ``first`` ..
+    ``first + S - 1``.  ``code`` int32 [V] maps a token to 0 .. A-1 or -1 (outside the alphabet: its windows are left out);
+    ``tables`` is a dict order n (1 .. 4) -> fp64 [A^n] of positive background probabilities, all on the device.  Per order the KL
+    divergence sum p log(p / q) over the distinct n-grams of the chain, p their frequency among its valid windows; the orders
+    are added ascending.  The order of addition does not depend on B."""
+    _req_cuda(tokens, code, *tables.values())
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.is_contiguous()
+    assert code.dtype == torch.int32 and code.dim() == 1 and code.is_contiguous()
+    B, T = tokens.shape
+    A = int(A)
+    mask, ptrs = 0, [None] * 4
+    for n, q in tables.items():
+        n = int(n)
+        if not 1 <= n <= 4:
+            raise ValueError(f"n-gram order {n}: one of 1 .. 4")
+        assert q.dtype == torch.float64 and q.dim() == 1 and q.numel() == A ** n and q.is_contiguous()
+        mask |= 1 << (n - 1)
+        ptrs[n - 1] = N.ptr(q)
+    out = torch.empty((B,), dtype=torch.float64, device=tokens.device)
+    N.check(N.lib.esmk_op_ngram_energy(N.ptr(tokens), N.ptr(code), *ptrs, mask, N.ptr(out), B, T, int(first), int(S),
+                                       code.numel(), A, N.cur_stream()))
+    return out
+
+
+def mh_accept_ex(tokens, site, tok, chain_ids, e_cur, inv_t, rung=None, e_contact=None, lp_sum=None, n_res=None, hastings=None,
+                 e_extra=None, w_contact=1.0, w_lm=1.0, w_extra=0.0, seed=0, step=0, slots=None, e_contact_cur=None, e_lm_cur=None,
+                 e_extra_cur=None):
+    """``mh_accept`` with a temperature per chain and a third energy term: chain c uses ``inv_t[rung[c]]`` (``inv_t`` fp64
+    [n_rung] on the device, ``rung`` int32 [n_chain] clamped, None: entry 0) and E' = (w_contact * e_contact + w_lm * -(lp_sum /
+    n_res)) + w_extra * e_extra (``e_extra`` None: the sum of two).  With ``e_extra`` None and one rung the bits of ``mh_accept``.
+    An accepted chain also gets ``e_extra_cur = e_extra``."""
+    f64 = (e_cur, e_contact, lp_sum, hastings, e_extra, e_contact_cur, e_lm_cur, e_extra_cur)
+    i32 = (site, tok, chain_ids, n_res, slots, rung)
+    _req_cuda(tokens, inv_t, *f64, *i32)
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.is_contiguous()
+    assert inv_t.dtype == torch.float64 and inv_t.dim() == 1 and inv_t.numel() >= 1 and inv_t.is_contiguous()
+    n_chain = chain_ids.numel()
+    for t in f64:
+        assert t is None or (t.dtype == torch.float64 and t.dim() == 1 and t.numel() == n_chain and t.is_contiguous())
+    for t in i32:
+        assert t is None or (t.dtype == torch.int32 and t.dim() == 1 and t.numel() == n_chain and t.is_contiguous())
+    B, T = tokens.shape
+    assert n_chain >= 1 and (slots is not None or n_chain <= B) and (lp_sum is None or n_res is not None)
+    dev = tokens.device
+    accepted = torch.empty((n_chain,), dtype=torch.uint8, device=dev)
+    u = torch.empty((n_chain,), dtype=torch.float64, device=dev)
+    e_prop = torch.empty((n_chain,), dtype=torch.float64, device=dev)
+    N.check(N.lib.esmk_op_mh_accept_ex(N.ptr(tokens), N.ptr(slots), N.ptr(site), N.ptr(tok), N.ptr(chain_ids), N.ptr(e_contact),
+                                       N.ptr(lp_sum), N.ptr(n_res), N.ptr(hastings), N.ptr(e_extra), float(w_contact), float(w_lm),
+                                       float(w_extra), N.ptr(inv_t), N.ptr(rung), inv_t.numel(), _seed64(seed), int(step),
+                                       N.ptr(e_cur), N.ptr(e_contact_cur), N.ptr(e_lm_cur), N.ptr(e_extra_cur), N.ptr(accepted),
+                                       N.ptr(u), N.ptr(e_prop), n_chain, B, T, N.cur_stream()))
+    return accepted, u, e_prop
+
+
+def replica_swap(rung, e_cur, inv_t, inv_t_host, ladder_ids, seed=0, round=0):
+    """Swap round ``round`` of the ladders of K = ``inv_t.numel()`` consecutive chains, in place on ``rung`` int32 [n_ladder * K] (a
+    permutation of 0 .. K-1 per ladder): ``(accepted uint8, u fp64)`` [n_ladder * K] each.  The chains at rungs k and k + 1, k % 2
+    == round % 2, exchange their rungs iff a >= 0 or u < exp(a) with a = (inv_t[k] - inv_t[k+1]) * (e_cur[x] - e_cur[y]) and u the
+    24-bit uniform of Philox counter (ladder_ids[l], round, 4, k); u is -1 for a chain without a partner in this round.
+    ``inv_t_host``: the K values on the host (a sequence of floats), checked there: finite and not negative."""
+    _req_cuda(rung, e_cur, inv_t, ladder_ids)
+    K = inv_t.numel()
+    assert inv_t.dtype == torch.float64 and inv_t.dim() == 1 and inv_t.is_contiguous() and K >= 1
+    n_ladder = ladder_ids.numel()
+    assert ladder_ids.dtype == torch.int32 and ladder_ids.dim() == 1 and ladder_ids.is_contiguous() and n_ladder >= 1
+    assert rung.dtype == torch.int32 and rung.dim() == 1 and rung.numel() == n_ladder * K and rung.is_contiguous()
+    assert e_cur.dtype == torch.float64 and e_cur.dim() == 1 and e_cur.numel() == n_ladder * K and e_cur.is_contiguous()
+    host = [float(v) for v in inv_t_host]
+    assert len(host) == K
+    accepted = torch.empty((n_ladder * K,), dtype=torch.uint8, device=rung.device)
+    u = torch.empty((n_ladder * K,), dtype=torch.float64, device=rung.device)
+    N.check(N.lib.esmk_op_replica_swap(N.ptr(rung), N.ptr(e_cur), N.ptr(inv_t), (ctypes.c_double * K)(*host), N.ptr(ladder_ids),
+                                       _seed64(seed), int(round), N.ptr(accepted), N.ptr(u), n_ladder, K, N.cur_stream()))
+    return accepted, u
+
+
 # ---- MSA row selection (include/esmk.h: esmk_op_msa_mismatch_rows ... esmk_op_rank_keys) --------------------------------------
 def _msa_dims(msa, L):
     """(N, L, ld) of a device byte matrix uint8 [N, ld] of which the first ``L`` columns count (None: all)."""

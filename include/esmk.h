@@ -869,6 +869,51 @@ int esmk_op_mh_accept(int64_t* tokens_dev, const int32_t* slot_dev, const int32_
 int esmk_op_hastings_rows(const float* logprobs_dev, const int32_t* old_dev, const int32_t* new_dev, float inv_t_prop,
                           double* h_out_dev, int n, int V, void* stream);
 
+/* The n-gram term of the design energy and replica exchange (esm_amd/design.py; csrc/tempering.hip).  fp64, every operation rounded
+ * once (no fused multiply-add), no atomics.
+ * esmk_op_ngram_energy: lm-design's n-gram term (examples/lm-design/utils/ngram.py, compute_kl_div).  tokens int64 [B,T]; the S
+ *   residues of a chain are the positions first .. first + S - 1; code int32 [V] maps a token to 0 .. A-1 or to -1 (a token outside
+ *   [0,V), or a code outside [0,A), counts as -1).  order_mask: bit n-1 chooses order n = 1 .. 4; qn_dev fp64 [A^n] is the dense
+ *   background table of order n, every entry finite and positive (the caller has applied the floor).  Per chain and chosen order:
+ *   window i (0 <= i <= S-n) is valid iff its n codes are all >= 0, its key is sum_k code[i+k] * A^(n-1-k); total = the valid
+ *   windows, c_i = the valid windows with the key of window i, window i is a first window iff no valid j < i has its key; KL_n =
+ *   the sum over the first windows of p * log(p / qn[key]), p = c_i / total; total == 0 (S < n included): KL_n = 0.0.
+ *   energy_out fp64 [B] = (((0.0 + KL_a) + KL_b) + ...) over the chosen orders, ascending.  One workgroup of 256 lanes per chain:
+ *   lane t adds the terms of the first windows among t, t + 256, ... in that order (any other window adds nothing), the lane sums
+ *   are added in a butterfly per wavefront and the four wavefront sums in order: the order of addition depends on S and
+ *   order_mask alone, and a chain gets the same bits alone and in any batch.  The counts are pairwise (S^2 comparisons per order).
+ * esmk_op_mh_accept_ex: esmk_op_mh_accept with a temperature per chain and a third energy term.  inv_t fp64 [n_rung], rung int32
+ *   [n_chain] or NULL (rung 0): chain c uses inv_t[clamp(rung[c], 0, n_rung-1)] (+inf: greedy, negative or NaN: rejects unless a
+ *   >= 0 holds, as any NaN).  e_extra fp64 [n_chain] or NULL: E' = (w_contact * e_contact[c] + w_lm * e_lm) + w_extra * e_extra[c];
+ *   with e_extra NULL the last addition is not made, and that call with one rung gives the bits of esmk_op_mh_accept.  On
+ *   acceptance e_extra_cur[c] (fp64 [n_chain] or NULL) = e_extra[c].  Counter, rule and the other outputs: esmk_op_mh_accept.
+ * esmk_op_replica_swap: chains form ladders of K consecutive slots (ladder l: slots l*K .. l*K+K-1); rung int32 [n_ladder*K]
+ *   holds a permutation of 0 .. K-1 per ladder, inv_t fp64 [K].  In swap round r one lane per pair (ladder l, lower rung k), k % 2
+ *   == r % 2 and k+1 < K, scans the ladder's K slots for the chain x at rung k and the chain y at rung k+1, computes a = (inv_t[k]
+ *   - inv_t[k+1]) * (e_cur[x] - e_cur[y]) and u = (word0 >> 8) * 2^-24 at Philox counter (ladder_id[l], r, 4, k) — purpose 4 = swap,
+ *   next to 0 .. 3 — and accepts iff a >= 0 or u < exp(a) (a NaN rejects): rung[x] = k+1, rung[y] = k.  Temperatures move, sequences
+ *   and chain ids stay with their slots.  The pairs of a round are disjoint: plain stores.  accepted_out uint8 [n_ladder*K]: 1 for
+ *   both chains of an accepted pair, else 0; u_out fp64 [n_ladder*K]: the pair's u for both chains of an attempted pair, -1.0
+ *   elsewhere.  inv_t_host: the caller's host copy of inv_t, read for validation only.
+ * Refused before any HIP call: null pointers (slot_dev, e_contact_dev, lp_sum_dev with n_res_dev, hastings_dev, e_extra_dev,
+ * rung_dev of esmk_op_mh_accept_ex, the *_cur_dev components, u_out_dev and e_prop_out_dev of esmk_op_mh_accept_ex, and the table of
+ * an order that is not chosen may be NULL), B, T, S, n_chain, n_ladder or n_rung <= 0, B*T, n_chain, n_rung or n_ladder*K > 2^24,
+ * S > 32768, first < 0 or first + S > T, V outside 1 .. 64, A outside 1 .. 32, an order_mask without one of the bits 0 .. 3 or
+ * with another bit, a chosen order whose table is NULL, weights that are not finite, a negative step or round, K outside 1 .. 64,
+ * an inv_t_host entry that is negative, NaN or infinite (a ladder has no greedy rung). */
+int esmk_op_ngram_energy(const int64_t* tokens_dev, const int32_t* code_dev, const double* q1_dev, const double* q2_dev,
+                         const double* q3_dev, const double* q4_dev, int order_mask, double* energy_out_dev, int B, int T, int first,
+                         int S, int V, int A, void* stream);
+int esmk_op_mh_accept_ex(int64_t* tokens_dev, const int32_t* slot_dev, const int32_t* site_dev, const int32_t* tok_dev,
+                         const int32_t* chain_id_dev, const double* e_contact_dev, const double* lp_sum_dev, const int32_t* n_res_dev,
+                         const double* hastings_dev, const double* e_extra_dev, double w_contact, double w_lm, double w_extra,
+                         const double* inv_t_dev, const int32_t* rung_dev, int n_rung, uint64_t seed, int step, double* e_cur_dev,
+                         double* e_contact_cur_dev, double* e_lm_cur_dev, double* e_extra_cur_dev, uint8_t* accepted_out_dev,
+                         double* u_out_dev, double* e_prop_out_dev, int n_chain, int B, int T, void* stream);
+int esmk_op_replica_swap(int32_t* rung_dev, const double* e_cur_dev, const double* inv_t_dev, const double* inv_t_host,
+                         const int32_t* ladder_id_dev, uint64_t seed, int round, uint8_t* accepted_out_dev, double* u_out_dev,
+                         int n_ladder, int K, void* stream);
+
 /* Choosing the rows of an MSA on the device (esm_amd/msa_select.py; csrc/msa_select.hip).  An MSA is msa uint8 [N,ld], row-major:
  * L <= ld columns count, bytes in [L,ld) of a row are never counted whatever they hold, and every byte value 0 .. 255 is legal
  * (a gap is a byte like any other).  mism(i,j) = #{c < L : msa[i,c] != msa[j,c]}.  Integer arithmetic and comparison logic
