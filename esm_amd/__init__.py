@@ -19,6 +19,7 @@ from .msa_select import (encode_msa, msa_mismatches, msa_neff, msa_neighbor_coun
 from .sampling import gibbs_sample, inpaint  # noqa: F401
 from .jacobian import categorical_jacobian, jacobian_contacts  # noqa: F401
 from .windows import forward_windows  # noqa: F401
+from .interventions import StreamEdit, forward_edited, mean_difference, stream_edits  # noqa: F401
 
 
 def __getattr__(name):

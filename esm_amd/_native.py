@@ -16,6 +16,7 @@ OUT_LOGITS, OUT_ATTN, OUT_CONTACTS, OUT_COL_ATTN, OUT_REPR_LOWP, OUT_ATTN_LOWP =
 EPI_STORE_T, EPI_STORE_F32, EPI_GELU_T, EPI_GELU_F32, EPI_RESID_F32 = 0, 1, 2, 3, 4
 EPI_QKV_ROPE, EPI_V_T, EPI_MSA_CTX = 5, 6, 7
 ESM1, ESM1_FINAL_BIAS = 2, 4  # esmk_config.no_rope values of the original ESM-1 architecture (include/esmk.h)
+EDIT_AXPBY, EDIT_PROJECT, MAX_STREAM_EDITS = 0, 1, 64  # esmk_stream_edit.op; the longest list esmk_set_stream_edits takes
 
 
 class EsmkConfig(ctypes.Structure):
@@ -45,6 +46,13 @@ class EsmkMsaConfig(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in (
         "num_layers", "embed_dim", "num_heads", "ffn_dim", "vocab", "pad_idx", "mask_idx", "cls_idx", "eos_idx",
         "prepend_bos", "append_eos", "num_positions", "has_msa_position_embedding", "operand_dtype", "weight_split")]
+
+
+class EsmkStreamEdit(ctypes.Structure):
+    """esmk_stream_edit (include/esmk.h): one edit of the residual stream after ``layer`` layers."""
+    _fields_ = [("layer", c_int32), ("op", c_int32), ("keep", c_float), ("gain", c_float),
+                ("rows_dev", c_void_p), ("n_rows", c_int32), ("token_set", ctypes.c_uint64),
+                ("src_dev", c_void_p), ("src_ld", c_int32), ("n_src", c_int32), ("src_index_dev", c_void_p)]
 
 
 class EsmkProfileEntry(ctypes.Structure):
@@ -103,6 +111,10 @@ SIGNATURES = {
     "esmk_forward_rows_contacts": (
         c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "esmk_debug_contact_groups": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_int32)]),
+    # edits of the residual stream between layers: the handle's list, and one edit as a single op
+    "esmk_set_stream_edits": (c_int, [c_void_p, POINTER(EsmkStreamEdit), c_int]),
+    "esmk_op_stream_edit": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(EsmkStreamEdit), c_void_p, c_int, c_void_p, c_void_p,
+                                    c_int, c_void_p]),
     # token-packed batch + row selection (mixed-length libraries of masked copies); the segment table is a host array
     "esmk_packed_rows_workspace_bytes": (
         c_int, [c_void_p, POINTER(c_int32), c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),

@@ -466,6 +466,21 @@ void fill_map_offsets(const int32_t* seg, int n_seg, int32_t* dst) {
     }
 }
 
+
+int check_stream_edit(const std::string& w, const esmk_stream_edit& e, int E, int L) {
+    if (L >= 0 && (e.layer < 0 || e.layer > L))
+        return fail(w + ": layer " + std::to_string(e.layer) + " is outside 0 .. " + std::to_string(L) + " (the stream after that many layers)");
+    if (e.op != ESMK_EDIT_AXPBY && e.op != ESMK_EDIT_PROJECT) return fail(w + ": op must be ESMK_EDIT_AXPBY or ESMK_EDIT_PROJECT");
+    if (e.op == ESMK_EDIT_PROJECT && !e.src_dev) return fail(w + ": ESMK_EDIT_PROJECT needs src_dev (the direction)");
+    if (e.rows_dev && e.n_rows < 0) return fail(w + ": n_rows must not be negative");
+    if (e.rows_dev && e.n_rows > ESMK_MAX_ROWS) return fail(w + ": n_rows exceeds 2^24 rows");
+    if (e.src_dev && e.src_ld != 0 && (e.src_ld < E || e.src_ld % 4 != 0))
+        return fail(w + ": src_ld must be 0 (one vector for every row) or a multiple of 4 that is >= embed_dim");
+    if (e.src_dev && e.src_ld != 0 && e.n_src <= 0) return fail(w + ": n_src must be positive when src_ld is a row stride");
+    if (E % 4 != 0 || E > 5120) return fail(w + ": the edit kernel takes embed_dim % 4 == 0, embed_dim <= 5120");
+    return 0;
+}
+
 }  // namespace esmk_host
 
 namespace {
@@ -597,12 +612,20 @@ struct Fwd {
     }
 };
 
+// the token-packed entries while the handle holds stream edits (esmk_set_stream_edits)
+int refuse_edits_packed(const std::string& who, const esmk_model* m) {
+    if (m->edits.empty()) return 0;
+    return fail(who + ": stream edits are set (esmk_set_stream_edits): they run on padded batches only (esmk_forward, "
+                      "esmk_forward_rows, esmk_forward_rows_contacts), a token-packed row space is not the caller's B*T rows");
+}
+
 // everything that needs no HIP call; the workspace plan
 int check_forward(const ForwardCall& c, Workspace* w) {
     const std::string who(c.who);
     const esmk_model* m = c.m;
     if (!m || !c.packed || !c.tokens || !c.workspace) return fail(who + ": null argument");
     if (m->is_msa) return fail(who + ": MSA handle (use esmk_msa_forward)");
+    if (c.pc && refuse_edits_packed(who, m)) return 1;
     if (c.B <= 0 || c.T <= 0) return fail(who + ": B and T must be positive");
     if ((long long)c.B * c.T > ESMK_MAX_ROWS) return fail(who + ": B*T exceeds 2^24 rows");
     if (c.n_repr > 0 && (!c.repr_layers || !c.repr_out)) return fail(who + ": null repr arrays");
@@ -687,7 +710,7 @@ int check_forms(const Fwd& f) {
     return 0;
 }
 
-// esm2.py:82-100: token statistics, embedding (token dropout), positions of ESM-1 / ESM-1b; representation 0
+// esm2.py:82-98: token statistics, embedding (token dropout), positions of ESM-1 / ESM-1b
 int embed_stage(const Fwd& f) {
     const esmk_model* m = f.m;
     const esmk_config& cfg = m->cfg;
@@ -738,7 +761,30 @@ int embed_stage(const Fwd& f) {
             }
         }
     }
-    return f.s.repr_copy(0, f.x, f.repr_lowp);  // esm2.py:99-100
+    return 0;
+}
+
+// The handle's edits of the stream after k layers (esmk_set_stream_edits), in list order: between the stage that wrote the
+// stream and the capture of representation k.  With the fold the rows of layers 1 .. L-1 re-enter the chain here (operand
+// row, mean, rstd by rowstats' arithmetic); for k = 0 the chain's entry pass follows, for k = L nothing reads the chain; the
+// plain and split-weight modes have no chain state: their next LayerNorm pass reads x.
+int stream_edit_stage(const Fwd& f, int k) {
+    if (f.m->edits.empty()) return 0;
+    const bool chain = f.fold && k >= 1 && k <= f.L - 1;
+    for (const esmk_stream_edit& e : f.m->edits) {
+        if (e.layer != k) continue;
+        StreamEditArgs a = stream_edit_args(e, f.x, f.c.tokens, f.N, f.E);
+        if (chain) {
+            a.y = f.act;
+            a.ldy = f.Kp;
+            a.mean = f.ln_mean;
+            a.rstd = f.ln_rstd;
+        }
+        const double rows = e.rows_dev ? (double)e.n_rows : (double)f.N;  // (an upper bound under the token selector)
+        ProfScope ps(f.m, f.s.st, PC_STREAM_EDIT, 3.0 * rows * f.E, rows * f.E * ((e.src_dev ? 12.0 : 8.0) + (chain ? f.s.os : 0)));
+        ESMK_TRY(launch_stream_edit(a, f.s.op, f.s.st));
+    }
+    return 0;
 }
 
 // self_attn_layer_norm and the q / k / v projections with RoPE (modules.py:123-124, multihead_attention.py:256-300)
@@ -992,12 +1038,15 @@ int forward_impl(const ForwardCall& c) {
     if (f.pc && upload_packed_tables(f)) return 1;
     if (check_forms(f)) return 1;
     if (embed_stage(f)) return 1;
+    if (stream_edit_stage(f, 0)) return 1;
+    if (f.s.repr_copy(0, f.x, f.repr_lowp)) return 1;  // esm2.py:99-100
     for (int l = 0; l < f.L; ++l) {  // esm2.py:111-121 -> modules.py:120-142
         const LayerOff& o = f.m->layer[l];
         if (qkv_stage(f, o, l)) return 1;        // self_attn_layer_norm; q, k, v
         if (attention_stage(f, o, l)) return 1;  // softmax(q k^T) v
         if (out_proj_stage(f, o)) return 1;      // x += out_proj(.); final_layer_norm
         if (ffn_stage(f, o, l)) return 1;        // x += fc2(gelu(fc1(.)))
+        if (stream_edit_stage(f, l + 1)) return 1;
         // esm2.py:117-118; ESM-1: layer L too (no final LayerNorm)
         if ((l + 1 < f.L || f.esm1) && f.s.repr_copy(l + 1, f.x, f.repr_lowp)) return 1;
     }
@@ -1294,6 +1343,20 @@ int esmk_pack_weight(esmk_model* m, void* packed_dev, size_t packed_bytes, const
     return 0;  // unknown keys are ignored
 }
 
+int esmk_set_stream_edits(esmk_model* m, const esmk_stream_edit* edits, int n) {
+    if (!m) return fail("esmk_set_stream_edits: null model");
+    if (m->is_msa)
+        return fail("esmk_set_stream_edits: MSA handle (stream edits are built for the ESM-2 / ESM-1b / ESM-1 stack; the esmk_msa_* "
+                    "entries run without them)");
+    if (n < 0 || n > ESMK_MAX_STREAM_EDITS)
+        return fail("esmk_set_stream_edits: n must be 0 (clear) .. " + std::to_string(ESMK_MAX_STREAM_EDITS));
+    if (n > 0 && !edits) return fail("esmk_set_stream_edits: null edit list");
+    for (int i = 0; i < n; ++i)
+        if (check_stream_edit("esmk_set_stream_edits: edit " + std::to_string(i), edits[i], m->E, m->L)) return 1;
+    m->edits.assign(edits, edits + n);  // (a refused list leaves the edits that were set)
+    return 0;
+}
+
 int esmk_workspace_bytes(const esmk_model* m, int B, int T, uint32_t out_flags, size_t* bytes) {
     if (!m || !bytes) return fail("esmk_workspace_bytes: null argument");
     if (m->is_msa) return fail("esmk_workspace_bytes: MSA handle (use esmk_msa_workspace_bytes)");
@@ -1588,6 +1651,7 @@ int esmk_forward_packed_rows(esmk_model* m, const void* packed_dev, const int64_
         return fail("esmk_forward_packed_rows: null argument");
     PackedCtx pc;
     if (check_packed_rows("esmk_forward_packed_rows", m, segments_host, n_seg, rows, n_sel, &pc)) return 1;
+    if (refuse_edits_packed("esmk_forward_packed_rows", m)) return 1;
     RowSel rs;
     if (workspace_bytes < plan_rows(m, 1, rows, n_sel, &rs, n_seg)) return fail("esmk_forward_packed_rows: workspace too small");
     if (!m->cfg.no_rope && m->inv_freq.empty()) return fail("esmk_forward_packed_rows: esmk_set_rope_inv_freq was not called");

@@ -103,6 +103,8 @@ struct esmk_model {
     float* d_ucos = nullptr;  // "unit" rotary tables (cos = 1, sin = 0): the MSA model has no RoPE
     float* d_usin = nullptr;
     int unit_cap = 0;
+    // edits of the residual stream between layers (esmk_set_stream_edits): copied descriptors, borrowed device pointers
+    std::vector<esmk_stream_edit> edits;
 };
 
 // Precision modes with split weights (esmk_config::weight_split): which matrices of a layer are kept as W_hi + W_lo (factor 2:
@@ -130,7 +132,7 @@ static inline int split_factor(const esmk_model* m, int cls, int epi);
 enum {
     PC_EMBED = 0, PC_LAYERNORM, PC_GEMM_QKV, PC_ATTENTION, PC_ATTN_PROBS, PC_GEMM_OUT, PC_GEMM_FC1,
     PC_GEMM_FC2, PC_COPY, PC_LM_DENSE, PC_LM_LOGITS, PC_CONTACTS,
-    PC_MSA_ROW_SCORES, PC_MSA_ROW_SOFTMAX, PC_MSA_ROW_CTX, PC_MSA_COL_ATTN, PC_LN_STATS, PC_COUNT
+    PC_MSA_ROW_SCORES, PC_MSA_ROW_SOFTMAX, PC_MSA_ROW_CTX, PC_MSA_COL_ATTN, PC_LN_STATS, PC_STREAM_EDIT, PC_COUNT
 };
 static const char* const kProfNames[PC_COUNT] = {
     "embed", "layernorm", "gemm_qkv_rope", "attention", "attention_probs", "gemm_out_proj",
@@ -138,7 +140,9 @@ static const char* const kProfNames[PC_COUNT] = {
     "msa_row_scores", "msa_row_softmax", "msa_row_context", "msa_col_attention",
     // LayerNorm fold: the row-statistics entry pass and the per-LayerNorm finalize launches (tiny; the LayerNorm passes
     // themselves are GEMM epilogue work) — "layernorm" keeps the standalone LayerNorm kernel (with the fold: the final one)
-    "ln_fold_stats"};
+    "ln_fold_stats",
+    // edits of the stream between layers (interventions.hip): no record unless edits are set
+    "stream_edit"};
 
 static inline int split_factor(const esmk_model* m, int cls, int epi) {
     const SplitPlan s = split_plan(m);
@@ -181,6 +185,18 @@ inline int head_slots(const esmk_model* m) { return m->D == 128 ? 128 : 64; }
 // esmk_debug_set("rows_contacts_own_groups", 1): esmk_forward_rows_contacts takes the batch's own head-group count instead of
 // the pinned one — the measurement of what the pin costs (tools/design_throughput.py); process wide, off by default
 extern int g_rows_contacts_own_groups;
+// one edit descriptor against a stream of width E and, for the handle's list, a stack of L layers (L < 0: the single op, which
+// has no layer); everything that needs no HIP call (engine.hip)
+int check_stream_edit(const std::string& who, const esmk_stream_edit& e, int E, int L);
+// the launch arguments of a descriptor on the stream x [N, E]; the fold outputs are the caller's to add
+inline esmk::StreamEditArgs stream_edit_args(const esmk_stream_edit& e, float* x, const int64_t* tokens, int N, int E) {
+    esmk::StreamEditArgs a;
+    a.x = x, a.tokens = tokens, a.N = N, a.E = E;
+    a.rows = e.rows_dev, a.n_rows = e.n_rows, a.token_set = e.token_set;
+    a.src = e.src_dev, a.src_ld = e.src_ld, a.n_src = e.n_src, a.src_index = e.src_index_dev;
+    a.keep = e.keep, a.gain = e.gain, a.op = e.op;
+    return a;
+}
 // rotary tables for rows 0 .. T-1 (engine.hip)
 int ensure_rope(esmk_model* m, int T, hipStream_t st);
 // "unit" rotary tables (cos = 1, sin = 0) for models without RoPE (MSA Transformer, ESM-1b)

@@ -217,6 +217,26 @@ int esmk_op_rowstats(const float* x_dev, void* y_dev, float* mean_dev, float* rs
     return 0;
 }
 
+// ---- one edit of the residual stream as a single op (tests/test_stream_edit_ops_gpu.py) --------------------------
+int esmk_op_stream_edit(float* x_dev, const int64_t* tokens_dev, int N, int E, const esmk_stream_edit* edit, void* y_dev, int ldy,
+                        float* mean_dev, float* rstd_dev, int operand_dtype, void* stream) {
+    if (!x_dev || !edit) return fail("esmk_op_stream_edit: null argument");
+    if (N <= 0 || N > ESMK_MAX_ROWS || E <= 0) return fail("esmk_op_stream_edit: need 0 < N <= 2^24 and E > 0");
+    if (check_stream_edit("esmk_op_stream_edit", *edit, E, -1)) return 1;
+    if (!edit->rows_dev && !tokens_dev) return fail("esmk_op_stream_edit: the token selector (rows_dev NULL) needs tokens_dev");
+    if (y_dev && (!mean_dev || !rstd_dev)) return fail("esmk_op_stream_edit: the fold outputs are y_dev, mean_dev and rstd_dev together");
+    if (y_dev && (ldy < E || ldy % 4 != 0)) return fail("esmk_op_stream_edit: ldy must be a multiple of 4 that is >= E");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16)
+        return fail("esmk_op_stream_edit: operand_dtype must be ESMK_F16 or ESMK_BF16");
+    StreamEditArgs a = stream_edit_args(*edit, x_dev, tokens_dev, N, E);
+    a.y = y_dev;
+    a.ldy = ldy;
+    a.mean = mean_dev;
+    a.rstd = rstd_dev;
+    ESMK_TRY(launch_stream_edit(a, operand_dtype, (hipStream_t)stream));
+    return 0;
+}
+
 int esmk_op_ln_finalize(const float* part_dev, float* mean_dev, float* rstd_dev, int rows, int parts, int E, void* stream) {
     if (!part_dev || !mean_dev || !rstd_dev) return fail("esmk_op_ln_finalize: null argument");
     ESMK_TRY(launch_ln_finalize(part_dev, mean_dev, rstd_dev, rows, parts, E, (hipStream_t)stream));

@@ -146,6 +146,26 @@ hipError_t launch_rowstats(const float* x, void* y, float* mean, float* rstd, in
 hipError_t launch_ln_finalize(const float* part, float* mean, float* rstd, int rows, int parts, int E, hipStream_t st);
 hipError_t launch_fold_weight(const void* src, int src_dtype, const float* gamma, const float* beta, void* dst, int dst_dtype,
                               float* bias2, size_t rows, size_t cols, size_t dst_ld, int row_map, int d, hipStream_t st);
+// interventions.hip — one edit of the fp32 residual stream x [N, E] in place (include/esmk.h, esmk_op_stream_edit: the
+// semantics).  rows != null: the listed rows (entries outside [0, N) are skipped), else every row whose token is in
+// token_set.  y != null: the edited rows' fold-chain state (y = T(x' - mean), mean, rstd) by rowstats_kernel's arithmetic.
+struct StreamEditArgs {
+    float* x = nullptr;
+    const int64_t* tokens = nullptr;  // [N]; read under the token selector only
+    const int* rows = nullptr;
+    int n_rows = 0;
+    unsigned long long token_set = 0;
+    const float* src = nullptr;  // row stride src_ld: 0 = one vector for every row, else >= E; n_src rows
+    int src_ld = 0, n_src = 0;
+    const int* src_index = nullptr;  // [n_rows] (token selector: [N]); null: source row i of listed row i / of row r
+    float keep = 1.f, gain = 0.f;
+    int op = 0;  // ESMK_EDIT_AXPBY | ESMK_EDIT_PROJECT
+    void* y = nullptr;
+    int ldy = 0;
+    float *mean = nullptr, *rstd = nullptr;
+    int N = 0, E = 0;
+};
+hipError_t launch_stream_edit(const StreamEditArgs& a, int operand_dtype, hipStream_t st);
 // MSA Transformer variants of the same kernel: output rows scaled by row_keep[row] (padded positions
 // zeroed, msa_transformer.py:171-172) and/or written in (b,c,r) row order for the column-attention block
 struct LnExtra {

@@ -320,6 +320,22 @@ class Esm2Engine(Engine):
         self.stream2 = None
         self.max_T = 0           # longest row a finished forward call has seen (its RoPE table exists and is ordered before us)
         self.dual_calls = 0
+        self.edits = None        # esm_amd.interventions.DeviceEdits the handle holds (esmk_set_stream_edits), or None
+
+    def set_edits(self, edits):
+        """The handle's stream edits become ``edits`` (``esm_amd.interventions.DeviceEdits`` or None); no call when they are."""
+        if edits is self.edits:
+            return
+        N = self.N
+        if self.handle:
+            N.check(N.lib.esmk_set_stream_edits(self.handle, None if edits is None else edits.array, 0 if edits is None else edits.n))
+        self.edits = edits
+
+    def _no_edits(self, what):
+        if self.edits is not None:
+            from .interventions import _NOT_BUILT
+
+            raise ValueError(f"{what} while stream edits are active: {_NOT_BUILT}")
 
     @staticmethod
     def _skip(key):
@@ -346,8 +362,9 @@ class Esm2Engine(Engine):
                 self.handle, N.ptr(self.packed), N.ptr(part(tok)), hi - lo, T, *self._repr_args(repr_set, [part(r) for r in reps]),
                 flags, N.ptr(part(logits)), N.ptr(part(attn)), N.ptr(part(contacts)), N.ptr(ws), ws.numel(), stream))
 
-        if (B >= 2 and logits is not None and _dual_stream_wanted(B * T) and T <= self.max_T and not self.profiling
-                and not torch.cuda.is_current_stream_capturing()):
+        # (an edited call runs on one stream: its row lists count through the whole batch, and the handle's edits are one state)
+        if (B >= 2 and logits is not None and self.edits is None and _dual_stream_wanted(B * T) and T <= self.max_T
+                and not self.profiling and not torch.cuda.is_current_stream_capturing()):
             # two half-batches, the second on the engine's own stream (see _dual_stream_window): same bits
             cur = torch.cuda.current_stream(self.device)
             if self.stream2 is None:
@@ -374,6 +391,7 @@ class Esm2Engine(Engine):
         ``esmk_forward_packed_maps`` when the ragged attention maps ``flat_at`` are asked for, ``esmk_forward_packed_ex`` for
         the ragged contact maps ``flat_ct`` alone, ``esmk_forward_packed`` otherwise."""
         N = self.N
+        self._no_edits("a token-packed forward")
         n_seg = seg.shape[0]
         seg_ptr = ctypes.cast(seg.data_ptr(), ctypes.POINTER(ctypes.c_int32))
         head = (self.handle, N.ptr(self.packed), N.ptr(flat), seg_ptr, n_seg, rows) + self._repr_args(repr_set, reps) + (
@@ -397,6 +415,7 @@ class Esm2Engine(Engine):
             got = self._rows(lib.esmk_rows_workspace_bytes, lib.esmk_forward_rows, (B, T), tok, sel_rows, V, return_logits)
             self.max_T = max(self.max_T, T)  # (not for a packed row space: its length is no row length)
             return got
+        self._no_edits("a token-packed forward")
         seg_ptr = ctypes.cast(seg.data_ptr(), ctypes.POINTER(ctypes.c_int32))
         return self._rows(lib.esmk_packed_rows_workspace_bytes, lib.esmk_forward_packed_rows, (seg_ptr, seg.shape[0], tok.numel()),
                           tok, sel_rows, V, return_logits)
@@ -539,4 +558,5 @@ class _EngineHost:
     def __getstate__(self):
         state = self.__dict__.copy()
         state["_engine"] = None  # the native handle is rebuilt lazily
+        state.pop("_stream_edits", None)  # (active edits hold device pointers of this process)
         return state

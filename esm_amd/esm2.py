@@ -25,7 +25,8 @@ class _Container(nn.Module):
     def forward(self, *a, **k):  # pragma: no cover
         raise RuntimeError(
             f"{type(self).__name__} is a parameter container of the MI355X engine; "
-            "the layer math runs inside ESM2.forward (libesmk.so), not per sub-module"
+            "the layer math runs inside ESM2.forward (libesmk.so), not per sub-module; what a forward hook would change "
+            "between layers is stated as esm_amd.StreamEdit (model.forward_edited, model.stream_edits)"
         )
 
 
@@ -156,6 +157,7 @@ class ESM2(_EngineHost, nn.Module):
         new = self._get_engine(device, _EngineHost._engine_key(self) + (self._fold_setting(known),))
         new.sync_weights(self, fp if new is eng else None)
         object.__setattr__(self, "_fold_fp", new.fingerprint if _ln_fold() == 0 else None)
+        new.set_edits(self.__dict__.get("_stream_edits"))  # (esm_amd/interventions.py; nothing to do unless they changed)
         return new
 
     def _fold_setting(self, gains_known=False):
@@ -248,6 +250,33 @@ class ESM2(_EngineHost, nn.Module):
         return result
 
     # ------------------------------------------------------------------------------------------
+    # writing into the stream between layers (esm_amd/interventions.py): patching, steering, ablation
+    def forward_edited(self, tokens, edits, repr_layers=[], need_head_weights=False, return_contacts=False, contacts_only=False):
+        """``esm_amd.interventions.forward_edited``: ``forward``'s dict of one forward with the ``StreamEdit`` list ``edits``
+        applied to the residual stream between layers; ``repr_layers`` shows the edited stream."""
+        from . import interventions
+
+        return interventions.forward_edited(self, tokens, edits, repr_layers=repr_layers, need_head_weights=need_head_weights,
+                                            return_contacts=return_contacts, contacts_only=contacts_only)
+
+    def stream_edits(self, edits):
+        """``with model.stream_edits(edits):`` every padded-path engine call inside (``forward``, the scoring, sampling, design
+        and Jacobian methods) runs with the token-set ``StreamEdit`` list ``edits`` applied."""
+        from . import interventions
+
+        return interventions.stream_edits(self, edits)
+
+    def _refuse_under_edits(self, what=None, varlen=False, window=None):
+        """Token-packed batches and windows are not built for edited runs: a ValueError that names the limit."""
+        if self.__dict__.get("_stream_edits") is None:
+            return
+        what = what or ("varlen=True" if varlen else "window=" if window is not None else None)
+        if what is not None:
+            from .interventions import _NOT_BUILT
+
+            raise ValueError(f"{what} inside model.stream_edits(...): {_NOT_BUILT}")
+
+    # ------------------------------------------------------------------------------------------
     # token-packed batches: no compute on padding (include/esmk.h, esmk_forward_packed)
     supports_varlen = True  # ESM-2 (all sizes) and ESM-1b / ESM-1v; the MSA Transformer has no such path
     supports_contacts_only = True  # forward(contacts_only=True): contact maps without the attention tensor
@@ -285,6 +314,7 @@ class ESM2(_EngineHost, nn.Module):
         The scoring methods follow the same rule (``esm_amd.scoring``): with ``varlen=True`` on an ESM-1 model or in the
         f16x3 mode, which have no token-packed form, the padded path runs."""
         assert tokens.ndim == 2
+        self._refuse_under_edits("forward_varlen")
         from . import _native as N
         from .packing import dense_from_views, pack_plan, ragged_views
 
@@ -366,6 +396,7 @@ class ESM2(_EngineHost, nn.Module):
     def masked_marginals(self, tokens, positions=None, chunk=None, varlen=False, chunk_rows=None, window=None, wrap=True):
         """``esm_amd.scoring.masked_marginals``: [B, T, V] fp32 log-probabilities, row (b, i) from the forward with token
         (b, i) alone masked."""
+        self._refuse_under_edits(varlen=varlen, window=window)
         from . import scoring
 
         return scoring.masked_marginals(self, tokens, positions=positions, chunk=chunk, **_varlen_kw(varlen, chunk_rows),
@@ -373,12 +404,14 @@ class ESM2(_EngineHost, nn.Module):
 
     def wt_marginals(self, tokens, varlen=False, chunk_rows=None, window=None, wrap=True):
         """``esm_amd.scoring.wt_marginals``: [B, T, V] fp32 log-probabilities of the unmasked forward, non-pad rows."""
+        self._refuse_under_edits(varlen=varlen, window=window)
         from . import scoring
 
         return scoring.wt_marginals(self, tokens, **_varlen_kw(varlen, chunk_rows), **_window_kw(window, wrap))
 
     def pseudo_log_likelihood(self, tokens, positions=None, chunk=None, varlen=False, chunk_rows=None, window=None, wrap=True):
         """``esm_amd.scoring.pseudo_log_likelihood``: [B] fp64, sum of the masked-marginal log-probability of the true token."""
+        self._refuse_under_edits(varlen=varlen, window=window)
         from . import scoring
 
         return scoring.pseudo_log_likelihood(self, tokens, positions=positions, chunk=chunk, **_varlen_kw(varlen, chunk_rows),
@@ -388,6 +421,7 @@ class ESM2(_EngineHost, nn.Module):
                      window=None, wrap=True):
         """``esm_amd.scoring.masked_joint``: one forward per position set with ALL its positions masked; (offsets, pos,
         logprobs [n_rows, V]) of the masked rows."""
+        self._refuse_under_edits(varlen=varlen, window=window)
         from . import scoring
 
         return scoring.masked_joint(self, tokens, position_sets, src=src, chunk=chunk, return_logits=return_logits,
@@ -396,6 +430,7 @@ class ESM2(_EngineHost, nn.Module):
     def score_variants(self, alphabet, sequence, variants, strategy="masked-marginals", offset_idx=0, sep=":", chunk=None,
                        window=None, wrap=True):
         """``esm_amd.scoring.score_variants``: floats, one per variant of one or more substitutions ('A42G:K50R')."""
+        self._refuse_under_edits(window=window)
         from . import scoring
 
         return scoring.score_variants(self, alphabet, sequence, variants, strategy=strategy, offset_idx=offset_idx, sep=sep,
@@ -405,6 +440,7 @@ class ESM2(_EngineHost, nn.Module):
                         chunk=None):
         """``esm_amd.windows.forward_windows``: ``forward``'s dict in source coordinates for sequences longer than the model's
         window — overlapping windows through ``forward``, logits / representations / contact maps stitched on the device."""
+        self._refuse_under_edits("forward_windows")
         from . import windows
 
         return windows.forward_windows(self, tokens, repr_layers=repr_layers, window=window, stride=stride, wrap=wrap,

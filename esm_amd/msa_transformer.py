@@ -203,6 +203,13 @@ class MSATransformer(_EngineHost, nn.Module):
     design = design_energy = masked_joint  # esm_amd.design runs chains of single sequences only
     forward_windows = masked_joint  # esm_amd.windows cuts single sequences into windows only
 
+    def stream_edits(self, *args, **kwargs):
+        from . import interventions
+
+        interventions.plan_edits(self, [])  # NotImplementedError: the axial stack has no edit point
+
+    forward_edited = stream_edits
+
     # Variant scoring of one MSA (esm_amd/msa_scoring.py over esmk_msa_forward_rows): an MSA plus a query row is another
     # argument shape than a batch of sequences, hence names of their own; the single-sequence names above keep refusing
     def msa_forward_rows(self, tokens, sel_rows, return_logits=False):

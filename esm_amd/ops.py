@@ -1238,3 +1238,47 @@ def gather_rows(x, sel, out=None):
     out = _out(out, (n, E), torch.float32, x.device)
     N.check(N.lib.esmk_op_gather_rows(N.ptr(x), N.ptr(sel), N.ptr(out), Nr, E, n, N.cur_stream()))
     return out
+
+
+def stream_edit_desc(layer, op, keep, gain, rows=None, token_set=0, src=None, src_ld=None, src_index=None, n_rows=None):
+    """The ``esmk_stream_edit`` descriptor of one edit (include/esmk.h) over device tensors, which the caller keeps alive:
+    ``rows`` int32 [n] or None (then ``token_set``, bit v = token v); ``src`` fp32 [E] (``src_ld`` 0) or [n_src, ld] (``src_ld``
+    its row stride unless given); ``src_index`` int32 or None.  ``n_rows``: the length of the list when it is not the tensor's
+    (an EMPTY list is a tensor of one element with ``n_rows`` 0: an empty tensor has no address, and a null ``rows_dev``
+    means the token selector)."""
+    _req_cuda(rows, src, src_index)
+    assert rows is None or (rows.dtype == torch.int32 and rows.numel() > 0)
+    assert src is None or src.dtype == torch.float32
+    assert src_index is None or src_index.dtype == torch.int32
+    if src is None:
+        ld, n_src = 0, 0
+    elif src.dim() == 1:
+        ld, n_src = 0, 1
+    else:
+        ld, n_src = src.stride(0), src.shape[0]
+    if n_rows is None:
+        n_rows = 0 if rows is None else rows.numel()
+    return N.EsmkStreamEdit(int(layer), int(op), float(keep), float(gain), N.ptr(rows), int(n_rows), int(token_set), N.ptr(src), ld if src_ld is None else int(src_ld), n_src, N.ptr(src_index))
+
+
+def stream_edit(x, op, keep=1.0, gain=1.0, rows=None, tokens=None, token_set=0, src=None, src_ld=None, src_index=None, y=None,
+                mean=None, rstd=None):
+    """One edit of the residual stream as a single launch (``esmk_op_stream_edit``): x fp32 [N, E] IN PLACE.  ``rows`` int32 [n]
+    lists the edited rows, or (None) every row whose token (``tokens`` int64 [N]) is in ``token_set``.  op ``N.EDIT_AXPBY``:
+    x' = keep x + gain s (no src: keep x); ``N.EDIT_PROJECT``: x' = x - gain <x, s> / <s, s> s.  With ``y`` (operand dtype
+    [>= N, ldy], its row stride taken from the tensor), ``mean`` and ``rstd`` fp32 [N] the edited rows' LayerNorm-fold state
+    is written as ``esmk_op_rowstats`` would from x'."""
+    _req_cuda(x, tokens, y, mean, rstd)
+    assert x.dtype == torch.float32 and x.dim() == 2
+    assert tokens is None or (tokens.dtype == torch.int64 and tokens.numel() == x.shape[0])
+    assert y is None or (y.dtype in (torch.float16, torch.bfloat16) and y.dim() == 2 and y.shape[0] >= x.shape[0])
+    n_rows = None
+    if rows is not None and rows.numel() == 0:
+        rows, n_rows = torch.zeros(1, dtype=torch.int32, device=x.device), 0
+    if src_index is not None and src_index.numel() == 0:
+        src_index = None
+    desc = stream_edit_desc(0, op, keep, gain, rows, token_set, src, src_ld, src_index, n_rows)
+    code = N.F16 if y is None else N.dtype_code(y.dtype)
+    N.check(N.lib.esmk_op_stream_edit(N.ptr(x), N.ptr(tokens), x.shape[0], x.shape[1], ctypes.byref(desc), N.ptr(y),
+                                      0 if y is None else y.stride(0), N.ptr(mean), N.ptr(rstd), code, N.cur_stream()))
+    return x

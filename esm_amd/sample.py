@@ -11,11 +11,16 @@ inpaint  ``_`` or ``<mask>`` in the input marks the positions to fill; everythin
 
 ``--top-k`` / ``--top-p`` put a top-k / nucleus filter in front of every draw, in either mode.
 
+``--steer VEC.npy --steer-layer K [--steer-gain A]`` draws from the STEERED model: A times the fp32 [embed_dim] direction in
+VEC.npy is added to every residue's stream after K layers in every forward of the run (``model.stream_edits``;
+``esm_amd.mean_difference`` makes such a direction).  Without them the run is the unsteered one, call for call.
+
 Every input record is run as ``--num-chains`` chains.  Chain ids count through the output (record r, copy c: r * num_chains +
 c), and a draw depends on (seed, chain id) alone, so one record of the output can be drawn again by itself.  The output is a
 FASTA file; a record is named ``<label>|chain=<id>|seed=<seed>``.
 """
 import argparse
+import contextlib
 import pathlib
 import sys
 
@@ -41,6 +46,9 @@ def create_parser():
                    help="inpaint only: a random order, or the most confident positions first (max log q / negative entropy)")
     p.add_argument("--num-chains", type=int, default=1, help="chains per input sequence")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--steer", type=pathlib.Path, default=None, help=".npy file of an [embed_dim] direction added to every residue's stream")
+    p.add_argument("--steer-layer", type=int, default=None, help="the stream after this many layers takes the direction (0 .. L)")
+    p.add_argument("--steer-gain", type=float, default=1.0, help="multiple of the direction that is added")
     p.add_argument("--output", type=pathlib.Path, required=True, help="FASTA file to write")
     return p
 
@@ -62,6 +70,10 @@ def parse_args(argv=None):
         parser.error("--top-k must lie in 0 .. 64 (0: no top-k filter)")
     if not 0.0 < args.top_p <= 1.0:
         parser.error("--top-p must lie in (0, 1] (1: no nucleus filter)")
+    if (args.steer is None) != (args.steer_layer is None):
+        parser.error("--steer and --steer-layer go together")
+    if args.steer is None and args.steer_gain != 1.0:
+        parser.error("--steer-gain needs --steer")
     if args.order != "random" and args.mode != "inpaint":
         parser.error("--order applies to --mode inpaint only: a Gibbs sweep has no masked positions to rank")
     return args
@@ -101,8 +113,26 @@ def decode(alphabet, row):
     return "".join(alphabet.get_tok(int(t)) for t in row if int(t) not in skip)
 
 
+def steering(model, args):
+    """The context the draws run in: ``model.stream_edits`` with the ``--steer`` direction, or nothing at all."""
+    if getattr(args, "steer", None) is None:
+        return contextlib.nullcontext()
+    import numpy as np
+    import torch
+
+    from .interventions import StreamEdit
+
+    vec = torch.from_numpy(np.load(args.steer).astype(np.float32).reshape(-1))
+    return model.stream_edits([StreamEdit(args.steer_layer, "add", vec, gain=args.steer_gain, positions="residues")])
+
+
 def sample_records(model, alphabet, chains, args):
     """The final sequence of every chain, ``PER_CALL`` chains per call."""
+    with steering(model, args):
+        return _sample_records(model, alphabet, chains, args)
+
+
+def _sample_records(model, alphabet, chains, args):
     convert = alphabet.get_batch_converter()
     out = []
     for lo in range(0, len(chains), PER_CALL):

@@ -259,6 +259,49 @@ int esmk_forward_rows_contacts(esmk_model* m, const void* packed_dev, const int6
  * 1 = esmk_forward_rows_contacts (the count of B = 1, whatever B is). */
 int esmk_debug_contact_groups(const esmk_model* m, int B, int T, int pinned, int32_t* groups);
 
+/* Edits of the residual stream between layers: activation patching, steering, ablation — what a forward hook on
+ * model.layers[k] that returns a changed output does to the reference.  The edits are state of the handle: while set, every
+ * esmk_forward, esmk_forward_rows and esmk_forward_rows_contacts applies the edits of layer k, in list order, to the fp32
+ * stream after k layers (k = 0: after the embedding, with the positions and emb_layer_norm_before of ESM-1b) and BEFORE
+ * representation k is captured — repr_layers shows the edited stream — so every later layer and the head see it.  k = L
+ * edits the stream in front of the final LayerNorm (ESM-1: the stream the output projection reads).  With the LayerNorm fold
+ * an edited row of a layer 1 .. L-1 re-enters the fold's chain (operand row, mean, rstd) by esmk_op_rowstats' arithmetic.
+ *   op ESMK_EDIT_AXPBY    x' = keep * x + gain * s, each product and the sum rounded to fp32 on its own (no fused
+ *                         multiply-add); src_dev NULL: x' = keep * x.  set (0, 1), add (1, a), scale (a, no src), zero (0, no src)
+ *   op ESMK_EDIT_PROJECT  c = gain <x, s> / <s, s>, both dot products accumulated in fp64, c rounded once to fp32;
+ *                         x' = x - c * s (product and difference rounded on their own); <s, s> = 0: the row stays as it is
+ *   rows_dev  int32 [n_rows], indices b*T + t into the call's B*T rows; indices outside are skipped; an index listed
+ *             twice is the caller's error.  NULL: every row whose token is in token_set (bit v = token v; vocab <= 64)
+ *   src_dev   fp32, n_src rows of stride src_ld: 0 (one vector for every row) or >= E, a multiple of 4; 16-byte aligned rows
+ *   src_index_dev  int32, the source row of listed row i (of row r under the token selector); NULL: i (r).  A row whose
+ *             source index is outside [0, n_src) is left as it is
+ * The descriptors are copied; the device pointers are borrowed until the edits are cleared (n = 0) or replaced.  At most
+ * ESMK_MAX_STREAM_EDITS.  Refused before any HIP call: an MSA handle, a layer outside [0, L], an unknown op, PROJECT
+ * without src_dev, a bad src_ld, n_rows < 0, E > 5120; and, while edits are set, the token-packed entries
+ * (esmk_forward_packed*, whose row space is not the caller's B*T rows).  With no edits set no launch, no workspace byte and
+ * no output bit differs from a handle that never had any. */
+enum { ESMK_EDIT_AXPBY = 0, ESMK_EDIT_PROJECT = 1 };
+#define ESMK_MAX_STREAM_EDITS 64
+typedef struct esmk_stream_edit {
+    int32_t layer; /* 0..L: the stream after `layer` layers; 0 = the embedded stream */
+    int32_t op;    /* ESMK_EDIT_AXPBY | ESMK_EDIT_PROJECT */
+    float keep, gain;
+    const int32_t* rows_dev; /* or NULL + token_set */
+    int32_t n_rows;
+    uint64_t token_set;
+    const float* src_dev;
+    int32_t src_ld;
+    int32_t n_src;
+    const int32_t* src_index_dev;
+} esmk_stream_edit;
+int esmk_set_stream_edits(esmk_model* m, const esmk_stream_edit* edits, int n);
+/* One edit as a single op on x fp32 [N,E] in place (tokens_dev int64 [N], read under the token selector only), with the fold
+ * outputs when y_dev is given: y[row][c] = T(x' - mean) (operand dtype, row stride ldy >= E; columns [E, ldy) are not
+ * written), mean[row], rstd[row] — the bits esmk_op_rowstats gives on x'.  Rows that are not selected are neither read nor
+ * written in any buffer.  E % 4 == 0, E <= 5120. */
+int esmk_op_stream_edit(float* x_dev, const int64_t* tokens_dev, int N, int E, const esmk_stream_edit* edit, void* y_dev, int ldy,
+                        float* mean_dev, float* rstd_dev, int operand_dtype, void* stream);
+
 /* The same for a token-packed batch: the masked copies of a library of sequences of DIFFERENT lengths (pseudo-log-likelihood
  * of designed sequences, insertion / deletion variants, wt-marginals over a FASTA file) laid back to back in one row space,
  * so that the layer stack does no work on padding.  It is the reference's loop (predict.py:138-143,205-215: one B = 1 forward
