@@ -20,16 +20,21 @@ from .sampling import gibbs_sample, inpaint  # noqa: F401
 from .jacobian import categorical_jacobian, jacobian_contacts  # noqa: F401
 from .windows import forward_windows  # noqa: F401
 from .interventions import StreamEdit, forward_edited, mean_difference, stream_edits  # noqa: F401
+from .pair_head import PairHead, distogram_bins, distogram_from_pdb  # noqa: F401
 
 
 def __getattr__(name):
     # esm_amd.design is the design module, which is callable as its own main function (``esm_amd.design(model, tokens, ...)``
     # is ``esm_amd.design.design``); loaded on first use, so that ``python -m esm_amd.design`` runs a module not yet imported
-    if name in ("design", "design_energy", "contacts_from_pdb"):
+    if name in ("design", "design_energy", "contacts_from_pdb", "DistogramTarget"):
         import importlib
 
         module = importlib.import_module(".design", __name__)
         return module if name == "design" else getattr(module, name)
+    if name == "pair_logits":  # likewise a module that is its own main function (``python -m esm_amd.pair_logits``)
+        import importlib
+
+        return importlib.import_module(".pair_logits", __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -111,6 +111,18 @@ SIGNATURES = {
     "esmk_forward_rows_contacts": (
         c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "esmk_debug_contact_groups": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_int32)]),
+    # linear pairwise heads on the attention maps: the handle's head (host arrays), the row-selected forward with its output,
+    # the kernels on stacked operands, the distogram cross-entropy
+    "esmk_set_pair_head": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),
+    "esmk_rows_pair_workspace_bytes": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
+    "esmk_forward_rows_pair": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "esmk_op_pair_head_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "esmk_op_pair_head": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "esmk_op_distogram_energy": (
+        c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
     # edits of the residual stream between layers: the handle's list, and one edit as a single op
     "esmk_set_stream_edits": (c_int, [c_void_p, POINTER(EsmkStreamEdit), c_int]),
     "esmk_op_stream_edit": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(EsmkStreamEdit), c_void_p, c_int, c_void_p, c_void_p,

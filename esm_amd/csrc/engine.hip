@@ -216,6 +216,25 @@ size_t plan_rows(const esmk_model* m, int B, int T, int n_sel, RowSel* rs, int p
     return c.off;
 }
 
+// esmk_forward_rows_pair: behind plan_rows' layout, every layer's q, k [L][B,H,T,slots] (operand dtype) and row log-sum-exp
+// [L][B,H,T]: the stacked operands of launch_pair_head.  A layer's q / k / lse outputs point at its slot.
+struct PairStash {
+    size_t q = 0, k = 0, lse = 0;      // byte offsets into the workspace
+    size_t qk_layer = 0, lse_layer = 0;  // bytes per layer
+    float* out = nullptr;              // fp32 [B,S,S,n_sym + n_asym]
+};
+size_t plan_rows_pair(const esmk_model* m, int B, int T, int n_sel, RowSel* rs, PairStash* ps) {
+    Carve c;
+    c.take(plan_rows(m, B, T, n_sel, rs));
+    const size_t N = (size_t)B * T;
+    ps->qk_layer = N * m->EA * op_size(m->cfg.operand_dtype);
+    ps->lse_layer = (size_t)B * m->H * T * 4;
+    ps->q = c.take(ps->qk_layer * m->L);
+    ps->k = c.take(ps->qk_layer * m->L);
+    ps->lse = c.take(ps->lse_layer * m->L);
+    return c.off;
+}
+
 // ESM-1: the sinusoidal position table for rows 0 .. T-1 (SinusoidalPositionalEmbedding.get_embedding, modules.py:283-295).
 // The half frequencies exp(j * -(ln 10000 / (half - 1))) are fp32 values of an fp32 argument, as the reference computes them
 // (correctly rounded here); angles, sin and cos on the device (sinus_table_kernel).
@@ -517,6 +536,7 @@ struct ForwardCall {
     const PackedCtx* pc = nullptr;  // token-packed batch: B = 1, T = rows
     const RowSel* rs = nullptr;     // esmk_forward_rows, esmk_forward_packed_rows, esmk_forward_rows_contacts
     int ct_G = 0;                   // esmk_forward_rows_contacts: the pinned head-group count of the fused contact head (0: from B)
+    const PairStash* ps = nullptr;  // esmk_forward_rows_pair: the q / k / lse stash behind the workspace and the head's output
 };
 
 // What the stages share: the call, the launch helpers, the workspace and the form the model runs in
@@ -1030,6 +1050,21 @@ int contacts_final(const Fwd& f) {
     return 0;
 }
 
+// the handle's pairwise head (esmk_set_pair_head) on the stashed q / k / lse of every layer: all L*H channels in one launch
+int pair_head_final(const Fwd& f) {
+    const esmk_model* m = f.m;
+    const esmk_config& cfg = m->cfg;
+    const PairStash& ps = *f.c.ps;
+    const int C_out = m->pair_sym + m->pair_asym;
+    const double pairs = (double)f.B * f.S_ct * f.S_ct;
+    ProfScope scope(f.m, f.s.st, PC_CONTACTS, 2.0 * pairs * f.L * f.H * C_out,
+                    2.0 * f.L * (double)ps.qk_layer + 3.0 * 4 * pairs * C_out);
+    ESMK_TRY(launch_pair_head(f.ws + ps.q, f.ws + ps.k, (const float*)(f.ws + ps.lse), f.key_bias, f.c.tokens, m->d_pair_w64,
+                              m->d_pair_bias, ps.out, f.L, f.B, f.H, f.T, head_slots(m), m->pair_sym, m->pair_asym, cfg.pad_idx,
+                              cfg.prepend_bos, cfg.append_eos, f.s.op, f.s.st));
+    return 0;
+}
+
 int forward_impl(const ForwardCall& c) {
     Workspace w;
     if (check_forward(c, &w)) return 1;
@@ -1042,6 +1077,11 @@ int forward_impl(const ForwardCall& c) {
     if (f.s.repr_copy(0, f.x, f.repr_lowp)) return 1;  // esm2.py:99-100
     for (int l = 0; l < f.L; ++l) {  // esm2.py:111-121 -> modules.py:120-142
         const LayerOff& o = f.m->layer[l];
+        if (c.ps) {  // the layer's q, k and lse stay: slot l of the stash (pair_head.hip reads all of them after the last layer)
+            f.q = f.ws + c.ps->q + (size_t)l * c.ps->qk_layer;
+            f.k = f.ws + c.ps->k + (size_t)l * c.ps->qk_layer;
+            f.lse = (float*)(f.ws + c.ps->lse + (size_t)l * c.ps->lse_layer);
+        }
         if (qkv_stage(f, o, l)) return 1;        // self_attn_layer_norm; q, k, v
         if (attention_stage(f, o, l)) return 1;  // softmax(q k^T) v
         if (out_proj_stage(f, o)) return 1;      // x += out_proj(.); final_layer_norm
@@ -1051,6 +1091,7 @@ int forward_impl(const ForwardCall& c) {
         if ((l + 1 < f.L || f.esm1) && f.s.repr_copy(l + 1, f.x, f.repr_lowp)) return 1;
     }
     if (head_stage(f)) return 1;
+    if (c.ps) return pair_head_final(f);
     return contacts_final(f);
 }
 
@@ -1138,6 +1179,8 @@ void esmk_destroy(esmk_model* m) {
     if (m->d_usin) (void)hipFree(m->d_usin);
     if (m->d_sinus) (void)hipFree(m->d_sinus);
     if (m->pk_host) (void)hipHostFree(m->pk_host);
+    if (m->d_pair_w64) (void)hipFree(m->d_pair_w64);
+    if (m->d_pair_bias) (void)hipFree(m->d_pair_bias);
     if (m->pk_event) (void)hipEventDestroy(m->pk_event);
     delete m;
 }
@@ -1474,6 +1517,83 @@ int esmk_forward_rows_contacts(esmk_model* m, const void* packed_dev, const int6
     c.workspace = workspace_dev, c.workspace_bytes = workspace_bytes, c.stream = stream;
     c.rs = &rs;
     c.ct_G = G;
+    return forward_impl(c);
+}
+
+// ---- linear pairwise heads on the attention maps (pair_head.hip) -------------------------------------------------
+int esmk_set_pair_head(esmk_model* m, const float* w_host, const float* bias_host, int n_sym, int n_asym) {
+    if (!m) return fail("esmk_set_pair_head: null model");
+    if (m->is_msa)
+        return fail("esmk_set_pair_head: MSA handle (the pairwise head is built for the ESM-2 / ESM-1b / ESM-1 stack; the MSA "
+                    "Transformer's row attention maps have no such path)");
+    if (n_sym < 0 || n_asym < 0) return fail("esmk_set_pair_head: n_sym and n_asym must not be negative");
+    if (n_sym + n_asym > 64) return fail("esmk_set_pair_head: n_sym + n_asym must be 0 (clear) .. 64");
+    const int C_out = n_sym + n_asym;
+    if (C_out > 0 && (!w_host || !bias_host)) return fail("esmk_set_pair_head: null weight or bias");
+    if (C_out == 0) {
+        m->pair_sym = m->pair_asym = 0;  // (the device copies stay for the next head)
+        return 0;
+    }
+    const size_t C = (size_t)m->L * m->H;
+    std::vector<float> w64(C * 64, 0.f);
+    for (size_t c = 0; c < C; ++c) memcpy(&w64[c * 64], w_host + c * C_out, (size_t)C_out * 4);
+    // (a forward in flight on another stream may still read the old copies)
+    ESMK_TRY(hipDeviceSynchronize());
+    if (!m->d_pair_w64) ESMK_TRY(hipMalloc(&m->d_pair_w64, C * 64 * 4));
+    if (!m->d_pair_bias) ESMK_TRY(hipMalloc(&m->d_pair_bias, 64 * 4));
+    ESMK_TRY(hipMemcpy(m->d_pair_w64, w64.data(), C * 64 * 4, hipMemcpyHostToDevice));
+    ESMK_TRY(hipMemcpy(m->d_pair_bias, bias_host, (size_t)C_out * 4, hipMemcpyHostToDevice));
+    m->pair_sym = n_sym;
+    m->pair_asym = n_asym;
+    return 0;
+}
+
+static int check_rows_pair(const char* who, const esmk_model* m, int B, int T, int n_sel) {
+    const std::string w(who);
+    if (m->is_msa) return fail(w + ": MSA handle (the MSA Transformer has no pairwise head on its attention maps)");
+    if (m->pair_sym + m->pair_asym <= 0) return fail(w + ": no pairwise head is set (esmk_set_pair_head)");
+    if (B <= 0 || T <= 0) return fail(w + ": B and T must be positive");
+    if ((long long)B * T > ESMK_MAX_ROWS) return fail(w + ": B*T exceeds 2^24 rows");
+    if (n_sel < 0) return fail(w + ": n_sel must not be negative");
+    if (n_sel > ESMK_MAX_ROWS) return fail(w + ": n_sel exceeds 2^24 rows");
+    if (n_sel > 0 && m->V > 64) return fail(w + ": vocabulary above 64 entries (the log-softmax holds one entry per lane)");
+    if (T - (m->cfg.prepend_bos ? 1 : 0) - (m->cfg.append_eos ? 1 : 0) <= 0)
+        return fail(w + ": no residue between <cls> and <eos>: the pair map is empty");
+    return 0;
+}
+
+int esmk_rows_pair_workspace_bytes(const esmk_model* m, int B, int T, int n_sel, size_t* bytes, size_t* logits_offset) {
+    if (!m || !bytes) return fail("esmk_rows_pair_workspace_bytes: null argument");
+    if (check_rows_pair("esmk_rows_pair_workspace_bytes", m, B, T, n_sel)) return 1;
+    RowSel rs;
+    PairStash ps;
+    *bytes = plan_rows_pair(m, B, T, n_sel, &rs, &ps);
+    if (logits_offset) *logits_offset = rs.logits;
+    return 0;
+}
+
+int esmk_forward_rows_pair(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev, int B, int T,
+                           const int32_t* sel_rows_dev, int n_sel, float* logprobs_out_dev, float* pair_out_dev,
+                           void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!m || !packed_dev || !tokens_dev || !pair_out_dev || !workspace_dev || (n_sel > 0 && (!sel_rows_dev || !logprobs_out_dev)))
+        return fail("esmk_forward_rows_pair: null argument");
+    if (check_rows_pair("esmk_forward_rows_pair", m, B, T, n_sel)) return 1;
+    RowSel rs;
+    PairStash ps;
+    if (workspace_bytes < plan_rows_pair(m, B, T, n_sel, &rs, &ps)) return fail("esmk_forward_rows_pair: workspace too small");
+    if (!m->cfg.no_rope && m->inv_freq.empty()) return fail("esmk_forward_rows_pair: esmk_set_rope_inv_freq was not called");
+    rs.sel_dev = sel_rows_dev;
+    rs.n_sel = n_sel;
+    rs.logprobs_out = logprobs_out_dev;
+    ps.out = pair_out_dev;
+    ForwardCall c;
+    c.who = "esmk_forward_rows_pair";
+    c.m = m, c.packed = packed_dev, c.tokens = tokens_dev, c.B = B, c.T = T;
+    c.flags = n_sel > 0 ? ESMK_OUT_LOGITS : 0;
+    c.logits = n_sel > 0 ? (char*)workspace_dev + rs.logits : nullptr;
+    c.workspace = workspace_dev, c.workspace_bytes = workspace_bytes, c.stream = stream;
+    c.rs = &rs;
+    c.ps = &ps;
     return forward_impl(c);
 }
 

@@ -105,6 +105,11 @@ struct esmk_model {
     int unit_cap = 0;
     // edits of the residual stream between layers (esmk_set_stream_edits): copied descriptors, borrowed device pointers
     std::vector<esmk_stream_edit> edits;
+    // linear pairwise head on the attention maps (esmk_set_pair_head): device copies, w64 [L*H][64] (columns past the head's
+    // outputs zero), bias [n_sym + n_asym]; both counts 0: no head
+    float* d_pair_w64 = nullptr;
+    float* d_pair_bias = nullptr;
+    int pair_sym = 0, pair_asym = 0;
 };
 
 // Precision modes with split weights (esmk_config::weight_split): which matrices of a layer are kept as W_hi + W_lo (factor 2:

@@ -1065,6 +1065,63 @@ int esmk_op_contact_energy(const float* contacts_dev, const uint8_t* target_dev,
     return 0;
 }
 
+// ---- linear pairwise heads on the attention maps (pair_head.hip) ---------------------------------------------------
+static int pair_head_op_check(const std::string& w, int B, int H, int T, int L, int head_dim, int n_sym, int n_asym,
+                              int prepend_bos, int append_eos) {
+    if (B <= 0 || H <= 0 || T <= 0 || L <= 0) return fail(w + ": B, H, T and num_layers must be positive");
+    if (head_dim != 64 && head_dim != 128) return fail(w + ": head_dim must be 64 or 128");
+    if ((prepend_bos != 0 && prepend_bos != 1) || (append_eos != 0 && append_eos != 1))
+        return fail(w + ": prepend_bos and append_eos must be 0 or 1");
+    if ((long long)B * T > ESMK_MAX_ROWS) return fail(w + ": B*T exceeds 2^24 rows");
+    if ((long long)L * H > (1 << 20)) return fail(w + ": num_layers * H is too large");
+    if (n_sym < 0 || n_asym < 0 || n_sym + n_asym <= 0 || n_sym + n_asym > 64)
+        return fail(w + ": n_sym and n_asym must not be negative, n_sym + n_asym must be 1 .. 64");
+    if (T - prepend_bos - append_eos <= 0) return fail(w + ": no pair map: T - prepend_bos - append_eos <= 0");
+    return 0;
+}
+
+int esmk_op_pair_head_workspace_bytes(int H, int num_layers, size_t* bytes) {
+    if (!bytes) return fail("esmk_op_pair_head_workspace_bytes: null argument");
+    if (H <= 0 || num_layers <= 0 || (long long)num_layers * H > (1 << 20))
+        return fail("esmk_op_pair_head_workspace_bytes: H and num_layers must be positive, num_layers * H at most 2^20");
+    *bytes = (size_t)num_layers * H * 64 * 4;
+    return 0;
+}
+
+int esmk_op_pair_head(const void* q_dev, const void* k_dev, const float* lse_dev, const float* key_bias_dev,
+                      const int64_t* tokens_dev, const float* w_dev, const float* bias_dev, int n_sym, int n_asym, float* out_dev,
+                      void* workspace_dev, size_t workspace_bytes, int B, int H, int T, int num_layers, int head_dim, int pad_idx,
+                      int prepend_bos, int append_eos, int operand_dtype, void* stream) {
+    const std::string who("esmk_op_pair_head");
+    if (!q_dev || !k_dev || !lse_dev || !w_dev || !out_dev || !workspace_dev) return fail(who + ": null argument");
+    if (operand_dtype != ESMK_DT_F16 && operand_dtype != ESMK_DT_BF16) return fail(who + ": operand_dtype must be fp16 or bf16");
+    if (pair_head_op_check(who, B, H, T, num_layers, head_dim, n_sym, n_asym, prepend_bos, append_eos)) return 1;
+    const int C = num_layers * H, C_out = n_sym + n_asym;
+    if (workspace_bytes < (size_t)C * 64 * 4) return fail(who + ": workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    float* w64 = (float*)workspace_dev;
+    ESMK_TRY(launch_pair_head_pad_w(w_dev, w64, C, C_out, st));
+    ESMK_TRY(launch_pair_head(q_dev, k_dev, lse_dev, key_bias_dev, tokens_dev, w64, bias_dev, out_dev, num_layers, B, H, T, head_dim,
+                              n_sym, n_asym, pad_idx, prepend_bos, append_eos, operand_dtype, st));
+    return 0;
+}
+
+int esmk_op_distogram_energy(const float* pair_logits_dev, int ld, int first, int n_bins, const uint8_t* target_bin_dev, int B, int S,
+                             int min_sep, double inv_temp, double* energy_out_dev, int32_t* count_out_dev, void* stream) {
+    const std::string who("esmk_op_distogram_energy");
+    if (!pair_logits_dev || !target_bin_dev || !energy_out_dev || !count_out_dev) return fail(who + ": null argument");
+    if (B <= 0 || S <= 0) return fail(who + ": B and S must be positive");
+    if (S > 32768) return fail(who + ": S above 32768 (the pairs of a map are indexed in 32 bits)");
+    if (B > ESMK_MAX_ROWS) return fail(who + ": B exceeds 2^24");
+    if (n_bins <= 0 || n_bins > 255) return fail(who + ": n_bins must be 1 .. 255 (255 is the ignore label)");
+    if (first < 0 || ld <= 0 || first + n_bins > ld) return fail(who + ": the bins first .. first + n_bins must lie inside the ld outputs of a pair");
+    if (min_sep < 0) return fail(who + ": min_sep must not be negative");
+    if (!(inv_temp > 0.0) || !std::isfinite(inv_temp)) return fail(who + ": inv_temp must be positive and finite");
+    ESMK_TRY(launch_distogram_energy(pair_logits_dev, ld, first, n_bins, target_bin_dev, energy_out_dev, count_out_dev, B, S, min_sep,
+                                     inv_temp, (hipStream_t)stream));
+    return 0;
+}
+
 int esmk_op_mh_accept(int64_t* tokens_dev, const int32_t* slot_dev, const int32_t* site_dev, const int32_t* tok_dev,
                       const int32_t* chain_id_dev, const double* e_contact_dev, const double* lp_sum_dev, const int32_t* n_res_dev,
                       const double* hastings_dev, double w_contact, double w_lm, double inv_temperature, uint64_t seed, int step,

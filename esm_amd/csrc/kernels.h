@@ -484,4 +484,18 @@ hipError_t launch_attention_probs(const void* q, const void* k, const float* lse
                                   int layer, int num_layers_total, int operand_dtype,
                                   hipStream_t st, bool lowp = false);
 
+// pair_head.hip — linear pairwise heads on the attention maps (esmk_set_pair_head, esmk_op_pair_head).  q, k [L,B,H,T,head_dim]
+// and lse [L,B,H,T] (log2 domain) of every layer, key_bias [B,T] (0 / -inf) and tokens [B,T] or null (either marks <pad>), w64 [L*H][64] (launch_pair_head_pad_w of
+// w [L*H][n_sym + n_asym]), bias [n_sym + n_asym] or null; out fp32 [B,S,S,n_sym + n_asym], S = T - prepend_bos - append_eos:
+// one accumulate launch over all channels, one in-place launch for the transpose term and the bias
+hipError_t launch_pair_head_pad_w(const float* w, float* w64, int C, int C_out, hipStream_t st);
+hipError_t launch_pair_head(const void* q, const void* k, const float* lse, const float* key_bias, const int64_t* tokens,
+                            const float* w64, const float* bias, float* out, int L, int B, int H, int T, int head_dim, int n_sym,
+                            int n_asym, int pad_idx, int prepend_bos, int append_eos, int operand_dtype, hipStream_t st);
+// the categorical cross-entropy of n_bins logits at pair_logits[b,i,j,first ..] (row stride ld) against target uint8 [S,S]
+// (>= n_bins: ignored), fp64, one workgroup per chain (esmk_op_distogram_energy)
+hipError_t launch_distogram_energy(const float* logits, int ld, int first, int n_bins, const unsigned char* target,
+                                   double* energy_out, int* count_out, int B, int S, int min_sep, double inv_temp,
+                                   hipStream_t st);
+
 }  // namespace esmk

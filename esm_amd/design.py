@@ -47,6 +47,12 @@ at neighbouring rungs of a ladder exchange their rungs with probability min(1, e
 round, 4, k)).  Temperatures move, sequences and chain ids stay in their slots, and the forward is the one the batch ran anyway.
 With ``replicas=None`` and ``w_ngram=0`` the calls, the bits and the return values are those of the loop above.
 
+``target`` may instead be a ``DistogramTarget(bins, head)``: lm-design's own structure term ``dist_cce_pos``, the categorical
+cross-entropy between the distance bins a linear projection of the attention maps predicts (``esm_amd.PairHead``, read from
+lm-design's projection checkpoint; esm_amd/pair_head.py) and the target's bins over the target's contacts.  The energy forward is
+then ``esmk_forward_rows_pair`` and the structure term ``esmk_op_distogram_energy``, in the slot of E_contact everywhere;
+``min_sep=0`` gives lm-design's term exactly and ``contact_loss`` is not used.  With any other target nothing changes.
+
 Not built: multi-site proposals, chains of different lengths, token-packed chains, the MSA Transformer (``NotImplementedError``).
 
     python -m esm_amd.design --model-location esm2_t33_650M_UR50D.pt --target-pdb 1abc.pdb --chain A --num-chains 16 \\
@@ -74,11 +80,10 @@ _THREE_TO_ONE = {"ALA": "A", "ARG": "R", "ASN": "N", "ASP": "D", "CYS": "C", "GL
                  "TYR": "Y", "VAL": "V", "MSE": "M", "SEC": "U", "PYL": "O"}
 
 
-def contacts_from_pdb(path, chain=None, cutoff=8.0):
-    """``(sequence, target)`` of one chain of a PDB file: the one-letter sequence of its residues in file order and the uint8
-    ``[S, S]`` target map — 1 where the C-beta atoms (C-alpha for glycine) of two residues are closer than ``cutoff`` angstrom, 0
-    where they are not, 2 (ignore) in the row and column of a residue that lacks the atom.  Plain ATOM records of the first
-    model; ``chain`` None: the first chain of the file; of alternate locations the first one seen counts.  numpy only."""
+def _read_cb(path, chain=None):
+    """``(sequence, have bool [S], xyz fp64 [S, 3])`` of one chain of a PDB file: the one-letter sequence of its residues in file
+    order and the C-beta atom (C-alpha for glycine) of each, ``have`` False (and a zero position) where a residue lacks it.  Plain
+    ATOM records of the first model; ``chain`` None: the first chain of the file; of alternate locations the first one seen."""
     order, atoms, names = [], {}, {}
     with open(path) as fh:
         for line in fh:
@@ -106,6 +111,15 @@ def contacts_from_pdb(path, chain=None, cutoff=8.0):
     seq = "".join(_THREE_TO_ONE.get(names[k], "X") for k in order)
     have = np.array([k in atoms for k in order])
     xyz = np.array([atoms.get(k, (0.0, 0.0, 0.0)) for k in order], dtype=np.float64).reshape(S, 3)
+    return seq, have, xyz
+
+
+def contacts_from_pdb(path, chain=None, cutoff=8.0):
+    """``(sequence, target)`` of one chain of a PDB file: the one-letter sequence of its residues in file order and the uint8
+    ``[S, S]`` target map — 1 where the C-beta atoms (C-alpha for glycine) of two residues are closer than ``cutoff`` angstrom, 0
+    where they are not, 2 (ignore) in the row and column of a residue that lacks the atom.  Plain ATOM records of the first
+    model; ``chain`` None: the first chain of the file; of alternate locations the first one seen counts.  numpy only."""
+    seq, have, xyz = _read_cb(path, chain)
     dist = np.sqrt(((xyz[:, None, :] - xyz[None, :, :]) ** 2).sum(-1))
     target = (dist < float(cutoff)).astype(np.uint8)
     target[~have, :] = IGNORE
@@ -131,6 +145,46 @@ def target_map(target, S=None):
     if bool(((t < 0) | (t > 2)).any()):
         raise ValueError("target: integer maps hold 0 (no contact), 1 (contact) or 2 (ignore)")
     return t.to(torch.uint8).contiguous()
+
+
+class DistogramTarget:
+    """lm-design's structure term ``dist_cce_pos`` as the ``target`` of ``design`` / ``design_energy``: the categorical
+    cross-entropy (examples/lm-design/utils/loss.py:10-29) between the distance bins a ``PairHead`` predicts from the attention
+    maps and the target's bins, over the target's contacts — the pairs whose bin is <= ``contact_cutoff_bin``
+    (struct_models.py:35; lm_design.py:254-280); every other pair, and every pair whose bin is 255, is ignored.
+
+    bins         uint8 ``[S, S]`` distance bins (``esm_amd.distogram_bins``, ``distogram_from_pdb``)
+    head         the ``esm_amd.PairHead`` (``PairHead.from_linear_projection``)
+    output       the head's output that holds the distance logits
+    temperature  the logits are divided by it before the softmax
+
+    The term comes from ``esmk_forward_rows_pair`` + ``esmk_op_distogram_energy`` and takes the slot of the contact term
+    everywhere: ``w_contact`` weighs it, ``e_contact`` names it in the trajectory and the log.  ``min_sep=0`` gives lm-design's
+    term exactly (the mean over ALL ordered pairs that count); ``contact_loss`` is ignored with this target."""
+
+    def __init__(self, bins, head, output="dist", contact_cutoff_bin=5, temperature=1.0):
+        from .pair_head import IGNORE_BIN, PairHead
+
+        if not isinstance(head, PairHead):
+            raise TypeError("DistogramTarget: head must be an esm_amd.PairHead")
+        if output not in head.outputs:
+            raise ValueError(f"DistogramTarget: the head has no output {output!r} (it has {sorted(head.outputs)})")
+        b = torch.as_tensor(np.asarray(bins) if not torch.is_tensor(bins) else bins).cpu()
+        if b.ndim != 2 or b.shape[0] != b.shape[1] or b.is_floating_point() or b.dtype == torch.bool:
+            raise ValueError(f"DistogramTarget: bins is an integer [S, S] map of distance bins, got {b.dtype} {tuple(b.shape)}")
+        self.head, self.output = head, output
+        self.first, hi = head.columns(output)
+        self.n_bins = hi - self.first
+        b = b.to(torch.int64)
+        if bool(((b < 0) | ((b >= self.n_bins) & (b != IGNORE_BIN))).any()):
+            raise ValueError(f"DistogramTarget: bins hold 0 .. {self.n_bins - 1} or {IGNORE_BIN} (ignore)")
+        self.contact_cutoff_bin = int(contact_cutoff_bin)
+        self.temperature = float(temperature)
+        if not (math.isfinite(self.temperature) and self.temperature > 0.0):
+            raise ValueError("DistogramTarget: temperature must be positive and finite")
+        counted = torch.where(b <= self.contact_cutoff_bin, b, torch.full_like(b, IGNORE_BIN))
+        self.bins = counted.to(torch.uint8).contiguous()  # what esmk_op_distogram_energy takes
+        self.S = int(b.shape[0])
 
 
 def batch_size(bytes_of, n_chains, max_bytes):
@@ -211,9 +265,19 @@ class _Setup:
             raise ValueError(f"contact_loss {contact_loss!r}: one of {CONTACT_LOSSES}")
         self.contact_loss = contact_loss
         self.min_sep = int(min_sep)
-        if self.min_sep < 1:
+        self.disto = None
+        if isinstance(target, DistogramTarget):  # the distogram term in the contact term's slot (contact_loss is not used)
+            if self.min_sep < 0:
+                raise ValueError("min_sep must not be negative")
+            if target.S != self.S:
+                raise ValueError(f"target holds bins of {target.S} residues but the chains have {self.S}: all chains have the "
+                                 "target's length")
+            target.head.check_model(model)
+            self.target = None
+            self.disto = target if self.w_contact != 0.0 else None
+        elif self.min_sep < 1:
             raise ValueError("min_sep must be at least 1")
-        if target is None:
+        elif target is None:
             if self.w_contact != 0.0:
                 raise ValueError("target=None needs w_contact=0")
             self.target = None
@@ -230,6 +294,7 @@ class _Energy:
     def __init__(self, model, setup, dev):
         self.model, self.su, self.dev = model, setup, dev
         self.target = None if setup.target is None else setup.target.to(dev)
+        self.bins = None if setup.disto is None else setup.disto.bins.to(dev)
         self.V = model.alphabet_size
         self._tables = {}
         self.ngram_code = self.ngram_q = None
@@ -246,6 +311,9 @@ class _Energy:
         with torch.cuda.device(self.dev):
             eng = self.model._engine_ready(self.dev)
             n_sel = B * su.S if su.w_lm != 0.0 else 0
+            if su.disto is not None:  # the q / k / lse of every layer, and the pair logits themselves
+                eng.set_pair_head(su.disto.head)
+                return eng.rows_pair_bytes(B, su.T, n_sel) + B * su.S * su.S * su.disto.head.n_out * 4
             if su.w_contact != 0.0:
                 return eng.rows_contacts_bytes(B, su.T, n_sel)
             return eng._query(eng.N.lib.esmk_rows_workspace_bytes, B, su.T, n_sel, offset=True)[0]
@@ -270,7 +338,15 @@ class _Energy:
         B = tok.shape[0]
         sel, sel_long, off, n_res = self.tables(B)
         want_lm = su.w_lm != 0.0
-        if su.w_contact != 0.0:
+        if su.disto is not None:
+            dt = su.disto
+            with torch.cuda.device(self.dev):
+                eng = self.model._engine_ready(self.dev)
+                eng.set_pair_head(dt.head)
+                pair = torch.empty((B, su.S, su.S, dt.head.n_out), dtype=torch.float32, device=self.dev)
+                lp = eng.forward_rows_pair(tok, sel if want_lm else None, self.V, pair)
+            e_contact = ops.distogram_energy(pair, self.bins, dt.first, dt.n_bins, su.min_sep, 1.0 / dt.temperature)[0]
+        elif su.w_contact != 0.0:
             with torch.cuda.device(self.dev):
                 lp, maps = self.model._engine_ready(self.dev).forward_rows_contacts(tok, sel if want_lm else None, self.V, su.S)
             e_contact = ops.contact_energy(maps, self.target, su.min_sep, su.contact_loss)[0]
@@ -331,7 +407,8 @@ def design(model, tokens, target, steps, positions=None, w_contact=1.0, w_lm=1.0
     toward ``target``: ``(tokens [B, T], energy fp64 [B])`` on the model's device — with ``replicas`` ``(tokens, energy, rung int32
     [B])`` —, plus the trajectory when asked for.
 
-    target       ``[S, S]`` bool, uint8 (0 / 1 / 2 = ignore) or float (thresholded at 0.5, NaN = ignore), S = T minus the
+    target       a ``DistogramTarget`` (lm-design's distance-bin term through a ``PairHead``; ``contact_loss`` is then ignored and
+                 ``min_sep`` may be 0), or ``[S, S]`` bool, uint8 (0 / 1 / 2 = ignore) or float (thresholded at 0.5, NaN = ignore), S = T minus the
                  <cls> / <eos> the alphabet adds (``contacts_from_pdb`` reads one from a PDB file); None with ``w_contact=0``.
     steps        every step proposes one single-site mutation per chain and accepts it with probability min(1, exp(-dE / T) *
                  q(x | x') / q(x' | x)).
@@ -544,6 +621,10 @@ def parse_args(argv=None):
     t.add_argument("--target-npy", help="[S, S] array: bool, 0 / 1 / 2 = ignore, or floats thresholded at 0.5 (NaN = ignore)")
     t.add_argument("--target-from-sequence", metavar="SEQ", help="the model's own contact map of a native sequence, at 0.5")
     t.add_argument("--no-target", action="store_true", help="LM term only (needs --length)")
+    p.add_argument("--structure", choices=("contacts", "distogram"), default="contacts",
+                   help="the structure term: the contact head's map against the target contacts, or (with --pair-head and "
+                        "--target-pdb) lm-design's distance-bin cross-entropy on a linear projection of the attention maps")
+    p.add_argument("--pair-head", metavar="CKPT", default=None, help="lm-design's linear projection checkpoint (--structure distogram)")
     p.add_argument("--chain", default=None, help="chain of --target-pdb (default: its first chain)")
     p.add_argument("--cutoff", type=_at_least(0.0, float), default=8.0, help="contact distance of --target-pdb in angstrom")
     p.add_argument("--length", type=_at_least(1), default=None, help="residues per chain with --no-target")
@@ -578,6 +659,10 @@ def parse_args(argv=None):
         p.error("--length goes with --no-target: the target sets the length")
     if a.chain is not None and a.target_pdb is None:
         p.error("--chain goes with --target-pdb")
+    if a.structure == "distogram" and (a.pair_head is None or a.target_pdb is None):
+        p.error("--structure distogram needs --pair-head and --target-pdb")
+    if a.structure == "contacts" and a.pair_head is not None:
+        p.error("--pair-head goes with --structure distogram")
     if (a.replicas is None) != (a.ladder is None):
         p.error("--replicas K and --ladder T0:T1 go together")
     if a.replicas is not None and a.num_chains % a.replicas != 0:
@@ -634,7 +719,11 @@ def main(argv=None):
     elif a.target_from_sequence:
         toks = convert([("native", a.target_from_sequence)])[2].cuda()
         target = model.predict_contacts(toks)[0].float().cpu().numpy()
-    length = a.length if a.no_target else int(np.asarray(target).shape[0])
+    if a.structure == "distogram":
+        from .pair_head import PairHead, distogram_from_pdb
+
+        target = DistogramTarget(distogram_from_pdb(a.target_pdb, a.chain)[1], PairHead.from_linear_projection(a.pair_head, model))
+    length = a.length if a.no_target else target.S if a.structure == "distogram" else int(np.asarray(target).shape[0])
     if a.init_sequence is not None:
         if len(a.init_sequence) != length:
             raise SystemExit(f"--init-sequence has {len(a.init_sequence)} residues, the target {length}")

@@ -438,6 +438,36 @@ class Esm2Engine(Engine):
         self.max_T = max(self.max_T, T)
         return out, contacts
 
+    def set_pair_head(self, head):
+        """The handle's pairwise head becomes ``head`` (``esm_amd.pair_head.PairHead`` or None); no call when it is."""
+        if head is getattr(self, "pair_head", None):
+            return
+        N = self.N
+        if head is None:
+            N.check(N.lib.esmk_set_pair_head(self.handle, None, None, 0, 0))
+        else:
+            w, b = head.matrix(), head.bias()  # fp32 CPU [C, C_out], [C_out]: the handle copies them
+            N.check(N.lib.esmk_set_pair_head(self.handle, N.ptr(w), N.ptr(b), head.n_sym, head.n_asym))
+        self.pair_head = head
+
+    def rows_pair_bytes(self, B, T, n_sel):
+        """The workspace ``esmk_forward_rows_pair`` takes: the q / k / lse of every layer included."""
+        return self._query(self.N.lib.esmk_rows_pair_workspace_bytes, B, T, n_sel, offset=True)[0]
+
+    def forward_rows_pair(self, tok, sel_rows, V, pair_out):
+        """``esmk_forward_rows_pair`` on ``tok`` int64 [B, T] with the head of ``set_pair_head``: fp32 [n, V] log-probabilities of
+        ``sel_rows`` (None when there are none); ``pair_out`` fp32 [B, S, S, C_out] receives the pair logits."""
+        N = self.N
+        B, T = tok.shape
+        n = 0 if sel_rows is None else sel_rows.numel()
+        ws = self.workspace_for_bytes(self.rows_pair_bytes(B, T, n))
+        out = torch.empty((n, V), dtype=torch.float32, device=self.device) if n else None
+        assert pair_out.dtype == torch.float32 and pair_out.is_contiguous() and pair_out.shape[0] == B
+        N.check(N.lib.esmk_forward_rows_pair(self.handle, N.ptr(self.packed), N.ptr(tok), B, T, N.ptr(sel_rows if n else None), n,
+                                             N.ptr(out), N.ptr(pair_out), N.ptr(ws), ws.numel(), N.cur_stream()))
+        self.max_T = max(self.max_T, T)
+        return out
+
 
 class MsaEngine(Engine):
     """The engine of ``MSATransformer``: ``esmk_msa_create`` and the ``esmk_msa_forward*`` entries."""

@@ -502,6 +502,14 @@ class ESM2(_EngineHost, nn.Module):
 
         return jacobian.jacobian_contacts(self, tokens, allowed=allowed, chunk=chunk, return_jacobian=return_jacobian)
 
+    # linear pairwise heads on the attention maps (esm_amd/pair_head.py): no attention tensor
+    def pair_logits(self, tokens, head, max_bytes=8 << 30, varlen=False, window=None):
+        """``esm_amd.pair_head.pair_logits``: name -> fp32 [B, S, S, n] logits of the ``PairHead`` ``head`` (lm-design's distogram
+        and orientation head, or any linear head on the L*H attention maps)."""
+        from . import pair_head
+
+        return pair_head.pair_logits(self, tokens, head, max_bytes=max_bytes, varlen=varlen, window=window)
+
     def predict_contacts(self, tokens):
         """Reference esm2.py:146-147 returns ``self(tokens, return_contacts=True)["contacts"]``, which first builds
         the [B,L,H,T,T] attention tensor (2.8 GB per 1024-token sequence at 650M).  Only the map leaves this call, so

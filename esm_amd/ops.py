@@ -1282,3 +1282,58 @@ def stream_edit(x, op, keep=1.0, gain=1.0, rows=None, tokens=None, token_set=0, 
     N.check(N.lib.esmk_op_stream_edit(N.ptr(x), N.ptr(tokens), x.shape[0], x.shape[1], ctypes.byref(desc), N.ptr(y),
                                       0 if y is None else y.stride(0), N.ptr(mean), N.ptr(rstd), code, N.cur_stream()))
     return x
+
+
+def pair_head(q, k, lse, w, bias=None, n_sym=None, key_bias=None, tokens=None, pad_idx=1, prepend_bos=True, append_eos=True):
+    """The linear pairwise head of csrc/pair_head.hip on stacked operands: q, k [L,B,H,T,D] (fp16 / bf16, D = 64 or 128, q in
+    the LOG2 domain: ``to_log2_domain``), lse [L,B,H,T] the NATURAL-log row log-sum-exp (as ``attention`` returns it; converted
+    here as fp32(lse * log2 e) in fp64), w fp32 [L*H, C_out] with the ``n_sym`` symmetric outputs first (default: all), bias fp32
+    [C_out] or None, key_bias fp32 [B,T] (0 / -inf) and / or tokens int64 [B,T] marking <pad> -> fp32 [B,S,S,C_out]:
+    ``sum_c w[c,o] (P_c[i,j] + P_c[j,i]) + bias[o]`` for o < n_sym, ``sum_c w[c,o] P_c[i,j] + bias[o]`` for the rest."""
+    _req_cuda(q, k, lse, w, bias, key_bias, tokens)
+    L, B, H, T, D = q.shape
+    assert q.dtype == k.dtype and q.shape == k.shape and q.is_contiguous() and k.is_contiguous()
+    assert w.dtype == torch.float32 and w.dim() == 2 and w.shape[0] == L * H and w.is_contiguous()
+    C_out = w.shape[1]
+    n_sym = C_out if n_sym is None else int(n_sym)
+    assert bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (C_out,) and bias.is_contiguous())
+    assert key_bias is None or (key_bias.dtype == torch.float32 and tuple(key_bias.shape) == (B, T) and key_bias.is_contiguous())
+    assert tokens is None or (tokens.dtype == torch.int64 and tuple(tokens.shape) == (B, T) and tokens.is_contiguous())
+    lse2 = (lse.double() * LOG2E).float().contiguous()
+    assert lse2.numel() == L * B * H * T
+    bos, eos = int(prepend_bos), int(append_eos)
+    S = T - bos - eos
+    n = ctypes.c_size_t()
+    N.check(N.lib.esmk_op_pair_head_workspace_bytes(H, L, ctypes.byref(n)))
+    workspace = torch.empty(max(n.value, 1), dtype=torch.uint8, device=q.device)
+    out = torch.empty((B, max(S, 0), max(S, 0), C_out), dtype=torch.float32, device=q.device)
+    N.check(N.lib.esmk_op_pair_head(N.ptr(q), N.ptr(k), N.ptr(lse2), N.ptr(key_bias), N.ptr(tokens), N.ptr(w), N.ptr(bias), n_sym,
+                                    C_out - n_sym, N.ptr(out), N.ptr(workspace), workspace.numel(), B, H, T, L, D, int(pad_idx), bos,
+                                    eos, N.dtype_code(q.dtype), N.cur_stream()))
+    return out
+
+
+def distogram_energy(pair_logits, target_bin, first=0, n_bins=None, min_sep=0, inv_temp=1.0):
+    """``(energy fp64 [B], count int32 [B])``: lm-design's categorical cross-entropy (utils/loss.py:10-29) of the ``n_bins``
+    logits ``pair_logits[b, i, j, first:first + n_bins]`` (fp32 [B, S, S, ld], possibly a last-axis view of a wider tensor)
+    against ``target_bin`` uint8 [S, S]: the mean over ALL ordered pairs with target_bin < n_bins (255 = ignore) and
+    |i - j| >= ``min_sep`` of -log(softmax(inv_temp * logits)[target_bin] + 1e-8), in fp64.  The order of addition does not
+    depend on B; no counted pair: 0.0."""
+    _req_cuda(target_bin)
+    if not pair_logits.is_cuda:
+        raise RuntimeError("esm_amd.ops: tensors must live on the GPU (no CPU fallback)")
+    assert pair_logits.dtype == torch.float32 and pair_logits.dim() == 4
+    B, S, S2, width = pair_logits.shape
+    n_bins = width - int(first) if n_bins is None else int(n_bins)
+    # a last-axis slice of a contiguous [B, S, S, ld] tensor: the kernel takes ld and the first column
+    ld = pair_logits.stride(2)
+    assert pair_logits.stride(3) == 1 and pair_logits.stride(1) == S * ld and pair_logits.stride(0) == S * S * ld
+    assert S == S2 and target_bin.dtype == torch.uint8 and tuple(target_bin.shape) == (S, S) and target_bin.is_contiguous()
+    energy = torch.empty((B,), dtype=torch.float64, device=pair_logits.device)
+    count = torch.empty((B,), dtype=torch.int32, device=pair_logits.device)
+    # the base of the row space: the view's first column is folded into ``first``
+    off = pair_logits.storage_offset() % ld if ld else 0
+    base = pair_logits.data_ptr() - off * 4
+    N.check(N.lib.esmk_op_distogram_energy(ctypes.c_void_p(base), ld, off + int(first), n_bins, N.ptr(target_bin), B, S,
+                                           int(min_sep), float(inv_temp), N.ptr(energy), N.ptr(count), N.cur_stream()))
+    return energy, count

@@ -1085,6 +1085,48 @@ int esmk_op_contacts(const float* attn_dev, const int64_t* tokens_dev, const flo
                      const float* b_dev, float* scratch_dev, float* out_dev, int B, int C, int T,
                      int eos_idx, int prepend_bos, int append_eos, void* stream);
 
+/* Linear pairwise heads on the attention maps without the [B,L,H,T,T] tensor (csrc/pair_head.hip; esm_amd/pair_head.py).  The
+ * head of lm-design's structure model (examples/lm-design/utils/linear_projection.py:85-135) is two 1 x 1 convolutions over the
+ * C = L*H attention channels c = layer * H + head: n_sym outputs on the symmetrised maps P + P^T, n_asym on the maps as they are.
+ * With w fp32 [C][n_sym + n_asym] (row c = the weights of channel c, the n_sym symmetric outputs first) and bias [n_sym + n_asym]:
+ *   Z[b,i,j,o]   = sum over c ascending of w[c,o] * P_c[b,i,j]          (fp32, one fused multiply-add per channel)
+ *   out[b,i,j,o] = Z[b,i,j,o] + Z[b,j,i,o] + bias[o]  for o < n_sym,    Z[b,i,j,o] + bias[o]  for the rest
+ * out fp32 [B,S,S,n_sym + n_asym], S = T - prepend_bos - append_eos: only the first / last position is cropped (no <eos> mask,
+ * no APC, linear_projection.py:76-82).  P_c is recomputed from the q, k and row log-sum-exp the attention kernel of the layer
+ * used; rows and columns of <pad> tokens are exact zeros, so entries that involve a <pad> position hold the bias.  One writer
+ * per element, no atomics, a fixed order of addition: a sequence's map does not depend on the batch it ran in.
+ * esmk_set_pair_head: the handle keeps a device copy of w_host / bias_host (host arrays); n_sym = n_asym = 0 clears the head.
+ *   Refused before any HIP call: a null model, an MSA handle, negative counts, n_sym + n_asym > 64, null arrays with a head.
+ * esmk_forward_rows_pair: esmk_forward_rows (the layer stack once, head and log-softmax on the n_sel selected rows; n_sel = 0
+ *   with null row arguments is allowed) plus pair_out_dev; every layer's q, k and lse are kept in the workspace
+ *   (esmk_rows_pair_workspace_bytes: 2 L B T H slots operand elements + 4 L B H T bytes on top of esmk_forward_rows') and the
+ *   head runs as ONE launch over all channels after the last layer.  The log-probability rows are bit for bit those of
+ *   esmk_forward_rows.  Padded batches only; every model and precision mode esmk_forward_rows_contacts serves; the handle's
+ *   stream edits apply.  Refused: no head set, an MSA handle, T - prepend_bos - append_eos <= 0, what esmk_forward_rows refuses.
+ * esmk_op_pair_head: the two kernels on caller-supplied stacked operands, laid out as the padded case of
+ *   esmk_op_contacts_fused_ex: q, k [L,B,H,T,head_dim] operand dtype (q in the log2 domain), lse fp32 [L,B,H,T] (log2 domain),
+ *   key_bias fp32 [B,T] (0 / -inf) or NULL, tokens int64 [B,T] or NULL (either marks <pad>), w_dev / bias_dev device arrays
+ *   (bias_dev may be NULL: 0), workspace of esmk_op_pair_head_workspace_bytes.
+ * esmk_op_distogram_energy: lm-design's categorical cross-entropy (utils/loss.py:10-29) of the n_bins logits
+ *   pair_logits[b,i,j,first .. first + n_bins) (fp32 [B,S,S,ld]) against target_bin uint8 [S,S]: per chain the mean over ALL
+ *   ordered pairs (i,j) with target_bin[i,j] < n_bins (255 = ignore) and |i - j| >= min_sep of
+ *   -log(softmax(inv_temp * logits)[target_bin] + 1e-8), in fp64.  One workgroup of 256 lanes per chain; lane t adds the terms of
+ *   the elements t, t + 256, ... of the row-major map in that order, the lane sums in a butterfly per wavefront, the four
+ *   wavefront sums in order: the order of addition does not depend on B.  energy_out fp64 [B], count_out int32 [B]; no counted
+ *   pair: 0.0. */
+int esmk_set_pair_head(esmk_model* m, const float* w_host, const float* bias_host, int n_sym, int n_asym);
+int esmk_rows_pair_workspace_bytes(const esmk_model* m, int B, int T, int n_sel, size_t* bytes, size_t* logits_offset);
+int esmk_forward_rows_pair(esmk_model* m, const void* packed_dev, const int64_t* tokens_dev, int B, int T,
+                           const int32_t* sel_rows_dev, int n_sel, float* logprobs_out_dev, float* pair_out_dev,
+                           void* workspace_dev, size_t workspace_bytes, void* stream);
+int esmk_op_pair_head_workspace_bytes(int H, int num_layers, size_t* bytes);
+int esmk_op_pair_head(const void* q_dev, const void* k_dev, const float* lse_dev, const float* key_bias_dev,
+                      const int64_t* tokens_dev, const float* w_dev, const float* bias_dev, int n_sym, int n_asym, float* out_dev,
+                      void* workspace_dev, size_t workspace_bytes, int B, int H, int T, int num_layers, int head_dim, int pad_idx,
+                      int prepend_bos, int append_eos, int operand_dtype, void* stream);
+int esmk_op_distogram_energy(const float* pair_logits_dev, int ld, int first, int n_bins, const uint8_t* target_bin_dev, int B, int S,
+                             int min_sep, double inv_temp, double* energy_out_dev, int32_t* count_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
