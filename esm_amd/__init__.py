@@ -21,6 +21,7 @@ from .jacobian import categorical_jacobian, jacobian_contacts  # noqa: F401
 from .windows import forward_windows  # noqa: F401
 from .interventions import StreamEdit, forward_edited, mean_difference, stream_edits  # noqa: F401
 from .pair_head import PairHead, distogram_bins, distogram_from_pdb  # noqa: F401
+from .sae import SparseAutoencoder  # noqa: F401
 
 
 def __getattr__(name):
@@ -35,6 +36,10 @@ def __getattr__(name):
         import importlib
 
         return importlib.import_module(".pair_logits", __name__)
+    if name == "sae_features":  # and ``python -m esm_amd.sae_features``
+        import importlib
+
+        return importlib.import_module(".sae_features", __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

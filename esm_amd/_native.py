@@ -123,6 +123,15 @@ SIGNATURES = {
                 c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "esmk_op_distogram_energy": (
         c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    # sparse-autoencoder features of the stream (csrc/sae.hip): the operand image, the row-wise top-k, the per-sequence
+    # maximum, the decode
+    "esmk_op_sae_cand": (c_int, []),
+    "esmk_op_sae_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p]),
+    "esmk_op_sae_topk": (c_int, [c_void_p, c_int, c_void_p, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
+    "esmk_op_sae_segment_max": (c_int, [c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                        c_void_p, c_void_p, c_void_p]),
+    "esmk_op_sae_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p]),
     # edits of the residual stream between layers: the handle's list, and one edit as a single op
     "esmk_set_stream_edits": (c_int, [c_void_p, POINTER(EsmkStreamEdit), c_int]),
     "esmk_op_stream_edit": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(EsmkStreamEdit), c_void_p, c_int, c_void_p, c_void_p,

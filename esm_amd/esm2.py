@@ -510,6 +510,16 @@ class ESM2(_EngineHost, nn.Module):
 
         return pair_head.pair_logits(self, tokens, head, max_bytes=max_bytes, varlen=varlen, window=window)
 
+    # sparse-autoencoder features of the stream (esm_amd/sae.py): device top-k per residue, maxima per protein
+    def sae_features(self, tokens, sae, layer, top_k=None, positions="residues", varlen=False, protein_max=False,
+                     return_dense=False, max_bytes=2 << 30):
+        """``esm_amd.sae.sae_features``: rows, indices, values and n_active of the ``SparseAutoencoder`` ``sae`` on representation
+        ``layer`` of every scored row; with ``protein_max`` the per-sequence maximum of every feature and where it was."""
+        from . import sae as S
+
+        return S.sae_features(self, tokens, sae, layer, top_k=top_k, positions=positions, varlen=varlen, protein_max=protein_max,
+                              return_dense=return_dense, max_bytes=max_bytes)
+
     def predict_contacts(self, tokens):
         """Reference esm2.py:146-147 returns ``self(tokens, return_contacts=True)["contacts"]``, which first builds
         the [B,L,H,T,T] attention tensor (2.8 GB per 1024-token sequence at 650M).  Only the map leaves this call, so

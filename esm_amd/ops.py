@@ -1337,3 +1337,103 @@ def distogram_energy(pair_logits, target_bin, first=0, n_bins=None, min_sep=0, i
     N.check(N.lib.esmk_op_distogram_energy(ctypes.c_void_p(base), ld, off + int(first), n_bins, N.ptr(target_bin), B, S,
                                            int(min_sep), float(inv_temp), N.ptr(energy), N.ptr(count), N.cur_stream()))
     return energy, count
+
+
+# ---- sparse-autoencoder features of the stream (include/esmk.h: esmk_op_sae_rows ... esmk_op_sae_decode) -------------------
+def sae_cand():
+    """The number of active features of a row up to which ``sae_topk`` selects in LDS (``kSaeCand`` of csrc/sae.hip)."""
+    return int(N.lib.esmk_op_sae_cand())
+
+
+def sae_rows(x, rows=None, b_dec=None, input_scale=1.0, out=None, n=None):
+    """The f16x3 activation image of SAE inputs (``esmk_op_sae_rows``): x fp32 [N, E], rows int32 [n] or None (the first ``n``
+    rows, default all) -> fp16 [>= n, ld >= 3 Ep] rows ``hi | hi | lo`` per 64-column K tile of u = input_scale * x - b_dec
+    (Ep = E rounded up to 64, pad columns zero); ``out`` is the caller's (row stride taken from the tensor) or allocated."""
+    _req_cuda(x, rows, b_dec, out)
+    assert x.dtype == torch.float32 and x.dim() == 2
+    assert rows is None or (rows.dtype == torch.int32 and rows.dim() == 1)
+    assert b_dec is None or (b_dec.dtype == torch.float32 and b_dec.numel() == x.shape[1])
+    Nr, E = x.shape
+    n = (Nr if rows is None else rows.numel()) if n is None else int(n)
+    assert rows is None or rows.numel() >= n
+    Ep = (E + 63) // 64 * 64
+    if out is None:
+        out = torch.empty((n, 3 * Ep), dtype=torch.float16, device=x.device)
+    assert out.dtype == torch.float16 and out.dim() == 2 and out.shape[0] >= n
+    N.check(N.lib.esmk_op_sae_rows(N.ptr(x), E, Nr, N.ptr(rows if n else None), n, N.ptr(b_dec), float(input_scale), N.ptr(out),
+                                   out.shape[1], E, N.cur_stream()))
+    return out
+
+
+def sae_topk(z, k, threshold=0.0, k_sae=0, n=None, indices=None, values=None, n_active=None, want_cutoff=False, want_path=False,
+             F=None):
+    """Row-wise top-k of SAE pre-activations (``esmk_op_sae_topk``): z fp32 [>= n, ldz] of which the first ``F`` columns
+    (default all) are features; ``threshold`` a float or fp32 [F] -> dict(indices int32 [n, k], values fp32 [n, k], n_active
+    int32 [n]) and, when asked for, cutoff (uint64 keys as int64 [n]) and path int32 [n] (0: the LDS path, > 0: the radix
+    select).  Output tensors may be the caller's ([>= n, k] / [>= n], written in place)."""
+    _req_cuda(z, indices, values, n_active)
+    assert z.dtype == torch.float32 and z.dim() == 2
+    n = z.shape[0] if n is None else int(n)
+    F = z.shape[1] if F is None else int(F)
+    assert z.shape[0] >= n
+    thr_t, thr_s = (threshold, 0.0) if isinstance(threshold, torch.Tensor) else (None, float(threshold))
+    if thr_t is not None:
+        _req_cuda(thr_t)
+        assert thr_t.dtype == torch.float32 and thr_t.numel() == F
+    dev = z.device
+    indices = torch.empty((n, k), dtype=torch.int32, device=dev) if indices is None else indices
+    values = torch.empty((n, k), dtype=torch.float32, device=dev) if values is None else values
+    n_active = torch.empty((n,), dtype=torch.int32, device=dev) if n_active is None else n_active
+    assert indices.dtype == torch.int32 and values.dtype == torch.float32 and n_active.dtype == torch.int32
+    assert indices.shape[0] >= n and values.shape[0] >= n and n_active.shape[0] >= n
+    assert tuple(indices.shape[1:]) == (k,) and tuple(values.shape[1:]) == (k,)
+    cutoff = torch.zeros((max(n, 1),), dtype=torch.int64, device=dev) if want_cutoff else None
+    path = torch.zeros((max(n, 1),), dtype=torch.int32, device=dev) if want_path else None
+    N.check(N.lib.esmk_op_sae_topk(N.ptr(z), z.shape[1], N.ptr(thr_t), thr_s, n, F, int(k), int(k_sae), N.ptr(indices),
+                                   N.ptr(values), N.ptr(n_active), N.ptr(cutoff), N.ptr(path), N.cur_stream()))
+    out = dict(indices=indices, values=values, n_active=n_active)
+    if want_cutoff:
+        out["cutoff"] = cutoff[:n]
+    if want_path:
+        out["path"] = path[:n]
+    return out
+
+
+def sae_segment_max(z, rows, seg_start, protein_max, protein_argmax, threshold=0.0, cutoff=None, row0=0, n=None, F=None):
+    """``esmk_op_sae_segment_max``: protein_max fp32 [B, F] / protein_argmax int32 [B, F] updated IN PLACE from the chunk z fp32
+    [>= n, ldz] holding rows row0 .. row0 + n of a row list; rows int32 [n, 2] the chunk's (sequence, position) pairs, seg_start
+    int32 [B + 1] the sequences' row ranges in the whole list; cutoff: ``sae_topk``'s, for a top-k autoencoder."""
+    _req_cuda(z, rows, seg_start, protein_max, protein_argmax, cutoff)
+    assert z.dtype == torch.float32 and z.dim() == 2
+    n = z.shape[0] if n is None else int(n)
+    B, Fm = protein_max.shape
+    F = Fm if F is None else int(F)
+    assert F == Fm and z.shape[1] >= F and z.shape[0] >= n
+    assert protein_max.dtype == torch.float32 and protein_argmax.dtype == torch.int32 and tuple(protein_argmax.shape) == (B, F)
+    assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[1] == 2 and rows.shape[0] >= n
+    assert seg_start.dtype == torch.int32 and seg_start.numel() == B + 1
+    assert cutoff is None or (cutoff.dtype == torch.int64 and cutoff.numel() >= n)
+    thr_t, thr_s = (threshold, 0.0) if isinstance(threshold, torch.Tensor) else (None, float(threshold))
+    if thr_t is not None:
+        _req_cuda(thr_t)
+        assert thr_t.dtype == torch.float32 and thr_t.numel() == F
+    N.check(N.lib.esmk_op_sae_segment_max(N.ptr(z), z.shape[1], N.ptr(thr_t), thr_s, N.ptr(cutoff), N.ptr(rows if n else seg_start),
+                                          N.ptr(seg_start), int(row0), n, F, B, N.ptr(protein_max), N.ptr(protein_argmax),
+                                          N.cur_stream()))
+    return protein_max, protein_argmax
+
+
+def sae_decode(indices, values, w_dec, b_dec=None, inv_scale=1.0, out=None):
+    """``esmk_op_sae_decode``: fp32 [n, E] = inv_scale * (b_dec + sum_r values[:, r] * w_dec[indices[:, r]]), one rounded product
+    and one rounded add per term in rank order; index -1 is skipped.  indices int32 [n, k], values fp32 [n, k], w_dec fp32 [F, E]."""
+    _req_cuda(indices, values, w_dec, b_dec, out)
+    assert indices.dtype == torch.int32 and values.dtype == torch.float32 and indices.dim() == 2 and indices.shape == values.shape
+    assert w_dec.dtype == torch.float32 and w_dec.dim() == 2
+    n, k = indices.shape
+    F, E = w_dec.shape
+    assert b_dec is None or (b_dec.dtype == torch.float32 and b_dec.numel() == E)
+    out = _out(out, (n, E), torch.float32, w_dec.device)
+    if n:
+        N.check(N.lib.esmk_op_sae_decode(N.ptr(indices), N.ptr(values), n, k, N.ptr(w_dec), N.ptr(b_dec), float(inv_scale),
+                                         N.ptr(out), E, F, N.cur_stream()))
+    return out

@@ -1127,6 +1127,48 @@ int esmk_op_pair_head(const void* q_dev, const void* k_dev, const float* lse_dev
 int esmk_op_distogram_energy(const float* pair_logits_dev, int ld, int first, int n_bins, const uint8_t* target_bin_dev, int B, int S,
                              int min_sep, double inv_temp, double* energy_out_dev, int32_t* count_out_dev, void* stream);
 
+/* Sparse-autoencoder features of the residual stream (csrc/sae.hip; esm_amd/sae.py).  For a captured representation row x
+ * (fp32 [E]):  u[e] = sub(mul(input_scale, x[e]), b_dec[e]) (two fp32 roundings, never fused);  z[f] = <w_enc[f], u> + b_enc[f];
+ * feature f is ACTIVE iff z[f] > threshold[f], threshold >= 0 (a NaN is never active, +inf is); its activation is z[f] if active,
+ * else 0.  The order everywhere is value descending, ties to the lower feature index; unused slots hold index -1 and value 0.
+ * The product runs through esmk_op_linear (ESMK_EPI_STORE_F32) over the f16x3 operand images: the activation image written
+ * here against the encoder image of esmk_op_split_weight_ex(parts = 3).  No entry uses a global atomic; every result is a
+ * function of its inputs alone.  n = 0 is allowed everywhere (nothing is launched).
+ * esmk_op_sae_rows: image fp16 [n, ld_image], row i = u of row rows[i] of x fp32 [N, ldx] (rows_dev int32 [n], clamped to
+ *   [0, N - 1]: device data; NULL: row i, n <= N) as hi | hi | lo per 64-column K tile, hi = fp16(u), lo = fp16(u - hi): the
+ *   layout esmk_op_layernorm_ex(x3 = 1) writes, 3 Ep columns with Ep = E rounded up to 64, pad columns zero; columns behind
+ *   3 Ep are not written.  b_dec_dev fp32 [E] or NULL (zeros).  |u| must stay inside fp16's range.
+ *   Refused: null x / image, E % 4, ldx < E or ldx % 4, ld_image < 3 Ep or ld_image % 4, a non-finite input_scale, n > N
+ *   without a list, x / b_dec not 16-byte aligned.
+ * esmk_op_sae_topk: one workgroup per row of z fp32 [n, ldz]: n_active[i] = the number of active features (k_sae > 0, a
+ *   top-k autoencoder that keeps k_sae features per row: min(k_sae, that number)), indices int32 [n, k] / values fp32 [n, k] =
+ *   the k best.  threshold_dev fp32 [F] or NULL (then the scalar `threshold`).  Rows with at most esmk_op_sae_cand() actives
+ *   are compacted into LDS and sorted there; rows with more go through a radix select over the row first (8-bit digits of the
+ *   64-bit key (value bits << 32) | (0xFFFFFFFF - index) from the high digit down) — path_dev int32 [n] or NULL receives 0 for
+ *   the first path and the number of digit passes for the second.  cutoff_dev uint64 [n] or NULL: the key of the k_sae-th
+ *   feature of a row with more than k_sae actives, else 0 (what esmk_op_sae_segment_max needs for a top-k autoencoder).
+ *   Refused: null pointers, F outside 4 .. 65536 or F % 4, k outside 1 .. 256, k_sae outside 0, k .. 256, ldz < F or ldz % 4,
+ *   a negative or NaN scalar threshold, z / threshold not 16-byte aligned.
+ * esmk_op_sae_segment_max: protein_max fp32 [B, F] / protein_argmax int32 [B, F] updated IN PLACE (the caller starts them at
+ *   0 / -1) from the chunk z fp32 [n, ldz] that holds rows row0 .. row0 + n of a row list; rows_dev int32 [n, 2] = the chunk's
+ *   (sequence, position) pairs, seg_start_dev int32 [B + 1] = sequence b owns rows seg_start[b] .. seg_start[b + 1] of the
+ *   WHOLE list.  One thread per (sequence, feature) walks the rows in order; a row replaces the stored value only if it is
+ *   strictly greater (the lowest position wins ties; chunks in order on one stream merge a split sequence correctly).
+ * esmk_op_sae_decode: out fp32 [n, E], out[e] = mul(inv_scale, b_dec[e] + sum over r = 0 .. k - 1 of mul(values[r],
+ *   w_dec[indices[r], e])), one rounded product and one rounded add per term in rank order; indices outside [0, F) are
+ *   skipped; w_dec fp32 [F, E], b_dec fp32 [E] or NULL (zeros). */
+int esmk_op_sae_cand(void);
+int esmk_op_sae_rows(const float* x_dev, int ldx, int N, const int32_t* rows_dev, int n, const float* b_dec_dev, float input_scale,
+                     void* image_dev, int ld_image, int E, void* stream);
+int esmk_op_sae_topk(const float* z_dev, int ldz, const float* threshold_dev, float threshold, int n, int F, int k, int k_sae,
+                     int32_t* indices_dev, float* values_dev, int32_t* n_active_dev, uint64_t* cutoff_dev, int32_t* path_dev,
+                     void* stream);
+int esmk_op_sae_segment_max(const float* z_dev, int ldz, const float* threshold_dev, float threshold, const uint64_t* cutoff_dev,
+                            const int32_t* rows_dev, const int32_t* seg_start_dev, int row0, int n, int F, int B,
+                            float* protein_max_dev, int32_t* protein_argmax_dev, void* stream);
+int esmk_op_sae_decode(const int32_t* indices_dev, const float* values_dev, int n, int k, const float* w_dec_dev,
+                       const float* b_dec_dev, float inv_scale, float* out_dev, int E, int F, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
