@@ -40,6 +40,11 @@ def __getattr__(name):
         import importlib
 
         return importlib.import_module(".sae_features", __name__)
+    if name in ("align", "align_embeddings", "alignment_strings"):  # esm_amd/align.py, also ``python -m esm_amd.align``
+        import importlib
+
+        module = importlib.import_module(".align", __name__)
+        return module if name == "align" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -132,6 +132,14 @@ SIGNATURES = {
     "esmk_op_sae_segment_max": (c_int, [c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                         c_void_p, c_void_p, c_void_p]),
     "esmk_op_sae_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p]),
+    # embedding-based alignment (csrc/align.hip): the two operand images, the z-score enhancement, the affine-gap DP, the walk
+    "esmk_op_align_panel": (c_int, []),
+    "esmk_op_align_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "esmk_op_align_enhance": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "esmk_op_align_dp": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "esmk_op_align_traceback": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
     # edits of the residual stream between layers: the handle's list, and one edit as a single op
     "esmk_set_stream_edits": (c_int, [c_void_p, POINTER(EsmkStreamEdit), c_int]),
     "esmk_op_stream_edit": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(EsmkStreamEdit), c_void_p, c_int, c_void_p, c_void_p,

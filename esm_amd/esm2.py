@@ -520,6 +520,14 @@ class ESM2(_EngineHost, nn.Module):
         return S.sae_features(self, tokens, sae, layer, top_k=top_k, positions=positions, varlen=varlen, protein_max=protein_max,
                               return_dense=return_dense, max_bytes=max_bytes)
 
+    # embedding-based alignment (esm_amd/align.py): similarity GEMM and affine-gap DP on the device
+    def align(self, tokens_a, tokens_b, layer=None, varlen=False, **kw):
+        """``esm_amd.align.align``: every sequence of ``tokens_a`` aligned against every sequence of ``tokens_b`` (or the listed
+        ``pairs``) on representation ``layer``: scores, end cells and, with ``paths``, the alignments' columns."""
+        from . import align as A
+
+        return A.align(self, tokens_a, tokens_b, layer=layer, varlen=varlen, **kw)
+
     def predict_contacts(self, tokens):
         """Reference esm2.py:146-147 returns ``self(tokens, return_contacts=True)["contacts"]``, which first builds
         the [B,L,H,T,T] attention tensor (2.8 GB per 1024-token sequence at 650M).  Only the map leaves this call, so

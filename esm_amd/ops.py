@@ -1437,3 +1437,96 @@ def sae_decode(indices, values, w_dec, b_dec=None, inv_scale=1.0, out=None):
         N.check(N.lib.esmk_op_sae_decode(N.ptr(indices), N.ptr(values), n, k, N.ptr(w_dec), N.ptr(b_dec), float(inv_scale),
                                          N.ptr(out), E, F, N.cur_stream()))
     return out
+
+
+# ---- embedding-based alignment (include/esmk.h: esmk_op_align_rows ... esmk_op_align_traceback) -----------------------------
+def align_panel():
+    """The columns one wavefront of the alignment DP covers at once (``kPanel`` of csrc/align.hip)."""
+    return int(N.lib.esmk_op_align_panel())
+
+
+def align_rows(x, rows=None, cosine=True, b_side=False, out=None, n=None):
+    """One of the two f16x3 operand images of the similarity GEMM (``esmk_op_align_rows``): x fp32 [N, E], rows int32 [n] or
+    None (the first ``n`` rows, default all; a negative index gives a zero row) -> fp16 [>= n, ld >= 3 Ep], ``hi | hi | lo`` per
+    64-column K tile, with ``b_side`` ``hi | lo | hi``; cosine: the rows are scaled to unit length first."""
+    _req_cuda(x, rows, out)
+    assert x.dtype == torch.float32 and x.dim() == 2
+    assert rows is None or (rows.dtype == torch.int32 and rows.dim() == 1)
+    Nr, E = x.shape
+    n = (Nr if rows is None else rows.numel()) if n is None else int(n)
+    assert rows is None or rows.numel() >= n
+    Ep = (E + 63) // 64 * 64
+    if out is None:
+        out = torch.empty((n, 3 * Ep), dtype=torch.float16, device=x.device)
+    assert out.dtype == torch.float16 and out.dim() == 2 and out.shape[0] >= n
+    N.check(N.lib.esmk_op_align_rows(N.ptr(x), E, Nr, N.ptr(rows if n else None), n, int(bool(cosine)), int(bool(b_side)),
+                                     N.ptr(out), out.shape[1], E, N.cur_stream()))
+    return out
+
+
+def _align_s(S, table, n_rows, n_cols):
+    _req_cuda(S, table)
+    assert S.dtype == torch.float32 and S.dim() == 2
+    assert table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 5
+    n_rows = S.shape[0] if n_rows is None else int(n_rows)
+    n_cols = S.shape[1] // 8 * 8 if n_cols is None else int(n_cols)
+    assert n_rows <= S.shape[0] and n_cols <= S.shape[1]
+    return n_rows, n_cols
+
+
+def align_enhance(S, table, max_lb, n_rows=None, n_cols=None, ws=None):
+    """``esmk_op_align_enhance``: the pair blocks of S fp32 [n_rows, ldS] that ``table`` (int64 [P, 5]) lists are replaced IN
+    PLACE by the mean of their row and column z-scores.  ``ws``: fp32 scratch of at least 2 max_lb floats, or allocated."""
+    n_rows, n_cols = _align_s(S, table, n_rows, n_cols)
+    P = table.shape[0]
+    if ws is None:
+        ws = torch.empty((max(min(P, 1024), 1) * 2 * int(max_lb),), dtype=torch.float32, device=S.device)
+    _req_cuda(ws)
+    assert ws.dtype == torch.float32
+    N.check(N.lib.esmk_op_align_enhance(N.ptr(S), S.shape[1], n_rows, n_cols, N.ptr(table), P, int(max_lb), N.ptr(ws), ws.numel(),
+                                        N.cur_stream()))
+    return S
+
+
+def align_dp(S, table, mode, gap_open, gap_extend, max_la, max_lb, want_traceback=True, tb=None, n_rows=None, n_cols=None, ws=None,
+             score=None, end=None):
+    """``esmk_op_align_dp``: per listed pair the affine-gap DP on its block of S -> dict(score fp32 [P], end int32 [P, 2]) and, with
+    ``want_traceback``, ``tb`` uint8 (the caller's, or allocated to hold what the table's offsets address — the table is then
+    read on the host).  mode 0 global, 1 local.  ``ws``: the boundary-column scratch a side b beyond ``align_panel()`` needs."""
+    n_rows, n_cols = _align_s(S, table, n_rows, n_cols)
+    P = table.shape[0]
+    dev = S.device
+    score = _out(score, (P,), torch.float32, dev)
+    end = _out(end, (P, 2), torch.int32, dev)
+    if want_traceback and tb is None:
+        t = table.cpu()
+        need = int((t[:, 4] + t[:, 1] * ((t[:, 3] + 15) // 16 * 16)).max()) if P else 0
+        tb = torch.zeros((max(need, 16),), dtype=torch.uint8, device=dev)
+    if int(max_lb) > align_panel() and ws is None:
+        ws = torch.empty((max(min(P, 16384), 1) * 2 * (int(max_la) + 1),), dtype=torch.float32, device=dev)
+    _req_cuda(tb, ws)
+    N.check(N.lib.esmk_op_align_dp(N.ptr(S), S.shape[1], n_rows, n_cols, N.ptr(table), P, int(mode), float(gap_open),
+                                   float(gap_extend), int(max_la), int(max_lb), N.ptr(score), N.ptr(end),
+                                   N.ptr(tb if want_traceback else None), tb.numel() if want_traceback else 0,
+                                   int(bool(want_traceback)), N.ptr(ws), 0 if ws is None else ws.numel(), N.cur_stream()))
+    out = dict(score=score, end=end)
+    if want_traceback:
+        out["tb"] = tb
+    return out
+
+
+def align_traceback(table, mode, end, tb, slot, cols, n_cols=None, n_match=None, start=None):
+    """``esmk_op_align_traceback``: walks the bytes of ``align_dp`` from ``end`` -> dict(n_cols, n_match int32 [P], start int32
+    [P, 2]); the columns go into the back of each pair's slot (first column ``slot[p]``, La + Lb long) of ``cols`` int32 [cap, 2]."""
+    _req_cuda(table, end, tb, slot, cols)
+    assert table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 5
+    assert end.dtype == torch.int32 and tb.dtype == torch.uint8 and slot.dtype == torch.int64 and cols.dtype == torch.int32
+    P = table.shape[0]
+    assert end.numel() == 2 * P and slot.numel() == P and cols.dim() == 2 and cols.shape[1] == 2
+    dev = table.device
+    n_cols = _out(n_cols, (P,), torch.int32, dev)
+    n_match = _out(n_match, (P,), torch.int32, dev)
+    start = _out(start, (P, 2), torch.int32, dev)
+    N.check(N.lib.esmk_op_align_traceback(N.ptr(table), P, int(mode), N.ptr(end), N.ptr(tb), tb.numel(), N.ptr(slot), N.ptr(cols),
+                                          cols.shape[0], N.ptr(n_cols), N.ptr(n_match), N.ptr(start), N.cur_stream()))
+    return dict(n_cols=n_cols, n_match=n_match, start=start)

@@ -1169,6 +1169,51 @@ int esmk_op_sae_segment_max(const float* z_dev, int ldz, const float* threshold_
 int esmk_op_sae_decode(const int32_t* indices_dev, const float* values_dev, int n, int k, const float* w_dec_dev,
                        const float* b_dec_dev, float inv_scale, float* out_dev, int E, int F, void* stream);
 
+/* Embedding-based alignment of two proteins (csrc/align.hip; esm_amd/align.py).  S[i][j] = <u_a[i], u_b[j]> is computed by
+ * esmk_op_linear (ESMK_EPI_STORE_F32) over the two images of esmk_op_align_rows; on S, per pair (i, j over 0 .. La x 0 .. Lb,
+ * fp32, H[0][0] = 0, E[i][0] = F[0][j] = -inf, max(x, y) = y if y > x else x, gap open o >= gap extend e >= 0):
+ *     E[i][j] = max(H[i][j-1] - o, E[i][j-1] - e)       bit 2 of the cell's byte iff E[i][j-1] - e > H[i][j-1] - o
+ *     F[i][j] = max(H[i-1][j] - o, F[i-1][j] - e)       bit 3, same rule
+ *     H[i][j] = the first of maximal value among [stop = 0 (local mode only; global starts from -inf), D = S[i-1][j-1] +
+ *               H[i-1][j-1], F[i][j], E[i][j]]           bits 0-1: 0, 1, 2, 3
+ * Global (mode 0): score H[La][Lb], end cell (La, Lb).  Local (mode 1): the largest H, the end cell the first such cell in
+ * row-major order; nothing above 0: score 0, end cell (0, 0).  No entry uses a global atomic; a pair's result does not depend
+ * on the other pairs of the launch.  n_pairs = 0 / n = 0 is allowed everywhere (nothing is launched).
+ * The pair table (int64 [n_pairs, 5], device data, every value clamped to the launch's buffers): first row of a in S, La,
+ *   first column of b in S (a multiple of 8; the 8-aligned columns behind Lb must exist: n_cols is a multiple of 8), Lb, the
+ *   pair's offset in the traceback buffer in bytes (a multiple of 8).  Byte (i, j), i, j >= 1, is at offset + (i - 1) * ld + j - 1
+ *   with ld = Lb rounded up to 16; bytes of the columns behind Lb are 0.
+ * esmk_op_align_panel: the columns a wavefront of the DP kernel covers at once; a longer side b goes panel by panel.
+ * esmk_op_align_rows: image fp16 [n, ld_image] of rows rows[i] of x fp32 [N, ldx] (device data: an index beyond N - 1 is
+ *   clamped, a NEGATIVE index writes a zero row; NULL: row i).  cosine = 1: u = x * r with r = float32(1 / sqrt(sum x^2)), the
+ *   sum in fp64 (thread t of 256 adds the squares of columns 4 t .. 4 t + 3, 4 t + 1024 .., ascending; the partial sums fold as
+ *   p[k] += p[k + s], s = 128, 64 .. 1), r = 0 for a zero row, the product rounded to fp32; cosine = 0: u = x (|x| < 65504).
+ *   b_side = 0: hi | hi | lo per 64-column K tile, b_side = 1: hi | lo | hi (what esmk_op_split_weight_ex(parts = 3) writes).
+ * esmk_op_align_enhance: in place, per pair block: S' = 0.5 ((S - mu_r[i]) inv_r[i] + (S - mu_c[j]) inv_c[j]), every operation
+ *   rounded to fp32; mu = float32(fp64 sum in ascending index order / n), sigma = float32(sqrt(fp64 sum of (S - m)^2, ascending,
+ *   / n)) with m the fp64 mean before rounding, inv = 1 / sigma in fp32, 0 where sigma = 0.  Pair blocks must not overlap.
+ *   ws_dev: at least 2 max_lb floats (more lets more workgroups run: up to 1024 x 2 max_lb); max_lb bounds every Lb.
+ * esmk_op_align_dp: score fp32 [n_pairs], end int32 [n_pairs, 2]; want_traceback = 1 also writes the bytes into tb_dev
+ *   (tb_bytes long), want_traceback = 0 touches no byte buffer.  max_la / max_lb (1 .. 8192) bound every pair's sides.  When
+ *   max_lb exceeds one panel, ws_dev must hold 2 (max_la + 1) floats per wavefront (at least one; up to 16384 are used).
+ *   Refused: null pointers, a side bound outside 1 .. 8192, e < 0, e > o, non-finite penalties, n_cols % 8, ldS < n_cols or
+ *   ldS % 4, S not 16-byte aligned, want_traceback without an 8-byte aligned buffer, a missing workspace.
+ * esmk_op_align_traceback: one thread per pair walks from end[p] and writes the columns — (i, j) a match, (i, -1) residue i of
+ *   a against a gap, (-1, j) — in ascending order into the BACK of the pair's slot of La + Lb columns: cols int32 [cols_cap, 2],
+ *   slot_dev int64 [n_pairs] the slots' first columns; n_cols, n_match int32 [n_pairs], start int32 [n_pairs, 2] the cell the
+ *   walk ended in.  At most La + Lb steps are taken whatever the bytes hold. */
+int esmk_op_align_panel(void);
+int esmk_op_align_rows(const float* x_dev, int ldx, int N, const int32_t* rows_dev, int n, int cosine, int b_side, void* image_dev,
+                       int ld_image, int E, void* stream);
+int esmk_op_align_enhance(float* S_dev, int ldS, int n_rows, int n_cols, const int64_t* table_dev, int n_pairs, int max_lb,
+                          float* ws_dev, long long ws_floats, void* stream);
+int esmk_op_align_dp(const float* S_dev, int ldS, int n_rows, int n_cols, const int64_t* table_dev, int n_pairs, int mode,
+                     float gap_open, float gap_extend, int max_la, int max_lb, float* score_dev, int32_t* end_dev, uint8_t* tb_dev,
+                     long long tb_bytes, int want_traceback, float* ws_dev, long long ws_floats, void* stream);
+int esmk_op_align_traceback(const int64_t* table_dev, int n_pairs, int mode, const int32_t* end_dev, const uint8_t* tb_dev,
+                            long long tb_bytes, const int64_t* slot_dev, int32_t* cols_dev, long long cols_cap, int32_t* n_cols_dev,
+                            int32_t* n_match_dev, int32_t* start_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
