@@ -45,6 +45,11 @@ def __getattr__(name):
 
         module = importlib.import_module(".align", __name__)
         return module if name == "align" else getattr(module, name)
+    if name in ("search", "EmbeddingIndex", "search_and_align"):  # esm_amd/search.py, also ``python -m esm_amd.search``
+        import importlib
+
+        module = importlib.import_module(".search", __name__)
+        return module if name == "search" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -140,6 +140,11 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "esmk_op_align_traceback": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
+    # protein search on pooled embeddings (csrc/search.hip): the per-protein mean, the streaming top-k
+    "esmk_op_pool_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "esmk_op_topk_merge": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    # early exit: the handle's layer limit
+    "esmk_set_layer_limit": (c_int, [c_void_p, c_int]),
     # edits of the residual stream between layers: the handle's list, and one edit as a single op
     "esmk_set_stream_edits": (c_int, [c_void_p, POINTER(EsmkStreamEdit), c_int]),
     "esmk_op_stream_edit": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(EsmkStreamEdit), c_void_p, c_int, c_void_p, c_void_p,

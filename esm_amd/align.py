@@ -26,8 +26,8 @@ A gap of k residues costs o + (k - 1) e.  ``mode="global"``: the score is H[La][
 the first such cell in row-major order, the walk back ending at the first stop; nothing above 0: score 0, an empty alignment.
 The defaults o = 1.0, e = 0.1 are this project's choice for cosine similarities in [-1, 1]; they are not tuned on any benchmark.
 
-Not built: the MSA Transformer, windows (``window=``), a prefilter on pooled embeddings, semiglobal (free end gap) alignment,
-more than the one best local path per pair.
+Not built: the MSA Transformer, windows (``window=``), semiglobal (free end gap) alignment, more than the one best local path
+per pair.  The prefilter on pooled embeddings is esm_amd/search.py.
 """
 import numpy as np
 import torch

@@ -657,6 +657,18 @@ int check_forward(const ForwardCall& c, Workspace* w) {
     if (want_contacts && !c.contacts) return fail(who + ": contacts buffer missing");
     for (int i = 0; i < c.n_repr; ++i)
         if (c.repr_layers[i] < 0 || c.repr_layers[i] > m->L || !c.repr_out[i]) return fail(who + ": bad repr layer request");
+    if (m->layer_limit > 0) {  // early exit: nothing above the last layer that runs can be asked for
+        const std::string lim = ": a layer limit of " + std::to_string(m->layer_limit) + " is set (esmk_set_layer_limit): ";
+        if (c.rs || c.ps || (c.pc && c.pc->maps)) return fail(who + lim + "this entry needs the whole stack");
+        if (c.flags & ESMK_OUT_LOGITS) return fail(who + lim + "ESMK_OUT_LOGITS needs the whole stack");
+        if (c.flags & (ESMK_OUT_ATTN | ESMK_OUT_ATTN_LOWP)) return fail(who + lim + "ESMK_OUT_ATTN / ESMK_OUT_ATTN_LOWP need the whole stack");
+        if (c.flags & ESMK_OUT_CONTACTS) return fail(who + lim + "ESMK_OUT_CONTACTS needs the whole stack");
+        for (int i = 0; i < c.n_repr; ++i)
+            if (c.repr_layers[i] > m->layer_limit)
+                return fail(who + lim + "representation " + std::to_string(c.repr_layers[i]) + " is above it");
+        for (const esmk_stream_edit& e : m->edits)
+            if (e.layer > m->layer_limit) return fail(who + lim + "a stream edit at layer " + std::to_string(e.layer) + " is above it");
+    }
     *w = plan_workspace(m, c.B, c.T, c.flags, c.pc ? c.pc->n_seg : 0, c.pc ? c.pc->ct : nullptr, c.pc && c.pc->maps, c.ct_G);
     if (c.workspace_bytes < w->total) return fail(who + ": workspace too small");
     return 0;
@@ -1075,7 +1087,10 @@ int forward_impl(const ForwardCall& c) {
     if (embed_stage(f)) return 1;
     if (stream_edit_stage(f, 0)) return 1;
     if (f.s.repr_copy(0, f.x, f.repr_lowp)) return 1;  // esm2.py:99-100
-    for (int l = 0; l < f.L; ++l) {  // esm2.py:111-121 -> modules.py:120-142
+    // early exit (esmk_set_layer_limit): the stack ends after `layers` layers; with the fold the last residual epilogue still
+    // emits the next layer's operand rows, which nothing reads
+    const int layers = f.m->layer_limit > 0 ? f.m->layer_limit : f.L;
+    for (int l = 0; l < layers; ++l) {  // esm2.py:111-121 -> modules.py:120-142
         const LayerOff& o = f.m->layer[l];
         if (c.ps) {  // the layer's q, k and lse stay: slot l of the stash (pair_head.hip reads all of them after the last layer)
             f.q = f.ws + c.ps->q + (size_t)l * c.ps->qk_layer;
@@ -1090,6 +1105,7 @@ int forward_impl(const ForwardCall& c) {
         // esm2.py:117-118; ESM-1: layer L too (no final LayerNorm)
         if ((l + 1 < f.L || f.esm1) && f.s.repr_copy(l + 1, f.x, f.repr_lowp)) return 1;
     }
+    if (layers < f.L) return 0;  // (check_forward: no head, map or contact output is asked for under a limit)
     if (head_stage(f)) return 1;
     if (c.ps) return pair_head_final(f);
     return contacts_final(f);
@@ -1397,6 +1413,17 @@ int esmk_set_stream_edits(esmk_model* m, const esmk_stream_edit* edits, int n) {
     for (int i = 0; i < n; ++i)
         if (check_stream_edit("esmk_set_stream_edits: edit " + std::to_string(i), edits[i], m->E, m->L)) return 1;
     m->edits.assign(edits, edits + n);  // (a refused list leaves the edits that were set)
+    return 0;
+}
+
+int esmk_set_layer_limit(esmk_model* m, int n_layers) {
+    if (!m) return fail("esmk_set_layer_limit: null model");
+    if (m->is_msa)
+        return fail("esmk_set_layer_limit: MSA handle (the early exit is built for the ESM-2 / ESM-1b / ESM-1 stack; the esmk_msa_* "
+                    "entries run the whole stack)");
+    if (n_layers < 0 || n_layers > m->L)
+        return fail("esmk_set_layer_limit: n_layers must be 0 (the whole stack) .. " + std::to_string(m->L));
+    m->layer_limit = n_layers == m->L ? 0 : n_layers;
     return 0;
 }
 
@@ -1719,6 +1746,9 @@ int esmk_forward_packed_maps(esmk_model* m, const void* packed_dev, const int64_
     if (check_packed("esmk_forward_packed_maps", m, segments_host, n_seg, rows, out_flags, kPackedExFlags | kMapFlags,
                      kPackedMapsOnly, &pc, &ct))
         return 1;
+    if (m->layer_limit > 0)
+        return fail("esmk_forward_packed_maps: a layer limit of " + std::to_string(m->layer_limit) +
+                    " is set (esmk_set_layer_limit): this entry needs the whole stack");
     if (pc.maps) {
         if (!attn_out_dev) return fail("esmk_forward_packed_maps: attention buffer missing");
         // sum(len^2) <= rows^2 <= 2^48 (check_seg_table): the product with L H stays inside 64 bits

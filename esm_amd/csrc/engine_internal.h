@@ -105,6 +105,8 @@ struct esmk_model {
     int unit_cap = 0;
     // edits of the residual stream between layers (esmk_set_stream_edits): copied descriptors, borrowed device pointers
     std::vector<esmk_stream_edit> edits;
+    // early exit (esmk_set_layer_limit): 0 < layer_limit < L stops the forward after that many layers; 0: the whole stack
+    int layer_limit = 0;
     // linear pairwise head on the attention maps (esmk_set_pair_head): device copies, w64 [L*H][64] (columns past the head's
     // outputs zero), bias [n_sym + n_asym]; both counts 0: no head
     float* d_pair_w64 = nullptr;

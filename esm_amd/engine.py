@@ -331,6 +331,11 @@ class Esm2Engine(Engine):
             N.check(N.lib.esmk_set_stream_edits(self.handle, None if edits is None else edits.array, 0 if edits is None else edits.n))
         self.edits = edits
 
+    def set_layer_limit(self, n):
+        """``esmk_set_layer_limit``: the forwards of the handle stop after ``n`` layers; 0 (or L): the whole stack."""
+        N = self.N
+        N.check(N.lib.esmk_set_layer_limit(self.handle, int(n)))
+
     def _no_edits(self, what):
         if self.edits is not None:
             from .interventions import _NOT_BUILT

@@ -528,6 +528,26 @@ class ESM2(_EngineHost, nn.Module):
 
         return A.align(self, tokens_a, tokens_b, layer=layer, varlen=varlen, **kw)
 
+    # protein search on pooled embeddings (esm_amd/search.py): early layer exit, per-protein mean, streaming cosine top-k
+    def embed_layer(self, tokens, layer=None, varlen=False, window=None):
+        """``esm_amd.search.embed_layer``: fp32 [B, T, E], representation ``layer`` (None: the last) as ``forward`` (with
+        ``varlen``: ``forward_varlen``) returns it, bit for bit — from a forward that runs only the layers below it."""
+        from . import search
+
+        return search.embed_layer(self, tokens, layer=layer, varlen=varlen, window=window)
+
+    def pool(self, tokens, layer=None, varlen=False, window=None):
+        """``esm_amd.search.pool``: fp32 [B, E], the mean of every sequence's residue rows of representation ``layer``."""
+        from . import search
+
+        return search.pool(self, tokens, layer=layer, varlen=varlen, window=window)
+
+    def search(self, index, tokens, top_k, varlen=False, **kw):
+        """``esm_amd.search.search``: ``pool`` on ``tokens`` at the index's layer, then ``index.search``."""
+        from . import search
+
+        return search.search(self, index, tokens, top_k, varlen=varlen, **kw)
+
     def predict_contacts(self, tokens):
         """Reference esm2.py:146-147 returns ``self(tokens, return_contacts=True)["contacts"]``, which first builds
         the [B,L,H,T,T] attention tensor (2.8 GB per 1024-token sequence at 650M).  Only the map leaves this call, so

@@ -210,6 +210,13 @@ class MSATransformer(_EngineHost, nn.Module):
 
     forward_edited = stream_edits
 
+    def embed_layer(self, *args, **kwargs):
+        from . import search
+
+        search.check_model(self, None)  # NotImplementedError: the early exit and the pooled index run single sequences
+
+    pool = search = embed_layer
+
     # Variant scoring of one MSA (esm_amd/msa_scoring.py over esmk_msa_forward_rows): an MSA plus a query row is another
     # argument shape than a batch of sequences, hence names of their own; the single-sequence names above keep refusing
     def msa_forward_rows(self, tokens, sel_rows, return_logits=False):

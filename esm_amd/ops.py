@@ -1530,3 +1530,47 @@ def align_traceback(table, mode, end, tb, slot, cols, n_cols=None, n_match=None,
     N.check(N.lib.esmk_op_align_traceback(N.ptr(table), P, int(mode), N.ptr(end), N.ptr(tb), tb.numel(), N.ptr(slot), N.ptr(cols),
                                           cols.shape[0], N.ptr(n_cols), N.ptr(n_match), N.ptr(start), N.cur_stream()))
     return dict(n_cols=n_cols, n_match=n_match, start=start)
+
+
+# ---- protein search on pooled embeddings (include/esmk.h: esmk_op_pool_rows, esmk_op_topk_merge) ----------------------------
+def pool_rows(x, rows, seg_off, out=None):
+    """The mean of listed rows per segment (``esmk_op_pool_rows``): x fp32 [N, ldx >= E], rows int32 [n] or None (row r is list
+    entry r), seg_off int32 [n_seg + 1] the segments' ranges in the list -> fp32 [n_seg, E]; the sum in fp64 in list order, an
+    empty segment gives a zero row.  ``out``'s width is E (default: x's)."""
+    _req_cuda(rows, seg_off, out)
+    if not x.is_cuda:
+        raise RuntimeError("esm_amd.ops: tensors must live on the GPU (no CPU fallback)")
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1  # (rows may be wider than E: ldx is the row stride)
+    assert rows is None or (rows.dtype == torch.int32 and rows.dim() == 1 and rows.is_contiguous())
+    assert seg_off.dtype == torch.int32 and seg_off.dim() == 1 and seg_off.numel() >= 1 and seg_off.is_contiguous()
+    n_seg = seg_off.numel() - 1
+    if out is None:
+        out = torch.empty((n_seg, x.shape[1]), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 2 and out.shape[0] == n_seg
+    N.check(N.lib.esmk_op_pool_rows(N.ptr(x), x.stride(0), x.shape[0], N.ptr(rows), N.ptr(seg_off), n_seg, N.ptr(out), out.shape[1],
+                                    N.cur_stream()))
+    return out
+
+
+def topk_merge(S, k, values=None, ids=None, n_cols=None, id_base=0, exclude=None, first=True, n_rows=None):
+    """One block of a streaming row-wise top-k (``esmk_op_topk_merge``): S fp32 [n_rows, ldS] of which the first ``n_cols``
+    columns are candidates (value, id_base + column); NaN values and the column whose id is ``exclude[row]`` (int32 [n_rows]) are
+    none.  Unless ``first``, the used slots of the running lists ``values`` fp32 / ``ids`` int32 [n_rows, k] are candidates too.
+    The lists receive the k best, value descending (IEEE total order), then id ascending; unused slots hold (-inf, -1)."""
+    _req_cuda(values, ids, exclude)
+    if not S.is_cuda:
+        raise RuntimeError("esm_amd.ops: tensors must live on the GPU (no CPU fallback)")
+    assert S.dtype == torch.float32 and S.dim() == 2 and S.stride(1) == 1  # (a view of wider rows: ldS is the row stride)
+    n_rows = S.shape[0] if n_rows is None else int(n_rows)
+    n_cols = S.shape[1] if n_cols is None else int(n_cols)
+    assert n_rows <= S.shape[0] and n_cols <= S.shape[1]
+    if values is None:
+        assert first, "topk_merge: a running list is needed unless first"
+        values = torch.empty((n_rows, int(k)), dtype=torch.float32, device=S.device)
+        ids = torch.empty((n_rows, int(k)), dtype=torch.int32, device=S.device)
+    assert values.dtype == torch.float32 and ids.dtype == torch.int32 and values.is_contiguous() and ids.is_contiguous()
+    assert tuple(values.shape) == (n_rows, int(k)) and tuple(ids.shape) == (n_rows, int(k))
+    assert exclude is None or (exclude.dtype == torch.int32 and exclude.is_contiguous() and exclude.numel() >= n_rows)
+    N.check(N.lib.esmk_op_topk_merge(N.ptr(S), S.stride(0), n_rows, n_cols, int(id_base), N.ptr(exclude), int(k), N.ptr(values),
+                                     N.ptr(ids), int(bool(first)), N.cur_stream()))
+    return values, ids

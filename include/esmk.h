@@ -295,6 +295,16 @@ typedef struct esmk_stream_edit {
     const int32_t* src_index_dev;
 } esmk_stream_edit;
 int esmk_set_stream_edits(esmk_model* m, const esmk_stream_edit* edits, int n);
+/* Early exit: state of the handle, like the edits.  n_layers = 0 or L: the whole stack (the default; a fresh handle behaves as
+ * before).  With 0 < n < L, esmk_forward, esmk_forward_packed and esmk_forward_packed_ex run the embedding stage, layers
+ * 0 .. n - 1 with the stream edits and the representation copies of layers 0 .. n, and return: no final LayerNorm, no head, no
+ * map and no contact stage.  Representation k <= n carries the bits the whole forward gives it.  With the LayerNorm fold the
+ * last residual epilogue still emits the operand rows of layer n, which nothing reads.  Workspace sizes do not change.
+ * Refused by name before any HIP call while such a limit is set: ESMK_OUT_LOGITS, ESMK_OUT_ATTN, ESMK_OUT_ATTN_LOWP,
+ * ESMK_OUT_CONTACTS, a repr_layers entry above n, a held stream edit at a layer above n, and the entries esmk_forward_rows,
+ * _rows_contacts, _rows_pair, _packed_rows and _packed_maps.  esmk_set_layer_limit itself refuses an MSA handle and n outside
+ * 0 .. L (the limit that was set stays). */
+int esmk_set_layer_limit(esmk_model* m, int n_layers);
 /* One edit as a single op on x fp32 [N,E] in place (tokens_dev int64 [N], read under the token selector only), with the fold
  * outputs when y_dev is given: y[row][c] = T(x' - mean) (operand dtype, row stride ldy >= E; columns [E, ldy) are not
  * written), mean[row], rstd[row] — the bits esmk_op_rowstats gives on x'.  Rows that are not selected are neither read nor
@@ -1213,6 +1223,31 @@ int esmk_op_align_dp(const float* S_dev, int ldS, int n_rows, int n_cols, const 
 int esmk_op_align_traceback(const int64_t* table_dev, int n_pairs, int mode, const int32_t* end_dev, const uint8_t* tb_dev,
                             long long tb_bytes, const int64_t* slot_dev, int32_t* cols_dev, long long cols_cap, int32_t* n_cols_dev,
                             int32_t* n_match_dev, int32_t* start_dev, void* stream);
+
+/* Protein search on pooled embeddings (csrc/search.hip; esm_amd/search.py): one vector per protein, a cosine top-k against a
+ * database of such vectors, the aligner above on the survivors.  The similarities are esmk_op_linear (ESMK_EPI_STORE_F32) over
+ * the two cosine images of esmk_op_align_rows, block of database rows by block.  No entry uses a global atomic; a segment's /
+ * a row's result does not depend on the other segments / rows of the launch.
+ * esmk_op_pool_rows: out fp32 [n_seg, E]; out[s][e] = float32(sum / count), sum the fp64 sum of x[rows[r]][e] over
+ *   r = seg_off[s] .. seg_off[s + 1] - 1 in ascending r, count the number of those r; an empty segment gives a zero row
+ *   (esmk_op_align_rows turns a zero row into a zero unit vector), not NaN.  x fp32 [N, ldx]; rows int32, the list (NULL: list
+ *   entry r is row r), seg_off int32 [n_seg + 1]; both are device data: a row index is clamped to [0, N - 1], an offset to
+ *   [0, seg_off[n_seg]] and to its predecessor.  E % 4 == 0, ldx >= E and ldx % 4 == 0, x and out 16-byte aligned.  A
+ *   protein's vector is a function of its own rows in list order, and the engine's rows are the same bits alone, padded and
+ *   token-packed: an index does not depend on how it was batched.
+ * esmk_op_topk_merge: one block of a streaming top-k.  Per row q the candidates are (S[q][j], id_base + j) for j < n_cols,
+ *   except a NaN value and the column with id_base + j == exclude[q] (exclude int32 [n_rows] or NULL), and, unless first != 0,
+ *   the used slots (id >= 0) of the running list val fp32 / id int32 [n_rows, k], whose ids the caller keeps disjoint from the
+ *   block's.  The list receives the k best under value descending, then id ascending; values compare in the total order of
+ *   their IEEE bits (-0.0 below +0.0; -inf is a value like any other); unused slots hold (-inf, -1) and stand behind every real
+ *   candidate.  Columns at or behind n_cols are never candidates (the float4 group that holds column n_cols - 1 is loaded
+ *   whole: ldS % 4 == 0).  first != 0 reads nothing of the lists.  One workgroup per row, one read of the row.
+ *   Refused: null S or lists, k outside 1 .. 1024, n_cols outside 1 .. 2^22, ldS < n_cols or ldS % 4, id_base < 0 or
+ *   id_base + n_cols > 2^31 - 1, S not 16-byte aligned, n_rows outside 0 .. 2^24 (0: nothing is launched). */
+int esmk_op_pool_rows(const float* x_dev, int ldx, int N, const int32_t* rows_dev, const int32_t* seg_off_dev, int n_seg,
+                      float* out_dev, int E, void* stream);
+int esmk_op_topk_merge(const float* S_dev, int ldS, int n_rows, int n_cols, int id_base, const int32_t* exclude_dev, int k,
+                       float* val_dev, int32_t* id_dev, int first, void* stream);
 
 #ifdef __cplusplus
 }
