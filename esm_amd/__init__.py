@@ -50,6 +50,11 @@ def __getattr__(name):
 
         module = importlib.import_module(".search", __name__)
         return module if name == "search" else getattr(module, name)
+    if name in ("cluster", "cluster_embeddings"):  # esm_amd/cluster.py, also ``python -m esm_amd.cluster``
+        import importlib
+
+        module = importlib.import_module(".cluster", __name__)
+        return module if name == "cluster" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

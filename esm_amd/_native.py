@@ -143,6 +143,13 @@ SIGNATURES = {
     # protein search on pooled embeddings (csrc/search.hip): the per-protein mean, the streaming top-k
     "esmk_op_pool_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "esmk_op_topk_merge": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    # range search and greedy clustering (csrc/cluster.hip): the thresholded row scan (count / fill), the rounds, the assignment
+    "esmk_op_range_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_int64, c_void_p]),
+    "esmk_op_cluster_mark": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "esmk_op_cluster_decide": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "esmk_op_cluster_assign": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                       c_void_p]),
     # early exit: the handle's layer limit
     "esmk_set_layer_limit": (c_int, [c_void_p, c_int]),
     # edits of the residual stream between layers: the handle's list, and one edit as a single op

@@ -1574,3 +1574,83 @@ def topk_merge(S, k, values=None, ids=None, n_cols=None, id_base=0, exclude=None
     N.check(N.lib.esmk_op_topk_merge(N.ptr(S), S.stride(0), n_rows, n_cols, int(id_base), N.ptr(exclude), int(k), N.ptr(values),
                                      N.ptr(ids), int(bool(first)), N.cur_stream()))
     return values, ids
+
+
+# ---- range search and greedy clustering (include/esmk.h: esmk_op_range_rows, esmk_op_cluster_mark / _decide / _assign) ------
+def range_rows(S, threshold, counts=None, offsets=None, cursor=None, ids=None, scores=None, n_cols=None, id_base=0, exclude=None,
+               n_rows=None):
+    """One block of a thresholded row scan (``esmk_op_range_rows``): S fp32 [n_rows, ldS]; column j < ``n_cols`` of row q passes
+    when ``S[q][j] >= threshold`` (a float comparison) and ``id_base + j != exclude[q]``.  With ``counts`` (int64 [n_rows]) the
+    count pass: the passing columns of every row are added to it.  With ``offsets`` (int64 [n_rows + 1]), ``cursor`` (int64
+    [n_rows]), ``ids`` (int32 [cap]) and ``scores`` (fp32 [cap]) the fill pass: row q's passing (id, score) pairs go, in
+    ascending column order, behind ``cursor[q]``, which advances; nothing is written at or behind ``offsets[q + 1]``."""
+    _req_cuda(counts, offsets, cursor, ids, scores, exclude)
+    if not S.is_cuda:
+        raise RuntimeError("esm_amd.ops: tensors must live on the GPU (no CPU fallback)")
+    assert S.dtype == torch.float32 and S.dim() == 2 and S.stride(1) == 1  # (a view of wider rows: ldS is the row stride)
+    n_rows = S.shape[0] if n_rows is None else int(n_rows)
+    n_cols = S.shape[1] if n_cols is None else int(n_cols)
+    assert n_rows <= S.shape[0] and n_cols <= S.shape[1]
+    fill = counts is None
+    if fill:
+        assert offsets is not None and cursor is not None and ids is not None and scores is not None, "range_rows: counts, or the four fill arrays"
+        assert offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.numel() >= n_rows + 1
+        assert cursor.dtype == torch.int64 and cursor.is_contiguous() and cursor.numel() >= n_rows
+        assert ids.dtype == torch.int32 and scores.dtype == torch.float32 and ids.is_contiguous() and scores.is_contiguous()
+        assert ids.dim() == 1 and ids.numel() == scores.numel()
+    else:
+        assert offsets is None and cursor is None and ids is None and scores is None, "range_rows: counts, or the four fill arrays"
+        assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() >= n_rows
+    assert exclude is None or (exclude.dtype == torch.int32 and exclude.is_contiguous() and exclude.numel() >= n_rows)
+    N.check(N.lib.esmk_op_range_rows(N.ptr(S), S.stride(0), n_rows, n_cols, int(id_base), N.ptr(exclude), float(threshold), int(fill),
+                                     N.ptr(counts), N.ptr(offsets), N.ptr(cursor), N.ptr(ids), N.ptr(scores),
+                                     ids.numel() if fill else 0, N.cur_stream()))
+    return cursor if fill else counts
+
+
+def _req_graph(offsets, ids, rank, state):
+    _req_cuda(offsets, ids, rank, state)
+    n = rank.numel()
+    assert offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.numel() == n + 1
+    assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.dim() == 1
+    assert rank.dtype == torch.int32 and rank.is_contiguous() and state.dtype == torch.int32 and state.is_contiguous() and state.numel() == n
+    return n
+
+
+def cluster_mark(offsets, ids, rank, state, blocked, covered, lanes=64):
+    """The mark launch of a clustering round (``esmk_op_cluster_mark``) on the CSR ``offsets`` int64 [n + 1] / ``ids`` int32
+    [nnz]: an undecided u (state 0) sets ``blocked[w]``, a new representative u (state 1) sets ``covered[w]``, for every w of
+    its out-list with ``rank[w] > rank[u]``.  ``lanes`` consecutive lanes walk one out-list."""
+    n = _req_graph(offsets, ids, rank, state)
+    _req_cuda(blocked, covered)
+    for t in (blocked, covered):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n
+    N.check(N.lib.esmk_op_cluster_mark(N.ptr(offsets), N.ptr(ids), n, ids.numel(), N.ptr(rank), N.ptr(state), N.ptr(blocked),
+                                       N.ptr(covered), int(lanes), N.cur_stream()))
+
+
+def cluster_decide(state, blocked, covered, remaining):
+    """The decide launch of a clustering round (``esmk_op_cluster_decide``): state 1 -> 2; an undecided node becomes covered (3)
+    if ``covered`` is set, a new representative (1) unless ``blocked`` is; ``blocked`` is cleared; the nodes left undecided are
+    added to ``remaining`` (int32 [1])."""
+    _req_cuda(state, blocked, covered, remaining)
+    n = state.numel()
+    for t in (state, blocked, covered):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n
+    assert remaining.dtype == torch.int32 and remaining.numel() >= 1
+    N.check(N.lib.esmk_op_cluster_decide(N.ptr(state), N.ptr(blocked), N.ptr(covered), n, N.ptr(remaining), N.cur_stream()))
+
+
+def cluster_assign(offsets, ids, scores, rank, state, nearest, key=None, lanes=64):
+    """The assignment (``esmk_op_cluster_assign``): key int64 [n] (the bits of a uint64; zeroed here unless given) receives per
+    node the maximum of ``[order(score) or 0] << 32 | 0xFFFFFFFF - rank[u]`` over the representatives u that list it and
+    rank before it.  0 stays where no representative does."""
+    n = _req_graph(offsets, ids, rank, state)
+    _req_cuda(scores, key)
+    assert scores is None or (scores.dtype == torch.float32 and scores.is_contiguous() and scores.numel() == ids.numel())
+    if key is None:
+        key = torch.zeros((n,), dtype=torch.int64, device=rank.device)
+    assert key.dtype == torch.int64 and key.is_contiguous() and key.numel() == n
+    N.check(N.lib.esmk_op_cluster_assign(N.ptr(offsets), N.ptr(ids), N.ptr(scores), n, ids.numel(), N.ptr(rank), N.ptr(state),
+                                         int(bool(nearest)), N.ptr(key), int(lanes), N.cur_stream()))
+    return key

@@ -5,7 +5,7 @@
     hits = model.search(index, tokens, top_k=100)                                  # scores fp32 [Q, k], ids int32 [Q, k]
     out = esm_amd.search_and_align(model, alphabet, queries, index, top_k=100, align_top=10, mode="local")
 
-    python -m esm_amd.search index --model-location M --fasta DB.fasta [--layer K] [--no-sequences] --output db.npz
+    python -m esm_amd.search index --model-location M --fasta DB.fasta [--layer K] [--no-sequences] [--center] --output db.npz
     python -m esm_amd.search query --model-location M --index db.npz --query Q.fasta --top N [--align ...] --output hits.tsv
 
 Definition (tests/_search_ref.py restates it in numpy, and the kernels reproduce that bit for bit).
@@ -20,7 +20,13 @@ candidate; the database is walked in blocks of ``Nb`` vectors, one GEMM into an 
 ``model.embed_layer`` runs only the layers below the representation (``esmk_set_layer_limit``): building an index of a
 mid-stack layer costs that share of the forward.
 
-Not built: a centred / whitened index, a 16-bit-only image at a third of the memory, a host-streamed or multi-GPU sharded index,
+A centred index (``index.centered()``, ``index --center``) holds ``center`` fp32 [E], the database mean — per column the fp64 sum
+of the vectors in ascending id, divided by N, rounded once — and vectors with it subtracted (one fp32 subtraction); ``search``
+and ``range_search`` subtract it from fp32 queries before the unit scaling.  Raw mean vectors of a language model share a large
+common component, so their cosines are high between unrelated proteins; thresholds (``range_search``, ``cluster``:
+esm_amd/cluster.py) only mean something on a centred index.
+
+Not built: a whitened index, a 16-bit-only image at a third of the memory, a host-streamed or multi-GPU sharded index,
 IVF / quantised search, the MSA Transformer, windows (``window=``).
 """
 import json
@@ -175,7 +181,10 @@ class EmbeddingIndex:
 
     META_KEYS = ("layer", "pooling", "num_layers", "embed_dim", "model")
 
-    def __init__(self, vectors, labels, lengths, sequences=None, meta=None):
+    def __init__(self, vectors, labels, lengths, sequences=None, meta=None, center=None):
+        if isinstance(center, torch.Tensor):
+            center = center.detach().to("cpu", torch.float32).numpy()
+        self.center = None if center is None else np.ascontiguousarray(center, dtype=np.float32).reshape(-1)  # already subtracted
         if isinstance(vectors, torch.Tensor):
             vectors = vectors.detach().to("cpu", torch.float32).numpy()
         self.vectors = np.ascontiguousarray(vectors, dtype=np.float32)
@@ -184,6 +193,8 @@ class EmbeddingIndex:
         if self.vectors.shape[1] % 4 != 0:
             raise ValueError(f"EmbeddingIndex: E = {self.vectors.shape[1]} must be a multiple of 4")
         n = self.vectors.shape[0]
+        if self.center is not None and self.center.shape[0] != self.vectors.shape[1]:
+            raise ValueError(f"EmbeddingIndex: center has {self.center.shape[0]} entries, the vectors have E = {self.vectors.shape[1]}")
         self.labels = [str(s) for s in labels]
         self.lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
         self.sequences = None if sequences is None else [str(s) for s in sequences]
@@ -205,11 +216,14 @@ class EmbeddingIndex:
 
     # -- files
     def save(self, path):
-        """An .npz of plain arrays (no pickle): vectors, labels, lengths, meta as JSON and, if held, the sequences."""
+        """An .npz of plain arrays (no pickle): vectors, labels, lengths, meta as JSON and, if held, the sequences and the
+        center."""
         arrays = dict(vectors=self.vectors, labels=np.array(self.labels, dtype=np.str_), lengths=self.lengths,
                       meta=np.array(json.dumps(self.meta), dtype=np.str_))
         if self.sequences is not None:
             arrays["sequences"] = np.array(self.sequences, dtype=np.str_)
+        if self.center is not None:
+            arrays["center"] = self.center
         with open(path, "wb") as fh:
             np.savez(fh, **arrays)
 
@@ -221,7 +235,20 @@ class EmbeddingIndex:
             if missing:
                 raise ValueError(f"EmbeddingIndex.load: {path} has no array {missing[0]!r}")
             seqs = z["sequences"].tolist() if "sequences" in z.files else None
-            return cls(z["vectors"], z["labels"].tolist(), z["lengths"], seqs, json.loads(str(z["meta"])))
+            center = z["center"] if "center" in z.files else None
+            return cls(z["vectors"], z["labels"].tolist(), z["lengths"], seqs, json.loads(str(z["meta"])), center)
+
+    def centered(self):
+        """A new index on the host with the database mean subtracted (module docstring): ``center[e]`` is the fp64 sum of
+        ``vectors[i][e]`` in ascending i, divided by N and rounded once to fp32; every vector loses it in one fp32
+        subtraction.  Labels, lengths, sequences and meta are carried over.  An index that is centred already is a ValueError."""
+        if self.center is not None:
+            raise ValueError("EmbeddingIndex.centered: the index is centred already")
+        acc = np.zeros((self.vectors.shape[1],), dtype=np.float64)
+        for row in self.vectors:  # one addition per vector: ascending order (np.sum would add pairwise)
+            acc += row
+        center = (acc / np.float64(len(self))).astype(np.float32)
+        return EmbeddingIndex(self.vectors - center, self.labels, self.lengths, self.sequences, self.meta, center)
 
     # -- building
     @classmethod
@@ -275,53 +302,134 @@ class EmbeddingIndex:
         self.image = image
         return self
 
+    def _query_vectors(self, queries, what):
+        """(queries as an [Q, E] tensor, whether the center still has to be subtracted).  Another index brings vectors that
+        are centred already: it must hold this index's center, or none while this one holds none."""
+        subtract = self.center is not None
+        if isinstance(queries, EmbeddingIndex):
+            if (queries.center is None) != (self.center is None) or (subtract and not np.array_equal(queries.center, self.center)):
+                raise ValueError(f"{what}: the query index and the database index do not hold the same center "
+                                 f"(query: {'none' if queries.center is None else 'one'}, database: "
+                                 f"{'none' if self.center is None else 'one'}); center both on one vector, or neither")
+            queries, subtract = torch.from_numpy(queries.vectors), False
+        if not isinstance(queries, torch.Tensor) or queries.dim() != 2:
+            raise ValueError(f"{what}: queries must be an fp32 [Q, E] tensor or an EmbeddingIndex")
+        E = self.vectors.shape[1]
+        if queries.shape[1] != E:
+            raise ValueError(f"{what}: queries have E = {queries.shape[1]}, the index has E = {E}")
+        return queries, subtract
+
+    def _query_rows(self, queries, subtract, dev):
+        """fp32 [Q, E] on the device, the center subtracted (one fp32 subtraction) where the index holds one."""
+        q = queries.detach().to(dev, torch.float32).contiguous()
+        return q - torch.from_numpy(self.center).to(dev) if subtract else q
+
+    def _similarity_blocks(self, img_q, Q, max_bytes):
+        """Yields (q0, q1, n0, cols, S) over the blocks of ``plan_search``: S fp32 [q1 - q0, cols rounded up to 256] is the
+        GEMM of the queries' image and database rows n0 .. n0 + cols - 1, in a scratch that the next block overwrites."""
+        from . import _native as N
+        from . import ops
+
+        n = len(self)
+        qc, nb = plan_search(n, Q, max_bytes)
+        scratch = torch.empty((qc * nb,), dtype=torch.float32, device=img_q.device)
+        for q0 in range(0, Q, qc):
+            q1 = min(q0 + qc, Q)
+            for n0 in range(0, n, nb):
+                cols = min(nb, n - n0)
+                width = _up(cols, BLOCK_ALIGN)  # (the image has these rows: zeros behind N)
+                S = scratch[:(q1 - q0) * width].view(q1 - q0, width)
+                ops.linear(img_q[q0:q1], self.image[n0:n0 + width], None, N.EPI_STORE_F32, out=S)
+                yield q0, q1, n0, cols, S
+
+    def range_search(self, queries, threshold, exclude_self=False, max_edges=1 << 28, max_bytes=2 << 30):
+        """Every database vector whose cosine to a query is at least ``threshold``: a CSR of device tensors, ``offsets`` int64
+        [Q + 1], ``ids`` int32 [nnz] and ``scores`` fp32 [nnz]; row q lists, in ascending id, every j with ``S[q][j] >=
+        threshold`` (a float comparison: NaN never passes, a tie does), S the matrix ``search(return_similarity=True)``
+        returns.  ``exclude_self`` leaves id q out of row q.  Two passes over the blocks of ``plan_search``, the [Q, N]
+        matrix never exists: the GEMM and a count launch (``esmk_op_range_rows``) per block, one read of the total by the
+        host — more than ``max_edges`` is a ValueError — a cumulative sum, then the same GEMMs and a fill launch per block."""
+        from . import ops
+
+        queries, subtract = self._query_vectors(queries, "range_search")
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("range_search: the threshold is NaN")
+        if int(max_edges) < 0:
+            raise ValueError(f"range_search: max_edges = {max_edges} is negative")
+        Q = int(queries.shape[0])
+        plan_search(len(self), max(Q, 1), max_bytes)
+        if self.image is None:
+            raise RuntimeError("EmbeddingIndex.range_search: call .to(device) first (the device image has not been built)")
+        dev = self.image.device
+        with torch.cuda.device(dev):
+            counts = torch.zeros((Q,), dtype=torch.int64, device=dev)
+            offsets = torch.zeros((Q + 1,), dtype=torch.int64, device=dev)
+            empty = dict(offsets=offsets, ids=torch.empty((0,), dtype=torch.int32, device=dev),
+                         scores=torch.empty((0,), dtype=torch.float32, device=dev))
+            if Q == 0:
+                return empty
+            img_q = ops.align_rows(self._query_rows(queries, subtract, dev), None, cosine=True, b_side=False)
+            exclude = torch.arange(Q, dtype=torch.int32, device=dev) if exclude_self else None
+            for q0, q1, n0, cols, S in self._similarity_blocks(img_q, Q, max_bytes):
+                ops.range_rows(S, threshold, counts=counts[q0:q1], n_cols=cols, id_base=n0,
+                               exclude=None if exclude is None else exclude[q0:q1])
+            total = int(counts.sum())  # the one read
+            if total > int(max_edges):
+                raise ValueError(f"range_search: threshold {threshold:g} passes {total} pairs, more than max_edges = {int(max_edges)}; "
+                                 "raise the threshold, or center the index first (EmbeddingIndex.centered()): raw mean vectors "
+                                 "share a large common component and their cosines are high everywhere")
+            torch.cumsum(counts, 0, out=offsets[1:])
+            if total == 0:
+                return empty
+            cursor = offsets[:-1].clone()
+            ids = torch.empty((total,), dtype=torch.int32, device=dev)
+            scores = torch.empty((total,), dtype=torch.float32, device=dev)
+            for q0, q1, n0, cols, S in self._similarity_blocks(img_q, Q, max_bytes):
+                ops.range_rows(S, threshold, offsets=offsets[q0:q1 + 1], cursor=cursor[q0:q1], ids=ids, scores=scores, n_cols=cols,
+                               id_base=n0, exclude=None if exclude is None else exclude[q0:q1])
+        return dict(offsets=offsets, ids=ids, scores=scores)
+
+    def cluster(self, threshold, priority="length", assign="first", max_edges=1 << 28, max_bytes=2 << 30):
+        """``esm_amd.cluster.cluster_embeddings`` on this index: greedy incremental clustering at cosine ``threshold``."""
+        from .cluster import cluster_embeddings
+
+        return cluster_embeddings(self, threshold, priority=priority, assign=assign, max_edges=max_edges, max_bytes=max_bytes)
+
     def search(self, queries, top_k, exclude_self=False, return_similarity=False, max_bytes=2 << 30):
         """The ``top_k`` nearest database vectors of every query by cosine (module docstring): a dict of device tensors
         ``scores`` fp32 [Q, k] and ``ids`` int32 [Q, k] (-inf / -1 behind the last hit).  ``queries``: fp32 [Q, E] or another
         ``EmbeddingIndex``.  ``exclude_self``: query q skips database id q (an index searched against itself).
         ``return_similarity`` also returns ``similarity`` fp32 [Q, N] as the GEMM wrote it (tests; at most 2^24 elements).  Per
         block of the database one GEMM and one merge launch on the current stream; the host reads nothing in between."""
-        from . import _native as N
         from . import ops
 
-        if isinstance(queries, EmbeddingIndex):
-            queries = torch.from_numpy(queries.vectors)
-        if not isinstance(queries, torch.Tensor) or queries.dim() != 2:
-            raise ValueError("search: queries must be an fp32 [Q, E] tensor or an EmbeddingIndex")
-        n, E = self.vectors.shape
-        if queries.shape[1] != E:
-            raise ValueError(f"search: queries have E = {queries.shape[1]}, the index has E = {E}")
+        queries, subtract = self._query_vectors(queries, "search")
+        n = len(self)
         top_k = int(top_k)
         if not 1 <= top_k <= MAX_K:
             raise ValueError(f"search: top_k must be 1 .. {MAX_K}, got {top_k}")
         Q = int(queries.shape[0])
         if return_similarity and Q * n > SIM_LIMIT:
             raise ValueError(f"search: return_similarity would hold {Q} x {n} values, at most 2^24 are handed back")
-        qc, nb = plan_search(n, max(Q, 1), max_bytes)
+        plan_search(n, max(Q, 1), max_bytes)  # (its refusals, before anything touches the device)
         if self.image is None:
             raise RuntimeError("EmbeddingIndex.search: call .to(device) first (the device image has not been built)")
         dev = self.image.device
         with torch.cuda.device(dev):
-            q = queries.detach().to(dev, torch.float32).contiguous()
+            q = self._query_rows(queries, subtract, dev)
             scores = torch.full((Q, top_k), float("-inf"), dtype=torch.float32, device=dev)
             ids = torch.full((Q, top_k), -1, dtype=torch.int32, device=dev)
             sim = torch.empty((Q, n), dtype=torch.float32, device=dev) if return_similarity else None
             if Q == 0:
                 return dict(scores=scores, ids=ids, **({"similarity": sim} if return_similarity else {}))
             img_q = ops.align_rows(q, None, cosine=True, b_side=False)
-            scratch = torch.empty((qc * nb,), dtype=torch.float32, device=dev)
             exclude = torch.arange(Q, dtype=torch.int32, device=dev) if exclude_self else None
-            for q0 in range(0, Q, qc):
-                q1 = min(q0 + qc, Q)
-                for n0 in range(0, n, nb):
-                    cols = min(nb, n - n0)
-                    width = _up(cols, BLOCK_ALIGN)  # (the image has these rows: zeros behind N)
-                    S = scratch[:(q1 - q0) * width].view(q1 - q0, width)
-                    ops.linear(img_q[q0:q1], self.image[n0:n0 + width], None, N.EPI_STORE_F32, out=S)
-                    ops.topk_merge(S, top_k, scores[q0:q1], ids[q0:q1], n_cols=cols, id_base=n0,
-                                   exclude=None if exclude is None else exclude[q0:q1], first=n0 == 0)
-                    if return_similarity:
-                        sim[q0:q1, n0:n0 + cols] = S[:, :cols]
+            for q0, q1, n0, cols, S in self._similarity_blocks(img_q, Q, max_bytes):
+                ops.topk_merge(S, top_k, scores[q0:q1], ids[q0:q1], n_cols=cols, id_base=n0,
+                               exclude=None if exclude is None else exclude[q0:q1], first=n0 == 0)
+                if return_similarity:
+                    sim[q0:q1, n0:n0 + cols] = S[:, :cols]
         out = dict(scores=scores, ids=ids)
         if return_similarity:
             out["similarity"] = sim
@@ -461,6 +569,7 @@ def parse_args(argv=None):
     a.add_argument("--fasta", required=True, help="FASTA file of the database")
     a.add_argument("--layer", type=int, default=None, help="the representation to pool (default: the last)")
     a.add_argument("--no-sequences", action="store_true", help="do not keep the sequences (no --align on this index)")
+    a.add_argument("--center", action="store_true", help="subtract the database mean (EmbeddingIndex.centered): for thresholds and clustering")
     a.add_argument("--output", required=True, help="the .npz of the index")
     a.add_argument("--batch-tokens", type=int, default=65536, help="tokens per forward batch")
     b = sub.add_parser("query", help="rank the database for every query; optionally align the best hits")
@@ -511,7 +620,7 @@ def main(argv=None):
         layer = check_model(model, args.layer, None, "search")
         index = EmbeddingIndex.build(model, alphabet, _records(args.fasta), layer=layer, batch_tokens=args.batch_tokens,
                                      keep_sequences=not args.no_sequences, model_name=str(args.model_location))
-        index.save(args.output)
+        (index.centered() if args.center else index).save(args.output)
         return 0
     index.check_model(model)
     index.to(model.embed_tokens.weight.device)

@@ -1249,6 +1249,49 @@ int esmk_op_pool_rows(const float* x_dev, int ldx, int N, const int32_t* rows_de
 int esmk_op_topk_merge(const float* S_dev, int ldS, int n_rows, int n_cols, int id_base, const int32_t* exclude_dev, int k,
                        float* val_dev, int32_t* id_dev, int first, void* stream);
 
+/* Range search and greedy incremental clustering on pooled embeddings (csrc/cluster.hip; esm_amd/cluster.py).  The
+ * similarities are the same GEMM blocks as the search's.  No entry uses a float atomic or scratch memory; all results are the
+ * same bits run after run.  Every entry checks its arguments before the first HIP call.
+ * esmk_op_range_rows: one block of a thresholded row scan.  Column j < n_cols of row q passes when S[q][j] >= threshold as a
+ *   float comparison (NaN never passes, a tie does, -0.0 >= +0.0 does; a NaN threshold passes nothing) and
+ *   id_base + j != exclude[q] (exclude int32 [n_rows] or NULL).  Columns at or behind n_cols never pass (the float4 group
+ *   that holds column n_cols - 1 is loaded whole: ldS % 4 == 0).  One workgroup per row, one read of the row.
+ *   fill == 0, the count pass: counts[q] (int64 [n_rows]) += the number of passing columns of row q.
+ *   fill != 0, the fill pass: the passing (id_base + j, S[q][j]) of row q, in ascending j, are written to ids / scores
+ *   (int32 / fp32 [cap]) from position cursor[q] on, and cursor[q] (int64 [n_rows]) advances by their number: blocks given in
+ *   ascending id_base leave row q's ids ascending.  Row q owns the positions offsets[q] .. offsets[q + 1] - 1 (offsets int64
+ *   [n_rows + 1]).  offsets and cursor are device data: the range is clamped into [0, cap], its end to no less than
+ *   its start, and the cursor into the range; a pair whose position is at or behind the range's end is not
+ *   written, and the cursor never passes the end.
+ *   Refused: null S; null counts (count pass); null offsets, cursor, ids or scores (fill pass); n_cols outside 1 .. 2^22;
+ *   ldS < n_cols or ldS % 4; id_base < 0 or id_base + n_cols > 2^31 - 1; cap < 0; S not 16-byte aligned, counts / offsets /
+ *   cursor not 8-byte aligned; n_rows outside 0 .. 2^24 (0: nothing is launched).
+ * The graph entries read a CSR of out-lists: offsets int64 [n + 1], ids int32 [nnz] (device data: a list's range is clamped
+ *   into [0, nnz], an id outside [0, n) is skipped), rank int32 [n] (a permutation of 0 .. n - 1: the lower rank is decided
+ *   first) and state int32 [n]: 0 undecided, 1 a new representative (its out-list not yet covered), 2 a representative, 3
+ *   covered.  lanes (a power of two, 1 .. 64) consecutive lanes walk one out-list.
+ * esmk_op_cluster_mark: for every w of out-list u with rank[w] > rank[u]: blocked[w] = 1 if state[u] == 0, covered[w] = 1 if
+ *   state[u] == 1 (int32 [n] each; plain stores of 1).  Reads state, writes only blocked and covered.
+ * esmk_op_cluster_decide: per node u: state 1 -> 2; state 0 -> 3 if covered[u], else -> 1 unless blocked[u]; blocked[u] = 0;
+ *   *remaining (int32, device) += the nodes still in state 0 (an integer atomic add per workgroup).
+ *   A round is mark, then decide, from state = blocked = covered = 0; when *remaining of a round is 0 the states are those
+ *   of the sequential greedy loop (walk by rank; an uncovered node becomes a representative and covers its out-list).
+ * esmk_op_cluster_assign: key[w] (uint64 [n], zeroed by the caller) = the maximum over the representatives u (state 1 or 2)
+ *   with w in out-list u and rank[u] < rank[w] of [o << 32 | 0xFFFFFFFF - rank[u]], o = 0 (nearest == 0: the representative
+ *   of the lowest rank) or the order of scores[i] (fp32 [nnz]; nearest != 0: the largest score in the total order of the
+ *   IEEE bits as in esmk_op_topk_merge, ties to the lower rank).  A 64-bit integer atomic max.
+ *   Refused by all three: null offsets, rank, state or flag / key arrays, null ids with nnz > 0, n outside 1 .. 2^24,
+ *   nnz < 0, lanes not a power of two in 1 .. 64, misaligned arrays. */
+int esmk_op_range_rows(const float* S_dev, int ldS, int n_rows, int n_cols, int id_base, const int32_t* exclude_dev, float threshold,
+                       int fill, int64_t* counts_dev, const int64_t* offsets_dev, int64_t* cursor_dev, int32_t* ids_dev,
+                       float* scores_dev, long long cap, void* stream);
+int esmk_op_cluster_mark(const int64_t* offsets_dev, const int32_t* ids_dev, int n, long long nnz, const int32_t* rank_dev,
+                         const int32_t* state_dev, int32_t* blocked_dev, int32_t* covered_dev, int lanes, void* stream);
+int esmk_op_cluster_decide(int32_t* state_dev, int32_t* blocked_dev, const int32_t* covered_dev, int n, int32_t* remaining_dev,
+                           void* stream);
+int esmk_op_cluster_assign(const int64_t* offsets_dev, const int32_t* ids_dev, const float* scores_dev, int n, long long nnz,
+                           const int32_t* rank_dev, const int32_t* state_dev, int nearest, uint64_t* key_dev, int lanes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
