@@ -3,7 +3,8 @@
 // S[i][j] = <u_a[i], u_b[j]> comes from the existing dense GEMM over two f16x3 operand images (hi | hi | lo rows of the a side
 // against hi | lo | hi rows of the b side, fp32 store epilogue); the kernels here are what stands around it, one launch each,
 // no global atomics, every result a function of its inputs alone:
-//     align_rows_kernel       gather the listed rows, form u (cosine: x * float32(1 / sqrt(sum x^2))), write one of the two images
+//     image_rows_kernel       (elementwise.hip) gather the listed rows, form u (cosine: x * float32(1 / sqrt(sum x^2))), write
+//                             one of the two images
 //     align_enhance_kernel    per pair block, in place: the mean of the row and the column z-score
 //     align_dp_kernel         per pair: Needleman-Wunsch / Smith-Waterman with affine gaps, score, end cell, traceback bytes
 //     align_traceback_kernel  per pair: walk the bytes, write the alignment's columns
@@ -35,31 +36,6 @@ using namespace esmk_host;
 
 namespace {
 
-ESMK_DEV float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-ESMK_DEV float add_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-ESMK_DEV float sub_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-ESMK_DEV double dadd_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-ESMK_DEV double dsub_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-ESMK_DEV double dmul_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-
 constexpr int kStrip = 8;              // columns a lane owns
 constexpr int kPanel = 64 * kStrip;    // columns a wavefront covers at once
 constexpr int kAlignMaxLen = 8192;     // the longest side
@@ -80,60 +56,6 @@ ESMK_DEV PairGeom pair_geom(const long long* t, int max_la, int max_lb, int n_ro
     g.a_off = (int)clampll(t[0], 0, n_rows - g.La);
     g.b_off = (int)clampll(t[2] & ~7LL, 0, n_cols - ((g.Lb + 7) & ~7));  // n_cols % 8 == 0
     return g;
-}
-
-// ---- rows ---------------------------------------------------------------------------------------------------------------
-// One workgroup per listed row; thread t owns the float4 groups t, t + 256, ... of the Ep columns.  The sum of squares is taken
-// in fp64: thread t adds its elements in ascending column order (the squares are exact in fp64), then the 256 partial sums
-// are folded as p[k] += p[k + s] for s = 128, 64, ... 1.  A negative row index writes a zero row (the pad rows of the b side).
-__global__ __launch_bounds__(256) void align_rows_kernel(const float* __restrict__ x, int ldx, int N, const int* __restrict__ rows,
-                                                         int cosine, int b_side, _Float16* __restrict__ out, int ldo, int E,
-                                                         int Ep) {
-    __shared__ double red[256];
-    const int i = blockIdx.x, tid = threadIdx.x;
-    int r = rows ? rows[i] : i;
-    const bool zero = r < 0;
-    r = min(max(r, 0), N - 1);
-    const float* xr = x + (size_t)r * ldx;
-    _Float16* o = out + (size_t)i * ldo;
-    float rinv = 1.f;
-    if (cosine) {
-        double part = 0.0;
-        for (int c = tid << 2; c < E; c += 1024) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(xr + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) part = dadd_rn(part, dmul_rn((double)v[e], (double)v[e]));
-        }
-        red[tid] = part;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (tid < s) red[tid] = dadd_rn(red[tid], red[tid + s]);
-            __syncthreads();
-        }
-        const double sum = red[0];
-        rinv = sum == 0.0 ? 0.f : (float)(1.0 / sqrt(sum));
-    }
-    for (int c = tid << 2; c < Ep; c += 1024) {
-        f32x4 u = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (c < E && !zero) {
-            u = *reinterpret_cast<const f32x4*>(xr + c);
-            if (cosine) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) u[e] = mul_rn(u[e], rinv);
-            }
-        }
-        f16x4 hi, lo;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            hi[e] = (_Float16)u[e];
-            const float rem = u[e] - (float)hi[e];  // exact in fp32
-            lo[e] = (_Float16)rem;
-        }
-        _Float16* t = o + (size_t)(c >> 6) * 192 + (c & 63);
-        *reinterpret_cast<f16x4*>(t) = hi;
-        *reinterpret_cast<f16x4*>(t + 64) = b_side ? lo : hi;
-        *reinterpret_cast<f16x4*>(t + 128) = b_side ? hi : lo;
-    }
 }
 
 // ---- enhancement --------------------------------------------------------------------------------------------------------
@@ -406,9 +328,8 @@ int esmk_op_align_rows(const float* x_dev, int ldx, int N, const int32_t* rows_d
     if (misaligned(x_dev, 16) || misaligned(image_dev, 8)) return fail(w + ": x must be 16-byte aligned, the image 8-byte aligned");
     if ((cosine | 1) != 1 || (b_side | 1) != 1) return fail(w + ": cosine and b_side must be 0 or 1");
     if (n == 0) return 0;
-    hipLaunchKernelGGL(align_rows_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, x_dev, ldx, N, rows_dev, cosine,
-                       b_side, (_Float16*)image_dev, ld_image, E, Ep);
-    ESMK_TRY(hipGetLastError());
+    ESMK_TRY(launch_image_rows(x_dev, ldx, N, rows_dev, n, /*b_dec=*/nullptr, /*scale=*/1.f, cosine, b_side, /*zero_negative=*/1,
+                               image_dev, ld_image, E, (hipStream_t)stream));
     return 0;
 }
 

@@ -184,6 +184,34 @@ ESMK_DEV void gelu_fast_x8(V& v) {
     }
 }
 
+// Where the arithmetic of an op is stated operation by operation (include/esmk.h: stream edits, the SAE and alignment operand
+// images, the alignment's enhancement), products and sums are rounded one at a time, never fused, so numpy reproduces the
+// result bit for bit.  hipcc contracts a * b + c by default; these six do not.
+ESMK_DEV float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+ESMK_DEV float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+ESMK_DEV float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+ESMK_DEV double dmul_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+ESMK_DEV double dadd_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+ESMK_DEV double dsub_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
 ESMK_DEV float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -124,34 +124,50 @@ hipError_t launch_contact_energy(const float* contacts, const unsigned char* tar
     return hipGetLastError();
 }
 
-// One lane per chain c, everything in fp64 with one rounding per operation (no contraction into fused multiply-adds):
-//   e_lm = -(lp_sum[c] / n_res[c]) (0 without lp_sum or with n_res[c] <= 0), e_c = e_contact[c] (0 without e_contact)
-//   E'   = w_contact * e_c + w_lm * e_lm,  dE = E' - e_cur[c],  h = hastings[c] or 0
-//   u    = (x >> 8) * 2^-24, x the first word of the generator at counter (chain_id[c], step, 3, 0)
-//   a    = -dE * inv_temperature + h;  accept iff tok[c] >= 0 and (a >= 0 or u < exp(a));  inv_temperature == +inf (greedy):
-//          accept iff tok[c] >= 0 and dE <= 0.  A NaN anywhere rejects.
+// One lane per chain c, everything in fp64 with one rounding per operation (no contraction into fused multiply-adds).  The one
+// acceptance kernel: esmk_op_mh_accept gives a scalar temperature and no third term, esmk_op_mh_accept_ex (replica exchange and
+// the n-gram term, tempering.hip) a temperature per chain and e_extra.
+//   e_lm  = -(lp_sum[c] / n_res[c]) (0 without lp_sum or with n_res[c] <= 0), e_c = e_contact[c] (0 without e_contact)
+//   E'    = (w_contact * e_c + w_lm * e_lm) + w_extra * e_extra[c]; without e_extra the last addition is not made
+//   dE    = E' - e_cur[c],  h = hastings[c] or 0
+//   u     = (x >> 8) * 2^-24, x the first word of the generator at counter (chain_id[c], step, 3, 0)
+//   inv_t = inv_t_tab[clamp(rung[c], 0, n_rung - 1)] (rung null: entry 0); inv_t_tab null: the scalar inv_t0 (no table to
+//           allocate or upload for one temperature)
+//   a     = -dE * inv_t + h;  accept iff tok[c] >= 0 and (a >= 0 or u < exp(a));  inv_t == +inf (greedy): accept iff tok[c] >= 0
+//           and dE <= 0.  A NaN anywhere rejects.
 // On acceptance tokens[slot, site[c]] = tok[c] (a site outside [0, T) writes no token), e_cur[c] = E', and the components
-// e_contact_cur[c] = e_c, e_lm_cur[c] = e_lm where those arrays are given.  accepted, u and E' are written for every chain.
+// e_contact_cur[c] = e_c, e_lm_cur[c] = e_lm, e_extra_cur[c] = e_extra[c] where those arrays are given.  accepted, u and E' are
+// written for every chain.
 __global__ __launch_bounds__(256) void mh_accept_kernel(int64_t* __restrict__ tokens, const int* __restrict__ slot,
                                                         const int* __restrict__ site, const int* __restrict__ tok,
                                                         const int* __restrict__ chain_id, const double* __restrict__ e_contact,
                                                         const double* __restrict__ lp_sum, const int* __restrict__ n_res,
-                                                        const double* __restrict__ hastings, double w_contact, double w_lm,
-                                                        double inv_temperature, unsigned long long seed, int step,
+                                                        const double* __restrict__ hastings, const double* __restrict__ e_extra,
+                                                        double w_contact, double w_lm, double w_extra,
+                                                        const double* __restrict__ inv_t_tab, double inv_t0,
+                                                        const int* __restrict__ rung, int n_rung, unsigned long long seed, int step,
                                                         double* __restrict__ e_cur, double* __restrict__ e_contact_cur,
-                                                        double* __restrict__ e_lm_cur, unsigned char* __restrict__ accepted_out,
-                                                        double* __restrict__ u_out, double* __restrict__ e_prop_out, int n_chain, int B,
-                                                        int T) {
+                                                        double* __restrict__ e_lm_cur, double* __restrict__ e_extra_cur,
+                                                        unsigned char* __restrict__ accepted_out, double* __restrict__ u_out,
+                                                        double* __restrict__ e_prop_out, int n_chain, int B, int T) {
     const size_t stride = (size_t)gridDim.x * 256;
     for (size_t c = (size_t)blockIdx.x * 256 + threadIdx.x; c < (size_t)n_chain; c += stride) {
         const double e_c = e_contact != nullptr ? e_contact[c] : 0.0;
         double e_lm = 0.0;
         if (lp_sum != nullptr && n_res != nullptr && n_res[c] > 0) e_lm = -(lp_sum[c] / (double)n_res[c]);
         const double a_c = w_contact * e_c, a_lm = w_lm * e_lm;
-        const double e_prop = a_c + a_lm;
+        double e_prop = a_c + a_lm;
+        double e_x = 0.0;
+        if (e_extra != nullptr) {
+            e_x = e_extra[c];
+            const double a_x = w_extra * e_x;
+            e_prop = e_prop + a_x;
+        }
         const double dE = e_prop - e_cur[c];
         const double h = hastings != nullptr ? hastings[c] : 0.0;
         const double u = (double)(philox_word0(seed, chain_id[c], step, kPurposeAcceptance, 0) >> 8) * 0x1p-24;
+        double inv_temperature = inv_t0;
+        if (inv_t_tab != nullptr) inv_temperature = inv_t_tab[rung != nullptr ? min(max(rung[c], 0), n_rung - 1) : 0];
         const int t = tok[c];
         bool accept;
         if (inv_temperature == (double)INFINITY) {
@@ -170,6 +186,7 @@ __global__ __launch_bounds__(256) void mh_accept_kernel(int64_t* __restrict__ to
             e_cur[c] = e_prop;
             if (e_contact_cur != nullptr) e_contact_cur[c] = e_c;
             if (e_lm_cur != nullptr) e_lm_cur[c] = e_lm;
+            if (e_extra_cur != nullptr && e_extra != nullptr) e_extra_cur[c] = e_x;
         }
         accepted_out[c] = accept ? 1 : 0;
         if (u_out != nullptr) u_out[c] = u;
@@ -178,17 +195,18 @@ __global__ __launch_bounds__(256) void mh_accept_kernel(int64_t* __restrict__ to
 }
 
 hipError_t launch_mh_accept(int64_t* tokens, const int* slot, const int* site, const int* tok, const int* chain_id,
-                            const double* e_contact, const double* lp_sum, const int* n_res, const double* hastings, double w_contact,
-                            double w_lm, double inv_temperature, unsigned long long seed, int step, double* e_cur,
-                            double* e_contact_cur, double* e_lm_cur, unsigned char* accepted_out, double* u_out, double* e_prop_out,
-                            int n_chain, int B, int T, hipStream_t st) {
+                            const double* e_contact, const double* lp_sum, const int* n_res, const double* hastings,
+                            const double* e_extra, double w_contact, double w_lm, double w_extra, const double* inv_t_tab,
+                            double inv_t0, const int* rung, int n_rung, unsigned long long seed, int step, double* e_cur,
+                            double* e_contact_cur, double* e_lm_cur, double* e_extra_cur, unsigned char* accepted_out, double* u_out,
+                            double* e_prop_out, int n_chain, int B, int T, hipStream_t st) {
     if (!tokens || !site || !tok || !chain_id || !e_cur || !accepted_out || n_chain <= 0 || B <= 0 || T <= 0 ||
-        (lp_sum != nullptr && n_res == nullptr) || !(inv_temperature >= 0.0))
+        (lp_sum != nullptr && n_res == nullptr) || (inv_t_tab != nullptr ? n_rung <= 0 : !(inv_t0 >= 0.0)))
         return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)std::min<size_t>(((size_t)n_chain + 255) / 256, 8192);
     hipLaunchKernelGGL(mh_accept_kernel, dim3(blocks), dim3(256), 0, st, tokens, slot, site, tok, chain_id, e_contact, lp_sum, n_res,
-                       hastings, w_contact, w_lm, inv_temperature, seed, step, e_cur, e_contact_cur, e_lm_cur, accepted_out, u_out,
-                       e_prop_out, n_chain, B, T);
+                       hastings, e_extra, w_contact, w_lm, w_extra, inv_t_tab, inv_t0, rung, n_rung, seed, step, e_cur,
+                       e_contact_cur, e_lm_cur, e_extra_cur, accepted_out, u_out, e_prop_out, n_chain, B, T);
     return hipGetLastError();
 }
 

@@ -778,6 +778,79 @@ hipError_t launch_convert2d_split(const void* src, int src_dtype, void* dst, siz
     return hipGetLastError();
 }
 
+// The f16x3 image of gathered fp32 ACTIVATION rows (esmk_op_sae_rows, esmk_op_align_rows): image row i holds
+// u = sub_rn(mul_rn(x[r], s), b_dec), r = rows[i] (rows null: i), every 64-column K tile as hi | hi | lo, with b_side as hi | lo | hi
+// (the layout convert2d_split_kernel<S, true> gives weights); columns E .. Ep are zero.  One workgroup per image row; thread t owns
+// the float4 groups t, t + 256, ... of the Ep columns (E % 4 == 0 and Ep % 64 == 0: a group never straddles E or a K tile).
+//   s      = scale, or with cosine float32(1 / sqrt(sum x^2)) (0 for a zero row).  The sum of squares is taken in fp64: thread t
+//            adds its elements in ascending column order (the squares are exact in fp64), then the 256 partial sums are folded
+//            as p[k] += p[k + s] for s = 128, 64, ... 1
+//   b_dec  null: 0.  x * 1.0f and u - 0.0f are exact, so the one formula serves every mode
+//   r      is device data: clamped to [0, N); with zero_negative a negative index writes a zero row instead (the pad rows of
+//            the alignment's b side)
+// COSINE = false compiles the sum of squares and its 2 KiB of LDS out; the part order is a template parameter too, so the
+// stores of either order are what a kernel of that order alone would hold.
+template <bool COSINE, bool B_SIDE>
+__global__ __launch_bounds__(256) void image_rows_kernel(const float* __restrict__ x, int ldx, int N, const int* __restrict__ rows,
+                                                         const float* __restrict__ b_dec, float scale, int zero_negative, _Float16* __restrict__ out, int ldo, int E, int Ep) {
+    const int i = blockIdx.x, tid = threadIdx.x;
+    int r = rows ? rows[i] : i;
+    const bool zero = zero_negative && r < 0;
+    r = min(max(r, 0), N - 1);
+    const float* xr = x + (size_t)r * ldx;
+    _Float16* o = out + (size_t)i * ldo;
+    float s = scale;
+    if constexpr (COSINE) {
+        __shared__ double red[256];
+        double part = 0.0;
+        for (int c = tid << 2; c < E; c += 1024) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(xr + c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) part = dadd_rn(part, dmul_rn((double)v[e], (double)v[e]));
+        }
+        red[tid] = part;
+        __syncthreads();
+        for (int k = 128; k > 0; k >>= 1) {
+            if (tid < k) red[tid] = dadd_rn(red[tid], red[tid + k]);
+            __syncthreads();
+        }
+        const double sum = red[0];
+        s = sum == 0.0 ? 0.f : (float)(1.0 / sqrt(sum));
+    }
+    for (int c = tid << 2; c < Ep; c += 1024) {
+        f32x4 u = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (c < E && !zero) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(xr + c);
+            const f32x4 b = b_dec ? *reinterpret_cast<const f32x4*>(b_dec + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) u[e] = sub_rn(mul_rn(v[e], s), b[e]);
+        }
+        f16x4 hi, lo;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            hi[e] = (_Float16)u[e];
+            const float rem = u[e] - (float)hi[e];  // exact in fp32
+            lo[e] = (_Float16)rem;
+        }
+        _Float16* t = o + (size_t)(c >> 6) * 192 + (c & 63);
+        *reinterpret_cast<f16x4*>(t) = hi;
+        *reinterpret_cast<f16x4*>(t + 64) = B_SIDE ? lo : hi;
+        *reinterpret_cast<f16x4*>(t + 128) = B_SIDE ? hi : lo;
+    }
+}
+
+hipError_t launch_image_rows(const float* x, int ldx, int N, const int* rows, int n, const float* b_dec, float scale, int cosine,
+                             int b_side, int zero_negative, void* out, int ldo, int E, hipStream_t st) {
+    const int Ep = (E + 63) / 64 * 64;
+    if (!x || !out || N <= 0 || n <= 0 || (!rows && n > N) || E <= 0 || E % 4 != 0 || ldx < E || ldo < 3 * Ep)
+        return hipErrorInvalidValue;
+    const auto kernel = cosine ? (b_side ? image_rows_kernel<true, true> : image_rows_kernel<true, false>)
+                               : (b_side ? image_rows_kernel<false, true> : image_rows_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(256), 0, st, x, ldx, N, rows, b_dec, scale, zero_negative, (_Float16*)out, ldo,
+                       E, Ep);
+    return hipGetLastError();
+}
+
 hipError_t launch_convert2d(const void* src, int src_dtype, void* dst, int dst_dtype, size_t rows, size_t cols,
                             size_t dst_ld, int row_map, int col_map, int d, hipStream_t st) {
     if (rows * cols == 0) return hipSuccess;

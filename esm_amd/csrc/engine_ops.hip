@@ -868,7 +868,8 @@ int esmk_op_mask_rows(const int64_t* tokens_dev, const int32_t* src_row_dev, con
     if (B <= 0 || T <= 0 || n <= 0) return fail("esmk_op_mask_rows: B, T and n must be positive");
     if ((long long)B * T > ESMK_MAX_ROWS || (long long)n * T > ESMK_MAX_ROWS)
         return fail("esmk_op_mask_rows: B*T or n*T exceeds 2^24 rows");
-    ESMK_TRY(launch_mask_rows(tokens_dev, src_row_dev, pos_dev, out_dev, B, T, n, mask_idx, (hipStream_t)stream));
+    ESMK_TRY(launch_copy_rows(tokens_dev, src_row_dev, /*start=*/nullptr, /*pos_off=*/nullptr, pos_dev, /*tok=*/nullptr, out_dev, B, T,
+                              n, T, /*total=*/0, /*V=*/0, /*head_tok=*/-1, /*tail_tok=*/-1, mask_idx, (hipStream_t)stream));
     return 0;
 }
 
@@ -879,8 +880,8 @@ int esmk_op_mask_rows_multi(const int64_t* tokens_dev, const int32_t* src_row_de
     if (total < 0) return fail("esmk_op_mask_rows_multi: total must not be negative");
     if ((long long)B * T > ESMK_MAX_ROWS || (long long)n * T > ESMK_MAX_ROWS)
         return fail("esmk_op_mask_rows_multi: B*T or n*T exceeds 2^24 rows");
-    ESMK_TRY(launch_mask_rows_multi(tokens_dev, src_row_dev, pos_off_dev, pos_dev, out_dev, B, T, n, total, mask_idx,
-                                    (hipStream_t)stream));
+    ESMK_TRY(launch_copy_rows(tokens_dev, src_row_dev, /*start=*/nullptr, pos_off_dev, pos_dev, /*tok=*/nullptr, out_dev, B, T, n, T,
+                              total, /*V=*/0, /*head_tok=*/-1, /*tail_tok=*/-1, mask_idx, (hipStream_t)stream));
     return 0;
 }
 
@@ -924,8 +925,8 @@ int esmk_op_window_rows(const int64_t* tokens_dev, const int32_t* src_row_dev, c
     if (total < 0) return fail("esmk_op_window_rows: total must not be negative");
     if ((long long)B * T > ESMK_MAX_ROWS || (long long)n * Tw > ESMK_MAX_ROWS)
         return fail("esmk_op_window_rows: B*T or n*Tw exceeds 2^24 rows");
-    ESMK_TRY(launch_window_rows(tokens_dev, src_row_dev, start_dev, mask_off_dev, mask_pos_dev, out_dev, B, T, n, Tw, total,
-                                head_tok, tail_tok, mask_idx, (hipStream_t)stream));
+    ESMK_TRY(launch_copy_rows(tokens_dev, src_row_dev, start_dev, mask_off_dev, mask_pos_dev, /*tok=*/nullptr, out_dev, B, T, n, Tw,
+                              total, /*V=*/0, head_tok, tail_tok, mask_idx, (hipStream_t)stream));
     return 0;
 }
 
@@ -973,18 +974,27 @@ int esmk_op_permute_positions(const int32_t* pos_off_dev, const int32_t* pos_in_
     return 0;
 }
 
+// what esmk_op_sample_rows and esmk_op_sample_rows_ex refuse alike, under the entry's own name
+static int sample_rows_check(const std::string& w, const void* lp, const void* row_chain, const void* row_index, const void* token_out,
+                             const void* logq_out, int n, int V, float inv_temperature, int step) {
+    if (!lp || !row_chain || !row_index || !token_out || !logq_out) return fail(w + ": null argument");
+    if (n <= 0 || n > ESMK_MAX_ROWS) return fail(w + ": n must be in 1 .. 2^24");
+    if (V <= 0 || V > 64) return fail(w + ": V must be in 1 .. 64 (one vocabulary entry per lane)");
+    if (!(inv_temperature >= 0.f) || inv_temperature > 3.0e38f)
+        return fail(w + ": inv_temperature must be finite and not negative (0: greedy)");
+    if (step < 0) return fail(w + ": step must not be negative");
+    return 0;
+}
+
 int esmk_op_sample_rows(const float* logprobs_dev, const int32_t* row_chain_dev, const int32_t* row_index_dev,
                         const int32_t* exclude_dev, uint64_t allowed_mask, float inv_temperature, uint64_t seed, int step,
                         int32_t* token_out_dev, float* logq_out_dev, float* u_out_dev, int n, int V, void* stream) {
-    if (!logprobs_dev || !row_chain_dev || !row_index_dev || !token_out_dev || !logq_out_dev)
-        return fail("esmk_op_sample_rows: null argument");
-    if (n <= 0 || n > ESMK_MAX_ROWS) return fail("esmk_op_sample_rows: n must be in 1 .. 2^24");
-    if (V <= 0 || V > 64) return fail("esmk_op_sample_rows: V must be in 1 .. 64 (one vocabulary entry per lane)");
-    if (!(inv_temperature >= 0.f) || inv_temperature > 3.0e38f)
-        return fail("esmk_op_sample_rows: inv_temperature must be finite and not negative (0: greedy)");
-    if (step < 0) return fail("esmk_op_sample_rows: step must not be negative");
+    if (int rc = sample_rows_check("esmk_op_sample_rows", logprobs_dev, row_chain_dev, row_index_dev, token_out_dev, logq_out_dev, n,
+                                   V, inv_temperature, step))
+        return rc;
     ESMK_TRY(launch_sample_rows(logprobs_dev, row_chain_dev, row_index_dev, exclude_dev, (unsigned long long)allowed_mask,
-                                inv_temperature, (unsigned long long)seed, step, token_out_dev, logq_out_dev, u_out_dev, n, V,
+                                inv_temperature, (unsigned long long)seed, step, /*top_k=*/0, /*top_p=*/1.f, /*score_kind=*/0,
+                                token_out_dev, logq_out_dev, u_out_dev, /*score_out=*/nullptr, /*kept_out=*/nullptr, n, V,
                                 (hipStream_t)stream));
     return 0;
 }
@@ -993,22 +1003,18 @@ int esmk_op_sample_rows_ex(const float* logprobs_dev, const int32_t* row_chain_d
                            const int32_t* exclude_dev, uint64_t allowed_mask, float inv_temperature, uint64_t seed, int step,
                            int top_k, float top_p, int score_kind, int32_t* token_out_dev, float* logq_out_dev, float* u_out_dev,
                            float* score_out_dev, uint64_t* kept_out_dev, int n, int V, void* stream) {
-    if (!logprobs_dev || !row_chain_dev || !row_index_dev || !token_out_dev || !logq_out_dev)
-        return fail("esmk_op_sample_rows_ex: null argument");
-    if (n <= 0 || n > ESMK_MAX_ROWS) return fail("esmk_op_sample_rows_ex: n must be in 1 .. 2^24");
-    if (V <= 0 || V > 64) return fail("esmk_op_sample_rows_ex: V must be in 1 .. 64 (one vocabulary entry per lane)");
-    if (!(inv_temperature >= 0.f) || inv_temperature > 3.0e38f)
-        return fail("esmk_op_sample_rows_ex: inv_temperature must be finite and not negative (0: greedy)");
-    if (step < 0) return fail("esmk_op_sample_rows_ex: step must not be negative");
+    if (int rc = sample_rows_check("esmk_op_sample_rows_ex", logprobs_dev, row_chain_dev, row_index_dev, token_out_dev, logq_out_dev,
+                                   n, V, inv_temperature, step))
+        return rc;
     if (top_k < 0 || top_k > 64) return fail("esmk_op_sample_rows_ex: top_k must be in 0 .. 64 (0: off)");
     if (!(top_p > 0.f && top_p <= 1.f)) return fail("esmk_op_sample_rows_ex: top_p must be in (0, 1] (1: off)");
     if (score_kind < 0 || score_kind > 2)
         return fail("esmk_op_sample_rows_ex: score_kind must be 0 (none), 1 (confidence) or 2 (negative entropy)");
     if (score_kind != 0 && !score_out_dev) return fail("esmk_op_sample_rows_ex: a score_kind other than 0 needs score_out_dev");
-    ESMK_TRY(launch_sample_rows_ex(logprobs_dev, row_chain_dev, row_index_dev, exclude_dev, (unsigned long long)allowed_mask,
-                                   inv_temperature, (unsigned long long)seed, step, top_k, top_p, score_kind, token_out_dev,
-                                   logq_out_dev, u_out_dev, score_out_dev, (unsigned long long*)kept_out_dev, n, V,
-                                   (hipStream_t)stream));
+    ESMK_TRY(launch_sample_rows(logprobs_dev, row_chain_dev, row_index_dev, exclude_dev, (unsigned long long)allowed_mask,
+                                inv_temperature, (unsigned long long)seed, step, top_k, top_p, score_kind, token_out_dev,
+                                logq_out_dev, u_out_dev, score_out_dev, (unsigned long long*)kept_out_dev, n, V,
+                                (hipStream_t)stream));
     return 0;
 }
 
@@ -1122,23 +1128,33 @@ int esmk_op_distogram_energy(const float* pair_logits_dev, int ld, int first, in
     return 0;
 }
 
+// what esmk_op_mh_accept and esmk_op_mh_accept_ex refuse alike, under the entry's own name; the temperature (a scalar there, a
+// table here) and the weights are the entry's own
+static int mh_accept_check(const std::string& w, bool null_arg, const void* lp_sum, const void* n_res, int n_chain, int B, int T) {
+    if (null_arg) return fail(w + ": null argument");
+    if (lp_sum && !n_res) return fail(w + ": lp_sum without n_res");
+    if (n_chain <= 0 || B <= 0 || T <= 0) return fail(w + ": n_chain, B and T must be positive");
+    if ((long long)B * T > ESMK_MAX_ROWS || n_chain > ESMK_MAX_ROWS) return fail(w + ": B*T or n_chain exceeds 2^24 rows");
+    return 0;
+}
+
 int esmk_op_mh_accept(int64_t* tokens_dev, const int32_t* slot_dev, const int32_t* site_dev, const int32_t* tok_dev,
                       const int32_t* chain_id_dev, const double* e_contact_dev, const double* lp_sum_dev, const int32_t* n_res_dev,
                       const double* hastings_dev, double w_contact, double w_lm, double inv_temperature, uint64_t seed, int step,
                       double* e_cur_dev, double* e_contact_cur_dev, double* e_lm_cur_dev, uint8_t* accepted_out_dev, double* u_out_dev,
                       double* e_prop_out_dev, int n_chain, int B, int T, void* stream) {
-    if (!tokens_dev || !site_dev || !tok_dev || !chain_id_dev || !e_cur_dev || !accepted_out_dev)
-        return fail("esmk_op_mh_accept: null argument");
-    if (lp_sum_dev && !n_res_dev) return fail("esmk_op_mh_accept: lp_sum without n_res");
-    if (n_chain <= 0 || B <= 0 || T <= 0) return fail("esmk_op_mh_accept: n_chain, B and T must be positive");
-    if ((long long)B * T > ESMK_MAX_ROWS || n_chain > ESMK_MAX_ROWS) return fail("esmk_op_mh_accept: B*T or n_chain exceeds 2^24 rows");
+    if (int rc = mh_accept_check("esmk_op_mh_accept",
+                                 !tokens_dev || !site_dev || !tok_dev || !chain_id_dev || !e_cur_dev || !accepted_out_dev, lp_sum_dev,
+                                 n_res_dev, n_chain, B, T))
+        return rc;
     if (!(inv_temperature >= 0.0)) return fail("esmk_op_mh_accept: inv_temperature must not be negative or NaN (+inf: greedy)");
-    if (!(w_contact == w_contact) || !(w_lm == w_lm) || std::isinf(w_contact) || std::isinf(w_lm))
-        return fail("esmk_op_mh_accept: the weights must be finite");
+    if (!std::isfinite(w_contact) || !std::isfinite(w_lm)) return fail("esmk_op_mh_accept: the weights must be finite");
     if (step < 0) return fail("esmk_op_mh_accept: step must not be negative");
     ESMK_TRY(launch_mh_accept(tokens_dev, slot_dev, site_dev, tok_dev, chain_id_dev, e_contact_dev, lp_sum_dev, n_res_dev, hastings_dev,
-                              w_contact, w_lm, inv_temperature, (unsigned long long)seed, step, e_cur_dev, e_contact_cur_dev,
-                              e_lm_cur_dev, accepted_out_dev, u_out_dev, e_prop_out_dev, n_chain, B, T, (hipStream_t)stream));
+                              /*e_extra=*/nullptr, w_contact, w_lm, /*w_extra=*/0.0, /*inv_t_tab=*/nullptr, inv_temperature,
+                              /*rung=*/nullptr, /*n_rung=*/0, (unsigned long long)seed, step, e_cur_dev, e_contact_cur_dev,
+                              e_lm_cur_dev, /*e_extra_cur=*/nullptr, accepted_out_dev, u_out_dev, e_prop_out_dev, n_chain, B, T,
+                              (hipStream_t)stream));
     return 0;
 }
 
@@ -1180,20 +1196,18 @@ int esmk_op_mh_accept_ex(int64_t* tokens_dev, const int32_t* slot_dev, const int
                          const double* inv_t_dev, const int32_t* rung_dev, int n_rung, uint64_t seed, int step, double* e_cur_dev,
                          double* e_contact_cur_dev, double* e_lm_cur_dev, double* e_extra_cur_dev, uint8_t* accepted_out_dev,
                          double* u_out_dev, double* e_prop_out_dev, int n_chain, int B, int T, void* stream) {
-    if (!tokens_dev || !site_dev || !tok_dev || !chain_id_dev || !e_cur_dev || !accepted_out_dev || !inv_t_dev)
-        return fail("esmk_op_mh_accept_ex: null argument");
-    if (lp_sum_dev && !n_res_dev) return fail("esmk_op_mh_accept_ex: lp_sum without n_res");
-    if (n_chain <= 0 || B <= 0 || T <= 0) return fail("esmk_op_mh_accept_ex: n_chain, B and T must be positive");
-    if ((long long)B * T > ESMK_MAX_ROWS || n_chain > ESMK_MAX_ROWS)
-        return fail("esmk_op_mh_accept_ex: B*T or n_chain exceeds 2^24 rows");
+    if (int rc = mh_accept_check("esmk_op_mh_accept_ex",
+                                 !tokens_dev || !site_dev || !tok_dev || !chain_id_dev || !e_cur_dev || !accepted_out_dev || !inv_t_dev,
+                                 lp_sum_dev, n_res_dev, n_chain, B, T))
+        return rc;
     if (n_rung <= 0 || n_rung > ESMK_MAX_ROWS) return fail("esmk_op_mh_accept_ex: n_rung must be in 1 .. 2^24");
     if (!std::isfinite(w_contact) || !std::isfinite(w_lm) || !std::isfinite(w_extra))
         return fail("esmk_op_mh_accept_ex: the weights must be finite");
     if (step < 0) return fail("esmk_op_mh_accept_ex: step must not be negative");
-    ESMK_TRY(launch_mh_accept_ex(tokens_dev, slot_dev, site_dev, tok_dev, chain_id_dev, e_contact_dev, lp_sum_dev, n_res_dev,
-                                 hastings_dev, e_extra_dev, w_contact, w_lm, w_extra, inv_t_dev, rung_dev, n_rung,
-                                 (unsigned long long)seed, step, e_cur_dev, e_contact_cur_dev, e_lm_cur_dev, e_extra_cur_dev,
-                                 accepted_out_dev, u_out_dev, e_prop_out_dev, n_chain, B, T, (hipStream_t)stream));
+    ESMK_TRY(launch_mh_accept(tokens_dev, slot_dev, site_dev, tok_dev, chain_id_dev, e_contact_dev, lp_sum_dev, n_res_dev, hastings_dev,
+                              e_extra_dev, w_contact, w_lm, w_extra, inv_t_dev, /*inv_t0=*/0.0, rung_dev, n_rung,
+                              (unsigned long long)seed, step, e_cur_dev, e_contact_cur_dev, e_lm_cur_dev, e_extra_cur_dev,
+                              accepted_out_dev, u_out_dev, e_prop_out_dev, n_chain, B, T, (hipStream_t)stream));
     return 0;
 }
 

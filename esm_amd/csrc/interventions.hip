@@ -12,21 +12,8 @@ namespace esmk {
 
 namespace {
 
-// The arithmetic of an edit is stated operation by operation (include/esmk.h): products and sums are rounded one at a
-// time, never fused, so numpy float32 reproduces x' bit for bit.  hipcc contracts a * b + c by default; these three do not.
-ESMK_DEV float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-ESMK_DEV float add_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-ESMK_DEV float sub_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-
+// The arithmetic of an edit is stated operation by operation (include/esmk.h): mul_rn / add_rn / sub_rn (common.h) round
+// products and sums one at a time, so numpy float32 reproduces x' bit for bit.
 ESMK_DEV double wave_sum_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

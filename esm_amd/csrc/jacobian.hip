@@ -1,7 +1,7 @@
 // jacobian.hip — the categorical Jacobian of a masked language model (esm_amd/jacobian.py): every candidate residue put at
 // every position of ONE protein, the change of the logits at every other position recorded as J[i, a, j, b] fp32
-// [L, nA, L, nA] (400 L^2 floats for the 20 standard residues: 1.7 GB at L = 1022).  The kernels here build the substituted
-// copies, scatter the logit differences of a chunk of copies into J, centre J along its four axes IN PLACE (one tensor, never
+// [L, nA, L, nA] (400 L^2 floats for the 20 standard residues: 1.7 GB at L = 1022).  copy_rows_kernel (scoring.hip) builds the substituted
+// copies; the kernels here scatter the logit differences of a chunk of copies into J, centre J along its four axes IN PLACE (one tensor, never
 // two), reduce it to the [L, L] coupling map and correct that by its average product.  The layer stack between the first two
 // is the time; these are bandwidth kernels.  No atomics anywhere: every sum runs in a fixed order in fp64, so no result
 // depends on the launch geometry or on how the copies were chunked.  All indices into J are 64 bit.
@@ -11,31 +11,6 @@
 #include <stdint.h>
 
 namespace esmk {
-
-// out[i, :] = tokens[src_row[i], :] with position pos[i] replaced by tok[i]: copy (position, candidate) of the categorical
-// Jacobian, a whole chunk of them at once.  src_row == nullptr: every row comes from tokens[0].  All lists are device data: a
-// source row outside [0, B) is clamped, a position outside [0, T) or a token outside [0, V) substitutes nothing.
-__global__ __launch_bounds__(256) void substitute_rows_kernel(const int64_t* __restrict__ tokens, const int* __restrict__ src_row,
-                                                              const int* __restrict__ pos, const int* __restrict__ tok,
-                                                              int64_t* __restrict__ out, int B, int T, int n, int V) {
-    const size_t total = (size_t)n * T;
-    const size_t stride = (size_t)gridDim.x * 256;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += stride) {
-        const int i = (int)(e / T), t = (int)(e - (size_t)i * T);
-        const int b = src_row ? min(max(src_row[i], 0), B - 1) : 0;
-        const int v = tok[i];
-        out[e] = (t == pos[i] && v >= 0 && v < V) ? (int64_t)v : tokens[(size_t)b * T + t];
-    }
-}
-
-hipError_t launch_substitute_rows(const int64_t* tokens, const int* src_row, const int* pos, const int* tok, int64_t* out, int B,
-                                  int T, int n, int V, hipStream_t st) {
-    if (!tokens || !pos || !tok || !out || B <= 0 || T <= 0 || n <= 0 || V <= 0) return hipErrorInvalidValue;
-    const size_t total = (size_t)n * T;
-    const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 8192);
-    hipLaunchKernelGGL(substitute_rows_kernel, dim3(blocks), dim3(256), 0, st, tokens, src_row, pos, tok, out, B, T, n, V);
-    return hipGetLastError();
-}
 
 // out[c, j, b] = logits[c * L + j, cols[b]] - wt[j, cols[b]]: the fp32 difference of two fp32 logits, copy c of the chunk against
 // the wild type.  out is the slice of J that starts at the chunk's first copy; one element per lane, the stores contiguous.
@@ -306,7 +281,8 @@ int esmk_op_substitute_rows(const int64_t* tokens_dev, const int32_t* src_row_de
     if (B <= 0 || T <= 0 || n <= 0 || V <= 0) return fail("esmk_op_substitute_rows: B, T, n and V must be positive");
     if ((long long)B * T > ESMK_MAX_ROWS || (long long)n * T > ESMK_MAX_ROWS)
         return fail("esmk_op_substitute_rows: B*T or n*T exceeds 2^24 rows");
-    ESMK_TRY(launch_substitute_rows(tokens_dev, src_row_dev, pos_dev, tok_dev, out_dev, B, T, n, V, (hipStream_t)stream));
+    ESMK_TRY(launch_copy_rows(tokens_dev, src_row_dev, /*start=*/nullptr, /*pos_off=*/nullptr, pos_dev, tok_dev, out_dev, B, T, n, T,
+                              /*total=*/0, V, /*head_tok=*/-1, /*tail_tok=*/-1, /*mask_idx=*/0, (hipStream_t)stream));
     return 0;
 }
 

@@ -199,6 +199,11 @@ hipError_t launch_convert2d(const void* src, int src_dtype, void* dst, int dst_d
 // (LnExtra::x3, GemmArgs::x3_out, attention's X3 output) a plain GEMM over K' = 3 K is A_hi W_hi + A_hi W_lo + A_lo W_hi
 hipError_t launch_convert2d_split(const void* src, int src_dtype, void* dst, size_t rows, size_t cols, size_t dst_ld,
                                   int row_map, int col_map, int d, hipStream_t st, int parts = 2);
+// the f16x3 image of n gathered fp32 activation rows: out fp16 [n, ldo >= 3 Ep], row i = hi | hi | lo (b_side: hi | lo | hi) per K
+// tile of u = x[rows[i]] * s - b_dec (one rounding each), s = scale or, with cosine, float32(1 / sqrt(fp64 sum x^2)); rows
+// int32 [n] or null (row i), clamped to [0,N), with zero_negative a negative index gives a zero row; b_dec fp32 [E] or null
+hipError_t launch_image_rows(const float* x, int ldx, int N, const int* rows, int n, const float* b_dec, float scale, int cosine,
+                             int b_side, int zero_negative, void* out, int ldo, int E, hipStream_t st);
 // RoPE tables cos/sin[t][i] = cos/sin(t * inv_freq[i]) (rotary_embedding.py:47-61), fp32
 hipError_t launch_rope_table(const float* inv_freq, float* cos, float* sin, int T, int half,
                              hipStream_t st);
@@ -206,15 +211,17 @@ hipError_t launch_copy_f32(const float* src, float* dst, size_t n, hipStream_t s
 // out[b,:] = mean of rows [first, first + min(count[b], T - first)) of x[b] ([B,T,E], any dtype code); NaN if empty
 hipError_t launch_masked_row_mean(const void* x, int x_dtype, const int* count, float* out, int B, int T, int E,
                                   int first, hipStream_t st);
-// scoring.hip — variant scoring (esmk_forward_rows).  out int64 [n,T]: row i = tokens[src_row[i]] (row 0 when src_row is
-// null) with position pos[i] set to mask_idx
-hipError_t launch_mask_rows(const int64_t* tokens, const int* src_row, const int* pos, int64_t* out, int B, int T, int n,
+// scoring.hip — the token copies of variant scoring (esmk_forward_rows), windowed scoring and the categorical Jacobian, one
+// kernel.  out int64 [n,Tw]: copy i, column c = tokens[src_row[i], start[i] + c - h] (h = 1 if head_tok >= 0; row and column
+// clamped; src_row null: row 0, start null: 0), column 0 = head_tok and column Tw - 1 = tail_tok where those are >= 0; the
+// entries of pos[pos_off[i] : pos_off[i+1]] (SOURCE token coordinates; pos_off int32 [n+1] clamped to [0,total], hi < lo: none;
+// pos_off null: pos[i] alone) that land on a body column become mask_idx, or with tok (int32 [n]) tok[i], a tok[i] outside
+// [0,V) substituting nothing.  esmk_op_mask_rows: pos; _mask_rows_multi: pos_off, pos; _substitute_rows: pos, tok (all three
+// Tw = T, no head or tail); _window_rows: everything but tok
+hipError_t launch_copy_rows(const int64_t* tokens, const int* src_row, const int* start, const int* pos_off, const int* pos,
+                            const int* tok, int64_t* out, int B, int T, int n, int Tw, int total, int V, int head_tok, int tail_tok,
                             int mask_idx, hipStream_t st);
-// the same with a LIST of positions per copy (multi-mutant variants): pos[pos_off[i] : pos_off[i+1]] of row i set to mask_idx;
-// pos_off int32 [n+1] (clamped to [0,total]; hi < lo: no position), pos int32 [total] (outside [0,T): masks nothing)
-hipError_t launch_mask_rows_multi(const int64_t* tokens, const int* src_row, const int* pos_off, const int* pos, int64_t* out,
-                                  int B, int T, int n, int total, int mask_idx, hipStream_t st);
-// the same into ONE packed row space of `rows` rows (esmk_forward_packed_rows): copy i = the first seg_len[i] tokens of
+// mask_rows_multi into ONE packed row space of `rows` rows (esmk_forward_packed_rows): copy i = the first seg_len[i] tokens of
 // tokens[src_row[i]] at out[seg_start[i] ...], its positions masked, the gap up to seg_start[i+1] (rows for the last copy) filled
 // with pad_idx; src_row, seg_start, seg_len int32 [n] (clamped: row to [0,B), length to [0,T], written range to [0,rows))
 hipError_t launch_mask_rows_packed(const int64_t* tokens, const int* src_row, const int* seg_start, const int* seg_len,
@@ -233,13 +240,7 @@ hipError_t launch_score_rows(const float* lp, const int* wt, const int* mt, cons
 // sequence (no atomics); target clamped to [0,V), offsets to [0,n_rows]
 hipError_t launch_sum_target_rows(const float* lp, const int* target, const int* off, double* out, int n_rows, int n_seq, int V,
                                   hipStream_t st);
-// windows.hip — proteins longer than the model's window (esm_amd/windows.py).  out int64 [n,Tw]: copy i, column c =
-// tokens[src_row[i], start[i] + c - h] (h = 1 if head_tok >= 0; row and column clamped), column 0 = head_tok and column Tw - 1 =
-// tail_tok where those are >= 0; the entries of pos[pos_off[i] : pos_off[i+1]] (SOURCE token coordinates) that land on a body
-// column become mask_idx
-hipError_t launch_window_rows(const int64_t* tokens, const int* src_row, const int* start, const int* pos_off, const int* pos,
-                              int64_t* out, int B, int T, int n, int Tw, int total, int head_tok, int tail_tok, int mask_idx,
-                              hipStream_t st);
+// windows.hip — proteins longer than the model's window (esm_amd/windows.py; the window copies are launch_copy_rows).
 // out fp32 [n_out,E]: out[r] = (sum_k w[k] x[src[k]]) / sum_k w[k], k ascending in [off[r], off[r+1]), fp32, one lane per
 // element; ONE entry: the row exactly; none: zeros; x [N,E] of any dtype code, E % 4 == 0, src clamped to [0,N)
 hipError_t launch_blend_rows(const void* x, int x_dtype, const int* off, const int* src, const float* w, float* out, int N, int E,
@@ -256,17 +257,14 @@ hipError_t launch_permute_positions(const int* pos_off, const int* pos_in, const
                                     int total, unsigned long long seed, int epoch, hipStream_t st);
 // one token per row of lp fp32 [n,V], V <= 64, from the candidates (bits of `allowed` below V, minus exclude[i]): tempered
 // inverse-CDF draw with the uniform of counter (row_chain[i], step, 1, row_index[i]), or the argmax for inv_temperature == 0;
-// token_out int32 [n] (-1: no candidate), logq_out fp32 [n], u_out fp32 [n] (optional); exclude int32 [n] (optional)
-hipError_t launch_sample_rows(const float* lp, const int* row_chain, const int* row_index, const int* exclude,
-                              unsigned long long allowed, float inv_temperature, unsigned long long seed, int step,
-                              int* token_out, float* logq_out, float* u_out, int n, int V, hipStream_t st);
-// launch_sample_rows with a top-k / nucleus filter in front of the draw (rank by the fp32 inputs, fp32 weights added in rank
-// order; top_k == 0 and top_p == 1: off, the bits of launch_sample_rows) and a per-row score over the unfiltered candidates
+// token_out int32 [n] (-1: no candidate), logq_out fp32 [n], u_out fp32 [n] (optional); exclude int32 [n] (optional).
+// A top-k / nucleus filter stands in front of the draw (rank by the fp32 inputs, fp32 weights added in rank order; top_k == 0
+// and top_p == 1: off, the plain draw of esmk_op_sample_rows), and a per-row score over the unfiltered candidates goes with it
 // (score_kind 0 none, 1 max log q, 2 sum q log q; fp64, rounded once); score_out fp32 [n], kept_out uint64 [n] (optional)
-hipError_t launch_sample_rows_ex(const float* lp, const int* row_chain, const int* row_index, const int* exclude,
-                                 unsigned long long allowed, float inv_temperature, unsigned long long seed, int step, int top_k,
-                                 float top_p, int score_kind, int* token_out, float* logq_out, float* u_out, float* score_out,
-                                 unsigned long long* kept_out, int n, int V, hipStream_t st);
+hipError_t launch_sample_rows(const float* lp, const int* row_chain, const int* row_index, const int* exclude,
+                              unsigned long long allowed, float inv_temperature, unsigned long long seed, int step, int top_k,
+                              float top_p, int score_kind, int* token_out, float* logq_out, float* u_out, float* score_out,
+                              unsigned long long* kept_out, int n, int V, hipStream_t st);
 // per chain c (rows row_off[c] : row_off[c+1] of score fp32 [n]) the sel_off[c+1] - sel_off[c] rows of the largest score, best
 // first, into sel_out[sel_off[c] ..], the others in ascending row order into rest_out[rest_off[c] ..]; one workgroup per chain
 hipError_t launch_select_rows(const float* score, const int* row_off, const int* sel_off, const int* rest_off, int* sel_out,
@@ -286,13 +284,16 @@ hipError_t launch_propose_mutations(const int64_t* tokens, const int* slot, cons
 // fp64, one workgroup per chain, fixed order; count[b] = the terms, 0 terms: energy 0
 hipError_t launch_contact_energy(const float* contacts, const unsigned char* target, double* energy_out, int* count_out, int B, int S,
                                  int min_sep, int kind, hipStream_t st);
-// E' = w_contact * e_contact[c] + w_lm * -(lp_sum[c] / n_res[c]); accept iff tok >= 0 and (a >= 0 or u < exp(a)), a = -(E' - e_cur[c])
-// * inv_temperature + hastings[c]; +inf: iff E' <= e_cur[c].  On acceptance the token, e_cur and the component energies are written
+// E' = (w_contact * e_contact[c] + w_lm * -(lp_sum[c] / n_res[c])) + w_extra * e_extra[c] (e_extra null: the sum of two); accept iff
+// tok >= 0 and (a >= 0 or u < exp(a)), a = -(E' - e_cur[c]) * inv_t + hastings[c]; +inf: iff E' <= e_cur[c].  inv_t = inv_t0, or with
+// a table (device fp64 [n_rung]) inv_t_tab[clamp(rung[c])] (rung null: entry 0).  On acceptance the token, e_cur and the
+// component energies are written
 hipError_t launch_mh_accept(int64_t* tokens, const int* slot, const int* site, const int* tok, const int* chain_id,
-                            const double* e_contact, const double* lp_sum, const int* n_res, const double* hastings, double w_contact,
-                            double w_lm, double inv_temperature, unsigned long long seed, int step, double* e_cur,
-                            double* e_contact_cur, double* e_lm_cur, unsigned char* accepted_out, double* u_out, double* e_prop_out,
-                            int n_chain, int B, int T, hipStream_t st);
+                            const double* e_contact, const double* lp_sum, const int* n_res, const double* hastings,
+                            const double* e_extra, double w_contact, double w_lm, double w_extra, const double* inv_t_tab,
+                            double inv_t0, const int* rung, int n_rung, unsigned long long seed, int step, double* e_cur,
+                            double* e_contact_cur, double* e_lm_cur, double* e_extra_cur, unsigned char* accepted_out, double* u_out,
+                            double* e_prop_out, int n_chain, int B, int T, hipStream_t st);
 // h[c] = (double)inv_t_prop * ((double)lp[c, old[c]] - (double)lp[c, new[c]]); a token outside [0,V): 0
 hipError_t launch_hastings_rows(const float* lp, const int* old_tok, const int* new_tok, float inv_t_prop, double* h_out, int n, int V,
                                 hipStream_t st);
@@ -306,24 +307,13 @@ struct NgramTables {
 // A <= 32 letters; such a window is left out); one workgroup per chain, fixed order; S <= 32768
 hipError_t launch_ngram_energy(const int64_t* tokens, const int* code, const NgramTables& q, double* energy_out, int B, int T,
                                int first, int S, int V, int A, int order_mask, hipStream_t st);
-// launch_mh_accept with inv_temperature = inv_t_tab[clamp(rung[c])] (rung null: entry 0) and E' = (w_contact * e_c + w_lm * e_lm) +
-// w_extra * e_extra[c] (e_extra null: the sum of two, the bits of launch_mh_accept); e_extra_cur written on acceptance
-hipError_t launch_mh_accept_ex(int64_t* tokens, const int* slot, const int* site, const int* tok, const int* chain_id,
-                               const double* e_contact, const double* lp_sum, const int* n_res, const double* hastings,
-                               const double* e_extra, double w_contact, double w_lm, double w_extra, const double* inv_t_tab,
-                               const int* rung, int n_rung, unsigned long long seed, int step, double* e_cur, double* e_contact_cur,
-                               double* e_lm_cur, double* e_extra_cur, unsigned char* accepted_out, double* u_out, double* e_prop_out,
-                               int n_chain, int B, int T, hipStream_t st);
+// (the acceptance with a temperature per chain and a third energy term is launch_mh_accept, design.hip)
 // swap round `round` of n_ladder ladders of K consecutive slots: the chains at rungs k and k + 1, k % 2 == round % 2, exchange
 // their rungs iff a >= 0 or u < exp(a), a = (inv_t[k] - inv_t[k+1]) * (e_cur[x] - e_cur[y]), u at counter (ladder_id, round, 4, k)
 hipError_t launch_replica_swap(int* rung, const double* e_cur, const double* inv_t, const int* ladder_id, unsigned long long seed,
                                int round, unsigned char* accepted_out, double* u_out, int n_ladder, int K, hipStream_t st);
 // jacobian.hip — the categorical Jacobian J[i,a,j,b] fp32 [L,nA,L,nA] of one protein (esm_amd/jacobian.py); nA <= 32, every
-// index into J 64 bit, every sum fp64 in a fixed order, no atomics.
-// out int64 [n,T]: row i = tokens[src_row[i]] (row 0 when src_row is null; clamped to [0,B)) with position pos[i] set to
-// tok[i]; a position outside [0,T) or a token outside [0,V) substitutes nothing
-hipError_t launch_substitute_rows(const int64_t* tokens, const int* src_row, const int* pos, const int* tok, int64_t* out, int B,
-                                  int T, int n, int V, hipStream_t st);
+// index into J 64 bit, every sum fp64 in a fixed order, no atomics.  (The substituted copies are launch_copy_rows.)
 // out [n_copies,L,nA] (the slice of J at the chunk's first copy): out[c,j,b] = logits[c*L+j, cols[b]] - wt[j, cols[b]] in fp32;
 // logits fp32 [n_copies*L,V], wt fp32 [L,V], cols int32 [nA] clamped to [0,V)
 hipError_t launch_jacobian_scatter(const float* logits, const float* wt, const int* cols, float* out, int n_copies, int L, int nA,

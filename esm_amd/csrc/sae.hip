@@ -4,7 +4,7 @@
 // feature f is ACTIVE iff z[f] > threshold[f] (thresholds >= 0: a NaN is never active, +inf is).  The product is the existing
 // dense GEMM over the f16x3 operand images (hi | hi | lo rows against hi | lo | hi weights, fp32 store epilogue); the kernels
 // here are what stands around it, one launch each, no global atomics, nothing that depends on the order lanes arrive in:
-//     sae_rows_kernel         gather the scored rows, form u, write the hi | hi | lo image the GEMM reads
+//     image_rows_kernel       (elementwise.hip) gather the scored rows, form u, write the hi | hi | lo image the GEMM reads
 //     sae_topk_kernel         per row: count the actives and select the k best, value descending, ties to the lower index
 //     sae_segment_max_kernel  per (sequence, feature): the largest activation over the sequence's rows and where it was
 //     sae_decode_kernel       x^ = inv_scale (b_dec + sum_r values[r] w_dec[indices[r]]), one rounded product and add per term
@@ -19,19 +19,6 @@ using namespace esmk_host;
 
 namespace {
 
-ESMK_DEV float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-ESMK_DEV float add_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-ESMK_DEV float sub_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-
 // The candidates of a row that the selection sorts in LDS.  A row with more actives goes through the radix select first.
 constexpr int kSaeCand = 1024;
 constexpr int kSaeMaxK = 256;
@@ -41,40 +28,6 @@ constexpr int kSaeMaxF = 65536;
 // the index below them the key is unique per feature and "key descending" is "value descending, ties to the lower index".
 ESMK_DEV unsigned long long sae_key(float v, int f) {
     return ((unsigned long long)__builtin_bit_cast(unsigned int, v) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)f);
-}
-
-// ---- rows ---------------------------------------------------------------------------------------------------------------
-// One workgroup per scored row; thread t owns the float4 groups t, t + 256, ... of the Ep columns (E % 4 == 0 and Ep % 64 == 0:
-// a group never straddles E or a 64-column K tile).  rows null: row i of x.  Listed rows are device data, hence the clamp.
-__global__ __launch_bounds__(256) void sae_rows_kernel(const float* __restrict__ x, int ldx, int N, const int* __restrict__ rows,
-                                                       const float* __restrict__ b_dec, float scale, _Float16* __restrict__ out,
-                                                       int ldo, int E, int Ep) {
-    const int i = blockIdx.x;
-    int r = rows ? rows[i] : i;
-    r = min(max(r, 0), N - 1);
-    const float* xr = x + (size_t)r * ldx;
-    _Float16* o = out + (size_t)i * ldo;
-    for (int c4 = threadIdx.x; c4 < (Ep >> 2); c4 += 256) {
-        const int c = c4 << 2;
-        f32x4 u = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (c < E) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(xr + c);
-            const f32x4 b = b_dec ? *reinterpret_cast<const f32x4*>(b_dec + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) u[e] = sub_rn(mul_rn(scale, v[e]), b[e]);
-        }
-        f16x4 hi, lo;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            hi[e] = (_Float16)u[e];
-            const float rem = u[e] - (float)hi[e];  // exact in fp32
-            lo[e] = (_Float16)rem;
-        }
-        _Float16* t = o + (size_t)(c >> 6) * 192 + (c & 63);
-        *reinterpret_cast<f16x4*>(t) = hi;
-        *reinterpret_cast<f16x4*>(t + 64) = hi;
-        *reinterpret_cast<f16x4*>(t + 128) = lo;
-    }
 }
 
 // ---- top-k --------------------------------------------------------------------------------------------------------------
@@ -298,9 +251,8 @@ int esmk_op_sae_rows(const float* x_dev, int ldx, int N, const int32_t* rows_dev
     if (misaligned(x_dev, 16) || misaligned(b_dec_dev, 16) || misaligned(image_dev, 8)) return fail(w + ": x and b_dec must be 16-byte aligned, the image 8-byte aligned");
     if (!(input_scale == input_scale) || std::isinf(input_scale)) return fail(w + ": input_scale must be finite");
     if (n == 0) return 0;
-    hipLaunchKernelGGL(sae_rows_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, x_dev, ldx, N, rows_dev, b_dec_dev,
-                       input_scale, (_Float16*)image_dev, ld_image, E, Ep);
-    ESMK_TRY(hipGetLastError());
+    ESMK_TRY(launch_image_rows(x_dev, ldx, N, rows_dev, n, b_dec_dev, input_scale, /*cosine=*/0, /*b_side=*/0, /*zero_negative=*/0,
+                               image_dev, ld_image, E, (hipStream_t)stream));
     return 0;
 }
 

@@ -5,7 +5,7 @@
 // on one stream, and every random number is addressed by (seed, chain id, epoch or step, purpose, index): it depends on
 // nothing else, so a chain draws the same tokens alone, in a batch, and in any launch geometry.  Confidence-ordered unmasking
 // (inpaint(order=...)) replaces the shuffle by a score per row and a per-chain choice of the best rows: esmk_forward_rows on
-// every remaining <mask> row -> sample_rows_ex_kernel (top-k / nucleus filter, draw, score) -> select_rows_kernel -> commit.
+// every remaining <mask> row -> sample_rows_kernel (top-k / nucleus filter, draw, score) -> select_rows_kernel -> commit.
 #include "common.h"
 #include "kernels.h"
 #include "philox.h"
@@ -46,84 +46,6 @@ hipError_t launch_permute_positions(const int* pos_off, const int* pos_in, const
     return hipGetLastError();
 }
 
-// One token per row of log-probabilities [n, V], V <= 64: one wavefront per row, one vocabulary entry per lane.
-//   u      = (word0(row_chain[i], step, 1, row_index[i]) >> 8) * 2^-24: exact in fp32, in [0, 1)
-//   cand   = the bits of allowed_mask below V, minus the token exclude[i] (when that is inside [0, V))
-//   inv_temperature > 0:  z_v = lp[v] * inv_temperature, m = max over cand of z, w_v = expf(z_v - m) on cand (0 elsewhere);
-//          the running sum c_v = w_0 + ... + w_v is added in fp32 in ascending token order — every lane walks the lanes
-//          0 .. 63 through a shuffle and adds the ones at or below itself, so lane v holds exactly the sequential sum and the
-//          last lane the total; token = the first candidate with c_v > u * total, the last candidate if there is none;
-//          logq = z_tok - m - log(total), taken in fp64 from the fp32 inputs and rounded to fp32 once
-//   inv_temperature == 0: the candidate with the largest lp, ties to the lowest index; logq = 0
-//   cand empty: token = -1, logq = 0
-//   every candidate at -inf (no log_softmax of finite logits gives that): m = -inf, every w is NaN, no running sum exceeds
-//          the threshold: token = the last candidate, logq = NaN.  Greedy takes the lowest candidate (all tie at -inf).
-// Nothing depends on the row's place in the launch.  expf is the precise one.
-__global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restrict__ lp, const int* __restrict__ row_chain,
-                                                          const int* __restrict__ row_index, const int* __restrict__ exclude,
-                                                          unsigned long long allowed, float inv_temperature,
-                                                          unsigned long long seed, int step, int* __restrict__ token_out,
-                                                          float* __restrict__ logq_out, float* __restrict__ u_out, int n, int V) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= n) return;  // wave uniform
-    const float u = (float)(philox_word0(seed, row_chain[row], step, kPurposeToken, row_index[row]) >> 8) * 0x1p-24f;
-    unsigned long long cand = V < 64 ? allowed & ((1ull << V) - 1) : allowed;
-    if (exclude != nullptr) {
-        const int ex = exclude[row];
-        if (ex >= 0 && ex < V) cand &= ~(1ull << ex);
-    }
-    const bool mine = (cand >> lane) & 1ull;  // lanes at or past V never are
-    const float x = mine ? lp[(size_t)row * V + lane] : -INFINITY;
-    int token = -1;
-    float logq = 0.f;
-    if (cand != 0ull) {  // wave uniform
-        const float z = inv_temperature > 0.f ? x * inv_temperature : x;  // (-inf stays -inf: inv_temperature > 0)
-        float m = z;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        if (inv_temperature > 0.f) {
-            const float w = mine ? expf(z - m) : 0.f;
-            float cum = 0.f;
-            for (int v = 0; v < V; ++v) {  // ascending token order, the same additions in every lane up to its own entry
-                const float wv = __shfl(w, v, 64);
-                if (v <= lane) cum += wv;
-            }
-            const float total = __shfl(cum, V - 1, 64);
-            const float thr = u * total;
-            const unsigned long long over = __ballot(mine && cum > thr);
-            token = over != 0ull ? __ffsll((long long)over) - 1 : 63 - __clzll((long long)cand);
-            // logq in fp64 from the fp32 inputs, rounded once: the fp32 chain z_tok - m - logf(total) lost up to 1.2 ulp of the
-            // result (5.6e-7 at logq = -4.9).  Butterfly reductions: every lane ends with the same bits.
-            const double zd = mine ? (double)x * (double)inv_temperature : -INFINITY;
-            double md = zd;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) md = fmax(md, __shfl_xor(md, o, 64));
-            double sd = mine ? exp(zd - md) : 0.0;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) sd += __shfl_xor(sd, o, 64);
-            logq = (float)(__shfl(zd, token, 64) - md - log(sd));
-        } else {
-            const unsigned long long top = __ballot(mine && x == m);  // (a row of NaNs only: no lane; the last candidate)
-            token = top != 0ull ? __ffsll((long long)top) - 1 : 63 - __clzll((long long)cand);
-        }
-    }
-    if (lane == 0) {
-        token_out[row] = token;
-        logq_out[row] = logq;
-        if (u_out != nullptr) u_out[row] = u;
-    }
-}
-
-hipError_t launch_sample_rows(const float* lp, const int* row_chain, const int* row_index, const int* exclude,
-                              unsigned long long allowed, float inv_temperature, unsigned long long seed, int step,
-                              int* token_out, float* logq_out, float* u_out, int n, int V, hipStream_t st) {
-    if (!lp || !row_chain || !row_index || !token_out || !logq_out || n <= 0 || V <= 0 || V > 64 || !(inv_temperature >= 0.f))
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sample_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, lp, row_chain, row_index, exclude,
-                       allowed, inv_temperature, seed, step, token_out, logq_out, u_out, n, V);
-    return hipGetLastError();
-}
-
 // v ranks before w in a best-first order of fp32 values: the larger value first, equal values by the lower index, NaN behind
 // everything (-inf included), among NaNs the lower index first.  Comparison logic only: a total order on (value, index).
 __device__ inline bool ranks_before(float xv, int v, float xw, int w) {
@@ -132,30 +54,43 @@ __device__ inline bool ranks_before(float xv, int v, float xw, int w) {
     return xv > xw || (xv == xw && v < w);
 }
 
-// sample_rows_kernel with a top-k / nucleus filter in front of the draw and a confidence score per row.  u, cand, z, m and
-// w_v = expf(z_v - m) are those of sample_rows_kernel.
+// One token per row of log-probabilities [n, V], V <= 64: one wavefront per row, one vocabulary entry per lane.  The one
+// statement of the draw: esmk_op_sample_rows is this kernel with both filters off and no score, esmk_op_sample_rows_ex all of it.
+//   u      = (word0(row_chain[i], step, 1, row_index[i]) >> 8) * 2^-24: exact in fp32, in [0, 1)
+//   cand   = the bits of allowed_mask below V, minus the token exclude[i] (when that is inside [0, V))
+//   z_v    = lp[v] * inv_temperature (greedy, inv_temperature == 0: lp[v]), m = max over cand of z, w_v = expf(z_v - m) on cand
+//          (0 elsewhere); expf is the precise one
 //   rank   of candidate v = the number of candidates that rank before it by the fp32 INPUT lp (ranks_before; inv_temperature
 //          > 0, so that is the order of the tempered values): every lane counts over a shuffle of the 64 lanes
 //   E_r    = the fp32 sum of the weights of the ranks before r, added in rank order: the wave walks the ranks 0, 1, ... (the
 //          lane holding rank r is found by a ballot, its weight broadcast) and every lane adds the ones before its own rank;
 //          W = the same sum over all candidates
-//   kept   = rank 0, and every rank r with (top_k == 0 || r < top_k) && (top_p >= 1 || E_r < top_p * W).  Both filters off:
-//          kept = cand without any of this arithmetic, and everything below is sample_rows_kernel bit for bit
-//   draw   as in sample_rows_kernel over the kept set: fp32 running sums in ascending token order, the first kept token whose
-//          sum exceeds u * total (the last kept one if none does), logq in fp64 relative to the kept set, rounded once
-//   greedy (inv_temperature == 0): the argmax of lp over cand, whatever the filters say (it is rank 0: always kept); kept and
-//          score are computed with z = lp
+//   kept   = rank 0, and every rank r with (top_k == 0 || r < top_k) && (top_p >= 1 || E_r < top_p * W).  Both filters off
+//          (top_k == 0, top_p == 1): kept = cand without any of this arithmetic
+//   draw   (inv_temperature > 0) over the kept set: the running sum c_v = w_0 + ... + w_v is added in fp32 in ascending token
+//          order — every lane walks the lanes 0 .. 63 through a shuffle and adds the ones at or below itself, so lane v holds
+//          exactly the sequential sum and the last lane the total; token = the first kept token with c_v > u * total, the last
+//          kept one if there is none; logq = z_tok - m - log(total) relative to the kept set, taken in fp64 from the fp32
+//          inputs and rounded to fp32 once
+//   greedy (inv_temperature == 0): the argmax of lp over cand, ties to the lowest index, whatever the filters say (it is rank
+//          0: always kept); logq = 0; kept and score are computed with z = lp
 //   score  over cand, before filtering, in fp64 from the fp32 inputs, rounded to fp32 once: kind 1 = max log q = -log(sum of
 //          exp(z - m)), kind 2 = sum of q log q (terms with q == 0 count as 0), q = softmax(z); cand empty: -inf
-// A row whose candidates all hold -inf has NaN weights: kept = rank 0 alone when top_p < 1 (no comparison with NaN holds).
-__global__ __launch_bounds__(256) void sample_rows_ex_kernel(const float* __restrict__ lp, const int* __restrict__ row_chain,
-                                                             const int* __restrict__ row_index, const int* __restrict__ exclude,
-                                                             unsigned long long allowed, float inv_temperature,
-                                                             unsigned long long seed, int step, int top_k, float top_p,
-                                                             int score_kind, int* __restrict__ token_out,
-                                                             float* __restrict__ logq_out, float* __restrict__ u_out,
-                                                             float* __restrict__ score_out,
-                                                             unsigned long long* __restrict__ kept_out, int n, int V) {
+//   cand empty: token = -1, logq = 0
+//   every candidate at -inf (no log_softmax of finite logits gives that): m = -inf, every w is NaN, no running sum exceeds
+//          the threshold: token = the last kept candidate, logq = NaN; kept = rank 0 alone when top_p < 1 (no comparison with
+//          NaN holds).  Greedy takes the lowest candidate (all tie at -inf).
+// Nothing depends on the row's place in the launch.  EX = false leaves the filters, the score and the kept set out of the
+// compiled code (the launcher takes it when none of them is asked for): the same statements, so the same bits.
+template <bool EX>
+__global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restrict__ lp, const int* __restrict__ row_chain,
+                                                          const int* __restrict__ row_index, const int* __restrict__ exclude,
+                                                          unsigned long long allowed, float inv_temperature,
+                                                          unsigned long long seed, int step, int top_k, float top_p,
+                                                          int score_kind, int* __restrict__ token_out,
+                                                          float* __restrict__ logq_out, float* __restrict__ u_out,
+                                                          float* __restrict__ score_out,
+                                                          unsigned long long* __restrict__ kept_out, int n, int V) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n) return;  // wave uniform
     const float u = (float)(philox_word0(seed, row_chain[row], step, kPurposeToken, row_index[row]) >> 8) * 0x1p-24f;
@@ -176,7 +111,7 @@ __global__ __launch_bounds__(256) void sample_rows_ex_kernel(const float* __rest
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
         const float w = mine ? expf(z - m) : 0.f;
-        if (top_k != 0 || top_p < 1.f) {  // wave uniform
+        if (EX && (top_k != 0 || top_p < 1.f)) {  // wave uniform
             int rank = 0;
             for (int v = 0; v < V; ++v) {
                 const float xv = __shfl(x, v, 64);
@@ -205,6 +140,8 @@ __global__ __launch_bounds__(256) void sample_rows_ex_kernel(const float* __rest
             const float thr = u * total;
             const unsigned long long over = __ballot(held && cum > thr);
             token = over != 0ull ? __ffsll((long long)over) - 1 : 63 - __clzll((long long)kept);
+            // logq in fp64 from the fp32 inputs, rounded once: the fp32 chain z_tok - m - logf(total) lost up to 1.2 ulp of the
+            // result (5.6e-7 at logq = -4.9).  Butterfly reductions: every lane ends with the same bits.
             const double zd = held ? (double)x * (double)inv_temperature : -INFINITY;
             double md = zd;
 #pragma unroll
@@ -217,7 +154,7 @@ __global__ __launch_bounds__(256) void sample_rows_ex_kernel(const float* __rest
             const unsigned long long top = __ballot(mine && x == m);  // (a row of NaNs only: no lane; the last candidate)
             token = top != 0ull ? __ffsll((long long)top) - 1 : 63 - __clzll((long long)cand);
         }
-        if (score_kind != 0) {  // butterfly reductions: every lane ends with the same bits
+        if (EX && score_kind != 0) {  // butterfly reductions: every lane ends with the same bits
             const double zd = mine ? (double)x * (double)scale : -INFINITY;
             double md = zd;
 #pragma unroll
@@ -243,22 +180,23 @@ __global__ __launch_bounds__(256) void sample_rows_ex_kernel(const float* __rest
         token_out[row] = token;
         logq_out[row] = logq;
         if (u_out != nullptr) u_out[row] = u;
-        if (score_out != nullptr && score_kind != 0) score_out[row] = score;
-        if (kept_out != nullptr) kept_out[row] = kept;
+        if (EX && score_out != nullptr && score_kind != 0) score_out[row] = score;
+        if (EX && kept_out != nullptr) kept_out[row] = kept;
     }
 }
 
-hipError_t launch_sample_rows_ex(const float* lp, const int* row_chain, const int* row_index, const int* exclude,
-                                 unsigned long long allowed, float inv_temperature, unsigned long long seed, int step, int top_k,
-                                 float top_p, int score_kind, int* token_out, float* logq_out, float* u_out, float* score_out,
-                                 unsigned long long* kept_out, int n, int V, hipStream_t st) {
+hipError_t launch_sample_rows(const float* lp, const int* row_chain, const int* row_index, const int* exclude,
+                              unsigned long long allowed, float inv_temperature, unsigned long long seed, int step, int top_k,
+                              float top_p, int score_kind, int* token_out, float* logq_out, float* u_out, float* score_out,
+                              unsigned long long* kept_out, int n, int V, hipStream_t st) {
     if (!lp || !row_chain || !row_index || !token_out || !logq_out || n <= 0 || V <= 0 || V > 64 || !(inv_temperature >= 0.f) ||
         top_k < 0 || top_k > 64 || !(top_p > 0.f && top_p <= 1.f) || score_kind < 0 || score_kind > 2 ||
         (score_kind != 0 && !score_out))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sample_rows_ex_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, lp, row_chain, row_index, exclude,
-                       allowed, inv_temperature, seed, step, top_k, top_p, score_kind, token_out, logq_out, u_out, score_out,
-                       kept_out, n, V);
+    const bool ex = top_k != 0 || top_p < 1.f || score_kind != 0 || kept_out != nullptr;
+    hipLaunchKernelGGL(ex ? sample_rows_kernel<true> : sample_rows_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, lp,
+                       row_chain, row_index, exclude, allowed, inv_temperature, seed, step, top_k, top_p, score_kind, token_out,
+                       logq_out, u_out, score_out, kept_out, n, V);
     return hipGetLastError();
 }
 

@@ -9,63 +9,72 @@
 
 namespace esmk {
 
-// out[i, :] = tokens[src_row[i], :] with position pos[i] replaced by mask_idx — the clone-and-assign of the reference's
-// masked-marginal loop for a whole chunk of positions at once.  src_row == nullptr: every row comes from tokens[0].  A
-// source row outside [0, B) is clamped; a position outside [0, T) masks nothing.
-__global__ __launch_bounds__(256) void mask_rows_kernel(const int64_t* __restrict__ tokens, const int* __restrict__ src_row,
-                                                        const int* __restrict__ pos, int64_t* __restrict__ out, int B, int T,
-                                                        int n, int64_t mask_idx) {
-    const size_t total = (size_t)n * T;
-    const size_t stride = (size_t)gridDim.x * 256;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += stride) {
-        const int i = (int)(e / T), t = (int)(e - (size_t)i * T);
-        const int b = src_row ? min(max(src_row[i], 0), B - 1) : 0;
-        out[e] = t == pos[i] ? mask_idx : tokens[(size_t)b * T + t];
-    }
-}
-
-hipError_t launch_mask_rows(const int64_t* tokens, const int* src_row, const int* pos, int64_t* out, int B, int T, int n,
-                            int mask_idx, hipStream_t st) {
-    if (B <= 0 || T <= 0 || n <= 0) return hipErrorInvalidValue;
-    const size_t total = (size_t)n * T;
-    const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 8192);
-    hipLaunchKernelGGL(mask_rows_kernel, dim3(blocks), dim3(256), 0, st, tokens, src_row, pos, out, B, T, n, (int64_t)mask_idx);
-    return hipGetLastError();
-}
-
-// out[i, :] = tokens[src_row[i], :] with every position of pos[pos_off[i] : pos_off[i + 1]] replaced by mask_idx: the joint
-// mask of a multi-mutant variant (all mutated positions masked in one forward).  One workgroup per copy, copies strided over
-// the grid; the row is copied, then (behind the barrier, so that the mask lands on top of the copy) the lanes stride over the
-// copy's position list.  All of the lists are device data the host never saw: a source row outside [0, B) is clamped, the
-// offsets are clamped to [0, total] (hi < lo: an empty list, a plain copy), a position outside [0, T) masks nothing, and a
-// repeated position stores the same value twice.
-__global__ __launch_bounds__(256) void mask_rows_multi_kernel(const int64_t* __restrict__ tokens, const int* __restrict__ src_row,
-                                                              const int* __restrict__ pos_off, const int* __restrict__ pos,
-                                                              int64_t* __restrict__ out, int B, int T, int n, int total,
-                                                              int64_t mask_idx) {
+// Every token copy with listed positions overwritten, in one kernel: the masked batch of the masked-marginal strategy
+// (esmk_op_mask_rows: the clone-and-assign of the reference's loop for a whole chunk of positions at once), the joint mask of a
+// multi-mutant variant (esmk_op_mask_rows_multi), the substituted copies of the categorical Jacobian (esmk_op_substitute_rows)
+// and the window copies of a protein longer than the model's window (esmk_op_window_rows).
+// Copy i, column c, holds tokens[clamp(src_row[i]), clamp(start[i] + c - h)], h = 1 if head_tok >= 0 else 0; column 0 is
+// head_tok when head_tok >= 0 and column Tw - 1 is tail_tok when tail_tok >= 0 (a wrapped window: a fragment tokenised as
+// the alphabet tokenises the substring; both negative: a raw token slice).  The entries of pos[pos_off[i] : pos_off[i + 1]] are
+// token coordinates of the SOURCE row: entry p becomes mask_idx at column p - start[i] + h where that is a body column (not
+// an overridden one) of the copy; any other entry masks nothing.  One workgroup per copy, copies strided over the grid; the
+// row is written, then (behind the barrier, so that the mask lands on top of the copy) the lanes stride over the copy's list.
+// A source row outside [0, B) and a source column outside [0, T) are clamped, the offsets to [0, total] (hi < lo: an empty
+// list, a plain copy), a repeated entry stores the same value twice.  Columns are computed in 64 bits: no start overflows.
+// What the three plain forms leave out is null: src_row (every copy comes from tokens[0]), start (0: with Tw = T and no head or
+// tail a position is its own column, and one outside [0, T) masks nothing), pos_off (the list of copy i is pos[i] alone), and
+// tok, the replacement token per copy in place of mask_idx: a tok[i] outside [0, V) substitutes nothing.
+__global__ __launch_bounds__(256) void copy_rows_kernel(const int64_t* __restrict__ tokens, const int* __restrict__ src_row,
+                                                        const int* __restrict__ start, const int* __restrict__ pos_off,
+                                                        const int* __restrict__ pos, const int* __restrict__ tok,
+                                                        int64_t* __restrict__ out, int B, int T, int n, int Tw, int total, int V,
+                                                        int64_t head_tok, int64_t tail_tok, int64_t mask_idx) {
+    const int h = head_tok >= 0 ? 1 : 0;
+    const int body_end = tail_tok >= 0 ? Tw - 1 : Tw;  // body columns: [h, body_end)
     for (int i = blockIdx.x; i < n; i += gridDim.x) {  // workgroup uniform: every lane reaches the barrier
         const int b = src_row ? min(max(src_row[i], 0), B - 1) : 0;
+        const long long s = (start ? (long long)start[i] : 0ll) - h;  // source column of copy column 0
         const int64_t* in = tokens + (size_t)b * T;
-        int64_t* o = out + (size_t)i * T;
-        for (int t = threadIdx.x; t < T; t += 256) o[t] = in[t];
+        int64_t* o = out + (size_t)i * Tw;
+        // the list's bounds, the replacement and the lane's first entry are read in front of the copy: their latency passes
+        // under it instead of standing behind the barrier
+        int lo = i, hi = i + 1;
+        if (pos_off) lo = min(max(pos_off[i], 0), total), hi = min(max(pos_off[i + 1], 0), total);
+        int64_t v = mask_idx;
+        if (tok) {
+            v = tok[i];
+            if (v < 0 || v >= V) hi = lo;
+        }
+        int j = lo + (int)threadIdx.x;
+        long long at = j < hi ? (long long)pos[j] - s : -1;  // the copy column of entry j; -1 is no body column
+#pragma unroll 4
+        for (int c = threadIdx.x; c < Tw; c += 256) {
+            const long long t = min(max(s + c, 0ll), (long long)T - 1);
+            int64_t x = in[t];
+            if (c == Tw - 1 && tail_tok >= 0) x = tail_tok;
+            if (c == 0 && head_tok >= 0) x = head_tok;
+            o[c] = x;
+        }
         __syncthreads();
-        const int lo = min(max(pos_off[i], 0), total), hi = min(max(pos_off[i + 1], 0), total);
-        for (int j = lo + (int)threadIdx.x; j < hi; j += 256) {
-            const int p = pos[j];
-            if (p >= 0 && p < T) o[p] = mask_idx;
+        while (j < hi) {
+            if (at >= h && at < body_end) o[at] = v;
+            j += 256;
+            if (j < hi) at = (long long)pos[j] - s;
         }
     }
 }
 
-hipError_t launch_mask_rows_multi(const int64_t* tokens, const int* src_row, const int* pos_off, const int* pos, int64_t* out,
-                                  int B, int T, int n, int total, int mask_idx, hipStream_t st) {
-    if (!tokens || !pos_off || !pos || !out || B <= 0 || T <= 0 || n <= 0 || total < 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mask_rows_multi_kernel, dim3((unsigned)std::min(n, 8192)), dim3(256), 0, st, tokens, src_row, pos_off, pos,
-                       out, B, T, n, total, (int64_t)mask_idx);
+hipError_t launch_copy_rows(const int64_t* tokens, const int* src_row, const int* start, const int* pos_off, const int* pos,
+                            const int* tok, int64_t* out, int B, int T, int n, int Tw, int total, int V, int head_tok, int tail_tok,
+                            int mask_idx, hipStream_t st) {
+    if (!tokens || !pos || !out || B <= 0 || T <= 0 || n <= 0 || Tw <= 0 || (pos_off && total < 0) || (tok && V <= 0))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)std::min(n, 8192)), dim3(256), 0, st, tokens, src_row, start, pos_off, pos,
+                       tok, out, B, T, n, Tw, total, V, (int64_t)head_tok, (int64_t)tail_tok, (int64_t)mask_idx);
     return hipGetLastError();
 }
 
-// The packed counterpart of mask_rows_multi_kernel (esmk_forward_packed_rows): copy i is the first seg_len[i] tokens of
+// The packed counterpart of esmk_op_mask_rows_multi (esmk_forward_packed_rows): copy i is the first seg_len[i] tokens of
 // tokens[src_row[i]], written to out[seg_start[i] : seg_start[i] + seg_len[i]] of ONE row space of `rows` rows, with every
 // position of pos[pos_off[i] : pos_off[i + 1]] replaced by mask_idx; the gap behind the copy — up to seg_start[i + 1], or to
 // `rows` behind the last copy — is filled with pad_idx (esmk_forward_packed wants pad_idx in gap rows; nothing is assumed

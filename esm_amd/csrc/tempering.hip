@@ -1,7 +1,7 @@
 // tempering.hip — the two things lm-design has around its energy forward that design.hip left out (esm_amd/design.py): the n-gram
 // term of the energy (examples/lm-design/utils/ngram.py: a KL divergence between the n-gram frequencies of a sequence and a
-// background) and replica exchange — an acceptance with a temperature per chain and a third energy term, and the swap of
-// temperatures between the neighbouring rungs of a ladder.  As in design.hip none of them is a hot loop, every random number is
+// background) and replica exchange — the swap of temperatures between the neighbouring rungs of a ladder; the acceptance with a
+// temperature per chain and a third energy term is mh_accept_kernel of design.hip.  As in design.hip none of them is a hot loop, every random number is
 // addressed by its counter alone, there are no atomics, and every fp64 sum has an order fixed by the shape alone.
 #include "common.h"
 #include "kernels.h"
@@ -125,83 +125,6 @@ hipError_t launch_ngram_energy(const int64_t* tokens, const int* code, const Ngr
         if (((order_mask >> (n - 1)) & 1) && !q.q[n - 1]) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ngram_energy_kernel, dim3((unsigned)std::min(B, 8192)), dim3(256), 0, st, tokens, code, q, energy_out, B, T,
                        first, S, V, A, order_mask);
-    return hipGetLastError();
-}
-
-// esmk_op_mh_accept (design.hip: mh_accept_kernel) with a temperature per chain and a third energy term, everything in fp64 with
-// one rounding per operation:
-//   inv_t = inv_t_tab[clamp(rung[c], 0, n_rung - 1)] (rung null: entry 0)
-//   E'    = (w_contact * e_c + w_lm * e_lm) + w_extra * e_extra[c]; without e_extra the last addition is not made
-// and from there the rule of mh_accept_kernel: with e_extra null and one rung the outputs carry its bits.  On acceptance
-// e_extra_cur[c] = e_extra[c] where both arrays are given.
-__global__ __launch_bounds__(256) void mh_accept_ex_kernel(int64_t* __restrict__ tokens, const int* __restrict__ slot,
-                                                           const int* __restrict__ site, const int* __restrict__ tok,
-                                                           const int* __restrict__ chain_id, const double* __restrict__ e_contact,
-                                                           const double* __restrict__ lp_sum, const int* __restrict__ n_res,
-                                                           const double* __restrict__ hastings, const double* __restrict__ e_extra,
-                                                           double w_contact, double w_lm, double w_extra,
-                                                           const double* __restrict__ inv_t_tab, const int* __restrict__ rung,
-                                                           int n_rung, unsigned long long seed, int step, double* __restrict__ e_cur,
-                                                           double* __restrict__ e_contact_cur, double* __restrict__ e_lm_cur,
-                                                           double* __restrict__ e_extra_cur, unsigned char* __restrict__ accepted_out,
-                                                           double* __restrict__ u_out, double* __restrict__ e_prop_out, int n_chain,
-                                                           int B, int T) {
-    const size_t stride = (size_t)gridDim.x * 256;
-    for (size_t c = (size_t)blockIdx.x * 256 + threadIdx.x; c < (size_t)n_chain; c += stride) {
-        const double e_c = e_contact != nullptr ? e_contact[c] : 0.0;
-        double e_lm = 0.0;
-        if (lp_sum != nullptr && n_res != nullptr && n_res[c] > 0) e_lm = -(lp_sum[c] / (double)n_res[c]);
-        const double a_c = w_contact * e_c, a_lm = w_lm * e_lm;
-        double e_prop = a_c + a_lm;
-        double e_x = 0.0;
-        if (e_extra != nullptr) {
-            e_x = e_extra[c];
-            const double a_x = w_extra * e_x;
-            e_prop = e_prop + a_x;
-        }
-        const double dE = e_prop - e_cur[c];
-        const double h = hastings != nullptr ? hastings[c] : 0.0;
-        const double u = (double)(philox_word0(seed, chain_id[c], step, kPurposeAcceptance, 0) >> 8) * 0x1p-24;
-        const double inv_temperature = inv_t_tab[rung != nullptr ? min(max(rung[c], 0), n_rung - 1) : 0];
-        const int t = tok[c];
-        bool accept;
-        if (inv_temperature == (double)INFINITY) {
-            accept = t >= 0 && dE <= 0.0;
-        } else {
-            const double scaled = -dE * inv_temperature;
-            const double a = scaled + h;
-            accept = t >= 0 && (a >= 0.0 || u < exp(a));
-        }
-        if (accept) {
-            const int p = site[c];
-            if (p >= 0 && p < T) {
-                const int b = slot != nullptr ? min(max(slot[c], 0), B - 1) : min((int)c, B - 1);
-                tokens[(size_t)b * T + p] = (int64_t)t;
-            }
-            e_cur[c] = e_prop;
-            if (e_contact_cur != nullptr) e_contact_cur[c] = e_c;
-            if (e_lm_cur != nullptr) e_lm_cur[c] = e_lm;
-            if (e_extra_cur != nullptr && e_extra != nullptr) e_extra_cur[c] = e_x;
-        }
-        accepted_out[c] = accept ? 1 : 0;
-        if (u_out != nullptr) u_out[c] = u;
-        if (e_prop_out != nullptr) e_prop_out[c] = e_prop;
-    }
-}
-
-hipError_t launch_mh_accept_ex(int64_t* tokens, const int* slot, const int* site, const int* tok, const int* chain_id,
-                               const double* e_contact, const double* lp_sum, const int* n_res, const double* hastings,
-                               const double* e_extra, double w_contact, double w_lm, double w_extra, const double* inv_t_tab,
-                               const int* rung, int n_rung, unsigned long long seed, int step, double* e_cur, double* e_contact_cur,
-                               double* e_lm_cur, double* e_extra_cur, unsigned char* accepted_out, double* u_out, double* e_prop_out,
-                               int n_chain, int B, int T, hipStream_t st) {
-    if (!tokens || !site || !tok || !chain_id || !e_cur || !accepted_out || !inv_t_tab || n_rung <= 0 || n_chain <= 0 || B <= 0 ||
-        T <= 0 || (lp_sum != nullptr && n_res == nullptr))
-        return hipErrorInvalidValue;
-    const unsigned blocks = (unsigned)std::min<size_t>(((size_t)n_chain + 255) / 256, 8192);
-    hipLaunchKernelGGL(mh_accept_ex_kernel, dim3(blocks), dim3(256), 0, st, tokens, slot, site, tok, chain_id, e_contact, lp_sum, n_res,
-                       hastings, e_extra, w_contact, w_lm, w_extra, inv_t_tab, rung, n_rung, seed, step, e_cur, e_contact_cur,
-                       e_lm_cur, e_extra_cur, accepted_out, u_out, e_prop_out, n_chain, B, T);
     return hipGetLastError();
 }
 

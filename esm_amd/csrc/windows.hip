@@ -1,58 +1,12 @@
 // windows.hip — the small kernels of windowed scoring and embedding (esm_amd/windows.py): proteins longer than the model's
-// window are run as model-sized window copies built on the device, and the per-window outputs are stitched back into
-// full-length outputs.  None of them is a hot loop: the layer stack between them is the time.  All index lists are device
+// window are run as model-sized window copies built on the device (copy_rows_kernel, scoring.hip), and the per-window outputs
+// are stitched back into full-length outputs.  None of them is a hot loop: the layer stack between them is the time.  All index lists are device
 // data the host never saw: every index is clamped, nothing is read or written out of bounds; plain vector stores, no atomics.
 #include "common.h"
 #include "kernels.h"
 #include <algorithm>
 
 namespace esmk {
-
-// Copy i, column c, holds tokens[clamp(src_row[i]), clamp(start[i] + c - h)], h = 1 if head_tok >= 0 else 0; column 0 is
-// head_tok when head_tok >= 0 and column Tw - 1 is tail_tok when tail_tok >= 0 (a wrapped window: a fragment tokenised as
-// the alphabet tokenises the substring; both negative: a raw token slice).  The entries of pos[pos_off[i] : pos_off[i + 1]] are
-// token coordinates of the SOURCE row: entry p becomes mask_idx at column p - start[i] + h where that is a body column (not
-// an overridden one) of the copy; any other entry masks nothing.  One workgroup per copy, copies strided over the grid; the
-// row is written, then (behind the barrier, so that the mask lands on top of the copy) the lanes stride over the copy's list.
-// A source row outside [0, B) and a source column outside [0, T) are clamped, the offsets to [0, total] (hi < lo: an empty
-// list), a repeated entry stores the same value twice.  Columns are computed in 64 bits: no start overflows.
-__global__ __launch_bounds__(256) void window_rows_kernel(const int64_t* __restrict__ tokens, const int* __restrict__ src_row,
-                                                          const int* __restrict__ start, const int* __restrict__ pos_off,
-                                                          const int* __restrict__ pos, int64_t* __restrict__ out, int B, int T,
-                                                          int n, int Tw, int total, int64_t head_tok, int64_t tail_tok,
-                                                          int64_t mask_idx) {
-    const int h = head_tok >= 0 ? 1 : 0;
-    const int body_end = tail_tok >= 0 ? Tw - 1 : Tw;  // body columns: [h, body_end)
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {  // workgroup uniform: every lane reaches the barrier
-        const int b = min(max(src_row[i], 0), B - 1);
-        const long long s = (long long)start[i] - h;  // source column of copy column 0
-        const int64_t* in = tokens + (size_t)b * T;
-        int64_t* o = out + (size_t)i * Tw;
-        for (int c = threadIdx.x; c < Tw; c += 256) {
-            const long long t = min(max(s + c, 0ll), (long long)T - 1);
-            int64_t v = in[t];
-            if (c == Tw - 1 && tail_tok >= 0) v = tail_tok;
-            if (c == 0 && head_tok >= 0) v = head_tok;
-            o[c] = v;
-        }
-        __syncthreads();
-        const int lo = min(max(pos_off[i], 0), total), hi = min(max(pos_off[i + 1], 0), total);
-        for (int j = lo + (int)threadIdx.x; j < hi; j += 256) {
-            const long long c = (long long)pos[j] - s;
-            if (c >= h && c < body_end) o[c] = mask_idx;
-        }
-    }
-}
-
-hipError_t launch_window_rows(const int64_t* tokens, const int* src_row, const int* start, const int* pos_off, const int* pos,
-                              int64_t* out, int B, int T, int n, int Tw, int total, int head_tok, int tail_tok, int mask_idx,
-                              hipStream_t st) {
-    if (!tokens || !src_row || !start || !pos_off || !pos || !out || B <= 0 || T <= 0 || n <= 0 || Tw <= 0 || total < 0)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(window_rows_kernel, dim3((unsigned)std::min(n, 8192)), dim3(256), 0, st, tokens, src_row, start, pos_off,
-                       pos, out, B, T, n, Tw, total, (int64_t)head_tok, (int64_t)tail_tok, (int64_t)mask_idx);
-    return hipGetLastError();
-}
 
 // out[r, :] = (sum_k w[k] x[src[k], :]) / sum_k w[k] over k in [off[r], off[r + 1]), ascending: the stitch of per-window rows
 // into full-length rows.  One lane per 4 neighbouring output elements (16 bytes of fp32), no exchange between lanes: every

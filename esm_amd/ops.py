@@ -647,22 +647,7 @@ def sample_rows(logprobs, row_chain, row_index, allowed_mask, inv_temperature=1.
     candidates with the uniform of Philox counter (row_chain[i], step, 1, row_index[i]) under the key ``seed``; 0: the
     candidate with the largest log-probability (ties: the lowest index).  No candidate: token -1.  ``logq`` is the
     log-probability of the drawn token under the distribution it was drawn from."""
-    _req_cuda(logprobs, row_chain, row_index, exclude)
-    assert logprobs.dtype == torch.float32 and logprobs.dim() == 2 and logprobs.is_contiguous()
-    n, V = logprobs.shape
-    for t in (row_chain, row_index) + ((exclude,) if exclude is not None else ()):
-        assert t.dtype == torch.int32 and t.dim() == 1 and t.numel() == n and t.is_contiguous()
-    allowed_mask = int(allowed_mask)
-    if not 0 <= allowed_mask < 2 ** 64:
-        raise ValueError("allowed_mask is a bitset over at most 64 vocabulary entries")
-    dev = logprobs.device
-    token = torch.empty((n,), dtype=torch.int32, device=dev)
-    logq = torch.empty((n,), dtype=torch.float32, device=dev)
-    u = torch.empty((n,), dtype=torch.float32, device=dev) if want_u else None
-    N.check(N.lib.esmk_op_sample_rows(N.ptr(logprobs), N.ptr(row_chain), N.ptr(row_index), N.ptr(exclude), allowed_mask,
-                                      float(inv_temperature), _seed64(seed), int(step), N.ptr(token), N.ptr(logq), N.ptr(u), n,
-                                      V, N.cur_stream()))
-    return token, logq, u
+    return _sample_rows(logprobs, row_chain, row_index, allowed_mask, inv_temperature, seed, step, exclude, want_u)[:3]
 
 
 SCORE_KINDS = {None: 0, "none": 0, "confidence": 1, "entropy": 2}  # score_kind of esmk_op_sample_rows_ex
@@ -678,6 +663,39 @@ def check_filters(top_k, top_p):
     return int(top_k), top_p
 
 
+def _sample_rows(logprobs, row_chain, row_index, allowed_mask, inv_temperature, seed, step, exclude, want_u, filters=None):
+    """The checks, the outputs and the call of ``sample_rows`` (``filters`` None: esmk_op_sample_rows) and of ``sample_rows_ex``
+    (``filters`` = (top_k, top_p, score, want_kept): esmk_op_sample_rows_ex)."""
+    _req_cuda(logprobs, row_chain, row_index, exclude)
+    assert logprobs.dtype == torch.float32 and logprobs.dim() == 2 and logprobs.is_contiguous()
+    n, V = logprobs.shape
+    for t in (row_chain, row_index) + ((exclude,) if exclude is not None else ()):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.numel() == n and t.is_contiguous()
+    allowed_mask = int(allowed_mask)
+    if not 0 <= allowed_mask < 2 ** 64:
+        raise ValueError("allowed_mask is a bitset over at most 64 vocabulary entries")
+    if filters is not None:
+        top_k, top_p = check_filters(*filters[:2])
+        score, want_kept = filters[2:]
+        if score not in SCORE_KINDS:
+            raise ValueError(f"score {score!r}: None, 'confidence' or 'entropy'")
+        kind = SCORE_KINDS[score]
+    dev = logprobs.device
+    token = torch.empty((n,), dtype=torch.int32, device=dev)
+    logq = torch.empty((n,), dtype=torch.float32, device=dev)
+    u = torch.empty((n,), dtype=torch.float32, device=dev) if want_u else None
+    head = (N.ptr(logprobs), N.ptr(row_chain), N.ptr(row_index), N.ptr(exclude), allowed_mask, float(inv_temperature),
+            _seed64(seed), int(step))
+    if filters is None:
+        N.check(N.lib.esmk_op_sample_rows(*head, N.ptr(token), N.ptr(logq), N.ptr(u), n, V, N.cur_stream()))
+        return token, logq, u, None, None
+    score_out = torch.empty((n,), dtype=torch.float32, device=dev) if kind else None
+    kept = torch.empty((n,), dtype=torch.int64, device=dev) if want_kept else None
+    N.check(N.lib.esmk_op_sample_rows_ex(*head, top_k, top_p, kind, N.ptr(token), N.ptr(logq), N.ptr(u), N.ptr(score_out),
+                                         N.ptr(kept), n, V, N.cur_stream()))
+    return token, logq, u, score_out, kept
+
+
 def sample_rows_ex(logprobs, row_chain, row_index, allowed_mask, inv_temperature=1.0, seed=0, step=0, exclude=None, want_u=True,
                    top_k=0, top_p=1.0, score=None, want_kept=True):
     """``sample_rows`` behind a top-k / nucleus filter, with a per-row score: ``(token int32 [n], logq fp32 [n], u fp32 [n] or
@@ -688,28 +706,8 @@ def sample_rows_ex(logprobs, row_chain, row_index, allowed_mask, inv_temperature
     the bits of ``sample_rows``.  ``score``: None, ``"confidence"`` (max log q) or ``"entropy"`` (sum q log q, the negative
     entropy), q = softmax(logprobs * inv_temperature) over the candidates before filtering (greedy: inv_temperature 1); -inf
     for a row without candidates.  ``kept``: the kept set of every row as the 64-bit pattern of an int64 (bit 63 is the sign)."""
-    _req_cuda(logprobs, row_chain, row_index, exclude)
-    assert logprobs.dtype == torch.float32 and logprobs.dim() == 2 and logprobs.is_contiguous()
-    n, V = logprobs.shape
-    for t in (row_chain, row_index) + ((exclude,) if exclude is not None else ()):
-        assert t.dtype == torch.int32 and t.dim() == 1 and t.numel() == n and t.is_contiguous()
-    allowed_mask = int(allowed_mask)
-    if not 0 <= allowed_mask < 2 ** 64:
-        raise ValueError("allowed_mask is a bitset over at most 64 vocabulary entries")
-    top_k, top_p = check_filters(top_k, top_p)
-    if score not in SCORE_KINDS:
-        raise ValueError(f"score {score!r}: None, 'confidence' or 'entropy'")
-    kind = SCORE_KINDS[score]
-    dev = logprobs.device
-    token = torch.empty((n,), dtype=torch.int32, device=dev)
-    logq = torch.empty((n,), dtype=torch.float32, device=dev)
-    u = torch.empty((n,), dtype=torch.float32, device=dev) if want_u else None
-    score_out = torch.empty((n,), dtype=torch.float32, device=dev) if kind else None
-    kept = torch.empty((n,), dtype=torch.int64, device=dev) if want_kept else None
-    N.check(N.lib.esmk_op_sample_rows_ex(N.ptr(logprobs), N.ptr(row_chain), N.ptr(row_index), N.ptr(exclude), allowed_mask,
-                                         float(inv_temperature), _seed64(seed), int(step), top_k, top_p, kind, N.ptr(token),
-                                         N.ptr(logq), N.ptr(u), N.ptr(score_out), N.ptr(kept), n, V, N.cur_stream()))
-    return token, logq, u, score_out, kept
+    return _sample_rows(logprobs, row_chain, row_index, allowed_mask, inv_temperature, seed, step, exclude, want_u,
+                        (top_k, top_p, score, want_kept))
 
 
 def select_rows(score, row_offsets, sel_offsets, rest_offsets=None, n_sel=None, n_rest=0, sel_out=None, rest_out=None):
@@ -815,10 +813,21 @@ def mh_accept(tokens, site, tok, chain_ids, e_cur, e_contact=None, lp_sum=None, 
     24-bit uniform of Philox counter (chain_ids[c], step, 3, 0); ``inv_temperature=inf``: iff E' <= e_cur.  An accepted chain
     gets ``tokens[slots[c], site[c]] = tok[c]`` (``slots`` None: row c), ``e_cur = E'`` and its component energies in
     ``e_contact_cur`` / ``e_lm_cur`` where given."""
-    f64 = (e_cur, e_contact, lp_sum, hastings, e_contact_cur, e_lm_cur)
-    i32 = (site, tok, chain_ids, n_res, slots)
-    _req_cuda(tokens, *f64, *i32)
+    return _mh_accept(tokens, site, tok, chain_ids, e_cur, e_contact, lp_sum, n_res, hastings, w_contact, w_lm, seed, step, slots,
+                      e_contact_cur, e_lm_cur, inv_temperature=inv_temperature)
+
+
+def _mh_accept(tokens, site, tok, chain_ids, e_cur, e_contact, lp_sum, n_res, hastings, w_contact, w_lm, seed, step, slots,
+               e_contact_cur, e_lm_cur, inv_temperature=None, ex=None):
+    """The tensor checks, the outputs and the call of ``mh_accept`` (a scalar ``inv_temperature``: esmk_op_mh_accept) and of
+    ``mh_accept_ex`` (``ex`` = (inv_t, rung, e_extra, w_extra, e_extra_cur): esmk_op_mh_accept_ex)."""
+    inv_t, rung, e_extra, w_extra, e_extra_cur = ex if ex is not None else (None,) * 5
+    f64 = (e_cur, e_contact, lp_sum, hastings, e_extra, e_contact_cur, e_lm_cur, e_extra_cur)
+    i32 = (site, tok, chain_ids, n_res, slots, rung)
+    _req_cuda(tokens, inv_t, *f64, *i32)
     assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.is_contiguous()
+    if ex is not None:
+        assert inv_t.dtype == torch.float64 and inv_t.dim() == 1 and inv_t.numel() >= 1 and inv_t.is_contiguous()
     n_chain = chain_ids.numel()
     for t in f64:
         assert t is None or (t.dtype == torch.float64 and t.dim() == 1 and t.numel() == n_chain and t.is_contiguous())
@@ -830,10 +839,16 @@ def mh_accept(tokens, site, tok, chain_ids, e_cur, e_contact=None, lp_sum=None, 
     accepted = torch.empty((n_chain,), dtype=torch.uint8, device=dev)
     u = torch.empty((n_chain,), dtype=torch.float64, device=dev)
     e_prop = torch.empty((n_chain,), dtype=torch.float64, device=dev)
-    N.check(N.lib.esmk_op_mh_accept(N.ptr(tokens), N.ptr(slots), N.ptr(site), N.ptr(tok), N.ptr(chain_ids), N.ptr(e_contact),
-                                    N.ptr(lp_sum), N.ptr(n_res), N.ptr(hastings), float(w_contact), float(w_lm),
-                                    float(inv_temperature), _seed64(seed), int(step), N.ptr(e_cur), N.ptr(e_contact_cur),
-                                    N.ptr(e_lm_cur), N.ptr(accepted), N.ptr(u), N.ptr(e_prop), n_chain, B, T, N.cur_stream()))
+    head = (N.ptr(tokens), N.ptr(slots), N.ptr(site), N.ptr(tok), N.ptr(chain_ids), N.ptr(e_contact), N.ptr(lp_sum), N.ptr(n_res),
+            N.ptr(hastings))
+    tail = (N.ptr(accepted), N.ptr(u), N.ptr(e_prop), n_chain, B, T, N.cur_stream())
+    if ex is None:
+        N.check(N.lib.esmk_op_mh_accept(*head, float(w_contact), float(w_lm), float(inv_temperature), _seed64(seed), int(step),
+                                        N.ptr(e_cur), N.ptr(e_contact_cur), N.ptr(e_lm_cur), *tail))
+    else:
+        N.check(N.lib.esmk_op_mh_accept_ex(*head, N.ptr(e_extra), float(w_contact), float(w_lm), float(w_extra), N.ptr(inv_t),
+                                           N.ptr(rung), inv_t.numel(), _seed64(seed), int(step), N.ptr(e_cur),
+                                           N.ptr(e_contact_cur), N.ptr(e_lm_cur), N.ptr(e_extra_cur), *tail))
     return accepted, u, e_prop
 
 
@@ -884,28 +899,8 @@ def mh_accept_ex(tokens, site, tok, chain_ids, e_cur, inv_t, rung=None, e_contac
     [n_rung] on the device, ``rung`` int32 [n_chain] clamped, None: entry 0) and E' = (w_contact * e_contact + w_lm * -(lp_sum /
     n_res)) + w_extra * e_extra (``e_extra`` None: the sum of two).  With ``e_extra`` None and one rung the bits of ``mh_accept``.
     An accepted chain also gets ``e_extra_cur = e_extra``."""
-    f64 = (e_cur, e_contact, lp_sum, hastings, e_extra, e_contact_cur, e_lm_cur, e_extra_cur)
-    i32 = (site, tok, chain_ids, n_res, slots, rung)
-    _req_cuda(tokens, inv_t, *f64, *i32)
-    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.is_contiguous()
-    assert inv_t.dtype == torch.float64 and inv_t.dim() == 1 and inv_t.numel() >= 1 and inv_t.is_contiguous()
-    n_chain = chain_ids.numel()
-    for t in f64:
-        assert t is None or (t.dtype == torch.float64 and t.dim() == 1 and t.numel() == n_chain and t.is_contiguous())
-    for t in i32:
-        assert t is None or (t.dtype == torch.int32 and t.dim() == 1 and t.numel() == n_chain and t.is_contiguous())
-    B, T = tokens.shape
-    assert n_chain >= 1 and (slots is not None or n_chain <= B) and (lp_sum is None or n_res is not None)
-    dev = tokens.device
-    accepted = torch.empty((n_chain,), dtype=torch.uint8, device=dev)
-    u = torch.empty((n_chain,), dtype=torch.float64, device=dev)
-    e_prop = torch.empty((n_chain,), dtype=torch.float64, device=dev)
-    N.check(N.lib.esmk_op_mh_accept_ex(N.ptr(tokens), N.ptr(slots), N.ptr(site), N.ptr(tok), N.ptr(chain_ids), N.ptr(e_contact),
-                                       N.ptr(lp_sum), N.ptr(n_res), N.ptr(hastings), N.ptr(e_extra), float(w_contact), float(w_lm),
-                                       float(w_extra), N.ptr(inv_t), N.ptr(rung), inv_t.numel(), _seed64(seed), int(step),
-                                       N.ptr(e_cur), N.ptr(e_contact_cur), N.ptr(e_lm_cur), N.ptr(e_extra_cur), N.ptr(accepted),
-                                       N.ptr(u), N.ptr(e_prop), n_chain, B, T, N.cur_stream()))
-    return accepted, u, e_prop
+    return _mh_accept(tokens, site, tok, chain_ids, e_cur, e_contact, lp_sum, n_res, hastings, w_contact, w_lm, seed, step, slots,
+                      e_contact_cur, e_lm_cur, ex=(inv_t, rung, e_extra, w_extra, e_extra_cur))
 
 
 def replica_swap(rung, e_cur, inv_t, inv_t_host, ladder_ids, seed=0, round=0):
@@ -1345,21 +1340,28 @@ def sae_cand():
     return int(N.lib.esmk_op_sae_cand())
 
 
+def _image_rows_args(x, rows, out, n):
+    """``(N, E, n, out)`` of ``sae_rows`` and ``align_rows``: the checks of x fp32 [N, E] and rows int32 [>= n] or None, and the
+    fp16 image [>= n, ld >= 3 Ep], the caller's or allocated."""
+    _req_cuda(x, rows, out)
+    assert x.dtype == torch.float32 and x.dim() == 2
+    assert rows is None or (rows.dtype == torch.int32 and rows.dim() == 1)
+    Nr, E = x.shape
+    n = (Nr if rows is None else rows.numel()) if n is None else int(n)
+    assert rows is None or rows.numel() >= n
+    if out is None:
+        out = torch.empty((n, 3 * ((E + 63) // 64 * 64)), dtype=torch.float16, device=x.device)
+    assert out.dtype == torch.float16 and out.dim() == 2 and out.shape[0] >= n
+    return Nr, E, n, out
+
+
 def sae_rows(x, rows=None, b_dec=None, input_scale=1.0, out=None, n=None):
     """The f16x3 activation image of SAE inputs (``esmk_op_sae_rows``): x fp32 [N, E], rows int32 [n] or None (the first ``n``
     rows, default all) -> fp16 [>= n, ld >= 3 Ep] rows ``hi | hi | lo`` per 64-column K tile of u = input_scale * x - b_dec
     (Ep = E rounded up to 64, pad columns zero); ``out`` is the caller's (row stride taken from the tensor) or allocated."""
-    _req_cuda(x, rows, b_dec, out)
-    assert x.dtype == torch.float32 and x.dim() == 2
-    assert rows is None or (rows.dtype == torch.int32 and rows.dim() == 1)
-    assert b_dec is None or (b_dec.dtype == torch.float32 and b_dec.numel() == x.shape[1])
-    Nr, E = x.shape
-    n = (Nr if rows is None else rows.numel()) if n is None else int(n)
-    assert rows is None or rows.numel() >= n
-    Ep = (E + 63) // 64 * 64
-    if out is None:
-        out = torch.empty((n, 3 * Ep), dtype=torch.float16, device=x.device)
-    assert out.dtype == torch.float16 and out.dim() == 2 and out.shape[0] >= n
+    Nr, E, n, out = _image_rows_args(x, rows, out, n)
+    _req_cuda(b_dec)
+    assert b_dec is None or (b_dec.dtype == torch.float32 and b_dec.numel() == E)
     N.check(N.lib.esmk_op_sae_rows(N.ptr(x), E, Nr, N.ptr(rows if n else None), n, N.ptr(b_dec), float(input_scale), N.ptr(out),
                                    out.shape[1], E, N.cur_stream()))
     return out
@@ -1449,16 +1451,7 @@ def align_rows(x, rows=None, cosine=True, b_side=False, out=None, n=None):
     """One of the two f16x3 operand images of the similarity GEMM (``esmk_op_align_rows``): x fp32 [N, E], rows int32 [n] or
     None (the first ``n`` rows, default all; a negative index gives a zero row) -> fp16 [>= n, ld >= 3 Ep], ``hi | hi | lo`` per
     64-column K tile, with ``b_side`` ``hi | lo | hi``; cosine: the rows are scaled to unit length first."""
-    _req_cuda(x, rows, out)
-    assert x.dtype == torch.float32 and x.dim() == 2
-    assert rows is None or (rows.dtype == torch.int32 and rows.dim() == 1)
-    Nr, E = x.shape
-    n = (Nr if rows is None else rows.numel()) if n is None else int(n)
-    assert rows is None or rows.numel() >= n
-    Ep = (E + 63) // 64 * 64
-    if out is None:
-        out = torch.empty((n, 3 * Ep), dtype=torch.float16, device=x.device)
-    assert out.dtype == torch.float16 and out.dim() == 2 and out.shape[0] >= n
+    Nr, E, n, out = _image_rows_args(x, rows, out, n)
     N.check(N.lib.esmk_op_align_rows(N.ptr(x), E, Nr, N.ptr(rows if n else None), n, int(bool(cosine)), int(bool(b_side)),
                                      N.ptr(out), out.shape[1], E, N.cur_stream()))
     return out

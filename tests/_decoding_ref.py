@@ -1,4 +1,4 @@
-"""numpy references of the decoding kernels (esm_amd/csrc/sampling.hip: ``sample_rows_ex_kernel``, ``select_rows_kernel``):
+"""numpy references of the decoding kernels (esm_amd/csrc/sampling.hip: ``sample_rows_kernel``, ``select_rows_kernel``):
 the top-k / nucleus filter in front of the draw, the per-row confidence scores and the per-chain choice of the best rows.
 Rank and selection are comparison logic on the fp32 inputs and are exact; the cumulative weights of the nucleus filter and the
 draw are taken in fp64, with the rule that says which rows a comparison may count ("decided": every boundary the fp32 kernel

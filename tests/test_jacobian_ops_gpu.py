@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import _jacobian_ref as R
+from esm_amd import _native as N
 from esm_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -47,6 +48,34 @@ def test_substitute_rows_is_exact(n, with_src):
     assert got.dtype == torch.int64 and torch.equal(got.cpu(), want)
     if not with_src:  # a single sequence [T] is row 0
         assert torch.equal(ops.substitute_rows(tokens[0].cuda(), pos.cuda(), tok.cuda(), vocab=V).cpu(), want)
+
+
+@pytest.mark.parametrize("n,T", [(9, 300), (8200, 5)])
+def test_substitute_rows_loop_trips_grid_wrap_and_clamps(n, T):
+    """T = 300: a copy is longer than one trip of its workgroup's 256 lanes and no multiple of it; n = 8200: the copies wrap the
+    grid of 8192 workgroups.  A position of -1 or T and a token of -1 or V substitute nothing, a source row of -2 or B + 3 is
+    clamped, and the row behind the last copy is not written."""
+    B, SENT = 3, -7
+    g = torch.Generator().manual_seed(n)
+    tokens = torch.randint(0, V, (B, T), generator=g, dtype=torch.int64)
+    pos = torch.randint(0, T, (n,), generator=g, dtype=torch.int32)
+    tok = torch.randint(0, V, (n,), generator=g, dtype=torch.int32)
+    src = torch.randint(0, B, (n,), generator=g, dtype=torch.int32)
+    pos[:8] = torch.tensor([-1, T, 3, 3, 0, T - 1, T - 1, min(256, T - 1)], dtype=torch.int32)
+    tok[:8] = torch.tensor([5, 5, -1, V, 0, V - 1, 7, 9], dtype=torch.int32)
+    src[:8] = torch.tensor([1, 2, 0, 1, -2, B + 3, 0, 1], dtype=torch.int32)
+    pos[n - 1], tok[n - 1], src[n - 1] = T - 1, V - 1, B - 1  # the last copy of the last trip
+    for with_src in (True, False):
+        want = tokens[src.long().clamp(0, B - 1)].clone() if with_src else tokens[:1].expand(n, T).clone()
+        hit = (pos >= 0) & (pos < T) & (tok >= 0) & (tok < V)
+        want[torch.arange(n)[hit], pos[hit].long()] = tok[hit].long()
+        out = torch.full((n + 1, T), SENT, dtype=torch.int64, device="cuda")
+        tok_d, pos_d, new_d, src_d = tokens.cuda(), pos.cuda(), tok.cuda(), src.cuda() if with_src else None
+        N.check(N.lib.esmk_op_substitute_rows(N.ptr(tok_d), N.ptr(src_d), N.ptr(pos_d), N.ptr(new_d), N.ptr(out), B, T, n, V,
+                                              N.cur_stream()))
+        assert torch.equal(out[:n].cpu(), want), with_src
+        assert (out[n] == SENT).all(), "a store behind the last copy"
+        assert torch.equal(ops.substitute_rows(tok_d, pos_d, new_d, src_d, vocab=V).cpu(), want)
 
 
 # ---- esmk_op_jacobian_scatter -----------------------------------------------------------------------------------------------

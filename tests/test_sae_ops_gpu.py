@@ -218,6 +218,18 @@ def test_rows_image(E, scale):
             assert (lo != 0).any()
 
 
+def test_rows_image_clamps_the_row_list():
+    """A listed row is device data: -3 gives the image of row 0, N + 5 that of row N - 1."""
+    N, E = 9, 320
+    g = torch.Generator(device="cuda").manual_seed(3)
+    x = torch.randn(N, E, device="cuda", generator=g) * 3
+    b_dec = torch.randn(E, device="cuda", generator=g)
+    rows = torch.tensor([-3, N + 5, 4], dtype=torch.int32, device="cuda")
+    got = ops.sae_rows(x, rows, b_dec, 0.37).view(torch.int16).cpu().numpy()
+    want = ref.image_rows(ref.u_rows(x.cpu().numpy()[[0, N - 1, 4]], None, b_dec.cpu().numpy(), 0.37)).view(np.int16)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:4].tolist()
+
+
 # ---- the encoder product through the chain of ops --------------------------------------------------------------------------
 @pytest.mark.parametrize("rows,F,E", [(67, 192, 64), (300, 4160, 320), (260, 1024, 1280)])
 def test_encoder_product(rows, F, E):

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from _scoring_ref import check_rows
+from esm_amd import _native as N
 from esm_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -70,3 +71,28 @@ def test_mask_rows_with_source_index():
     want[torch.arange(T), pos] = MASK
     got = ops.mask_rows(tokens.cuda(), pos.to(torch.int32).cuda(), src.to(torch.int32).cuda(), mask_idx=MASK)
     assert torch.equal(got.cpu(), want)
+
+
+@pytest.mark.parametrize("n,T", [(7, 300), (8200, 5)])
+def test_mask_rows_loop_trips_grid_wrap_and_clamps(n, T):
+    """T = 300: a copy is longer than one trip of its workgroup's 256 lanes and no multiple of it; n = 8200: the copies wrap the
+    grid of 8192 workgroups.  A position of -1 or T masks nothing, a source row of -2 or B + 3 is clamped, and the row behind
+    the last copy is not written."""
+    B, MASK, SENT = 3, 32, -7
+    g = torch.Generator().manual_seed(n)
+    tokens = torch.randint(4, 24, (B, T), generator=g, dtype=torch.int64)
+    pos = torch.randint(0, T, (n,), generator=g, dtype=torch.int32)
+    src = torch.randint(0, B, (n,), generator=g, dtype=torch.int32)
+    pos[:6] = torch.tensor([-1, T, 0, T - 1, T - 1, min(256, T - 1)], dtype=torch.int32)
+    src[:6] = torch.tensor([1, 2, -2, B + 3, 0, 1], dtype=torch.int32)
+    pos[n - 1], src[n - 1] = T - 1, B - 1  # the last copy of the last trip
+    for with_src in (True, False):
+        want = tokens[src.long().clamp(0, B - 1)].clone() if with_src else tokens[:1].expand(n, T).clone()
+        hit = (pos >= 0) & (pos < T)
+        want[torch.arange(n)[hit], pos[hit].long()] = MASK
+        out = torch.full((n + 1, T), SENT, dtype=torch.int64, device="cuda")
+        tok_d, pos_d, src_d = tokens.cuda(), pos.cuda(), src.cuda() if with_src else None
+        N.check(N.lib.esmk_op_mask_rows(N.ptr(tok_d), N.ptr(src_d), N.ptr(pos_d), N.ptr(out), B, T, n, MASK, N.cur_stream()))
+        assert torch.equal(out[:n].cpu(), want), with_src
+        assert (out[n] == SENT).all(), "a store behind the last copy"
+        assert torch.equal(ops.mask_rows(tok_d, pos_d, src_d, mask_idx=MASK).cpu(), want)
