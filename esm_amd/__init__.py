@@ -55,6 +55,15 @@ def __getattr__(name):
 
         module = importlib.import_module(".cluster", __name__)
         return module if name == "cluster" else getattr(module, name)
+    if name == "build_msa":  # esm_amd/build_msa.py: ``python -m esm_amd.build_msa``, and callable as msa_build.build_msa
+        import importlib
+
+        return importlib.import_module(".build_msa", __name__)
+    if name in ("msa_build", "build_msas", "BuiltMSA"):  # esm_amd/msa_build.py: search hits to a query-anchored MSA
+        import importlib
+
+        module = importlib.import_module(".msa_build", __name__)
+        return module if name == "msa_build" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

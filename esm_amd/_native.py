@@ -150,6 +150,10 @@ SIGNATURES = {
     "esmk_op_cluster_decide": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "esmk_op_cluster_assign": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                        c_void_p]),
+    # search hits to an MSA (csrc/msa_build.hip): alignment paths to rows of a byte matrix, gap-aware pairwise identity
+    "esmk_op_msa_project": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_int, c_void_p, c_void_p]),
+    "esmk_op_msa_pair_identity": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     # early exit: the handle's layer limit
     "esmk_set_layer_limit": (c_int, [c_void_p, c_int]),
     # edits of the residual stream between layers: the handle's list, and one edit as a single op

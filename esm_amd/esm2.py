@@ -548,6 +548,19 @@ class ESM2(_EngineHost, nn.Module):
 
         return search.search(self, index, tokens, top_k, varlen=varlen, **kw)
 
+    # search hits to a query-anchored MSA (esm_amd/msa_build.py): projection, coverage and redundancy filters on the device
+    def build_msas(self, alphabet, queries, index, **kw):
+        """``esm_amd.msa_build.build_msas``: one ``BuiltMSA`` per query (label, sequence) from the aligned hits of ``index``."""
+        from . import msa_build
+
+        return msa_build.build_msas(self, alphabet, queries, index, **kw)
+
+    def build_msa(self, alphabet, query, index, **kw):
+        """``esm_amd.msa_build.build_msa``: ``build_msas`` for one query."""
+        from . import msa_build
+
+        return msa_build.build_msa(self, alphabet, query, index, **kw)
+
     def predict_contacts(self, tokens):
         """Reference esm2.py:146-147 returns ``self(tokens, return_contacts=True)["contacts"]``, which first builds
         the [B,L,H,T,T] attention tensor (2.8 GB per 1024-token sequence at 650M).  Only the map leaves this call, so

@@ -1647,3 +1647,57 @@ def cluster_assign(offsets, ids, scores, rank, state, nearest, key=None, lanes=6
     N.check(N.lib.esmk_op_cluster_assign(N.ptr(offsets), N.ptr(ids), N.ptr(scores), n, ids.numel(), N.ptr(rank), N.ptr(state),
                                          int(bool(nearest)), N.ptr(key), int(lanes), N.cur_stream()))
     return key
+
+
+# ---- search hits to an MSA (include/esmk.h: esmk_op_msa_project, esmk_op_msa_pair_identity) ---------------------------------
+def msa_project(cols, col_offsets, seqs, seq_off, seq_len, query, ld=None, msa=None, stats=None):
+    """The alignment paths of the P hits of one query as rows of a byte matrix (``esmk_op_msa_project``): (msa uint8 [P, ld],
+    stats int32 [P, 6]).  ``cols`` int32 [n, 2] and ``col_offsets`` int64 [P + 1] as ``align`` returns them — the offsets index
+    into ``cols``, so the hits of one query are given by their slice of the offsets and the whole of ``cols``; ``seqs`` uint8
+    [n_bytes], hit p's residues at ``seq_off[p]`` (int64 [P]), ``seq_len[p]`` (int32 [P]) of them; ``query`` uint8 [Lq].
+    Row p is '-' in the columns below Lq except ``msa[p][i] = seqs[seq_off[p] + j]`` for every match (i, j) of its path, and 0
+    from Lq to ``ld`` (default: Lq rounded up to 4).  stats: n_match, n_ident, n_ins, n_del, first and last matched query column."""
+    _req_cuda(cols, col_offsets, seqs, seq_off, seq_len, query, msa, stats)
+    assert cols.dtype == torch.int32 and cols.dim() == 2 and cols.shape[1] == 2
+    assert col_offsets.dtype == torch.int64 and col_offsets.dim() == 1 and col_offsets.numel() >= 1
+    P = col_offsets.numel() - 1
+    assert seqs.dtype == torch.uint8 and seqs.dim() == 1 and query.dtype == torch.uint8 and query.dim() == 1
+    assert seq_off.dtype == torch.int64 and seq_off.numel() == P and seq_len.dtype == torch.int32 and seq_len.numel() == P
+    Lq = query.numel()
+    ld = (Lq + 3) // 4 * 4 if ld is None else int(ld)
+    dev = query.device
+    if msa is None:
+        msa = torch.empty((P, ld), dtype=torch.uint8, device=dev)
+    if stats is None:
+        stats = torch.empty((P, 6), dtype=torch.int32, device=dev)
+    assert msa.dtype == torch.uint8 and msa.dim() == 2 and msa.shape[0] >= P and msa.shape[1] == ld
+    assert stats.dtype == torch.int32 and stats.numel() >= 6 * P
+    if P == 0:  # (empty tensors have no address to hand over)
+        return msa, stats
+    N.check(N.lib.esmk_op_msa_project(N.ptr(cols), cols.shape[0], N.ptr(col_offsets), P, N.ptr(seqs), seqs.numel(), N.ptr(seq_off),
+                                      N.ptr(seq_len), N.ptr(query), Lq, N.ptr(msa), ld, N.ptr(stats), N.cur_stream()))
+    return msa, stats
+
+
+def msa_pair_identity(msa, L=None, gap=ord("-"), min_overlap=1, i0=0, nb=None, out=None):
+    """Rows ``i0 .. i0 + nb - 1`` (default: all) of the gap-aware pairwise identity of ``msa`` uint8 [N, ld] over its first ``L``
+    columns (``esmk_op_msa_pair_identity``): fp32 [nb, N rounded up to 4], ``S[r][j] = same / both`` — ``both`` the columns
+    in which neither row holds the byte ``gap``, ``same`` those in which the two bytes are equal — where ``both >= min_overlap``
+    and 0 elsewhere; the columns behind N are 0.  A block is what ``range_rows`` takes (``n_cols=N``).  ``msa`` may be a view
+    with a row stride (odd strides and bases take the byte-wise loads)."""
+    if not msa.is_cuda:
+        raise RuntimeError("esm_amd.ops: tensors must live on the GPU (no CPU fallback)")
+    assert msa.dtype == torch.uint8 and msa.dim() == 2 and (msa.shape[1] == 1 or msa.stride(1) == 1)
+    N_, ld = msa.shape[0], (msa.stride(0) if msa.shape[0] > 1 else msa.shape[1])
+    L = msa.shape[1] if L is None else int(L)
+    if N_ < 1 or not 1 <= L <= msa.shape[1]:
+        raise ValueError(f"msa: need at least one row and 1 <= L <= {msa.shape[1]} columns, got N = {N_}, L = {L}")
+    nb = N_ - int(i0) if nb is None else int(nb)
+    ldS = (N_ + 3) // 4 * 4
+    if out is None:
+        out = torch.empty((max(nb, 0), ldS), dtype=torch.float32, device=msa.device)
+    _req_cuda(out)
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] >= nb and out.shape[1] == ldS
+    N.check(N.lib.esmk_op_msa_pair_identity(N.ptr(msa), N_, L, ld, int(gap), int(min_overlap), int(i0), nb, N.ptr(out), ldS,
+                                            N.cur_stream()))
+    return out

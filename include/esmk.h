@@ -1292,6 +1292,38 @@ int esmk_op_cluster_decide(int32_t* state_dev, int32_t* blocked_dev, const int32
 int esmk_op_cluster_assign(const int64_t* offsets_dev, const int32_t* ids_dev, const float* scores_dev, int n, long long nnz,
                            const int32_t* rank_dev, const int32_t* state_dev, int nearest, uint64_t* key_dev, int lanes, void* stream);
 
+/* From search hits to a query-anchored MSA (csrc/msa_build.hip; esm_amd/msa_build.py).  Integer and comparison logic, no atomics,
+ * no scratch memory; all results are the same bits whatever the launch geometry.  Both entries check their arguments before
+ * the first HIP call.
+ * esmk_op_msa_project: the alignment paths of the P hits of one query as rows of a byte matrix.  cols int32 [n_cols_total, 2]
+ *   and col_offsets int64 [P + 1] as esmk_op_align_traceback leaves them (hit p owns cols[col_offsets[p] .. col_offsets[p + 1]);
+ *   the offsets index from cols_dev, so a query's slice of a longer table is given by its col_offsets alone); seqs uint8
+ *   [n_bytes], the hits' residues as one blob, hit p at seq_off[p] (int64 [P]) with seq_len[p] (int32 [P]) bytes; query uint8
+ *   [Lq].  msa uint8 [P, ld]: columns 0 .. Lq - 1 of row p are '-' except msa[p][i] = seqs[seq_off[p] + j] for every path column
+ *   (i, j) that is a match; columns Lq .. ld - 1 are 0.  A path column is a match when 0 <= i < Lq and 0 <= j < len, a deletion
+ *   when 0 <= i < Lq and j == -1, an insertion when i == -1 and 0 <= j < len; any other column is ignored.  Everything is device
+ *   data: len is seq_len[p] clamped to the bytes the blob holds behind seq_off[p] (0 for a seq_off outside the blob), the
+ *   path's range is clamped into [0, n_cols_total] and its end to no less than its start.  stats int32 [P, 6]: n_match; n_ident
+ *   (matches whose letter equals query[i]); n_ins and n_del, the insertions and deletions whose path position lies strictly
+ *   between those of the first and the last match; the query columns of the first and of the last match (by path position;
+ *   -1, -1 without a match).  A path that names a query column twice leaves one of its letters there.  One wavefront per hit.
+ *   Refused: null col_offsets, seq_off, seq_len, query, msa or stats; null cols with n_cols_total > 0, null seqs with
+ *   n_bytes > 0; negative n_cols_total or n_bytes; P outside 0 .. 2^24 (0: nothing is launched); Lq outside 1 .. 8192; ld < Lq
+ *   or ld % 4; P * ld >= 2^31; col_offsets / seq_off not 8-byte aligned, cols / seq_len / msa / stats not 4-byte aligned.
+ * esmk_op_msa_pair_identity: rows i0 .. i0 + nb - 1 of the gap-aware identity matrix of msa uint8 [N, ld] over the columns
+ *   c < L.  both(r, j) = the columns in which neither row holds the gap byte, same(r, j) = those of them in which the bytes
+ *   are equal; S[r - i0][j] = float(same) / float(both), one correctly rounded fp32 division, when both >= min_overlap, else
+ *   0: never NaN.  S fp32 [nb, ldS]; columns N .. ldS - 1 are written as 0: a block is what esmk_op_range_rows takes.  Every
+ *   byte value is legal, nothing at or behind column L is compared.  64 x 64 tiles, a workgroup owns its tile of S.
+ *   Refused: null msa or S; N outside 1 .. 2^22; L outside 1 .. 65535; ld < L; N * ld >= 2^31; gap outside 0 .. 255;
+ *   min_overlap < 1; a row block outside [0, N) or of more than 2^21 rows (nb == 0: nothing is launched); ldS < N, ldS % 4
+ *   or ldS > 2^22; S not 16-byte aligned. */
+int esmk_op_msa_project(const int32_t* cols_dev, long long n_cols_total, const int64_t* col_offsets_dev, int P, const uint8_t* seqs_dev,
+                        long long n_bytes, const int64_t* seq_off_dev, const int32_t* seq_len_dev, const uint8_t* query_dev, int Lq,
+                        uint8_t* msa_dev, int ld, int32_t* stats_dev, void* stream);
+int esmk_op_msa_pair_identity(const uint8_t* msa_dev, int N, int L, int ld, int gap, int min_overlap, int i0, int nb, float* S_dev,
+                              int ldS, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
