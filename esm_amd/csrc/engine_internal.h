@@ -45,7 +45,8 @@ struct MsaLayerOff {
 }  // namespace esmk_host
 
 // row counts travel as int through the kernels (row * ld products are widened to 64 bit); 2^24 rows of fp32
-// residual already exceed one GPU's HBM for every supported width, so this is a guard, not a limit in practice
+// residual already exceed one GPU's HBM for every supported width, so this is a guard, not a limit in practice.
+// tests/test_index_width_ops_gpu.py and tests/test_index_width_engine_gpu.py run the kernels past 2^31 and 2^32 bytes.
 #define ESMK_MAX_ROWS (1LL << 24)
 
 #define ESMK_TRY(expr)                                             \

@@ -19,6 +19,9 @@ from oracle.esm2_oracle import esm2_forward
 
 pytestmark = pytest.mark.gpu
 
+SPLIT_STORE_T_TOL = 6e-4  # linear_split, operand-dtype store: the fp16 output rounding itself, relative to the largest value
+SPLIT_GELU_TOL = 1e-3     # linear_split, GELU epilogue, relative to the largest value
+
 
 @pytest.mark.parametrize("M,N,K", [(512, 256, 64), (1000, 1288, 320), (4096, 1280, 1280)])
 def test_linear_split_matches_fp64(M, N, K):
@@ -41,13 +44,13 @@ def test_linear_split_matches_fp64(M, N, K):
         e_split, e_plain = (got - ref).abs().max().item() / scale, (plain - ref).abs().max().item() / scale
         print(f"\n({M},{N},{K}) epi {epi}: split {e_split:.2e}, plain fp16 weights {e_plain:.2e}")
         if epi == nat.EPI_STORE_T:
-            assert e_split < 6e-4  # the fp16 output rounding itself
+            assert e_split < SPLIT_STORE_T_TOL
         else:
             assert e_split < 1e-5 and e_plain > 8 * e_split, (e_split, e_plain)
     # GELU epilogue against the same function in fp64
     got = ops.linear_split(a, w2, bias, nat.EPI_GELU_T).double()
     want = torch.nn.functional.gelu(ref)
-    assert (got - want).abs().max().item() < 1e-3 * want.abs().max().item()
+    assert (got - want).abs().max().item() < SPLIT_GELU_TOL * want.abs().max().item()
 
 
 def test_650m_dims_split_weights_meet_the_contract(monkeypatch):

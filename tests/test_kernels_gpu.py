@@ -369,6 +369,21 @@ def test_attention_lazy_offset_edge_cases(ops, scale):
     assert (lse - lse_ref).abs().max().item() < 2e-3 * max(1.0, lse_ref.abs().max().item())
 
 
+CONTACTS_TOL = 2e-5  # ops.contacts against the restated head, absolute (the output is a sigmoid)
+
+
+def contact_head_ref(attn, tokens, w, b):
+    """reference: esm/modules.py:338-357 + symmetrize/apc (modules.py:27-41), restated; attn [B,L,H,T,T] -> [B,T-2,T-2]"""
+    B, L, H, T, _ = attn.shape
+    em = tokens.ne(2).float()
+    a = attn * (em[:, :, None] * em[:, None, :])[:, None, None]
+    a = a[..., :-1, :-1][..., 1:, 1:].reshape(B, L * H, T - 2, T - 2)
+    s = a + a.transpose(-1, -2)
+    a1, a2, a12 = s.sum(-1, keepdim=True), s.sum(-2, keepdim=True), s.sum((-1, -2), keepdim=True)
+    n = s - a1 * a2 / a12
+    return torch.sigmoid((n.permute(0, 2, 3, 1) @ w.t()).squeeze(-1) + b)
+
+
 @pytest.mark.parametrize("B,L,H,T", [(2, 2, 3, 40), (1, 1, 2, 130)])
 def test_contacts(ops, B, L, H, T):
     g = torch.Generator(device="cuda").manual_seed(6)
@@ -383,12 +398,4 @@ def test_contacts(ops, B, L, H, T):
     w = torch.randn(1, L * H, device="cuda", generator=g)
     b = torch.randn(1, device="cuda", generator=g)
     out = ops.contacts(attn, tokens, w, b)
-    # reference: esm/modules.py:338-357 + symmetrize/apc (modules.py:27-41), restated
-    em = tokens.ne(2).float()
-    a = attn * (em[:, :, None] * em[:, None, :])[:, None, None]
-    a = a[..., :-1, :-1][..., 1:, 1:].reshape(B, L * H, T - 2, T - 2)
-    s = a + a.transpose(-1, -2)
-    a1, a2, a12 = s.sum(-1, keepdim=True), s.sum(-2, keepdim=True), s.sum((-1, -2), keepdim=True)
-    n = s - a1 * a2 / a12
-    ref = torch.sigmoid((n.permute(0, 2, 3, 1) @ w.t()).squeeze(-1) + b)
-    assert (out - ref).abs().max().item() < 2e-5
+    assert (out - contact_head_ref(attn, tokens, w, b)).abs().max().item() < CONTACTS_TOL

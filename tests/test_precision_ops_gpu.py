@@ -331,6 +331,13 @@ def test_f16x3_product(M, N, K):
         nat.lib.esmk_debug_gemm_impl(0, 0)
 
 
+def gelu_x3_bound(a3d, w3d, bias, pre, v, K):
+    """the four-term bound of hi + lo = v against gelu64(pre): accumulation, the polynomial, the split"""
+    acc = (3 * K + 2) * U * (a3d.abs() @ w3d.abs().t() + bias.double().abs())
+    poly = 1.4e-6 * pre.abs().clamp(min=1.0).where(pre.abs() > 4.75, torch.ones_like(pre))  # common.h, the degree-11 set
+    return 1.13 * acc + poly + 2.0 ** -21 * v.abs()
+
+
 @pytest.mark.parametrize("M,N,K3", [(256, 256, 192), (300, 320, 192), (1000, 1280, 960)])
 def test_linear_gelu_x3(M, N, K3):
     K = K3 // 3
@@ -350,9 +357,7 @@ def test_linear_gelu_x3(M, N, K3):
     hi, hi2, lo = (t[:, :, s].reshape(M, N) for s in range(3))
     assert torch.equal(bits(hi2), bits(hi))
     v = hi.double() + lo.double()
-    acc = (3 * K + 2) * U * (a3d.abs() @ w3d.abs().t() + bias.double().abs())
-    poly = 1.4e-6 * pre.abs().clamp(min=1.0).where(pre.abs() > 4.75, torch.ones_like(pre))  # common.h, the degree-11 set
-    bound = 1.13 * acc + poly + 2.0 ** -21 * v.abs()
+    bound = gelu_x3_bound(a3d, w3d, bias, pre, v, K)
     r = ((v - want).abs() / bound).max().item()
     rem = (lo.double().abs() - (2.0 ** -11 * hi.double().abs() + U)).max().item()
     print(f"\nlinear_gelu_x3 ({M},{N},{K3}): {r:.3f} of the bound, max |hi + lo - gelu| {(v - want).abs().max().item():.2e}, "

@@ -14,6 +14,7 @@ import esm
 from esm_amd.synth import synth_esm2_state_dict, synth_tokens
 
 pytestmark = pytest.mark.gpu
+ROW_MEAN_TOL = 2e-6  # masked_row_mean against torch's fp32 mean, per 64 rows of the slice
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -36,7 +37,7 @@ def test_masked_row_mean_matches_torch(dt, B, T, E):
         if counts[b] == 0:
             assert torch.isnan(out[b]).all() and torch.isnan(want).all()
         else:
-            assert (out[b] - want).abs().max().item() < 2e-6 * max(1.0, T / 64), (b, int(counts[b]))
+            assert (out[b] - want).abs().max().item() < ROW_MEAN_TOL * max(1.0, T / 64), (b, int(counts[b]))
     again = ops.masked_row_mean(x, counts.cuda(), first_row=1)
     assert torch.equal(torch.nan_to_num(out), torch.nan_to_num(again))  # deterministic
 

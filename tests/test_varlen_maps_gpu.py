@@ -159,7 +159,10 @@ def test_some_fixture_carries_attentions():
 
 def test_map_offsets_past_2_31_elements():
     """53 sequences of 1022 tokens and a short one, 2 layers x 20 heads: 2.2e9 map elements (4.4 GB of fp16) in front of the
-    last sequence.  The element offsets are 64-bit prefix sums; nothing else in the suite reaches past 2^31."""
+    last sequence.  The element offsets are 64-bit prefix sums: the one place where the packed map buffer passes 2^31
+    elements.  (tests/test_index_width_ops_gpu.py and tests/test_index_width_engine_gpu.py take the tensors of the padded
+    kernels, of packed attention and of the layer loop past 2^31 and 2^32 bytes; the packed map and contact kernels are held
+    by this test alone.)"""
     L, E, H = 2, 1280, 20
     model = build(L, E, H, seed=3).half()
     lengths = [1022] * 53 + [77]
