@@ -140,6 +140,10 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "esmk_op_align_traceback": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
+    "esmk_op_align_dp_ex": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "esmk_op_align_traceback_ex": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     # protein search on pooled embeddings (csrc/search.hip): the per-protein mean, the streaming top-k
     "esmk_op_pool_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "esmk_op_topk_merge": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),

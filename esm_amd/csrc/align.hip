@@ -18,6 +18,21 @@
 // Traceback bytes exist for the cells i, j >= 1 (row i - 1, column j - 1 of a byte matrix with a row stride of Lb rounded up to
 // 16); on row 0 and column 0 the walk needs none: global mode emits the remaining gaps, local mode stops (H = 0 there).
 //
+// Free end gaps (global mode only; the `free_ends` mask of the _ex entries, wave-uniform; 0 is plain global mode).  Only the
+// "stop" candidate on the borders and the end cell change, every fp32 operation and its order stay:
+//     1 a_start  H[i][0] = 0 for all i (the column-0 value local mode uses); the walk stops on column 0
+//     4 b_start  on row 0 the stop candidate is 0, so H[0][j] = 0 with choice "stop"; the walk stops on row 0
+//     2 a_end    the cells (i, Lb), i = 1 .. La, are end-cell candidates next to the corner (La, Lb)
+//     8 b_end    the cells (La, j), j = 1 .. Lb, are
+// E and F on the borders are unchanged.  Among the candidates (never a cell with i = 0 or j = 0) the largest H wins, ties go
+// to the lower row, then the lower column: a lane keeps its first best, and the wavefront reduction below orders the lanes.
+//
+// Several hits per pair (Waterman-Eggert): the traceback kernel, given a writable S, stores -inf at every MATCH cell of the
+// path it walks (plain vector stores of one float by the thread that walks the pair), and the DP and the walk run again on the
+// same S; gap states may still cross an earlier path.  A pair's block of S belongs to that pair alone — the callers list no
+// pair twice (align.py's check_pairs) and every sequence of b has its own columns — so no other thread reads or writes those
+// cells in the launch.  -inf + finite and the comparisons produce no NaN (H is never +inf).
+//
 // The DP kernel: one wavefront per pair, four per workgroup.  Lane l owns the 8 columns j0 + 8 l + 1 .. j0 + 8 l + 8 of a panel
 // of 512 in registers (H and F of the previous row) and works on row t - l at step t; the strip's right edge (H, E) moves to lane
 // l + 1 once per step.  A side wider than one panel goes panel by panel: lane 63 writes the boundary column (H, E per row) to
@@ -112,7 +127,7 @@ struct AlignDpArgs {
     const float* S;
     int ldS, n_rows, n_cols;
     const long long* table;  // [n_pairs, 5]: row offset of a, La, column offset of b (a multiple of 8), Lb, traceback offset (bytes)
-    int n_pairs, local;
+    int n_pairs, local, free_ends;
     float o, e;
     int max_la, max_lb;
     float* score;
@@ -123,13 +138,19 @@ struct AlignDpArgs {
     int n_waves;
 };
 
-__global__ __launch_bounds__(256) void align_dp_kernel(const AlignDpArgs a) {
+// One body, two instances: kFree = false is the kernel of the plain modes (the mask is the constant 0 there, so the stop
+// candidate is a constant and the candidate search below does not exist); kFree = true is launched when free_ends != 0.
+template <bool kFree>
+ESMK_DEV __attribute__((always_inline)) void align_dp_body(const AlignDpArgs& a) {
     const int lane = threadIdx.x & 63;
     const int gw = uniform(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (gw >= a.n_waves) return;
     const float NEG = -__builtin_inff();
     const float o = a.o, e = a.e;
     const bool local = a.local != 0;
+    const int fe = kFree ? uniform(a.free_ends) : 0;
+    const bool zero_col = local || (fe & 1) != 0, zero_row = (fe & 4) != 0, a_end = (fe & 2) != 0, b_end = (fe & 8) != 0;
+    const bool track = local || fe != 0;  // the end cell is searched for, not given
     f32x2* wsw = a.ws ? a.ws + (size_t)gw * (a.max_la + 1) : nullptr;
     for (int p = gw; p < a.n_pairs; p += a.n_waves) {
         const long long* t = a.table + 5 * (size_t)p;
@@ -188,7 +209,7 @@ __global__ __launch_bounds__(256) void align_dp_kernel(const AlignDpArgs a) {
                 } else {
                     const float x = h0 - o, y = f0 - e;
                     f0 = y > x ? y : x;
-                    h0 = local ? 0.f : f0;
+                    h0 = zero_col ? 0.f : f0;
                 }
                 if (lane == 0) {
                     hl = carry_in ? cin[0] : h0;
@@ -199,6 +220,8 @@ __global__ __launch_bounds__(256) void align_dp_kernel(const AlignDpArgs a) {
                 float hd = hdiag;
                 const float sv[kStrip] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
                 unsigned int w[2] = {0u, 0u};
+                const float stop = local || (zero_row && top) ? 0.f : NEG;
+                const bool corner_row = !track && on && i == La;
 #pragma unroll
                 for (int c = 0; c < kStrip; ++c) {
                     const float ex = hl - o, ey = el - e;
@@ -208,7 +231,7 @@ __global__ __launch_bounds__(256) void align_dp_kernel(const AlignDpArgs a) {
                     const bool fb = !top && fy > fx;
                     const float F = top ? NEG : (fb ? fy : fx);
                     const float D = top ? NEG : sv[c] + hd;
-                    float best = local ? 0.f : NEG;
+                    float best = stop;
                     unsigned int ch = 0;
                     if (D > best) best = D, ch = 1;
                     if (F > best) best = F, ch = 2;
@@ -223,8 +246,18 @@ __global__ __launch_bounds__(256) void align_dp_kernel(const AlignDpArgs a) {
                     w[c >> 2] |= byte << (8 * (c & 3));
                     if (local) {
                         if (on && valid && i >= 1 && (best > bv || (best == bv && i < bi))) bv = best, bi = i, bj = jl + c + 1;
-                    } else if (on && i == La && jl + c + 1 == Lb) {
+                    } else if (corner_row && jl + c + 1 == Lb) {
                         bv = best, bi = La, bj = Lb;
+                    }
+                }
+                // free ends: the row's end-cell candidates: all cells of row La with b_end, the cell in column Lb of the rows
+                // i >= 1 with a_end, the corner in any case; the first best in row order is kept (as in local mode)
+                if (kFree && on && i >= 1 && (a_end || i == La)) {
+                    const bool all = b_end && i == La;
+#pragma unroll
+                    for (int c = 0; c < kStrip; ++c) {
+                        const float h = Hp[c];
+                        if (jl + c < Lb && (all || jl + c + 1 == Lb) && (h > bv || (h == bv && i < bi))) bv = h, bi = i, bj = jl + c + 1;
                     }
                 }
                 hdiag = hleft;
@@ -246,17 +279,25 @@ __global__ __launch_bounds__(256) void align_dp_kernel(const AlignDpArgs a) {
         }
         if (lane == 0) {
             a.score[p] = bv;
-            a.end[2 * p] = local ? bi : La;
-            a.end[2 * p + 1] = local ? bj : Lb;
+            a.end[2 * p] = track ? bi : La;
+            a.end[2 * p + 1] = track ? bj : Lb;
         }
     }
 }
 
+__global__ __launch_bounds__(256) void align_dp_kernel(const AlignDpArgs a) { align_dp_body<false>(a); }
+__global__ __launch_bounds__(256) void align_dp_free_kernel(const AlignDpArgs a) { align_dp_body<true>(a); }
+
 // ---- traceback ----------------------------------------------------------------------------------------------------------
 // One thread per pair.  The columns are found from the end cell backwards and written from the back of the pair's slot of
 // La + Lb columns, so that they stand in ascending order in [slot end - n_cols, slot end).  At most La + Lb steps are taken
-// whatever the bytes hold (each step lowers i or j).
+// whatever the bytes hold (each step lowers i or j).  With a free start the walk stops where it reaches that border (H = 0
+// there, choice "stop").  S_mask non-null: every match cell of the path is set to -inf in the pair's block of S.  The block
+// is clamped by pair_geom to S (n_rows, n_cols) and to the longest side, so no table can direct a store outside S; for a
+// table within the DP launch's max_la / max_lb — every table the callers build — it is the block the DP kernel read.
 __global__ __launch_bounds__(64) void align_traceback_kernel(const long long* __restrict__ table, int n_pairs, int local,
+                                                             int free_ends, float* __restrict__ S_mask, int ldS, int n_rows,
+                                                             int n_cols_S,
                                                              const int* __restrict__ end, const unsigned char* __restrict__ tb,
                                                              long long tb_bytes, const long long* __restrict__ slot,
                                                              int* __restrict__ cols, long long cols_cap, int* __restrict__ n_cols,
@@ -269,6 +310,9 @@ __global__ __launch_bounds__(64) void align_traceback_kernel(const long long* __
     const long long need = (long long)La * ldtb, cap = (long long)La + Lb;
     int i = min(max(end[2 * p], 0), La), j = min(max(end[2 * p + 1], 0), Lb);
     int n = 0, nm = 0;
+    PairGeom g = {0, 0, 0, 0};
+    if (S_mask) g = pair_geom(t, kAlignMaxLen, kAlignMaxLen, n_rows, n_cols_S);
+    float* Sp = S_mask ? S_mask + (size_t)g.a_off * ldS + g.b_off : nullptr;
     if (La >= 1 && Lb >= 1 && need <= tb_bytes && cap <= cols_cap) {
         const unsigned char* tp = tb + clampll(t[4] & ~7LL, 0, tb_bytes - need);
         int* out = cols + 2 * (clampll(slot[p], 0, cols_cap - cap) + cap);
@@ -277,7 +321,7 @@ __global__ __launch_bounds__(64) void align_traceback_kernel(const long long* __
             if (i == 0 && j == 0) break;
             int ci, cj;
             if (i == 0 || j == 0) {
-                if (local) break;
+                if (local || (free_ends & (j == 0 ? 1 : 4))) break;
                 if (j == 0) ci = --i, cj = -1;
                 else ci = -1, cj = --j;
                 state = 0;
@@ -291,6 +335,7 @@ __global__ __launch_bounds__(64) void align_traceback_kernel(const long long* __
                         ci = --i, cj = --j;
                         ++nm, ++n;
                         out[-2 * n] = ci, out[-2 * n + 1] = cj;
+                        if (Sp && ci < g.La && cj < g.Lb) Sp[(size_t)ci * ldS + cj] = -__builtin_inff();
                         continue;
                     }
                 }
@@ -358,14 +403,21 @@ int esmk_op_align_enhance(float* S_dev, int ldS, int n_rows, int n_cols, const i
     return 0;
 }
 
-int esmk_op_align_dp(const float* S_dev, int ldS, int n_rows, int n_cols, const int64_t* table_dev, int n_pairs, int mode,
-                     float gap_open, float gap_extend, int max_la, int max_lb, float* score_dev, int32_t* end_dev, uint8_t* tb_dev,
-                     long long tb_bytes, int want_traceback, float* ws_dev, long long ws_floats, void* stream) {
-    const std::string w("esmk_op_align_dp");
+static int check_free_ends(const std::string& w, int mode, int free_ends) {
+    if (free_ends < 0 || free_ends > 15) return fail(w + ": free_ends must be 0 .. 15 (1 a_start, 2 a_end, 4 b_start, 8 b_end)");
+    if (free_ends != 0 && mode != 0) return fail(w + ": free_ends requires mode 0 (global)");
+    return 0;
+}
+
+static int align_dp(const std::string& w, const float* S_dev, int ldS, int n_rows, int n_cols, const int64_t* table_dev, int n_pairs,
+                    int mode, int free_ends, float gap_open, float gap_extend, int max_la, int max_lb, float* score_dev,
+                    int32_t* end_dev, uint8_t* tb_dev, long long tb_bytes, int want_traceback, float* ws_dev, long long ws_floats,
+                    void* stream) {
     if (max_la < 1 || max_la > kAlignMaxLen || max_lb < 1 || max_lb > kAlignMaxLen) return fail(w + ": max_la and max_lb must be 1 .. 8192");
     if (int rc = check_s(w, S_dev, ldS, n_rows, n_cols, table_dev, n_pairs)) return rc;
     if (!score_dev || !end_dev) return fail(w + ": null argument");
     if (mode != 0 && mode != 1) return fail(w + ": mode must be 0 (global) or 1 (local)");
+    if (int rc = check_free_ends(w, mode, free_ends)) return rc;
     if (!(gap_extend >= 0.f) || !(gap_open >= gap_extend) || std::isinf(gap_open)) return fail(w + ": need 0 <= gap_extend <= gap_open < inf");
     if ((want_traceback | 1) != 1) return fail(w + ": want_traceback must be 0 or 1");
     if (want_traceback && (!tb_dev || tb_bytes <= 0 || misaligned(tb_dev, 8))) return fail(w + ": the traceback buffer must be given, 8-byte aligned");
@@ -378,10 +430,50 @@ int esmk_op_align_dp(const float* S_dev, int ldS, int n_rows, int n_cols, const 
     }
     AlignDpArgs a;
     a.S = S_dev, a.ldS = ldS, a.n_rows = n_rows, a.n_cols = n_cols, a.table = (const long long*)table_dev, a.n_pairs = n_pairs;
-    a.local = mode, a.o = gap_open, a.e = gap_extend, a.max_la = max_la, a.max_lb = max_lb, a.score = score_dev, a.end = end_dev;
+    a.local = mode, a.free_ends = free_ends, a.o = gap_open, a.e = gap_extend, a.max_la = max_la, a.max_lb = max_lb, a.score = score_dev, a.end = end_dev;
     a.tb = want_traceback ? tb_dev : nullptr, a.tb_bytes = want_traceback ? tb_bytes : 0;
     a.ws = max_lb > kPanel ? (f32x2*)ws_dev : nullptr, a.n_waves = (int)n_waves;
-    hipLaunchKernelGGL(align_dp_kernel, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(free_ends != 0 ? align_dp_free_kernel : align_dp_kernel, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0,
+                       (hipStream_t)stream, a);
+    ESMK_TRY(hipGetLastError());
+    return 0;
+}
+
+int esmk_op_align_dp(const float* S_dev, int ldS, int n_rows, int n_cols, const int64_t* table_dev, int n_pairs, int mode,
+                     float gap_open, float gap_extend, int max_la, int max_lb, float* score_dev, int32_t* end_dev, uint8_t* tb_dev,
+                     long long tb_bytes, int want_traceback, float* ws_dev, long long ws_floats, void* stream) {
+    return align_dp("esmk_op_align_dp", S_dev, ldS, n_rows, n_cols, table_dev, n_pairs, mode, 0, gap_open, gap_extend, max_la, max_lb,
+                    score_dev, end_dev, tb_dev, tb_bytes, want_traceback, ws_dev, ws_floats, stream);
+}
+
+int esmk_op_align_dp_ex(const float* S_dev, int ldS, int n_rows, int n_cols, const int64_t* table_dev, int n_pairs, int mode,
+                        int free_ends, float gap_open, float gap_extend, int max_la, int max_lb, float* score_dev, int32_t* end_dev,
+                        uint8_t* tb_dev, long long tb_bytes, int want_traceback, float* ws_dev, long long ws_floats, void* stream) {
+    return align_dp("esmk_op_align_dp_ex", S_dev, ldS, n_rows, n_cols, table_dev, n_pairs, mode, free_ends, gap_open, gap_extend,
+                    max_la, max_lb, score_dev, end_dev, tb_dev, tb_bytes, want_traceback, ws_dev, ws_floats, stream);
+}
+
+static int align_traceback(const std::string& w, const int64_t* table_dev, int n_pairs, int mode, int free_ends,
+                           const int32_t* end_dev, const uint8_t* tb_dev, long long tb_bytes, const int64_t* slot_dev,
+                           int32_t* cols_dev, long long cols_cap, int32_t* n_cols_dev, int32_t* n_match_dev, int32_t* start_dev,
+                           float* S_mask_dev, int ldS, int n_rows, int n_cols, void* stream) {
+    if (!table_dev || !end_dev || !tb_dev || !slot_dev || !cols_dev || !n_cols_dev || !n_match_dev || !start_dev) return fail(w + ": null argument");
+    if (n_pairs < 0 || n_pairs > ESMK_MAX_ROWS) return fail(w + ": need 0 <= n_pairs <= 2^24");
+    if (mode != 0 && mode != 1) return fail(w + ": mode must be 0 (global) or 1 (local)");
+    if (int rc = check_free_ends(w, mode, free_ends)) return rc;
+    if (S_mask_dev) {
+        if (n_rows <= 0 || n_rows > ESMK_MAX_ROWS || n_cols <= 0 || n_cols % 8 != 0 || ldS < n_cols || ldS % 4 != 0)
+            return fail(w + ": S_mask needs 0 < n_rows <= 2^24, n_cols a positive multiple of 8, ldS a multiple of 4 that is >= n_cols");
+        if (misaligned(S_mask_dev, 16)) return fail(w + ": S_mask must be 16-byte aligned");
+    } else if (ldS != 0 || n_rows != 0 || n_cols != 0) {
+        return fail(w + ": without S_mask, ldS, n_rows and n_cols must be 0");
+    }
+    if (tb_bytes <= 0 || cols_cap <= 0) return fail(w + ": tb_bytes and cols_cap must be positive");
+    if (misaligned(table_dev, 8) || misaligned(slot_dev, 8)) return fail(w + ": the table and the slots must be 8-byte aligned");
+    if (n_pairs == 0) return 0;
+    hipLaunchKernelGGL(align_traceback_kernel, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
+                       (const long long*)table_dev, n_pairs, mode, free_ends, S_mask_dev, ldS, n_rows, n_cols, end_dev, tb_dev,
+                       tb_bytes, (const long long*)slot_dev, cols_dev, cols_cap, n_cols_dev, n_match_dev, start_dev);
     ESMK_TRY(hipGetLastError());
     return 0;
 }
@@ -389,18 +481,16 @@ int esmk_op_align_dp(const float* S_dev, int ldS, int n_rows, int n_cols, const 
 int esmk_op_align_traceback(const int64_t* table_dev, int n_pairs, int mode, const int32_t* end_dev, const uint8_t* tb_dev,
                             long long tb_bytes, const int64_t* slot_dev, int32_t* cols_dev, long long cols_cap, int32_t* n_cols_dev,
                             int32_t* n_match_dev, int32_t* start_dev, void* stream) {
-    const std::string w("esmk_op_align_traceback");
-    if (!table_dev || !end_dev || !tb_dev || !slot_dev || !cols_dev || !n_cols_dev || !n_match_dev || !start_dev) return fail(w + ": null argument");
-    if (n_pairs < 0 || n_pairs > ESMK_MAX_ROWS) return fail(w + ": need 0 <= n_pairs <= 2^24");
-    if (mode != 0 && mode != 1) return fail(w + ": mode must be 0 (global) or 1 (local)");
-    if (tb_bytes <= 0 || cols_cap <= 0) return fail(w + ": tb_bytes and cols_cap must be positive");
-    if (misaligned(table_dev, 8) || misaligned(slot_dev, 8)) return fail(w + ": the table and the slots must be 8-byte aligned");
-    if (n_pairs == 0) return 0;
-    hipLaunchKernelGGL(align_traceback_kernel, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
-                       (const long long*)table_dev, n_pairs, mode, end_dev, tb_dev, tb_bytes, (const long long*)slot_dev, cols_dev,
-                       cols_cap, n_cols_dev, n_match_dev, start_dev);
-    ESMK_TRY(hipGetLastError());
-    return 0;
+    return align_traceback("esmk_op_align_traceback", table_dev, n_pairs, mode, 0, end_dev, tb_dev, tb_bytes, slot_dev, cols_dev,
+                           cols_cap, n_cols_dev, n_match_dev, start_dev, nullptr, 0, 0, 0, stream);
+}
+
+int esmk_op_align_traceback_ex(const int64_t* table_dev, int n_pairs, int mode, int free_ends, const int32_t* end_dev,
+                               const uint8_t* tb_dev, long long tb_bytes, const int64_t* slot_dev, int32_t* cols_dev,
+                               long long cols_cap, int32_t* n_cols_dev, int32_t* n_match_dev, int32_t* start_dev, float* S_mask_dev,
+                               int ldS, int n_rows, int n_cols, void* stream) {
+    return align_traceback("esmk_op_align_traceback_ex", table_dev, n_pairs, mode, free_ends, end_dev, tb_dev, tb_bytes, slot_dev,
+                           cols_dev, cols_cap, n_cols_dev, n_match_dev, start_dev, S_mask_dev, ldS, n_rows, n_cols, stream);
 }
 
 }  // extern "C"

@@ -12,14 +12,17 @@ a3m file is made of.  What hhblits and hhfilter do after their search is done he
 in numpy and plain loops, and the device path reproduces that exactly):
 1. One ``search_and_align`` call for all queries.  ``align_kw`` defaults to ``mode="local", enhance=True``: raw cosines of
    unrelated residues are all positive, so a local alignment on them spans everything.  These defaults and the gap penalties
-   (``align``'s o = 1.0, e = 0.1) are this project's choice; they are not tuned on any benchmark.
+   (``align``'s o = 1.0, e = 0.1) are this project's choice; they are not tuned on any benchmark.  ``free_ends="b"`` (with
+   ``mode="global"``) aligns the whole query inside each hit instead.  ``hits_per_pair=K`` > 1: every VALID hit of a target
+   (``align``'s ``valid``) is a candidate row of its own, with the target's ``hit_id`` and, from the second on, the label
+   ``<label>|hit=<k>`` — a repeat protein gives one row per copy of the query it holds.
 2. Per query, its hits' sequences go to the device as one blob and ``esmk_op_msa_project`` writes one row of Lq bytes per hit:
    '-' everywhere, the hit's letter in every matched query column; and per hit six integers (``STATS``).  The unaligned ends of
    a hit and its insertions are not in the row (an a3m's match states).
 3. The row filter, on the int32 stats on the device: a hit stays when ``n_match >= 1``, ``n_match >= min_coverage * Lq`` and
    ``n_ident >= min_query_identity * n_match`` — each product in fp64, the integers converted exactly.
 4. The redundancy filter at ``max_identity`` (hhfilter's -id; None skips it).  The rows are ranked: the query, then the hits by
-   alignment score descending, ties to the prefilter's rank.  The gap-aware identity of two rows is same / both
+   alignment score descending, ties to the prefilter's rank, then to the lower hit number k.  The gap-aware identity of two rows is same / both
    (``esmk_op_msa_pair_identity``: ``both`` the columns in which neither has a gap, ``same`` those in which they agree; 0 when
    ``both < min_overlap``).  Walk the rows by rank: a row that no earlier kept row has covered is kept and covers every later
    row whose identity to it is at least ``max_identity`` — the greedy cover of esm_amd/cluster.py on the thresholded identity
@@ -30,8 +33,8 @@ in numpy and plain loops, and the device path reproduces that exactly):
    keeps the best ranked.
 Between 2 and 5 the host reads the number of kept rows and the undecided counts of ``greedy_rounds``, nothing else.
 
-Not built: one command that loads both models and chains into ``predict_msa``; iterative (profile) search rounds; semiglobal
-alignment; several local hits per target; a projection launch that serves several queries.
+Not built: one command that loads both models and chains into ``predict_msa``; iterative (profile) search rounds; a projection
+launch that serves several queries.
 """
 import numpy as np
 import torch
@@ -77,6 +80,10 @@ def check_args(index, depth=None, min_coverage=0.5, max_identity=0.9, min_query_
             raise ValueError(f"build_msas: {k} is not an argument of this call")
     kw = dict(mode="local", enhance=True)
     kw.update(align_kw)
+    if "free_ends" in kw or "hits_per_pair" in kw or "min_hit_score" in kw:
+        from .align import check_hits
+
+        check_hits(kw["mode"], kw.get("free_ends"), kw.get("hits_per_pair", 1), kw.get("min_hit_score", 0.0))
     return depth, min_coverage, max_identity, min_query_identity, int(min_overlap), kw
 
 
@@ -246,10 +253,11 @@ def redundancy_keep(M, Lq, order, max_identity, min_overlap, max_bytes):
 
 
 def msa_from_hits(query, index, hit_ids, scores, cols, col_offsets, depth=None, min_coverage=0.5, max_identity=0.9,
-                  min_query_identity=0.0, min_overlap=8, subsample="first", theta=0.2, seed=0, max_bytes=2 << 30):
+                  min_query_identity=0.0, min_overlap=8, subsample="first", theta=0.2, seed=0, max_bytes=2 << 30, hit_numbers=None):
     """Steps 2 to 5 for one query: ``query`` (label, sequence); ``hit_ids`` the database ids of its P hits in the prefilter's
     order (host ints), ``scores`` fp32 [P] their alignment scores, ``cols`` / ``col_offsets`` (int64 [P + 1], indexing ``cols``)
-    their paths, on the device.  Returns a ``BuiltMSA``."""
+    their paths, on the device.  ``hit_numbers`` (several hits per target): per hit its number k among its target's hits, a
+    target's hits standing one after the other; k >= 1 is labelled ``<label>|hit=<k>``.  Returns a ``BuiltMSA``."""
     from . import ops
     from .msa_select import subsample_indices
 
@@ -293,13 +301,27 @@ def msa_from_hits(query, index, hit_ids, scores, cols, col_offsets, depth=None, 
         offs = col_offsets.cpu().tolist() if P else [0]
         kept_hits = [r - 1 for r in sel_host[1:]]
         counts = dict(hits=P, after_row_filter=passed.sum(), after_redundancy_filter=n_nonredundant, kept=len(sel_host))
-        return BuiltMSA(M[sel][:, :Lq].contiguous(), [label] + [index.labels[hit_ids[h]] for h in kept_hits], ids_dev[sel], all_scores[sel],
+        names = [index.labels[t] for t in hit_ids]
+        if hit_numbers is not None:
+            names = [f"{name}|hit={int(k)}" if k else name for name, k in zip(names, hit_numbers)]
+        return BuiltMSA(M[sel][:, :Lq].contiguous(), [label] + [names[h] for h in kept_hits], ids_dev[sel], all_scores[sel],
                         stats[sel], counts=counts, paths=(cols, [(offs[h], offs[h + 1]) for h in kept_hits], [seqs[h] for h in kept_hits]))
 
 
 def msas_from_alignment(queries, index, alignment, **kw):
-    """Steps 2 to 5 for every query on the ``alignment`` dict of one ``search_and_align(..., paths=True)`` call."""
+    """Steps 2 to 5 for every query on the ``alignment`` dict of one ``search_and_align(..., paths=True)`` call.  An alignment
+    with several hits per pair (``hit``, ``valid``) is cut down to its valid entries first: one read of their number."""
     queries = [(str(a), str(b)) for a, b in queries]
+    hit_numbers = None
+    if "valid" in alignment:
+        keep = alignment["valid"].nonzero().flatten()
+        nc = alignment["n_cols"].long()
+        nk = nc[keep]
+        offsets = torch.cat([nk.new_zeros(1), nk.cumsum(0)])
+        total = int(offsets[-1])
+        pos = torch.repeat_interleave((nc.cumsum(0) - nc)[keep] - offsets[:-1], nk, output_size=total) + torch.arange(total, device=nk.device)
+        hit_numbers = alignment["hit"][keep].cpu().tolist()
+        alignment = dict(pairs=alignment["pairs"][keep], score=alignment["score"][keep], cols=alignment["cols"][pos], col_offsets=offsets)
     pairs = alignment["pairs"].cpu().numpy()
     bounds = np.searchsorted(pairs[:, 0], np.arange(len(queries) + 1))  # (pairs are in query order)
     dev = alignment["pairs"].device
@@ -310,7 +332,8 @@ def msas_from_alignment(queries, index, alignment, **kw):
             cols, col_offsets = alignment["cols"], alignment["col_offsets"][p0:p1 + 1]
         else:
             cols, col_offsets = torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros((1,), dtype=torch.int64, device=dev)
-        out.append(msa_from_hits(query, index, [int(t) for t in pairs[p0:p1, 1]], alignment["score"][p0:p1], cols, col_offsets, **kw))
+        out.append(msa_from_hits(query, index, [int(t) for t in pairs[p0:p1, 1]], alignment["score"][p0:p1], cols, col_offsets,
+                                 hit_numbers=None if hit_numbers is None else hit_numbers[p0:p1], **kw))
     return out
 
 
@@ -318,7 +341,7 @@ def build_msas(model, alphabet, queries, index, top_k=1024, depth=None, min_cove
                min_overlap=8, subsample="first", theta=0.2, seed=0, batch_tokens=65536, max_bytes=2 << 30, **align_kw):
     """One ``BuiltMSA`` per query (module docstring).  ``queries``: records [(label, sequence)]; ``index`` holds its sequences
     and is on the device; ``top_k`` hits per query go to the aligner.  ``align_kw`` (mode, gap_open, gap_extend, enhance,
-    max_bytes) defaults to ``mode="local", enhance=True``: these and the gap penalties are this project's choice and are not
+    max_bytes, free_ends, hits_per_pair, min_hit_score) defaults to ``mode="local", enhance=True``: these and the gap penalties are this project's choice and are not
     tuned on any benchmark.  ``max_bytes`` bounds one block of the identity matrix."""
     from .search import check_model, search_and_align
 
@@ -358,7 +381,9 @@ def parse_args(argv=None):
     p.add_argument("--max-identity", type=float, default=0.9, help="pairwise identity at which a better ranked row covers another")
     p.add_argument("--min-query-identity", type=float, default=0.0, help="identical share of a hit's matches it needs")
     p.add_argument("--subsample", choices=[s for s in STRATEGIES if s != "greedy-min"], default="first")
-    p.add_argument("--mode", choices=("local", "global"), default="local")
+    p.add_argument("--mode", choices=("local", "global"), default=None, help="default: local")
+    from .align import add_hit_options, resolve_hit_options
+    add_hit_options(p, "target")
     p.add_argument("--gap-open", type=float, default=1.0)
     p.add_argument("--gap-extend", type=float, default=0.1)
     p.add_argument("--no-enhance", action="store_true", help="align on raw cosines (default: row and column z-scores)")
@@ -367,6 +392,7 @@ def parse_args(argv=None):
                                                    "the identity (redundancy) filter, the rows written, and Neff")
     p.add_argument("--batch-tokens", type=int, default=65536)
     args = p.parse_args(argv)
+    resolve_hit_options(p, args, "local")
     if not 1 <= args.top <= 1024:
         p.error("--top must be 1 .. 1024")
     if args.depth is not None and args.depth < 1:
@@ -407,7 +433,7 @@ def main(argv=None):
     built = build_msas(model, alphabet, queries, index, top_k=args.top, depth=args.depth, min_coverage=args.min_coverage,
                        max_identity=args.max_identity, min_query_identity=args.min_query_identity, subsample=args.subsample,
                        batch_tokens=args.batch_tokens, mode=args.mode, gap_open=args.gap_open, gap_extend=args.gap_extend,
-                       enhance=not args.no_enhance)
+                       enhance=not args.no_enhance, free_ends=args.free_ends, hits_per_pair=args.hits_per_target)
     os.makedirs(args.output_dir, exist_ok=True)
     for name, b in zip(names, built):
         b.write_a3m(os.path.join(args.output_dir, name), insertions=not args.no_insertions)

@@ -1482,10 +1482,11 @@ def align_enhance(S, table, max_lb, n_rows=None, n_cols=None, ws=None):
 
 
 def align_dp(S, table, mode, gap_open, gap_extend, max_la, max_lb, want_traceback=True, tb=None, n_rows=None, n_cols=None, ws=None,
-             score=None, end=None):
-    """``esmk_op_align_dp``: per listed pair the affine-gap DP on its block of S -> dict(score fp32 [P], end int32 [P, 2]) and, with
+             score=None, end=None, free_ends=0):
+    """``esmk_op_align_dp_ex``: per listed pair the affine-gap DP on its block of S -> dict(score fp32 [P], end int32 [P, 2]) and, with
     ``want_traceback``, ``tb`` uint8 (the caller's, or allocated to hold what the table's offsets address — the table is then
-    read on the host).  mode 0 global, 1 local.  ``ws``: the boundary-column scratch a side b beyond ``align_panel()`` needs."""
+    read on the host).  mode 0 global, 1 local.  ``ws``: the boundary-column scratch a side b beyond ``align_panel()`` needs.
+    ``free_ends``: the free-end mask of global mode (1 a_start, 2 a_end, 4 b_start, 8 b_end; 0: plain global)."""
     n_rows, n_cols = _align_s(S, table, n_rows, n_cols)
     P = table.shape[0]
     dev = S.device
@@ -1498,19 +1499,22 @@ def align_dp(S, table, mode, gap_open, gap_extend, max_la, max_lb, want_tracebac
     if int(max_lb) > align_panel() and ws is None:
         ws = torch.empty((max(min(P, 16384), 1) * 2 * (int(max_la) + 1),), dtype=torch.float32, device=dev)
     _req_cuda(tb, ws)
-    N.check(N.lib.esmk_op_align_dp(N.ptr(S), S.shape[1], n_rows, n_cols, N.ptr(table), P, int(mode), float(gap_open),
-                                   float(gap_extend), int(max_la), int(max_lb), N.ptr(score), N.ptr(end),
-                                   N.ptr(tb if want_traceback else None), tb.numel() if want_traceback else 0,
-                                   int(bool(want_traceback)), N.ptr(ws), 0 if ws is None else ws.numel(), N.cur_stream()))
+    N.check(N.lib.esmk_op_align_dp_ex(N.ptr(S), S.shape[1], n_rows, n_cols, N.ptr(table), P, int(mode), int(free_ends),
+                                      float(gap_open), float(gap_extend), int(max_la), int(max_lb), N.ptr(score), N.ptr(end),
+                                      N.ptr(tb if want_traceback else None), tb.numel() if want_traceback else 0,
+                                      int(bool(want_traceback)), N.ptr(ws), 0 if ws is None else ws.numel(), N.cur_stream()))
     out = dict(score=score, end=end)
     if want_traceback:
         out["tb"] = tb
     return out
 
 
-def align_traceback(table, mode, end, tb, slot, cols, n_cols=None, n_match=None, start=None):
-    """``esmk_op_align_traceback``: walks the bytes of ``align_dp`` from ``end`` -> dict(n_cols, n_match int32 [P], start int32
-    [P, 2]); the columns go into the back of each pair's slot (first column ``slot[p]``, La + Lb long) of ``cols`` int32 [cap, 2]."""
+def align_traceback(table, mode, end, tb, slot, cols, n_cols=None, n_match=None, start=None, free_ends=0, S_mask=None,
+                    n_rows_S=None, n_cols_S=None):
+    """``esmk_op_align_traceback_ex``: walks the bytes of ``align_dp`` from ``end`` -> dict(n_cols, n_match int32 [P], start int32
+    [P, 2]); the columns go into the back of each pair's slot (first column ``slot[p]``, La + Lb long) of ``cols`` int32 [cap, 2].
+    ``free_ends``: the mask ``align_dp`` ran with.  ``S_mask``: the S of ``align_dp`` — every match cell of every walked path is
+    set to -inf in it, so that the next ``align_dp`` on it finds each pair's next path; pair blocks must not overlap."""
     _req_cuda(table, end, tb, slot, cols)
     assert table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 5
     assert end.dtype == torch.int32 and tb.dtype == torch.uint8 and slot.dtype == torch.int64 and cols.dtype == torch.int32
@@ -1520,8 +1524,13 @@ def align_traceback(table, mode, end, tb, slot, cols, n_cols=None, n_match=None,
     n_cols = _out(n_cols, (P,), torch.int32, dev)
     n_match = _out(n_match, (P,), torch.int32, dev)
     start = _out(start, (P, 2), torch.int32, dev)
-    N.check(N.lib.esmk_op_align_traceback(N.ptr(table), P, int(mode), N.ptr(end), N.ptr(tb), tb.numel(), N.ptr(slot), N.ptr(cols),
-                                          cols.shape[0], N.ptr(n_cols), N.ptr(n_match), N.ptr(start), N.cur_stream()))
+    ldS = rows_S = cols_S = 0
+    if S_mask is not None:
+        rows_S, cols_S = _align_s(S_mask, table, n_rows_S, n_cols_S)
+        ldS = S_mask.shape[1]
+    N.check(N.lib.esmk_op_align_traceback_ex(N.ptr(table), P, int(mode), int(free_ends), N.ptr(end), N.ptr(tb), tb.numel(),
+                                             N.ptr(slot), N.ptr(cols), cols.shape[0], N.ptr(n_cols), N.ptr(n_match), N.ptr(start),
+                                             N.ptr(S_mask), ldS, rows_S, cols_S, N.cur_stream()))
     return dict(n_cols=n_cols, n_match=n_match, start=start)
 
 

@@ -484,7 +484,8 @@ def search_and_align(model, alphabet, queries, index, top_k, align_top=None, bat
                      **align_kw):
     """The prefilter, then the aligner on the survivors.  ``queries``: records [(label, sequence)]; ``index`` holds its
     sequences and is on the device.  Every query's ``align_top`` (None: all ``top_k``) best hits are aligned by
-    ``align.align_listed_rows`` (``align_kw``: mode, gap_open, gap_extend, enhance, paths, max_bytes) on representation
+    ``align.align_listed_rows`` (``align_kw``: mode, gap_open, gap_extend, enhance, paths, max_bytes, free_ends, hits_per_pair,
+    min_hit_score — with K hits per pair every pair stands K times, with ``hit`` and ``valid``) on representation
     ``index.meta["layer"]``, queries in groups whose hit union fits ``batch_tokens``.  Returns the prefilter's ``scores`` /
     ``ids`` and ``alignment``: align's dict with ``pairs`` int32 [P, 2] = (query, database id), in query order, each query's
     hits by rank."""
@@ -497,6 +498,8 @@ def search_and_align(model, alphabet, queries, index, top_k, align_top=None, bat
     if "pairs" in align_kw or "return_similarity" in align_kw or "similarity" in align_kw:
         raise ValueError("search_and_align: pairs, similarity and return_similarity are not arguments of this call")
     A.check_args(align_kw.get("mode", "global"), align_kw.get("gap_open", 1.0), align_kw.get("gap_extend", 0.1))
+    _, n_hits, _ = A.check_hits(align_kw.get("mode", "global"), align_kw.get("free_ends"), align_kw.get("hits_per_pair", 1),
+                                align_kw.get("min_hit_score", 0.0), align_kw.get("paths", True))
     queries = [(str(a), str(b)) for a, b in queries]
     layer = int(index.meta["layer"])
     qvec = pool_records(model, alphabet, queries, layer, batch_tokens, varlen)
@@ -526,6 +529,8 @@ def search_and_align(model, alphabet, queries, index, top_k, align_top=None, bat
     if not parts:
         alignment = dict(pairs=torch.zeros((0, 2), dtype=torch.int32, device=dev), score=torch.zeros((0,), dtype=torch.float32, device=dev),
                          end=torch.zeros((0, 2), dtype=torch.int32, device=dev))
+        if n_hits > 1:
+            alignment.update(hit=torch.zeros((0,), dtype=torch.int32, device=dev), valid=torch.zeros((0,), dtype=torch.bool, device=dev))
     else:
         alignment = {k: torch.cat([p[k] for p in parts], 0) for k in ("pairs", "score", "end")}
         if paths:
@@ -533,6 +538,9 @@ def search_and_align(model, alphabet, queries, index, top_k, align_top=None, bat
                 alignment[k] = torch.cat([p[k] for p in parts], 0)
             nc = alignment["n_cols"].long()
             alignment["col_offsets"] = torch.cat([nc.new_zeros(1), nc.cumsum(0)])
+        if n_hits > 1:
+            for k in ("hit", "valid"):
+                alignment[k] = torch.cat([p[k] for p in parts], 0)
     return dict(scores=pre["scores"], ids=pre["ids"], alignment=alignment)
 
 
@@ -540,9 +548,9 @@ def search_and_align(model, alphabet, queries, index, top_k, align_top=None, bat
 TSV_HEADER = ("query", "target", "rank", "cosine")
 
 
-def write_tsv(fh, hits, aligned=False):
+def write_tsv(fh, hits, aligned=False, hit_column=False):
     """One line per hit: query, target, rank (1-based), cosine; with ``aligned`` the columns of ``align.write_tsv`` follow
-    (score, score_per_residue, n_match, query_range, target_range).  ``hits``: dicts with query, target, rank, cosine and, when
+    (score, score_per_residue, n_match, query_range, target_range and, with ``hit_column``, hit).  ``hits``: dicts with query, target, rank, cosine and, when
     aligned, what ``align.write_tsv`` reads."""
     import io
 
@@ -551,7 +559,7 @@ def write_tsv(fh, hits, aligned=False):
     tail = []
     if aligned:
         buf = io.StringIO()
-        A.write_tsv(buf, hits)
+        A.write_tsv(buf, hits, hit_column=hit_column)
         tail = [line.split("\t")[2:] for line in buf.getvalue().splitlines()]
     fh.write("\t".join(TSV_HEADER + (tuple(tail[0]) if aligned else ())) + "\n")
     for i, h in enumerate(hits):
@@ -579,7 +587,9 @@ def parse_args(argv=None):
     b.add_argument("--top", type=int, required=True, help="hits per query (1 .. 1024)")
     b.add_argument("--align", action="store_true", help="align the hits (needs an index with sequences)")
     b.add_argument("--align-top", type=int, default=None, help="align only the M best hits of every query")
-    b.add_argument("--mode", choices=("global", "local"), default="global")
+    b.add_argument("--mode", choices=("global", "local"), default=None, help="default: global")
+    from .align import add_hit_options, resolve_hit_options
+    add_hit_options(b, "target")
     b.add_argument("--gap-open", type=float, default=1.0)
     b.add_argument("--gap-extend", type=float, default=0.1)
     b.add_argument("--enhance", action="store_true", help="sharpen S by row and column z-scores")
@@ -591,8 +601,10 @@ def parse_args(argv=None):
     if args.command == "query":
         if not 1 <= args.top <= MAX_K:
             p.error(f"--top must be 1 .. {MAX_K}")
-        if not args.align and (args.align_top is not None or args.alignments or args.enhance):
-            p.error("--align-top, --alignments and --enhance need --align")
+        if not args.align and (args.align_top is not None or args.alignments or args.enhance or args.free_ends is not None
+                               or args.hits_per_target != 1):
+            p.error("--align-top, --alignments, --enhance, --free-ends and --hits-per-target need --align")
+        resolve_hit_options(p, args, "global")
         if args.align_top is not None and args.align_top < 1:
             p.error("--align-top must be at least 1")
     return args
@@ -611,6 +623,7 @@ def main(argv=None):
 
     if args.command == "query":
         A.check_args(args.mode, args.gap_open, args.gap_extend)
+        A.check_hits(args.mode, args.free_ends, args.hits_per_target)
         index = EmbeddingIndex.load(args.index)
         if args.align and index.sequences is None:
             raise ValueError("search: --align needs an index with sequences (it was written with --no-sequences)")
@@ -628,13 +641,14 @@ def main(argv=None):
     if args.align:
         out = search_and_align(model, alphabet, queries, index, args.top, align_top=args.align_top, batch_tokens=args.batch_tokens,
                                search_bytes=args.max_bytes, mode=args.mode, gap_open=args.gap_open, gap_extend=args.gap_extend,
-                               enhance=args.enhance)
+                               enhance=args.enhance, free_ends=args.free_ends, hits_per_pair=args.hits_per_target)
     else:
         qvec = pool_records(model, alphabet, queries, int(index.meta["layer"]), args.batch_tokens)
         out = index.search(qvec, args.top, max_bytes=args.max_bytes)
     scores, ids = out["scores"].cpu().numpy(), out["ids"].cpu().numpy()
     al = {k: v.cpu().numpy() for k, v in out["alignment"].items()} if args.align else None
-    by_pair = {} if al is None else {(int(q), int(t)): p for p, (q, t) in enumerate(al["pairs"])}
+    K = args.hits_per_target if args.align else 1
+    by_pair = {} if al is None else {(int(q), int(t)): p for p, (q, t) in list(enumerate(al["pairs"]))[::K]}  # a pair's first entry
     hits = []
     for q in range(len(queries)):
         for r in range(ids.shape[1]):
@@ -646,11 +660,18 @@ def main(argv=None):
             if args.align:
                 if p is None:  # beyond --align-top: ranked, not aligned
                     continue
-                h.update(score=float(al["score"][p]), la=len(queries[q][1]), lb=int(index.lengths[t]), n_match=int(al["n_match"][p]),
-                         start=al["start"][p].tolist(), end=al["end"][p].tolist(), pair=p, q=q, t=t)
+                for k in range(K):  # of several hits per target the best is always listed, the others when they are valid
+                    if k and not al["valid"][p + k]:
+                        break
+                    hk = dict(h)
+                    hk.update(score=float(al["score"][p + k]), la=len(queries[q][1]), lb=int(index.lengths[t]),
+                              n_match=int(al["n_match"][p + k]), start=al["start"][p + k].tolist(), end=al["end"][p + k].tolist(),
+                              pair=p + k, q=q, t=t, hit=k)
+                    hits.append(hk)
+                continue
             hits.append(h)
     with open(args.output, "w") as fh:
-        write_tsv(fh, hits, aligned=args.align)
+        write_tsv(fh, hits, aligned=args.align, hit_column=K > 1)
     if args.alignments:
         with open(args.alignments, "w") as fh:
             for h in hits:

@@ -1211,7 +1211,19 @@ int esmk_op_sae_decode(const int32_t* indices_dev, const float* values_dev, int 
  * esmk_op_align_traceback: one thread per pair walks from end[p] and writes the columns — (i, j) a match, (i, -1) residue i of
  *   a against a gap, (-1, j) — in ascending order into the BACK of the pair's slot of La + Lb columns: cols int32 [cols_cap, 2],
  *   slot_dev int64 [n_pairs] the slots' first columns; n_cols, n_match int32 [n_pairs], start int32 [n_pairs, 2] the cell the
- *   walk ended in.  At most La + Lb steps are taken whatever the bytes hold. */
+ *   walk ended in.  At most La + Lb steps are taken whatever the bytes hold.
+ * esmk_op_align_dp_ex / esmk_op_align_traceback_ex: the same with free end gaps.  free_ends (0 .. 15, mode 0 only; 0 is the
+ *   plain entry): 1 a_start: H[i][0] = 0, the walk stops on column 0; 4 b_start: on row 0 the stop candidate is 0 (H[0][j] = 0,
+ *   choice "stop"), the walk stops on row 0; 2 a_end: the cells (i, Lb), i = 1 .. La, are end-cell candidates next to the corner
+ *   (La, Lb); 8 b_end: the cells (La, j), j = 1 .. Lb.  The largest H among the candidates wins, ties go to the lower row, then
+ *   the lower column; cells with i = 0 or j = 0 are never candidates.  E and F on the borders, every fp32 operation and the
+ *   byte layout are unchanged.  Refused before any HIP call: free_ends outside 0 .. 15, free_ends != 0 with mode 1.
+ *   S_mask_dev (traceback_ex; NULL: none, and ldS = n_rows = n_cols = 0): the S of the DP call, writable, with its ldS, n_rows,
+ *   n_cols: the walking thread stores -inf at S[i][j] of every MATCH column (i, j) of its path, inside the pair's block clamped
+ *   to S and to the longest side (no table can direct a store outside S; for a table within the DP call's max_la / max_lb it is
+ *   the block the DP read), so that the next esmk_op_align_dp_ex on the same S finds the pair's next best path (Waterman-Eggert;
+ *   gap states may cross earlier paths).  A pair's block must belong to that pair alone: no pair listed twice, no overlapping
+ *   blocks. */
 int esmk_op_align_panel(void);
 int esmk_op_align_rows(const float* x_dev, int ldx, int N, const int32_t* rows_dev, int n, int cosine, int b_side, void* image_dev,
                        int ld_image, int E, void* stream);
@@ -1223,6 +1235,13 @@ int esmk_op_align_dp(const float* S_dev, int ldS, int n_rows, int n_cols, const 
 int esmk_op_align_traceback(const int64_t* table_dev, int n_pairs, int mode, const int32_t* end_dev, const uint8_t* tb_dev,
                             long long tb_bytes, const int64_t* slot_dev, int32_t* cols_dev, long long cols_cap, int32_t* n_cols_dev,
                             int32_t* n_match_dev, int32_t* start_dev, void* stream);
+int esmk_op_align_dp_ex(const float* S_dev, int ldS, int n_rows, int n_cols, const int64_t* table_dev, int n_pairs, int mode,
+                        int free_ends, float gap_open, float gap_extend, int max_la, int max_lb, float* score_dev, int32_t* end_dev,
+                        uint8_t* tb_dev, long long tb_bytes, int want_traceback, float* ws_dev, long long ws_floats, void* stream);
+int esmk_op_align_traceback_ex(const int64_t* table_dev, int n_pairs, int mode, int free_ends, const int32_t* end_dev,
+                               const uint8_t* tb_dev, long long tb_bytes, const int64_t* slot_dev, int32_t* cols_dev,
+                               long long cols_cap, int32_t* n_cols_dev, int32_t* n_match_dev, int32_t* start_dev, float* S_mask_dev,
+                               int ldS, int n_rows, int n_cols, void* stream);
 
 /* Protein search on pooled embeddings (csrc/search.hip; esm_amd/search.py): one vector per protein, a cosine top-k against a
  * database of such vectors, the aligner above on the survivors.  The similarities are esmk_op_linear (ESMK_EPI_STORE_F32) over

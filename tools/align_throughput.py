@@ -5,7 +5,7 @@ writes today: cosine similarity in torch on the device, the matrix to the host, 
 (scores only), one pair at a time.
 
   python tools/align_throughput.py [--queries 64] [--targets 256] [--embed-dim 1280] [--mode local] [--baseline-pairs 24]
-      [--rounds 5] [--out profiles/align_throughput.log]
+      [--rounds 5] [--free-ends b] [--hits-per-pair 3] [--baseline-lib OTHER/libesmk.so] [--out profiles/align_throughput.log]
 
 Lengths are drawn from the UniRef-like mix of tools/bench_varlen.py; the representations are random fp32 rows of ``--embed-dim``
 columns (1280: the 650M model) — the forward is not part of the measurement, the alignment is.  The host loop is far too slow
@@ -13,8 +13,16 @@ for all pairs: it is timed on the first ``--baseline-pairs`` pairs of a fixed sh
 engine (a cell is one (i, j) of a pair).  One warm-up of every side, then --rounds timed rounds alternating the sides in one
 process, each ending in a device synchronise; medians [min .. max].  The DP kernel's share is measured on the call's first
 block with device events: images + GEMM, DP, walk.  The two sides' scores are compared on the baseline pairs (torch's fp32
-similarity is rounded differently from the f16x3 GEMM: the largest difference is reported, not asserted)."""
+similarity is rounded differently from the f16x3 GEMM: the largest difference is reported, not asserted).
+
+``--free-ends`` (a, b, both) and ``--hits-per-pair K`` add sides of the same alternating rounds: global mode with that mask
+(scores only, with paths) and ``--mode`` with K hits per pair.  ``--baseline-lib`` names another build of libesmk.so (the parent
+commit's): local and global mode, scores only and with paths, are timed under it and under this library as further sides, the
+library swapped in around each of its calls; an older build has no ``_ex`` alignment entries, so those calls (always with
+free_ends = 0 and without a mask there) go to its plain entries."""
 import argparse
+import contextlib
+import ctypes
 import os
 import statistics
 import sys
@@ -31,6 +39,39 @@ from bench_varlen import uniref_like_lengths  # noqa: E402
 from esm_amd import _native as N  # noqa: E402
 from esm_amd import align as A  # noqa: E402
 from esm_amd import ops  # noqa: E402
+
+
+class BaselineLibrary:
+    """Another build of libesmk.so under the signatures of esm_amd/_native.py.  The two ``_ex`` alignment entries an older
+    build lacks are served by its plain entries: the calls made under it carry free_ends = 0 and no mask."""
+
+    def __init__(self, path):
+        self._lib = ctypes.CDLL(path)
+        for name, (res, argtypes) in N.SIGNATURES.items():
+            fn = getattr(self._lib, name, None)
+            if fn is not None:
+                fn.restype, fn.argtypes = res, argtypes
+
+    def __getattr__(self, name):
+        return getattr(self._lib, name)
+
+    def esmk_op_align_dp_ex(self, *a):
+        assert a[7] == 0
+        return self._lib.esmk_op_align_dp(*a[:7], *a[8:])
+
+    def esmk_op_align_traceback_ex(self, *a):
+        assert a[3] == 0 and not a[13].value
+        return self._lib.esmk_op_align_traceback(*a[:3], *a[4:13], a[17])
+
+
+@contextlib.contextmanager
+def library(lib):
+    """Every engine call inside goes to ``lib`` (esm_amd looks ``_native.lib`` up at call time)."""
+    mine, N.lib = N.lib, lib
+    try:
+        yield
+    finally:
+        N.lib = mine
 
 
 def numpy_dp_score(S, local, o, e):
@@ -122,6 +163,9 @@ def main():
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--max-bytes", type=int, default=4 << 30)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--free-ends", choices=("a", "b", "both"), default=None, help="a further side: global mode with this free-end mask")
+    p.add_argument("--hits-per-pair", type=int, default=1, help="a further side: --mode with K hits per pair")
+    p.add_argument("--baseline-lib", default=None, help="another build of libesmk.so: local and global mode under it are further sides")
     p.add_argument("--out", default=None)
     args = p.parse_args()
     if not torch.cuda.is_available():
@@ -144,6 +188,28 @@ def main():
         "host loop (sample)": (lambda: host_loop(reps_a, reps_b, sample, local, args.gap_open, args.gap_extend), sample_cells),
         "engine on the sample": (lambda: A.align_embeddings((flat_a, len_a), (flat_b, len_b), pairs=sample, paths=False, **kw), sample_cells),
     }
+    both = ((flat_a, len_a), (flat_b, len_b))
+    pen = dict(gap_open=args.gap_open, gap_extend=args.gap_extend, max_bytes=args.max_bytes)
+    if args.free_ends:
+        sides["free_ends=%s, scores only" % args.free_ends] = (lambda: A.align_embeddings(*both, mode="global", free_ends=args.free_ends, paths=False, **pen), cells)
+        sides["free_ends=%s, with paths" % args.free_ends] = (lambda: A.align_embeddings(*both, mode="global", free_ends=args.free_ends, **pen), cells)
+    if args.hits_per_pair > 1:
+        sides["%s, %d hits per pair" % (args.mode, args.hits_per_pair)] = (lambda: A.align_embeddings(*both, hits_per_pair=args.hits_per_pair, **kw), cells)
+    base = None
+    if args.baseline_lib:
+        base = BaselineLibrary(args.baseline_lib)
+
+        def under(lib, mode, paths):
+            def call():
+                with library(lib):
+                    return A.align_embeddings(*both, mode=mode, paths=paths, **pen)
+            return call
+
+        for mode in ("local", "global"):
+            for paths in (False, True):
+                what = "%s, %s" % (mode, "with paths" if paths else "scores only")
+                sides["parent library, " + what] = (under(base, mode, paths), cells)
+                sides["this library,   " + what] = (under(N.lib, mode, paths), cells)
     times = {name: [] for name in sides}
     for fn, _ in sides.values():
         fn()
@@ -156,9 +222,26 @@ def main():
              % (len(len_a), len(len_b), np.mean(len_a), np.mean(len_b), E, torch.cuda.get_device_name(0), args.mode, args.gap_open,
                 args.gap_extend, cells / 1e9, blocks, "" if blocks == 1 else "s", args.max_bytes, args.rounds), ""]
     for name, (_, c) in sides.items():
-        lines.append("    %-22s %s   (%d pairs)" % (name, fmt(times[name], c), len(sample) if "sample" in name else len(pairs)))
+        lines.append("    %-42s %s   (%d pairs)" % (name, fmt(times[name], c), len(sample) if "sample" in name else len(pairs)))
     ratio = (cells / statistics.median(times["engine, scores only"])) / (sample_cells / statistics.median(times["host loop (sample)"]))
     lines.append("    cells per second, engine (scores only, all pairs) over host loop (sample): %.0f x" % ratio)
+    if base is not None:
+        lines.append("    parent library: %s; this library: %s" % (base.esmk_version().decode(), N.lib.esmk_version().decode()))
+        for mode in ("local", "global"):
+            for what in ("scores only", "with paths"):
+                old, new = times["parent library, %s, %s" % (mode, what)], times["this library,   %s, %s" % (mode, what)]
+                m_old, m_new, spread = statistics.median(old), statistics.median(new), max(old) - min(old)
+                ok = min(old) <= m_new <= max(old) or m_new <= m_old + spread
+                lines.append("    %s, %s: this library's median %.2f ms against the parent's %.2f ms [%.2f .. %.2f]: %s" % (
+                    mode, what, 1e3 * m_new, 1e3 * m_old, 1e3 * min(old), 1e3 * max(old),
+                    "within the parent's rounds" if ok else "SLOWER than the parent's rounds"))
+            outs = [sides["%s %s, with paths" % (lib, mode)][0]() for lib in ("parent library,", "this library,  ")]
+            same = all(torch.equal(outs[0][k], outs[1][k]) for k in ("score", "end", "cols"))
+            lines.append("    %s: score, end and cols of the two libraries: %s" % (mode, "the same bits" if same else "DIFFERENT"))
+    if args.hits_per_pair > 1:
+        one = statistics.median(times["engine, with paths"])
+        k_hits = statistics.median(times["%s, %d hits per pair" % (args.mode, args.hits_per_pair)])
+        lines.append("    %d hits per pair cost %.2f x the call with one hit (both with paths; images and GEMM run once)" % (args.hits_per_pair, k_hits / one))
     ours = sides["engine on the sample"][0]()["score"].cpu().numpy()
     theirs = np.array(sides["host loop (sample)"][0](), dtype=np.float64)
     lines.append("    scores on the sample: largest difference %.3e (largest score %.3f)" % (np.abs(ours - theirs).max(), np.abs(theirs).max()))
